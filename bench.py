@@ -25,9 +25,17 @@ The (128 N) x 128 tensor is row-sharded (reference loops cpu_cryptosystem_tensor
 independent per row), no exchange between chained adds, ONE all-gather of the final result inside the timed region
 -- RCCL through the library's communicator, on the stream the kernels run on.
 
-Extra objects on the JSON line: "roofline" (algorithmic bytes of one launch of the dominant kernel / its HIP-event
-time vs 8 TB/s), "roofline_valu" (the bound that binds, from committed counter files) and "cpu_baseline" (the C++/GMP
-oracle restating the reference loop, timed on this box's host cores on a bounded sample, rank 0, N = 1 only).
+A plain run sets up, warms up, times the steps and prints the JSON line (metric, value, unit, ms_per_step, ...).
+`--full` adds the measurements that take runs of their own, as extra objects on the line: "roofline" (algorithmic bytes
+of one launch of the dominant kernel / its HIP-event time vs 8 TB/s), "roofline_valu" (the bound that binds, from
+committed counter files), "add_ciphertext_records" (the ciphertext-level entry on the same inputs), "input_family_ii"
+(independent random forms) and "cpu_baseline" (the C++/GMP oracle restating the reference loop, timed on this box's host
+cores on a bounded sample, rank 0, N = 1 only).
+
+`--dump-outputs DIR`: after the timed steps, rank 0 writes the ciphertext records the last step produced (the whole
+result, gathered over the ranks) as DIR/result_records.npy, float64 of the u32 record words, shape (n, 2, 168), and their
+positions in the row-major result as DIR/result_index.npy; above DUMP_MAX_CTS ciphertexts a fixed seeded sample.  The
+inputs depend on the arguments only, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import glob
@@ -44,6 +52,7 @@ sys.path.insert(0, ROOT)
 REC_WORDS = 168
 REC_BYTES = REC_WORDS * 4
 CT_BYTES = 2 * REC_BYTES
+DUMP_MAX_CTS = 16384          # 16 384 ciphertexts x 2 records x 168 words as float64 = 44 MB, under the 64 MB a dump may take
 
 
 def hx(s):
@@ -156,6 +165,19 @@ def random_forms_gpu(eng, prm, n, seed, bits=192):
     base.free()
     ex.free()
     return out
+
+
+def dump_outputs(out_dir, recs, n_cts):
+    """--dump-outputs: `recs` (the u32 words of n_cts ciphertexts) as DIR/result_records.npy in float64 (exact for u32),
+    with their positions as DIR/result_index.npy; above DUMP_MAX_CTS ciphertexts a sorted sample drawn with a fixed seed"""
+    import numpy as np
+    recs = np.asarray(recs, dtype=np.uint32).reshape(n_cts, 2, REC_WORDS)
+    idx = np.arange(n_cts)
+    if n_cts > DUMP_MAX_CTS:
+        idx = np.sort(np.random.default_rng(20240601).choice(n_cts, DUMP_MAX_CTS, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "result_records.npy"), recs[idx].astype(np.float64))
+    np.save(os.path.join(out_dir, "result_index.npy"), idx.astype(np.float64))
 
 
 # ------------------------------------------------------------------------------------------ counter files
@@ -508,40 +530,46 @@ def main_matadd(args):
     eng.device_status(clear=True)
     elapsed = timed_region(args.steps, args.warmup, step_chain, gather, fence, rdv)
     status = eng.device_status(clear=True)
+    if rank == 0 and args.dump_outputs:
+        # before anything below reuses bufs: the last step's result (the gathered whole with a communicator)
+        res = gathered if comm is not None else state["cur"]
+        dump_outputs(args.dump_outputs, res.host(), res.nbytes // CT_BYTES)
 
     # ---- roofline: HIP events around back-to-back launches of the dominant kernel ----------
     iters = max(5, min(args.steps, 20))
-    ms_launch = eng.time_compose(ct1.ptr, ct2.ptr, bufs[0].ptr, nrec, iters, stream)
-    # algorithmic bytes: S = payload bytes of one serialised ciphertext (no offset table),
-    # measured on the inputs and the output actually used; matadd moves 3 S per ciphertext-op
-    samp = min(E, 1024)
+    roofline = roofline_valu = None
+    if args.full:
+        ms_launch = eng.time_compose(ct1.ptr, ct2.ptr, bufs[0].ptr, nrec, iters, stream)
+        # algorithmic bytes: S = payload bytes of one serialised ciphertext (no offset table),
+        # measured on the inputs and the output actually used; matadd moves 3 S per ciphertext-op
+        samp = min(E, 1024)
 
-    def payload_per_ct(buf):
-        recs = buf.host(samp * CT_BYTES)
-        b = eng.records_to_bytes(recs, [samp])
-        return (len(b) - 4 - 4 - 48 * samp) / samp
+        def payload_per_ct(buf):
+            recs = buf.host(samp * CT_BYTES)
+            b = eng.records_to_bytes(recs, [samp])
+            return (len(b) - 4 - 4 - 48 * samp) / samp
 
-    S_in1, S_in2, S_out = payload_per_ct(ct1), payload_per_ct(ct2), payload_per_ct(bufs[0])
-    alg_bytes = (S_in1 + S_in2 + S_out) * E
-    achieved = alg_bytes / (ms_launch * 1e-3) / 1e9
-    # HBM-side bytes per launch: PMC counters (FETCH_SIZE, WRITE_SIZE, separate rocprofv3 passes) corrected
-    # with factors calibrated on a record-copy kernel of the same access pattern -- measured by
-    # tools/gpu_counters.sh and committed under profiles/ (a profiler cannot run inside this process)
-    tj, traffic_src = committed_counter_file("traffic.json", nrec, "traffic_bytes_per_launch")
-    traffic = int(tj["traffic_bytes_per_launch"]) if tj else None
-    roofline = {"bound": "hbm", "achieved": round(achieved, 3), "peak": 8000.0, "unit": "GB/s",
-                "frac": round(achieved / 8000.0, 6), "traffic": traffic, "traffic_source": traffic_src,
-                "kernel": "k_compose_wg", "launch_ms": round(ms_launch, 4),
-                "algorithmic_bytes_per_launch": int(alg_bytes), "kernel_code_hash": kernel_code_hash(),
-                "note": "class-group composition is integer-VALU bound (see DESIGN.md); HBM fraction is reported as the contract asks"}
-    vj, valu_src = committed_counter_file("valu.json", nrec, "valu_wave_insts_per_launch")
-    roofline_valu = valu_roofline(vj, valu_src, ms_launch, "k_compose_wg")
+        S_in1, S_in2, S_out = payload_per_ct(ct1), payload_per_ct(ct2), payload_per_ct(bufs[0])
+        alg_bytes = (S_in1 + S_in2 + S_out) * E
+        achieved = alg_bytes / (ms_launch * 1e-3) / 1e9
+        # HBM-side bytes per launch: PMC counters (FETCH_SIZE, WRITE_SIZE, separate rocprofv3 passes) corrected
+        # with factors calibrated on a record-copy kernel of the same access pattern -- measured by
+        # tools/gpu_counters.sh and committed under profiles/ (a profiler cannot run inside this process)
+        tj, traffic_src = committed_counter_file("traffic.json", nrec, "traffic_bytes_per_launch")
+        traffic = int(tj["traffic_bytes_per_launch"]) if tj else None
+        roofline = {"bound": "hbm", "achieved": round(achieved, 3), "peak": 8000.0, "unit": "GB/s",
+                    "frac": round(achieved / 8000.0, 6), "traffic": traffic, "traffic_source": traffic_src,
+                    "kernel": "k_compose_wg", "launch_ms": round(ms_launch, 4),
+                    "algorithmic_bytes_per_launch": int(alg_bytes), "kernel_code_hash": kernel_code_hash(),
+                    "note": "class-group composition is integer-VALU bound (see DESIGN.md); HBM fraction is reported as the contract asks"}
+        vj, valu_src = committed_counter_file("valu.json", nrec, "valu_wave_insts_per_launch")
+        roofline_valu = valu_roofline(vj, valu_src, ms_launch, "k_compose_wg")
 
     # ---- the ciphertext-level entry point on the same inputs (what add_ciphertext_tensors calls): the operands were made
     # by encrypt_tensor, one r per tensor as in the reference, so their c1 are shared and that composition is done once.
     # Reported beside the headline, which stays on the plain 2E-composition kernel.
     folded = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         fo = DBuf(eng, ct1.nbytes)
         eng.add_ciphertext_records(ct1.ptr, ct2.ptr, fo.ptr, E, stream)
         eng.compose_records(ct1.ptr, ct2.ptr, bufs[1].ptr, nrec, stream)
@@ -564,7 +592,7 @@ def main_matadd(args):
 
     # ---- input family (ii): independent random forms, same launch size ------------------------
     fam2 = None
-    if rank == 0 and world == 1 and not args.no_family2:
+    if rank == 0 and world == 1 and args.full and not args.no_family2:
         fa = random_forms_gpu(eng, prm, nrec, 4242)
         fb = random_forms_gpu(eng, prm, nrec, 4343)
         fo = DBuf(eng, fa.nbytes)
@@ -578,7 +606,7 @@ def main_matadd(args):
 
     # ---- CPU baseline (oracle = checker, timed on a bounded sample) -------------------------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib as O
         ns = min(E, 16384)
@@ -707,49 +735,53 @@ def main_scal_matmul(args):
     eng.device_status(clear=True)
     elapsed = timed_region(args.steps, max(1, args.warmup), step, lambda: None, lambda: eng.stream_sync(stream), rdv)
     status = eng.device_status(clear=True)
+    if rank == 0 and args.dump_outputs:
+        res = gathered if comm is not None else out
+        dump_outputs(args.dump_outputs, res.host(), res.nbytes // CT_BYTES)
 
     # ---- roofline of the dominant kernel: events around every kernel of the product on the launch stream
-    eng.set_option("profile_kernels", 1)
-    iters = max(1, min(args.steps, 3))
-    for _ in range(iters):
-        eng.scal_matmul_records(cts.ptr, ex.ptr, zero.ptr, out.ptr, n, m, p, stream)
-    eng.stream_sync(stream)
-    # per call: summed duration and launch count of every kernel of the product (the tree form launches k_tree_level once per
-    # level and row chunk); the dominant one carries the roofline object
-    kms, launches = {}, {}
-    for kn in ("k_tree_level", "k_scal_matmul_wnaf", "k_pow_table", "k_wnaf_digits"):
-        ms, cnt = eng.profile_read(kn)
-        kms[kn] = round(ms / iters, 4) if cnt else None
-        launches[kn] = cnt // iters if cnt else 0
-    eng.profile_read("k_wnaf_digits", clear=True)
-    eng.set_option("profile_kernels", 0)
-    samp = min(n * m, 1024)
-    S_in = (len(eng.records_to_bytes(cts.host(samp * CT_BYTES), [samp])) - 8 - 48 * samp) / samp
-    so = min(n * p, 1024)
-    S_out = (len(eng.records_to_bytes(out.host(so * CT_BYTES), [so])) - 8 - 48 * so) / so
-    expbits = max(exps).bit_length()
-    alg_bytes = n * m * S_in + n * p * S_out + m * p * ((expbits + 7) // 8)
     roofline = None
-    timed = {kk: v for kk, v in kms.items() if v}
-    if timed:
-        dom = max(timed, key=timed.get)
-        ach = alg_bytes / (timed[dom] * 1e-3) / 1e9
-        roofline = {"bound": "hbm", "achieved": round(ach, 4), "peak": 8000.0, "unit": "GB/s", "frac": round(ach / 8000.0, 8),
-                    "traffic": None, "kernel": dom, "launch_ms": timed[dom], "launches_per_call": launches[dom],
-                    "other_kernels_ms": {kk: v for kk, v in kms.items() if kk != dom},
-                    "algorithmic_bytes_per_launch": int(alg_bytes),
-                    "formula": "(n m + n p) S + m p ceil(expbits / 8), S = measured payload of a serialised ciphertext; launch_ms = the "
-                               "dominant kernel's launches of ONE product summed (HIP events inside the library)",
-                    "kernel_code_hash": kernel_code_hash(),
-                    "note": "integer-VALU bound: one output coefficient is ~bits squarings + m bits/(w+1) compositions"}
-        mj, msrc = committed_counter_file("valu_matmul.json", n * p * 2, "valu_wave_insts_per_launch")
-        if mj and mj.get("shape") == [n, m, p] and mj.get("kernel", "k_scal_matmul_wnaf") == dom:
-            roofline["valu"] = valu_roofline(mj, msrc, timed[dom], dom)
-            roofline["traffic"] = mj.get("traffic_bytes_per_launch")
+    if args.full:
+        eng.set_option("profile_kernels", 1)
+        iters = max(1, min(args.steps, 3))
+        for _ in range(iters):
+            eng.scal_matmul_records(cts.ptr, ex.ptr, zero.ptr, out.ptr, n, m, p, stream)
+        eng.stream_sync(stream)
+        # per call: summed duration and launch count of every kernel of the product (the tree form launches k_tree_level once per
+        # level and row chunk); the dominant one carries the roofline object
+        kms, launches = {}, {}
+        for kn in ("k_tree_level", "k_scal_matmul_wnaf", "k_pow_table", "k_wnaf_digits"):
+            ms, cnt = eng.profile_read(kn)
+            kms[kn] = round(ms / iters, 4) if cnt else None
+            launches[kn] = cnt // iters if cnt else 0
+        eng.profile_read("k_wnaf_digits", clear=True)
+        eng.set_option("profile_kernels", 0)
+        samp = min(n * m, 1024)
+        S_in = (len(eng.records_to_bytes(cts.host(samp * CT_BYTES), [samp])) - 8 - 48 * samp) / samp
+        so = min(n * p, 1024)
+        S_out = (len(eng.records_to_bytes(out.host(so * CT_BYTES), [so])) - 8 - 48 * so) / so
+        expbits = max(exps).bit_length()
+        alg_bytes = n * m * S_in + n * p * S_out + m * p * ((expbits + 7) // 8)
+        timed = {kk: v for kk, v in kms.items() if v}
+        if timed:
+            dom = max(timed, key=timed.get)
+            ach = alg_bytes / (timed[dom] * 1e-3) / 1e9
+            roofline = {"bound": "hbm", "achieved": round(ach, 4), "peak": 8000.0, "unit": "GB/s", "frac": round(ach / 8000.0, 8),
+                        "traffic": None, "kernel": dom, "launch_ms": timed[dom], "launches_per_call": launches[dom],
+                        "other_kernels_ms": {kk: v for kk, v in kms.items() if kk != dom},
+                        "algorithmic_bytes_per_launch": int(alg_bytes),
+                        "formula": "(n m + n p) S + m p ceil(expbits / 8), S = measured payload of a serialised ciphertext; launch_ms = the "
+                                   "dominant kernel's launches of ONE product summed (HIP events inside the library)",
+                        "kernel_code_hash": kernel_code_hash(),
+                        "note": "integer-VALU bound: one output coefficient is ~bits squarings + m bits/(w+1) compositions"}
+            mj, msrc = committed_counter_file("valu_matmul.json", n * p * 2, "valu_wave_insts_per_launch")
+            if mj and mj.get("shape") == [n, m, p] and mj.get("kernel", "k_scal_matmul_wnaf") == dom:
+                roofline["valu"] = valu_roofline(mj, msrc, timed[dom], dom)
+                roofline["traffic"] = mj.get("traffic_bytes_per_launch")
 
     # ---- CPU baseline: the oracle's scal_2d (reference loop structure, qfi.inl wNAF-7 tables) on a row sample
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib as O
         cores = host_cpu_share(O.max_threads())
@@ -821,6 +853,12 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rows", type=int, default=128)
     ap.add_argument("--cols", type=int, default=128)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own: roofline objects, the ciphertext-level "
+                         "entry, the second input family and the CPU baseline (off: those objects are null)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's result records as DIR/result_records.npy (float64) and "
+                         "their positions as DIR/result_index.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak (default, the driver's contract): every GPU holds its own rows x cols tensor.  strong: ONE rows x cols "
@@ -850,6 +888,8 @@ def main(argv=None):
     args = parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be positive")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be positive and --warmup not negative")
     launched = "WORLD_SIZE" in os.environ          # a launcher (torchrun, or this file's own parent) made us a rank
     if args.launch_dry_run:
         port = int(os.environ.get("MASTER_PORT", "0")) or free_port()

@@ -752,7 +752,7 @@ def test_c4_row_sharded_scal_matmul_through_rccl(params128, tmp_path):
     import subprocess
     env = dict(os.environ, COFHE_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29731", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "scal_matmul", "--rows", "256", "--cols", "256",
-                        "--steps", "1", "--warmup", "1", "--dump-dir", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+                        "--steps", "1", "--warmup", "1", "--full", "--dump-dir", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     meta = json.load(open(tmp_path / "meta.json"))

@@ -10,7 +10,7 @@ r=${sz%x*}; c=${sz#*x}
 for round in 1 2; do
 for f in $LIBS; do
   echo -n "== $sz round $round $f  "
-  timeout -k 10 300 python bench.py --lib $GRAFT_REPO_ROOT/$f --rows $r --cols $c --steps 20 --warmup 3 --no-cpu-baseline --no-family2 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['launch_ms'], d['device_status'])"
+  timeout -k 10 300 python bench.py --full --lib $PWD/$f --rows $r --cols $c --steps 20 --warmup 3 --no-cpu-baseline --no-family2 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['launch_ms'], d['device_status'])"
 done
 done
 done

@@ -8,6 +8,6 @@ for sz in $SIZES; do
 r=${sz%x*}; c=${sz#*x}
 for f in $LIBS; do
   echo -n "== $sz $f  "
-  timeout -k 10 300 python bench.py --lib $GRAFT_REPO_ROOT/$f --rows $r --cols $c --steps 20 --warmup 3 --no-cpu-baseline --no-family2 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('launch_ms', d['roofline']['launch_ms'], 'folded_ms', d['add_ciphertext_records']['ms_per_add'], d['device_status'])"
+  timeout -k 10 300 python bench.py --full --lib $PWD/$f --rows $r --cols $c --steps 20 --warmup 3 --no-cpu-baseline --no-family2 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('launch_ms', d['roofline']['launch_ms'], 'folded_ms', d['add_ciphertext_records']['ms_per_add'], d['device_status'])"
 done
 done
