@@ -628,11 +628,13 @@ __global__ void __launch_bounds__(WG_BLOCK, 3) k_pow_table3(const uint32_t *__re
 // of the segment with a non-zero digit) instead of by every chain in every round (until round 3 each round's scan for the
 // next non-zero digit was a chain of dependent byte loads in front of the table gather).
 //   word = kind << 29 | j << 8 | negative << 7 | (|digit| >> 1)
+// j has 21 bits: base index < 2^21 (the chains: j < m; the tree's Horner schedule: j = off_T[s] < N_T, see MM_INDEX_LIMIT)
 // word route for common factors (qf.hpp) in the matrix product: 248.2 vs 252.8 ms at 64 x 256 . 256 x 256, interleaved runs
 #ifndef COFHE_MATMUL_WORD_ROUTE
 #define COFHE_MATMUL_WORD_ROUTE true
 #endif
 constexpr uint32_t MM_END = 0, MM_SQUARE = 1, MM_MUL = 2, MM_FIRST = 3, MM_ZEROMUL = 4, MM_FIRSTZERO = 5, MM_FIRSTONE = 6;
+constexpr uint32_t MM_INDEX_LIMIT = 1u << 21;        // base indices of an op word: 0 .. 2^21 - 1
 #if PART_HAS(0)
 __global__ void k_matmul_schedule(const int8_t *__restrict__ digits, const uint32_t *__restrict__ maxlen, uint32_t m, uint32_t p,
                                   uint32_t segs, uint32_t rcap, uint32_t *__restrict__ ops, uint32_t *__restrict__ counts,
@@ -810,7 +812,9 @@ __global__ void __launch_bounds__(WG_BLOCK, 3) k_scal_matmul_wnaf3(const uint32_
 // The levels of a chunk of R rows live in two buffers used in turn, record index (i N_l + u) 2 + h -- row-major like a table,
 // so the top level T (every c_T <= 1) is read by the Horner kernel as a table with N_T one-entry bases per row.
 // ------------------------------------------------------------------------------------------
-constexpr int TREE_LEVELS = 22;              // m < 2^21 entries per segment
+// Levels: m < 2^21 entries per segment.  The top level's element index off_T[s] goes into the Horner op word's 21-bit base
+// index, so the tree is taken only while N_T <= 2^21 (cofhe_hip_scal_matmul_records; N_T reaches ~ len p, not m)
+constexpr int TREE_LEVELS = 22;
 #if PART_HAS(0)
 // cnt[s] = number of non-zero digits of column k at position t, s = t p + k < len p
 __global__ void k_tree_count(const int8_t *__restrict__ digits, const uint32_t *__restrict__ maxlen, uint32_t m, uint32_t p,
@@ -915,7 +919,7 @@ __global__ void k_tree_horner_schedule(const uint32_t *__restrict__ maxlen, uint
     const uint32_t *offT = off + (uint64_t)T * (S_cap + 1);
     uint32_t *o = ops + (uint64_t)k * rcap;
     uint32_t r = 0;
-    bool have = false;
+    bool have = false, big = false;
     for (int t = (int)*maxlen - 1; t >= 0; t--) {
         const uint32_t s = (uint32_t)t * p + k;
         if (have) {
@@ -923,15 +927,17 @@ __global__ void k_tree_horner_schedule(const uint32_t *__restrict__ maxlen, uint
             r++;
         }
         if (c[s] != 0) {
-            if (r < rcap) o[r] = ((have ? MM_MUL : MM_FIRST) << 29) | (offT[s] << 8);
+            if (r < rcap) o[r] = ((have ? MM_MUL : MM_FIRST) << 29) | ((offT[s] & (MM_INDEX_LIMIT - 1)) << 8);
             r++;
             have = true;
+            big = big || offT[s] >= MM_INDEX_LIMIT;
         }
     }
     if (r < rcap) o[r] = (have ? MM_ZEROMUL : MM_FIRSTZERO) << 29;
     r++;
     counts[k] = r < rcap ? r : rcap;
-    if (r > rcap) atomicOr(status, CF_ST_SCHEDULE_CAP);
+    // an index the op word cannot hold (the host does not take the tree then): the product would be wrong, so say so
+    if (r > rcap || big) atomicOr(status, CF_ST_SCHEDULE_CAP);
 }
 #else
 __global__ void k_tree_count(const int8_t *__restrict__ digits, const uint32_t *__restrict__ maxlen, uint32_t m, uint32_t p,
@@ -1613,13 +1619,14 @@ struct DevBuf {                  // from the context's block cache
         if (p) (void)cofhe_hip_free(ctx, p);
     }
 };
-// RAII span of the "profile_kernels" option: two events on the launch stream around one kernel launch
+// RAII span of the "profile_kernels" option: two events on the launch stream around one kernel launch.  Spans are named after
+// the kernel build actually launched, so that a test can tell which route a call took (cofhe_hip_profile_read's launch count)
 struct ProfScope {
     cofhe_hip_ctx *ctx;
     hipStream_t st;
     cofhe_hip_ctx::ProfSpan sp{nullptr, nullptr, nullptr};
     ProfScope(cofhe_hip_ctx *c, const char *name, hipStream_t s) : ctx(c), st(s) {
-        if (!c->opt_profile || c->prof.size() >= 65536) return;
+        if (!c->opt_profile || !name || c->prof.size() >= 65536) return;
         if (hipEventCreate(&sp.a) != hipSuccess) return;
         if (hipEventCreate(&sp.b) != hipSuccess) {
             (void)hipEventDestroy(sp.a);
@@ -1631,6 +1638,7 @@ struct ProfScope {
     ~ProfScope() {
         if (!sp.name) return;
         (void)hipEventRecord(sp.b, st);
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);       // some launchers (compose, add) run without the context lock
         ctx->prof.push_back(sp);
     }
 };
@@ -1798,12 +1806,15 @@ int cofhe_hip_compose_records(cofhe_hip_ctx *ctx, const void *d_a, const void *d
     unsigned blocks;
     if (int rc = compose_blocks(n, &blocks)) return rc;
     HIPCHK(hipSetDevice(ctx->device));
-    if (blocks <= 3u * NUM_CUS)      // the whole grid is resident at three workgroups per CU: the build with 168 registers per lane
+    if (blocks <= 3u * NUM_CUS) {    // the whole grid is resident at three workgroups per CU: the build with 168 registers per lane
+        ProfScope ps(ctx, "k_compose_wg3", (hipStream_t)stream);
         hipLaunchKernelGGL(k_compose_wg3, dim3(blocks), dim3(WG_BLOCK), 0, (hipStream_t)stream, (const uint32_t *)d_a,
                            (const uint32_t *)d_b, (uint32_t *)d_out, n, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
-    else
+    } else {
+        ProfScope ps(ctx, "k_compose_wg", (hipStream_t)stream);
         hipLaunchKernelGGL(k_compose_wg, dim3(blocks), dim3(WG_BLOCK), 0, (hipStream_t)stream, (const uint32_t *)d_a,
                            (const uint32_t *)d_b, (uint32_t *)d_out, n, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+    }
     HIPCHK(hipGetLastError());
     return COFHE_HIP_OK;
 }
@@ -1851,16 +1862,22 @@ int cofhe_hip_add_ciphertext_records(cofhe_hip_ctx *ctx, const void *d_a, const 
     unsigned blocks_shared;
     if (int rc = compose_blocks(n_ct + 1, &blocks_shared)) return rc;
     if (blocks <= 3u * NUM_CUS) {    // even with distinct c1 the whole grid is resident at three workgroups per CU
+        ProfScope ps(ctx, "k_add_ct3", st);
         hipLaunchKernelGGL(k_add_ct3, dim3(blocks), dim3(WG_BLOCK), 0, st, (const uint32_t *)d_a, (const uint32_t *)d_b, (uint32_t *)d_out,
                            n_ct, (const uint32_t *)flag, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status, 0u);
     } else if (blocks_shared <= 3u * NUM_CUS) {
         // only the folded case fits at three per CU, and the host does not know which case it is: a pair of launches, each
         // sized and built for its case; the one whose case it is not returns at once (128x128: 0.308 -> 0.29x ms folded)
-        hipLaunchKernelGGL(k_add_ct3, dim3(blocks_shared), dim3(WG_BLOCK), 0, st, (const uint32_t *)d_a, (const uint32_t *)d_b,
-                           (uint32_t *)d_out, n_ct, (const uint32_t *)flag, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status, 1u);
+        {
+            ProfScope ps(ctx, "k_add_ct3", st);
+            hipLaunchKernelGGL(k_add_ct3, dim3(blocks_shared), dim3(WG_BLOCK), 0, st, (const uint32_t *)d_a, (const uint32_t *)d_b,
+                               (uint32_t *)d_out, n_ct, (const uint32_t *)flag, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status, 1u);
+        }
+        ProfScope ps(ctx, "k_add_ct", st);
         hipLaunchKernelGGL(k_add_ct, dim3(blocks), dim3(WG_BLOCK), 0, st, (const uint32_t *)d_a, (const uint32_t *)d_b, (uint32_t *)d_out,
                            n_ct, (const uint32_t *)flag, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status, 2u);
     } else {
+        ProfScope ps(ctx, "k_add_ct", st);
         hipLaunchKernelGGL(k_add_ct, dim3(blocks), dim3(WG_BLOCK), 0, st, (const uint32_t *)d_a, (const uint32_t *)d_b, (uint32_t *)d_out,
                            n_ct, (const uint32_t *)flag, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status, 0u);
     }
@@ -2094,6 +2111,8 @@ int pow_shared(cofhe_hip_ctx *ctx, const void *d_base, uint32_t stride, const vo
     int form = ctx->opt_ladder_form ? ctx->opt_ladder_form : (n <= 256 ? 1 : 3);           // one ladder per CU at most: four per CU ran at half speed each
     if (form == 1 && n > POW_PAIR_MAX_LADDERS) form = 4;        // the pair's two workgroups must be resident together
     hipLaunchKernelGGL(k_wnaf_digits, dim3(1), dim3(64), 0, st, (const uint32_t *)d_exp, (uint64_t)1, form == 1 ? 2u : w, digits, maxlen);
+    ProfScope ps(ctx, form == 1 ? "k_pow_shared_pair" : form == 4 ? "k_pow_shared_wide" : (form == 2 && n <= 64 / G) ? "k_pow_shared_solo" : "k_pow_shared",
+                 st);
     if (form == 1)
         hipLaunchKernelGGL(k_pow_shared_pair, dim3((unsigned)(2 * n)), dim3(64), 0, st, (const uint32_t *)d_base, (const int8_t *)digits,
                            (const uint32_t *)maxlen, table, pairctl, (uint32_t *)d_out, n, stride, (const uint32_t *)ctx->d_one,
@@ -2137,6 +2156,7 @@ int pow_shared_c1(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_exp, void
     if (extra) *extra = ex;
     uint32_t *res = (uint32_t *)(d_out ? d_out : ex);
     const unsigned blocks = (unsigned)std::min<uint64_t>((n_ct * REC_WORDS + 255) / 256, 4096);
+    ProfScope ps(ctx, "k_spread_records", st);               // the witness of the shared route: one ladder, then this copy
     hipLaunchKernelGGL(k_spread_records, dim3(blocks), dim3(256), 0, st, res, n_ct);
     HIPCHK(hipGetLastError());
     return COFHE_HIP_OK;
@@ -2238,13 +2258,17 @@ int cofhe_hip_scal_matmul_records(cofhe_hip_ctx *ctx, const void *d_cts, const v
         // Long exponents make long trees (N_1 ~ p bits m / 2 (w + 1) elements per row): when fewer than 16 rows fit a chunk the
         // workgroups mix tree elements, copies ride along as dummy compositions, and the chains win again (32x256.256x256 with
         // 128-bit exponents: 0.83 s in 14-row chunks against 0.68 s; profiles/r04_a/tree_time_chunks.txt)
-        const bool tree_pays = R >= 16 || R == n || ctx->opt_matmul_tree == 1;
+        // The Horner chains address the top level's N_T elements through the op word's 21-bit base index (off_T[s] < N_T):
+        // beyond 2^21 elements the tree is not taken, "matmul_tree" = 1 included, and the chains below run instead
+        const bool tree_fits = info[T] <= MM_INDEX_LIMIT;
+        const bool tree_pays = tree_fits && (R >= 16 || R == n || ctx->opt_matmul_tree == 1);
         if (tree_pays) {
         const uint32_t *table = (const uint32_t *)d_cts;          // w == 2: the only table entry is the base itself
         if (tw > 1 && nbase) {
             unsigned tblocks;
             if (int rc = compose_blocks(nbase, &tblocks)) return rc;
             ProfScope ps(ctx, "k_pow_table", st);
+            ProfScope ps3(ctx, tblocks <= 3u * NUM_CUS ? "k_pow_table3" : nullptr, st);
             if ((tblocks) <= 3u * NUM_CUS)      // resident at three workgroups per CU: the 168-register build
                 hipLaunchKernelGGL(k_pow_table3, dim3(tblocks), dim3(WG_BLOCK), 0, st, (const uint32_t *)d_cts, (uint32_t *)(ws + tp.off("table")), nbase,
                                    tw, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
@@ -2289,6 +2313,7 @@ int cofhe_hip_scal_matmul_records(cofhe_hip_ctx *ctx, const void *d_cts, const v
             unsigned hb;
             if (int rc = compose_blocks((uint64_t)rows * p * 2, &hb)) return rc;
             ProfScope ps(ctx, "k_scal_matmul_wnaf", st);
+            ProfScope ps3(ctx, hb <= 3u * NUM_CUS ? "k_scal_matmul_wnaf3" : nullptr, st);
             if ((hb) <= 3u * NUM_CUS)      // resident at three workgroups per CU: the 168-register build
                 hipLaunchKernelGGL(k_scal_matmul_wnaf3, dim3(hb), dim3(WG_BLOCK), 0, st, (const uint32_t *)b_lvl[(T - 1) & 1].p, (const uint32_t *)b_ops.p,
                                    (const uint32_t *)b_cnt.p, rcap_h, (const uint32_t *)d_zero, (uint32_t *)d_out + (uint64_t)r0 * p * 2 * REC_WORDS,
@@ -2345,6 +2370,7 @@ int cofhe_hip_scal_matmul_records(cofhe_hip_ctx *ctx, const void *d_cts, const v
         unsigned tblocks;
         if (int rc = compose_blocks(nbase, &tblocks)) return rc;
         ProfScope ps(ctx, "k_pow_table", st);
+        ProfScope ps3(ctx, tblocks <= 3u * NUM_CUS ? "k_pow_table3" : nullptr, st);
         if ((tblocks) <= 3u * NUM_CUS)      // resident at three workgroups per CU: the 168-register build
             hipLaunchKernelGGL(k_pow_table3, dim3(tblocks), dim3(WG_BLOCK), 0, st, (const uint32_t *)d_cts, (uint32_t *)(ws + mp_.off("table")), nbase, tw,
                                (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
@@ -2357,6 +2383,7 @@ int cofhe_hip_scal_matmul_records(cofhe_hip_ctx *ctx, const void *d_cts, const v
     if (int rc = compose_blocks(out_forms * segs, &mblocks)) return rc;
     {
         ProfScope ps(ctx, "k_scal_matmul_wnaf", st);
+        ProfScope ps3(ctx, mblocks <= 3u * NUM_CUS ? "k_scal_matmul_wnaf3" : nullptr, st);
         if ((mblocks) <= 3u * NUM_CUS)      // resident at three workgroups per CU: the 168-register build
             hipLaunchKernelGGL(k_scal_matmul_wnaf3, dim3(mblocks), dim3(WG_BLOCK), 0, st, table, (const uint32_t *)ops,
                                (const uint32_t *)counts, rcap, (const uint32_t *)d_zero, segs > 1 ? partial : (uint32_t *)d_out, n, m, p, tw,
@@ -2419,6 +2446,7 @@ int cofhe_hip_decrypt_records(cofhe_hip_ctx *ctx, const void *d_cts, const void 
         return rc;
     unsigned blocks;
     if (int rc = compose_blocks(n_ct, &blocks)) return rc;
+    ProfScope ps(ctx, blocks <= 3u * NUM_CUS ? "k_decrypt3" : "k_decrypt", (hipStream_t)stream);
     if ((blocks) <= 3u * NUM_CUS)      // resident at three workgroups per CU: the 168-register build
         hipLaunchKernelGGL(k_decrypt3, dim3(blocks), dim3(WG_BLOCK), 0, (hipStream_t)stream, (const uint32_t *)d_cts,
                            (const uint32_t *)d_parts, 1u, (uint64_t)0, (const uint32_t *)ctx->d_ftab, (uint32_t *)d_out, n_ct,
@@ -2499,6 +2527,7 @@ int cofhe_hip_combine_part_decryptions_records(cofhe_hip_ctx *ctx, const void *d
     if (int rc = ensure_ftab(ctx, f_record, kbits, stream)) return rc;
     unsigned blocks;
     if (int rc = compose_blocks(n_ct, &blocks)) return rc;
+    ProfScope ps(ctx, blocks <= 3u * NUM_CUS ? "k_decrypt3" : "k_decrypt", (hipStream_t)stream);
     if ((blocks) <= 3u * NUM_CUS)      // resident at three workgroups per CU: the 168-register build
         hipLaunchKernelGGL(k_decrypt3, dim3(blocks), dim3(WG_BLOCK), 0, (hipStream_t)stream, (const uint32_t *)d_cts,
                            (const uint32_t *)d_parts, n_parts, negmask, (const uint32_t *)ctx->d_ftab, (uint32_t *)d_out, n_ct,

@@ -79,12 +79,19 @@ int cofhe_hip_trim(cofhe_hip_ctx *ctx, size_t keep_bytes);
  *   "ladder_form"      shared-exponent ladders (decryption): 0 by their number, 1 a pair of wavefronts per ladder (wide
  *                      layout: one squares, one multiplies), 2 the 8-lane in-wave form (<= 8 ladders), 3 the throughput
  *                      kernel, 4 one wavefront per ladder (wide layout, left to right with a table)
- *   "matmul_tree"      -1: the launcher decides; 1: the matrix product as per-position product trees + a Horner chain;
- *                      0: lockstep chains (the form of rounds 1-3)
+ *   "matmul_tree"      -1: the launcher decides; 1: the matrix product as per-position product trees + a Horner chain
+ *                      wherever its encoding allows (at most 2^21 non-empty (bit position, column) segments; beyond that the
+ *                      chains run); 0: lockstep chains (the form of rounds 1-3)
  *   "matmul_segments"  >= 1: pieces the inner dimension is cut into when the product has few outputs
  *   "profile_kernels"  != 0: cofhe_hip_scal_matmul_records brackets each of its kernels with HIP events on the launch
  *                      stream; cofhe_hip_profile_read(ctx, "k_tree_level" | "k_scal_matmul_wnaf" | "k_pow_table" | "k_wnaf_digits", ...)
- *                      waits for them and returns the summed duration and the launch count (clear != 0 drops all spans)
+ *                      waits for them and returns the summed duration and the launch count (clear != 0 drops all spans).
+ *                      The three-per-CU builds get a span of their own inside those ("k_scal_matmul_wnaf3", "k_pow_table3"),
+ *                      and the kernels of the other entry points one named after the build launched: "k_compose_wg3" |
+ *                      "k_compose_wg", "k_add_ct3" | "k_add_ct", "k_pow_shared_pair" | "k_pow_shared_wide" |
+ *                      "k_pow_shared_solo" | "k_pow_shared" (ladders; "k_spread_records" when a
+ *                      tensor's shared c1 ran one ladder), "k_decrypt3" | "k_decrypt" -- what a test reads to
+ *                      see which route a call took
  * The results do not depend on them; tests pin them to drive every width through the parity checker. */
 int cofhe_hip_ctx_set_option(cofhe_hip_ctx *ctx, const char *name, int64_t value);
 int cofhe_hip_profile_read(cofhe_hip_ctx *ctx, const char *kernel, float *total_ms, uint32_t *launches, int clear);

@@ -11,47 +11,9 @@ from conftest import ROOT, load_json
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import pyref as P  # noqa: E402
 from lopsided import lopsided_pool as _lopsided_pool  # noqa: E402
+from gpu_inputs import _device_status_stays_clear, _pt_bytes, _random_tensor, _records_of, engine, hx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
-
-
-def hx(s):
-    return -int(s[1:], 16) if s.startswith("-") else int(s, 16)
-
-
-_engines = {}
-
-
-def _pt_bytes(shape, vals):
-    import struct
-    offs, blobs, last = [], [], 0
-    for v in vals:
-        offs.append(last | ((1 << 63) if v <= 0 else 0))
-        w = max(abs(v).bit_length(), 1) // 8 + 1
-        blobs.append(abs(v).to_bytes(w, "little"))
-        last += w
-    out = struct.pack("<I", len(shape)) + b"".join(struct.pack("<I", d) for d in shape)
-    return out + b"".join(struct.pack("<Q", o) for o in offs) + b"".join(blobs)
-
-
-@pytest.fixture(autouse=True)
-def _device_status_stays_clear():
-    """after EVERY GPU test: no kernel of any context the test used hit a safety cap (lane.hpp: CF_ST_*).  The status
-    word is what caught round 2's wrong-discriminant bug; a parity test that passes with a cap bit set is not a pass."""
-    yield
-    for delta, E in list(_engines.items()):
-        assert E.device_status(clear=True) == 0, "device status word set on the context of |Delta| = %d bits" % (-delta).bit_length()
-
-
-def engine(delta):
-    # the PyTorch wheel bundles its own HIP runtime: when torch shares the process (the resident
-    # tensor tests below) it has to initialise the GPU before libcofhe_hip.so does
-    import torch
-    torch.cuda.init()
-    from cofhe_amd import Engine
-    if delta not in _engines:
-        _engines[delta] = Engine(delta)
-    return _engines[delta]
 
 
 def test_golden_add(golden):
@@ -78,17 +40,6 @@ def test_golden_scal_2d(golden):
     v = vec["scal_2d"]
     out = engine(d).scal_ciphertext_tensors(bytes.fromhex(v["s"]), bytes.fromhex(v["cts"]), bytes.fromhex(v["zero"]))
     assert out == bytes.fromhex(v["out"])
-
-
-def _random_tensor(d, n, seed, nbase=24):
-    rng = P.SplitMix64(seed)
-    base = [P.random_form(d, rng) for _ in range(nbase)]
-    cts = []
-    for i in range(n):
-        a = base[rng.below(nbase)]
-        b = base[rng.below(nbase)]
-        cts.append((a, b))
-    return cts
 
 
 def test_add_16x16_vs_oracle(params128):
@@ -652,12 +603,6 @@ def test_pow_fixed_base_equals_ladder(golden):
     torch.cuda.synchronize()
     assert torch.equal(got, want)
     assert E.device_status() == 0
-
-
-def _records_of(E, cts):
-    import numpy as np
-    _, recs = E.bytes_to_records(P.serialize_ciphertext_tensor([len(cts)], cts))
-    return recs.view(np.int32)
 
 
 def test_add_128x128_full_bytes_vs_oracle(params128):

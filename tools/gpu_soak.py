@@ -7,7 +7,7 @@ import torch
 torch.cuda.init()
 import pyref as P, oracle_lib as O
 from cofhe_amd import Engine
-from test_gpu_parity import _random_tensor, _pt_bytes, hx
+from gpu_inputs import _random_tensor, _pt_bytes, hx
 
 def one(d, k, seed):
     E = Engine(d)

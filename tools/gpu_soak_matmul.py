@@ -7,7 +7,7 @@ import torch
 torch.cuda.init()
 import pyref as P, oracle_lib as O
 from cofhe_amd import Engine
-from test_gpu_parity import _random_tensor, _pt_bytes, hx
+from gpu_inputs import _random_tensor, _pt_bytes, hx
 
 t0 = time.time()
 for name, shapes in (("s128_k128", [(16, 96, 24), (5, 200, 7), (40, 33, 40)]), ("s128_k256", [(8, 64, 16)])):
