@@ -1,0 +1,1543 @@
+// abi.hip -- the C ABI of include/cofhe_hip.h: the context, the block cache, the workspace plans, the kernel
+// launchers and the host-side tensor formats.  The kernels it launches are declared in kernels.hpp and defined in
+// cofhe_hip.hip and wide.hip; this file holds no device code of its own.
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/cofhe_hip.h"
+#include "ctx.hpp"
+#include "form_io.hpp"
+#include "kernels.hpp"
+
+using namespace cofhe;
+using namespace cofhe_k;
+
+namespace {
+
+// ---- little-endian byte strings <-> limb records (host) ------------------------------------
+struct IntView {
+    const uint8_t *p;
+    size_t n;
+    bool neg;
+};
+
+size_t sig_bytes(const uint8_t *p, size_t n) {
+    while (n > 0 && p[n - 1] == 0) n--;
+    return n;
+}
+
+int parse_tensor(const uint8_t *bytes, size_t len, size_t per_elem, uint32_t *ndim, uint32_t shape[8],
+                 std::vector<IntView> &ints) {
+    if (len < 4) return fail(COFHE_HIP_EINVAL, "tensor buffer too short");
+    uint32_t nd;
+    memcpy(&nd, bytes, 4);
+    if (nd > 8) return fail(COFHE_HIP_EINVAL, "tensor rank above 8");
+    if (len < 4 + 4ull * nd) return fail(COFHE_HIP_EINVAL, "tensor buffer too short");
+    uint64_t ne = 1;
+    for (uint32_t i = 0; i < nd; i++) {
+        memcpy(&shape[i], bytes + 4 + 4 * i, 4);
+        if (shape[i] != 0 && ne > (1ull << 40) / shape[i]) return fail(COFHE_HIP_EINVAL, "tensor too large");     // before the product can wrap
+        ne *= shape[i];
+    }
+    *ndim = nd;
+    const uint64_t cnt = ne * per_elem;
+    const size_t hdr = 4 + 4ull * nd + 8ull * cnt;
+    if (len < hdr) return fail(COFHE_HIP_EINVAL, "tensor buffer too short");
+    const uint8_t *tab = bytes + 4 + 4ull * nd;
+    const uint8_t *body = bytes + hdr;
+    const size_t blen = len - hdr;
+    ints.resize(cnt);
+    const uint64_t M = ~(1ull << 63);
+    for (uint64_t i = 0; i < cnt; i++) {
+        uint64_t o, o2;
+        memcpy(&o, tab + 8 * i, 8);
+        if (i + 1 < cnt) {
+            memcpy(&o2, tab + 8 * (i + 1), 8);
+            o2 &= M;
+        } else {
+            o2 = blen;
+        }
+        const uint64_t st = o & M;
+        if (o2 < st || o2 > blen) return fail(COFHE_HIP_EINVAL, "corrupt offset table");
+        ints[i] = IntView{body + st, (size_t)(o2 - st), (o >> 63) != 0};
+    }
+    return COFHE_HIP_OK;
+}
+
+bool put_limbs(uint32_t *dst, int words, const IntView &v) {
+    size_t n = sig_bytes(v.p, v.n);
+    if (n > (size_t)words * 4) return false;
+    memset(dst, 0, (size_t)words * 4);
+    memcpy(dst, v.p, n);     // little-endian host
+    return true;
+}
+
+size_t bits_of(const uint32_t *w, int words) {
+    for (int i = words - 1; i >= 0; i--)
+        if (w[i]) return (size_t)i * 32 + 32 - __builtin_clz(w[i]);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *cofhe_hip_last_error(void) { return g_err.c_str(); }
+int cofhe_hip_record_words(void) { return REC_WORDS; }
+int cofhe_hip_exp_words(void) { return EXP_MAG_WORDS; }
+void cofhe_hip_host_free(void *p) { free(p); }
+
+int cofhe_hip_ctx_create(int device, const uint8_t *absdelta_le, size_t len, cofhe_hip_ctx **out) {
+    if (!out || !absdelta_le) return fail(COFHE_HIP_EINVAL, "null argument");
+    int ndev = 0;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(COFHE_HIP_EHIP, "no such HIP device (the engine has no CPU fallback)");
+    HIPCHK(hipSetDevice(device));
+    size_t n = sig_bytes(absdelta_le, len);
+    if (n == 0 || n > 2 * PLIMBS * 4) return fail(COFHE_HIP_EINVAL, "discriminant out of range");
+    std::vector<uint32_t> dl(2 * PLIMBS + 1, 0);
+    memcpy(dl.data(), absdelta_le, n);
+    const int dbits = (int)bits_of(dl.data(), 2 * PLIMBS);
+    // capacity: reduced a, b < 2^(dbits/2) must leave headroom in one 1280-bit plane
+    if (dbits > 2400) return fail(COFHE_HIP_EINVAL, "discriminant above 2400 bits is not supported by the 40-limb planes");
+    const uint32_t mod4 = (4u - (dl[0] & 3u)) & 3u;     // Delta mod 4 from |Delta|
+    if (mod4 != 0 && mod4 != 1) return fail(COFHE_HIP_EINVAL, "Delta must be 0 or 1 mod 4");
+    // principal form (1, b0, (b0 - Delta)/4)
+    std::vector<uint32_t> one(REC_WORDS, 0);
+    one[REC_A] = 1;
+    one[REC_B] = mod4;
+    {   // c = (b0 + |Delta|) / 4
+        uint64_t carry = mod4;
+        std::vector<uint32_t> t(2 * PLIMBS + 1, 0);
+        for (int i = 0; i < 2 * PLIMBS + 1; i++) {
+            uint64_t s = (uint64_t)dl[i] + carry;
+            t[i] = (uint32_t)s;
+            carry = s >> 32;
+        }
+        for (int i = 0; i < 2 * PLIMBS; i++) one[REC_C + i] = (t[i] >> 2) | (t[i + 1] << 30);
+    }
+    cofhe_hip_ctx *c = new cofhe_hip_ctx();
+    c->device = device;
+    c->dbits = dbits;
+    c->half_dbits = (dbits + 1) / 2;
+    hipError_t e = hipMalloc((void **)&c->d_one, (REC_WORDS + 2 * PLIMBS + 4 + cofhe_hip_ctx::N_FLAGS) * 4);
+    if (e != hipSuccess) {
+        delete c;
+        return fail(COFHE_HIP_EHIP, std::string("hipMalloc: ") + hipGetErrorString(e));
+    }
+    c->d_absdelta = c->d_one + REC_WORDS;
+    c->d_status = c->d_absdelta + 2 * PLIMBS;
+    c->d_flags = c->d_status + 4;
+    e = hipMemset(c->d_status, 0, 16);
+    if (e == hipSuccess) e = hipMemcpy(c->d_absdelta, dl.data(), 2 * PLIMBS * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(c->d_one, one.data(), REC_WORDS * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        hipFree(c->d_one);
+        delete c;
+        return fail(COFHE_HIP_EHIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
+    }
+    {   // block cache limit: an eighth of the device memory, at most 64 GiB (cofhe_hip_trim changes it)
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b / 8 < c->pool_cap) c->pool_cap = total_b / 8;
+    }
+    *out = c;
+    return COFHE_HIP_OK;
+}
+
+static void pool_release_all(cofhe_hip_ctx *ctx);
+void cofhe_hip_ctx_destroy(cofhe_hip_ctx *ctx) {
+    if (!ctx) return;
+    hipSetDevice(ctx->device);
+    hipFree(ctx->d_one);
+    if (ctx->workspace) hipFree(ctx->workspace);
+    if (ctx->ws_event) (void)hipEventDestroy(ctx->ws_event);
+    if (ctx->d_ftab) hipFree(ctx->d_ftab);
+    for (auto &e : ctx->fb)
+        if (e.d_table) hipFree(e.d_table);
+    (void)hipDeviceSynchronize();
+    for (auto &sp : ctx->prof) {
+        (void)hipEventDestroy(sp.a);
+        (void)hipEventDestroy(sp.b);
+    }
+    pool_release_all(ctx);
+    delete ctx;
+}
+
+// Allocation goes through a per-context cache of freed blocks (exact rounded size): hipFree synchronises the whole
+// device and hipMalloc costs ~100 us, which dominated chains of small tensor operations.  A freed block carries an
+// event recorded on the null stream (ordered after everything submitted to it and to blocking streams); taking the
+// block out again waits for that event on the host, normally long past.
+static void pool_release_all(cofhe_hip_ctx *ctx) {
+    for (auto &kv : ctx->pool) {
+        (void)hipEventDestroy(kv.second.ev);
+        (void)hipFree(kv.second.p);
+    }
+    ctx->pool.clear();
+    ctx->pooled_bytes = 0;
+}
+// hipMalloc that gives the context's cached blocks back to the driver and retries when the device is out of memory:
+// the cache may hold up to pool_cap bytes that nobody is using
+static hipError_t dev_alloc(cofhe_hip_ctx *ctx, void **dptr, size_t bytes) {
+    hipError_t e = hipMalloc(dptr, bytes);
+    if (e == hipErrorOutOfMemory && !ctx->pool.empty()) {
+        (void)hipGetLastError();
+        (void)hipDeviceSynchronize();
+        pool_release_all(ctx);
+        e = hipMalloc(dptr, bytes);
+    }
+    return e;
+}
+int cofhe_hip_malloc(cofhe_hip_ctx *ctx, size_t bytes, void **dptr) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    // size classes: multiples of 512 B up to 4 KiB, above that eighths of the power of two below the request (at most
+    // 12.5 % slack), so that buffers of slightly different lengths (serialised tensors) share cached blocks
+    size_t sz = ((bytes ? bytes : 4) + 511) & ~(size_t)511;
+    if (sz > 4096) {
+        size_t p2 = (size_t)1 << (63 - __builtin_clzll((unsigned long long)sz));
+        const size_t step = p2 / 8;
+        sz = (sz + step - 1) / step * step;
+    }
+    auto it = ctx->pool.find(sz);
+    if (it != ctx->pool.end()) {
+        const cofhe_hip_ctx::Pooled b = it->second;
+        ctx->pool.erase(it);
+        ctx->pooled_bytes -= sz;
+        HIPCHK(hipEventSynchronize(b.ev));
+        (void)hipEventDestroy(b.ev);
+        *dptr = b.p;
+        ctx->live[b.p] = sz;
+        return COFHE_HIP_OK;
+    }
+    HIPCHK(dev_alloc(ctx, dptr, sz));
+    ctx->live[*dptr] = sz;
+    return COFHE_HIP_OK;
+}
+int cofhe_hip_free(cofhe_hip_ctx *ctx, void *dptr) { return cofhe_hip_free_on_stream(ctx, dptr, nullptr); }
+int cofhe_hip_free_on_stream(cofhe_hip_ctx *ctx, void *dptr, void *stream) {
+    if (!dptr) return COFHE_HIP_OK;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    auto it = ctx->live.find(dptr);
+    if (it == ctx->live.end()) {            // not one of ours
+        HIPCHK(hipFree(dptr));
+        return COFHE_HIP_OK;
+    }
+    const size_t sz = it->second;
+    ctx->live.erase(it);
+    if (ctx->pooled_bytes + sz > ctx->pool_cap) {
+        HIPCHK(hipFree(dptr));
+        return COFHE_HIP_OK;
+    }
+    cofhe_hip_ctx::Pooled b{dptr, nullptr};
+    HIPCHK(hipEventCreateWithFlags(&b.ev, hipEventDisableTiming));
+    // the event orders the block's reuse after the work already queued on `stream` (the stream the block was last used
+    // on; the null stream also covers every blocking stream)
+    HIPCHK(hipEventRecord(b.ev, (hipStream_t)stream));
+    ctx->pool.emplace(sz, b);
+    ctx->pooled_bytes += sz;
+    return COFHE_HIP_OK;
+}
+int cofhe_hip_ctx_set_option(cofhe_hip_ctx *ctx, const char *name, int64_t value) {
+    if (!ctx || !name) return fail(COFHE_HIP_EINVAL, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    const std::string n(name);
+    if (n == "wnaf_width") {
+        if (value != 0 && (value < 2 || value > 8)) return fail(COFHE_HIP_EINVAL, "wnaf_width: 0 (automatic) or 2..8");
+        ctx->opt_wnaf_width = (uint32_t)value;
+    } else if (n == "matmul_segments") {
+        if (value < 0 || value > (1 << 20)) return fail(COFHE_HIP_EINVAL, "matmul_segments: 0 (automatic) or a positive count");
+        ctx->opt_matmul_segments = (uint32_t)value;
+    } else if (n == "ladder_form") {
+        if (value < 0 || value > 4)
+            return fail(COFHE_HIP_EINVAL, "ladder_form: 0 (automatic), 1 (wide, two wavefronts), 2 (solo), 3 (throughput kernel), 4 (wide, one wavefront)");
+        ctx->opt_ladder_form = (int)value;
+    } else if (n == "matmul_tree") {
+        if (value < -1 || value > 1) return fail(COFHE_HIP_EINVAL, "matmul_tree: -1 (automatic), 0 (chains) or 1 (product tree)");
+        ctx->opt_matmul_tree = (int)value;
+    } else if (n == "profile_kernels") {
+        ctx->opt_profile = value != 0;
+    } else {
+        return fail(COFHE_HIP_EINVAL, "unknown option: " + n);
+    }
+    return COFHE_HIP_OK;
+}
+int cofhe_hip_profile_read(cofhe_hip_ctx *ctx, const char *kernel, float *total_ms, uint32_t *launches, int clear) {
+    if (!ctx || !kernel || !total_ms) return fail(COFHE_HIP_EINVAL, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    float sum = 0;
+    uint32_t cnt = 0;
+    for (auto &sp : ctx->prof) {
+        if (strcmp(sp.name, kernel) != 0) continue;
+        HIPCHK(hipEventSynchronize(sp.b));
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, sp.a, sp.b));
+        sum += ms;
+        cnt++;
+    }
+    *total_ms = sum;
+    if (launches) *launches = cnt;
+    if (clear) {
+        for (auto &sp : ctx->prof) {
+            (void)hipEventDestroy(sp.a);
+            (void)hipEventDestroy(sp.b);
+        }
+        ctx->prof.clear();
+    }
+    return COFHE_HIP_OK;
+}
+int cofhe_hip_trim(cofhe_hip_ctx *ctx, size_t keep_bytes) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    ctx->pool_cap = keep_bytes;
+    if (ctx->pooled_bytes > keep_bytes) {
+        HIPCHK(hipDeviceSynchronize());
+        pool_release_all(ctx);
+    }
+    return COFHE_HIP_OK;
+}
+int cofhe_hip_upload(cofhe_hip_ctx *ctx, void *dst, const void *src, size_t bytes, void *stream) {
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
+    return COFHE_HIP_OK;
+}
+int cofhe_hip_download(cofhe_hip_ctx *ctx, void *dst, const void *src, size_t bytes, void *stream) {
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return COFHE_HIP_OK;
+}
+int cofhe_hip_stream_sync(cofhe_hip_ctx *ctx, void *stream) {
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return COFHE_HIP_OK;
+}
+
+
+int cofhe_hip_device_status(cofhe_hip_ctx *ctx, uint32_t *word, int clear, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (!word) return fail(COFHE_HIP_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipMemcpyAsync(word, ctx->d_status, 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    if (clear) HIPCHK(hipMemsetAsync(ctx->d_status, 0, 4, (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return COFHE_HIP_OK;
+}
+
+int cofhe_hip_validate_records(cofhe_hip_ctx *ctx, const void *d_records, uint64_t n_records, int *all_valid, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (!all_valid) return fail(COFHE_HIP_EINVAL, "null argument");
+    *all_valid = 1;
+    if (n_records == 0) return COFHE_HIP_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    unsigned blocks;
+    {
+        const uint64_t b = (n_records + WG_GROUPS - 1) / WG_GROUPS;
+        if (b > 0x7FFFFFFFull) return fail(COFHE_HIP_EINVAL, "work size out of range");
+        blocks = (unsigned)b;
+    }
+    uint32_t *d_err = ctx->d_status + 1;              // second word of the status area: validation verdict
+    HIPCHK(hipMemsetAsync(d_err, 0, 4, (hipStream_t)stream));
+    hipLaunchKernelGGL(k_validate_forms, dim3(blocks), dim3(WG_BLOCK), 0, (hipStream_t)stream, (const uint32_t *)d_records, n_records,
+                       (const uint32_t *)ctx->d_absdelta, d_err);
+    HIPCHK(hipGetLastError());
+    uint32_t e = 0;
+    HIPCHK(hipMemcpyAsync(&e, d_err, 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    *all_valid = e == 0 ? 1 : 0;
+    return COFHE_HIP_OK;
+}
+
+namespace {
+struct DevBuf {                  // from the context's block cache
+    cofhe_hip_ctx *ctx = nullptr;
+    void *p = nullptr;
+    int get(cofhe_hip_ctx *c, size_t bytes) {
+        ctx = c;
+        return cofhe_hip_malloc(c, bytes, &p);
+    }
+    ~DevBuf() {
+        if (p) (void)cofhe_hip_free(ctx, p);
+    }
+};
+// RAII span of the "profile_kernels" option: two events on the launch stream around one kernel launch.  Spans are named after
+// the kernel build actually launched, so that a test can tell which route a call took (cofhe_hip_profile_read's launch count)
+struct ProfScope {
+    cofhe_hip_ctx *ctx;
+    hipStream_t st;
+    cofhe_hip_ctx::ProfSpan sp{nullptr, nullptr, nullptr};
+    ProfScope(cofhe_hip_ctx *c, const char *name, hipStream_t s) : ctx(c), st(s) {
+        if (!c->opt_profile || !name || c->prof.size() >= 65536) return;
+        if (hipEventCreate(&sp.a) != hipSuccess) return;
+        if (hipEventCreate(&sp.b) != hipSuccess) {
+            (void)hipEventDestroy(sp.a);
+            return;
+        }
+        sp.name = name;
+        (void)hipEventRecord(sp.a, st);
+    }
+    ~ProfScope() {
+        if (!sp.name) return;
+        (void)hipEventRecord(sp.b, st);
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);       // some launchers (compose, add) run without the context lock
+        ctx->prof.push_back(sp);
+    }
+};
+// The kernels with two builds (cofhe_hip.hip: k_compose_wg and k_compose_wg3, and their kin): the three-per-CU build (168
+// registers per lane, fewer spills) whenever the whole grid is resident at three workgroups per CU, the plain build, which
+// leaves room for four, otherwise
+bool fits_three_per_cu(unsigned blocks) { return blocks <= 3u * NUM_CUS; }
+// launches the build that fits a grid of `blocks` workgroups, in a "profile_kernels" span named span3 or span (null: none)
+extern "C++" template <typename... P, typename... A>
+void launch_wg(cofhe_hip_ctx *ctx, void (*k3)(P...), void (*k)(P...), const char *span3, const char *span, unsigned blocks,
+               hipStream_t st, A... args) {
+    const bool three = fits_three_per_cu(blocks);
+    ProfScope ps(ctx, three ? span3 : span, st);
+    hipLaunchKernelGGL(three ? k3 : k, dim3(blocks), dim3(WG_BLOCK), 0, st, args...);
+}
+int compose_blocks(uint64_t n, unsigned *blocks) {
+    uint64_t b = (n + WG_GROUPS - 1) / WG_GROUPS;
+    if (b == 0 || b > 0x7FFFFFFFull) return fail(COFHE_HIP_EINVAL, "work size out of range");
+    *blocks = (unsigned)b;
+    return COFHE_HIP_OK;
+}
+
+// ---- how the entry points carve the context's workspace ------------------------------------------------------------------
+// Every launcher that uses the workspace takes its regions from ONE of the plan functions below, and
+// cofhe_hip_workspace_plan hands the same plans out (host only, no GPU), so that a CPU test can check sizes and offsets --
+// disjoint, ordered, each at least what its kernel indexes -- for any operand count without running anything.
+extern "C++" {
+struct WsPlan {
+    static constexpr int MAX = 8;
+    cofhe_hip_ws_region r[MAX];
+    int n = 0;
+    size_t total = 0;
+    size_t add(const char *name, size_t bytes) {            // regions start on 256-byte boundaries
+        const size_t off = (total + 255) & ~(size_t)255;
+        if (n < MAX) {
+            memset(&r[n], 0, sizeof(r[n]));
+            strncpy(r[n].name, name, sizeof(r[n].name) - 1);
+            r[n].offset = off;
+            r[n].bytes = bytes;
+            n++;
+        }
+        total = off + bytes;
+        return off;
+    }
+    size_t off(const char *name) const {
+        for (int i = 0; i < n; i++)
+            if (strcmp(r[i].name, name) == 0) return (size_t)r[i].offset;
+        return (size_t)-1;
+    }
+    size_t bytes(const char *name) const {
+        for (int i = 0; i < n; i++)
+            if (strcmp(r[i].name, name) == 0) return (size_t)r[i].bytes;
+        return 0;
+    }
+};
+constexpr uint32_t POW_SHARED_W = 6, POW_SHARED_TW = 1u << (POW_SHARED_W - 2);      // 16 odd powers per base: 10.5 KB
+constexpr uint32_t POW_PAIR_MAX_LADDERS = 256;       // k_pow_shared_pair: two single-wavefront workgroups per ladder, all resident
+// k_pow_shared over n_ladders bases: [front: the caller's records][table: (tw + 2) slots for every group of the GRID -- idle
+// groups own slots too][digits of the one exponent][its length]
+inline WsPlan plan_pow_shared(uint64_t n_ladders, size_t front_bytes) {
+    WsPlan p;
+    const uint64_t blocks = (n_ladders + WG_GROUPS - 1) / WG_GROUPS;
+    p.add("front", front_bytes);
+    p.add("table", (size_t)blocks * WG_GROUPS * (POW_SHARED_TW + 2) * REC_WORDS * 4);
+    p.add("digits", (size_t)WNAF_POSITIONS);
+    p.add("maxlen", 256);
+    p.add("pairctl", (size_t)POW_PAIR_MAX_LADDERS * 16);       // k_pow_shared_pair: published / taken counts per ladder (zeroed with the digits)
+    return p;
+}
+inline size_t accumulate_tree_bytes(uint32_t n, uint32_t m, uint32_t p) {
+    return 2 * ((size_t)n * ((m + 1) / 2) * 2 * p * REC_WORDS * 4);
+}
+// the matrix product: [tables (tw > 1)][digits: WNAF_POSITIONS x m p bytes][maxlen][schedules: rcap words per column]
+// [schedule lengths][partial products and their tree (segs > 1)]
+inline uint32_t matmul_rcap(uint32_t exp_bits, uint32_t m, uint32_t segs) {
+    const uint32_t seglen = (m + segs - 1) / segs;
+    return (exp_bits + 2) * (seglen + 1) + 2;               // per position: a squaring and at most seglen products
+}
+inline WsPlan plan_scal_matmul(uint32_t n, uint32_t m, uint32_t p, uint32_t exp_bits, uint32_t w, uint32_t segs) {
+    WsPlan q;
+    const uint64_t nbase = (uint64_t)n * m * 2, n_exps = (uint64_t)m * p;
+    const uint32_t tw = 1u << (w - 2);
+    const uint32_t ncols = segs * p;
+    q.add("table", tw > 1 ? (size_t)nbase * tw * REC_WORDS * 4 : 0);
+    q.add("digits", (size_t)WNAF_POSITIONS * n_exps);
+    q.add("maxlen", 256);
+    q.add("ops", (size_t)ncols * matmul_rcap(exp_bits, m, segs) * 4);
+    q.add("counts", (size_t)ncols * 4);
+    q.add("partial", segs > 1 ? (size_t)n * segs * p * 2 * REC_WORDS * 4 : 0);
+    q.add("tree", segs > 1 ? accumulate_tree_bytes(n, segs, p) : 0);
+    return q;
+}
+// the product-tree form of the matrix product, what lives in the workspace: tables, digits, their length, and the per-level
+// segment counts / offsets / totals of k_tree_plan (S_cap = (exp_bits + 2) p segments at most).  Entry lists, maps, the Horner
+// schedule and the two level buffers are sized by the totals read back from `info` and come from the block cache.
+inline WsPlan plan_scal_matmul_tree(uint32_t n, uint32_t m, uint32_t p, uint32_t exp_bits, uint32_t w) {
+    WsPlan q;
+    const uint64_t nbase = (uint64_t)n * m * 2, n_exps = (uint64_t)m * p;
+    const uint32_t tw = 1u << (w - 2);
+    const size_t S_cap = (size_t)(exp_bits + 2) * p;
+    q.add("table", tw > 1 ? (size_t)nbase * tw * REC_WORDS * 4 : 0);
+    q.add("digits", (size_t)WNAF_POSITIONS * n_exps);
+    q.add("maxlen", 256);
+    q.add("counts", (size_t)(TREE_LEVELS + 1) * S_cap * 4);
+    q.add("offsets", (size_t)(TREE_LEVELS + 1) * (S_cap + 1) * 4);
+    q.add("info", 256);
+    return q;
+}
+inline WsPlan plan_accumulate_tree(uint32_t n, uint32_t m, uint32_t p) {
+    WsPlan q;
+    const size_t half = accumulate_tree_bytes(n, m, p) / 2;
+    q.add("level_a", half);
+    q.add("level_b", half);
+    return q;
+}
+// one chunk of encrypt_tensor: [table pointers + slot counter][entry indices: cap x ne][level: cap x ne records]
+// [next level: ceil(cap / 2) x ne records]
+inline WsPlan plan_encrypt_chunk(uint64_t ne, uint32_t kbits) {
+    WsPlan q;
+    const uint32_t cap = kbits / 2 + 3;                      // pk^r + at most ceil((k + 1) / 2) digits
+    q.add("header", 256);
+    q.add("idx", (size_t)cap * ne * 4);
+    q.add("level_a", (size_t)cap * ne * REC_WORDS * 4);
+    q.add("level_b", ((size_t)(cap + 1) / 2) * ne * REC_WORDS * 4);
+    return q;
+}
+// n fixed-base powers of at most mmax table entries each: two tree levels and the gather list (n pointers + n mmax indices)
+inline WsPlan plan_fixed_base(uint32_t n, uint32_t mmax) {
+    WsPlan q;
+    const size_t half = (size_t)n * mmax * REC_WORDS * 4;
+    q.add("level_a", half);
+    q.add("level_b", half);
+    q.add("gather", ((size_t)n + ((size_t)n * mmax + 1) / 2) * 8);
+    return q;
+}
+}  // extern "C++"
+
+// One user of the workspace at a time, on the device as well: the host lock (ctx->mu) only covers the enqueueing, the
+// kernels run on after the entry point has returned.  A call on another stream first waits for the event the previous
+// user recorded behind its last launch (calls on the same stream are ordered anyway); constructed under ctx->mu, before
+// ensure_workspace, so that a reallocation's stream synchronisation covers the previous user too.
+struct WsUse {
+    cofhe_hip_ctx *ctx;
+    hipStream_t st;
+    WsUse(cofhe_hip_ctx *c, hipStream_t s) : ctx(c), st(s) {
+        if (ctx->ws_event_set && ctx->ws_stream != st) (void)hipStreamWaitEvent(st, ctx->ws_event, 0);
+    }
+    ~WsUse() {
+        if (!ctx->ws_event && hipEventCreateWithFlags(&ctx->ws_event, hipEventDisableTiming) != hipSuccess) {
+            ctx->ws_event = nullptr;
+            (void)hipStreamSynchronize(st);                    // no event to hand over: finish before anybody else starts
+            ctx->ws_event_set = false;
+            return;
+        }
+        ctx->ws_event_set = hipEventRecord(ctx->ws_event, st) == hipSuccess;
+        ctx->ws_stream = st;
+        if (!ctx->ws_event_set) (void)hipStreamSynchronize(st);
+    }
+};
+
+// grow-only workspace of the context (tables, digit arrays, intermediate records)
+int ensure_workspace(cofhe_hip_ctx *ctx, size_t need, hipStream_t st) {
+    if (ctx->workspace_bytes >= need) return COFHE_HIP_OK;
+    HIPCHK(hipStreamSynchronize(st));
+    if (ctx->workspace) HIPCHK(hipFree(ctx->workspace));
+    ctx->workspace = nullptr;
+    ctx->workspace_bytes = 0;
+    HIPCHK(dev_alloc(ctx, &ctx->workspace, need));
+    ctx->workspace_bytes = need;
+    return COFHE_HIP_OK;
+}
+}  // namespace
+
+int cofhe_hip_compose_records(cofhe_hip_ctx *ctx, const void *d_a, const void *d_b, void *d_out, uint64_t n,
+                              void *stream) {
+    if (n == 0) return COFHE_HIP_OK;
+    unsigned blocks;
+    if (int rc = compose_blocks(n, &blocks)) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    launch_wg(ctx, k_compose_wg3, k_compose_wg, "k_compose_wg3", "k_compose_wg", blocks, (hipStream_t)stream, (const uint32_t *)d_a,
+              (const uint32_t *)d_b, (uint32_t *)d_out, n, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+
+int cofhe_hip_compose_wide_records(cofhe_hip_ctx *ctx, const void *d_a, const void *d_b, void *d_out, uint64_t n, uint32_t reps,
+                                   uint32_t *fallbacks, void *stream) {
+    if (n == 0) return COFHE_HIP_OK;
+    if (n > 0x7FFFFFFFull) return fail(COFHE_HIP_EINVAL, "work size out of range");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    uint32_t *d_fb = nullptr;
+    if (fallbacks) {
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        d_fb = ctx->d_flags + (ctx->flag_next++ % cofhe_hip_ctx::N_FLAGS);
+        HIPCHK(hipMemsetAsync(d_fb, 0, 4, st));
+    }
+    hipLaunchKernelGGL(k_compose_wide, dim3((unsigned)n), dim3(64), 0, st, (const uint32_t *)d_a, (const uint32_t *)d_b, (uint32_t *)d_out, n,
+                       reps, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status, d_fb);
+    HIPCHK(hipGetLastError());
+    if (fallbacks) {
+        HIPCHK(hipMemcpyAsync(fallbacks, d_fb, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    return COFHE_HIP_OK;
+}
+
+int cofhe_hip_add_ciphertext_records(cofhe_hip_ctx *ctx, const void *d_a, const void *d_b, void *d_out, uint64_t n_ct, void *stream) {
+    if (n_ct == 0) return COFHE_HIP_OK;
+    if (n_ct > (1ull << 40)) return fail(COFHE_HIP_EINVAL, "tensor too large");
+    unsigned blocks;
+    if (int rc = compose_blocks(n_ct * 2, &blocks)) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    uint32_t *flag;
+    {
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);        // the flag words are handed out round robin
+        flag = ctx->d_flags + (ctx->flag_next++ % cofhe_hip_ctx::N_FLAGS);
+    }
+    HIPCHK(hipMemsetAsync(flag, 0, 4, st));
+    const unsigned scan_blocks = (unsigned)std::min<uint64_t>((n_ct * REC_WORDS + 255) / 256, 2048);
+    if (n_ct > 1)
+        hipLaunchKernelGGL(k_c1_distinct, dim3(scan_blocks), dim3(256), 0, st, (const uint32_t *)d_a, (const uint32_t *)d_b, n_ct, flag);
+    else
+        HIPCHK(hipMemsetAsync(flag, 1, 1, st));                   // one ciphertext: nothing to fold
+    unsigned blocks_shared;
+    if (int rc = compose_blocks(n_ct + 1, &blocks_shared)) return rc;
+    const auto add = [&](unsigned grid, uint32_t only) {
+        launch_wg(ctx, k_add_ct3, k_add_ct, "k_add_ct3", "k_add_ct", grid, st, (const uint32_t *)d_a, (const uint32_t *)d_b, (uint32_t *)d_out,
+                  n_ct, (const uint32_t *)flag, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status, only);
+    };
+    if (!fits_three_per_cu(blocks) && fits_three_per_cu(blocks_shared)) {
+        // only the folded case fits at three per CU, and the host does not know which case it is: a pair of launches, each
+        // sized and built for its case; the one whose case it is not returns at once (128x128: 0.308 -> 0.29x ms folded)
+        add(blocks_shared, 1u);
+        add(blocks, 2u);
+    } else {
+        add(blocks, 0u);     // even with distinct c1, a grid that fits is resident at three workgroups per CU
+    }
+    if (n_ct > 1) hipLaunchKernelGGL(k_c1_spread, dim3(scan_blocks), dim3(256), 0, st, (uint32_t *)d_out, n_ct, (const uint32_t *)flag);
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+
+namespace {
+// k_pow keeps the running power in the output record: an output that overlaps the bases (in-place use) gets the bases
+// copied to the workspace first
+int pow_launch(cofhe_hip_ctx *ctx, const void *d_base, const void *d_exp, void *d_out, uint64_t n_records, uint32_t exp_mode, void *stream) {
+    unsigned blocks;
+    if (int rc = compose_blocks(n_records, &blocks)) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t bytes = (size_t)n_records * REC_WORDS * 4;
+    const uint8_t *b0 = (const uint8_t *)d_base, *o0 = (const uint8_t *)d_out;
+    if (b0 < o0 + bytes && o0 < b0 + bytes) {
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);    // the workspace belongs to one call at a time ...
+        WsUse use(ctx, st);                                    // ... until its kernel has finished (k_pow reads the copy)
+        if (int rc = ensure_workspace(ctx, bytes, st)) return rc;
+        HIPCHK(hipMemcpyAsync(ctx->workspace, d_base, bytes, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(k_pow, dim3(blocks), dim3(WG_BLOCK), 0, st, (const uint32_t *)ctx->workspace, (const uint32_t *)d_exp,
+                           (uint32_t *)d_out, n_records, 1u, exp_mode, (const uint32_t *)ctx->d_one,
+                           (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+        HIPCHK(hipGetLastError());
+        return COFHE_HIP_OK;
+    }
+    hipLaunchKernelGGL(k_pow, dim3(blocks), dim3(WG_BLOCK), 0, st, (const uint32_t *)d_base, (const uint32_t *)d_exp,
+                       (uint32_t *)d_out, n_records, 1u, exp_mode, (const uint32_t *)ctx->d_one,
+                       (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+}  // namespace
+
+int cofhe_hip_pow_records(cofhe_hip_ctx *ctx, const void *d_base, const void *d_exp, void *d_out, uint64_t n_ct,
+                          void *stream) {
+    if (n_ct == 0) return COFHE_HIP_OK;
+    return pow_launch(ctx, d_base, d_exp, d_out, n_ct * 2, 0u, stream);
+}
+
+namespace {
+// tree_scratch: accumulate_tree_bytes() of device memory for the tree path, or nullptr to take it from the
+// context workspace
+int accumulate_impl(cofhe_hip_ctx *ctx, const void *d_x, const void *d_zero, void *d_out, uint32_t n, uint32_t m,
+                    uint32_t p, void *tree_scratch, void *stream);
+}  // namespace
+
+int cofhe_hip_accumulate_records(cofhe_hip_ctx *ctx, const void *d_x, const void *d_zero, void *d_out, uint32_t n,
+                                 uint32_t m, uint32_t p, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    WsUse use(ctx, (hipStream_t)stream);
+    return accumulate_impl(ctx, d_x, d_zero, d_out, n, m, p, nullptr, stream);
+}
+
+namespace {
+int accumulate_impl(cofhe_hip_ctx *ctx, const void *d_x, const void *d_zero, void *d_out, uint32_t n, uint32_t m,
+                    uint32_t p, void *tree_scratch, void *stream) {
+    const uint64_t total = (uint64_t)n * p * 2;
+    if (total == 0) return COFHE_HIP_OK;
+    unsigned blocks;
+    if (int rc = compose_blocks(total, &blocks)) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (total < 16384 && m >= 4) {
+        // too few outputs to fill 256 CUs with chains of m compositions: pairwise product tree, ceil(log2 m)
+        // launches over [n][m'][2p] slices in two ping-pong buffers, then the composition with Enc(0)
+        hipStream_t st = (hipStream_t)stream;
+        const uint32_t q = 2 * p;
+        const WsPlan tp = plan_accumulate_tree(n, m, p);
+        if (!tree_scratch) {
+            if (int rc = ensure_workspace(ctx, tp.total, st)) return rc;
+            tree_scratch = ctx->workspace;
+        }
+        uint32_t *buf[2] = {(uint32_t *)((uint8_t *)tree_scratch + tp.off("level_a")), (uint32_t *)((uint8_t *)tree_scratch + tp.off("level_b"))};
+        const uint32_t *src = (const uint32_t *)d_x;
+        uint32_t mm = m;
+        int which = 0;
+        while (mm > 1) {
+            const uint32_t mh = (mm + 1) / 2;
+            unsigned b2;
+            if (int rc = compose_blocks((uint64_t)n * mh * q, &b2)) return rc;
+            hipLaunchKernelGGL(k_compose_pairs, dim3(b2), dim3(WG_BLOCK), 0, st, src, (const uint32_t *)ctx->d_one, buf[which], n, mm,
+                               q, 0u, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+            src = buf[which];
+            which ^= 1;
+            mm = mh;
+        }
+        hipLaunchKernelGGL(k_compose_pairs, dim3(blocks), dim3(WG_BLOCK), 0, st, src, (const uint32_t *)d_zero, (uint32_t *)d_out, n,
+                           1u, q, 1u, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+        HIPCHK(hipGetLastError());
+        return COFHE_HIP_OK;
+    }
+    hipLaunchKernelGGL(k_accumulate, dim3(blocks), dim3(WG_BLOCK), 0, (hipStream_t)stream, (const uint32_t *)d_x,
+                       (const uint32_t *)d_zero, (uint32_t *)d_out, n, m, p, (const uint32_t *)ctx->d_absdelta,
+                       ctx->half_dbits, ctx->d_status);
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+}  // namespace
+
+// out = base^e through the table base^(2^j) of the context (built by a chain of squarings on first use, then cached):
+// the signed binary digits of e select ~bits/3 entries, which a pairwise product tree multiplies in ~log2 launches
+// of a few hundred independent compositions -- milliseconds instead of the ~0.45 s serial ladder.  For the powers
+// that always have the same base: h^r and pk^r of encryption (cpu_cryptosystem_tensor_ops.inl:7-12), h^sk of key generation.
+int cofhe_hip_pow_fixed_base_records(cofhe_hip_ctx *ctx, uint32_t n, const uint32_t *base_records, const uint32_t *exp_records, void *d_out,
+                                     void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (!base_records || !exp_records || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
+    if (n == 0) return COFHE_HIP_OK;
+    if (n > 4) return fail(COFHE_HIP_EINVAL, "at most 4 fixed-base powers per call (the context keeps 4 tables)");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    WsUse use(ctx, st);
+    const uint32_t TABLE_LEN = EXP_MAG_WORDS * 32 + 2;
+    // ---- tables of the bases (all n must be resident at once: the ones of this call are stamped first)
+    cofhe_hip_ctx::FixedBase *fbs[4] = {nullptr, nullptr, nullptr, nullptr};
+    const uint64_t call_stamp = ++ctx->fb_clock;
+    for (uint32_t b = 0; b < n; b++) {
+        const uint32_t *base_record = base_records + (size_t)b * REC_WORDS;
+        cofhe_hip_ctx::FixedBase *fb = nullptr, *victim = nullptr;
+        for (auto &e : ctx->fb) {
+            if (e.d_table && memcmp(e.base, base_record, REC_WORDS * 4) == 0) fb = &e;
+            if (e.stamp == call_stamp) continue;                       // in use by this call
+            if (!victim || !e.d_table || (victim->d_table && e.stamp < victim->stamp)) victim = &e;
+        }
+        if (!fb) {
+            fb = victim;
+            HIPCHK(hipStreamSynchronize(st));
+            if (!fb->d_table) HIPCHK(dev_alloc(ctx, (void **)&fb->d_table, (size_t)(TABLE_LEN + 1) * REC_WORDS * 4));
+            fb->len = 0;
+            HIPCHK(hipMemcpyAsync(fb->d_table + (size_t)TABLE_LEN * REC_WORDS, base_record, REC_WORDS * 4, hipMemcpyHostToDevice, st));
+            // one chain of ~1000 squarings: the latency kernel (one wavefront, wide layout); ladder_form 3 keeps the old one
+            if (ctx->opt_ladder_form == 3)
+                hipLaunchKernelGGL(k_square_chain, dim3(1), dim3(WG_BLOCK), 0, st, (const uint32_t *)(fb->d_table + (size_t)TABLE_LEN * REC_WORDS),
+                                   fb->d_table, TABLE_LEN, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+            else
+                hipLaunchKernelGGL(k_square_chain_wide, dim3(1), dim3(64), 0, st, (const uint32_t *)(fb->d_table + (size_t)TABLE_LEN * REC_WORDS),
+                                   fb->d_table, TABLE_LEN, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+            HIPCHK(hipGetLastError());
+            memcpy(fb->base, base_record, REC_WORDS * 4);
+            fb->len = TABLE_LEN;
+        }
+        fb->stamp = call_stamp;
+        fbs[b] = fb;
+    }
+    // ---- non-adjacent form of |e| on the host: digit_i = bit_(i+1)(3x) - bit_(i+1)(x)
+    std::vector<std::vector<uint32_t>> sel(n);
+    uint32_t mmax = 1;
+    for (uint32_t b = 0; b < n; b++) {
+        const uint32_t *exp_record = exp_records + (size_t)b * EXP_REC_WORDS;
+        const bool neg = exp_record[EXP_MAG_WORDS] != 0;
+        uint32_t x3[EXP_MAG_WORDS + 1];
+        uint64_t carry = 0;
+        for (int w = 0; w < EXP_MAG_WORDS; w++) {
+            const uint64_t t = (uint64_t)exp_record[w] * 3u + carry;
+            x3[w] = (uint32_t)t;
+            carry = t >> 32;
+        }
+        x3[EXP_MAG_WORDS] = (uint32_t)carry;
+        auto bit = [](const uint32_t *v, int words, int i) -> int { return (i >> 5) < words ? (int)((v[i >> 5] >> (i & 31)) & 1u) : 0; };
+        for (int i = 0; i < (int)TABLE_LEN; i++) {
+            const int dgt = bit(x3, EXP_MAG_WORDS + 1, i + 1) - bit(exp_record, EXP_MAG_WORDS, i + 1);
+            if (dgt != 0) sel[b].push_back((uint32_t)i | (b << 24) | (((dgt < 0) != neg) ? 0x80000000u : 0u));
+        }
+        if (sel[b].size() > mmax) mmax = (uint32_t)sel[b].size();
+    }
+    // ---- one gather and one product tree for all n powers (slices padded with the principal form)
+    std::vector<uint64_t> host((size_t)n + ((size_t)n * mmax + 1) / 2);
+    for (uint32_t b = 0; b < n; b++) host[b] = (uint64_t)(uintptr_t)fbs[b]->d_table;
+    uint32_t *hidx = (uint32_t *)(host.data() + n);
+    for (uint32_t b = 0; b < n; b++)
+        for (uint32_t i = 0; i < mmax; i++) hidx[(size_t)b * mmax + i] = i < sel[b].size() ? sel[b][i] : 0xFFFFFFFFu;
+    const WsPlan fp = plan_fixed_base(n, mmax);
+    if (int rc = ensure_workspace(ctx, fp.total, st)) return rc;
+    uint8_t *ws = (uint8_t *)ctx->workspace;
+    uint64_t *d_tabs = (uint64_t *)(ws + fp.off("gather"));
+    HIPCHK(hipMemcpyAsync(d_tabs, host.data(), host.size() * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));          // `host` is a local vector: the copy must have read it before it goes
+    uint32_t *buf[2] = {(uint32_t *)(ws + fp.off("level_a")), (uint32_t *)(ws + fp.off("level_b"))};
+    const uint32_t total = n * mmax;
+    hipLaunchKernelGGL(k_gather_signed, dim3((total + WG_GROUPS - 1) / WG_GROUPS), dim3(WG_BLOCK), 0, st, (const uint64_t *)d_tabs,
+                       (const uint32_t *)(d_tabs + n), (uint64_t)total, (const uint32_t *)ctx->d_one, buf[0]);
+    uint32_t mm = mmax;
+    int which = 0;
+    while (mm > 1) {
+        const uint32_t mh = (mm + 1) / 2;
+        uint32_t *dst = mh == 1 ? (uint32_t *)d_out : buf[which ^ 1];
+        hipLaunchKernelGGL(k_compose_pairs, dim3((n * mh + WG_GROUPS - 1) / WG_GROUPS), dim3(WG_BLOCK), 0, st, (const uint32_t *)buf[which],
+                           (const uint32_t *)ctx->d_one, dst, n, mm, 1u, 0u, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+        which ^= 1;
+        mm = mh;
+    }
+    if (mmax == 1) HIPCHK(hipMemcpyAsync(d_out, buf[0], (size_t)n * REC_WORDS * 4, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+int cofhe_hip_pow_fixed_base_record(cofhe_hip_ctx *ctx, const uint32_t *base_record, const uint32_t *exp_record, void *d_out, void *stream) {
+    return cofhe_hip_pow_fixed_base_records(ctx, 1, base_record, exp_record, d_out, stream);
+}
+
+int cofhe_hip_pow_form_records(cofhe_hip_ctx *ctx, const void *d_base, const void *d_exp, void *d_out, uint64_t n_forms,
+                               void *stream) {
+    if (n_forms == 0) return COFHE_HIP_OK;
+    return pow_launch(ctx, d_base, d_exp, d_out, n_forms, 1u, stream);
+}
+
+namespace {
+// out[i] = base[i * stride]^e, e one exponent record on the device; extra_bytes of the workspace are
+// left free in front for the caller (returned through *extra)
+int pow_shared(cofhe_hip_ctx *ctx, const void *d_base, uint32_t stride, const void *d_exp, void *d_out, uint64_t n,
+               size_t extra_bytes, void **extra, hipStream_t st) {
+    unsigned blocks;
+    if (int rc = compose_blocks(n, &blocks)) return rc;
+    const uint32_t w = POW_SHARED_W, tw = POW_SHARED_TW;
+    const WsPlan pp = plan_pow_shared(n, extra_bytes);         // front | table: odd powers, x^2, running power | digits | length
+    if (int rc = ensure_workspace(ctx, pp.total, st)) return rc;
+    uint8_t *ws = (uint8_t *)ctx->workspace;
+    if (extra) *extra = ws + pp.off("front");
+    if (!d_out) d_out = ws + pp.off("front");                  // result into the caller's part of the workspace
+    uint32_t *table = (uint32_t *)(ws + pp.off("table"));
+    int8_t *digits = (int8_t *)(ws + pp.off("digits"));
+    uint32_t *maxlen = (uint32_t *)(ws + pp.off("maxlen"));
+    uint32_t *pairctl = (uint32_t *)(ws + pp.off("pairctl"));
+    HIPCHK(hipMemsetAsync(digits, 0, pp.off("pairctl") + (size_t)POW_PAIR_MAX_LADDERS * 16 - pp.off("digits"), st));
+    // Few ladders (one, when a tensor shares its c1): latency is all there is -- the wavefront-wide layout (wide.hip), a pair
+    // of wavefronts per ladder (one squares, one multiplies: k_pow_shared_pair, non-adjacent digits), up to one ladder per CU
+    // (profiles/r04_a/wide_time.txt); "ladder_form" pins the choice (1: the pair, 2: the 8-lane solo form of round 4's first
+    // step, 3: the throughput kernel, 4: one wavefront per ladder, left to right with a table of odd powers)
+    int form = ctx->opt_ladder_form ? ctx->opt_ladder_form : (n <= 256 ? 1 : 3);           // one ladder per CU at most: four per CU ran at half speed each
+    if (form == 1 && n > POW_PAIR_MAX_LADDERS) form = 4;        // the pair's two workgroups must be resident together
+    hipLaunchKernelGGL(k_wnaf_digits, dim3(1), dim3(64), 0, st, (const uint32_t *)d_exp, (uint64_t)1, form == 1 ? 2u : w, digits, maxlen);
+    ProfScope ps(ctx, form == 1 ? "k_pow_shared_pair" : form == 4 ? "k_pow_shared_wide" : (form == 2 && n <= 64 / G) ? "k_pow_shared_solo" : "k_pow_shared",
+                 st);
+    if (form == 1)
+        hipLaunchKernelGGL(k_pow_shared_pair, dim3((unsigned)(2 * n)), dim3(64), 0, st, (const uint32_t *)d_base, (const int8_t *)digits,
+                           (const uint32_t *)maxlen, table, pairctl, (uint32_t *)d_out, n, stride, (const uint32_t *)ctx->d_one,
+                           (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);     // the table region serves as the rings
+    else if (form == 4)
+        hipLaunchKernelGGL(k_pow_shared_wide, dim3((unsigned)n), dim3(64), 0, st, (const uint32_t *)d_base, (const int8_t *)digits,
+                           (const uint32_t *)maxlen, table, (uint32_t *)d_out, n, stride, tw, (const uint32_t *)ctx->d_one,
+                           (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+    else if (form == 2 && n <= 64 / G)
+        hipLaunchKernelGGL(k_pow_shared_solo, dim3(1), dim3(64), 0, st, (const uint32_t *)d_base, (const int8_t *)digits,
+                           (const uint32_t *)maxlen, table, (uint32_t *)d_out, n, stride, tw, (const uint32_t *)ctx->d_one,
+                           (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+    else
+        hipLaunchKernelGGL(k_pow_shared, dim3(blocks), dim3(WG_BLOCK), 0, st, (const uint32_t *)d_base, (const int8_t *)digits,
+                           (const uint32_t *)maxlen, table, (uint32_t *)d_out, n, stride, tw, (const uint32_t *)ctx->d_one,
+                           (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+// out[i] = c1_i^e for the n_ct ciphertexts of a tensor (decryption, threshold decryption).  A tensor that encrypt_tensor
+// made -- or a sum of such tensors -- carries ONE c1 (cpu_cryptosystem_tensor_ops.inl:7-12): then one ladder runs and its
+// result is copied, instead of n_ct identical ladders of ~1100 compositions each (the latency of the call stays that
+// of one ladder; what goes away is the work: a 1024x1024 tensor decrypts ~8x faster).  Found out per call by one
+// pass over the c1 records; tensors with differing c1 (results of scal_ciphertext_tensors) take the plain path.
+int pow_shared_c1(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_exp, void *d_out, uint64_t n_ct, size_t extra_bytes, void **extra,
+                  hipStream_t st) {
+    bool shared = false;
+    if (n_ct >= 64) {
+        uint32_t *flag = ctx->d_flags + (ctx->flag_next++ % cofhe_hip_ctx::N_FLAGS);
+        HIPCHK(hipMemsetAsync(flag, 0, 4, st));
+        const unsigned scan_blocks = (unsigned)std::min<uint64_t>((n_ct * REC_WORDS + 255) / 256, 2048);
+        hipLaunchKernelGGL(k_c1_distinct, dim3(scan_blocks), dim3(256), 0, st, (const uint32_t *)d_cts, (const uint32_t *)d_cts, n_ct, flag);
+        uint32_t distinct = 1;
+        HIPCHK(hipMemcpyAsync(&distinct, flag, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        shared = distinct == 0;
+    }
+    if (!shared) return pow_shared(ctx, d_cts, 2, d_exp, d_out, n_ct, extra_bytes, extra, st);
+    void *ex = nullptr;
+    if (int rc = pow_shared(ctx, d_cts, 2, d_exp, d_out, 1, extra_bytes, &ex, st)) return rc;
+    if (extra) *extra = ex;
+    uint32_t *res = (uint32_t *)(d_out ? d_out : ex);
+    const unsigned blocks = (unsigned)std::min<uint64_t>((n_ct * REC_WORDS + 255) / 256, 4096);
+    ProfScope ps(ctx, "k_spread_records", st);               // the witness of the shared route: one ladder, then this copy
+    hipLaunchKernelGGL(k_spread_records, dim3(blocks), dim3(256), 0, st, res, n_ct);
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+}  // namespace
+
+int cofhe_hip_part_decrypt_records(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_share, void *d_out,
+                                   uint64_t n_ct, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (n_ct == 0) return COFHE_HIP_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    WsUse use(ctx, (hipStream_t)stream);
+    return pow_shared_c1(ctx, d_cts, d_share, d_out, n_ct, 0, nullptr, (hipStream_t)stream);
+}
+
+int cofhe_hip_scal_matmul_records(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_exp, const void *d_zero,
+                                  void *d_out, uint32_t n, uint32_t m, uint32_t p, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if ((uint64_t)n * p == 0) return COFHE_HIP_OK;
+    unsigned blocks;
+    if (int rc = compose_blocks((uint64_t)n * p * 2, &blocks)) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    WsUse use(ctx, st);
+    // window width: a table of 2^(w-2) odd powers per base costs that many compositions and is used by
+    // the p columns of its row, saving ~bits*(1/3 - 1/(w+1)) compositions in each; keep the tables under
+    // 1/8 of the device memory
+    const uint64_t nbase = (uint64_t)n * m * 2, n_exps = (uint64_t)m * p;
+    uint32_t w = 2, exp_bits = 0;                              // exp_bits: longest exponent of the call
+    if (m > 0) {
+        // per base: 2^(w-2) compositions for the table, then ~bits/(w+1) per column -- needs the exponent
+        // length, which lives on the device: one small reduction and a 4-byte read-back
+        if (int rc = ensure_workspace(ctx, 256, st)) return rc;
+        uint32_t *d_bits = (uint32_t *)ctx->workspace;
+        uint32_t bits = 0;
+        HIPCHK(hipMemsetAsync(d_bits, 0, 4, st));
+        hipLaunchKernelGGL(k_exp_maxbits, dim3((unsigned)((n_exps + 255) / 256)), dim3(256), 0, st, (const uint32_t *)d_exp, n_exps,
+                           d_bits);
+        HIPCHK(hipMemcpyAsync(&bits, d_bits, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        exp_bits = bits;
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(hipMemGetInfo(&free_b, &total_b));
+        double best = (double)p * bits / 3.0;                      // w = 2: plain NAF, no table
+        for (uint32_t cand = 3; cand <= 8; cand++) {
+            const uint64_t bytes = nbase * (1ull << (cand - 2)) * REC_WORDS * 4;
+            if (bytes > total_b / 8 || bytes > free_b / 2) break;
+            const double cost = (double)(1u << (cand - 2)) + (double)p * bits / (cand + 1.0);
+            if (cost < best) {
+                best = cost;
+                w = cand;
+            }
+        }
+        if (ctx->opt_wnaf_width >= 2 && ctx->opt_wnaf_width <= 8) w = ctx->opt_wnaf_width;      // cofhe_hip_ctx_set_option
+    }
+    const uint32_t tw = 1u << (w - 2);
+    if (m >= (1u << 21)) return fail(COFHE_HIP_EINVAL, "inner dimension beyond 2^21");
+    // The product-tree form (kernels above: k_tree_*) when there is something to pair up and enough outputs for the Horner
+    // chains to fill the GPU; small products keep the segmented lockstep chains below, which measured faster there
+    // (profiles/r04_a/tree_time.txt: 8x64.64x64 11.7 vs 12.8 ms, 64^3 21.6 vs 20.9, 32x256.256x256 k-bit 683 vs 673,
+    // 256^3 884 vs 787 ms -- chains vs tree).  "matmul_tree" = 0 / 1 pins the choice.
+    const bool use_tree = ctx->opt_matmul_tree == 1 || (ctx->opt_matmul_tree == -1 && m >= 8 && (uint64_t)n * p * 2 >= 4096);
+    if (use_tree && m > 0) {
+        const WsPlan tp = plan_scal_matmul_tree(n, m, p, exp_bits, w);
+        if (int rc = ensure_workspace(ctx, tp.total, st)) return rc;
+        uint8_t *ws = (uint8_t *)ctx->workspace;
+        int8_t *digits = (int8_t *)(ws + tp.off("digits"));
+        uint32_t *maxlen = (uint32_t *)(ws + tp.off("maxlen"));
+        uint32_t *d_c = (uint32_t *)(ws + tp.off("counts")), *d_off = (uint32_t *)(ws + tp.off("offsets"));
+        uint32_t *d_info = (uint32_t *)(ws + tp.off("info"));
+        const uint32_t S_cap = (exp_bits + 2) * p;
+        HIPCHK(hipMemsetAsync(digits, 0, tp.off("maxlen") + 256 - tp.off("digits"), st));
+        {
+            ProfScope ps(ctx, "k_wnaf_digits", st);
+            hipLaunchKernelGGL(k_wnaf_digits, dim3((unsigned)((n_exps + 255) / 256)), dim3(256), 0, st, (const uint32_t *)d_exp, n_exps, w,
+                               digits, maxlen);
+        }
+        HIPCHK(hipMemsetAsync(d_c, 0, (size_t)S_cap * 4, st));              // level 0 of segments beyond the longest exponent
+        hipLaunchKernelGGL(k_tree_count, dim3((unsigned)(((uint64_t)S_cap + 255) / 256)), dim3(256), 0, st, (const int8_t *)digits,
+                           (const uint32_t *)maxlen, m, p, d_c);
+        hipLaunchKernelGGL(k_tree_plan, dim3(1), dim3(1024), 0, st, (const uint32_t *)maxlen, p, S_cap, d_c, d_off, d_info);
+        uint32_t info[TREE_LEVELS + 3];
+        HIPCHK(hipMemcpyAsync(info, d_info, sizeof(info), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));                           // `info` is on the host
+        const uint32_t T = info[TREE_LEVELS + 1], S = info[TREE_LEVELS + 2];
+        if (T < 1 || T > TREE_LEVELS || S > S_cap) return fail(COFHE_HIP_EHIP, "matrix product: tree plan out of range");
+        // rows per chunk: the two level buffers hold N_1 x rows x 2 records each (level 1 is the largest) ...
+        const uint64_t n1 = info[1] ? info[1] : 1;
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(hipMemGetInfo(&free_b, &total_b));
+        // ... and small enough for the context's block cache to keep both of them between calls (a quarter of its cap each):
+        // buffers beyond the cap are given back to the driver at the end of every call, and allocating tens of GB anew
+        // cost the product more than its kernels (bench.py, first tree build: 2.03 s per 256^3 product of which 0.78 s compute)
+        const uint64_t budget = std::min<uint64_t>(free_b / 4, std::max<uint64_t>(ctx->pool_cap / 4, (uint64_t)1 << 30));
+        uint64_t R = budget / (n1 * 2 * REC_WORDS * 4);
+        if (R >= 16) R &= ~(uint64_t)15;                           // 2 R a multiple of 32: the groups of a workgroup share their element
+        if (R < 1) R = 1;
+        if (R > n) R = n;
+        // Long exponents make long trees (N_1 ~ p bits m / 2 (w + 1) elements per row): when fewer than 16 rows fit a chunk the
+        // workgroups mix tree elements, copies ride along as dummy compositions, and the chains win again (32x256.256x256 with
+        // 128-bit exponents: 0.83 s in 14-row chunks against 0.68 s; profiles/r04_a/tree_time_chunks.txt)
+        // The Horner chains address the top level's N_T elements through the op word's 21-bit base index (off_T[s] < N_T):
+        // beyond 2^21 elements the tree is not taken, "matmul_tree" = 1 included, and the chains below run instead
+        const bool tree_fits = info[T] <= MM_INDEX_LIMIT;
+        const bool tree_pays = tree_fits && (R >= 16 || R == n || ctx->opt_matmul_tree == 1);
+        if (tree_pays) {
+        const uint32_t *table = (const uint32_t *)d_cts;          // w == 2: the only table entry is the base itself
+        if (tw > 1 && nbase) {
+            unsigned tblocks;
+            if (int rc = compose_blocks(nbase, &tblocks)) return rc;
+            ProfScope ps(ctx, "k_pow_table", st);
+            launch_wg(ctx, k_pow_table3, k_pow_table, "k_pow_table3", nullptr, tblocks, st, (const uint32_t *)d_cts,
+                      (uint32_t *)(ws + tp.off("table")), nbase, tw, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+            table = (const uint32_t *)(ws + tp.off("table"));
+        }
+        uint64_t map_words = 0;
+        for (uint32_t l = 1; l <= T; l++) map_words += info[l];
+        const uint32_t len = p ? S / p : 0;                       // bit positions in use
+        const uint32_t rcap_h = 2 * len + 2;
+        DevBuf b_ent, b_map, b_ops, b_cnt, b_lvl[2];
+        if (int rc = b_ent.get(ctx, (size_t)info[0] * 4 + 4)) return rc;
+        if (int rc = b_map.get(ctx, (size_t)map_words * 4 + 4)) return rc;
+        if (int rc = b_ops.get(ctx, (size_t)p * rcap_h * 4)) return rc;
+        if (int rc = b_cnt.get(ctx, (size_t)p * 4)) return rc;
+        hipLaunchKernelGGL(k_tree_fill, dim3(S ? S : 1), dim3(64), 0, st, (const int8_t *)digits, m, p, S_cap, (const uint32_t *)d_c,
+                           (const uint32_t *)d_off, (const uint32_t *)d_info, (uint32_t *)b_ent.p, (uint32_t *)b_map.p);
+        hipLaunchKernelGGL(k_tree_horner_schedule, dim3((p + 63) / 64), dim3(64), 0, st, (const uint32_t *)maxlen, p, S_cap, (const uint32_t *)d_c,
+                           (const uint32_t *)d_off, (const uint32_t *)d_info, rcap_h, (uint32_t *)b_ops.p, (uint32_t *)b_cnt.p, ctx->d_status);
+        const size_t lvl_bytes = (size_t)n1 * R * 2 * REC_WORDS * 4;
+        if (int rc = b_lvl[0].get(ctx, lvl_bytes)) return rc;
+        if (int rc = b_lvl[1].get(ctx, lvl_bytes)) return rc;
+        const uint32_t *maps = (const uint32_t *)b_map.p;
+        for (uint32_t r0 = 0; r0 < n; r0 += (uint32_t)R) {
+            const uint32_t rows = std::min<uint32_t>((uint32_t)R, n - r0);
+            uint64_t map_base = 0;
+            for (uint32_t l = 0; l < T; l++) {                     // level l -> l + 1
+                const uint64_t items = (uint64_t)info[l + 1] * rows * 2;
+                unsigned lb;
+                if (items == 0) break;
+                if (int rc = compose_blocks(items, &lb)) return rc;
+                const uint32_t *src = l == 0 ? table + (uint64_t)r0 * m * 2 * tw * REC_WORDS : (const uint32_t *)b_lvl[(l - 1) & 1].p;
+                ProfScope ps(ctx, "k_tree_level", st);
+                hipLaunchKernelGGL(k_tree_level, dim3(lb), dim3(WG_BLOCK), 0, st, src, l == 0 ? 1u : 0u, (const uint32_t *)b_ent.p,
+                                   (const uint32_t *)(d_off + (uint64_t)l * (S_cap + 1)), (const uint32_t *)(d_off + (uint64_t)(l + 1) * (S_cap + 1)),
+                                   maps + map_base, info[l], info[l + 1], rows, m, tw, (uint32_t *)b_lvl[l & 1].p,
+                                   (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+                map_base += info[l + 1];
+            }
+            unsigned hb;
+            if (int rc = compose_blocks((uint64_t)rows * p * 2, &hb)) return rc;
+            ProfScope ps(ctx, "k_scal_matmul_wnaf", st);
+            launch_wg(ctx, k_scal_matmul_wnaf3, k_scal_matmul_wnaf, "k_scal_matmul_wnaf3", nullptr, hb, st, (const uint32_t *)b_lvl[(T - 1) & 1].p,
+                      (const uint32_t *)b_ops.p, (const uint32_t *)b_cnt.p, rcap_h, (const uint32_t *)d_zero,
+                      (uint32_t *)d_out + (uint64_t)r0 * p * 2 * REC_WORDS, rows, info[T] ? info[T] : 1u, p, 1u, 1u, (const uint32_t *)ctx->d_one,
+                      (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+        }
+        HIPCHK(hipGetLastError());
+        // the cached blocks go back behind the work queued on this stream
+        for (DevBuf *b : {&b_ent, &b_map, &b_ops, &b_cnt, &b_lvl[0], &b_lvl[1]}) {
+            (void)cofhe_hip_free_on_stream(ctx, b->p, stream);
+            b->p = nullptr;
+        }
+        return COFHE_HIP_OK;
+        }       // tree_pays
+    }
+    // few outputs (the reference's own benchmark shape is 8 x 64 . 64 x 64): cut the inner dimension into
+    // segments so that the chains fill the GPU, then fold the partial products with the accumulation tree
+    uint32_t segs = 1;
+    const uint64_t out_forms = (uint64_t)n * p * 2;
+    if (out_forms < 32768 && m >= 8) {                        // 32768 chains = 4 workgroups on each of 256 CUs
+        const uint64_t want = (32768 + out_forms - 1) / out_forms;
+        segs = (uint32_t)(want < 16 ? want : 16);
+        if (segs > m / 4) segs = m / 4;
+        if (segs < 2) segs = 1;
+    }
+    if (ctx->opt_matmul_segments >= 1 && ctx->opt_matmul_segments <= m) segs = ctx->opt_matmul_segments;
+    // workspace: plan_scal_matmul -- tables (tw > 1), digits, maxlen, schedules (rcap words per column), their lengths,
+    // partial products and their tree (segs > 1)
+    const uint32_t ncols = segs * p;
+    const uint32_t rcap = matmul_rcap(exp_bits, m, segs);
+    const WsPlan mp_ = plan_scal_matmul(n, m, p, exp_bits, w, segs);
+    if (int rc = ensure_workspace(ctx, mp_.total, st)) return rc;
+    uint8_t *ws = (uint8_t *)ctx->workspace;
+    int8_t *digits = (int8_t *)(ws + mp_.off("digits"));
+    uint32_t *maxlen = (uint32_t *)(ws + mp_.off("maxlen"));
+    uint32_t *ops = (uint32_t *)(ws + mp_.off("ops"));
+    uint32_t *counts = (uint32_t *)(ws + mp_.off("counts"));
+    uint32_t *partial = (uint32_t *)(ws + mp_.off("partial"));
+    HIPCHK(hipMemsetAsync(digits, 0, mp_.off("maxlen") + 256 - mp_.off("digits"), st));
+    if (n_exps) {
+        ProfScope ps(ctx, "k_wnaf_digits", st);
+        hipLaunchKernelGGL(k_wnaf_digits, dim3((unsigned)((n_exps + 255) / 256)), dim3(256), 0, st, (const uint32_t *)d_exp,
+                           n_exps, w, digits, maxlen);
+    }
+    hipLaunchKernelGGL(k_matmul_schedule, dim3(ncols), dim3(64), 0, st, (const int8_t *)digits, (const uint32_t *)maxlen, m, p,
+                       segs, rcap, ops, counts, ctx->d_status);
+    const uint32_t *table = (const uint32_t *)d_cts;          // w == 2: the only table entry is the base itself
+    if (tw > 1 && nbase) {
+        unsigned tblocks;
+        if (int rc = compose_blocks(nbase, &tblocks)) return rc;
+        ProfScope ps(ctx, "k_pow_table", st);
+        launch_wg(ctx, k_pow_table3, k_pow_table, "k_pow_table3", nullptr, tblocks, st, (const uint32_t *)d_cts,
+                  (uint32_t *)(ws + mp_.off("table")), nbase, tw, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+        table = (const uint32_t *)(ws + mp_.off("table"));
+    }
+    unsigned mblocks;
+    if (int rc = compose_blocks(out_forms * segs, &mblocks)) return rc;
+    {
+        ProfScope ps(ctx, "k_scal_matmul_wnaf", st);
+        launch_wg(ctx, k_scal_matmul_wnaf3, k_scal_matmul_wnaf, "k_scal_matmul_wnaf3", nullptr, mblocks, st, table, (const uint32_t *)ops,
+                  (const uint32_t *)counts, rcap, (const uint32_t *)d_zero, segs > 1 ? partial : (uint32_t *)d_out, n, m, p, tw, segs,
+                  (const uint32_t *)ctx->d_one, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+    }
+    HIPCHK(hipGetLastError());
+    if (segs > 1)
+        return accumulate_impl(ctx, partial, d_zero, d_out, n, segs, p, ws + mp_.off("tree"), stream);
+    return COFHE_HIP_OK;
+}
+
+namespace {
+// the table f^(-2^j), j < k, of the decryption kernels (built on first use, cached in the context)
+int ensure_ftab(cofhe_hip_ctx *ctx, const uint32_t *f_record, uint32_t kbits, void *stream) {
+    if (kbits == 0 || 2 * kbits + 1 > (uint32_t)PLIMBS * 32 || kbits > EXP_MAG_WORDS * 32 - 1)
+        return fail(COFHE_HIP_EINVAL, "k out of range");
+    HIPCHK(hipSetDevice(ctx->device));
+    if (ctx->ftab_k != kbits || memcmp(ctx->ftab_f, f_record, REC_WORDS * 4) != 0) {
+        // ftab[2j], ftab[2j+1] = f^(-2^j): k "ciphertexts" (f, f) raised to -2^j by k_pow
+        HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+        if (ctx->d_ftab) HIPCHK(hipFree(ctx->d_ftab));
+        ctx->d_ftab = nullptr;
+        ctx->ftab_k = 0;
+        std::vector<uint32_t> base((size_t)kbits * 2 * REC_WORDS), ex((size_t)kbits * EXP_REC_WORDS, 0);
+        for (uint32_t j = 0; j < kbits; j++) {
+            memcpy(&base[(size_t)(2 * j) * REC_WORDS], f_record, REC_WORDS * 4);
+            memcpy(&base[(size_t)(2 * j + 1) * REC_WORDS], f_record, REC_WORDS * 4);
+            ex[(size_t)j * EXP_REC_WORDS + (j >> 5)] = 1u << (j & 31);
+            ex[(size_t)j * EXP_REC_WORDS + EXP_MAG_WORDS] = 1u;          // negative
+        }
+        struct Tmp { void *p = nullptr; ~Tmp() { if (p) (void)hipFree(p); } } db, de;
+        HIPCHK(dev_alloc(ctx, &db.p, base.size() * 4));
+        HIPCHK(dev_alloc(ctx, &de.p, ex.size() * 4));
+        HIPCHK(dev_alloc(ctx, (void **)&ctx->d_ftab, base.size() * 4));
+        HIPCHK(hipMemcpy(db.p, base.data(), base.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(de.p, ex.data(), ex.size() * 4, hipMemcpyHostToDevice));
+        if (int rc = cofhe_hip_pow_records(ctx, db.p, de.p, ctx->d_ftab, kbits, nullptr)) return rc;
+        HIPCHK(hipDeviceSynchronize());
+        memcpy(ctx->ftab_f, f_record, REC_WORDS * 4);
+        ctx->ftab_k = kbits;
+    }
+    return COFHE_HIP_OK;
+}
+}  // namespace
+
+int cofhe_hip_decrypt_records(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_sk, const uint32_t *f_record,
+                              void *d_out, uint64_t n_ct, uint32_t kbits, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (n_ct == 0) return COFHE_HIP_OK;
+    if (int rc = ensure_ftab(ctx, f_record, kbits, stream)) return rc;
+    WsUse use(ctx, (hipStream_t)stream);
+    // d = c1^sk for every ciphertext (windowed ladder), then m = dlog(c2 o d^-1): the combiner with one part, which
+    // k_decrypt reads from the front of the workspace (plan "decrypt": front = one record per ciphertext)
+    void *d_parts = nullptr;
+    if (int rc = pow_shared_c1(ctx, d_cts, d_sk, nullptr, n_ct, (size_t)n_ct * REC_WORDS * 4, &d_parts, (hipStream_t)stream))
+        return rc;
+    unsigned blocks;
+    if (int rc = compose_blocks(n_ct, &blocks)) return rc;
+    launch_wg(ctx, k_decrypt3, k_decrypt, "k_decrypt3", "k_decrypt", blocks, (hipStream_t)stream, (const uint32_t *)d_cts,
+              (const uint32_t *)d_parts, 1u, (uint64_t)0, (const uint32_t *)ctx->d_ftab, (uint32_t *)d_out, n_ct, (int)kbits,
+              (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+
+int cofhe_hip_encrypt_records(cofhe_hip_ctx *ctx, const void *d_plain, const void *d_c1_pkr, const uint32_t *f_record,
+                              void *d_out, uint64_t n_ct, uint32_t kbits, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (n_ct == 0) return COFHE_HIP_OK;
+    if (int rc = ensure_ftab(ctx, f_record, kbits, stream)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    WsUse use(ctx, st);
+    // c2_i = pk^r o f^(m_i) is a product of table entries (one per non-zero signed digit of m_i, ~k/3 of them) and has
+    // no squarings, so it is multiplied out as a pairwise TREE over all elements at once: log2 levels of independent
+    // compositions (k_compose_pairs over the entry-major layout) instead of a lockstep chain of ~k/3 rounds.  Same
+    // number of compositions; at 128x128 the chain kernel took 22 ms, one ciphertext 20 ms (latency of 45 rounds).
+    const uint32_t cap = kbits / 2 + 3;                          // pk^r + at most ceil((k + 1) / 2) digits
+    const uint64_t CHUNK = 65536;                                // elements per pass: bounds the workspace (cap x CHUNK records x 2)
+    for (uint64_t e0 = 0; e0 < n_ct; e0 += CHUNK) {
+        const uint64_t ne = n_ct - e0 < CHUNK ? n_ct - e0 : CHUNK;
+        const WsPlan ep = plan_encrypt_chunk(ne, kbits);
+        if (int rc = ensure_workspace(ctx, ep.total, st)) return rc;
+        uint8_t *ws = (uint8_t *)ctx->workspace;
+        uint64_t *d_tabs = (uint64_t *)(ws + ep.off("header"));   // [0] table of f, [1] (h^r, pk^r); [2] = the slot counter
+        uint32_t *d_max = (uint32_t *)(ws + ep.off("header") + 16);
+        uint32_t *d_idx = (uint32_t *)(ws + ep.off("idx"));
+        uint32_t *buf[2] = {(uint32_t *)(ws + ep.off("level_a")), (uint32_t *)(ws + ep.off("level_b"))};
+        const uint64_t tabs[3] = {(uint64_t)(uintptr_t)ctx->d_ftab, (uint64_t)(uintptr_t)d_c1_pkr, 0};
+        HIPCHK(hipMemcpyAsync(d_tabs, tabs, sizeof(tabs), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_encrypt_select, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st,
+                           (const uint32_t *)d_plain + e0 * EXP_REC_WORDS, ne, (int)kbits, cap, d_idx, d_max);
+        uint32_t mmax = 0;
+        HIPCHK(hipMemcpyAsync(&mmax, d_max, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));                        // also: `tabs` has been read
+        if (mmax == 0 || mmax > cap) return fail(COFHE_HIP_EHIP, "encryption: slot count out of range");
+        const uint64_t total = (uint64_t)mmax * ne;
+        unsigned gblocks;
+        if (int rc = compose_blocks(total, &gblocks)) return rc;
+        hipLaunchKernelGGL(k_gather_signed, dim3(gblocks), dim3(WG_BLOCK), 0, st, (const uint64_t *)d_tabs, (const uint32_t *)d_idx, total,
+                           (const uint32_t *)ctx->d_one, buf[0]);
+        uint32_t mm = mmax;
+        int which = 0;
+        while (mm > 1) {
+            const uint32_t mh = (mm + 1) / 2;
+            unsigned blocks;
+            if (int rc = compose_blocks((uint64_t)mh * ne, &blocks)) return rc;
+            hipLaunchKernelGGL(k_compose_pairs, dim3(blocks), dim3(WG_BLOCK), 0, st, (const uint32_t *)buf[which], (const uint32_t *)ctx->d_one,
+                               buf[which ^ 1], 1u, mm, (uint32_t)ne, 0u, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+            which ^= 1;
+            mm = mh;
+        }
+        const unsigned zblocks = (unsigned)std::min<uint64_t>((ne * 2 * REC_WORDS + 255) / 256, 4096);
+        hipLaunchKernelGGL(k_zip_ciphertexts, dim3(zblocks), dim3(256), 0, st, (const uint32_t *)d_c1_pkr, (const uint32_t *)buf[which], ne,
+                           (uint32_t *)d_out + e0 * 2 * REC_WORDS);
+        HIPCHK(hipGetLastError());
+    }
+    return COFHE_HIP_OK;
+}
+
+int cofhe_hip_combine_part_decryptions_records(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_parts,
+                                               uint32_t n_parts, const int32_t *lambda, const uint32_t *f_record,
+                                               void *d_out, uint64_t n_ct, uint32_t kbits, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (n_parts == 0 || n_parts > 64) return fail(COFHE_HIP_EINVAL, "between 1 and 64 partial decryptions per ciphertext");
+    uint64_t negmask = 0;
+    for (uint32_t i = 0; i < n_parts; i++) {
+        if (lambda[i] != 1 && lambda[i] != -1) return fail(COFHE_HIP_EINVAL, "reconstruction coefficients must be +1 or -1");
+        if (lambda[i] < 0) negmask |= 1ull << i;
+    }
+    if (n_ct == 0) return COFHE_HIP_OK;
+    if (int rc = ensure_ftab(ctx, f_record, kbits, stream)) return rc;
+    unsigned blocks;
+    if (int rc = compose_blocks(n_ct, &blocks)) return rc;
+    launch_wg(ctx, k_decrypt3, k_decrypt, "k_decrypt3", "k_decrypt", blocks, (hipStream_t)stream, (const uint32_t *)d_cts,
+              (const uint32_t *)d_parts, n_parts, negmask, (const uint32_t *)ctx->d_ftab, (uint32_t *)d_out, n_ct, (int)kbits,
+              (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+
+int cofhe_hip_time_compose(cofhe_hip_ctx *ctx, const void *d_a, const void *d_b, void *d_out, uint64_t n, int iters,
+                           void *stream, float *ms_per_launch) {
+    if (iters <= 0 || n == 0) return fail(COFHE_HIP_EINVAL, "iters and n must be positive");
+    unsigned blocks;
+    if (int rc = compose_blocks(n, &blocks)) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipEvent_t e0, e1;
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    HIPCHK(hipEventRecord(e0, (hipStream_t)stream));
+    for (int i = 0; i < iters; i++)      // what cofhe_hip_compose_records launches, without its span
+        launch_wg(ctx, k_compose_wg3, k_compose_wg, nullptr, nullptr, blocks, (hipStream_t)stream, (const uint32_t *)d_a,
+                  (const uint32_t *)d_b, (uint32_t *)d_out, n, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+    HIPCHK(hipEventRecord(e1, (hipStream_t)stream));
+    HIPCHK(hipEventSynchronize(e1));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    hipEventDestroy(e0);
+    hipEventDestroy(e1);
+    HIPCHK(hipGetLastError());
+    *ms_per_launch = ms / iters;
+    return COFHE_HIP_OK;
+}
+
+int cofhe_hip_workspace_plan(const char *op, const uint64_t *args, uint32_t n_args, cofhe_hip_ws_region *regions, uint32_t cap,
+                             uint32_t *n_regions, uint64_t *total_bytes) {
+    if (!op || !args || !n_regions || !total_bytes) return fail(COFHE_HIP_EINVAL, "null argument");
+    const std::string o(op);
+    auto need = [&](uint32_t k) { return n_args == k; };
+    WsPlan p;
+    if (o == "pow_shared" && need(2)) {
+        p = plan_pow_shared(args[0], (size_t)args[1]);
+    } else if ((o == "decrypt" || o == "part_decrypt") && need(2)) {
+        // pow_shared_c1: one ladder when the tensor shares its c1 (found out per call for n_ct >= 64), else one per ciphertext;
+        // decryption keeps c1^sk of every ciphertext in front of the tables (k_decrypt reads it as its one "part")
+        const uint64_t n_ct = args[0], ladders = (args[1] && n_ct >= 64) ? 1 : n_ct;
+        p = plan_pow_shared(ladders, o == "decrypt" ? (size_t)n_ct * REC_WORDS * 4 : 0);
+    } else if (o == "scal_matmul" && need(6)) {
+        if (args[4] < 2 || args[4] > 8 || args[5] < 1) return fail(COFHE_HIP_EINVAL, "scal_matmul plan: w in 2..8, segs >= 1");
+        p = plan_scal_matmul((uint32_t)args[0], (uint32_t)args[1], (uint32_t)args[2], (uint32_t)args[3], (uint32_t)args[4], (uint32_t)args[5]);
+    } else if (o == "scal_matmul_tree" && need(5)) {
+        if (args[4] < 2 || args[4] > 8) return fail(COFHE_HIP_EINVAL, "scal_matmul_tree plan: w in 2..8");
+        p = plan_scal_matmul_tree((uint32_t)args[0], (uint32_t)args[1], (uint32_t)args[2], (uint32_t)args[3], (uint32_t)args[4]);
+    } else if (o == "accumulate_tree" && need(3)) {
+        p = plan_accumulate_tree((uint32_t)args[0], (uint32_t)args[1], (uint32_t)args[2]);
+    } else if (o == "encrypt_chunk" && need(2)) {
+        p = plan_encrypt_chunk(args[0], (uint32_t)args[1]);
+    } else if (o == "fixed_base" && need(2)) {
+        p = plan_fixed_base((uint32_t)args[0], (uint32_t)args[1]);
+    } else {
+        return fail(COFHE_HIP_EINVAL, "unknown workspace plan or wrong argument count: " + o);
+    }
+    *n_regions = (uint32_t)p.n;
+    *total_bytes = p.total;
+    for (int i = 0; i < p.n && (uint32_t)i < cap && regions; i++) regions[i] = p.r[i];
+    return COFHE_HIP_OK;
+}
+
+namespace {
+struct StreamTimer {
+    hipEvent_t a = nullptr, b = nullptr;
+};
+}  // namespace
+int cofhe_hip_timer_start(cofhe_hip_ctx *ctx, void *stream, void **timer) {
+    if (!ctx || !timer) return fail(COFHE_HIP_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    StreamTimer *t = new StreamTimer();
+    hipError_t e = hipEventCreate(&t->a);
+    if (e == hipSuccess) e = hipEventCreate(&t->b);
+    if (e == hipSuccess) e = hipEventRecord(t->a, (hipStream_t)stream);
+    if (e != hipSuccess) {
+        if (t->a) (void)hipEventDestroy(t->a);
+        if (t->b) (void)hipEventDestroy(t->b);
+        delete t;
+        return fail(COFHE_HIP_EHIP, std::string("stream timer: ") + hipGetErrorString(e));
+    }
+    *timer = t;
+    return COFHE_HIP_OK;
+}
+int cofhe_hip_timer_stop(cofhe_hip_ctx *ctx, void *timer, void *stream, float *ms) {
+    if (!ctx || !timer || !ms) return fail(COFHE_HIP_EINVAL, "null argument");
+    StreamTimer *t = (StreamTimer *)timer;
+    hipError_t e = hipEventRecord(t->b, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipEventSynchronize(t->b);
+    if (e == hipSuccess) e = hipEventElapsedTime(ms, t->a, t->b);
+    (void)hipEventDestroy(t->a);
+    (void)hipEventDestroy(t->b);
+    delete t;
+    if (e != hipSuccess) return fail(COFHE_HIP_EHIP, std::string("stream timer: ") + hipGetErrorString(e));
+    return COFHE_HIP_OK;
+}
+
+// ---- formats ---------------------------------------------------------------------------------
+namespace {
+// forms_per_elem = 2: ciphertext tensors (c1, c2); 1: partial-decryption tensors (one form each)
+int form_bytes_to_records(const uint8_t *bytes, size_t len, int forms_per_elem, uint32_t *ndim, uint32_t shape[8],
+                          uint32_t **records, uint64_t *n_records) {
+    std::vector<IntView> ints;
+    if (int rc = parse_tensor(bytes, len, 3 * (size_t)forms_per_elem, ndim, shape, ints)) return rc;
+    const uint64_t nrec = ints.size() / 3;
+    uint32_t *r = (uint32_t *)calloc(nrec ? nrec * REC_WORDS : 1, 4);
+    if (!r) return fail(COFHE_HIP_ENOMEM, "out of host memory");
+    for (uint64_t i = 0; i < nrec; i++) {
+        uint32_t *rec = r + i * REC_WORDS;
+        const IntView &a = ints[3 * i], &b = ints[3 * i + 1], &cc = ints[3 * i + 2];
+        bool ok = put_limbs(rec + REC_A, PLIMBS, a) && put_limbs(rec + REC_B, PLIMBS, b) &&
+                  put_limbs(rec + REC_C, 2 * PLIMBS, cc);
+        // a and c of a form are positive: their flag is set only for the value zero
+        if (ok && (bits_of(rec + REC_A, PLIMBS) == 0 || bits_of(rec + REC_C, 2 * PLIMBS) == 0)) ok = false;
+        if (!ok) {
+            free(r);
+            return fail(COFHE_HIP_EINVAL, "form coefficient outside the supported range");
+        }
+        rec[REC_SIGN] = (b.neg && bits_of(rec + REC_B, PLIMBS) != 0) ? 1u : 0u;
+    }
+    *records = r;
+    *n_records = nrec;
+    return COFHE_HIP_OK;
+}
+
+int form_records_to_bytes(const uint32_t *records, uint64_t nrec, int forms_per_elem, uint32_t ndim,
+                          const uint32_t *shape, uint8_t **bytes, size_t *len) {
+    uint64_t ne = 1;
+    for (uint32_t i = 0; i < ndim; i++) {
+        if (shape[i] != 0 && ne > (1ull << 40) / shape[i]) return fail(COFHE_HIP_EINVAL, "tensor too large");
+        ne *= shape[i];
+    }
+    if (ne * (uint64_t)forms_per_elem != nrec) return fail(COFHE_HIP_EINVAL, "shape does not match the record count");
+    const uint64_t cnt = nrec * 3;
+    std::vector<uint64_t> offs(cnt);
+    uint64_t last = 0;
+    for (uint64_t i = 0; i < nrec; i++) {
+        const uint32_t *rec = records + i * REC_WORDS;
+        const size_t ba = bits_of(rec + REC_A, PLIMBS), bb = bits_of(rec + REC_B, PLIMBS),
+                     bc = bits_of(rec + REC_C, 2 * PLIMBS);
+        // slot width = mpz_sizeinbase(x, 2) / 8 + 1 (sizeinbase(0) == 1); flag = (sgn != 1)
+        const size_t w[3] = {(ba ? ba : 1) / 8 + 1, (bb ? bb : 1) / 8 + 1, (bc ? bc : 1) / 8 + 1};
+        const bool flag[3] = {ba == 0, bb == 0 || rec[REC_SIGN] != 0, bc == 0};
+        for (int k = 0; k < 3; k++) {
+            offs[3 * i + k] = last | (flag[k] ? (1ull << 63) : 0ull);
+            last += w[k];
+        }
+    }
+    const size_t hdr = 4 + 4ull * ndim + 8ull * cnt;
+    const size_t total = hdr + last;
+    uint8_t *out = (uint8_t *)calloc(total ? total : 1, 1);
+    if (!out) return fail(COFHE_HIP_ENOMEM, "out of host memory");
+    memcpy(out, &ndim, 4);
+    for (uint32_t i = 0; i < ndim; i++) memcpy(out + 4 + 4 * i, &shape[i], 4);
+    memcpy(out + 4 + 4ull * ndim, offs.data(), 8ull * cnt);
+    uint8_t *body = out + hdr;
+    const uint64_t M = ~(1ull << 63);
+    for (uint64_t i = 0; i < nrec; i++) {
+        const uint32_t *rec = records + i * REC_WORDS;
+        const uint32_t *src[3] = {rec + REC_A, rec + REC_B, rec + REC_C};
+        for (int k = 0; k < 3; k++) {
+            const uint64_t st = offs[3 * i + k] & M;
+            const uint64_t en = (3 * i + k + 1 < cnt) ? (offs[3 * i + k + 1] & M) : last;
+            memcpy(body + st, src[k], (size_t)(en - st));   // slot never exceeds the limb array
+        }
+    }
+    *bytes = out;
+    *len = total;
+    return COFHE_HIP_OK;
+}
+
+}  // namespace
+
+int cofhe_hip_bytes_to_records(const uint8_t *bytes, size_t len, uint32_t *ndim, uint32_t shape[8], uint32_t **records,
+                               uint64_t *n_records) {
+    return form_bytes_to_records(bytes, len, 2, ndim, shape, records, n_records);
+}
+int cofhe_hip_records_to_bytes(const uint32_t *records, uint64_t nrec, uint32_t ndim, const uint32_t *shape,
+                               uint8_t **bytes, size_t *len) {
+    return form_records_to_bytes(records, nrec, 2, ndim, shape, bytes, len);
+}
+int cofhe_hip_pdr_bytes_to_records(const uint8_t *bytes, size_t len, uint32_t *ndim, uint32_t shape[8],
+                                   uint32_t **records, uint64_t *n_records) {
+    return form_bytes_to_records(bytes, len, 1, ndim, shape, records, n_records);
+}
+int cofhe_hip_pdr_records_to_bytes(const uint32_t *records, uint64_t nrec, uint32_t ndim, const uint32_t *shape,
+                                   uint8_t **bytes, size_t *len) {
+    return form_records_to_bytes(records, nrec, 1, ndim, shape, bytes, len);
+}
+
+int cofhe_hip_bytes_to_exponents(const uint8_t *bytes, size_t len, uint32_t *ndim, uint32_t shape[8], uint32_t **exps,
+                                 uint64_t *n_exps) {
+    std::vector<IntView> ints;
+    if (int rc = parse_tensor(bytes, len, 1, ndim, shape, ints)) return rc;
+    uint32_t *r = (uint32_t *)calloc(ints.size() ? ints.size() * EXP_REC_WORDS : 1, 4);
+    if (!r) return fail(COFHE_HIP_ENOMEM, "out of host memory");
+    for (size_t i = 0; i < ints.size(); i++) {
+        uint32_t *rec = r + i * EXP_REC_WORDS;
+        if (!put_limbs(rec, EXP_MAG_WORDS, ints[i])) {
+            free(r);
+            return fail(COFHE_HIP_EINVAL, "exponent wider than 992 bits");
+        }
+        rec[EXP_MAG_WORDS] = (ints[i].neg && bits_of(rec, EXP_MAG_WORDS) != 0) ? 1u : 0u;
+    }
+    *exps = r;
+    *n_exps = ints.size();
+    return COFHE_HIP_OK;
+}
+
+// ---- whole operations on host buffers ---------------------------------------------------------
+// The serialised tensors are uploaded verbatim and converted on the GPU (wire.hip): PCIe carries the
+// ~786 B/ciphertext of the wire format instead of 1344 B of records, and no host loop touches the data.
+namespace {
+// host bytes -> device records; kind as in cofhe_hip_unpack_tensor_device
+int load_tensor(cofhe_hip_ctx *ctx, const uint8_t *bytes, size_t len, int kind, DevBuf &recs, uint32_t *ndim,
+                uint32_t shape[8], uint64_t *n_records) {
+    if (len < 4) return fail(COFHE_HIP_EINVAL, "tensor buffer too short");
+    const size_t rec_bytes = kind == 0 ? EXP_REC_WORDS * 4 : REC_WORDS * 4;
+    const uint64_t cap = (len / 8) / (kind == 0 ? 1 : 3) + 1;      // every integer owns an 8-byte table entry
+    DevBuf raw;
+    if (int rc = raw.get(ctx, len)) return rc;
+    if (int rc = recs.get(ctx, cap * rec_bytes)) return rc;
+    HIPCHK(hipMemcpy(raw.p, bytes, len, hipMemcpyHostToDevice));
+    return cofhe_hip_unpack_tensor_device(ctx, raw.p, len, kind, recs.p, cap, ndim, shape, n_records, nullptr);
+}
+int finish(cofhe_hip_ctx *ctx, const DevBuf &dout, uint64_t nrec, uint32_t ndim, const uint32_t *shape, uint8_t **out,
+           size_t *outlen) {
+    const size_t cap = cofhe_hip_packed_size_bound(nrec, 2, ndim);
+    DevBuf packed;
+    if (int rc = packed.get(ctx, cap)) return rc;
+    size_t len = 0;
+    if (int rc = cofhe_hip_pack_tensor_device(ctx, dout.p, nrec, 2, ndim, shape, packed.p, cap, &len, nullptr)) return rc;
+    uint8_t *h = (uint8_t *)malloc(len ? len : 1);
+    if (!h) return fail(COFHE_HIP_ENOMEM, "out of host memory");
+    hipError_t e = hipMemcpy(h, packed.p, len, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+        free(h);
+        return fail(COFHE_HIP_EHIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
+    }
+    *out = h;
+    *outlen = len;
+    return COFHE_HIP_OK;
+}
+}  // namespace
+
+int cofhe_hip_add_ciphertext_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *t1, size_t l1, const uint8_t *t2, size_t l2,
+                                           uint8_t **out, size_t *outlen) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    uint32_t nd1, nd2, s1[8], s2[8];
+    uint64_t n1, n2;
+    HIPCHK(hipSetDevice(ctx->device));
+    DevBuf da, db, dc;
+    if (int rc = load_tensor(ctx, t1, l1, 2, da, &nd1, s1, &n1)) return rc;
+    if (int rc = load_tensor(ctx, t2, l2, 2, db, &nd2, s2, &n2)) return rc;
+    if (nd1 != nd2 || memcmp(s1, s2, 4 * nd1) != 0) return fail(COFHE_HIP_ESHAPE, "Tensor shapes must be equal");
+    const size_t bytes = (size_t)n1 * REC_WORDS * 4;
+    if (int rc = dc.get(ctx, bytes ? bytes : 4)) return rc;
+    if (int rc = cofhe_hip_add_ciphertext_records(ctx, da.p, db.p, dc.p, n1 / 2, nullptr)) return rc;
+    return finish(ctx, dc, n1, nd1, s1, out, outlen);
+}
+
+int cofhe_hip_scal_ciphertext_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *s, size_t ls, const uint8_t *cts, size_t lc,
+                                            const uint8_t *zero, size_t lz, uint8_t **out, size_t *outlen) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    uint32_t nds, ndc, ss[8], sc[8];
+    uint64_t ne, nr;
+    HIPCHK(hipSetDevice(ctx->device));
+    DevBuf de, dc, dz, dout;
+    if (int rc = load_tensor(ctx, s, ls, 0, de, &nds, ss, &ne)) return rc;
+    if (int rc = load_tensor(ctx, cts, lc, 2, dc, &ndc, sc, &nr)) return rc;
+    if (nds > 2 || ndc > 2 || nds != ndc)
+        return fail(COFHE_HIP_ENDIM, "Tensors must be 0D, 1D or 2D for now");
+    if (nds <= 1) {
+        // 0-D x 0-D (one exponent, one ciphertext: tensor_ops.inl:275-278, without the reference's re-randomisation --
+        // this entry point is deterministic) and 1-D x 1-D element-wise
+        if (nds == 1 && ss[0] != sc[0]) return fail(COFHE_HIP_ESHAPE, "Vector sizes must be equal");
+        if (ne * 2 != nr) return fail(COFHE_HIP_ESHAPE, "Vector sizes must be equal");
+        if (int rc = dout.get(ctx, nr ? nr * REC_WORDS * 4 : 4)) return rc;
+        if (int rc = cofhe_hip_pow_records(ctx, dc.p, de.p, dout.p, nr / 2, nullptr)) return rc;
+        return finish(ctx, dout, nr, ndc, sc, out, outlen);
+    }
+    // 2-D: cts n x m, s m x p
+    const uint32_t n = sc[0], m = sc[1], p = ss[1];
+    if (ss[0] != m) return fail(COFHE_HIP_ESHAPE, "inner dimensions of the matrix product differ");
+    uint32_t ndz, sz[8];
+    uint64_t nz;
+    if (!zero) return fail(COFHE_HIP_EINVAL, "the 2-D product needs the encryption of zero it starts from");
+    if (int rc = load_tensor(ctx, zero, lz, 2, dz, &ndz, sz, &nz)) return rc;
+    if (nz != 2) return fail(COFHE_HIP_EINVAL, "zero must be a one-element ciphertext tensor");
+    const uint64_t nout = (uint64_t)n * p * 2;
+    if (int rc = dout.get(ctx, nout ? nout * REC_WORDS * 4 : 4)) return rc;
+    if (int rc = cofhe_hip_scal_matmul_records(ctx, dc.p, de.p, dz.p, dout.p, n, m, p, nullptr)) return rc;
+    const uint32_t so[2] = {n, p};
+    return finish(ctx, dout, nout, 2, so, out, outlen);
+}
+
+}  // extern "C"

@@ -1,0 +1,106 @@
+// kernels.hpp -- one declaration of every kernel that abi.hip launches.  The definitions, with their
+// __launch_bounds__, are in cofhe_hip.hip (the throughput kernels, in three COFHE_PART passes) and wide.hip
+// (the latency kernels); wire.hip launches its own kernels.  A declaration that matches no definition is an
+// undefined symbol when the library is loaded (tests/test_cabi.py).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace cofhe_k {
+
+// tensor addition and form validation (cofhe_hip.hip)
+__global__ void k_compose_wg(const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, uint32_t *__restrict__ out, uint64_t n,
+                             const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status);
+__global__ void k_compose_wg3(const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, uint32_t *__restrict__ out, uint64_t n,
+                              const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status);
+__global__ void k_validate_forms(const uint32_t *__restrict__ recs, uint64_t n, const uint32_t *__restrict__ absdelta, uint32_t *__restrict__ err);
+__global__ void k_c1_distinct(const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, uint64_t n_ct, uint32_t *__restrict__ flag);
+__global__ void k_c1_spread(uint32_t *__restrict__ out, uint64_t n_ct, const uint32_t *__restrict__ flag);
+__global__ void k_spread_records(uint32_t *__restrict__ recs, uint64_t n);
+__global__ void k_add_ct(const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, uint32_t *__restrict__ out, uint64_t n_ct,
+                         const uint32_t *__restrict__ flag, const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status,
+                         uint32_t only);
+__global__ void k_add_ct3(const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, uint32_t *__restrict__ out, uint64_t n_ct,
+                          const uint32_t *__restrict__ flag, const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status,
+                          uint32_t only);
+
+// powering, encryption and the pairwise product trees (cofhe_hip.hip)
+__global__ void k_pow(const uint32_t *__restrict__ base, const uint32_t *__restrict__ exps, uint32_t *__restrict__ out, uint64_t n_records,
+                      uint32_t base_stride, uint32_t exp_mode, const uint32_t *__restrict__ one_rec, const uint32_t *__restrict__ absdelta,
+                      int half_dbits, uint32_t *__restrict__ status);
+__global__ void k_square_chain(const uint32_t *__restrict__ base, uint32_t *__restrict__ table, uint32_t len, const uint32_t *__restrict__ absdelta,
+                               int half_dbits, uint32_t *__restrict__ status);
+__global__ void k_gather_signed(const uint64_t *__restrict__ tabs, const uint32_t *__restrict__ idx, uint64_t n, const uint32_t *__restrict__ one_rec,
+                                uint32_t *__restrict__ out);
+__global__ void k_encrypt_select(const uint32_t *__restrict__ plain, uint64_t n_ct, int kbits, uint32_t cap, uint32_t *__restrict__ idx,
+                                 uint32_t *__restrict__ max_slots);
+__global__ void k_zip_ciphertexts(const uint32_t *__restrict__ c1, const uint32_t *__restrict__ c2, uint64_t n_ct, uint32_t *__restrict__ out);
+__global__ void k_compose_pairs(const uint32_t *__restrict__ x, const uint32_t *__restrict__ pad, uint32_t *__restrict__ out, uint32_t n, uint32_t m,
+                                uint32_t q, uint32_t pad_by_h, const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status);
+__global__ void k_accumulate(const uint32_t *__restrict__ x, const uint32_t *__restrict__ zero, uint32_t *__restrict__ out, uint32_t n, uint32_t m,
+                             uint32_t p, const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status);
+
+// the plaintext-matrix x ciphertext-matrix product: chains and product tree (cofhe_hip.hip)
+__global__ void k_exp_maxbits(const uint32_t *__restrict__ exps, uint64_t n_exps, uint32_t *__restrict__ maxbits);
+__global__ void k_wnaf_digits(const uint32_t *__restrict__ exps, uint64_t n_exps, uint32_t w, int8_t *__restrict__ digits,
+                              uint32_t *__restrict__ maxlen);
+__global__ void k_pow_table(const uint32_t *__restrict__ base, uint32_t *__restrict__ table, uint64_t n_records, uint32_t tw,
+                            const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status);
+__global__ void k_pow_table3(const uint32_t *__restrict__ base, uint32_t *__restrict__ table, uint64_t n_records, uint32_t tw,
+                             const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status);
+__global__ void k_matmul_schedule(const int8_t *__restrict__ digits, const uint32_t *__restrict__ maxlen, uint32_t m, uint32_t p, uint32_t segs,
+                                  uint32_t rcap, uint32_t *__restrict__ ops, uint32_t *__restrict__ counts, uint32_t *__restrict__ status);
+__global__ void k_scal_matmul_wnaf(const uint32_t *__restrict__ table, const uint32_t *__restrict__ ops, const uint32_t *__restrict__ counts,
+                                   uint32_t rcap, const uint32_t *__restrict__ zero, uint32_t *__restrict__ out, uint32_t n, uint32_t m, uint32_t p,
+                                   uint32_t tw, uint32_t segs, const uint32_t *__restrict__ one_rec, const uint32_t *__restrict__ absdelta,
+                                   int half_dbits, uint32_t *__restrict__ status);
+__global__ void k_scal_matmul_wnaf3(const uint32_t *__restrict__ table, const uint32_t *__restrict__ ops, const uint32_t *__restrict__ counts,
+                                    uint32_t rcap, const uint32_t *__restrict__ zero, uint32_t *__restrict__ out, uint32_t n, uint32_t m, uint32_t p,
+                                    uint32_t tw, uint32_t segs, const uint32_t *__restrict__ one_rec, const uint32_t *__restrict__ absdelta,
+                                    int half_dbits, uint32_t *__restrict__ status);
+__global__ void k_tree_count(const int8_t *__restrict__ digits, const uint32_t *__restrict__ maxlen, uint32_t m, uint32_t p,
+                             uint32_t *__restrict__ cnt);
+__global__ void k_tree_plan(const uint32_t *__restrict__ maxlen, uint32_t p, uint32_t S_cap, uint32_t *__restrict__ c, uint32_t *__restrict__ off,
+                            uint32_t *__restrict__ info);
+__global__ void k_tree_fill(const int8_t *__restrict__ digits, uint32_t m, uint32_t p, uint32_t S_cap, const uint32_t *__restrict__ c,
+                            const uint32_t *__restrict__ off, const uint32_t *__restrict__ info, uint32_t *__restrict__ ent0,
+                            uint32_t *__restrict__ maps);
+__global__ void k_tree_horner_schedule(const uint32_t *__restrict__ maxlen, uint32_t p, uint32_t S_cap, const uint32_t *__restrict__ c,
+                                       const uint32_t *__restrict__ off, const uint32_t *__restrict__ info, uint32_t rcap, uint32_t *__restrict__ ops,
+                                       uint32_t *__restrict__ counts, uint32_t *__restrict__ status);
+__global__ void k_tree_level(const uint32_t *__restrict__ src, uint32_t from_table, const uint32_t *__restrict__ ent0,
+                             const uint32_t *__restrict__ off_cur, const uint32_t *__restrict__ off_next, const uint32_t *__restrict__ map_next,
+                             uint32_t n_cur, uint32_t n_next, uint32_t rows, uint32_t m, uint32_t tw, uint32_t *__restrict__ dst,
+                             const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status);
+
+// shared-base ladders and decryption (cofhe_hip.hip)
+__global__ void k_pow_shared(const uint32_t *__restrict__ base, const int8_t *__restrict__ digits, const uint32_t *__restrict__ maxlen,
+                             uint32_t *__restrict__ table, uint32_t *__restrict__ out, uint64_t n_items, uint32_t base_stride, uint32_t tw,
+                             const uint32_t *__restrict__ one_rec, const uint32_t *__restrict__ absdelta, int half_dbits,
+                             uint32_t *__restrict__ status);
+__global__ void k_pow_shared_solo(const uint32_t *__restrict__ base, const int8_t *__restrict__ digits, const uint32_t *__restrict__ maxlen,
+                                  uint32_t *__restrict__ table, uint32_t *__restrict__ out, uint64_t n_items, uint32_t base_stride, uint32_t tw,
+                                  const uint32_t *__restrict__ one_rec, const uint32_t *__restrict__ absdelta, int half_dbits,
+                                  uint32_t *__restrict__ status);
+__global__ void k_decrypt(const uint32_t *__restrict__ cts, const uint32_t *__restrict__ parts, uint32_t n_parts, uint64_t negmask,
+                          const uint32_t *__restrict__ ftab, uint32_t *__restrict__ out, uint64_t n_ct, int kbits,
+                          const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status);
+__global__ void k_decrypt3(const uint32_t *__restrict__ cts, const uint32_t *__restrict__ parts, uint32_t n_parts, uint64_t negmask,
+                           const uint32_t *__restrict__ ftab, uint32_t *__restrict__ out, uint64_t n_ct, int kbits,
+                           const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status);
+
+// the latency kernels of wide.hip: one ladder / one composition per wavefront, wavefront-wide layout
+__global__ void k_pow_shared_wide(const uint32_t *__restrict__ base, const int8_t *__restrict__ digits, const uint32_t *__restrict__ maxlen,
+                                  uint32_t *__restrict__ table, uint32_t *__restrict__ out, uint64_t n_items, uint32_t base_stride, uint32_t tw,
+                                  const uint32_t *__restrict__ one_rec, const uint32_t *__restrict__ absdelta, int half_dbits,
+                                  uint32_t *__restrict__ status);
+__global__ void k_compose_wide(const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, uint32_t *__restrict__ out, uint64_t n, uint32_t reps,
+                               const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status,
+                               uint32_t *__restrict__ fallbacks);
+__global__ void k_pow_shared_pair(const uint32_t *__restrict__ base, const int8_t *__restrict__ digits, const uint32_t *__restrict__ maxlen,
+                                  uint32_t *__restrict__ ring_all, uint32_t *__restrict__ ctl_all, uint32_t *__restrict__ out, uint64_t n_items,
+                                  uint32_t base_stride, const uint32_t *__restrict__ one_rec, const uint32_t *__restrict__ absdelta, int half_dbits,
+                                  uint32_t *__restrict__ status);
+__global__ void k_square_chain_wide(const uint32_t *__restrict__ base, uint32_t *__restrict__ table, uint32_t len,
+                                    const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status);
+}  // namespace cofhe_k

@@ -60,6 +60,10 @@ constexpr int PLIMBS = G * CH;    // limbs per plane (40 limbs = 1280 bits)
 #define COFHE_WG_GROUPS 32
 #endif
 constexpr int WG_GROUPS = COFHE_WG_GROUPS;   // one request per lane of the serving wavefront (<= 64)
+constexpr int WG_BLOCK = WG_GROUPS * G;
+// MI355X: 256 CUs, 4 workgroups of this size resident on each; the dispatcher deals the first
+// 1024 workgroups out CU by CU, so blockIdx / 256 is the arrival order on the CU (Ctx::rank)
+constexpr unsigned NUM_CUS = 256;
 constexpr int WG_MAIL_WORDS = WG_GROUPS * 8 + WG_GROUPS * 4 + 4;     // replies (up to 8 words per group) | any-flag | stop bits per group
 constexpr int SCRATCH_WORDS = 209;  // group scratch (LDS slice): 4 operand planes / 4x8 chunk tails; odd stride: the
                                     // serving lanes read one word of every slice at once (bank = 17 l + i mod 32)

@@ -15,4 +15,15 @@
 namespace cofhe {
 constexpr int REC_WORDS = 168;
 constexpr int REC_A = 0, REC_B = 40, REC_C = 80, REC_SIGN = 160;
+
+// An op word of the matrix product's schedules (k_matmul_schedule, k_tree_horner_schedule), one composition each:
+//   word = kind << 29 | j << 8 | negative << 7 | (|digit| >> 1)
+// j has 21 bits: base index < 2^21 (the chains: j < m; the tree's Horner schedule: j = off_T[s] < N_T, see MM_INDEX_LIMIT)
+constexpr uint32_t MM_END = 0, MM_SQUARE = 1, MM_MUL = 2, MM_FIRST = 3, MM_ZEROMUL = 4, MM_FIRSTZERO = 5, MM_FIRSTONE = 6;
+constexpr uint32_t MM_INDEX_LIMIT = 1u << 21;        // base indices of an op word: 0 .. 2^21 - 1
+
+// Levels of the matrix product's product tree: m < 2^21 entries per segment.  The top level's element index off_T[s] goes
+// into the Horner op word's 21-bit base index, so the tree is taken only while N_T <= 2^21 (cofhe_hip_scal_matmul_records;
+// N_T reaches ~ len p, not m)
+constexpr int TREE_LEVELS = 22;
 }  // namespace cofhe

@@ -561,6 +561,7 @@ CF_DEV void qf_inverse(Ctx &c, QForm &f) {
 // Exponent record: EXP_MAG_WORDS little-endian magnitude words followed by one sign word.
 constexpr int EXP_MAG_WORDS = 31;     // 992-bit magnitudes: covers encryption randomness (~970 bits)
 constexpr int EXP_REC_WORDS = 32;
+constexpr int WNAF_POSITIONS = EXP_MAG_WORDS * 32 + 2;      // wNAF digit positions of an exponent (k_wnaf_digits)
 
 CF_DEV int exp_bitlen(const uint32_t *e) {
     int n = 0;

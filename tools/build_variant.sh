@@ -1,20 +1,12 @@
 #!/bin/bash
 # tools/build_variant.sh NAME [extra hipcc flags...] -- builds build/libcofhe_hip_NAME.so (tuning variants of the
-# product library; bench.py loads one with --lib).  SRC=<dir> builds from another source tree (e.g. an export of an
-# earlier commit: git archive HEAD cofhe_amd/csrc include | tar -x -C /tmp/base_src; SRC=/tmp/base_src).
+# product library; bench.py loads one with --lib) with __graft_entry__.build_library.  SRC=<dir> builds from another
+# source tree (e.g. an export of an earlier commit: git archive HEAD cofhe_amd/csrc include | tar -x -C /tmp/base_src;
+# SRC=/tmp/base_src); a tree from before the C ABI moved to abi.hip is built with that tree's own build().
 set -e
 cd "$(dirname "$0")/.."
 name=$1; shift
 S=${SRC:-.}
-mkdir -p build/obj_$name
-FLAGS="--offload-arch=gfx950 -O2 -std=c++17 -fPIC -Wno-unused-value $*"
-pids=()
-for part in 0 1 2; do
-  /opt/rocm/bin/hipcc $FLAGS -DCOFHE_PART=$part -c $S/cofhe_amd/csrc/cofhe_hip.hip -o build/obj_$name/part$part.o & pids+=($!)
-done
-/opt/rocm/bin/hipcc $FLAGS -c $S/cofhe_amd/csrc/wire.hip -o build/obj_$name/wire.o & pids+=($!)
-/opt/rocm/bin/hipcc $FLAGS -c $S/cofhe_amd/csrc/shard.hip -o build/obj_$name/shard.o & pids+=($!)
-/opt/rocm/bin/hipcc $FLAGS -c $S/cofhe_amd/csrc/wide.hip -o build/obj_$name/wide.o & pids+=($!)
-for p in "${pids[@]}"; do wait $p; done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o build/libcofhe_hip_$name.so build/obj_$name/part0.o build/obj_$name/part1.o build/obj_$name/part2.o build/obj_$name/wire.o build/obj_$name/shard.o build/obj_$name/wide.o -ldl
+python3 -c 'import sys; import __graft_entry__ as g; g.build_library(sys.argv[1], sys.argv[2], sys.argv[3], sys.argv[4:])' \
+  $S/cofhe_amd/csrc build/obj_$name build/libcofhe_hip_$name.so "$@"
 echo "built build/libcofhe_hip_$name.so"

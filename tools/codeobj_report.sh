@@ -1,13 +1,14 @@
 #!/bin/bash
 # tools/codeobj_report.sh -> per-kernel register / scratch / code size and the instruction mix of k_compose_wg: the
-# static view of the gfx950 code objects of the last build (cofhe_amd/csrc/obj/*.o, one per part of cofhe_hip.hip)
+# static view of the gfx950 code objects of the last build (every object in cofhe_amd/csrc/obj/ that holds device code)
 set -e
 cd "$(dirname "$0")/.."
 BIN=/opt/rocm/lib/llvm/bin
 TMP=$(mktemp -d)
-for n in part0 part1 part2 wire; do
-  cp cofhe_amd/csrc/obj/$n.o $TMP/$n.o
-  (cd $TMP && $BIN/llvm-objdump --offloading $n.o > /dev/null && mv $n.o.0.hipv4-amdgcn-amd-amdhsa--gfx950 $n.co)
+for o in cofhe_amd/csrc/obj/*.o; do
+  n=$(basename $o .o)
+  cp $o $TMP/$n.o
+  (cd $TMP && $BIN/llvm-objdump --offloading $n.o > /dev/null && { [ ! -f $n.o.0.hipv4-amdgcn-amd-amdhsa--gfx950 ] || mv $n.o.0.hipv4-amdgcn-amd-amdhsa--gfx950 $n.co; })
 done
 echo "== kernels (metadata notes of the code objects)"
 for f in $TMP/*.co; do

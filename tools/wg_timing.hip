@@ -9,6 +9,7 @@ __device__ unsigned int g_wg_wave[16384 * 4];              // per hardware wavef
 __device__ unsigned long long g_wg_clk[16384 * 2];
 __device__ unsigned int g_wg_flags[16384];                  // CF_FLAG bits: 1 common factor, 2 general route, 4 long-division step, 8 add-back         // s_memtime (shader clock) at the start / end of every workgroup
 #include "../cofhe_amd/csrc/cofhe_hip.hip"
+#include "../include/cofhe_hip.h"
 
 #include <algorithm>
 #include <chrono>
