@@ -85,6 +85,45 @@ size_t bits_of(const uint32_t *w, int words) {
 
 }  // namespace
 
+
+// ---- the host side of the fixed-base comb: per context, its cached tables and its two option pins ----------------------
+namespace {
+struct CombTable {
+    uint32_t base[REC_WORDS];
+    uint32_t w = 0;
+    uint32_t *d = nullptr;
+    uint64_t stamp = 0;
+};
+struct CombState {
+    static constexpr int N_TABLES = 8;           // w = 10: 100 x 512 records = 34.4 MB each
+    CombTable tabs[N_TABLES];
+    uint64_t clock = 0;
+    uint32_t opt_width = 0;                      // "comb_width": 0 = the launcher decides
+    uint64_t opt_chunk = 0;                      // "comb_chunk": 0 = the launcher decides
+};
+std::mutex g_comb_mu;
+std::unordered_map<const cofhe_hip_ctx *, CombState *> g_comb;
+CombState &comb_state(const cofhe_hip_ctx *ctx) {
+    std::lock_guard<std::mutex> lk(g_comb_mu);
+    CombState *&st = g_comb[ctx];
+    if (!st) st = new CombState();
+    return *st;
+}
+void comb_release(const cofhe_hip_ctx *ctx) {
+    CombState *st = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(g_comb_mu);
+        auto it = g_comb.find(ctx);
+        if (it == g_comb.end()) return;
+        st = it->second;
+        g_comb.erase(it);
+    }
+    for (auto &t : st->tabs)
+        if (t.d) (void)hipFree(t.d);
+    delete st;
+}
+}  // namespace
+
 extern "C" {
 
 const char *cofhe_hip_last_error(void) { return g_err.c_str(); }
@@ -159,6 +198,7 @@ void cofhe_hip_ctx_destroy(cofhe_hip_ctx *ctx) {
     if (ctx->d_ftab) hipFree(ctx->d_ftab);
     for (auto &e : ctx->fb)
         if (e.d_table) hipFree(e.d_table);
+    comb_release(ctx);
     (void)hipDeviceSynchronize();
     for (auto &sp : ctx->prof) {
         (void)hipEventDestroy(sp.a);
@@ -262,6 +302,12 @@ int cofhe_hip_ctx_set_option(cofhe_hip_ctx *ctx, const char *name, int64_t value
         ctx->opt_matmul_tree = (int)value;
     } else if (n == "profile_kernels") {
         ctx->opt_profile = value != 0;
+    } else if (n == "comb_width") {
+        if (value != 0 && (value < COMB_W_MIN || value > COMB_W_MAX)) return fail(COFHE_HIP_EINVAL, "comb_width: 0 (automatic) or 2..10");
+        comb_state(ctx).opt_width = (uint32_t)value;
+    } else if (n == "comb_chunk") {
+        if (value < 0 || value > (1ll << 32)) return fail(COFHE_HIP_EINVAL, "comb_chunk: 0 (automatic) or a positive count");
+        comb_state(ctx).opt_chunk = (uint64_t)value;
     } else {
         return fail(COFHE_HIP_EINVAL, "unknown option: " + n);
     }
@@ -521,6 +567,52 @@ inline WsPlan plan_fixed_base(uint32_t n, uint32_t mmax) {
     q.add("gather", ((size_t)n + ((size_t)n * mmax + 1) / 2) * 8);
     return q;
 }
+// The fixed-base comb (comb.hpp): items are ciphertexts (kind 1 encrypt_fresh, 2 rerandomize: two columns each) or powers
+// (kind 0: one column each).  One chunk of `ne` items: [level_a: the fused first level, slots / 2 records per column]
+// [level_b: the next level, ceil(slots / 4) per column]; the levels above alternate between the two.
+constexpr uint64_t COMB_WS_LIMIT = 4ull << 30;               // one call's workspace, whatever n
+constexpr uint64_t COMB_CHUNK_MAX = 65536;                   // items per pass when nothing else limits it
+struct CombCall {
+    CombShape s;
+    uint32_t slots;
+    uint64_t chunk;
+};
+inline CombShape comb_shape_of(uint32_t kind, uint32_t w, uint32_t exp_bits, uint32_t kbits) {
+    CombShape s{};
+    s.w = w;
+    s.npos_r = comb_positions(exp_bits < COMB_EXP_BITS ? exp_bits : COMB_EXP_BITS, w);
+    s.npos_m = kind == 1 ? comb_positions(kbits, w) : 0u;
+    s.leaf = kind == 2 ? 1u : 0u;
+    s.halves = kind == 0 ? 1u : 2u;
+    s.kbits = kbits;
+    return s;
+}
+inline WsPlan plan_comb_chunk(const CombShape &s, uint64_t ne) {
+    WsPlan q;
+    const uint64_t cols = ne * s.halves, slots = comb_slots(s);
+    q.add("level_a", (size_t)(slots / 2) * cols * REC_WORDS * 4);
+    q.add("level_b", (size_t)((slots + 3) / 4) * cols * REC_WORDS * 4);
+    return q;
+}
+// the launcher's decisions for n items whose longest exponent has exp_bits bits: w (pinned, or the widest, 10, for every
+// count from 1 024 ciphertexts up -- fresh encryption of 16 384 took 62.6 / 45.5 / 36.3 ms at w = 6 / 8 / 10, 262 144: 1001 /
+// 724 / 571 ms, profiles/r07_fresh; below that the call is latency and w does not matter; a table of 34 MB builds in 1.7 ms)
+// and the chunk (pinned, or as many items as keep the workspace within COMB_WS_LIMIT)
+inline uint32_t comb_auto_width(uint64_t n, uint32_t exp_bits) {
+    (void)n;
+    return exp_bits < 64 ? 4u : 10u;          // short exponents: a few positions at any w, and a table 64 times smaller
+}
+inline CombCall comb_call(uint32_t kind, uint64_t n, uint32_t exp_bits, uint32_t kbits, uint32_t w_pin, uint64_t chunk_pin) {
+    CombCall c{};
+    c.s = comb_shape_of(kind, w_pin ? w_pin : comb_auto_width(n, exp_bits), exp_bits, kbits);
+    c.slots = comb_slots(c.s);
+    const uint64_t per_item = plan_comb_chunk(c.s, 1).total;
+    uint64_t fit = (COMB_WS_LIMIT - 512) / per_item;
+    if (fit > COMB_CHUNK_MAX) fit = COMB_CHUNK_MAX;
+    c.chunk = chunk_pin ? (chunk_pin < fit ? chunk_pin : fit) : fit;
+    if (n < c.chunk) c.chunk = n ? n : 1;
+    return c;
+}
 }  // extern "C++"
 
 // One user of the workspace at a time, on the device as well: the host lock (ctx->mu) only covers the enqueueing, the
@@ -722,6 +814,39 @@ int accumulate_impl(cofhe_hip_ctx *ctx, const void *d_x, const void *d_zero, voi
     HIPCHK(hipGetLastError());
     return COFHE_HIP_OK;
 }
+// The chain base^(2^j), j < FIXED_BASE_CHAIN_LEN, of a base from the context's cache, built on a miss into the least recently
+// used slot that this call (call_stamp) does not hold: one chain of ~1000 squarings on `st`.  The fixed-base powers and the
+// comb tables (which start from every w-th entry) share it.
+constexpr uint32_t FIXED_BASE_CHAIN_LEN = EXP_MAG_WORDS * 32 + 2;
+int fixed_base_chain(cofhe_hip_ctx *ctx, const uint32_t *base_record, uint64_t call_stamp, hipStream_t st, cofhe_hip_ctx::FixedBase **out) {
+    const uint32_t TABLE_LEN = FIXED_BASE_CHAIN_LEN;
+    cofhe_hip_ctx::FixedBase *fb = nullptr, *victim = nullptr;
+    for (auto &e : ctx->fb) {
+        if (e.d_table && memcmp(e.base, base_record, REC_WORDS * 4) == 0) fb = &e;
+        if (e.stamp == call_stamp) continue;                       // in use by this call
+        if (!victim || !e.d_table || (victim->d_table && e.stamp < victim->stamp)) victim = &e;
+    }
+    if (!fb) {
+        fb = victim;
+        HIPCHK(hipStreamSynchronize(st));
+        if (!fb->d_table) HIPCHK(dev_alloc(ctx, (void **)&fb->d_table, (size_t)(TABLE_LEN + 1) * REC_WORDS * 4));
+        fb->len = 0;
+        HIPCHK(hipMemcpyAsync(fb->d_table + (size_t)TABLE_LEN * REC_WORDS, base_record, REC_WORDS * 4, hipMemcpyHostToDevice, st));
+        // one chain of ~1000 squarings: the latency kernel (one wavefront, wide layout); ladder_form 3 keeps the old one
+        if (ctx->opt_ladder_form == 3)
+            hipLaunchKernelGGL(k_square_chain, dim3(1), dim3(WG_BLOCK), 0, st, (const uint32_t *)(fb->d_table + (size_t)TABLE_LEN * REC_WORDS),
+                               fb->d_table, TABLE_LEN, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+        else
+            hipLaunchKernelGGL(k_square_chain_wide, dim3(1), dim3(64), 0, st, (const uint32_t *)(fb->d_table + (size_t)TABLE_LEN * REC_WORDS),
+                               fb->d_table, TABLE_LEN, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+        HIPCHK(hipGetLastError());
+        memcpy(fb->base, base_record, REC_WORDS * 4);
+        fb->len = TABLE_LEN;
+    }
+    fb->stamp = call_stamp;
+    *out = fb;
+    return COFHE_HIP_OK;
+}
 }  // namespace
 
 // out = base^e through the table base^(2^j) of the context (built by a chain of squarings on first use, then cached):
@@ -737,38 +862,12 @@ int cofhe_hip_pow_fixed_base_records(cofhe_hip_ctx *ctx, uint32_t n, const uint3
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     WsUse use(ctx, st);
-    const uint32_t TABLE_LEN = EXP_MAG_WORDS * 32 + 2;
+    const uint32_t TABLE_LEN = FIXED_BASE_CHAIN_LEN;
     // ---- tables of the bases (all n must be resident at once: the ones of this call are stamped first)
     cofhe_hip_ctx::FixedBase *fbs[4] = {nullptr, nullptr, nullptr, nullptr};
     const uint64_t call_stamp = ++ctx->fb_clock;
-    for (uint32_t b = 0; b < n; b++) {
-        const uint32_t *base_record = base_records + (size_t)b * REC_WORDS;
-        cofhe_hip_ctx::FixedBase *fb = nullptr, *victim = nullptr;
-        for (auto &e : ctx->fb) {
-            if (e.d_table && memcmp(e.base, base_record, REC_WORDS * 4) == 0) fb = &e;
-            if (e.stamp == call_stamp) continue;                       // in use by this call
-            if (!victim || !e.d_table || (victim->d_table && e.stamp < victim->stamp)) victim = &e;
-        }
-        if (!fb) {
-            fb = victim;
-            HIPCHK(hipStreamSynchronize(st));
-            if (!fb->d_table) HIPCHK(dev_alloc(ctx, (void **)&fb->d_table, (size_t)(TABLE_LEN + 1) * REC_WORDS * 4));
-            fb->len = 0;
-            HIPCHK(hipMemcpyAsync(fb->d_table + (size_t)TABLE_LEN * REC_WORDS, base_record, REC_WORDS * 4, hipMemcpyHostToDevice, st));
-            // one chain of ~1000 squarings: the latency kernel (one wavefront, wide layout); ladder_form 3 keeps the old one
-            if (ctx->opt_ladder_form == 3)
-                hipLaunchKernelGGL(k_square_chain, dim3(1), dim3(WG_BLOCK), 0, st, (const uint32_t *)(fb->d_table + (size_t)TABLE_LEN * REC_WORDS),
-                                   fb->d_table, TABLE_LEN, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
-            else
-                hipLaunchKernelGGL(k_square_chain_wide, dim3(1), dim3(64), 0, st, (const uint32_t *)(fb->d_table + (size_t)TABLE_LEN * REC_WORDS),
-                                   fb->d_table, TABLE_LEN, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
-            HIPCHK(hipGetLastError());
-            memcpy(fb->base, base_record, REC_WORDS * 4);
-            fb->len = TABLE_LEN;
-        }
-        fb->stamp = call_stamp;
-        fbs[b] = fb;
-    }
+    for (uint32_t b = 0; b < n; b++)
+        if (int rc = fixed_base_chain(ctx, base_records + (size_t)b * REC_WORDS, call_stamp, st, &fbs[b])) return rc;
     // ---- non-adjacent form of |e| on the host: digit_i = bit_(i+1)(3x) - bit_(i+1)(x)
     std::vector<std::vector<uint32_t>> sel(n);
     uint32_t mmax = 1;
@@ -828,6 +927,149 @@ int cofhe_hip_pow_form_records(cofhe_hip_ctx *ctx, const void *d_base, const voi
                                void *stream) {
     if (n_forms == 0) return COFHE_HIP_OK;
     return pow_launch(ctx, d_base, d_exp, d_out, n_forms, 1u, stream);
+}
+
+// ---- the fixed-base comb (comb.hpp, comb.hip) -----------------------------------------------------------------------------
+// base^e[i] for many exponents against one cached table per (base, w): one fused gather + first-level launch and the
+// k_compose_pairs levels of a pairwise tree per chunk, ~floor(bits/w) + 1 compositions per power and no squarings.
+namespace {
+int comb_check(uint64_t kind, uint64_t n, uint64_t exp_bits, uint64_t kbits, uint64_t w, uint64_t chunk) {
+    if (kind > 2) return fail(COFHE_HIP_EINVAL, "comb: kind 0 (powers), 1 (fresh encryption) or 2 (re-randomisation)");
+    if (n > (1ull << 36)) return fail(COFHE_HIP_EINVAL, "comb: too many items");
+    if (exp_bits > COMB_EXP_BITS) return fail(COFHE_HIP_EINVAL, "comb: exponents have at most 992 bits");
+    if (w != 0 && (w < (uint64_t)COMB_W_MIN || w > (uint64_t)COMB_W_MAX)) return fail(COFHE_HIP_EINVAL, "comb: w is 0 (automatic) or 2..10");
+    if (kind == 1 && (kbits == 0 || 2 * kbits + 1 > (uint64_t)PLIMBS * 32 || kbits > EXP_MAG_WORDS * 32 - 1))
+        return fail(COFHE_HIP_EINVAL, "k out of range");
+    if (chunk > (1ull << 32)) return fail(COFHE_HIP_EINVAL, "comb: chunk out of range");
+    return COFHE_HIP_OK;
+}
+
+// the comb table of (base, w), from the cache or built on `st`: T[j][1] = chain entry w j (one strided copy), then the
+// w - 1 levels of k_comb_table.  The tables of one call are all stamped with call_stamp and are not evicted by it.
+int comb_table(cofhe_hip_ctx *ctx, const uint32_t *base_record, uint32_t w, uint64_t call_stamp, hipStream_t st, const uint32_t **out) {
+    CombState &cs = comb_state(ctx);
+    CombTable *hit = nullptr, *victim = nullptr;
+    for (auto &t : cs.tabs) {
+        if (t.d && t.w == w && memcmp(t.base, base_record, REC_WORDS * 4) == 0) hit = &t;
+        if (t.stamp == call_stamp) continue;
+        if (!victim || !t.d || (victim->d && t.stamp < victim->stamp)) victim = &t;
+    }
+    if (!hit) {
+        if (!victim) return fail(COFHE_HIP_EINVAL, "comb: no table slot left");
+        hit = victim;
+        const uint32_t npos = comb_table_positions(w), D = comb_entries(w);
+        HIPCHK(hipStreamSynchronize(st));                         // the slot's previous table may still be read
+        if (hit->d) HIPCHK(hipFree(hit->d));
+        hit->d = nullptr;
+        hit->w = 0;
+        HIPCHK(dev_alloc(ctx, (void **)&hit->d, (size_t)npos * D * REC_WORDS * 4));
+        cofhe_hip_ctx::FixedBase *fb = nullptr;
+        if (int rc = fixed_base_chain(ctx, base_record, ++ctx->fb_clock, st, &fb)) return rc;
+        HIPCHK(hipMemcpy2DAsync(hit->d, (size_t)D * REC_WORDS * 4, fb->d_table, (size_t)w * REC_WORDS * 4, REC_WORDS * 4, npos,
+                                hipMemcpyDeviceToDevice, st));
+        for (uint32_t half = 1; half < D; half *= 2) {
+            unsigned blocks;
+            if (int rc = compose_blocks((uint64_t)npos * half, &blocks)) return rc;
+            ProfScope ps(ctx, "k_comb_table", st);
+            hipLaunchKernelGGL(k_comb_table, dim3(blocks), dim3(WG_BLOCK), 0, st, hit->d, npos, w, half, (const uint32_t *)ctx->d_absdelta,
+                               ctx->half_dbits, ctx->d_status);
+        }
+        HIPCHK(hipGetLastError());
+        memcpy(hit->base, base_record, REC_WORDS * 4);
+        hit->w = w;
+    }
+    hit->stamp = call_stamp;
+    *out = hit->d;
+    return COFHE_HIP_OK;
+}
+
+// kind 0: out[i] = base0^r[i] (n records); 1: out[2i] = h^r[i], out[2i+1] = pk^r[i] o f^(m[i] mod 2^k); 2: out[2i] =
+// leaf[2i] o h^r[i], out[2i+1] = leaf[2i+1] o pk^r[i].  bases: host records of (base0 | h, pk, f) as the kind needs.
+int comb_run(cofhe_hip_ctx *ctx, uint32_t kind, const uint32_t *const bases[3], const void *d_r, const void *d_m, const void *d_leaf,
+             void *d_out, uint64_t n, uint32_t kbits, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    for (int b = 0; b < (kind == 0 ? 1 : kind == 1 ? 3 : 2); b++)
+        if (!bases[b]) return fail(COFHE_HIP_EINVAL, "null argument");
+    if (int rc = comb_check(kind, n, 0, kbits, 0, 0)) return rc;
+    if (n == 0) return COFHE_HIP_OK;
+    if (!d_r || !d_out || (kind == 1 && !d_m) || (kind == 2 && !d_leaf)) return fail(COFHE_HIP_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    WsUse use(ctx, st);
+    const CombState &cs = comb_state(ctx);
+    // the tree's shape follows the longest exponent: the one read-back of the call
+    uint32_t exp_bits = 0;
+    {
+        uint32_t *d_mb = ctx->d_flags + (ctx->flag_next++ % cofhe_hip_ctx::N_FLAGS);
+        HIPCHK(hipMemsetAsync(d_mb, 0, 4, st));
+        hipLaunchKernelGGL(k_exp_maxbits, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t *)d_r, n, d_mb);
+        HIPCHK(hipMemcpyAsync(&exp_bits, d_mb, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    const CombCall cc = comb_call(kind, n, exp_bits, kbits, cs.opt_width, cs.opt_chunk);
+    const uint64_t call_stamp = ++comb_state(ctx).clock;
+    const uint32_t *tabs[3] = {nullptr, nullptr, nullptr};
+    for (int b = 0; b < (kind == 0 ? 1 : kind == 1 ? 3 : 2); b++)
+        if (int rc = comb_table(ctx, bases[b], cc.s.w, call_stamp, st, &tabs[b])) return rc;
+    const WsPlan wp = plan_comb_chunk(cc.s, cc.chunk);
+    if (int rc = ensure_workspace(ctx, wp.total, st)) return rc;
+    uint8_t *ws = (uint8_t *)ctx->workspace;
+    uint32_t *buf[2] = {(uint32_t *)(ws + wp.off("level_a")), (uint32_t *)(ws + wp.off("level_b"))};
+    const uint32_t H = cc.s.halves;
+    for (uint64_t e0 = 0; e0 < n; e0 += cc.chunk) {
+        const uint64_t ne = n - e0 < cc.chunk ? n - e0 : cc.chunk, ncols = ne * H;
+        uint32_t *out = (uint32_t *)d_out + e0 * H * REC_WORDS;
+        uint32_t mm = cc.slots / 2;
+        unsigned blocks;
+        if (int rc = compose_blocks(ncols * mm, &blocks)) return rc;
+        {
+            ProfScope ps(ctx, "k_comb_first", st);
+            hipLaunchKernelGGL(k_comb_first, dim3(blocks), dim3(WG_BLOCK), 0, st, cc.s, tabs[0], tabs[1], tabs[2],
+                               (const uint32_t *)d_r + e0 * EXP_REC_WORDS, d_m ? (const uint32_t *)d_m + e0 * EXP_REC_WORDS : nullptr,
+                               d_leaf ? (const uint32_t *)d_leaf + e0 * H * REC_WORDS : nullptr, ncols, (const uint32_t *)ctx->d_one,
+                               mm == 1 ? out : buf[0], (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+        }
+        int which = 0;
+        while (mm > 1) {
+            const uint32_t mh = (mm + 1) / 2;
+            if (int rc = compose_blocks((uint64_t)mh * ncols, &blocks)) return rc;
+            ProfScope ps(ctx, "k_compose_pairs", st);
+            hipLaunchKernelGGL(k_compose_pairs, dim3(blocks), dim3(WG_BLOCK), 0, st, (const uint32_t *)buf[which], (const uint32_t *)ctx->d_one,
+                               mh == 1 ? out : buf[which ^ 1], 1u, mm, (uint32_t)ncols, 0u, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits,
+                               ctx->d_status);
+            which ^= 1;
+            mm = mh;
+        }
+        HIPCHK(hipGetLastError());
+    }
+    return COFHE_HIP_OK;
+}
+}  // namespace
+
+int cofhe_hip_pow_fixed_base_many_records(cofhe_hip_ctx *ctx, const uint32_t *base_record, const void *d_exps, void *d_out, uint64_t n,
+                                          void *stream) {
+    const uint32_t *bases[3] = {base_record, nullptr, nullptr};
+    return comb_run(ctx, 0, bases, d_exps, nullptr, nullptr, d_out, n, 0, stream);
+}
+int cofhe_hip_encrypt_fresh_records(cofhe_hip_ctx *ctx, const void *d_plain, const void *d_r, const uint32_t *h_record, const uint32_t *pk_record,
+                                    const uint32_t *f_record, void *d_out, uint64_t n_ct, uint32_t kbits, void *stream) {
+    const uint32_t *bases[3] = {h_record, pk_record, f_record};
+    return comb_run(ctx, 1, bases, d_r, d_plain, nullptr, d_out, n_ct, kbits, stream);
+}
+int cofhe_hip_rerandomize_records(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_r, const uint32_t *h_record, const uint32_t *pk_record,
+                                  void *d_out, uint64_t n_ct, void *stream) {
+    const uint32_t *bases[3] = {h_record, pk_record, nullptr};
+    return comb_run(ctx, 2, bases, d_r, nullptr, d_cts, d_out, n_ct, 0, stream);
+}
+int cofhe_hip_comb_shape(uint32_t kind, uint64_t n, uint32_t exp_bits, uint32_t kbits, uint32_t w_pin, uint64_t chunk_pin, uint32_t *w,
+                         uint32_t *slots, uint64_t *chunk) {
+    if (!w || !slots || !chunk) return fail(COFHE_HIP_EINVAL, "null argument");
+    if (int rc = comb_check(kind, n, exp_bits, kbits, w_pin, chunk_pin)) return rc;
+    const CombCall cc = comb_call(kind, n, exp_bits, kbits, w_pin, chunk_pin);
+    *w = cc.s.w;
+    *slots = cc.slots;
+    *chunk = cc.chunk;
+    return COFHE_HIP_OK;
 }
 
 namespace {
@@ -1298,6 +1540,11 @@ int cofhe_hip_workspace_plan(const char *op, const uint64_t *args, uint32_t n_ar
         p = plan_encrypt_chunk(args[0], (uint32_t)args[1]);
     } else if (o == "fixed_base" && need(2)) {
         p = plan_fixed_base((uint32_t)args[0], (uint32_t)args[1]);
+    } else if (o == "comb" && need(6)) {
+        // kind, n items, exp_bits, kbits, w (0: automatic), chunk (0: automatic): the regions of one (the largest) chunk
+        if (int rc = comb_check(args[0], args[1], args[2], args[3], args[4], args[5])) return rc;
+        const CombCall cc = comb_call((uint32_t)args[0], args[1], (uint32_t)args[2], (uint32_t)args[3], (uint32_t)args[4], args[5]);
+        p = plan_comb_chunk(cc.s, cc.chunk);
     } else {
         return fail(COFHE_HIP_EINVAL, "unknown workspace plan or wrong argument count: " + o);
     }

@@ -1,10 +1,12 @@
 // kernels.hpp -- one declaration of every kernel that abi.hip launches.  The definitions, with their
 // __launch_bounds__, are in cofhe_hip.hip (the throughput kernels, in three COFHE_PART passes) and wide.hip
 // (the latency kernels); wire.hip launches its own kernels.  A declaration that matches no definition is an
-// undefined symbol when the library is loaded (tests/test_cabi.py).
+// undefined symbol when the library is loaded (tests/test_cabi.py).  comb.hip holds the two kernels of the fixed-base comb.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "comb.hpp"
 
 namespace cofhe_k {
 
@@ -103,4 +105,12 @@ __global__ void k_pow_shared_pair(const uint32_t *__restrict__ base, const int8_
                                   uint32_t *__restrict__ status);
 __global__ void k_square_chain_wide(const uint32_t *__restrict__ base, uint32_t *__restrict__ table, uint32_t len,
                                     const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status);
+
+// the fixed-base comb (comb.hip, comb.hpp): one level of a table, and the gather fused with the first tree level
+__global__ void k_comb_table(uint32_t *__restrict__ table, uint32_t npos, uint32_t w, uint32_t half, const uint32_t *__restrict__ absdelta,
+                             int half_dbits, uint32_t *__restrict__ status);
+__global__ void k_comb_first(cofhe::CombShape s, const uint32_t *__restrict__ tab0, const uint32_t *__restrict__ tab1,
+                             const uint32_t *__restrict__ tabf, const uint32_t *__restrict__ r_exps, const uint32_t *__restrict__ m_exps,
+                             const uint32_t *__restrict__ leaf, uint64_t ncols, const uint32_t *__restrict__ one_rec, uint32_t *__restrict__ out,
+                             const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status);
 }  // namespace cofhe_k

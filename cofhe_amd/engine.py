@@ -251,6 +251,30 @@ class Engine:
                                               f.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(d_out),
                                               C.c_uint64(n_ciphertexts), C.c_uint32(kbits), C.c_void_p(stream)))
 
+    def pow_fixed_base_many_records(self, base_record, d_exps, d_out, n, stream=0):
+        """out[i] = base^e[i] by the fixed-base comb: base_record a host uint32[168], d_exps n exponent records, d_out n records"""
+        import numpy as np
+        b = np.ascontiguousarray(base_record, dtype=np.uint32)
+        assert b.size == 168
+        _chk(self.L.cofhe_hip_pow_fixed_base_many_records(self.ctx, b.ctypes.data_as(C.c_void_p), C.c_void_p(d_exps), C.c_void_p(d_out),
+                                                          C.c_uint64(n), C.c_void_p(stream)))
+
+    def encrypt_fresh_records(self, d_plain, d_r, h_record, pk_record, f_record, d_out, n_ciphertexts, kbits, stream=0):
+        """out[i] = (h^r_i, pk^r_i o f^(m_i mod 2^k)): one r per ciphertext (d_r: n exponent records); h, pk, f host records"""
+        import numpy as np
+        recs = [np.ascontiguousarray(x, dtype=np.uint32) for x in (h_record, pk_record, f_record)]
+        assert all(x.size == 168 for x in recs)
+        _chk(self.L.cofhe_hip_encrypt_fresh_records(self.ctx, C.c_void_p(d_plain), C.c_void_p(d_r), *[x.ctypes.data_as(C.c_void_p) for x in recs],
+                                                    C.c_void_p(d_out), C.c_uint64(n_ciphertexts), C.c_uint32(kbits), C.c_void_p(stream)))
+
+    def rerandomize_records(self, d_cts, d_r, h_record, pk_record, d_out, n_ciphertexts, stream=0):
+        """out[i] = (c1_i o h^r_i, c2_i o pk^r_i); d_out may be d_cts"""
+        import numpy as np
+        recs = [np.ascontiguousarray(x, dtype=np.uint32) for x in (h_record, pk_record)]
+        assert all(x.size == 168 for x in recs)
+        _chk(self.L.cofhe_hip_rerandomize_records(self.ctx, C.c_void_p(d_cts), C.c_void_p(d_r), *[x.ctypes.data_as(C.c_void_p) for x in recs],
+                                                  C.c_void_p(d_out), C.c_uint64(n_ciphertexts), C.c_void_p(stream)))
+
     def part_decrypt_records(self, d_cts, d_share, d_out, n_ciphertexts, stream=0):
         """d_out: n form records = c1^share"""
         _chk(self.L.cofhe_hip_part_decrypt_records(self.ctx, C.c_void_p(d_cts), C.c_void_p(d_share), C.c_void_p(d_out),
@@ -385,6 +409,19 @@ def workspace_plan(op: str, *args):
     a = (C.c_uint64 * max(1, len(args)))(*[int(x) for x in args])
     _chk(L.cofhe_hip_workspace_plan(op.encode(), a, C.c_uint32(len(args)), regs, C.c_uint32(8), C.byref(n), C.byref(total)))
     return [(regs[i].name.decode(), int(regs[i].offset), int(regs[i].bytes)) for i in range(n.value)], int(total.value)
+
+
+COMB_POWERS, COMB_ENCRYPT, COMB_RERANDOMIZE = 0, 1, 2
+
+
+def comb_shape(kind: int, n: int, exp_bits: int, kbits: int = 0, w: int = 0, chunk: int = 0):
+    """cofhe_hip_comb_shape (host only): (w, slots per output record, items per pass) the comb launcher takes for n items of
+    `kind` whose longest exponent has exp_bits bits; w / chunk pin the "comb_width" / "comb_chunk" options (0: automatic)"""
+    L = load_library()
+    ow, sl, ch = C.c_uint32(), C.c_uint32(), C.c_uint64()
+    _chk(L.cofhe_hip_comb_shape(C.c_uint32(kind), C.c_uint64(n), C.c_uint32(exp_bits), C.c_uint32(kbits), C.c_uint32(w), C.c_uint64(chunk),
+                                C.byref(ow), C.byref(sl), C.byref(ch)))
+    return int(ow.value), int(sl.value), int(ch.value)
 
 
 def gather_plan(n_rows: int, row_bytes: int, world: int):

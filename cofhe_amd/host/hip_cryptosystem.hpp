@@ -223,6 +223,12 @@ class CipherText {
 };
 
 enum class Precision { FP32, FP64 };
+// Randomness of the tensor operations.  None (the default): encrypt_tensor draws ONE r per call, as the reference does
+// (tensor_ops.inl:1-19), and the tensor operations are deterministic.  PerElement: every ciphertext that encrypt_tensor,
+// add_ciphertext_tensors, scal_ciphertext_tensors or negate_ciphertext_tensor returns carries its own fresh r -- the
+// reference's compiled-out ADD_RANDOMNESS_IN_HOMOMORPHIC_OPERATIONS + DIFFERENT_RANDOMNESS_FOR_EACH_OPERATION mode
+// (cpu_cryptosystem_vector_ops.inl:1-2).  With one r per tensor, c2_i o c2_j^-1 = f^(m_i - m_j) leaks every plaintext difference.
+enum class TensorRandomness { None, PerElement };
 enum class SecurityLevel { LOW, MEDIUM, HIGH };
 
 // ---- the engine -----------------------------------------------------------------------------
@@ -289,7 +295,8 @@ class HIPCryptoSystem {
     }
     HIPCryptoSystem(const HIPCryptoSystem &o)
         : sec_level_(o.sec_level_), k_(o.k_), device_(o.device_), N_(o.N_), deltaK_(o.deltaK_), delta_(o.delta_),
-          f_(o.f_), h_(o.h_), exponent_bound_(o.exponent_bound_), rerandomize_(o.rerandomize_) {
+          f_(o.f_), h_(o.h_), exponent_bound_(o.exponent_bound_), rerandomize_(o.rerandomize_),
+          tensor_randomness_(o.tensor_randomness_) {
         gmp_randinit_mt(rng_);
         gmp_randseed_ui(rng_, std::random_device{}());     // a copy draws fresh randomness (hpp:37-40)
         open_device();
@@ -411,6 +418,7 @@ class HIPCryptoSystem {
         return out;
     }
     Tensor<CipherText *> encrypt_tensor(const PublicKey &pk, const Tensor<PlainText *> &pts) const {
+        if (tensor_randomness_ == TensorRandomness::PerElement) return encrypt_tensor_fresh(pk, pts);
         Mpz r;
         {
             std::lock_guard<std::mutex> lk(rng_mutex_);      // the object is shared between server threads
@@ -626,6 +634,7 @@ class HIPCryptoSystem {
             throw std::invalid_argument("Tensor shapes must be equal");
         DeviceTensor a = upload(ct1), b = upload(ct2);
         DeviceTensor r = add_ciphertext_tensors(a, b);
+        rerandomize_result(pk, r);
         return download(std::move(r));
     }
     // Scalar forms.  The reference re-randomises their result with a fresh r (hsm2k.add_ciphertexts / scal_ciphertexts
@@ -633,6 +642,21 @@ class HIPCryptoSystem {
     // (c1 h^r, c2 pk^r).  Same here by default; set_rerandomize(false) gives the bare composition / power, which is
     // what a byte-for-byte parity check needs (the tensor forms the reference benchmarks are deterministic anyway).
     void set_rerandomize(bool on) { rerandomize_ = on; }
+    // TensorRandomness::PerElement: fresh r per ciphertext for encrypt_tensor and the outputs of the tensor operations
+    void set_tensor_randomness(TensorRandomness mode) { tensor_randomness_ = mode; }
+    TensorRandomness tensor_randomness() const { return tensor_randomness_; }
+    // (c1_i o h^r_i, c2_i o pk^r_i) with a fresh r_i < exponent_bound per element: what a tensor needs before it leaves the
+    // process, whatever the mode (one batched comb call, cofhe_hip_rerandomize_records)
+    Tensor<CipherText *> rerandomize_ciphertext_tensor(const PublicKey &pk, const Tensor<CipherText *> &cts) const {
+        if (cts.is_zero_degree()) {
+            Tensor<CipherText *> r = rerandomize_ciphertext_tensor(pk, Tensor<CipherText *>(1, cts.get_value()));
+            return Tensor<CipherText *>(r.at(0));
+        }
+        DeviceTensor in = upload(cts);
+        DeviceTensor out = alloc(cts.shape(), cts.num_elements());
+        rerandomize_into(pk, in, out);
+        return download(std::move(out));
+    }
     // The device status word is sticky: once a kernel has hit a safety cap (an operand that was not a reduced form of this
     // discriminant), every read of results of this cryptosystem throws until its owner acknowledges the fault here.
     // Returns the word that was set.
@@ -669,6 +693,7 @@ class HIPCryptoSystem {
             if (s.shape()[0] != cts.shape()[0]) throw std::invalid_argument("Vector sizes must be equal");
             DeviceTensor out = alloc(cts.shape(), cts.num_elements());
             check(cofhe_hip_pow_records(ctx_, dc.ptr_, dex, out.ptr_, cts.num_elements(), nullptr));
+            rerandomize_result(pk, out);
             return download(std::move(out));
         }
         if (s.ndim() != 2 || cts.ndim() != 2) throw std::invalid_argument("Tensors must be 0D, 1D or 2D for now");
@@ -684,6 +709,7 @@ class HIPCryptoSystem {
         DeviceTensor out = alloc({n, p}, n * p);
         check(cofhe_hip_scal_matmul_records(ctx_, dc.ptr_, dex, dz.ptr_, out.ptr_, (uint32_t)n, (uint32_t)m, (uint32_t)p,
                                             nullptr));
+        rerandomize_result(pk, out);           // one fresh r per output (the reference's branch reuses one per row)
         return download(std::move(out));
     }
 
@@ -1096,6 +1122,52 @@ class HIPCryptoSystem {
         return CipherText(r[0], r[1]);
     }
     bool rerandomize_ = true;
+    TensorRandomness tensor_randomness_ = TensorRandomness::None;
+    // n exponent records of r_i, uniform below exponent_bound
+    std::vector<uint32_t> draw_randomness(size_t n) const {
+        std::vector<uint32_t> ex(n * EXPW, 0);
+        Mpz r;
+        std::lock_guard<std::mutex> lk(rng_mutex_);
+        for (size_t i = 0; i < n; i++) {
+            mpz_urandomm(r.get(), rng_, exponent_bound_.get());
+            pack_exponent(r, &ex[i * EXPW]);
+        }
+        return ex;
+    }
+    void rerandomize_into(const PublicKey &pk, const DeviceTensor &in, DeviceTensor &out) const {
+        if (in.n_ == 0) return;
+        std::vector<uint32_t> ex = draw_randomness(in.n_), hrec(REC, 0), pkrec(REC, 0);
+        pack_form(h_, hrec.data());
+        pack_form(pk, pkrec.data());
+        void *dr = nullptr;
+        check(cofhe_hip_malloc(ctx_, ex.size() * 4, &dr)); Guard g1{ctx_, dr};
+        check(cofhe_hip_upload(ctx_, dr, ex.data(), ex.size() * 4, nullptr));
+        check(cofhe_hip_rerandomize_records(ctx_, in.ptr_, dr, hrec.data(), pkrec.data(), out.ptr_, in.n_, nullptr));
+        check(cofhe_hip_stream_sync(ctx_, nullptr));          // `ex` goes with this frame
+    }
+    // a result of this object (its own block, nobody else's view) re-randomised in place in PerElement mode
+    void rerandomize_result(const PublicKey &pk, DeviceTensor &t) const {
+        if (tensor_randomness_ == TensorRandomness::PerElement) rerandomize_into(pk, t, t);
+    }
+    Tensor<CipherText *> encrypt_tensor_fresh(const PublicKey &pk, const Tensor<PlainText *> &pts) const {
+        const size_t E = pts.num_elements();
+        std::vector<uint32_t> ex = draw_randomness(E), plain(E * EXPW, 0), hrec(REC, 0), pkrec(REC, 0), frec(REC, 0);
+        Tensor<PlainText *> pflat = pts;
+        if (!pts.is_zero_degree()) pflat.flatten();
+        for (size_t i = 0; i < E; i++) pack_exponent(*pflat[i], &plain[i * EXPW]);
+        pack_form(h_, hrec.data());
+        pack_form(pk, pkrec.data());
+        pack_form(f_, frec.data());
+        void *dr = nullptr, *dpl = nullptr;
+        check(cofhe_hip_malloc(ctx_, ex.size() * 4 + 4, &dr)); Guard g1{ctx_, dr};
+        check(cofhe_hip_malloc(ctx_, plain.size() * 4 + 4, &dpl)); Guard g2{ctx_, dpl};
+        check(cofhe_hip_upload(ctx_, dr, ex.data(), ex.size() * 4, nullptr));
+        check(cofhe_hip_upload(ctx_, dpl, plain.data(), plain.size() * 4, nullptr));
+        DeviceTensor out = alloc(pts.is_zero_degree() ? std::vector<size_t>{1} : pts.shape(), E);
+        check(cofhe_hip_encrypt_fresh_records(ctx_, dpl, dr, hrec.data(), pkrec.data(), frec.data(), out.ptr_, E, k_, nullptr));
+        check(cofhe_hip_stream_sync(ctx_, nullptr));
+        return download(std::move(out));
+    }
     struct Guard {
         cofhe_hip_ctx *ctx;
         void *p;

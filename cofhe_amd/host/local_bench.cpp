@@ -18,6 +18,8 @@
 #include <iostream>
 #include <memory>
 #include <numeric>
+#include <set>
+#include <string>
 #include <thread>
 #include <utility>
 
@@ -287,6 +289,76 @@ static void bench_encrypt_decrypt(size_t n, size_t m) {
     std::cout << "  roundtrip and homomorphic checks: " << (ok ? "ok" : "FAILED") << std::endl;
     std::cout << "n: " << n << " m: " << m << std::endl;
     if (!ok) throw std::runtime_error("decryption mismatch");
+}
+
+// fresh randomness per element (TensorRandomness::PerElement): encrypt_tensor gives every ciphertext its own r, the tensor
+// operations re-randomise their outputs, rerandomize_ciphertext_tensor does it on request; everything decrypts as before
+static void bench_fresh_randomness(size_t n) {
+    auto cs = make_cryptosystem(128, 128, Device::GPU);
+    using CS = decltype(cs);
+    auto sk = cs.keygen();
+    auto pk = cs.keygen(sk);
+    Tensor<CS::PlainText *> pts(n, nullptr);
+    std::vector<float> want(n);
+    for (size_t i = 0; i < n; i++) {
+        want[i] = (float)((long)i - (long)(n / 2));
+        pts.at(i) = new CS::PlainText(cs.make_plaintext(want[i]));
+    }
+    bool ok = true;
+    auto c1_text = [](const CS::CipherText &c) { return c.c1().a().str() + " " + c.c1().b().str(); };
+    auto distinct_c1 = [&](const Tensor<CS::CipherText *> &t) {
+        std::set<std::string> seen;
+        for (size_t i = 0; i < t.num_elements(); i++) seen.insert(c1_text(*t[i]));
+        return seen.size() == t.num_elements();
+    };
+    auto decrypts_to = [&](const Tensor<CS::CipherText *> &t, float factor) {
+        auto res = cs.decrypt_tensor(sk, t);
+        bool good = true;
+        for (size_t i = 0; i < n; i++) {
+            if (cs.get_float_from_plaintext(*res.at(i)) != factor * want[i]) good = false;
+            delete res.at(i);
+        }
+        return good;
+    };
+    auto shared = cs.encrypt_tensor(pk, pts);                 // default mode: one r for the tensor
+    cs.synchronize();
+    for (size_t i = 1; i < n; i++)
+        if (c1_text(*shared[i]) != c1_text(*shared[0])) ok = false;
+    cs.set_tensor_randomness(TensorRandomness::PerElement);
+    auto t0 = Clock::now();
+    auto ct = cs.encrypt_tensor(pk, pts);
+    cs.synchronize();
+    const double enc_ms = std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
+    const bool enc_distinct = distinct_c1(ct), enc_dec = decrypts_to(ct, 1.0f);
+    auto sum = cs.add_ciphertext_tensors(pk, ct, ct);
+    Tensor<CS::PlainText *> three(n, nullptr);
+    CS::PlainText p3 = cs.make_plaintext(3);
+    for (size_t i = 0; i < n; i++) three.at(i) = &p3;
+    auto tri = cs.scal_ciphertext_tensors(pk, three, ct);
+    auto neg = cs.negate_ciphertext_tensor(pk, ct);
+    t0 = Clock::now();
+    auto rr = cs.rerandomize_ciphertext_tensor(pk, shared);
+    cs.synchronize();
+    const double rr_ms = std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
+    const bool ops_distinct = distinct_c1(sum) && distinct_c1(tri) && distinct_c1(neg) && distinct_c1(rr);
+    const bool ops_dec = decrypts_to(sum, 2.0f) && decrypts_to(tri, 3.0f) && decrypts_to(neg, -1.0f) && decrypts_to(rr, 1.0f);
+    ok = ok && enc_distinct && enc_dec && ops_distinct && ops_dec;
+    std::ofstream("local_bench_fresh_ct.bin", std::ios::binary) << cs.serialize_ciphertext_tensor(ct);
+    std::ofstream("local_bench_fresh_rerand.bin", std::ios::binary) << cs.serialize_ciphertext_tensor(rr);
+    {
+        Mpz ad = cs.discriminant();
+        ad.neg();
+        std::ofstream("local_bench_absdelta.txt") << ad.str() << "\n";
+    }
+    std::cout << "  per-element encrypt_tensor: " << enc_ms << " ms, rerandomize_ciphertext_tensor: " << rr_ms << " ms (" << n
+              << " ciphertexts)" << std::endl;
+    std::cout << "  distinct c1: encrypt " << (enc_distinct ? "yes" : "NO") << ", add / scal / negate / rerandomize "
+              << (ops_distinct ? "yes" : "NO") << "; decryption: encrypt " << (enc_dec ? "yes" : "NO") << ", ops " << (ops_dec ? "yes" : "NO")
+              << std::endl;
+    std::cout << "  agree: " << (ok ? "yes" : "NO") << std::endl;
+    for (auto *t : {&shared, &ct, &sum, &tri, &neg, &rr}) free_all(*t);
+    free_all(pts);
+    if (!ok) throw std::runtime_error("fresh randomness check failed");
 }
 
 // threshold decryption end to end (the reference has no local benchmark for it; the calls are the
@@ -570,7 +642,7 @@ static void plaintexts_mode(const char *in, const char *out) {
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        std::cerr << "Usage: " << argv[0] << " <encrypt_decrypt|ciphertext_matadd|scal_matmul|threshold|ciphertext_matmul> [sizes]" << std::endl;
+        std::cerr << "Usage: " << argv[0] << " <encrypt_decrypt|ciphertext_matadd|scal_matmul|threshold|ciphertext_matmul|fresh_randomness> [sizes]" << std::endl;
         return 1;
     }
     std::string mode = argv[1];
@@ -594,6 +666,8 @@ int main(int argc, char **argv) {
         } else if (mode == "plaintexts") {
             if (argc < 4) throw std::invalid_argument("plaintexts <in> <out>");
             plaintexts_mode(argv[2], argv[3]);
+        } else if (mode == "fresh_randomness") {
+            bench_fresh_randomness(argc > 2 ? std::stoul(argv[2]) : 256);
         } else if (mode == "formats") {
             bench_formats();
         } else if (mode == "threads") {

@@ -83,6 +83,8 @@ int cofhe_hip_trim(cofhe_hip_ctx *ctx, size_t keep_bytes);
  *                      wherever its encoding allows (at most 2^21 non-empty (bit position, column) segments; beyond that the
  *                      chains run); 0: lockstep chains (the form of rounds 1-3)
  *   "matmul_segments"  >= 1: pieces the inner dimension is cut into when the product has few outputs
+ *   "comb_width"       2..10: window width of the fixed-base comb (cofhe_hip_pow_fixed_base_many_records and kin)
+ *   "comb_chunk"       >= 1: items per pass of the comb (capped where the 4 GiB workspace bound needs it)
  *   "profile_kernels"  != 0: cofhe_hip_scal_matmul_records brackets each of its kernels with HIP events on the launch
  *                      stream; cofhe_hip_profile_read(ctx, "k_tree_level" | "k_scal_matmul_wnaf" | "k_pow_table" | "k_wnaf_digits", ...)
  *                      waits for them and returns the summed duration and the launch count (clear != 0 drops all spans).
@@ -172,6 +174,38 @@ int cofhe_hip_pow_fixed_base_records(cofhe_hip_ctx *ctx, uint32_t n, const uint3
  * cpu_cryptosystem_tensor_ops.inl:1-19 (one r per tensor, element i = CipherText(hsm2k, m_i, c1, pkr)). */
 int cofhe_hip_encrypt_records(cofhe_hip_ctx *ctx, const void *d_plain, const void *d_c1_pkr, const uint32_t *f_record,
                               void *d_out, uint64_t n_ciphertexts, uint32_t kbits, void *stream);
+/* ---- fresh randomness per element: the fixed-base comb (cofhe_amd/csrc/comb.hpp) ----
+ * A tensor that encrypt_tensor makes shares ONE r (cpu_cryptosystem_tensor_ops.inl:1-19): c2_i o c2_j^-1 = f^(m_i - m_j), and
+ * discrete logarithms in <f> are public, so the ciphertexts alone give every plaintext difference mod 2^k.  These entry
+ * points give each ciphertext its own r -- the reference's ADD_RANDOMNESS_IN_HOMOMORPHIC_OPERATIONS /
+ * DIFFERENT_RANDOMNESS_FOR_EACH_OPERATION branches (cpu_cryptosystem_vector_ops.inl:1-2, tensor_ops.inl:142-162, 212-240,
+ * 287-310, 357-375, 431-460), which are compiled out there.  Each power is a product of ~floor(bits/w) + 1 entries of a
+ * table T[j][d] = base^(d 2^(wj)) (signed Booth digits, no squarings), cached per (base, w) in the context (w = 8: 10.8 MB;
+ * first use of a base: its chain of ~1000 squarings plus w - 1 table levels).  Exponents and plaintexts are exponent
+ * records on the device, signs honoured; r = 0 gives the principal form; n = 0 does nothing.  The caller supplies the
+ * randomness (r_i < exponent_bound), as for cofhe_hip_encrypt_records.  Options "comb_width" (2..10) and "comb_chunk"
+ * (items per pass) pin the launcher's choices; the results do not depend on them.  Each call synchronises `stream` once
+ * (the longest exponent sizes the tree: a 4-byte read-back), and its workspace stays within 4 GiB for any n.
+ * With "profile_kernels" on, every launch records a span: "k_comb_table" (w - 1 per table built), "k_comb_first" (one per
+ * chunk) and "k_compose_pairs" (the levels above). */
+/* out[i] = base^e[i]: n exponent records on the device, one HOST base record (any reduced form).  Reference: the nupow of
+ * h^r_i and pk^r_i in the branches above (tensor_ops.inl:223-226 asks for exactly this batch). */
+int cofhe_hip_pow_fixed_base_many_records(cofhe_hip_ctx *ctx, const uint32_t *base_record, const void *d_exps, void *d_out, uint64_t n,
+                                          void *stream);
+/* out[i] = (h^r[i], pk^r[i] o f^(m[i] mod 2^k)): encryption with its own randomness per element.  h, pk, f: HOST records.
+ * Reference: encrypt_tensor, cpu_cryptosystem_tensor_ops.inl:1-19, with one r per element instead of one per call. */
+int cofhe_hip_encrypt_fresh_records(cofhe_hip_ctx *ctx, const void *d_plain, const void *d_r, const uint32_t *h_record,
+                                    const uint32_t *pk_record, const uint32_t *f_record, void *d_out, uint64_t n_ciphertexts,
+                                    uint32_t kbits, void *stream);
+/* out[i] = (c1[i] o h^r[i], c2[i] o pk^r[i]): re-randomisation (an encryption of 0 added); d_out may equal d_cts.
+ * Reference: the re-randomised outputs of add / scal / negate, tensor_ops.inl:142-162, 212-240, 287-310, 357-375, 431-460. */
+int cofhe_hip_rerandomize_records(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_r, const uint32_t *h_record,
+                                  const uint32_t *pk_record, void *d_out, uint64_t n_ciphertexts, void *stream);
+/* The comb launcher's decisions as data (host only, no GPU): for kind 0 (powers), 1 (fresh encryption) or 2
+ * (re-randomisation) of n items whose longest exponent has exp_bits bits, with the "comb_width" / "comb_chunk" pins
+ * w_pin / chunk_pin (0 = automatic): the window width, the slots (tree leaves) of one output record and the items per pass. */
+int cofhe_hip_comb_shape(uint32_t kind, uint64_t n, uint32_t exp_bits, uint32_t kbits, uint32_t w_pin, uint64_t chunk_pin, uint32_t *w,
+                         uint32_t *slots, uint64_t *chunk);
 /* threshold decryption, party side: out[e] = c1[e] ^ share (one form record per ciphertext; d_share: one
  * exponent record on the device).  Reference: partDecrypt, cpu_cryptosystem_distributed.inl:259-269, looped
  * by part_decrypt_tensor, cpu_cryptosystem_tensor_ops.inl:35-48. */
@@ -199,6 +233,8 @@ int cofhe_hip_time_compose(cofhe_hip_ctx *ctx, const void *d_a, const void *d_b,
  *      "accumulate_tree"  args: n, m, p
  *      "encrypt_chunk"    args: n_elements, kbits
  *      "fixed_base"       args: n_powers, max_entries
+ *      "comb"             args: kind, n_items, exp_bits, kbits, w, chunk   (the comb entry points above; w, chunk: 0 = automatic;
+ *                         the regions of one pass over the largest chunk, cofhe_hip_comb_shape gives its size)
  * regions[i] = name, byte offset, byte count, in workspace order; *total_bytes = what ensure_workspace is asked for. */
 typedef struct {
     char name[24];
