@@ -1,11 +1,13 @@
-// abi.hip -- the C ABI of include/cofhe_hip.h: the context, the block cache, the workspace plans, the kernel
-// launchers and the host-side tensor formats.  The kernels it launches are declared in kernels.hpp and defined in
-// cofhe_hip.hip and wide.hip; this file holds no device code of its own.
+// abi.hip -- the C ABI of include/cofhe_hip.h, in this order: the context, the block cache, the launch helpers (spans, the
+// two-build launch, flag words, the table-cache lookup), the workspace plans, the launchers (one launch site per kernel and
+// route; product_tree is the pairwise tree of them all) and the host-side tensor formats.  The kernels are declared in
+// kernels.hpp and defined in cofhe_hip.hip, wide.hip and comb.hip; this file holds no device code of its own.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -19,62 +21,10 @@ using namespace cofhe_k;
 
 namespace {
 
-// ---- little-endian byte strings <-> limb records (host) ------------------------------------
-struct IntView {
-    const uint8_t *p;
-    size_t n;
-    bool neg;
-};
-
+// ---- little-endian limb strings (host): the context reads its discriminant with these, the formats section its tensors
 size_t sig_bytes(const uint8_t *p, size_t n) {
     while (n > 0 && p[n - 1] == 0) n--;
     return n;
-}
-
-int parse_tensor(const uint8_t *bytes, size_t len, size_t per_elem, uint32_t *ndim, uint32_t shape[8],
-                 std::vector<IntView> &ints) {
-    if (len < 4) return fail(COFHE_HIP_EINVAL, "tensor buffer too short");
-    uint32_t nd;
-    memcpy(&nd, bytes, 4);
-    if (nd > 8) return fail(COFHE_HIP_EINVAL, "tensor rank above 8");
-    if (len < 4 + 4ull * nd) return fail(COFHE_HIP_EINVAL, "tensor buffer too short");
-    uint64_t ne = 1;
-    for (uint32_t i = 0; i < nd; i++) {
-        memcpy(&shape[i], bytes + 4 + 4 * i, 4);
-        if (shape[i] != 0 && ne > (1ull << 40) / shape[i]) return fail(COFHE_HIP_EINVAL, "tensor too large");     // before the product can wrap
-        ne *= shape[i];
-    }
-    *ndim = nd;
-    const uint64_t cnt = ne * per_elem;
-    const size_t hdr = 4 + 4ull * nd + 8ull * cnt;
-    if (len < hdr) return fail(COFHE_HIP_EINVAL, "tensor buffer too short");
-    const uint8_t *tab = bytes + 4 + 4ull * nd;
-    const uint8_t *body = bytes + hdr;
-    const size_t blen = len - hdr;
-    ints.resize(cnt);
-    const uint64_t M = ~(1ull << 63);
-    for (uint64_t i = 0; i < cnt; i++) {
-        uint64_t o, o2;
-        memcpy(&o, tab + 8 * i, 8);
-        if (i + 1 < cnt) {
-            memcpy(&o2, tab + 8 * (i + 1), 8);
-            o2 &= M;
-        } else {
-            o2 = blen;
-        }
-        const uint64_t st = o & M;
-        if (o2 < st || o2 > blen) return fail(COFHE_HIP_EINVAL, "corrupt offset table");
-        ints[i] = IntView{body + st, (size_t)(o2 - st), (o >> 63) != 0};
-    }
-    return COFHE_HIP_OK;
-}
-
-bool put_limbs(uint32_t *dst, int words, const IntView &v) {
-    size_t n = sig_bytes(v.p, v.n);
-    if (n > (size_t)words * 4) return false;
-    memset(dst, 0, (size_t)words * 4);
-    memcpy(dst, v.p, n);     // little-endian host
-    return true;
 }
 
 size_t bits_of(const uint32_t *w, int words) {
@@ -85,8 +35,8 @@ size_t bits_of(const uint32_t *w, int words) {
 
 }  // namespace
 
-
 // ---- the host side of the fixed-base comb: per context, its cached tables and its two option pins ----------------------
+// A side table keyed by the context pointer, not members of cofhe_hip_ctx: ctx.hpp is one of the files the kernel code hash reads.
 namespace {
 struct CombTable {
     uint32_t base[REC_WORDS];
@@ -404,12 +354,13 @@ namespace {
 struct DevBuf {                  // from the context's block cache
     cofhe_hip_ctx *ctx = nullptr;
     void *p = nullptr;
+    void *stream = nullptr;      // the block goes back behind the work queued on this stream (null: on any blocking stream)
     int get(cofhe_hip_ctx *c, size_t bytes) {
         ctx = c;
         return cofhe_hip_malloc(c, bytes, &p);
     }
     ~DevBuf() {
-        if (p) (void)cofhe_hip_free(ctx, p);
+        if (p) (void)cofhe_hip_free_on_stream(ctx, p, stream);
     }
 };
 // RAII span of the "profile_kernels" option: two events on the launch stream around one kernel launch.  Spans are named after
@@ -452,6 +403,37 @@ int compose_blocks(uint64_t n, unsigned *blocks) {
     if (b == 0 || b > 0x7FFFFFFFull) return fail(COFHE_HIP_EINVAL, "work size out of range");
     *blocks = (unsigned)b;
     return COFHE_HIP_OK;
+}
+// one of the context's flag words for a one-word read-back or verdict of this call, handed out round robin (ctx.hpp) under
+// the context lock, which the launchers that need nothing else of it (compose_wide, add) do not hold
+uint32_t *flag_word(cofhe_hip_ctx *ctx) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    return ctx->d_flags + (ctx->flag_next++ % cofhe_hip_ctx::N_FLAGS);
+}
+// grid of the k_c1_distinct / k_c1_spread scans over the records of n_ct ciphertexts
+unsigned scan_blocks(uint64_t n_ct) { return (unsigned)std::min<uint64_t>((n_ct * REC_WORDS + 255) / 256, 2048); }
+// the longest exponent of a call, which lives on the device: one small reduction and a 4-byte read-back
+int max_exp_bits(cofhe_hip_ctx *ctx, const void *d_exps, uint64_t n_exps, hipStream_t st, uint32_t *bits) {
+    uint32_t *d_bits = flag_word(ctx);
+    HIPCHK(hipMemsetAsync(d_bits, 0, 4, st));
+    hipLaunchKernelGGL(k_exp_maxbits, dim3((unsigned)((n_exps + 255) / 256)), dim3(256), 0, st, (const uint32_t *)d_exps, n_exps, d_bits);
+    HIPCHK(hipMemcpyAsync(bits, d_bits, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return COFHE_HIP_OK;
+}
+// The lookup of the two table caches (ctx->fb and CombState::tabs; `dev` is the slot's device pointer): returns the filled slot
+// that `match` accepts, or null, and in *victim the slot a miss may take: an empty one, else the least recently used, never
+// one stamped by the current call (null when every slot is).  What happens on a miss is the caller's.
+extern "C++" template <typename Slot, size_t N, typename Match>
+Slot *cache_lookup(Slot (&slots)[N], uint32_t *Slot::*dev, uint64_t call_stamp, Match match, Slot **victim) {
+    Slot *hit = nullptr;
+    *victim = nullptr;
+    for (Slot &s : slots) {
+        if (s.*dev && match(s)) hit = &s;
+        if (s.stamp == call_stamp) continue;                       // in use by this call
+        if (!*victim || !(s.*dev) || ((*victim)->*dev && s.stamp < (*victim)->stamp)) *victim = &s;
+    }
+    return hit;
 }
 
 // ---- how the entry points carve the context's workspace ------------------------------------------------------------------
@@ -671,8 +653,7 @@ int cofhe_hip_compose_wide_records(cofhe_hip_ctx *ctx, const void *d_a, const vo
     hipStream_t st = (hipStream_t)stream;
     uint32_t *d_fb = nullptr;
     if (fallbacks) {
-        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-        d_fb = ctx->d_flags + (ctx->flag_next++ % cofhe_hip_ctx::N_FLAGS);
+        d_fb = flag_word(ctx);
         HIPCHK(hipMemsetAsync(d_fb, 0, 4, st));
     }
     hipLaunchKernelGGL(k_compose_wide, dim3((unsigned)n), dim3(64), 0, st, (const uint32_t *)d_a, (const uint32_t *)d_b, (uint32_t *)d_out, n,
@@ -692,15 +673,10 @@ int cofhe_hip_add_ciphertext_records(cofhe_hip_ctx *ctx, const void *d_a, const 
     if (int rc = compose_blocks(n_ct * 2, &blocks)) return rc;
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
-    uint32_t *flag;
-    {
-        std::lock_guard<std::recursive_mutex> lk(ctx->mu);        // the flag words are handed out round robin
-        flag = ctx->d_flags + (ctx->flag_next++ % cofhe_hip_ctx::N_FLAGS);
-    }
+    uint32_t *flag = flag_word(ctx);
     HIPCHK(hipMemsetAsync(flag, 0, 4, st));
-    const unsigned scan_blocks = (unsigned)std::min<uint64_t>((n_ct * REC_WORDS + 255) / 256, 2048);
     if (n_ct > 1)
-        hipLaunchKernelGGL(k_c1_distinct, dim3(scan_blocks), dim3(256), 0, st, (const uint32_t *)d_a, (const uint32_t *)d_b, n_ct, flag);
+        hipLaunchKernelGGL(k_c1_distinct, dim3(scan_blocks(n_ct)), dim3(256), 0, st, (const uint32_t *)d_a, (const uint32_t *)d_b, n_ct, flag);
     else
         HIPCHK(hipMemsetAsync(flag, 1, 1, st));                   // one ciphertext: nothing to fold
     unsigned blocks_shared;
@@ -717,7 +693,7 @@ int cofhe_hip_add_ciphertext_records(cofhe_hip_ctx *ctx, const void *d_a, const 
     } else {
         add(blocks, 0u);     // even with distinct c1, a grid that fits is resident at three workgroups per CU
     }
-    if (n_ct > 1) hipLaunchKernelGGL(k_c1_spread, dim3(scan_blocks), dim3(256), 0, st, (uint32_t *)d_out, n_ct, (const uint32_t *)flag);
+    if (n_ct > 1) hipLaunchKernelGGL(k_c1_spread, dim3(scan_blocks(n_ct)), dim3(256), 0, st, (uint32_t *)d_out, n_ct, (const uint32_t *)flag);
     HIPCHK(hipGetLastError());
     return COFHE_HIP_OK;
 }
@@ -732,16 +708,14 @@ int pow_launch(cofhe_hip_ctx *ctx, const void *d_base, const void *d_exp, void *
     hipStream_t st = (hipStream_t)stream;
     const size_t bytes = (size_t)n_records * REC_WORDS * 4;
     const uint8_t *b0 = (const uint8_t *)d_base, *o0 = (const uint8_t *)d_out;
+    std::unique_lock<std::recursive_mutex> lk(ctx->mu, std::defer_lock);
+    std::optional<WsUse> use;                                  // declared after the lock: released before it
     if (b0 < o0 + bytes && o0 < b0 + bytes) {
-        std::lock_guard<std::recursive_mutex> lk(ctx->mu);    // the workspace belongs to one call at a time ...
-        WsUse use(ctx, st);                                    // ... until its kernel has finished (k_pow reads the copy)
+        lk.lock();                                             // the workspace belongs to one call at a time ...
+        use.emplace(ctx, st);                                  // ... until its kernel has finished (k_pow reads the copy)
         if (int rc = ensure_workspace(ctx, bytes, st)) return rc;
         HIPCHK(hipMemcpyAsync(ctx->workspace, d_base, bytes, hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(k_pow, dim3(blocks), dim3(WG_BLOCK), 0, st, (const uint32_t *)ctx->workspace, (const uint32_t *)d_exp,
-                           (uint32_t *)d_out, n_records, 1u, exp_mode, (const uint32_t *)ctx->d_one,
-                           (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
-        HIPCHK(hipGetLastError());
-        return COFHE_HIP_OK;
+        d_base = ctx->workspace;
     }
     hipLaunchKernelGGL(k_pow, dim3(blocks), dim3(WG_BLOCK), 0, st, (const uint32_t *)d_base, (const uint32_t *)d_exp,
                        (uint32_t *)d_out, n_records, 1u, exp_mode, (const uint32_t *)ctx->d_one,
@@ -749,29 +723,30 @@ int pow_launch(cofhe_hip_ctx *ctx, const void *d_base, const void *d_exp, void *
     HIPCHK(hipGetLastError());
     return COFHE_HIP_OK;
 }
-}  // namespace
-
-int cofhe_hip_pow_records(cofhe_hip_ctx *ctx, const void *d_base, const void *d_exp, void *d_out, uint64_t n_ct,
-                          void *stream) {
-    if (n_ct == 0) return COFHE_HIP_OK;
-    return pow_launch(ctx, d_base, d_exp, d_out, n_ct * 2, 0u, stream);
+// The pairwise product tree: folds src[n][mm][q] (mm slices of q records in each of n rows; a slice without a partner is
+// paired with the principal form) down to one slice per row, ceil(log2 mm) k_compose_pairs launches.  The levels go to
+// `next`, `other`, `next`, ... in turn -- the order is part of the caller's workspace plan, whose second buffer may only
+// be large enough for the level after the first -- except the last one, which goes to `last` when that is given.  Each
+// launch carries a span of the name `span` (null: none).  *result (if asked for): where the fold lies; src itself when mm == 1.
+int product_tree(cofhe_hip_ctx *ctx, const uint32_t *src, uint32_t *next, uint32_t *other, uint32_t *last, uint32_t n, uint32_t mm, uint32_t q,
+                 const char *span, hipStream_t st, const uint32_t **result) {
+    while (mm > 1) {
+        const uint32_t mh = (mm + 1) / 2;
+        unsigned blocks;
+        if (int rc = compose_blocks((uint64_t)n * mh * q, &blocks)) return rc;
+        uint32_t *dst = mh == 1 && last ? last : next;
+        ProfScope ps(ctx, span, st);
+        hipLaunchKernelGGL(k_compose_pairs, dim3(blocks), dim3(WG_BLOCK), 0, st, src, (const uint32_t *)ctx->d_one, dst, n, mm, q, 0u,
+                           (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+        src = dst;
+        std::swap(next, other);
+        mm = mh;
+    }
+    if (result) *result = src;
+    return COFHE_HIP_OK;
 }
-
-namespace {
 // tree_scratch: accumulate_tree_bytes() of device memory for the tree path, or nullptr to take it from the
 // context workspace
-int accumulate_impl(cofhe_hip_ctx *ctx, const void *d_x, const void *d_zero, void *d_out, uint32_t n, uint32_t m,
-                    uint32_t p, void *tree_scratch, void *stream);
-}  // namespace
-
-int cofhe_hip_accumulate_records(cofhe_hip_ctx *ctx, const void *d_x, const void *d_zero, void *d_out, uint32_t n,
-                                 uint32_t m, uint32_t p, void *stream) {
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    WsUse use(ctx, (hipStream_t)stream);
-    return accumulate_impl(ctx, d_x, d_zero, d_out, n, m, p, nullptr, stream);
-}
-
-namespace {
 int accumulate_impl(cofhe_hip_ctx *ctx, const void *d_x, const void *d_zero, void *d_out, uint32_t n, uint32_t m,
                     uint32_t p, void *tree_scratch, void *stream) {
     const uint64_t total = (uint64_t)n * p * 2;
@@ -789,20 +764,10 @@ int accumulate_impl(cofhe_hip_ctx *ctx, const void *d_x, const void *d_zero, voi
             if (int rc = ensure_workspace(ctx, tp.total, st)) return rc;
             tree_scratch = ctx->workspace;
         }
-        uint32_t *buf[2] = {(uint32_t *)((uint8_t *)tree_scratch + tp.off("level_a")), (uint32_t *)((uint8_t *)tree_scratch + tp.off("level_b"))};
-        const uint32_t *src = (const uint32_t *)d_x;
-        uint32_t mm = m;
-        int which = 0;
-        while (mm > 1) {
-            const uint32_t mh = (mm + 1) / 2;
-            unsigned b2;
-            if (int rc = compose_blocks((uint64_t)n * mh * q, &b2)) return rc;
-            hipLaunchKernelGGL(k_compose_pairs, dim3(b2), dim3(WG_BLOCK), 0, st, src, (const uint32_t *)ctx->d_one, buf[which], n, mm,
-                               q, 0u, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
-            src = buf[which];
-            which ^= 1;
-            mm = mh;
-        }
+        const uint32_t *src;
+        if (int rc = product_tree(ctx, (const uint32_t *)d_x, (uint32_t *)((uint8_t *)tree_scratch + tp.off("level_a")),
+                                  (uint32_t *)((uint8_t *)tree_scratch + tp.off("level_b")), nullptr, n, m, q, nullptr, st, &src))
+            return rc;
         hipLaunchKernelGGL(k_compose_pairs, dim3(blocks), dim3(WG_BLOCK), 0, st, src, (const uint32_t *)d_zero, (uint32_t *)d_out, n,
                            1u, q, 1u, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
         HIPCHK(hipGetLastError());
@@ -814,18 +779,31 @@ int accumulate_impl(cofhe_hip_ctx *ctx, const void *d_x, const void *d_zero, voi
     HIPCHK(hipGetLastError());
     return COFHE_HIP_OK;
 }
+}  // namespace
+
+int cofhe_hip_pow_records(cofhe_hip_ctx *ctx, const void *d_base, const void *d_exp, void *d_out, uint64_t n_ct,
+                          void *stream) {
+    if (n_ct == 0) return COFHE_HIP_OK;
+    return pow_launch(ctx, d_base, d_exp, d_out, n_ct * 2, 0u, stream);
+}
+
+int cofhe_hip_accumulate_records(cofhe_hip_ctx *ctx, const void *d_x, const void *d_zero, void *d_out, uint32_t n,
+                                 uint32_t m, uint32_t p, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    WsUse use(ctx, (hipStream_t)stream);
+    return accumulate_impl(ctx, d_x, d_zero, d_out, n, m, p, nullptr, stream);
+}
+
+namespace {
 // The chain base^(2^j), j < FIXED_BASE_CHAIN_LEN, of a base from the context's cache, built on a miss into the least recently
 // used slot that this call (call_stamp) does not hold: one chain of ~1000 squarings on `st`.  The fixed-base powers and the
 // comb tables (which start from every w-th entry) share it.
 constexpr uint32_t FIXED_BASE_CHAIN_LEN = EXP_MAG_WORDS * 32 + 2;
 int fixed_base_chain(cofhe_hip_ctx *ctx, const uint32_t *base_record, uint64_t call_stamp, hipStream_t st, cofhe_hip_ctx::FixedBase **out) {
     const uint32_t TABLE_LEN = FIXED_BASE_CHAIN_LEN;
-    cofhe_hip_ctx::FixedBase *fb = nullptr, *victim = nullptr;
-    for (auto &e : ctx->fb) {
-        if (e.d_table && memcmp(e.base, base_record, REC_WORDS * 4) == 0) fb = &e;
-        if (e.stamp == call_stamp) continue;                       // in use by this call
-        if (!victim || !e.d_table || (victim->d_table && e.stamp < victim->stamp)) victim = &e;
-    }
+    cofhe_hip_ctx::FixedBase *victim;
+    cofhe_hip_ctx::FixedBase *fb = cache_lookup(ctx->fb, &cofhe_hip_ctx::FixedBase::d_table, call_stamp,
+                                                [&](const cofhe_hip_ctx::FixedBase &e) { return memcmp(e.base, base_record, REC_WORDS * 4) == 0; }, &victim);
     if (!fb) {
         fb = victim;
         HIPCHK(hipStreamSynchronize(st));
@@ -833,12 +811,10 @@ int fixed_base_chain(cofhe_hip_ctx *ctx, const uint32_t *base_record, uint64_t c
         fb->len = 0;
         HIPCHK(hipMemcpyAsync(fb->d_table + (size_t)TABLE_LEN * REC_WORDS, base_record, REC_WORDS * 4, hipMemcpyHostToDevice, st));
         // one chain of ~1000 squarings: the latency kernel (one wavefront, wide layout); ladder_form 3 keeps the old one
-        if (ctx->opt_ladder_form == 3)
-            hipLaunchKernelGGL(k_square_chain, dim3(1), dim3(WG_BLOCK), 0, st, (const uint32_t *)(fb->d_table + (size_t)TABLE_LEN * REC_WORDS),
-                               fb->d_table, TABLE_LEN, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
-        else
-            hipLaunchKernelGGL(k_square_chain_wide, dim3(1), dim3(64), 0, st, (const uint32_t *)(fb->d_table + (size_t)TABLE_LEN * REC_WORDS),
-                               fb->d_table, TABLE_LEN, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+        const bool old = ctx->opt_ladder_form == 3;
+        hipLaunchKernelGGL(old ? k_square_chain : k_square_chain_wide, dim3(1), dim3(old ? WG_BLOCK : 64), 0, st,
+                           (const uint32_t *)(fb->d_table + (size_t)TABLE_LEN * REC_WORDS), fb->d_table, TABLE_LEN,
+                           (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
         HIPCHK(hipGetLastError());
         memcpy(fb->base, base_record, REC_WORDS * 4);
         fb->len = TABLE_LEN;
@@ -905,17 +881,9 @@ int cofhe_hip_pow_fixed_base_records(cofhe_hip_ctx *ctx, uint32_t n, const uint3
     const uint32_t total = n * mmax;
     hipLaunchKernelGGL(k_gather_signed, dim3((total + WG_GROUPS - 1) / WG_GROUPS), dim3(WG_BLOCK), 0, st, (const uint64_t *)d_tabs,
                        (const uint32_t *)(d_tabs + n), (uint64_t)total, (const uint32_t *)ctx->d_one, buf[0]);
-    uint32_t mm = mmax;
-    int which = 0;
-    while (mm > 1) {
-        const uint32_t mh = (mm + 1) / 2;
-        uint32_t *dst = mh == 1 ? (uint32_t *)d_out : buf[which ^ 1];
-        hipLaunchKernelGGL(k_compose_pairs, dim3((n * mh + WG_GROUPS - 1) / WG_GROUPS), dim3(WG_BLOCK), 0, st, (const uint32_t *)buf[which],
-                           (const uint32_t *)ctx->d_one, dst, n, mm, 1u, 0u, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
-        which ^= 1;
-        mm = mh;
-    }
-    if (mmax == 1) HIPCHK(hipMemcpyAsync(d_out, buf[0], (size_t)n * REC_WORDS * 4, hipMemcpyDeviceToDevice, st));
+    const uint32_t *res;
+    if (int rc = product_tree(ctx, buf[0], buf[1], buf[0], (uint32_t *)d_out, n, mmax, 1u, nullptr, st, &res)) return rc;
+    if (res != d_out) HIPCHK(hipMemcpyAsync(d_out, res, (size_t)n * REC_WORDS * 4, hipMemcpyDeviceToDevice, st));     // mmax == 1: nothing to fold
     HIPCHK(hipGetLastError());
     return COFHE_HIP_OK;
 }
@@ -948,12 +916,9 @@ int comb_check(uint64_t kind, uint64_t n, uint64_t exp_bits, uint64_t kbits, uin
 // w - 1 levels of k_comb_table.  The tables of one call are all stamped with call_stamp and are not evicted by it.
 int comb_table(cofhe_hip_ctx *ctx, const uint32_t *base_record, uint32_t w, uint64_t call_stamp, hipStream_t st, const uint32_t **out) {
     CombState &cs = comb_state(ctx);
-    CombTable *hit = nullptr, *victim = nullptr;
-    for (auto &t : cs.tabs) {
-        if (t.d && t.w == w && memcmp(t.base, base_record, REC_WORDS * 4) == 0) hit = &t;
-        if (t.stamp == call_stamp) continue;
-        if (!victim || !t.d || (victim->d && t.stamp < victim->stamp)) victim = &t;
-    }
+    CombTable *victim;
+    CombTable *hit = cache_lookup(cs.tabs, &CombTable::d, call_stamp,
+                                  [&](const CombTable &t) { return t.w == w && memcmp(t.base, base_record, REC_WORDS * 4) == 0; }, &victim);
     if (!hit) {
         if (!victim) return fail(COFHE_HIP_EINVAL, "comb: no table slot left");
         hit = victim;
@@ -999,13 +964,7 @@ int comb_run(cofhe_hip_ctx *ctx, uint32_t kind, const uint32_t *const bases[3], 
     const CombState &cs = comb_state(ctx);
     // the tree's shape follows the longest exponent: the one read-back of the call
     uint32_t exp_bits = 0;
-    {
-        uint32_t *d_mb = ctx->d_flags + (ctx->flag_next++ % cofhe_hip_ctx::N_FLAGS);
-        HIPCHK(hipMemsetAsync(d_mb, 0, 4, st));
-        hipLaunchKernelGGL(k_exp_maxbits, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t *)d_r, n, d_mb);
-        HIPCHK(hipMemcpyAsync(&exp_bits, d_mb, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
+    if (int rc = max_exp_bits(ctx, d_r, n, st, &exp_bits)) return rc;
     const CombCall cc = comb_call(kind, n, exp_bits, kbits, cs.opt_width, cs.opt_chunk);
     const uint64_t call_stamp = ++comb_state(ctx).clock;
     const uint32_t *tabs[3] = {nullptr, nullptr, nullptr};
@@ -1029,17 +988,7 @@ int comb_run(cofhe_hip_ctx *ctx, uint32_t kind, const uint32_t *const bases[3], 
                                d_leaf ? (const uint32_t *)d_leaf + e0 * H * REC_WORDS : nullptr, ncols, (const uint32_t *)ctx->d_one,
                                mm == 1 ? out : buf[0], (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
         }
-        int which = 0;
-        while (mm > 1) {
-            const uint32_t mh = (mm + 1) / 2;
-            if (int rc = compose_blocks((uint64_t)mh * ncols, &blocks)) return rc;
-            ProfScope ps(ctx, "k_compose_pairs", st);
-            hipLaunchKernelGGL(k_compose_pairs, dim3(blocks), dim3(WG_BLOCK), 0, st, (const uint32_t *)buf[which], (const uint32_t *)ctx->d_one,
-                               mh == 1 ? out : buf[which ^ 1], 1u, mm, (uint32_t)ncols, 0u, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits,
-                               ctx->d_status);
-            which ^= 1;
-            mm = mh;
-        }
+        if (int rc = product_tree(ctx, buf[0], buf[1], buf[0], out, 1u, mm, (uint32_t)ncols, "k_compose_pairs", st, nullptr)) return rc;
         HIPCHK(hipGetLastError());
     }
     return COFHE_HIP_OK;
@@ -1097,22 +1046,22 @@ int pow_shared(cofhe_hip_ctx *ctx, const void *d_base, uint32_t stride, const vo
     int form = ctx->opt_ladder_form ? ctx->opt_ladder_form : (n <= 256 ? 1 : 3);           // one ladder per CU at most: four per CU ran at half speed each
     if (form == 1 && n > POW_PAIR_MAX_LADDERS) form = 4;        // the pair's two workgroups must be resident together
     hipLaunchKernelGGL(k_wnaf_digits, dim3(1), dim3(64), 0, st, (const uint32_t *)d_exp, (uint64_t)1, form == 1 ? 2u : w, digits, maxlen);
-    ProfScope ps(ctx, form == 1 ? "k_pow_shared_pair" : form == 4 ? "k_pow_shared_wide" : (form == 2 && n <= 64 / G) ? "k_pow_shared_solo" : "k_pow_shared",
-                 st);
+    // forms 4, 2 (while its ladders fit one wavefront) and 3 take the same arguments; the span is named after the kernel
+    struct Ladder {
+        decltype(&k_pow_shared) kernel;
+        unsigned grid, block;
+        const char *span;
+    };
+    const Ladder l = form == 4                    ? Ladder{k_pow_shared_wide, (unsigned)n, 64, "k_pow_shared_wide"}
+                     : (form == 2 && n <= 64 / G) ? Ladder{k_pow_shared_solo, 1, 64, "k_pow_shared_solo"}
+                                                  : Ladder{k_pow_shared, blocks, WG_BLOCK, "k_pow_shared"};
+    ProfScope ps(ctx, form == 1 ? "k_pow_shared_pair" : l.span, st);
     if (form == 1)
         hipLaunchKernelGGL(k_pow_shared_pair, dim3((unsigned)(2 * n)), dim3(64), 0, st, (const uint32_t *)d_base, (const int8_t *)digits,
                            (const uint32_t *)maxlen, table, pairctl, (uint32_t *)d_out, n, stride, (const uint32_t *)ctx->d_one,
                            (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);     // the table region serves as the rings
-    else if (form == 4)
-        hipLaunchKernelGGL(k_pow_shared_wide, dim3((unsigned)n), dim3(64), 0, st, (const uint32_t *)d_base, (const int8_t *)digits,
-                           (const uint32_t *)maxlen, table, (uint32_t *)d_out, n, stride, tw, (const uint32_t *)ctx->d_one,
-                           (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
-    else if (form == 2 && n <= 64 / G)
-        hipLaunchKernelGGL(k_pow_shared_solo, dim3(1), dim3(64), 0, st, (const uint32_t *)d_base, (const int8_t *)digits,
-                           (const uint32_t *)maxlen, table, (uint32_t *)d_out, n, stride, tw, (const uint32_t *)ctx->d_one,
-                           (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
     else
-        hipLaunchKernelGGL(k_pow_shared, dim3(blocks), dim3(WG_BLOCK), 0, st, (const uint32_t *)d_base, (const int8_t *)digits,
+        hipLaunchKernelGGL(l.kernel, dim3(l.grid), dim3(l.block), 0, st, (const uint32_t *)d_base, (const int8_t *)digits,
                            (const uint32_t *)maxlen, table, (uint32_t *)d_out, n, stride, tw, (const uint32_t *)ctx->d_one,
                            (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
     HIPCHK(hipGetLastError());
@@ -1127,10 +1076,9 @@ int pow_shared_c1(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_exp, void
                   hipStream_t st) {
     bool shared = false;
     if (n_ct >= 64) {
-        uint32_t *flag = ctx->d_flags + (ctx->flag_next++ % cofhe_hip_ctx::N_FLAGS);
+        uint32_t *flag = flag_word(ctx);
         HIPCHK(hipMemsetAsync(flag, 0, 4, st));
-        const unsigned scan_blocks = (unsigned)std::min<uint64_t>((n_ct * REC_WORDS + 255) / 256, 2048);
-        hipLaunchKernelGGL(k_c1_distinct, dim3(scan_blocks), dim3(256), 0, st, (const uint32_t *)d_cts, (const uint32_t *)d_cts, n_ct, flag);
+        hipLaunchKernelGGL(k_c1_distinct, dim3(scan_blocks(n_ct)), dim3(256), 0, st, (const uint32_t *)d_cts, (const uint32_t *)d_cts, n_ct, flag);
         uint32_t distinct = 1;
         HIPCHK(hipMemcpyAsync(&distinct, flag, 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
@@ -1158,156 +1106,128 @@ int cofhe_hip_part_decrypt_records(cofhe_hip_ctx *ctx, const void *d_cts, const 
     return pow_shared_c1(ctx, d_cts, d_share, d_out, n_ct, 0, nullptr, (hipStream_t)stream);
 }
 
-int cofhe_hip_scal_matmul_records(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_exp, const void *d_zero,
-                                  void *d_out, uint32_t n, uint32_t m, uint32_t p, void *stream) {
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if ((uint64_t)n * p == 0) return COFHE_HIP_OK;
-    unsigned blocks;
-    if (int rc = compose_blocks((uint64_t)n * p * 2, &blocks)) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    WsUse use(ctx, st);
-    // window width: a table of 2^(w-2) odd powers per base costs that many compositions and is used by
-    // the p columns of its row, saving ~bits*(1/3 - 1/(w+1)) compositions in each; keep the tables under
-    // 1/8 of the device memory
+namespace {
+// ---- the matrix product: what its two routes share, the routes, then the entry point that chooses ------------------------
+// the width-w digits of n_exps exponents and the length of the longest, in a "k_wnaf_digits" span
+void wnaf_digits(cofhe_hip_ctx *ctx, const void *d_exp, uint64_t n_exps, uint32_t w, int8_t *digits, uint32_t *maxlen, hipStream_t st) {
+    if (n_exps == 0) return;
+    ProfScope ps(ctx, "k_wnaf_digits", st);
+    hipLaunchKernelGGL(k_wnaf_digits, dim3((unsigned)((n_exps + 255) / 256)), dim3(256), 0, st, (const uint32_t *)d_exp, n_exps, w, digits, maxlen);
+}
+// the tw odd powers of each of the nbase records into `room`, in a "k_pow_table" span (around the "k_pow_table3" one of the
+// three-per-CU build); *table: where the route finds them
+int pow_table(cofhe_hip_ctx *ctx, const void *d_cts, uint64_t nbase, uint32_t tw, void *room, hipStream_t st, const uint32_t **table) {
+    *table = (const uint32_t *)d_cts;                         // w == 2: the only table entry is the base itself
+    if (tw == 1 || nbase == 0) return COFHE_HIP_OK;
+    unsigned tblocks;
+    if (int rc = compose_blocks(nbase, &tblocks)) return rc;
+    ProfScope ps(ctx, "k_pow_table", st);
+    launch_wg(ctx, k_pow_table3, k_pow_table, "k_pow_table3", nullptr, tblocks, st, (const uint32_t *)d_cts, (uint32_t *)room, nbase, tw,
+              (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+    *table = (const uint32_t *)room;
+    return COFHE_HIP_OK;
+}
+
+// The product-tree route (k_tree_*) at window width w for exponents of at most exp_bits bits.  *taken = false: declined --
+// only the digits and the plan have been computed, no output written -- and the caller runs the chains instead.
+int matmul_tree_route(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_exp, const void *d_zero, void *d_out, uint32_t n, uint32_t m, uint32_t p,
+                      uint32_t w, uint32_t exp_bits, hipStream_t st, bool *taken) {
+    *taken = false;
     const uint64_t nbase = (uint64_t)n * m * 2, n_exps = (uint64_t)m * p;
-    uint32_t w = 2, exp_bits = 0;                              // exp_bits: longest exponent of the call
-    if (m > 0) {
-        // per base: 2^(w-2) compositions for the table, then ~bits/(w+1) per column -- needs the exponent
-        // length, which lives on the device: one small reduction and a 4-byte read-back
-        if (int rc = ensure_workspace(ctx, 256, st)) return rc;
-        uint32_t *d_bits = (uint32_t *)ctx->workspace;
-        uint32_t bits = 0;
-        HIPCHK(hipMemsetAsync(d_bits, 0, 4, st));
-        hipLaunchKernelGGL(k_exp_maxbits, dim3((unsigned)((n_exps + 255) / 256)), dim3(256), 0, st, (const uint32_t *)d_exp, n_exps,
-                           d_bits);
-        HIPCHK(hipMemcpyAsync(&bits, d_bits, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        exp_bits = bits;
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        double best = (double)p * bits / 3.0;                      // w = 2: plain NAF, no table
-        for (uint32_t cand = 3; cand <= 8; cand++) {
-            const uint64_t bytes = nbase * (1ull << (cand - 2)) * REC_WORDS * 4;
-            if (bytes > total_b / 8 || bytes > free_b / 2) break;
-            const double cost = (double)(1u << (cand - 2)) + (double)p * bits / (cand + 1.0);
-            if (cost < best) {
-                best = cost;
-                w = cand;
-            }
-        }
-        if (ctx->opt_wnaf_width >= 2 && ctx->opt_wnaf_width <= 8) w = ctx->opt_wnaf_width;      // cofhe_hip_ctx_set_option
-    }
     const uint32_t tw = 1u << (w - 2);
-    if (m >= (1u << 21)) return fail(COFHE_HIP_EINVAL, "inner dimension beyond 2^21");
-    // The product-tree form (kernels above: k_tree_*) when there is something to pair up and enough outputs for the Horner
-    // chains to fill the GPU; small products keep the segmented lockstep chains below, which measured faster there
-    // (profiles/r04_a/tree_time.txt: 8x64.64x64 11.7 vs 12.8 ms, 64^3 21.6 vs 20.9, 32x256.256x256 k-bit 683 vs 673,
-    // 256^3 884 vs 787 ms -- chains vs tree).  "matmul_tree" = 0 / 1 pins the choice.
-    const bool use_tree = ctx->opt_matmul_tree == 1 || (ctx->opt_matmul_tree == -1 && m >= 8 && (uint64_t)n * p * 2 >= 4096);
-    if (use_tree && m > 0) {
-        const WsPlan tp = plan_scal_matmul_tree(n, m, p, exp_bits, w);
-        if (int rc = ensure_workspace(ctx, tp.total, st)) return rc;
-        uint8_t *ws = (uint8_t *)ctx->workspace;
-        int8_t *digits = (int8_t *)(ws + tp.off("digits"));
-        uint32_t *maxlen = (uint32_t *)(ws + tp.off("maxlen"));
-        uint32_t *d_c = (uint32_t *)(ws + tp.off("counts")), *d_off = (uint32_t *)(ws + tp.off("offsets"));
-        uint32_t *d_info = (uint32_t *)(ws + tp.off("info"));
-        const uint32_t S_cap = (exp_bits + 2) * p;
-        HIPCHK(hipMemsetAsync(digits, 0, tp.off("maxlen") + 256 - tp.off("digits"), st));
-        {
-            ProfScope ps(ctx, "k_wnaf_digits", st);
-            hipLaunchKernelGGL(k_wnaf_digits, dim3((unsigned)((n_exps + 255) / 256)), dim3(256), 0, st, (const uint32_t *)d_exp, n_exps, w,
-                               digits, maxlen);
+    const WsPlan tp = plan_scal_matmul_tree(n, m, p, exp_bits, w);
+    if (int rc = ensure_workspace(ctx, tp.total, st)) return rc;
+    uint8_t *ws = (uint8_t *)ctx->workspace;
+    int8_t *digits = (int8_t *)(ws + tp.off("digits"));
+    uint32_t *maxlen = (uint32_t *)(ws + tp.off("maxlen"));
+    uint32_t *d_c = (uint32_t *)(ws + tp.off("counts")), *d_off = (uint32_t *)(ws + tp.off("offsets"));
+    uint32_t *d_info = (uint32_t *)(ws + tp.off("info"));
+    const uint32_t S_cap = (exp_bits + 2) * p;
+    HIPCHK(hipMemsetAsync(digits, 0, tp.off("maxlen") + 256 - tp.off("digits"), st));
+    wnaf_digits(ctx, d_exp, n_exps, w, digits, maxlen, st);
+    HIPCHK(hipMemsetAsync(d_c, 0, (size_t)S_cap * 4, st));              // level 0 of segments beyond the longest exponent
+    hipLaunchKernelGGL(k_tree_count, dim3((unsigned)(((uint64_t)S_cap + 255) / 256)), dim3(256), 0, st, (const int8_t *)digits,
+                       (const uint32_t *)maxlen, m, p, d_c);
+    hipLaunchKernelGGL(k_tree_plan, dim3(1), dim3(1024), 0, st, (const uint32_t *)maxlen, p, S_cap, d_c, d_off, d_info);
+    uint32_t info[TREE_LEVELS + 3];
+    HIPCHK(hipMemcpyAsync(info, d_info, sizeof(info), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));                           // `info` is on the host
+    const uint32_t T = info[TREE_LEVELS + 1], S = info[TREE_LEVELS + 2];
+    if (T < 1 || T > TREE_LEVELS || S > S_cap) return fail(COFHE_HIP_EHIP, "matrix product: tree plan out of range");
+    // rows per chunk: the two level buffers hold N_1 x rows x 2 records each (level 1 is the largest) ...
+    const uint64_t n1 = info[1] ? info[1] : 1;
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    // ... and small enough for the context's block cache to keep both of them between calls (a quarter of its cap each):
+    // buffers beyond the cap are given back to the driver at the end of every call, and allocating tens of GB anew
+    // cost the product more than its kernels (bench.py, first tree build: 2.03 s per 256^3 product of which 0.78 s compute)
+    const uint64_t budget = std::min<uint64_t>(free_b / 4, std::max<uint64_t>(ctx->pool_cap / 4, (uint64_t)1 << 30));
+    uint64_t R = budget / (n1 * 2 * REC_WORDS * 4);
+    if (R >= 16) R &= ~(uint64_t)15;                           // 2 R a multiple of 32: the groups of a workgroup share their element
+    if (R < 1) R = 1;
+    if (R > n) R = n;
+    // Long exponents make long trees (N_1 ~ p bits m / 2 (w + 1) elements per row): when fewer than 16 rows fit a chunk the
+    // workgroups mix tree elements, copies ride along as dummy compositions, and the chains win again (32x256.256x256 with
+    // 128-bit exponents: 0.83 s in 14-row chunks against 0.68 s; profiles/r04_a/tree_time_chunks.txt)
+    // The Horner chains address the top level's N_T elements through the op word's 21-bit base index (off_T[s] < N_T):
+    // beyond 2^21 elements the tree is not taken, "matmul_tree" = 1 included, and the chains run instead
+    const bool tree_fits = info[T] <= MM_INDEX_LIMIT;
+    const bool tree_pays = tree_fits && (R >= 16 || R == n || ctx->opt_matmul_tree == 1);
+    if (!tree_pays) return COFHE_HIP_OK;
+    const uint32_t *table;
+    if (int rc = pow_table(ctx, d_cts, nbase, tw, ws + tp.off("table"), st, &table)) return rc;
+    uint64_t map_words = 0;
+    for (uint32_t l = 1; l <= T; l++) map_words += info[l];
+    const uint32_t len = p ? S / p : 0;                       // bit positions in use
+    const uint32_t rcap_h = 2 * len + 2;
+    DevBuf b_ent, b_map, b_ops, b_cnt, b_lvl[2];
+    for (DevBuf *b : {&b_ent, &b_map, &b_ops, &b_cnt, &b_lvl[0], &b_lvl[1]}) b->stream = st;      // on every way out
+    if (int rc = b_ent.get(ctx, (size_t)info[0] * 4 + 4)) return rc;
+    if (int rc = b_map.get(ctx, (size_t)map_words * 4 + 4)) return rc;
+    if (int rc = b_ops.get(ctx, (size_t)p * rcap_h * 4)) return rc;
+    if (int rc = b_cnt.get(ctx, (size_t)p * 4)) return rc;
+    hipLaunchKernelGGL(k_tree_fill, dim3(S ? S : 1), dim3(64), 0, st, (const int8_t *)digits, m, p, S_cap, (const uint32_t *)d_c,
+                       (const uint32_t *)d_off, (const uint32_t *)d_info, (uint32_t *)b_ent.p, (uint32_t *)b_map.p);
+    hipLaunchKernelGGL(k_tree_horner_schedule, dim3((p + 63) / 64), dim3(64), 0, st, (const uint32_t *)maxlen, p, S_cap, (const uint32_t *)d_c,
+                       (const uint32_t *)d_off, (const uint32_t *)d_info, rcap_h, (uint32_t *)b_ops.p, (uint32_t *)b_cnt.p, ctx->d_status);
+    const size_t lvl_bytes = (size_t)n1 * R * 2 * REC_WORDS * 4;
+    if (int rc = b_lvl[0].get(ctx, lvl_bytes)) return rc;
+    if (int rc = b_lvl[1].get(ctx, lvl_bytes)) return rc;
+    const uint32_t *maps = (const uint32_t *)b_map.p;
+    for (uint32_t r0 = 0; r0 < n; r0 += (uint32_t)R) {
+        const uint32_t rows = std::min<uint32_t>((uint32_t)R, n - r0);
+        uint64_t map_base = 0;
+        for (uint32_t l = 0; l < T; l++) {                     // level l -> l + 1
+            const uint64_t items = (uint64_t)info[l + 1] * rows * 2;
+            unsigned lb;
+            if (items == 0) break;
+            if (int rc = compose_blocks(items, &lb)) return rc;
+            const uint32_t *src = l == 0 ? table + (uint64_t)r0 * m * 2 * tw * REC_WORDS : (const uint32_t *)b_lvl[(l - 1) & 1].p;
+            ProfScope ps(ctx, "k_tree_level", st);
+            hipLaunchKernelGGL(k_tree_level, dim3(lb), dim3(WG_BLOCK), 0, st, src, l == 0 ? 1u : 0u, (const uint32_t *)b_ent.p,
+                               (const uint32_t *)(d_off + (uint64_t)l * (S_cap + 1)), (const uint32_t *)(d_off + (uint64_t)(l + 1) * (S_cap + 1)),
+                               maps + map_base, info[l], info[l + 1], rows, m, tw, (uint32_t *)b_lvl[l & 1].p,
+                               (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+            map_base += info[l + 1];
         }
-        HIPCHK(hipMemsetAsync(d_c, 0, (size_t)S_cap * 4, st));              // level 0 of segments beyond the longest exponent
-        hipLaunchKernelGGL(k_tree_count, dim3((unsigned)(((uint64_t)S_cap + 255) / 256)), dim3(256), 0, st, (const int8_t *)digits,
-                           (const uint32_t *)maxlen, m, p, d_c);
-        hipLaunchKernelGGL(k_tree_plan, dim3(1), dim3(1024), 0, st, (const uint32_t *)maxlen, p, S_cap, d_c, d_off, d_info);
-        uint32_t info[TREE_LEVELS + 3];
-        HIPCHK(hipMemcpyAsync(info, d_info, sizeof(info), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));                           // `info` is on the host
-        const uint32_t T = info[TREE_LEVELS + 1], S = info[TREE_LEVELS + 2];
-        if (T < 1 || T > TREE_LEVELS || S > S_cap) return fail(COFHE_HIP_EHIP, "matrix product: tree plan out of range");
-        // rows per chunk: the two level buffers hold N_1 x rows x 2 records each (level 1 is the largest) ...
-        const uint64_t n1 = info[1] ? info[1] : 1;
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        // ... and small enough for the context's block cache to keep both of them between calls (a quarter of its cap each):
-        // buffers beyond the cap are given back to the driver at the end of every call, and allocating tens of GB anew
-        // cost the product more than its kernels (bench.py, first tree build: 2.03 s per 256^3 product of which 0.78 s compute)
-        const uint64_t budget = std::min<uint64_t>(free_b / 4, std::max<uint64_t>(ctx->pool_cap / 4, (uint64_t)1 << 30));
-        uint64_t R = budget / (n1 * 2 * REC_WORDS * 4);
-        if (R >= 16) R &= ~(uint64_t)15;                           // 2 R a multiple of 32: the groups of a workgroup share their element
-        if (R < 1) R = 1;
-        if (R > n) R = n;
-        // Long exponents make long trees (N_1 ~ p bits m / 2 (w + 1) elements per row): when fewer than 16 rows fit a chunk the
-        // workgroups mix tree elements, copies ride along as dummy compositions, and the chains win again (32x256.256x256 with
-        // 128-bit exponents: 0.83 s in 14-row chunks against 0.68 s; profiles/r04_a/tree_time_chunks.txt)
-        // The Horner chains address the top level's N_T elements through the op word's 21-bit base index (off_T[s] < N_T):
-        // beyond 2^21 elements the tree is not taken, "matmul_tree" = 1 included, and the chains below run instead
-        const bool tree_fits = info[T] <= MM_INDEX_LIMIT;
-        const bool tree_pays = tree_fits && (R >= 16 || R == n || ctx->opt_matmul_tree == 1);
-        if (tree_pays) {
-        const uint32_t *table = (const uint32_t *)d_cts;          // w == 2: the only table entry is the base itself
-        if (tw > 1 && nbase) {
-            unsigned tblocks;
-            if (int rc = compose_blocks(nbase, &tblocks)) return rc;
-            ProfScope ps(ctx, "k_pow_table", st);
-            launch_wg(ctx, k_pow_table3, k_pow_table, "k_pow_table3", nullptr, tblocks, st, (const uint32_t *)d_cts,
-                      (uint32_t *)(ws + tp.off("table")), nbase, tw, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
-            table = (const uint32_t *)(ws + tp.off("table"));
-        }
-        uint64_t map_words = 0;
-        for (uint32_t l = 1; l <= T; l++) map_words += info[l];
-        const uint32_t len = p ? S / p : 0;                       // bit positions in use
-        const uint32_t rcap_h = 2 * len + 2;
-        DevBuf b_ent, b_map, b_ops, b_cnt, b_lvl[2];
-        if (int rc = b_ent.get(ctx, (size_t)info[0] * 4 + 4)) return rc;
-        if (int rc = b_map.get(ctx, (size_t)map_words * 4 + 4)) return rc;
-        if (int rc = b_ops.get(ctx, (size_t)p * rcap_h * 4)) return rc;
-        if (int rc = b_cnt.get(ctx, (size_t)p * 4)) return rc;
-        hipLaunchKernelGGL(k_tree_fill, dim3(S ? S : 1), dim3(64), 0, st, (const int8_t *)digits, m, p, S_cap, (const uint32_t *)d_c,
-                           (const uint32_t *)d_off, (const uint32_t *)d_info, (uint32_t *)b_ent.p, (uint32_t *)b_map.p);
-        hipLaunchKernelGGL(k_tree_horner_schedule, dim3((p + 63) / 64), dim3(64), 0, st, (const uint32_t *)maxlen, p, S_cap, (const uint32_t *)d_c,
-                           (const uint32_t *)d_off, (const uint32_t *)d_info, rcap_h, (uint32_t *)b_ops.p, (uint32_t *)b_cnt.p, ctx->d_status);
-        const size_t lvl_bytes = (size_t)n1 * R * 2 * REC_WORDS * 4;
-        if (int rc = b_lvl[0].get(ctx, lvl_bytes)) return rc;
-        if (int rc = b_lvl[1].get(ctx, lvl_bytes)) return rc;
-        const uint32_t *maps = (const uint32_t *)b_map.p;
-        for (uint32_t r0 = 0; r0 < n; r0 += (uint32_t)R) {
-            const uint32_t rows = std::min<uint32_t>((uint32_t)R, n - r0);
-            uint64_t map_base = 0;
-            for (uint32_t l = 0; l < T; l++) {                     // level l -> l + 1
-                const uint64_t items = (uint64_t)info[l + 1] * rows * 2;
-                unsigned lb;
-                if (items == 0) break;
-                if (int rc = compose_blocks(items, &lb)) return rc;
-                const uint32_t *src = l == 0 ? table + (uint64_t)r0 * m * 2 * tw * REC_WORDS : (const uint32_t *)b_lvl[(l - 1) & 1].p;
-                ProfScope ps(ctx, "k_tree_level", st);
-                hipLaunchKernelGGL(k_tree_level, dim3(lb), dim3(WG_BLOCK), 0, st, src, l == 0 ? 1u : 0u, (const uint32_t *)b_ent.p,
-                                   (const uint32_t *)(d_off + (uint64_t)l * (S_cap + 1)), (const uint32_t *)(d_off + (uint64_t)(l + 1) * (S_cap + 1)),
-                                   maps + map_base, info[l], info[l + 1], rows, m, tw, (uint32_t *)b_lvl[l & 1].p,
-                                   (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
-                map_base += info[l + 1];
-            }
-            unsigned hb;
-            if (int rc = compose_blocks((uint64_t)rows * p * 2, &hb)) return rc;
-            ProfScope ps(ctx, "k_scal_matmul_wnaf", st);
-            launch_wg(ctx, k_scal_matmul_wnaf3, k_scal_matmul_wnaf, "k_scal_matmul_wnaf3", nullptr, hb, st, (const uint32_t *)b_lvl[(T - 1) & 1].p,
-                      (const uint32_t *)b_ops.p, (const uint32_t *)b_cnt.p, rcap_h, (const uint32_t *)d_zero,
-                      (uint32_t *)d_out + (uint64_t)r0 * p * 2 * REC_WORDS, rows, info[T] ? info[T] : 1u, p, 1u, 1u, (const uint32_t *)ctx->d_one,
-                      (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
-        }
-        HIPCHK(hipGetLastError());
-        // the cached blocks go back behind the work queued on this stream
-        for (DevBuf *b : {&b_ent, &b_map, &b_ops, &b_cnt, &b_lvl[0], &b_lvl[1]}) {
-            (void)cofhe_hip_free_on_stream(ctx, b->p, stream);
-            b->p = nullptr;
-        }
-        return COFHE_HIP_OK;
-        }       // tree_pays
+        unsigned hb;
+        if (int rc = compose_blocks((uint64_t)rows * p * 2, &hb)) return rc;
+        ProfScope ps(ctx, "k_scal_matmul_wnaf", st);
+        launch_wg(ctx, k_scal_matmul_wnaf3, k_scal_matmul_wnaf, "k_scal_matmul_wnaf3", nullptr, hb, st, (const uint32_t *)b_lvl[(T - 1) & 1].p,
+                  (const uint32_t *)b_ops.p, (const uint32_t *)b_cnt.p, rcap_h, (const uint32_t *)d_zero,
+                  (uint32_t *)d_out + (uint64_t)r0 * p * 2 * REC_WORDS, rows, info[T] ? info[T] : 1u, p, 1u, 1u, (const uint32_t *)ctx->d_one,
+                  (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
     }
+    HIPCHK(hipGetLastError());
+    *taken = true;
+    return COFHE_HIP_OK;
+}
+
+// The chains route: segmented lockstep chains, one per output form and segment.
+int matmul_chains_route(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_exp, const void *d_zero, void *d_out, uint32_t n, uint32_t m, uint32_t p,
+                        uint32_t w, uint32_t exp_bits, hipStream_t st) {
+    const uint64_t nbase = (uint64_t)n * m * 2, n_exps = (uint64_t)m * p;
+    const uint32_t tw = 1u << (w - 2);
     // few outputs (the reference's own benchmark shape is 8 x 64 . 64 x 64): cut the inner dimension into
     // segments so that the chains fill the GPU, then fold the partial products with the accumulation tree
     uint32_t segs = 1;
@@ -1332,22 +1252,11 @@ int cofhe_hip_scal_matmul_records(cofhe_hip_ctx *ctx, const void *d_cts, const v
     uint32_t *counts = (uint32_t *)(ws + mp_.off("counts"));
     uint32_t *partial = (uint32_t *)(ws + mp_.off("partial"));
     HIPCHK(hipMemsetAsync(digits, 0, mp_.off("maxlen") + 256 - mp_.off("digits"), st));
-    if (n_exps) {
-        ProfScope ps(ctx, "k_wnaf_digits", st);
-        hipLaunchKernelGGL(k_wnaf_digits, dim3((unsigned)((n_exps + 255) / 256)), dim3(256), 0, st, (const uint32_t *)d_exp,
-                           n_exps, w, digits, maxlen);
-    }
+    wnaf_digits(ctx, d_exp, n_exps, w, digits, maxlen, st);
     hipLaunchKernelGGL(k_matmul_schedule, dim3(ncols), dim3(64), 0, st, (const int8_t *)digits, (const uint32_t *)maxlen, m, p,
                        segs, rcap, ops, counts, ctx->d_status);
-    const uint32_t *table = (const uint32_t *)d_cts;          // w == 2: the only table entry is the base itself
-    if (tw > 1 && nbase) {
-        unsigned tblocks;
-        if (int rc = compose_blocks(nbase, &tblocks)) return rc;
-        ProfScope ps(ctx, "k_pow_table", st);
-        launch_wg(ctx, k_pow_table3, k_pow_table, "k_pow_table3", nullptr, tblocks, st, (const uint32_t *)d_cts,
-                  (uint32_t *)(ws + mp_.off("table")), nbase, tw, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
-        table = (const uint32_t *)(ws + mp_.off("table"));
-    }
+    const uint32_t *table;
+    if (int rc = pow_table(ctx, d_cts, nbase, tw, ws + mp_.off("table"), st, &table)) return rc;
     unsigned mblocks;
     if (int rc = compose_blocks(out_forms * segs, &mblocks)) return rc;
     {
@@ -1358,8 +1267,54 @@ int cofhe_hip_scal_matmul_records(cofhe_hip_ctx *ctx, const void *d_cts, const v
     }
     HIPCHK(hipGetLastError());
     if (segs > 1)
-        return accumulate_impl(ctx, partial, d_zero, d_out, n, segs, p, ws + mp_.off("tree"), stream);
+        return accumulate_impl(ctx, partial, d_zero, d_out, n, segs, p, ws + mp_.off("tree"), st);
     return COFHE_HIP_OK;
+}
+}  // namespace
+
+int cofhe_hip_scal_matmul_records(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_exp, const void *d_zero,
+                                  void *d_out, uint32_t n, uint32_t m, uint32_t p, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if ((uint64_t)n * p == 0) return COFHE_HIP_OK;
+    unsigned blocks;
+    if (int rc = compose_blocks((uint64_t)n * p * 2, &blocks)) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    WsUse use(ctx, st);
+    // window width: a table of 2^(w-2) odd powers per base costs that many compositions and is used by
+    // the p columns of its row, saving ~bits*(1/3 - 1/(w+1)) compositions in each; keep the tables under
+    // 1/8 of the device memory
+    const uint64_t nbase = (uint64_t)n * m * 2;
+    uint32_t w = 2, exp_bits = 0;                              // exp_bits: longest exponent of the call
+    if (m > 0) {
+        // per base: 2^(w-2) compositions for the table, then ~bits/(w+1) per column -- needs the exponent length
+        if (int rc = max_exp_bits(ctx, d_exp, (uint64_t)m * p, st, &exp_bits)) return rc;
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(hipMemGetInfo(&free_b, &total_b));
+        double best = (double)p * exp_bits / 3.0;                      // w = 2: plain NAF, no table
+        for (uint32_t cand = 3; cand <= 8; cand++) {
+            const uint64_t bytes = nbase * (1ull << (cand - 2)) * REC_WORDS * 4;
+            if (bytes > total_b / 8 || bytes > free_b / 2) break;
+            const double cost = (double)(1u << (cand - 2)) + (double)p * exp_bits / (cand + 1.0);
+            if (cost < best) {
+                best = cost;
+                w = cand;
+            }
+        }
+        if (ctx->opt_wnaf_width >= 2 && ctx->opt_wnaf_width <= 8) w = ctx->opt_wnaf_width;      // cofhe_hip_ctx_set_option
+    }
+    if (m >= (1u << 21)) return fail(COFHE_HIP_EINVAL, "inner dimension beyond 2^21");
+    // The product-tree form (matmul_tree_route) when there is something to pair up and enough outputs for the Horner
+    // chains to fill the GPU; small products keep the segmented lockstep chains (matmul_chains_route), which measured faster there
+    // (profiles/r04_a/tree_time.txt: 8x64.64x64 11.7 vs 12.8 ms, 64^3 21.6 vs 20.9, 32x256.256x256 k-bit 683 vs 673,
+    // 256^3 884 vs 787 ms -- chains vs tree).  "matmul_tree" = 0 / 1 pins the choice.
+    const bool use_tree = ctx->opt_matmul_tree == 1 || (ctx->opt_matmul_tree == -1 && m >= 8 && (uint64_t)n * p * 2 >= 4096);
+    if (use_tree && m > 0) {
+        bool taken = false;
+        if (int rc = matmul_tree_route(ctx, d_cts, d_exp, d_zero, d_out, n, m, p, w, exp_bits, st, &taken)) return rc;
+        if (taken) return COFHE_HIP_OK;
+    }
+    return matmul_chains_route(ctx, d_cts, d_exp, d_zero, d_out, n, m, p, w, exp_bits, st);
 }
 
 namespace {
@@ -1394,6 +1349,17 @@ int ensure_ftab(cofhe_hip_ctx *ctx, const uint32_t *f_record, uint32_t kbits, vo
     }
     return COFHE_HIP_OK;
 }
+// m = dlog(c2 o prod parts^-+1) for every ciphertext: the one launch of decryption and of the threshold combiner
+int decrypt_launch(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_parts, uint32_t n_parts, uint64_t negmask, void *d_out, uint64_t n_ct,
+                   uint32_t kbits, void *stream) {
+    unsigned blocks;
+    if (int rc = compose_blocks(n_ct, &blocks)) return rc;
+    launch_wg(ctx, k_decrypt3, k_decrypt, "k_decrypt3", "k_decrypt", blocks, (hipStream_t)stream, (const uint32_t *)d_cts,
+              (const uint32_t *)d_parts, n_parts, negmask, (const uint32_t *)ctx->d_ftab, (uint32_t *)d_out, n_ct, (int)kbits,
+              (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
 }  // namespace
 
 int cofhe_hip_decrypt_records(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_sk, const uint32_t *f_record,
@@ -1407,13 +1373,7 @@ int cofhe_hip_decrypt_records(cofhe_hip_ctx *ctx, const void *d_cts, const void 
     void *d_parts = nullptr;
     if (int rc = pow_shared_c1(ctx, d_cts, d_sk, nullptr, n_ct, (size_t)n_ct * REC_WORDS * 4, &d_parts, (hipStream_t)stream))
         return rc;
-    unsigned blocks;
-    if (int rc = compose_blocks(n_ct, &blocks)) return rc;
-    launch_wg(ctx, k_decrypt3, k_decrypt, "k_decrypt3", "k_decrypt", blocks, (hipStream_t)stream, (const uint32_t *)d_cts,
-              (const uint32_t *)d_parts, 1u, (uint64_t)0, (const uint32_t *)ctx->d_ftab, (uint32_t *)d_out, n_ct, (int)kbits,
-              (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    return decrypt_launch(ctx, d_cts, d_parts, 1u, 0, d_out, n_ct, kbits, stream);
 }
 
 int cofhe_hip_encrypt_records(cofhe_hip_ctx *ctx, const void *d_plain, const void *d_c1_pkr, const uint32_t *f_record,
@@ -1451,19 +1411,10 @@ int cofhe_hip_encrypt_records(cofhe_hip_ctx *ctx, const void *d_plain, const voi
         if (int rc = compose_blocks(total, &gblocks)) return rc;
         hipLaunchKernelGGL(k_gather_signed, dim3(gblocks), dim3(WG_BLOCK), 0, st, (const uint64_t *)d_tabs, (const uint32_t *)d_idx, total,
                            (const uint32_t *)ctx->d_one, buf[0]);
-        uint32_t mm = mmax;
-        int which = 0;
-        while (mm > 1) {
-            const uint32_t mh = (mm + 1) / 2;
-            unsigned blocks;
-            if (int rc = compose_blocks((uint64_t)mh * ne, &blocks)) return rc;
-            hipLaunchKernelGGL(k_compose_pairs, dim3(blocks), dim3(WG_BLOCK), 0, st, (const uint32_t *)buf[which], (const uint32_t *)ctx->d_one,
-                               buf[which ^ 1], 1u, mm, (uint32_t)ne, 0u, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
-            which ^= 1;
-            mm = mh;
-        }
+        const uint32_t *c2;
+        if (int rc = product_tree(ctx, buf[0], buf[1], buf[0], nullptr, 1u, mmax, (uint32_t)ne, nullptr, st, &c2)) return rc;
         const unsigned zblocks = (unsigned)std::min<uint64_t>((ne * 2 * REC_WORDS + 255) / 256, 4096);
-        hipLaunchKernelGGL(k_zip_ciphertexts, dim3(zblocks), dim3(256), 0, st, (const uint32_t *)d_c1_pkr, (const uint32_t *)buf[which], ne,
+        hipLaunchKernelGGL(k_zip_ciphertexts, dim3(zblocks), dim3(256), 0, st, (const uint32_t *)d_c1_pkr, c2, ne,
                            (uint32_t *)d_out + e0 * 2 * REC_WORDS);
         HIPCHK(hipGetLastError());
     }
@@ -1482,13 +1433,7 @@ int cofhe_hip_combine_part_decryptions_records(cofhe_hip_ctx *ctx, const void *d
     }
     if (n_ct == 0) return COFHE_HIP_OK;
     if (int rc = ensure_ftab(ctx, f_record, kbits, stream)) return rc;
-    unsigned blocks;
-    if (int rc = compose_blocks(n_ct, &blocks)) return rc;
-    launch_wg(ctx, k_decrypt3, k_decrypt, "k_decrypt3", "k_decrypt", blocks, (hipStream_t)stream, (const uint32_t *)d_cts,
-              (const uint32_t *)d_parts, n_parts, negmask, (const uint32_t *)ctx->d_ftab, (uint32_t *)d_out, n_ct, (int)kbits,
-              (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    return decrypt_launch(ctx, d_cts, d_parts, n_parts, negmask, d_out, n_ct, kbits, stream);
 }
 
 int cofhe_hip_time_compose(cofhe_hip_ctx *ctx, const void *d_a, const void *d_b, void *d_out, uint64_t n, int iters,
@@ -1590,6 +1535,59 @@ int cofhe_hip_timer_stop(cofhe_hip_ctx *ctx, void *timer, void *stream, float *m
 
 // ---- formats ---------------------------------------------------------------------------------
 namespace {
+// little-endian byte strings <-> limb records
+struct IntView {
+    const uint8_t *p;
+    size_t n;
+    bool neg;
+};
+
+int parse_tensor(const uint8_t *bytes, size_t len, size_t per_elem, uint32_t *ndim, uint32_t shape[8],
+                 std::vector<IntView> &ints) {
+    if (len < 4) return fail(COFHE_HIP_EINVAL, "tensor buffer too short");
+    uint32_t nd;
+    memcpy(&nd, bytes, 4);
+    if (nd > 8) return fail(COFHE_HIP_EINVAL, "tensor rank above 8");
+    if (len < 4 + 4ull * nd) return fail(COFHE_HIP_EINVAL, "tensor buffer too short");
+    uint64_t ne = 1;
+    for (uint32_t i = 0; i < nd; i++) {
+        memcpy(&shape[i], bytes + 4 + 4 * i, 4);
+        if (shape[i] != 0 && ne > (1ull << 40) / shape[i]) return fail(COFHE_HIP_EINVAL, "tensor too large");     // before the product can wrap
+        ne *= shape[i];
+    }
+    *ndim = nd;
+    const uint64_t cnt = ne * per_elem;
+    const size_t hdr = 4 + 4ull * nd + 8ull * cnt;
+    if (len < hdr) return fail(COFHE_HIP_EINVAL, "tensor buffer too short");
+    const uint8_t *tab = bytes + 4 + 4ull * nd;
+    const uint8_t *body = bytes + hdr;
+    const size_t blen = len - hdr;
+    ints.resize(cnt);
+    const uint64_t M = ~(1ull << 63);
+    for (uint64_t i = 0; i < cnt; i++) {
+        uint64_t o, o2;
+        memcpy(&o, tab + 8 * i, 8);
+        if (i + 1 < cnt) {
+            memcpy(&o2, tab + 8 * (i + 1), 8);
+            o2 &= M;
+        } else {
+            o2 = blen;
+        }
+        const uint64_t st = o & M;
+        if (o2 < st || o2 > blen) return fail(COFHE_HIP_EINVAL, "corrupt offset table");
+        ints[i] = IntView{body + st, (size_t)(o2 - st), (o >> 63) != 0};
+    }
+    return COFHE_HIP_OK;
+}
+
+bool put_limbs(uint32_t *dst, int words, const IntView &v) {
+    size_t n = sig_bytes(v.p, v.n);
+    if (n > (size_t)words * 4) return false;
+    memset(dst, 0, (size_t)words * 4);
+    memcpy(dst, v.p, n);     // little-endian host
+    return true;
+}
+
 // forms_per_elem = 2: ciphertext tensors (c1, c2); 1: partial-decryption tensors (one form each)
 int form_bytes_to_records(const uint8_t *bytes, size_t len, int forms_per_elem, uint32_t *ndim, uint32_t shape[8],
                           uint32_t **records, uint64_t *n_records) {
