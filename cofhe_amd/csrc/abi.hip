@@ -550,7 +550,8 @@ inline WsPlan plan_fixed_base(uint32_t n, uint32_t mmax) {
     return q;
 }
 // The fixed-base comb (comb.hpp): items are ciphertexts (kind 1 encrypt_fresh, 2 rerandomize: two columns each) or powers
-// (kind 0: one column each).  One chunk of `ne` items: [level_a: the fused first level, slots / 2 records per column]
+// (kind 0: one column each); kind 3, the plaintext addend, has one column per ciphertext (its c2), kind 4, the addend with
+// fresh randomness, an encryption's two columns and the leaf.  One chunk of `ne` items: [level_a: the fused first level, slots / 2 records per column]
 // [level_b: the next level, ceil(slots / 4) per column]; the levels above alternate between the two.
 constexpr uint64_t COMB_WS_LIMIT = 4ull << 30;               // one call's workspace, whatever n
 constexpr uint64_t COMB_CHUNK_MAX = 65536;                   // items per pass when nothing else limits it
@@ -562,11 +563,12 @@ struct CombCall {
 inline CombShape comb_shape_of(uint32_t kind, uint32_t w, uint32_t exp_bits, uint32_t kbits) {
     CombShape s{};
     s.w = w;
-    s.npos_r = comb_positions(exp_bits < COMB_EXP_BITS ? exp_bits : COMB_EXP_BITS, w);
-    s.npos_m = kind == 1 ? comb_positions(kbits, w) : 0u;
-    s.leaf = kind == 2 ? 1u : 0u;
-    s.halves = kind == 0 ? 1u : 2u;
+    s.npos_r = kind == 3 ? 0u : comb_positions(exp_bits < COMB_EXP_BITS ? exp_bits : COMB_EXP_BITS, w);
+    s.npos_m = kind == 1 || kind >= 3 ? comb_positions(kbits, w) : 0u;
+    s.leaf = kind >= 2 ? 1u : 0u;
+    s.halves = kind == 0 || kind == 3 ? 1u : 2u;
     s.kbits = kbits;
+    s.c2_only = kind == 3 ? 1u : 0u;
     return s;
 }
 inline WsPlan plan_comb_chunk(const CombShape &s, uint64_t ne) {
@@ -586,7 +588,8 @@ inline uint32_t comb_auto_width(uint64_t n, uint32_t exp_bits) {
 }
 inline CombCall comb_call(uint32_t kind, uint64_t n, uint32_t exp_bits, uint32_t kbits, uint32_t w_pin, uint64_t chunk_pin) {
     CombCall c{};
-    c.s = comb_shape_of(kind, w_pin ? w_pin : comb_auto_width(n, exp_bits), exp_bits, kbits);
+    // kind 3 has no r: its one exponent is m mod 2^k, so k picks the width (and a context that also encrypts shares the table of f)
+    c.s = comb_shape_of(kind, w_pin ? w_pin : comb_auto_width(n, kind == 3 ? kbits : exp_bits), exp_bits, kbits);
     c.slots = comb_slots(c.s);
     const uint64_t per_item = plan_comb_chunk(c.s, 1).total;
     uint64_t fit = (COMB_WS_LIMIT - 512) / per_item;
@@ -666,7 +669,15 @@ int cofhe_hip_compose_wide_records(cofhe_hip_ctx *ctx, const void *d_a, const vo
     return COFHE_HIP_OK;
 }
 
-int cofhe_hip_add_ciphertext_records(cofhe_hip_ctx *ctx, const void *d_a, const void *d_b, void *d_out, uint64_t n_ct, void *stream) {
+namespace {
+// the two builds of a ciphertext-pair kernel (k_add_ct / k_sub_ct and their three-per-CU forms) and their span names
+using CtPairKernel = void (*)(const uint32_t *, const uint32_t *, uint32_t *, uint64_t, const uint32_t *, const uint32_t *, int, uint32_t *, uint32_t);
+struct CtPairBuilds {
+    CtPairKernel k3, k;
+    const char *span3, *span;
+};
+// out[i] = a[i] (op) b[i] over n_ct ciphertexts: the c1 scan, the launch route that fits, the spread of a folded c1
+int ct_pair_launch(cofhe_hip_ctx *ctx, const CtPairBuilds &kb, const void *d_a, const void *d_b, void *d_out, uint64_t n_ct, void *stream) {
     if (n_ct == 0) return COFHE_HIP_OK;
     if (n_ct > (1ull << 40)) return fail(COFHE_HIP_EINVAL, "tensor too large");
     unsigned blocks;
@@ -682,7 +693,7 @@ int cofhe_hip_add_ciphertext_records(cofhe_hip_ctx *ctx, const void *d_a, const 
     unsigned blocks_shared;
     if (int rc = compose_blocks(n_ct + 1, &blocks_shared)) return rc;
     const auto add = [&](unsigned grid, uint32_t only) {
-        launch_wg(ctx, k_add_ct3, k_add_ct, "k_add_ct3", "k_add_ct", grid, st, (const uint32_t *)d_a, (const uint32_t *)d_b, (uint32_t *)d_out,
+        launch_wg(ctx, kb.k3, kb.k, kb.span3, kb.span, grid, st, (const uint32_t *)d_a, (const uint32_t *)d_b, (uint32_t *)d_out,
                   n_ct, (const uint32_t *)flag, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status, only);
     };
     if (!fits_three_per_cu(blocks) && fits_three_per_cu(blocks_shared)) {
@@ -694,6 +705,33 @@ int cofhe_hip_add_ciphertext_records(cofhe_hip_ctx *ctx, const void *d_a, const 
         add(blocks, 0u);     // even with distinct c1, a grid that fits is resident at three workgroups per CU
     }
     if (n_ct > 1) hipLaunchKernelGGL(k_c1_spread, dim3(scan_blocks(n_ct)), dim3(256), 0, st, (uint32_t *)d_out, n_ct, (const uint32_t *)flag);
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+}  // namespace
+
+int cofhe_hip_add_ciphertext_records(cofhe_hip_ctx *ctx, const void *d_a, const void *d_b, void *d_out, uint64_t n_ct, void *stream) {
+    return ct_pair_launch(ctx, CtPairBuilds{k_add_ct3, k_add_ct, "k_add_ct3", "k_add_ct"}, d_a, d_b, d_out, n_ct, stream);
+}
+int cofhe_hip_sub_ciphertext_records(cofhe_hip_ctx *ctx, const void *d_a, const void *d_b, void *d_out, uint64_t n_ct, void *stream) {
+    return ct_pair_launch(ctx, CtPairBuilds{k_sub_ct3, k_sub_ct, "k_sub_ct3", "k_sub_ct"}, d_a, d_b, d_out, n_ct, stream);
+}
+
+namespace {
+// out[r] = in[r]^-1 for the records r = i stride + offset, i < n
+int invert_launch(cofhe_hip_ctx *ctx, const void *d_in, void *d_out, uint64_t n, uint32_t stride, uint32_t offset, hipStream_t st) {
+    unsigned blocks;
+    if (int rc = compose_blocks(n, &blocks)) return rc;
+    ProfScope ps(ctx, "k_invert_records", st);
+    hipLaunchKernelGGL(k_invert_records, dim3(blocks), dim3(WG_BLOCK), 0, st, (const uint32_t *)d_in, (uint32_t *)d_out, n, stride, offset);
+    return COFHE_HIP_OK;
+}
+}  // namespace
+int cofhe_hip_invert_records(cofhe_hip_ctx *ctx, const void *d_in, void *d_out, uint64_t n_records, void *stream) {
+    if (n_records == 0) return COFHE_HIP_OK;
+    if (!d_in || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    if (int rc = invert_launch(ctx, d_in, d_out, n_records, 1u, 0u, (hipStream_t)stream)) return rc;
     HIPCHK(hipGetLastError());
     return COFHE_HIP_OK;
 }
@@ -902,11 +940,12 @@ int cofhe_hip_pow_form_records(cofhe_hip_ctx *ctx, const void *d_base, const voi
 // k_compose_pairs levels of a pairwise tree per chunk, ~floor(bits/w) + 1 compositions per power and no squarings.
 namespace {
 int comb_check(uint64_t kind, uint64_t n, uint64_t exp_bits, uint64_t kbits, uint64_t w, uint64_t chunk) {
-    if (kind > 2) return fail(COFHE_HIP_EINVAL, "comb: kind 0 (powers), 1 (fresh encryption) or 2 (re-randomisation)");
+    if (kind > 4)
+        return fail(COFHE_HIP_EINVAL, "comb: kind 0 (powers), 1 (fresh encryption), 2 (re-randomisation), 3 (plaintext addend) or 4 (addend with randomness)");
     if (n > (1ull << 36)) return fail(COFHE_HIP_EINVAL, "comb: too many items");
     if (exp_bits > COMB_EXP_BITS) return fail(COFHE_HIP_EINVAL, "comb: exponents have at most 992 bits");
     if (w != 0 && (w < (uint64_t)COMB_W_MIN || w > (uint64_t)COMB_W_MAX)) return fail(COFHE_HIP_EINVAL, "comb: w is 0 (automatic) or 2..10");
-    if (kind == 1 && (kbits == 0 || 2 * kbits + 1 > (uint64_t)PLIMBS * 32 || kbits > EXP_MAG_WORDS * 32 - 1))
+    if ((kind == 1 || kind >= 3) && (kbits == 0 || 2 * kbits + 1 > (uint64_t)PLIMBS * 32 || kbits > EXP_MAG_WORDS * 32 - 1))
         return fail(COFHE_HIP_EINVAL, "k out of range");
     if (chunk > (1ull << 32)) return fail(COFHE_HIP_EINVAL, "comb: chunk out of range");
     return COFHE_HIP_OK;
@@ -949,46 +988,69 @@ int comb_table(cofhe_hip_ctx *ctx, const uint32_t *base_record, uint32_t w, uint
 }
 
 // kind 0: out[i] = base0^r[i] (n records); 1: out[2i] = h^r[i], out[2i+1] = pk^r[i] o f^(m[i] mod 2^k); 2: out[2i] =
-// leaf[2i] o h^r[i], out[2i+1] = leaf[2i+1] o pk^r[i].  bases: host records of (base0 | h, pk, f) as the kind needs.
+// leaf[2i] o h^r[i], out[2i+1] = leaf[2i+1] o pk^r[i]; 3: out[2i+1] = leaf[2i+1] o f^m[i], the records 2i copied (d_out
+// other than d_leaf) -- no r, no read-back; 4: out[2i] = leaf[2i] o h^r[i], out[2i+1] = leaf[2i+1] o pk^r[i] o f^m[i].
+// mode (kinds 3, 4): 0 as written, 1 m negated (ct - m), 2 every leaf inverted (m - ct; kind 3 inverts the records 2i too).
+// bases: host records of (base0 | h, pk, f) as the kind needs.
 int comb_run(cofhe_hip_ctx *ctx, uint32_t kind, const uint32_t *const bases[3], const void *d_r, const void *d_m, const void *d_leaf,
-             void *d_out, uint64_t n, uint32_t kbits, void *stream) {
+             void *d_out, uint64_t n, uint32_t kbits, void *stream, int mode = 0) {
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    for (int b = 0; b < (kind == 0 ? 1 : kind == 1 ? 3 : 2); b++)
-        if (!bases[b]) return fail(COFHE_HIP_EINVAL, "null argument");
+    static const unsigned NEEDS[5] = {1u, 7u, 3u, 4u, 7u};       // which of (base0 | h, pk, f) a kind reads
+    if (kind > 4) return fail(COFHE_HIP_EINVAL, "comb: no such kind");
+    for (int b = 0; b < 3; b++)
+        if ((NEEDS[kind] >> b & 1u) && !bases[b]) return fail(COFHE_HIP_EINVAL, "null argument");
     if (int rc = comb_check(kind, n, 0, kbits, 0, 0)) return rc;
     if (n == 0) return COFHE_HIP_OK;
-    if (!d_r || !d_out || (kind == 1 && !d_m) || (kind == 2 && !d_leaf)) return fail(COFHE_HIP_EINVAL, "null argument");
+    const bool has_r = kind != 3, has_m = kind == 1 || kind >= 3, has_leaf = kind >= 2;
+    if (!d_out || (has_r && !d_r) || (has_m && !d_m) || (has_leaf && !d_leaf)) return fail(COFHE_HIP_EINVAL, "null argument");
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     WsUse use(ctx, st);
     const CombState &cs = comb_state(ctx);
-    // the tree's shape follows the longest exponent: the one read-back of the call
+    // the tree's shape follows the longest exponent: the one read-back of the call (kind 3: its shape follows from k alone)
     uint32_t exp_bits = 0;
-    if (int rc = max_exp_bits(ctx, d_r, n, st, &exp_bits)) return rc;
-    const CombCall cc = comb_call(kind, n, exp_bits, kbits, cs.opt_width, cs.opt_chunk);
+    if (has_r)
+        if (int rc = max_exp_bits(ctx, d_r, n, st, &exp_bits)) return rc;
+    CombCall cc = comb_call(kind, n, exp_bits, kbits, cs.opt_width, cs.opt_chunk);
+    cc.s.m_neg = mode == 1 ? 1u : 0u;
+    cc.s.leaf_inv = mode == 2 ? 1u : 0u;
     const uint64_t call_stamp = ++comb_state(ctx).clock;
     const uint32_t *tabs[3] = {nullptr, nullptr, nullptr};
-    for (int b = 0; b < (kind == 0 ? 1 : kind == 1 ? 3 : 2); b++)
-        if (int rc = comb_table(ctx, bases[b], cc.s.w, call_stamp, st, &tabs[b])) return rc;
+    for (int b = 0; b < 3; b++)
+        if (NEEDS[kind] >> b & 1u)
+            if (int rc = comb_table(ctx, bases[b], cc.s.w, call_stamp, st, &tabs[b])) return rc;
     const WsPlan wp = plan_comb_chunk(cc.s, cc.chunk);
     if (int rc = ensure_workspace(ctx, wp.total, st)) return rc;
     uint8_t *ws = (uint8_t *)ctx->workspace;
     uint32_t *buf[2] = {(uint32_t *)(ws + wp.off("level_a")), (uint32_t *)(ws + wp.off("level_b"))};
-    const uint32_t H = cc.s.halves;
+    // R: records per item in the caller's tensors (kind 3 has one column, the second record of a ciphertext)
+    const uint32_t H = cc.s.halves, R = kind == 3 ? 2u : H;
+    const size_t rec_bytes = (size_t)REC_WORDS * 4;
+    if (kind == 3) {                 // the c1 records: inverted (m - ct), copied, or left where they are
+        if (mode == 2) {
+            if (int rc = invert_launch(ctx, d_leaf, d_out, n, 2u, 0u, st)) return rc;
+        } else if (d_out != d_leaf) {
+            HIPCHK(hipMemcpy2DAsync(d_out, 2 * rec_bytes, d_leaf, 2 * rec_bytes, rec_bytes, n, hipMemcpyDeviceToDevice, st));
+        }
+    }
     for (uint64_t e0 = 0; e0 < n; e0 += cc.chunk) {
         const uint64_t ne = n - e0 < cc.chunk ? n - e0 : cc.chunk, ncols = ne * H;
-        uint32_t *out = (uint32_t *)d_out + e0 * H * REC_WORDS;
+        uint32_t *out = (uint32_t *)d_out + e0 * R * REC_WORDS;
         uint32_t mm = cc.slots / 2;
         unsigned blocks;
         if (int rc = compose_blocks(ncols * mm, &blocks)) return rc;
         {
             ProfScope ps(ctx, "k_comb_first", st);
             hipLaunchKernelGGL(k_comb_first, dim3(blocks), dim3(WG_BLOCK), 0, st, cc.s, tabs[0], tabs[1], tabs[2],
-                               (const uint32_t *)d_r + e0 * EXP_REC_WORDS, d_m ? (const uint32_t *)d_m + e0 * EXP_REC_WORDS : nullptr,
-                               d_leaf ? (const uint32_t *)d_leaf + e0 * H * REC_WORDS : nullptr, ncols, (const uint32_t *)ctx->d_one,
-                               mm == 1 ? out : buf[0], (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+                               d_r ? (const uint32_t *)d_r + e0 * EXP_REC_WORDS : nullptr, d_m ? (const uint32_t *)d_m + e0 * EXP_REC_WORDS : nullptr,
+                               d_leaf ? (const uint32_t *)d_leaf + e0 * R * REC_WORDS : nullptr, ncols, (const uint32_t *)ctx->d_one,
+                               mm == 1 && kind != 3 ? out : buf[0], (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
         }
-        if (int rc = product_tree(ctx, buf[0], buf[1], buf[0], out, 1u, mm, (uint32_t)ncols, "k_compose_pairs", st, nullptr)) return rc;
+        // kind 3's columns are every second record of the output: its tree ends in the workspace and one strided copy places it
+        const uint32_t *top = nullptr;
+        if (int rc = product_tree(ctx, buf[0], buf[1], buf[0], kind == 3 ? nullptr : out, 1u, mm, (uint32_t)ncols, "k_compose_pairs", st, &top))
+            return rc;
+        if (kind == 3) HIPCHK(hipMemcpy2DAsync(out + REC_WORDS, 2 * rec_bytes, top, rec_bytes, rec_bytes, ne, hipMemcpyDeviceToDevice, st));
         HIPCHK(hipGetLastError());
     }
     return COFHE_HIP_OK;
@@ -1009,6 +1071,13 @@ int cofhe_hip_rerandomize_records(cofhe_hip_ctx *ctx, const void *d_cts, const v
                                   void *d_out, uint64_t n_ct, void *stream) {
     const uint32_t *bases[3] = {h_record, pk_record, nullptr};
     return comb_run(ctx, 2, bases, d_r, nullptr, d_cts, d_out, n_ct, 0, stream);
+}
+int cofhe_hip_add_plain_records(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_plain, const void *d_r, const uint32_t *h_record,
+                                const uint32_t *pk_record, const uint32_t *f_record, void *d_out, uint64_t n_ct, uint32_t kbits, int mode,
+                                void *stream) {
+    if (mode < 0 || mode > 2) return fail(COFHE_HIP_EINVAL, "add_plain: mode 0 (ct + m), 1 (ct - m) or 2 (m - ct)");
+    const uint32_t *bases[3] = {d_r ? h_record : nullptr, d_r ? pk_record : nullptr, f_record};
+    return comb_run(ctx, d_r ? 4u : 3u, bases, d_r, d_plain, d_cts, d_out, n_ct, kbits, stream, mode);
 }
 int cofhe_hip_comb_shape(uint32_t kind, uint64_t n, uint32_t exp_bits, uint32_t kbits, uint32_t w_pin, uint64_t chunk_pin, uint32_t *w,
                          uint32_t *slots, uint64_t *chunk) {
@@ -1486,7 +1555,7 @@ int cofhe_hip_workspace_plan(const char *op, const uint64_t *args, uint32_t n_ar
     } else if (o == "fixed_base" && need(2)) {
         p = plan_fixed_base((uint32_t)args[0], (uint32_t)args[1]);
     } else if (o == "comb" && need(6)) {
-        // kind, n items, exp_bits, kbits, w (0: automatic), chunk (0: automatic): the regions of one (the largest) chunk
+        // kind (0..4), n items, exp_bits, kbits, w (0: automatic), chunk (0: automatic): the regions of one (the largest) chunk
         if (int rc = comb_check(args[0], args[1], args[2], args[3], args[4], args[5])) return rc;
         const CombCall cc = comb_call((uint32_t)args[0], args[1], (uint32_t)args[2], (uint32_t)args[3], (uint32_t)args[4], args[5]);
         p = plan_comb_chunk(cc.s, cc.chunk);
@@ -1732,10 +1801,9 @@ int finish(cofhe_hip_ctx *ctx, const DevBuf &dout, uint64_t nrec, uint32_t ndim,
     *outlen = len;
     return COFHE_HIP_OK;
 }
-}  // namespace
-
-int cofhe_hip_add_ciphertext_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *t1, size_t l1, const uint8_t *t2, size_t l2,
-                                           uint8_t **out, size_t *outlen) {
+// two ciphertext tensors of equal shape through one of the ciphertext-pair entry points
+int ct_pair_bytes(cofhe_hip_ctx *ctx, int (*op)(cofhe_hip_ctx *, const void *, const void *, void *, uint64_t, void *), const uint8_t *t1, size_t l1,
+                  const uint8_t *t2, size_t l2, uint8_t **out, size_t *outlen) {
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     uint32_t nd1, nd2, s1[8], s2[8];
     uint64_t n1, n2;
@@ -1746,8 +1814,32 @@ int cofhe_hip_add_ciphertext_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *t1
     if (nd1 != nd2 || memcmp(s1, s2, 4 * nd1) != 0) return fail(COFHE_HIP_ESHAPE, "Tensor shapes must be equal");
     const size_t bytes = (size_t)n1 * REC_WORDS * 4;
     if (int rc = dc.get(ctx, bytes ? bytes : 4)) return rc;
-    if (int rc = cofhe_hip_add_ciphertext_records(ctx, da.p, db.p, dc.p, n1 / 2, nullptr)) return rc;
+    if (int rc = op(ctx, da.p, db.p, dc.p, n1 / 2, nullptr)) return rc;
     return finish(ctx, dc, n1, nd1, s1, out, outlen);
+}
+}  // namespace
+
+int cofhe_hip_add_ciphertext_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *t1, size_t l1, const uint8_t *t2, size_t l2,
+                                           uint8_t **out, size_t *outlen) {
+    return ct_pair_bytes(ctx, cofhe_hip_add_ciphertext_records, t1, l1, t2, l2, out, outlen);
+}
+int cofhe_hip_sub_ciphertext_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *t1, size_t l1, const uint8_t *t2, size_t l2,
+                                           uint8_t **out, size_t *outlen) {
+    return ct_pair_bytes(ctx, cofhe_hip_sub_ciphertext_records, t1, l1, t2, l2, out, outlen);
+}
+int cofhe_hip_add_plaintext_tensor_bytes(cofhe_hip_ctx *ctx, const uint8_t *cts, size_t lc, const uint8_t *pt, size_t lp,
+                                         const uint32_t *f_record, uint32_t kbits, int mode, uint8_t **out, size_t *outlen) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (mode < 0 || mode > 2) return fail(COFHE_HIP_EINVAL, "add_plain: mode 0 (ct + m), 1 (ct - m) or 2 (m - ct)");
+    uint32_t ndc, ndp, sc[8], sp[8];
+    uint64_t nr, ne;
+    HIPCHK(hipSetDevice(ctx->device));
+    DevBuf dc, dp;
+    if (int rc = load_tensor(ctx, cts, lc, 2, dc, &ndc, sc, &nr)) return rc;
+    if (int rc = load_tensor(ctx, pt, lp, 0, dp, &ndp, sp, &ne)) return rc;
+    if (ndc != ndp || memcmp(sc, sp, 4 * ndc) != 0 || nr != 2 * ne) return fail(COFHE_HIP_ESHAPE, "Tensor shapes must be equal");
+    if (int rc = cofhe_hip_add_plain_records(ctx, dc.p, dp.p, nullptr, nullptr, nullptr, f_record, dc.p, ne, kbits, mode, nullptr)) return rc;
+    return finish(ctx, dc, nr, ndc, sc, out, outlen);
 }
 
 int cofhe_hip_scal_ciphertext_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *s, size_t ls, const uint8_t *cts, size_t lc,

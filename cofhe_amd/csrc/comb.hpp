@@ -13,10 +13,14 @@
 //   [0, npos_r)                 positions of r against the column's r table (half 0: h or the base, half 1: pk)
 //   [npos_r, npos_r + npos_m)   positions of m mod 2^k against the table of f -- half 1 of an encryption only; the
 //                               other half has principal forms there
-//   npos_r + npos_m             the leaf (re-randomisation): record 2i + h of the input ciphertexts
+//   npos_r + npos_m             the leaf (re-randomisation, plaintext addend): record 2i + h of the input ciphertexts,
+//                               inverted where the shape says so (m - ct)
 //   up to an even count         principal forms
 // Columns are the output records: (c1 of ciphertext 0, c2 of ciphertext 0, c1 of ciphertext 1, ...), or one per
 // exponent for plain powers.  The fused first level composes slots 2s and 2s + 1 of a column; k_compose_pairs does the rest.
+// A plaintext addend without randomness (c2_only) has ONE column per ciphertext, its c2: no r positions, the positions
+// of m, the leaf 2i + 1 -- ct + m = (c1, c2 o f^m) spends nothing on c1.  With randomness it is an encryption's two
+// columns plus the leaf: (c1 o h^r, c2 o pk^r o f^m) in one tree.
 #pragma once
 #include "qf.hpp"
 
@@ -60,7 +64,11 @@ struct CombShape {
     uint32_t npos_m;    // positions of m mod 2^k (encryption), else 0
     uint32_t leaf;      // 1: one slot holds the input record (re-randomisation)
     uint32_t halves;    // columns per item: 2 (ciphertexts) or 1 (plain powers)
-    uint32_t kbits;     // k (encryption)
+    uint32_t kbits;     // k (encryption, plaintext addend)
+    // the plaintext addend; zero in every other call
+    uint32_t c2_only;   // 1: one column per ciphertext, its c2 (half 1, leaf record 2i + 1)
+    uint32_t m_neg;     // 1: the digits of m change sign (ct - m)
+    uint32_t leaf_inv;  // 1: the leaf is inverted (m - ct)
 };
 constexpr uint32_t comb_slots(const CombShape &s) { return (s.npos_r + s.npos_m + s.leaf + 1u) & ~1u; }
 
@@ -82,7 +90,7 @@ CF_DEV CombSel comb_select(const CombShape &s, uint32_t h, uint32_t slot, const 
             const int j = (int)(slot - s.npos_r);
             const int d = comb_digit(m_exp, j, (int)s.w, (int)s.kbits);          // f has order 2^k: m mod 2^k
             o.pos = j;
-            o.digit = m_exp[EXP_MAG_WORDS] ? -d : d;
+            o.digit = ((m_exp[EXP_MAG_WORDS] != 0) != (s.m_neg != 0)) ? -d : d;
             o.table = d != 0 ? 2 : -1;
         }
     } else if (s.leaf && slot == s.npos_r + s.npos_m) {

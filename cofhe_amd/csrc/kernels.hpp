@@ -1,7 +1,8 @@
 // kernels.hpp -- one declaration of every kernel that abi.hip launches.  The definitions, with their
 // __launch_bounds__, are in cofhe_hip.hip (the throughput kernels, in three COFHE_PART passes) and wide.hip
 // (the latency kernels); wire.hip launches its own kernels.  A declaration that matches no definition is an
-// undefined symbol when the library is loaded (tests/test_cabi.py).  comb.hip holds the two kernels of the fixed-base comb.
+// undefined symbol when the library is loaded (tests/test_cabi.py).  comb.hip holds the two kernels of the fixed-base comb,
+// affine.hip the ciphertext difference and the record inverse.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -113,4 +114,13 @@ __global__ void k_comb_first(cofhe::CombShape s, const uint32_t *__restrict__ ta
                              const uint32_t *__restrict__ tabf, const uint32_t *__restrict__ r_exps, const uint32_t *__restrict__ m_exps,
                              const uint32_t *__restrict__ leaf, uint64_t ncols, const uint32_t *__restrict__ one_rec, uint32_t *__restrict__ out,
                              const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status);
+
+// ciphertext differences and record inverses (affine.hip): k_add_ct's protocol with the second operand inverted
+__global__ void k_sub_ct(const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, uint32_t *__restrict__ out, uint64_t n_ct,
+                         const uint32_t *__restrict__ flag, const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status,
+                         uint32_t only);
+__global__ void k_sub_ct3(const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, uint32_t *__restrict__ out, uint64_t n_ct,
+                          const uint32_t *__restrict__ flag, const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status,
+                          uint32_t only);
+__global__ void k_invert_records(const uint32_t *in, uint32_t *out, uint64_t n, uint32_t stride, uint32_t offset);
 }  // namespace cofhe_k

@@ -92,6 +92,26 @@ class Engine:
                                                            C.c_char_p(t2), C.c_size_t(len(t2)), C.byref(out), C.byref(n)))
         return self._take(out, n)
 
+    def sub_ciphertext_tensors(self, t1: bytes, t2: bytes) -> bytes:
+        """t1 - t2 element-wise (the compute node's SUBTRACT): one composition per record, with the inverse of t2's forms"""
+        out = C.POINTER(C.c_uint8)()
+        n = C.c_size_t()
+        _chk(self.L.cofhe_hip_sub_ciphertext_tensors_bytes(self.ctx, C.c_char_p(t1), C.c_size_t(len(t1)),
+                                                           C.c_char_p(t2), C.c_size_t(len(t2)), C.byref(out), C.byref(n)))
+        return self._take(out, n)
+
+    def add_plaintext_tensor(self, cts: bytes, pt: bytes, f_record, kbits: int, mode: int = 0) -> bytes:
+        """mode 0: cts + pt, 1: cts - pt, 2: pt - cts, without an encryption: (c1, c2 o f^m); f_record: host uint32[168]"""
+        import numpy as np
+        f = np.ascontiguousarray(f_record, dtype=np.uint32)
+        assert f.size == 168
+        out = C.POINTER(C.c_uint8)()
+        n = C.c_size_t()
+        _chk(self.L.cofhe_hip_add_plaintext_tensor_bytes(self.ctx, C.c_char_p(cts), C.c_size_t(len(cts)), C.c_char_p(pt), C.c_size_t(len(pt)),
+                                                         f.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_uint32(kbits), C.c_int(mode),
+                                                         C.byref(out), C.byref(n)))
+        return self._take(out, n)
+
     def scal_ciphertext_tensors(self, s: bytes, cts: bytes, zero: bytes = None) -> bytes:
         out = C.POINTER(C.c_uint8)()
         n = C.c_size_t()
@@ -197,6 +217,32 @@ class Engine:
         """ciphertext-level add: folds the shared c1 of encrypt_tensor-made operands (n + 1 compositions, not 2 n)"""
         _chk(self.L.cofhe_hip_add_ciphertext_records(self.ctx, C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_out),
                                                      C.c_uint64(n_ciphertexts), C.c_void_p(stream)))
+
+    def sub_ciphertext_records(self, d_a, d_b, d_out, n_ciphertexts, stream=0):
+        """out[i] = a[i] - b[i]: a o b^-1 per record, folding and launch routes as add_ciphertext_records; d_out may be d_a or d_b"""
+        _chk(self.L.cofhe_hip_sub_ciphertext_records(self.ctx, C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_out),
+                                                     C.c_uint64(n_ciphertexts), C.c_void_p(stream)))
+
+    def invert_records(self, d_in, d_out, n_records, stream=0):
+        """out[i] = in[i]^-1 on form records (a ciphertext tensor: Enc(-m) at no composition); in place allowed"""
+        _chk(self.L.cofhe_hip_invert_records(self.ctx, C.c_void_p(d_in), C.c_void_p(d_out), C.c_uint64(n_records), C.c_void_p(stream)))
+
+    def add_plain_records(self, d_cts, d_plain, f_record, d_out, n_ciphertexts, kbits, mode=0, d_r=None, h_record=None, pk_record=None,
+                          stream=0):
+        """mode 0: ct + m, 1: ct - m, 2: m - ct (d_plain: n exponent records).  Without d_r: (c1, c2 o f^m), deterministic and
+        purely stream-ordered; with d_r (n exponent records) and the host records h, pk: fresh randomness in the same tree.
+        d_out may be d_cts."""
+        import numpy as np
+        f = np.ascontiguousarray(f_record, dtype=np.uint32)
+        assert f.size == 168
+        hp = [None, None]
+        if d_r is not None:
+            hp = [np.ascontiguousarray(x, dtype=np.uint32) for x in (h_record, pk_record)]
+            assert all(x.size == 168 for x in hp)
+        _chk(self.L.cofhe_hip_add_plain_records(self.ctx, C.c_void_p(d_cts), C.c_void_p(d_plain), C.c_void_p(d_r),
+                                                *[x.ctypes.data_as(C.c_void_p) if x is not None else C.c_void_p() for x in hp],
+                                                f.ctypes.data_as(C.c_void_p), C.c_void_p(d_out), C.c_uint64(n_ciphertexts), C.c_uint32(kbits),
+                                                C.c_int(mode), C.c_void_p(stream)))
 
     def pow_records(self, d_base, d_exp, d_out, n_ciphertexts, stream=0):
         _chk(self.L.cofhe_hip_pow_records(self.ctx, C.c_void_p(d_base), C.c_void_p(d_exp), C.c_void_p(d_out),

@@ -744,6 +744,57 @@ class HIPCryptoSystem {
         return r;
     }
 
+    // ---- differences and plaintext addends without a negation or an encryption ----------------------------------------------
+    // a - b element-wise: (a.c1 o b.c1^-1, a.c2 o b.c2^-1), one composition per record (the inverse of a reduced form is a
+    // sign flip) where negate + add spends k + 2.  The compute node's SUBTRACT, which the reference answers "Not implemented"
+    // (include/node/compute_request_handler.hpp:67-76, 342-344); shapes and ownership as add_ciphertext_tensors.
+    Tensor<CipherText *> sub_ciphertext_tensors(const PublicKey &pk, const Tensor<CipherText *> &ct1,
+                                                const Tensor<CipherText *> &ct2) const {
+        if (ct1.is_zero_degree() && ct2.is_zero_degree())
+            return Tensor<CipherText *>(new CipherText(sub_ciphertexts(pk, *ct1.get_value(), *ct2.get_value())));
+        if (ct1.is_zero_degree() != ct2.is_zero_degree() || ct1.shape() != ct2.shape())
+            throw std::invalid_argument("Tensor shapes must be equal");
+        DeviceTensor a = upload(ct1), b = upload(ct2);
+        DeviceTensor r = sub_ciphertext_tensors(a, b);
+        rerandomize_result(pk, r);
+        return download(std::move(r));
+    }
+    // scalar form, re-randomised under set_rerandomize as add_ciphertexts is
+    CipherText sub_ciphertexts(const PublicKey &pk, const CipherText &ct1, const CipherText &ct2) const {
+        Tensor<CipherText *> t1(1, const_cast<CipherText *>(&ct1)), t2(1, const_cast<CipherText *>(&ct2));
+        DeviceTensor a = upload(t1), b = upload(t2);
+        DeviceTensor d = sub_ciphertext_tensors(a, b);
+        Tensor<CipherText *> r = download(d);                      // eager copy: the element outlives the block
+        CipherText out = *r.at(0);
+        delete r.at(0);
+        return rerandomized(pk, out);
+    }
+    // (c1^-1, c2^-1): an encryption of -m mod 2^k at no composition.  Not the ciphertext negate_ciphertext_tensor returns
+    // (ct^(2^k - 1), tensor_ops.inl:135-195, kept as it is); the plaintexts agree.  Deterministic in every mode.
+    Tensor<CipherText *> invert_ciphertext_tensor(const Tensor<CipherText *> &ct) const {
+        if (ct.is_zero_degree()) {
+            Tensor<CipherText *> r = invert_ciphertext_tensor(Tensor<CipherText *>(1, ct.get_value()));
+            return Tensor<CipherText *>(r.at(0));
+        }
+        DeviceTensor in = upload(ct);
+        DeviceTensor out = alloc(ct.shape(), ct.num_elements());
+        check(cofhe_hip_invert_records(ctx_, in.ptr_, out.ptr_, 2 * in.n_, nullptr));
+        return download(std::move(out));
+    }
+    // ct + pt, ct - pt, pt - ct element-wise without encrypting pt: (c1, c2 o f^(+-pt)) against the cached table of f, where
+    // the node's mixed ADD (compute_request_handler.hpp:384-403, 452-470) encrypts the plaintext -- h^r, pk^r, f^m -- and adds.
+    // A tensor that shared its c1 still does afterwards.  In TensorRandomness::PerElement mode the same tree also carries a
+    // fresh r per element: (c1 o h^r, c2 o pk^r o f^(+-pt)).
+    Tensor<CipherText *> add_plaintext_tensor(const PublicKey &pk, const Tensor<CipherText *> &ct, const Tensor<PlainText *> &pt) const {
+        return plaintext_addend(pk, ct, pt, 0);
+    }
+    Tensor<CipherText *> sub_plaintext_tensor(const PublicKey &pk, const Tensor<CipherText *> &ct, const Tensor<PlainText *> &pt) const {
+        return plaintext_addend(pk, ct, pt, 1);
+    }
+    Tensor<CipherText *> plaintext_sub_ciphertext_tensor(const PublicKey &pk, const Tensor<PlainText *> &pt, const Tensor<CipherText *> &ct) const {
+        return plaintext_addend(pk, ct, pt, 2);
+    }
+
     // ---- device-resident variants -------------------------------------------------------------
     // the block behind a tensor whose elements are, in order, ALL the elements of one device block (the result of
     // a previous operation handed back unchanged); nullptr otherwise
@@ -808,6 +859,12 @@ class HIPCryptoSystem {
         if (a.shape_ != b.shape_) throw std::invalid_argument("Tensor shapes must be equal");
         DeviceTensor r = alloc(a.shape_, a.n_);
         check(cofhe_hip_add_ciphertext_records(ctx_, a.ptr_, b.ptr_, r.ptr_, a.n_, nullptr));
+        return r;
+    }
+    DeviceTensor sub_ciphertext_tensors(const DeviceTensor &a, const DeviceTensor &b) const {
+        if (a.shape_ != b.shape_) throw std::invalid_argument("Tensor shapes must be equal");
+        DeviceTensor r = alloc(a.shape_, a.n_);
+        check(cofhe_hip_sub_ciphertext_records(ctx_, a.ptr_, b.ptr_, r.ptr_, a.n_, nullptr));
         return r;
     }
     void synchronize() const { check(cofhe_hip_stream_sync(ctx_, nullptr)); }
@@ -1148,6 +1205,38 @@ class HIPCryptoSystem {
     // a result of this object (its own block, nobody else's view) re-randomised in place in PerElement mode
     void rerandomize_result(const PublicKey &pk, DeviceTensor &t) const {
         if (tensor_randomness_ == TensorRandomness::PerElement) rerandomize_into(pk, t, t);
+    }
+    // mode 0: ct + pt, 1: ct - pt, 2: pt - ct (cofhe_hip_add_plain_records); 0-D in, 0-D out
+    Tensor<CipherText *> plaintext_addend(const PublicKey &pk, const Tensor<CipherText *> &ct, const Tensor<PlainText *> &pt, int mode) const {
+        if (ct.is_zero_degree() && pt.is_zero_degree()) {
+            Tensor<CipherText *> r = plaintext_addend(pk, Tensor<CipherText *>(1, ct.get_value()), Tensor<PlainText *>(1, pt.get_value()), mode);
+            return Tensor<CipherText *>(r.at(0));
+        }
+        if (ct.is_zero_degree() != pt.is_zero_degree() || ct.shape() != pt.shape()) throw std::invalid_argument("Tensor shapes must be equal");
+        const size_t E = ct.num_elements();
+        const bool fresh = tensor_randomness_ == TensorRandomness::PerElement;
+        Tensor<PlainText *> pflat = pt;
+        pflat.flatten();
+        std::vector<uint32_t> plain(E * EXPW, 0), ex, hrec(REC, 0), pkrec(REC, 0), frec(REC, 0);
+        for (size_t i = 0; i < E; i++) pack_exponent(*pflat[i], &plain[i * EXPW]);
+        pack_form(f_, frec.data());
+        void *dpl = nullptr, *dr = nullptr;
+        check(cofhe_hip_malloc(ctx_, plain.size() * 4 + 4, &dpl)); Guard g1{ctx_, dpl};
+        check(cofhe_hip_upload(ctx_, dpl, plain.data(), plain.size() * 4, nullptr));
+        Guard g2{ctx_, nullptr};
+        if (fresh && E) {
+            ex = draw_randomness(E);
+            pack_form(h_, hrec.data());
+            pack_form(pk, pkrec.data());
+            check(cofhe_hip_malloc(ctx_, ex.size() * 4, &dr));
+            g2.p = dr;
+            check(cofhe_hip_upload(ctx_, dr, ex.data(), ex.size() * 4, nullptr));
+        }
+        DeviceTensor in = upload(ct);
+        DeviceTensor out = alloc(ct.shape(), E);
+        check(cofhe_hip_add_plain_records(ctx_, in.ptr_, dpl, dr, hrec.data(), pkrec.data(), frec.data(), out.ptr_, E, k_, mode, nullptr));
+        check(cofhe_hip_stream_sync(ctx_, nullptr));          // `plain` and `ex` go with this frame
+        return download(std::move(out));
     }
     Tensor<CipherText *> encrypt_tensor_fresh(const PublicKey &pk, const Tensor<PlainText *> &pts) const {
         const size_t E = pts.num_elements();

@@ -361,6 +361,175 @@ static void bench_fresh_randomness(size_t n) {
     if (!ok) throw std::runtime_error("fresh randomness check failed");
 }
 
+// differences and plaintext addends (sub_ciphertext_tensors, invert_ciphertext_tensor, add / sub_plaintext_tensor,
+// plaintext_sub_ciphertext_tensor) against decryption, in the default mode, per element, 0-D and in PerElement mode
+static void bench_affine(size_t n) {
+    auto cs = make_cryptosystem(128, 128, Device::GPU);
+    using CS = decltype(cs);
+    auto sk = cs.keygen();
+    auto pk = cs.keygen(sk);
+    Tensor<CS::PlainText *> pa(n, nullptr), pb(n, nullptr), pm(n, nullptr);
+    std::vector<float> a(n), b(n), m(n);
+    for (size_t i = 0; i < n; i++) {
+        a[i] = (float)((long)(i * 7 % 101) - 50);
+        b[i] = (float)((long)(i * 13 % 89) - 44);
+        m[i] = (float)((long)(i * 5 % 61) - 30);
+        pa.at(i) = new CS::PlainText(cs.make_plaintext(a[i]));
+        pb.at(i) = new CS::PlainText(cs.make_plaintext(b[i]));
+        pm.at(i) = new CS::PlainText(cs.make_plaintext(m[i]));
+    }
+    auto decrypts_to = [&](const Tensor<CS::CipherText *> &t, auto want) {
+        auto res = cs.decrypt_tensor(sk, t);
+        bool good = true;
+        for (size_t i = 0; i < n; i++) {
+            if (cs.get_float_from_plaintext(*res.at(i)) != want(i)) good = false;
+            delete res.at(i);
+        }
+        return good;
+    };
+    auto c1_text = [](const CS::CipherText &c) { return c.c1().a().str() + " " + c.c1().b().str(); };
+    auto distinct_c1 = [&](const Tensor<CS::CipherText *> &t) {
+        std::set<std::string> seen;
+        for (size_t i = 0; i < t.num_elements(); i++) seen.insert(c1_text(*t[i]));
+        return seen.size() == t.num_elements();
+    };
+    auto ca = cs.encrypt_tensor(pk, pa), cb = cs.encrypt_tensor(pk, pb);
+    cs.synchronize();
+    bool ok = true;
+    auto timed = [&](double &ms, auto fn) {
+        auto t0 = Clock::now();
+        auto r = fn();
+        cs.synchronize();
+        ms = std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
+        return r;
+    };
+    double sub_ms = 0, neg_add_ms = 0, plain_ms = 0, enc_add_ms = 0;
+    auto diff = timed(sub_ms, [&]() { return cs.sub_ciphertext_tensors(pk, ca, cb); });
+    auto diff_ref = timed(neg_add_ms, [&]() {
+        auto nb = cs.negate_ciphertext_tensor(pk, cb);
+        auto r = cs.add_ciphertext_tensors(pk, ca, nb);
+        free_all(nb);
+        return r;
+    });
+    auto sum_m = timed(plain_ms, [&]() { return cs.add_plaintext_tensor(pk, ca, pm); });
+    auto sum_ref = timed(enc_add_ms, [&]() {
+        auto em = cs.encrypt_tensor(pk, pm);
+        auto r = cs.add_ciphertext_tensors(pk, ca, em);
+        free_all(em);
+        return r;
+    });
+    auto dif_m = cs.sub_plaintext_tensor(pk, ca, pm);
+    auto m_dif = cs.plaintext_sub_ciphertext_tensor(pk, pm, ca);
+    auto inv = cs.invert_ciphertext_tensor(ca);
+    const bool dec_ok = decrypts_to(diff, [&](size_t i) { return a[i] - b[i]; }) && decrypts_to(diff_ref, [&](size_t i) { return a[i] - b[i]; }) &&
+                        decrypts_to(sum_m, [&](size_t i) { return a[i] + m[i]; }) && decrypts_to(sum_ref, [&](size_t i) { return a[i] + m[i]; }) &&
+                        decrypts_to(dif_m, [&](size_t i) { return a[i] - m[i]; }) && decrypts_to(m_dif, [&](size_t i) { return m[i] - a[i]; }) &&
+                        decrypts_to(inv, [&](size_t i) { return -a[i]; });
+    // the plaintext addend leaves c1 alone: a tensor that shared its c1 still does
+    bool c1_kept = true;
+    for (size_t i = 0; i < n; i++)
+        if (c1_text(*sum_m[i]) != c1_text(*ca[0]) || c1_text(*dif_m[i]) != c1_text(*ca[0])) c1_kept = false;
+    // shape errors and the 0-D forms
+    bool shape_ok = false;
+    try {
+        Tensor<CS::CipherText *> shorter(n > 1 ? n - 1 : 2, ca[0]);
+        (void)cs.sub_ciphertext_tensors(pk, ca, shorter);
+    } catch (const std::invalid_argument &e) {
+        shape_ok = std::string(e.what()) == "Tensor shapes must be equal";
+    }
+    bool scalar_ok = true;
+    {
+        CS::CipherText x = *ca[1 % n], y = *cb[1 % n];
+        CS::PlainText mm = *pm[1 % n];
+        Tensor<CS::CipherText *> tx(&x), ty(&y);
+        Tensor<CS::PlainText *> tm(&mm);
+        auto d0 = cs.sub_ciphertext_tensors(pk, tx, ty);
+        auto s0 = cs.add_plaintext_tensor(pk, tx, tm);
+        auto i0 = cs.invert_ciphertext_tensor(tx);
+        if (!d0.is_zero_degree() || !s0.is_zero_degree() || !i0.is_zero_degree()) scalar_ok = false;
+        if (cs.get_float_from_plaintext(cs.decrypt(sk, *d0.get_value())) != a[1 % n] - b[1 % n]) scalar_ok = false;
+        if (cs.get_float_from_plaintext(cs.decrypt(sk, *s0.get_value())) != a[1 % n] + m[1 % n]) scalar_ok = false;
+        if (cs.get_float_from_plaintext(cs.decrypt(sk, *i0.get_value())) != -a[1 % n]) scalar_ok = false;
+        // the scalar difference is re-randomised like the scalar sum: a second call gives another ciphertext
+        auto d1 = cs.sub_ciphertexts(pk, x, y);
+        if (d1.c1() == d0.get_value()->c1()) scalar_ok = false;
+        if (cs.get_float_from_plaintext(cs.decrypt(sk, d1)) != a[1 % n] - b[1 % n]) scalar_ok = false;
+        delete d0.get_value(); delete s0.get_value(); delete i0.get_value();
+    }
+    std::ofstream("local_bench_affine_sub.bin", std::ios::binary) << cs.serialize_ciphertext_tensor(diff);
+    std::ofstream("local_bench_affine_plain.bin", std::ios::binary) << cs.serialize_ciphertext_tensor(m_dif);
+    // PerElement mode: the same results with a fresh r per element
+    cs.set_tensor_randomness(TensorRandomness::PerElement);
+    auto fdiff = cs.sub_ciphertext_tensors(pk, ca, cb);
+    auto fsum = cs.add_plaintext_tensor(pk, ca, pm);
+    auto fmdif = cs.plaintext_sub_ciphertext_tensor(pk, pm, ca);
+    const bool fresh_ok = (n < 2 || (distinct_c1(fdiff) && distinct_c1(fsum) && distinct_c1(fmdif))) &&
+                          decrypts_to(fdiff, [&](size_t i) { return a[i] - b[i]; }) && decrypts_to(fsum, [&](size_t i) { return a[i] + m[i]; }) &&
+                          decrypts_to(fmdif, [&](size_t i) { return m[i] - a[i]; });
+    cs.set_tensor_randomness(TensorRandomness::None);
+    ok = dec_ok && c1_kept && shape_ok && scalar_ok && fresh_ok;
+    {
+        Mpz ad = cs.discriminant();
+        ad.neg();
+        std::ofstream("local_bench_absdelta.txt") << ad.str() << "\n";
+    }
+    std::cout << "  sub_ciphertext_tensors " << sub_ms << " ms, negate + add " << neg_add_ms << " ms; add_plaintext_tensor " << plain_ms
+              << " ms, encrypt_tensor + add " << enc_add_ms << " ms (" << n << " ciphertexts, host wall clock, first calls)" << std::endl;
+    std::cout << "  decryption: " << (dec_ok ? "yes" : "NO") << ", c1 kept by the plaintext addend: " << (c1_kept ? "yes" : "NO")
+              << ", shape error: " << (shape_ok ? "yes" : "NO") << ", 0-D forms: " << (scalar_ok ? "yes" : "NO") << ", per-element mode: "
+              << (fresh_ok ? "yes" : "NO") << std::endl;
+    std::cout << "  agree: " << (ok ? "yes" : "NO") << std::endl;
+    for (auto *t : {&ca, &cb, &diff, &diff_ref, &sum_m, &sum_ref, &dif_m, &m_dif, &inv, &fdiff, &fsum, &fmdif}) free_all(*t);
+    free_all(pa); free_all(pb); free_all(pm);
+    if (!ok) throw std::runtime_error("affine check failed");
+}
+
+// the Beaver element product with LocalCipherTextMultiplier::set_direct_differences: x*y mod 2^k as without it
+static void bench_beaver_direct(size_t n) {
+    auto cs = make_cryptosystem(128, 128, Device::GPU);
+    using CS = decltype(cs);
+    auto sk = cs.keygen();
+    LocalSMPCClient<CS> client(cs, sk);
+    LocalCipherTextMultiplier<CS> mul(client);
+    const auto &pk = client.network_public_key();
+    Tensor<CS::PlainText *> px(n, nullptr), py(n, nullptr);
+    std::vector<float> want(n);
+    for (size_t i = 0; i < n; i++) {
+        const float x = (float)((long)(i % 7) - 3), y = (float)((long)(i % 5) + 1);
+        want[i] = x * y;
+        px.at(i) = new CS::PlainText(cs.make_plaintext(x));
+        py.at(i) = new CS::PlainText(cs.make_plaintext(y));
+    }
+    auto cx = cs.encrypt_tensor(pk, px), cy = cs.encrypt_tensor(pk, py);
+    bool ok = true;
+    double ms[2] = {0, 0};
+    for (int pass = 0; pass < 2; pass++)          // a warm-up pass builds the tables; the second is timed
+        for (int direct = 0; direct < 2; direct++) {
+            mul.set_direct_differences(direct != 0);
+            cs.synchronize();
+            auto t0 = Clock::now();
+            auto res = mul.multiply_ciphertext_tensors(cx, cy);
+            cs.synchronize();
+            ms[direct] = std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
+            auto dec = cs.decrypt_tensor(sk, res);
+            for (size_t i = 0; i < n; i++)
+                if (cs.get_float_from_plaintext(*dec.at(i)) != want[i]) ok = false;
+            if (direct && pass) std::ofstream("local_bench_beaver_direct.bin", std::ios::binary) << cs.serialize_ciphertext_tensor(res);
+            free_all(res);
+            free_all(dec);
+        }
+    {
+        Mpz ad = cs.discriminant();
+        ad.neg();
+        std::ofstream("local_bench_absdelta.txt") << ad.str() << "\n";
+    }
+    std::cout << "  " << n << " element products: reference sequence " << ms[0] << " ms, direct differences " << ms[1]
+              << " ms (host wall clock, triplet generation and decryptions included)" << std::endl;
+    std::cout << "  agree: " << (ok ? "yes" : "NO") << std::endl;
+    free_all(cx); free_all(cy); free_all(px); free_all(py);
+    if (!ok) throw std::runtime_error("beaver product mismatch");
+}
+
 // threshold decryption end to end (the reference has no local benchmark for it; the calls are the
 // ones PartialDecryptionRequestHandler / SMPCClient make, partial_decryption_request_handler.hpp:140,
 // smpc_client.hpp:137): share sk t-out-of-n, every party of the first threshold set runs
@@ -642,7 +811,7 @@ static void plaintexts_mode(const char *in, const char *out) {
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        std::cerr << "Usage: " << argv[0] << " <encrypt_decrypt|ciphertext_matadd|scal_matmul|threshold|ciphertext_matmul|fresh_randomness> [sizes]" << std::endl;
+        std::cerr << "Usage: " << argv[0] << " <encrypt_decrypt|ciphertext_matadd|scal_matmul|threshold|ciphertext_matmul|fresh_randomness|affine|beaver_direct> [sizes]" << std::endl;
         return 1;
     }
     std::string mode = argv[1];
@@ -668,6 +837,10 @@ int main(int argc, char **argv) {
             plaintexts_mode(argv[2], argv[3]);
         } else if (mode == "fresh_randomness") {
             bench_fresh_randomness(argc > 2 ? std::stoul(argv[2]) : 256);
+        } else if (mode == "affine") {
+            bench_affine(argc > 2 ? std::stoul(argv[2]) : 64);
+        } else if (mode == "beaver_direct") {
+            bench_beaver_direct(argc > 2 ? std::stoul(argv[2]) : 8);
         } else if (mode == "formats") {
             bench_formats();
         } else if (mode == "threads") {

@@ -12,6 +12,9 @@
 // The protocol per element (ciphertext_multiplications.hpp:115-160), with (a, b, c = ab) a triplet:
 //   e = Dec(x - a), d = Dec(y - b);  x*y = e*b + d*a + c + e*d
 // i.e. 2 negations, 5 additions, 2 scalings, 1 encryption and 2 decryptions per product.
+// LocalCipherTextMultiplier::set_direct_differences(true) opens x - a, y - b with sub_ciphertext_tensors (one composition
+// per record where a negation is ct^(2^k - 1): k squarings and a product) and closes with add_plaintext_tensor(..., e*d)
+// (c2 o f^(ed) against the cached table of f) instead of an encryption and an addition: no negation and no encryption.
 #pragma once
 #include "hip_cryptosystem.hpp"
 
@@ -102,6 +105,9 @@ class LocalCipherTextMultiplier {
     using PlainText = typename CryptoSystem::PlainText;
 
     explicit LocalCipherTextMultiplier(Client &client) : client_m(client) {}
+    // off (the default): the reference's sequence of calls; on: differences by subtraction, e*d added as a plaintext
+    void set_direct_differences(bool on) { direct_differences_m = on; }
+    bool direct_differences() const { return direct_differences_m; }
 
     CipherText multiply_ciphertexts(const CipherText &ct1, const CipherText &ct2) {
         Tensor<CipherText *> a(1, const_cast<CipherText *>(&ct1)), b(1, const_cast<CipherText *>(&ct2));
@@ -142,6 +148,7 @@ class LocalCipherTextMultiplier {
     Tensor<CipherText *> handle_vector_ciphertext_mul(const Tensor<CipherText *> &ct1, const Tensor<CipherText *> &ct2) {
         const size_t n = ct1.shape()[0];
         if (ct2.num_elements() != n) throw std::invalid_argument("Tensor shapes must be equal");
+        if (direct_differences_m) return vector_mul_direct(ct1, ct2, n);
         auto &cs = client_m.crypto_system();
         const auto &pk = client_m.network_public_key();
         auto triplets = client_m.get_beavers_triplets(n);
@@ -185,7 +192,47 @@ class LocalCipherTextMultiplier {
     }
 
   private:
+    // the same product with x - a, y - b by subtraction and e*d as a plaintext addend: per element 2 compositions for the
+    // differences (plus the folded c1) and one comb tree for f^(ed), against 2 (k + 1) + 2 compositions and an encryption
+    Tensor<CipherText *> vector_mul_direct(const Tensor<CipherText *> &ct1, const Tensor<CipherText *> &ct2, size_t n) {
+        auto &cs = client_m.crypto_system();
+        const auto &pk = client_m.network_public_key();
+        auto triplets = client_m.get_beavers_triplets(n);
+        Tensor<CipherText *> a_tensor(n, nullptr), b_tensor(n, nullptr), c_tensor(n, nullptr);
+        for (size_t i = 0; i < n; i++) {
+            a_tensor[i] = triplets.at(i, 0);
+            b_tensor[i] = triplets.at(i, 1);
+            c_tensor[i] = triplets.at(i, 2);
+        }
+        auto ct1_sub_a = cs.sub_ciphertext_tensors(pk, ct1, a_tensor);
+        auto ct2_sub_b = cs.sub_ciphertext_tensors(pk, ct2, b_tensor);
+        auto pt1 = client_m.decrypt_tensor(ct1_sub_a);
+        auto pt2 = client_m.decrypt_tensor(ct2_sub_b);
+        auto pt1_pt2 = cs.multiply_plaintext_tensors(pt1, pt2);
+        auto pt1_b = cs.scal_ciphertext_tensors(pk, pt1, b_tensor);
+        auto pt2_a = cs.scal_ciphertext_tensors(pk, pt2, a_tensor);
+        auto s1 = cs.add_ciphertext_tensors(pk, pt1_b, pt2_a);
+        auto s2 = cs.add_ciphertext_tensors(pk, s1, c_tensor);
+        auto ct = cs.add_plaintext_tensor(pk, s2, pt1_pt2);
+        for (size_t i = 0; i < n; i++) {
+            delete triplets.at(i, 0);
+            delete triplets.at(i, 1);
+            delete triplets.at(i, 2);
+            delete ct1_sub_a[i];
+            delete ct2_sub_b[i];
+            delete pt1[i];
+            delete pt2[i];
+            delete pt1_pt2[i];
+            delete pt1_b[i];
+            delete pt2_a[i];
+            delete s1[i];
+            delete s2[i];
+        }
+        return ct;
+    }
+
     Client &client_m;
+    bool direct_differences_m = false;
 };
 
 }  // namespace CoFHE

@@ -129,6 +129,15 @@ int cofhe_hip_compose_wide_records(cofhe_hip_ctx *ctx, const void *d_a, const vo
  * the composition c1 o c1' is computed once and copied: n_ct + 1 compositions instead of 2 n_ct.  Detected on the
  * device per call (one pass over the c1 records); tensors with differing c1 take the plain path.  d_out may be d_a. */
 int cofhe_hip_add_ciphertext_records(cofhe_hip_ctx *ctx, const void *d_a, const void *d_b, void *d_out, uint64_t n_ct, void *stream);
+/* out[i] = a[i] - b[i]: (a.c1 o b.c1^-1, a.c2 o b.c2^-1), one composition per record -- the inverse of a reduced form is a
+ * sign flip -- where negate (b^(2^k - 1), k squarings and a product per record) followed by an addition spends k + 2.  Folding
+ * of a shared c1 and launch routes as cofhe_hip_add_ciphertext_records; d_out may be d_a or d_b.  "profile_kernels" spans
+ * "k_sub_ct3" | "k_sub_ct".  Reference: the compute node's SUBTRACT, which answers "Not implemented"
+ * (include/node/compute_request_handler.hpp:67-76, 342-344). */
+int cofhe_hip_sub_ciphertext_records(cofhe_hip_ctx *ctx, const void *d_a, const void *d_b, void *d_out, uint64_t n_ct, void *stream);
+/* out[i] = in[i]^-1 on form records (a ciphertext tensor: 2 n_ct records): Enc(-m) at no composition, a ciphertext other
+ * than negate_ciphertext_tensor's ct^(2^k - 1) (tensor_ops.inl:431-460) with the same plaintext; in place allowed. */
+int cofhe_hip_invert_records(cofhe_hip_ctx *ctx, const void *d_in, void *d_out, uint64_t n_records, void *stream);
 /* out[2e+h] = base[2e+h] ^ exp[e] for E ciphertexts (h = 0,1) */
 int cofhe_hip_pow_records(cofhe_hip_ctx *ctx, const void *d_base, const void *d_exp, void *d_out,
                           uint64_t n_ciphertexts, void *stream);
@@ -201,8 +210,19 @@ int cofhe_hip_encrypt_fresh_records(cofhe_hip_ctx *ctx, const void *d_plain, con
  * Reference: the re-randomised outputs of add / scal / negate, tensor_ops.inl:142-162, 212-240, 287-310, 357-375, 431-460. */
 int cofhe_hip_rerandomize_records(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_r, const uint32_t *h_record,
                                   const uint32_t *pk_record, void *d_out, uint64_t n_ciphertexts, void *stream);
-/* The comb launcher's decisions as data (host only, no GPU): for kind 0 (powers), 1 (fresh encryption) or 2
- * (re-randomisation) of n items whose longest exponent has exp_bits bits, with the "comb_width" / "comb_chunk" pins
+/* Ciphertext and plaintext tensor combined without an encryption.  mode 0: ct + m, 1: ct - m, 2: m - ct, with m[i]
+ * exponent records (sign honoured, reduced mod 2^k).  d_r NULL: deterministic, (c1, c2 o f^(+-m)) -- c1 untouched (mode 2:
+ * inverted), one tree of ~k/w + 2 slots per ciphertext against the cached table of f, no read-back: purely stream-ordered
+ * (h_record, pk_record unused).  d_r given (with h, pk): the result carries fresh randomness, (c1 o h^r, c2 o pk^r o f^m) in
+ * one tree.  f: HOST record; d_out may equal d_cts.  Reference: the node's mixed ADD encrypts the plaintext and adds
+ * (include/node/compute_request_handler.hpp:384-403, 452-470): h^r, pk^r, f^m and two compositions per element, and a
+ * second c1 in the result. */
+int cofhe_hip_add_plain_records(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_plain, const void *d_r, const uint32_t *h_record,
+                                const uint32_t *pk_record, const uint32_t *f_record, void *d_out, uint64_t n_ct, uint32_t kbits, int mode,
+                                void *stream);
+/* The comb launcher's decisions as data (host only, no GPU): for kind 0 (powers), 1 (fresh encryption), 2
+ * (re-randomisation), 3 (plaintext addend: one column per ciphertext, exp_bits unused) or 4 (plaintext addend with fresh
+ * randomness) of n items whose longest exponent has exp_bits bits, with the "comb_width" / "comb_chunk" pins
  * w_pin / chunk_pin (0 = automatic): the window width, the slots (tree leaves) of one output record and the items per pass. */
 int cofhe_hip_comb_shape(uint32_t kind, uint64_t n, uint32_t exp_bits, uint32_t kbits, uint32_t w_pin, uint64_t chunk_pin, uint32_t *w,
                          uint32_t *slots, uint64_t *chunk);
@@ -281,6 +301,14 @@ void cofhe_hip_host_free(void *p);
 /* ---- whole operations on host buffers in the reference's binary formats ---- */
 int cofhe_hip_add_ciphertext_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *t1, size_t l1,
                                            const uint8_t *t2, size_t l2, uint8_t **out, size_t *outlen);
+/* t1 - t2 element-wise: the node's SUBTRACT (compute_request_handler.hpp:67-76, 342-344); shapes must be equal */
+int cofhe_hip_sub_ciphertext_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *t1, size_t l1,
+                                           const uint8_t *t2, size_t l2, uint8_t **out, size_t *outlen);
+/* cts (ciphertext tensor) and pt (plaintext tensor) of equal shape, mode 0: cts + pt, 1: cts - pt, 2: pt - cts,
+ * deterministic: the node's mixed ADD / SUBTRACT (compute_request_handler.hpp:384-403, 452-470) without the encryption.
+ * f_record: HOST record of f. */
+int cofhe_hip_add_plaintext_tensor_bytes(cofhe_hip_ctx *ctx, const uint8_t *cts, size_t lc, const uint8_t *pt, size_t lp,
+                                         const uint32_t *f_record, uint32_t kbits, int mode, uint8_t **out, size_t *outlen);
 /* s: plaintext tensor; 1-D x 1-D -> element-wise, 2-D x 2-D -> matmul (zero: 1-element tensor) */
 int cofhe_hip_scal_ciphertext_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *s, size_t ls,
                                             const uint8_t *cts, size_t lc, const uint8_t *zero, size_t lz,

@@ -114,6 +114,35 @@ ex = dev_i32(exp_records([(1 << K) - 1] * E))
 sec = timed(lambda: eng.pow_records(cts.data_ptr(), ex.data_ptr(), out.data_ptr(), E))
 emit("negate_ciphertext_tensor (exponent 2^k - 1)", [E], sec, E, "ciphertexts/s", kernel="k_pow")
 
+# ---- differences, inverses and plaintext addends (affine.hip, the comb's kinds 3 and 4) -----------------
+other = fresh(E)
+sec = timed(lambda: eng.sub_ciphertext_records(cts.data_ptr(), other.data_ptr(), out.data_ptr(), E), reps=10)
+emit("sub_ciphertext_tensors, shared c1 folded (cofhe_hip_sub_ciphertext_records)", [E], sec, E, "ciphertext-ops/s",
+     kernel="k_c1_distinct + k_sub_ct + k_c1_spread")
+sec = timed(lambda: eng.invert_records(cts.data_ptr(), out.data_ptr(), 2 * E), reps=10)
+emit("invert_ciphertext_tensor (cofhe_hip_invert_records)", [E], sec, E, "ciphertexts/s", kernel="k_invert_records")
+f_rec = form_record(hx(prm["f"]["a"]), hx(prm["f"]["b"]), hx(prm["f"]["c"]))
+h_rec = form_record(hx(prm["h"]["a"]), hx(prm["h"]["b"]), hx(prm["h"]["c"]))
+pk_rec = form_record(hx(prm["pk"]["a"]), hx(prm["pk"]["b"]), hx(prm["pk"]["c"]))
+pm = dev_i32(exp_records([rng.bits(K) for _ in range(E)]))
+sec = timed(lambda: eng.add_plain_records(cts.data_ptr(), pm.data_ptr(), f_rec, out.data_ptr(), E, K, 0), reps=3)
+emit("add_plaintext_tensor (cofhe_hip_add_plain_records, no randomness)", [E], sec, E, "ciphertexts/s", kernel="k_comb_first + k_compose_pairs tree")
+pr = dev_i32(exp_records([rng.bits(960) for _ in range(E)]))
+sec = timed(lambda: eng.add_plain_records(cts.data_ptr(), pm.data_ptr(), f_rec, out.data_ptr(), E, K, 0, d_r=pr.data_ptr(), h_record=h_rec,
+                                          pk_record=pk_rec), reps=3)
+emit("add_plaintext_tensor with fresh randomness (cofhe_hip_add_plain_records, d_r)", [E], sec, E, "ciphertexts/s",
+     kernel="k_comb_first + k_compose_pairs tree")
+ha, hb = (eng.records_to_bytes(t.cpu().numpy().view(np.uint32), [128, 128]) for t in (cts, other))
+t0 = time.perf_counter()
+hc = eng.sub_ciphertext_tensors(ha, hb)
+emit("sub_ciphertext_tensors, host bytes in/out (cofhe_hip_sub_ciphertext_tensors_bytes)", [128, 128], time.perf_counter() - t0, E, "ciphertext-ops/s")
+from gpu_inputs import _pt_bytes  # noqa: E402
+hp_ = _pt_bytes([128, 128], [rng.bits(K) for _ in range(E)])
+t0 = time.perf_counter()
+hc = eng.add_plaintext_tensor(ha, hp_, f_rec, K, 0)
+emit("add_plaintext_tensor, host bytes in/out (cofhe_hip_add_plaintext_tensor_bytes)", [128, 128], time.perf_counter() - t0, E, "ciphertext-ops/s")
+del other, pm, pr, ha, hb, hc, hp_
+
 # ---- encryption with given randomness (fixed-base f^m) --------------------------------------------
 pl = dev_i32(exp_records([rng.bits(K) for _ in range(E)]))
 fr_ = lambda o: form_record(hx(o["a"]), hx(o["b"]), hx(o["c"]))
