@@ -1,7 +1,8 @@
 // abi.hip -- the C ABI of include/cofhe_hip.h, in this order: the context, the block cache, the launch helpers (spans, the
 // two-build launch, flag words, the table-cache lookup), the workspace plans, the launchers (one launch site per kernel and
 // route; product_tree is the pairwise tree of them all) and the host-side tensor formats.  The kernels are declared in
-// kernels.hpp and defined in cofhe_hip.hip, wide.hip and comb.hip; this file holds no device code of its own.
+// kernels.hpp and defined in cofhe_hip.hip, wide.hip, comb.hip, affine.hip and matmul_left.hip; this file holds no device code
+// of its own.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -15,6 +16,7 @@
 #include "ctx.hpp"
 #include "form_io.hpp"
 #include "kernels.hpp"
+#include "plain_mm.hpp"
 
 using namespace cofhe;
 using namespace cofhe_k;
@@ -1387,6 +1389,68 @@ int cofhe_hip_scal_matmul_records(cofhe_hip_ctx *ctx, const void *d_cts, const v
 }
 
 namespace {
+// the one launch site of k_transpose_records: out (cols x rows) = in (rows x cols)^T, elements of `words` words; 16-byte pieces
+// when both pointers and the element size allow them (a caller's pointer is only known to be 4-byte aligned)
+int transpose_launch(const void *d_in, void *d_out, uint32_t rows, uint32_t cols, uint32_t words, hipStream_t st) {
+    const bool vec16 = words % 4 == 0 && (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0;
+    const uint64_t total = (uint64_t)rows * cols * (vec16 ? words / 4 : words);
+    if (total == 0) return COFHE_HIP_OK;
+    const unsigned blocks = (unsigned)std::min<uint64_t>((total + 255) / 256, 64u * NUM_CUS);       // grid-stride beyond that
+    hipLaunchKernelGGL(k_transpose_records, dim3(blocks), dim3(256), 0, st, (const uint32_t *)d_in, (uint32_t *)d_out, rows, cols, words,
+                       vec16 ? 1u : 0u);
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+bool overlaps(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
+}
+}  // namespace
+
+// Needs no workspace plan of its own: the temporaries are three blocks of the block cache, and the product it calls carves
+// the workspace by its own plans ("scal_matmul", "scal_matmul_tree") for the transposed shape (p, m, n).
+int cofhe_hip_matmul_plain_ct_records(cofhe_hip_ctx *ctx, const void *d_s, const void *d_cts, const void *d_zero, void *d_out, uint32_t n,
+                                      uint32_t m, uint32_t p, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if ((uint64_t)n * p == 0) return COFHE_HIP_OK;
+    const size_t ct_bytes = (size_t)2 * REC_WORDS * 4, exp_bytes = (size_t)EXP_REC_WORDS * 4;
+    const size_t out_bytes = (size_t)n * p * ct_bytes, cts_bytes = (size_t)m * p * ct_bytes, s_bytes = (size_t)n * m * exp_bytes;
+    if (overlaps(d_out, out_bytes, d_cts, cts_bytes) || overlaps(d_out, out_bytes, d_s, s_bytes) || overlaps(d_out, out_bytes, d_zero, ct_bytes))
+        return fail(COFHE_HIP_EINVAL, "matmul_plain_ct: the output overlaps an input");
+    if (m >= (1u << 21)) return fail(COFHE_HIP_EINVAL, "inner dimension beyond 2^21");
+    unsigned blocks;
+    if (int rc = compose_blocks((uint64_t)n * p * 2, &blocks)) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf cts_t, s_t, out_t;                    // cts^T (p x m), s^T (m x n), out^T (p x n)
+    cts_t.stream = s_t.stream = out_t.stream = stream;
+    if (int rc = cts_t.get(ctx, cts_bytes ? cts_bytes : 4)) return rc;
+    if (int rc = s_t.get(ctx, s_bytes ? s_bytes : 4)) return rc;
+    if (int rc = out_t.get(ctx, out_bytes)) return rc;
+    if (int rc = transpose_launch(d_cts, cts_t.p, m, p, 2 * REC_WORDS, st)) return rc;
+    if (int rc = transpose_launch(d_s, s_t.p, n, m, EXP_REC_WORDS, st)) return rc;
+    if (int rc = cofhe_hip_scal_matmul_records(ctx, cts_t.p, s_t.p, d_zero, out_t.p, p, m, n, stream)) return rc;
+    return transpose_launch(out_t.p, d_out, p, n, 2 * REC_WORDS, st);
+}
+
+int cofhe_hip_matmul_plain_plain_records(cofhe_hip_ctx *ctx, const void *d_a, const void *d_b, void *d_out, uint32_t n, uint32_t m, uint32_t p,
+                                         uint32_t kbits, void *stream) {
+    if (kbits == 0 || kbits > 32u * PMM_MAX_LIMBS || 2 * kbits + 1 > (uint32_t)PLIMBS * 32) return fail(COFHE_HIP_EINVAL, "k out of range");
+    if ((uint64_t)n * p == 0) return COFHE_HIP_OK;
+    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4;
+    if (overlaps(d_out, (size_t)n * p * exp_bytes, d_a, (size_t)n * m * exp_bytes) ||
+        overlaps(d_out, (size_t)n * p * exp_bytes, d_b, (size_t)m * p * exp_bytes))
+        return fail(COFHE_HIP_EINVAL, "matmul_plain_plain: the output overlaps an input");
+    const uint32_t gx = (p + PMM_TILE - 1) / PMM_TILE, gy = (n + PMM_TILE - 1) / PMM_TILE;
+    if (gy > 65535u) return fail(COFHE_HIP_EINVAL, "work size out of range");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_plain_matmul, dim3(gx, gy), dim3(PMM_THREADS), 0, (hipStream_t)stream, (const uint32_t *)d_a, (const uint32_t *)d_b,
+                       (uint32_t *)d_out, n, m, p, kbits);
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+
+namespace {
 // the table f^(-2^j), j < k, of the decryption kernels (built on first use, cached in the context)
 int ensure_ftab(cofhe_hip_ctx *ctx, const uint32_t *f_record, uint32_t kbits, void *stream) {
     if (kbits == 0 || 2 * kbits + 1 > (uint32_t)PLIMBS * 32 || kbits > EXP_MAG_WORDS * 32 - 1)
@@ -1873,6 +1937,31 @@ int cofhe_hip_scal_ciphertext_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *s
     const uint64_t nout = (uint64_t)n * p * 2;
     if (int rc = dout.get(ctx, nout ? nout * REC_WORDS * 4 : 4)) return rc;
     if (int rc = cofhe_hip_scal_matmul_records(ctx, dc.p, de.p, dz.p, dout.p, n, m, p, nullptr)) return rc;
+    const uint32_t so[2] = {n, p};
+    return finish(ctx, dout, nout, 2, so, out, outlen);
+}
+
+int cofhe_hip_matmul_plain_ct_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *s, size_t ls, const uint8_t *cts, size_t lc,
+                                            const uint8_t *zero, size_t lz, uint8_t **out, size_t *outlen) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    uint32_t nds, ndc, ss[8], sc[8];
+    uint64_t ne, nr;
+    HIPCHK(hipSetDevice(ctx->device));
+    DevBuf de, dc, dz, dout;
+    if (int rc = load_tensor(ctx, s, ls, 0, de, &nds, ss, &ne)) return rc;
+    if (int rc = load_tensor(ctx, cts, lc, 2, dc, &ndc, sc, &nr)) return rc;
+    if (nds != 2 || ndc != 2) return fail(COFHE_HIP_ESHAPE, "the plaintext-left product takes two matrices");
+    // s n x m, cts m x p
+    const uint32_t n = ss[0], m = ss[1], p = sc[1];
+    if (sc[0] != m) return fail(COFHE_HIP_ESHAPE, "inner dimensions of the matrix product differ");
+    uint32_t ndz, sz[8];
+    uint64_t nz;
+    if (!zero) return fail(COFHE_HIP_EINVAL, "the 2-D product needs the encryption of zero it starts from");
+    if (int rc = load_tensor(ctx, zero, lz, 2, dz, &ndz, sz, &nz)) return rc;
+    if (nz != 2) return fail(COFHE_HIP_EINVAL, "zero must be a one-element ciphertext tensor");
+    const uint64_t nout = (uint64_t)n * p * 2;
+    if (int rc = dout.get(ctx, nout ? nout * REC_WORDS * 4 : 4)) return rc;
+    if (int rc = cofhe_hip_matmul_plain_ct_records(ctx, de.p, dc.p, dz.p, dout.p, n, m, p, nullptr)) return rc;
     const uint32_t so[2] = {n, p};
     return finish(ctx, dout, nout, 2, so, out, outlen);
 }

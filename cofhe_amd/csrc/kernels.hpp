@@ -2,7 +2,8 @@
 // __launch_bounds__, are in cofhe_hip.hip (the throughput kernels, in three COFHE_PART passes) and wide.hip
 // (the latency kernels); wire.hip launches its own kernels.  A declaration that matches no definition is an
 // undefined symbol when the library is loaded (tests/test_cabi.py).  comb.hip holds the two kernels of the fixed-base comb,
-// affine.hip the ciphertext difference and the record inverse.
+// affine.hip the ciphertext difference and the record inverse, matmul_left.hip the record transpose and the plaintext
+// matrix product.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -123,4 +124,11 @@ __global__ void k_sub_ct3(const uint32_t *__restrict__ a, const uint32_t *__rest
                           const uint32_t *__restrict__ flag, const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status,
                           uint32_t only);
 __global__ void k_invert_records(const uint32_t *in, uint32_t *out, uint64_t n, uint32_t stride, uint32_t offset);
+
+// the plaintext-left matrix product and matrix Beaver triplets (matmul_left.hip): a rows x cols matrix of `words`-word
+// elements transposed (vec16: 16-byte pieces), and out = a . b mod 2^kbits on exponent records (plain_mm.hpp)
+__global__ void k_transpose_records(const uint32_t *__restrict__ in, uint32_t *__restrict__ out, uint32_t rows, uint32_t cols, uint32_t words,
+                                    uint32_t vec16);
+__global__ void k_plain_matmul(const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, uint32_t *__restrict__ out, uint32_t n, uint32_t m,
+                               uint32_t p, uint32_t kbits);
 }  // namespace cofhe_k

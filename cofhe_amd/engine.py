@@ -121,6 +121,16 @@ class Engine:
                                                             C.byref(out), C.byref(n)))
         return self._take(out, n)
 
+    def matmul_plain_ct_tensors(self, s: bytes, cts: bytes, zero: bytes) -> bytes:
+        """s (plaintext tensor, n x m) . cts (ciphertext tensor, m x p) from zero (1-element ciphertext tensor): the linear
+        layer y = W x with plaintext weights, the mirror image of the 2-D scal_ciphertext_tensors"""
+        out = C.POINTER(C.c_uint8)()
+        n = C.c_size_t()
+        _chk(self.L.cofhe_hip_matmul_plain_ct_tensors_bytes(self.ctx, C.c_char_p(s), C.c_size_t(len(s)), C.c_char_p(cts),
+                                                            C.c_size_t(len(cts)), C.c_char_p(zero), C.c_size_t(len(zero)),
+                                                            C.byref(out), C.byref(n)))
+        return self._take(out, n)
+
     # ---- format conversion (host) ----------------------------------------------------------
     def bytes_to_records(self, t: bytes):
         import numpy as np
@@ -252,6 +262,20 @@ class Engine:
         _chk(self.L.cofhe_hip_scal_matmul_records(self.ctx, C.c_void_p(d_cts), C.c_void_p(d_exp), C.c_void_p(d_zero),
                                                   C.c_void_p(d_out), C.c_uint32(n), C.c_uint32(m), C.c_uint32(p),
                                                   C.c_void_p(stream)))
+
+    def matmul_plain_ct_records(self, d_s, d_cts, d_zero, d_out, n, m, p, stream=0):
+        """out[i,k] = zero o prod_j cts[j,k]^s[i,j]: s n x m exponent records, cts m x p, out n x p; scal_matmul_records on
+        transposed views (temporaries from the block cache); d_out must not overlap an input"""
+        _chk(self.L.cofhe_hip_matmul_plain_ct_records(self.ctx, C.c_void_p(d_s), C.c_void_p(d_cts), C.c_void_p(d_zero),
+                                                      C.c_void_p(d_out), C.c_uint32(n), C.c_uint32(m), C.c_uint32(p),
+                                                      C.c_void_p(stream)))
+
+    def matmul_plain_plain_records(self, d_a, d_b, d_out, n, m, p, kbits, stream=0):
+        """out = a (n x m) . b (m x p) mod 2^kbits on exponent records, outputs in [0, 2^k) with sign word 0; one launch,
+        purely stream-ordered"""
+        _chk(self.L.cofhe_hip_matmul_plain_plain_records(self.ctx, C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_out),
+                                                         C.c_uint32(n), C.c_uint32(m), C.c_uint32(p), C.c_uint32(kbits),
+                                                         C.c_void_p(stream)))
 
     def decrypt_records(self, d_cts, d_sk, f_record, d_out, n_ciphertexts, kbits, stream=0):
         """f_record: host numpy uint32[168]; d_out: n * (ceil(k/32) + 1) words"""

@@ -713,6 +713,59 @@ class HIPCryptoSystem {
         return download(std::move(out));
     }
 
+    // plaintext matrix (n x m) . ciphertext matrix (m x p): res[i,k] = zero o prod_j cts[j,k]^s[i,j], a linear layer y = W x
+    // with plaintext weights.  The reference has no such operation (its 2-D scal_ciphertext_tensors has the ciphertext
+    // matrix on the left); the engine runs that product on transposed views (cofhe_hip_matmul_plain_ct_records).  Starts
+    // from a fresh encryption of zero like the 2-D branch above; pass `zero` to make the call reproducible.
+    Tensor<CipherText *> matmul_plaintext_ciphertext_tensors(const PublicKey &pk, const Tensor<PlainText *> &s,
+                                                             const Tensor<CipherText *> &cts, const CipherText *zero = nullptr) const {
+        if (s.ndim() != 2 || cts.ndim() != 2) throw std::invalid_argument("matmul_plaintext_ciphertext_tensors: both operands must be 2D");
+        CipherText z = zero ? *zero : encrypt(pk, make_plaintext(0));
+        Tensor<CipherText *> zt(1, &z);
+        DeviceTensor out = matmul_plaintext_ciphertext_tensors(s, upload(cts), upload(zt));
+        rerandomize_result(pk, out);           // one fresh r per output, as scal_ciphertext_tensors
+        return download(std::move(out));
+    }
+    // the same on resident operands; deterministic (no re-randomisation), like the other DeviceTensor members
+    DeviceTensor matmul_plaintext_ciphertext_tensors(const Tensor<PlainText *> &s, const DeviceTensor &cts, const DeviceTensor &zero) const {
+        if (s.ndim() != 2 || cts.shape_.size() != 2) throw std::invalid_argument("matmul_plaintext_ciphertext_tensors: both operands must be 2D");
+        const size_t n = s.shape()[0], m = s.shape()[1], p = cts.shape_[1];
+        if (cts.shape_[0] != m)
+            throw std::invalid_argument("matmul_plaintext_ciphertext_tensors: inner dimensions differ (plaintext columns != ciphertext rows)");
+        if (zero.n_ != 1) throw std::invalid_argument("matmul_plaintext_ciphertext_tensors: zero must be one ciphertext");
+        std::vector<uint32_t> ex = pack_exponents(s);
+        void *dex = nullptr;
+        check(cofhe_hip_malloc(ctx_, ex.size() * 4 + 4, &dex));
+        Guard g1{ctx_, dex};
+        check(cofhe_hip_upload(ctx_, dex, ex.data(), ex.size() * 4, nullptr));
+        DeviceTensor out = alloc({n, p}, n * p);
+        check(cofhe_hip_matmul_plain_ct_records(ctx_, dex, cts.ptr_, zero.ptr_, out.ptr_, (uint32_t)n, (uint32_t)m, (uint32_t)p, nullptr));
+        return out;
+    }
+    // a (n x m) . b (m x p) mod 2^k on the device (k_plain_matmul): the E D term of a matrix Beaver triplet and the C = A B of
+    // its generation.  The element-wise multiply_plaintext_tensors is a host loop and stays one.
+    Tensor<PlainText *> matmul_plaintext_tensors(const Tensor<PlainText *> &a, const Tensor<PlainText *> &b) const {
+        if (a.ndim() != 2 || b.ndim() != 2) throw std::invalid_argument("matmul_plaintext_tensors: both operands must be 2D");
+        const size_t n = a.shape()[0], m = a.shape()[1], p = b.shape()[1];
+        if (b.shape()[0] != m) throw std::invalid_argument("matmul_plaintext_tensors: inner dimensions differ");
+        std::vector<uint32_t> ea = pack_exponents(a), eb = pack_exponents(b), eo(n * p * EXPW, 0);
+        void *da = nullptr, *db = nullptr, *dout = nullptr;
+        check(cofhe_hip_malloc(ctx_, ea.size() * 4 + 4, &da)); Guard g1{ctx_, da};
+        check(cofhe_hip_malloc(ctx_, eb.size() * 4 + 4, &db)); Guard g2{ctx_, db};
+        check(cofhe_hip_malloc(ctx_, eo.size() * 4 + 4, &dout)); Guard g3{ctx_, dout};
+        check(cofhe_hip_upload(ctx_, da, ea.data(), ea.size() * 4, nullptr));
+        check(cofhe_hip_upload(ctx_, db, eb.data(), eb.size() * 4, nullptr));
+        check(cofhe_hip_matmul_plain_plain_records(ctx_, da, db, dout, (uint32_t)n, (uint32_t)m, (uint32_t)p, k_, nullptr));
+        check(cofhe_hip_download(ctx_, eo.data(), dout, eo.size() * 4, nullptr));
+        Tensor<PlainText *> res(std::vector<size_t>{n, p}, nullptr);
+        for (size_t i = 0; i < n * p; i++) {
+            Mpz v;
+            mpz_import(v.get(), EXPW - 1, -1, 4, 0, 0, &eo[i * EXPW]);
+            res[i] = new PlainText(std::move(v));
+        }
+        return res;
+    }
+
     // res[i,k] = zero o prod_j x[i,j,k] for x of n*m*p ciphertexts (flat, row-major): the
     // accumulation loop of the ciphertext x ciphertext matrix product
     // (include/smpc/ciphertext_multiplications.hpp:85-101) as one kernel

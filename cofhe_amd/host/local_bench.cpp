@@ -621,6 +621,98 @@ static void bench_ciphertext_matmul(size_t n, size_t m, size_t p, size_t t, size
     if (!ok) throw std::runtime_error("ciphertext matmul mismatch");
 }
 
+// plaintext matrix (n x m) . ciphertext matrix (m x p), the linear layer y = W x: deterministic operands and a fixed Enc(0),
+// written to files for the parity checker like the scal_matmul mode (local_bench_lmm_*.bin)
+static void bench_plain_ct_matmul(size_t n, size_t m, size_t p) {
+    auto cs = make_cryptosystem(128, 128, Device::GPU);
+    using CS = decltype(cs);
+    auto sk = cs.keygen();
+    auto pk = cs.keygen(sk);
+    Tensor<CS::PlainText *> w(n, m, nullptr), x(m, p, nullptr);
+    for (size_t i = 0; i < n * m; i++) w[i] = new CS::PlainText(cs.make_plaintext((float)(i % 7) - 3.0f));       // weights of both signs
+    for (size_t i = 0; i < m * p; i++) x[i] = new CS::PlainText(cs.make_plaintext((float)(i + 1)));
+    auto cx = cs.encrypt_tensor(pk, x);
+    auto zero = cs.encrypt(pk, cs.make_plaintext(0));
+    Benchmark b("plain_ct_matmul (plaintext n x m . ciphertext m x p)");
+    std::string out_bytes;
+    bool ok = true;
+    b.run([&]() {
+        auto res = cs.matmul_plaintext_ciphertext_tensors(pk, w, cx, &zero);
+        out_bytes = cs.serialize_ciphertext_tensor(res);
+        auto dec = cs.decrypt_tensor(sk, res);
+        for (size_t i = 0; i < n; i++)
+            for (size_t k = 0; k < p; k++) {
+                float want = 0;
+                for (size_t j = 0; j < m; j++) want += ((float)((i * m + j) % 7) - 3.0f) * (float)(j * p + k + 1);
+                if (cs.get_float_from_plaintext(*dec[i * p + k]) != want) ok = false;
+            }
+        free_all(res);
+        free_all(dec);
+    }, 1);
+    b.print_summary();
+    std::ofstream("local_bench_lmm_s.bin", std::ios::binary) << cs.serialize_plaintext_tensor(w);
+    std::ofstream("local_bench_lmm_cts.bin", std::ios::binary) << cs.serialize_ciphertext_tensor(cx);
+    {
+        Tensor<CS::CipherText *> zt(1, &zero);
+        std::ofstream("local_bench_lmm_zero.bin", std::ios::binary) << cs.serialize_ciphertext_tensor(zt);
+    }
+    std::ofstream("local_bench_lmm_out.bin", std::ios::binary) << out_bytes;
+    {
+        Mpz ad = cs.discriminant();
+        ad.neg();
+        std::ofstream("local_bench_absdelta.txt") << ad.str() << "\n";
+    }
+    free_all(w); free_all(x); free_all(cx);
+    std::cout << "  decrypts to W x: " << (ok ? "yes" : "NO") << std::endl;
+    std::cout << "n: " << n << " m: " << m << " p: " << p << std::endl;
+    if (!ok) throw std::runtime_error("plaintext-left product mismatch");
+}
+
+// the ciphertext x ciphertext matrix product twice on the same inputs: the reference's expansion into n m p element
+// products (2 n m p opened values) and one matrix triplet (LocalCipherTextMultiplier::set_matrix_triplets: n m + m p)
+static void bench_ciphertext_matmul_matrix(size_t n, size_t m, size_t p, size_t t, size_t parties) {
+    auto cs = make_cryptosystem(128, 128, Device::GPU);
+    using CS = decltype(cs);
+    auto sk = cs.keygen();
+    std::unique_ptr<LocalSMPCClient<CS>> client(t ? new LocalSMPCClient<CS>(cs, sk, t, parties) : new LocalSMPCClient<CS>(cs, sk));
+    LocalCipherTextMultiplier<CS> mul(*client);
+    const auto &pk = client->network_public_key();
+    Tensor<CS::PlainText *> pa(n, m, nullptr), pb(m, p, nullptr);
+    for (size_t i = 0; i < n * m; i++) pa[i] = new CS::PlainText(cs.make_plaintext((float)(i % 7) - 3.0f));
+    for (size_t i = 0; i < m * p; i++) pb[i] = new CS::PlainText(cs.make_plaintext((float)(i % 5) + 1.0f));
+    auto ca = cs.encrypt_tensor(pk, pa), cb = cs.encrypt_tensor(pk, pb);
+    bool ok[2] = {true, true};
+    double ms[2] = {0, 0};
+    size_t opened[2] = {0, 0};
+    for (int matrix = 0; matrix < 2; matrix++) {
+        mul.set_matrix_triplets(matrix != 0);
+        const size_t before = client->decrypted_elements();
+        cs.synchronize();
+        auto t0 = Clock::now();
+        auto res = mul.multiply_ciphertext_tensors(ca, cb);
+        cs.synchronize();
+        ms[matrix] = std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
+        opened[matrix] = client->decrypted_elements() - before;
+        auto dec = cs.decrypt_tensor(sk, res);
+        for (size_t i = 0; i < n; i++)
+            for (size_t k = 0; k < p; k++) {
+                float want = 0;
+                for (size_t j = 0; j < m; j++) want += ((float)((i * m + j) % 7) - 3.0f) * ((float)((j * p + k) % 5) + 1.0f);
+                if (cs.get_float_from_plaintext(*dec[i * p + k]) != want) ok[matrix] = false;
+            }
+        free_all(res);
+        free_all(dec);
+    }
+    const std::string how = t ? "threshold " + std::to_string(t) + " of " + std::to_string(parties) : std::string("secret key");
+    std::cout << "  element flow: decrypted_elements " << opened[0] << ", " << ms[0] << " ms: " << (ok[0] ? "ok" : "FAILED") << std::endl;
+    std::cout << "  matrix flow: decrypted_elements " << opened[1] << ", " << ms[1] << " ms: " << (ok[1] ? "ok" : "FAILED") << std::endl;
+    std::cout << "  (host wall clock, triplet generation and decryptions included; " << how << ")" << std::endl;
+    std::cout << "  agree: " << (ok[0] && ok[1] ? "yes" : "NO") << std::endl;
+    std::cout << "n: " << n << " m: " << m << " p: " << p << std::endl;
+    free_all(ca); free_all(cb); free_all(pa); free_all(pb);
+    if (!(ok[0] && ok[1])) throw std::runtime_error("ciphertext matmul mismatch");
+}
+
 // text formats of single values and the binary plaintext-tensor format (cpu_cryptosystem.inl:124-318): written to
 // files for the parity checker, and read back
 static void bench_formats() {
@@ -811,7 +903,7 @@ static void plaintexts_mode(const char *in, const char *out) {
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        std::cerr << "Usage: " << argv[0] << " <encrypt_decrypt|ciphertext_matadd|scal_matmul|threshold|ciphertext_matmul|fresh_randomness|affine|beaver_direct> [sizes]" << std::endl;
+        std::cerr << "Usage: " << argv[0] << " <encrypt_decrypt|ciphertext_matadd|scal_matmul|threshold|ciphertext_matmul|fresh_randomness|affine|beaver_direct|plain_ct_matmul|ciphertext_matmul_matrix> [sizes]" << std::endl;
         return 1;
     }
     std::string mode = argv[1];
@@ -832,6 +924,13 @@ int main(int argc, char **argv) {
                    p = argc > 4 ? std::stoul(argv[4]) : 4, t = argc > 5 ? std::stoul(argv[5]) : 0,
                    parties = argc > 6 ? std::stoul(argv[6]) : 3;
             bench_ciphertext_matmul(n, m, p, t, parties);
+        } else if (mode == "plain_ct_matmul") {
+            bench_plain_ct_matmul(argc > 2 ? std::stoul(argv[2]) : 3, argc > 3 ? std::stoul(argv[3]) : 5, argc > 4 ? std::stoul(argv[4]) : 4);
+        } else if (mode == "ciphertext_matmul_matrix") {
+            size_t n = argc > 2 ? std::stoul(argv[2]) : 4, m = argc > 3 ? std::stoul(argv[3]) : 4,
+                   p = argc > 4 ? std::stoul(argv[4]) : 4, t = argc > 5 ? std::stoul(argv[5]) : 0,
+                   parties = argc > 6 ? std::stoul(argv[6]) : 3;
+            bench_ciphertext_matmul_matrix(n, m, p, t, parties);
         } else if (mode == "plaintexts") {
             if (argc < 4) throw std::invalid_argument("plaintexts <in> <out>");
             plaintexts_mode(argv[2], argv[3]);

@@ -15,6 +15,13 @@
 // LocalCipherTextMultiplier::set_direct_differences(true) opens x - a, y - b with sub_ciphertext_tensors (one composition
 // per record where a negation is ct^(2^k - 1): k squarings and a product) and closes with add_plaintext_tensor(..., e*d)
 // (c2 o f^(ed) against the cached table of f) instead of an encryption and an addition: no negation and no encryption.
+//
+// Matrix triplets (set_matrix_triplets(true), the 2-D product only; the reference has no such flow).  The reference expands an
+// n x m by m x p product into n m p element products: n m p triplets and 2 n m p threshold decryptions.  With ONE matrix
+// triplet [A] (n x m), [B] (m x p), [C] = [A B]:
+//   E = Dec(X - A), D = Dec(Y - B);  X Y = E [B] + [A] D + [C] + E D
+// which opens n m + m p values, and spends a plaintext-left product (matmul_plaintext_ciphertext_tensors), a ciphertext-left
+// product (scal_ciphertext_tensors) and a plaintext matrix product mod 2^k (matmul_plaintext_tensors).
 #pragma once
 #include "hip_cryptosystem.hpp"
 
@@ -68,6 +75,23 @@ class LocalSMPCClient {
         return t;
     }
 
+    // one matrix triplet: {[A] (n x m), [B] (m x p), [C] = [A B mod 2^k] (n x p)}, A and B uniform in Z/2^k; the caller
+    // owns the elements and uses the triplet once
+    Vector<Tensor<CipherText *>> get_beavers_matrix_triplet(size_t n, size_t m, size_t p) {
+        Tensor<PlainText *> pa(n, m, nullptr), pb(m, p, nullptr);
+        for (size_t i = 0; i < n * m; i++) pa[i] = new PlainText(cs_.random_plaintext(cs_.message_bits()));
+        for (size_t i = 0; i < m * p; i++) pb[i] = new PlainText(cs_.random_plaintext(cs_.message_bits()));
+        auto pc = cs_.matmul_plaintext_tensors(pa, pb);
+        Vector<Tensor<CipherText *>> t;
+        t.push_back(cs_.encrypt_tensor(pk_, pa));
+        t.push_back(cs_.encrypt_tensor(pk_, pb));
+        t.push_back(cs_.encrypt_tensor(pk_, pc));
+        for (size_t i = 0; i < n * m; i++) delete pa[i];
+        for (size_t i = 0; i < m * p; i++) delete pb[i];
+        for (size_t i = 0; i < n * p; i++) delete pc[i];
+        return t;
+    }
+
     Tensor<PlainText *> decrypt_tensor(const Tensor<CipherText *> &ct) {
         decrypted_ += ct.num_elements();
         if (threshold_ == 0) return cs_.decrypt_tensor(sk_, ct);
@@ -108,6 +132,9 @@ class LocalCipherTextMultiplier {
     // off (the default): the reference's sequence of calls; on: differences by subtraction, e*d added as a plaintext
     void set_direct_differences(bool on) { direct_differences_m = on; }
     bool direct_differences() const { return direct_differences_m; }
+    // off (the default): the 2-D product expands into n m p element products as the reference does; on: one matrix triplet
+    void set_matrix_triplets(bool on) { matrix_triplets_m = on; }
+    bool matrix_triplets() const { return matrix_triplets_m; }
 
     CipherText multiply_ciphertexts(const CipherText &ct1, const CipherText &ct2) {
         Tensor<CipherText *> a(1, const_cast<CipherText *>(&ct1)), b(1, const_cast<CipherText *>(&ct2));
@@ -127,6 +154,7 @@ class LocalCipherTextMultiplier {
             // instead of the n*p*m serial nucomp loop (:85-101)
             const size_t n = ct1.shape()[0], m = ct1.shape()[1], p = ct2.shape()[1], nmp = n * m * p;
             if (ct2.shape()[0] != m) throw std::invalid_argument("Tensor shapes must be equal");
+            if (matrix_triplets_m) return matrix_mul_triplet(ct1, ct2, n, m, p);
             Tensor<CipherText *> ct1_nmp(nmp, nullptr), ct2_nmp(nmp, nullptr);
             for (size_t i = 0; i < n; i++)
                 for (size_t j = 0; j < m; j++)
@@ -231,8 +259,46 @@ class LocalCipherTextMultiplier {
         return ct;
     }
 
+    // X (n x m) . Y (m x p) with one matrix triplet: n m + m p opened values instead of 2 n m p
+    Tensor<CipherText *> matrix_mul_triplet(const Tensor<CipherText *> &x, const Tensor<CipherText *> &y, size_t n, size_t m, size_t p) {
+        auto &cs = client_m.crypto_system();
+        const auto &pk = client_m.network_public_key();
+        auto triplet = client_m.get_beavers_matrix_triplet(n, m, p);
+        auto &a_tensor = triplet[0], &b_tensor = triplet[1], &c_tensor = triplet[2];
+        auto x_sub_a = cs.sub_ciphertext_tensors(pk, x, a_tensor);
+        auto y_sub_b = cs.sub_ciphertext_tensors(pk, y, b_tensor);
+        auto e = client_m.decrypt_tensor(x_sub_a);
+        auto d = client_m.decrypt_tensor(y_sub_b);
+        auto e_b = cs.matmul_plaintext_ciphertext_tensors(pk, e, b_tensor);
+        auto a_d = cs.scal_ciphertext_tensors(pk, d, a_tensor);
+        auto s1 = cs.add_ciphertext_tensors(pk, e_b, a_d);
+        auto s2 = cs.add_ciphertext_tensors(pk, s1, c_tensor);
+        auto e_d = cs.matmul_plaintext_tensors(e, d);
+        auto ct = cs.add_plaintext_tensor(pk, s2, e_d);
+        for (size_t i = 0; i < n * m; i++) {
+            delete a_tensor[i];
+            delete x_sub_a[i];
+            delete e[i];
+        }
+        for (size_t i = 0; i < m * p; i++) {
+            delete b_tensor[i];
+            delete y_sub_b[i];
+            delete d[i];
+        }
+        for (size_t i = 0; i < n * p; i++) {
+            delete c_tensor[i];
+            delete e_b[i];
+            delete a_d[i];
+            delete s1[i];
+            delete s2[i];
+            delete e_d[i];
+        }
+        return ct;
+    }
+
     Client &client_m;
     bool direct_differences_m = false;
+    bool matrix_triplets_m = false;
 };
 
 }  // namespace CoFHE

@@ -11,6 +11,10 @@
  *   cofhe_hip_scal_matmul_records    the 2-D branch, cpu_cryptosystem_tensor_ops.inl:342-461
  *                                    (qfi_nupow tables, include/x86_64/qfi.inl:1-135, fused
  *                                    with the accumulation loop :403-417)
+ *   cofhe_hip_matmul_plain_ct_...    nothing: the plaintext matrix on the LEFT of the ciphertext matrix (y = W x); the
+ *                                    reference's 2-D branch is ciphertext-left only
+ *   cofhe_hip_matmul_plain_plain_... nothing: a plaintext matrix product mod 2^k, the E D term of a matrix Beaver
+ *                                    triplet (include/smpc/ciphertext_multiplications.hpp:51-111 expands into elements)
  *   cofhe_hip_decrypt_records        decrypt_tensor's per-element work, cpu_cryptosystem_tensor_ops.inl:21-33
  *   cofhe_hip_part_decrypt_records,  part_decrypt_tensor / combine_part_decryption_results_tensor,
  *   cofhe_hip_combine_part_...       cpu_cryptosystem_tensor_ops.inl:35-73 (cpu_cryptosystem_distributed.inl:231-285)
@@ -148,6 +152,25 @@ int cofhe_hip_pow_records(cofhe_hip_ctx *ctx, const void *d_base, const void *d_
 int cofhe_hip_scal_matmul_records(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_exp,
                                   const void *d_zero, void *d_out, uint32_t n, uint32_t m, uint32_t p,
                                   void *stream);
+/* The plaintext-LEFT product: out[i,k] = zero o prod_j cts[j,k]^s[i,j];  s n x m (exponent records), cts m x p, out n x p,
+ * zero 1 ct -- a linear layer y = W x with plaintext weights and encrypted activations.  The reference has no such
+ * operation (its 2-D scal_ciphertext_tensors has the ciphertext matrix on the left).  Runs cofhe_hip_scal_matmul_records on
+ * transposed views, out^T (p x n) = cts^T (p x m) . s^T (m x n): three transposes of fixed-size records around the existing
+ * routes, which keep their width choice, tree / chains / segments and options.  The class group is commutative and the
+ * reduced form unique, so the bytes are those of any other order of the factors.  The three temporaries (2 m p and 2 n p
+ * form records, n m exponent records) come from the context's block cache and go back behind the work queued on `stream`.
+ * Inherited from cofhe_hip_scal_matmul_records: m < 2^21, 2 n p records within the launch limit, and its one or two
+ * synchronisations of `stream` (NOT purely stream-ordered).  d_out must not overlap d_s, d_cts or d_zero: COFHE_HIP_EINVAL,
+ * nothing written.  n p == 0: nothing to do; m == 0: zero everywhere. */
+int cofhe_hip_matmul_plain_ct_records(cofhe_hip_ctx *ctx, const void *d_s, const void *d_cts, const void *d_zero, void *d_out,
+                                      uint32_t n, uint32_t m, uint32_t p, void *stream);
+/* out[i,k] = sum_j a[i,j] b[j,k] mod 2^kbits on exponent records (a n x m, b m x p, out n x p; 32 words each: 31 of
+ * magnitude and a sign word).  Negative inputs count as -mag mod 2^k and magnitudes of 2^k and above are reduced first; the
+ * outputs lie in [0, 2^k) with sign word 0.  1 <= kbits <= 639 (the bound of the decryption table), any kbits in that range:
+ * the top limb is masked.  One launch, purely stream-ordered: no workspace, no read-back.  d_out must not overlap the
+ * inputs.  The E D term of a matrix Beaver triplet, and the C = A B of its generation. */
+int cofhe_hip_matmul_plain_plain_records(cofhe_hip_ctx *ctx, const void *d_a, const void *d_b, void *d_out, uint32_t n, uint32_t m,
+                                         uint32_t p, uint32_t kbits, void *stream);
 /* decryption: for each of n ciphertexts, m with c2 o (c1^sk)^-1 = f^m.  sk: one exponent record on
  * the device; f_record: HOST pointer to the 168-word record of f = (2^(2k), 2^(k+1), 1 - Delta_K)
  * (its table of f^(-2^j) is built on first use and cached in the context).  d_out receives
@@ -309,6 +332,11 @@ int cofhe_hip_sub_ciphertext_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *t1
  * f_record: HOST record of f. */
 int cofhe_hip_add_plaintext_tensor_bytes(cofhe_hip_ctx *ctx, const uint8_t *cts, size_t lc, const uint8_t *pt, size_t lp,
                                          const uint32_t *f_record, uint32_t kbits, int mode, uint8_t **out, size_t *outlen);
+/* s (plaintext tensor, n x m) . cts (ciphertext tensor, m x p) -> n x p, from zero (1-element ciphertext tensor): the
+ * serialised twin of cofhe_hip_matmul_plain_ct_records.  Incoming forms are validated (COFHE_HIP_EINVAL for a non-form);
+ * COFHE_HIP_ESHAPE when an operand is not 2-D or s.shape[1] != cts.shape[0]. */
+int cofhe_hip_matmul_plain_ct_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *s, size_t ls, const uint8_t *cts, size_t lc,
+                                            const uint8_t *zero, size_t lz, uint8_t **out, size_t *outlen);
 /* s: plaintext tensor; 1-D x 1-D -> element-wise, 2-D x 2-D -> matmul (zero: 1-element tensor) */
 int cofhe_hip_scal_ciphertext_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *s, size_t ls,
                                             const uint8_t *cts, size_t lc, const uint8_t *zero, size_t lz,
