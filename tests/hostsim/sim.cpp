@@ -8,6 +8,13 @@
 #include <thread>
 #include <vector>
 
+// lane.hpp first, so that the rare-route marks of the arithmetic (CF_FLAG: bit 8 = the add-back of mp_divrem_norm) land in
+// a word the tests can read -- the product headers stay as they are
+#include "../../cofhe_amd/csrc/lane.hpp"
+static std::atomic<unsigned> g_sim_flags{0};
+#undef CF_FLAG
+#define CF_FLAG(bits) do { if (c.gl == 0) g_sim_flags.fetch_or(bits); } while (0)
+
 #include "../../cofhe_amd/csrc/form_io.hpp"
 
 using namespace cofhe;
@@ -82,6 +89,7 @@ static void st(const Ctx &c, const Mp<P> &x, uint32_t *w) {
 
 extern "C" {
 unsigned sim_status(void) { return g_sim_status.exchange(0); }     // device status word of the simulator (lane.hpp: CF_ST_*)
+unsigned sim_flags(void) { return g_sim_flags.exchange(0); }        // rare routes taken since the last call (CF_FLAG bits)
 void sim_stats(long *out) { memcpy(out, &g_stats, sizeof(g_stats)); memset(&g_stats, 0, sizeof(g_stats)); }
 
 // out[80] = x[40] * y[40], count instances
@@ -110,6 +118,44 @@ void sim_divrem21(const uint32_t *num, const uint32_t *den, uint32_t *quot, uint
             mp_divrem(c, n, ld<1>(c, den + 40 * i), q);
             st(c, q, quot + 80 * i);
             st(c, n, rem + 80 * i);
+        }
+    });
+}
+// the other instantiations: num[40] / den[40] (qf.hpp: the word-factor route and the general gcd structure) and
+// num[80] / den[80] (none in the product: the staged-divisor loop of mp_divrem and, below 64 bits, mp_divrem_cons)
+void sim_divrem11(const uint32_t *num, const uint32_t *den, uint32_t *quot, uint32_t *rem, int count) {
+    run_group([&](Ctx &c) {
+        for (int i = 0; i < count; i++) {
+            Mp<1> n = ld<1>(c, num + 40 * i), q;
+            mp_divrem(c, n, ld<1>(c, den + 40 * i), q);
+            st(c, q, quot + 40 * i);
+            st(c, n, rem + 40 * i);
+        }
+    });
+}
+void sim_divrem22(const uint32_t *num, const uint32_t *den, uint32_t *quot, uint32_t *rem, int count) {
+    run_group([&](Ctx &c) {
+        for (int i = 0; i < count; i++) {
+            Mp<2> n = ld<2>(c, num + 80 * i), q;
+            mp_divrem(c, n, ld<2>(c, den + 80 * i), q);
+            st(c, q, quot + 80 * i);
+            st(c, n, rem + 80 * i);
+        }
+    });
+}
+// x[80] divided by the word W through mp_divrem_word, and x mod W through mp_mod_word: quot[80], out[2 i] = remainder,
+// out[2 i + 1] = mp_mod_word
+void sim_divrem_word(const uint32_t *x, const uint32_t *W, uint32_t *quot, uint32_t *out, int count) {
+    run_group([&](Ctx &c) {
+        for (int i = 0; i < count; i++) {
+            const WordDiv d = worddiv_make(W[i]);
+            Mp<2> v = ld<2>(c, x + 80 * i);
+            const uint32_t m = mp_mod_word(c, v, d), r = mp_divrem_word(c, v, d);
+            st(c, v, quot + 80 * i);
+            if (c.gl == 0) {
+                out[2 * i] = r;
+                out[2 * i + 1] = m;
+            }
         }
     });
 }
@@ -150,15 +196,49 @@ void sim_mod_primorial(const uint32_t *x, uint32_t *out, int count) {
 void sim_word_xgcd16(const uint32_t *m, const uint32_t *a, uint32_t *g, uint32_t *inv, int count) {
     for (int i = 0; i < count; i++) word_xgcd16(m[i], a[i], g[i], inv[i]);
 }
-// r[80] = A*x - B*y  and  s[80] = A*x + B*y (mod 2^2560)
-void sim_lincomb(const uint32_t *x, const uint32_t *y, uint32_t A, uint32_t B, uint32_t *r, uint32_t *s, int count) {
+// r[80] = A*x - B*y  and  s[80] = A*x + B*y (mod 2^2560); top[2 i], top[2 i + 1] = the words that leave the top plane
+// (mp_lincomb_sub_carry: A*x - B*y == r + (word - B) 2^2560; mp_lincomb_add: the high word of the sum)
+void sim_lincomb(const uint32_t *x, const uint32_t *y, uint32_t A, uint32_t B, uint32_t *r, uint32_t *s, uint32_t *top, int count) {
     run_group([&](Ctx &c) {
         for (int i = 0; i < count; i++) {
             Mp<2> a = ld<2>(c, x + 80 * i), b = ld<2>(c, y + 80 * i), o;
-            mp_lincomb_sub(c, o, A, a, B, b);
+            const uint32_t ws = mp_lincomb_sub_carry(c, o, A, a, B, b);
             st(c, o, r + 80 * i);
-            (void)mp_lincomb_add(c, o, A, a, B, b);
+            const uint32_t wa = mp_lincomb_add(c, o, A, a, B, b);
             st(c, o, s + 80 * i);
+            if (c.gl == 0) {
+                top[2 * i] = ws;
+                top[2 * i + 1] = wa;
+            }
+        }
+    });
+}
+// s[80] = x + y (mp_add: the general resolve on a sum), carry[i] = what leaves the top plane
+void sim_add(const uint32_t *x, const uint32_t *y, uint32_t *s, uint32_t *carry, int count) {
+    run_group([&](Ctx &c) {
+        for (int i = 0; i < count; i++) {
+            Mp<2> o;
+            const uint32_t cy = mp_add(c, o, ld<2>(c, x + 80 * i), ld<2>(c, y + 80 * i));
+            st(c, o, s + 80 * i);
+            if (c.gl == 0) carry[i] = cy;
+        }
+    });
+}
+// out[5 i ..] = mp_cmp(x, y) | low, high word of mp_bits64(x, pos) | mp_bits32(x, pos) | mp_get_limb(x, idx)
+void sim_bits(const uint32_t *x, const uint32_t *y, const int *pos, const int *idx, uint32_t *out, int count) {
+    run_group([&](Ctx &c) {
+        for (int i = 0; i < count; i++) {
+            const Mp<2> a = ld<2>(c, x + 80 * i), b = ld<2>(c, y + 80 * i);
+            const int cm = mp_cmp(c, a, b);
+            const uint64_t w = mp_bits64(c, a, pos[i]);
+            const uint32_t h = mp_bits32(c, a, pos[i]), l = mp_get_limb(c, a, idx[i]);
+            if (c.gl == 0) {
+                out[5 * i] = (uint32_t)cm;
+                out[5 * i + 1] = (uint32_t)w;
+                out[5 * i + 2] = (uint32_t)(w >> 32);
+                out[5 * i + 3] = h;
+                out[5 * i + 4] = l;
+            }
         }
     });
 }

@@ -29,13 +29,14 @@ unsigned simw_status(void) { return g_sim_status.exchange(0); }
 void simw_mul(const uint32_t *x, const uint32_t *y, uint32_t *out, int count) {
     for (int i = 0; i < count; i++) stw(w_mul(ldw(x + 128 * i), ldw(y + 128 * i)), out + 128 * i);
 }
-// r = A x - B y and s = A x + B y (mod 2^4096)
-void simw_lincomb(const uint32_t *x, const uint32_t *y, uint32_t A, uint32_t B, uint32_t *r, uint32_t *s, int count) {
+// r = A x - B y and s = A x + B y (mod 2^4096); top[2 i], top[2 i + 1] = the words that leave the top (w_lincomb_sub:
+// A x - B y == r + (word - B) 2^4096; w_lincomb_add: the high word of the sum)
+void simw_lincomb(const uint32_t *x, const uint32_t *y, uint32_t A, uint32_t B, uint32_t *r, uint32_t *s, uint32_t *top, int count) {
     for (int i = 0; i < count; i++) {
         WN o;
-        (void)w_lincomb_sub(o, A, ldw(x + 128 * i), B, ldw(y + 128 * i));
+        top[2 * i] = w_lincomb_sub(o, A, ldw(x + 128 * i), B, ldw(y + 128 * i));
         stw(o, r + 128 * i);
-        (void)w_lincomb_add(o, A, ldw(x + 128 * i), B, ldw(y + 128 * i));
+        top[2 * i + 1] = w_lincomb_add(o, A, ldw(x + 128 * i), B, ldw(y + 128 * i));
         stw(o, s + 128 * i);
     }
 }

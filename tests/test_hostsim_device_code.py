@@ -10,6 +10,7 @@ import sys
 import numpy as np
 import pytest
 
+import prim_cases as PC
 import simlib as S
 from conftest import ROOT, load_json
 
@@ -28,35 +29,47 @@ def rnd(rng, bits):
 
 
 def test_mul():
-    rng = random.Random(1)
     L = S.lib()
-    sizes = [1, 31, 32, 33, 160, 161, 640, 1044, 1279, 1280]
-    xs = [rnd(rng, rng.choice(sizes)) for _ in range(24)] + [0, 1, (1 << 1280) - 1]
-    ys = [rnd(rng, rng.choice(sizes)) for _ in range(24)] + [(1 << 1280) - 1, 0, (1 << 1280) - 1]
+    xs, ys, xs2, ys2 = PC.mul_cases()
     out = np.zeros(80 * len(xs), dtype=np.uint32)
     L.sim_mul11(S.P(S.pack(xs, 40)), S.P(S.pack(ys, 40)), S.P(out), len(xs))
     assert S.unpack(out, 80) == [a * b for a, b in zip(xs, ys)]
-    xs2 = [rnd(rng, rng.choice([2086, 2560, 1300, 5])) for _ in range(10)] + [(1 << 2560) - 1]
-    ys2 = [rnd(rng, rng.choice([1044, 1280, 17, 522])) for _ in range(10)] + [(1 << 1280) - 1]
     out = np.zeros(120 * len(xs2), dtype=np.uint32)
     L.sim_mul21(S.P(S.pack(xs2, 80)), S.P(S.pack(ys2, 40)), S.P(out), len(xs2))
     assert S.unpack(out, 120) == [a * b for a, b in zip(xs2, ys2)]
 
 
-def test_lincomb_shift_bitlen():
-    rng = random.Random(2)
-    L = S.lib()
-    n = 12
-    xs = [rnd(rng, 2500) for _ in range(n)]
-    ys = [rnd(rng, 2400) for _ in range(n)]
-    for A, B in [(0x7FFFFFFF, 12345), (1, 0x7FFFFFFF), (65535, 1)]:
+def _check_lincomb(L, cases):
+    """mp_lincomb_sub_carry and mp_lincomb_add on (A, B, x, y): both results modulo 2^2560 and the words that leave the top
+    plane -- A x - B y == r + (word - B) 2^2560, A x + B y == s + word 2^2560"""
+    groups = {}
+    for A, B, x, y in cases:
+        groups.setdefault((A, B), []).append((x, y))
+    for (A, B), pairs in groups.items():
+        xs, ys = [p[0] for p in pairs], [p[1] for p in pairs]
+        n = len(xs)
         r = np.zeros(80 * n, dtype=np.uint32)
         s = np.zeros(80 * n, dtype=np.uint32)
-        L.sim_lincomb(S.P(S.pack(xs, 80)), S.P(S.pack(ys, 80)), C.c_uint32(A), C.c_uint32(B), S.P(r), S.P(s), n)
-        assert S.unpack(r, 80) == [(A * a - B * b) % M2 for a, b in zip(xs, ys)]
-        assert S.unpack(s, 80) == [(A * a + B * b) % M2 for a, b in zip(xs, ys)]
-    for sh in [0, 1, 31, 32, 33, 160, 161, 1279, 1280, 1281, 2000]:
-        vals = [rnd(rng, b) for b in (2560, 100, 1280)] + [0, 1, M2 - 1]
+        top = np.zeros(2 * n, dtype=np.uint32)
+        L.sim_lincomb(S.P(S.pack(xs, 80)), S.P(S.pack(ys, 80)), C.c_uint32(A), C.c_uint32(B), S.P(r), S.P(s), S.P(top), n)
+        assert S.unpack(r, 80) == [(A * a - B * b) % M2 for a, b in zip(xs, ys)], (A, B)
+        assert S.unpack(s, 80) == [(A * a + B * b) % M2 for a, b in zip(xs, ys)], (A, B)
+        assert [int(t) for t in top[0::2]] == [(A * a - B * b) // M2 + B for a, b in zip(xs, ys)], (A, B)
+        assert [int(t) for t in top[1::2]] == [(A * a + B * b) // M2 for a, b in zip(xs, ys)], (A, B)
+    xs, ys = [c[2] for c in cases], [c[3] for c in cases]
+    n = len(xs)
+    s = np.zeros(80 * n, dtype=np.uint32)
+    cy = np.zeros(n, dtype=np.uint32)
+    L.sim_add(S.P(S.pack(xs, 80)), S.P(S.pack(ys, 80)), S.P(s), S.P(cy), n)
+    assert S.unpack(s, 80) == [(a + b) % M2 for a, b in zip(xs, ys)]
+    assert [int(t) for t in cy] == [(a + b) // M2 for a, b in zip(xs, ys)]
+
+
+def _check_shifts(L, cases):
+    groups = {}
+    for sh, v in cases:
+        groups.setdefault(sh, []).append(v)
+    for sh, vals in groups.items():
         m = len(vals)
         l, r, h = (np.zeros(80 * m, dtype=np.uint32) for _ in range(3))
         bits = np.zeros(m, dtype=np.int32)
@@ -67,72 +80,51 @@ def test_lincomb_shift_bitlen():
         assert [int(b) for b in bits] == [a.bit_length() for a in vals]
 
 
+def test_lincomb_shift_bitlen():
+    L = S.lib()
+    lin, shifts = PC.lincomb_shift_cases()
+    _check_lincomb(L, lin)
+    _check_shifts(L, shifts)
+
+
 def test_carry_ripples_across_lanes():
     """long carry / borrow runs: the resolve takes its rare full-chain path (limb 0 of a chunk == 2^32 - 1)"""
+    _check_lincomb(S.lib(), PC.carry_ripple_cases())
+
+
+def test_carry_chain_bounds_and_resolve_handovers():
+    """the carry chain of lincomb_plane with every product and carry at its maximum (A + B = 2^32 on all-ones operands),
+    sums that carry out of the top plane, a word handed from lane 7 of plane 0 into an all-ones lane 0 of plane 1"""
+    _check_lincomb(S.lib(), PC.lincomb_bound_cases())
+
+
+def test_bit_positions_at_lane_and_plane_edges():
+    """shifts and lengths at limb, lane and plane edges; mp_cmp, mp_bits64, mp_bits32, mp_get_limb on windows that straddle
+    a lane edge, the plane edge and the top of the number"""
     L = S.lib()
-    xs = [(1 << 1600) - 1, (1 << 2560) - 1, (1 << 160) - 1, (1 << 1600), (1 << 2400), ((1 << 800) - 1) << 160, (1 << 2559) + (1 << 32) - 1,
-          (1 << 1280) - 1, 1 << 1280]
-    ys = [1, 1, (1 << 32) - 1, 1, (1 << 161) + 1, 1 << 160, 1, 1, 1]
-    # the sparse resolve of sums (mp_resolve_sparse): a word handed over into an all-ones limb 0 next to a limb 1 that is
-    # NOT all ones (fast path: the carry stops in limb 1) although limbs 2-4 are; then the same with limb 1 all ones in one
-    # lane only (fallback to the general resolve for the whole wavefront)
-    pat = lambda l1: sum(((0xFFFFFFFF if i % 5 != 1 else l1(i)) << (32 * i)) for i in range(80))
-    top = sum(1 << (32 * i) for i in range(80) if i % 5 == 4)
-    xs += [pat(lambda i: 5), pat(lambda i: 0xFFFFFFFF if i == 16 else 7), pat(lambda i: 0xFFFFFFFE)]
-    ys += [top, top, top | 1]
-    n = len(xs)
-    r = np.zeros(80 * n, dtype=np.uint32)
-    s = np.zeros(80 * n, dtype=np.uint32)
-    for A, B in [(1, 1), (3, 1), (1, 0x7FFFFFFF), (0x3FFFFFF, 0x3FFFFFF)]:
-        L.sim_lincomb(S.P(S.pack(xs, 80)), S.P(S.pack(ys, 80)), C.c_uint32(A), C.c_uint32(B), S.P(r), S.P(s), n)
-        assert S.unpack(r, 80) == [(A * a - B * b) % M2 for a, b in zip(xs, ys)]
-        assert S.unpack(s, 80) == [(A * a + B * b) % M2 for a, b in zip(xs, ys)]
+    _check_shifts(L, PC.shift_edge_cases())
+    cases = PC.bits_cases()
+    n = len(cases)
+    pos = np.array([c[2] for c in cases], dtype=np.int32)
+    idx = np.array([c[3] for c in cases], dtype=np.int32)
+    out = np.zeros(5 * n, dtype=np.uint32)
+    L.sim_bits(S.P(S.pack([c[0] for c in cases], 80)), S.P(S.pack([c[1] for c in cases], 80)), pos.ctypes.data_as(C.POINTER(C.c_int)),
+               idx.ctypes.data_as(C.POINTER(C.c_int)), S.P(out), n)
+    for i, (x, y, p, k) in enumerate(cases):
+        o = [int(v) for v in out[5 * i:5 * i + 5]]
+        assert o[0] == ((x > y) - (x < y)) % (1 << 32), i
+        assert o[1] | (o[2] << 32) == (x >> p) & ((1 << 64) - 1), i
+        assert o[3] == (x >> p) & 0xFFFFFFFF, i
+        assert o[4] == ((x >> (32 * k)) & 0xFFFFFFFF if 0 <= k < 80 else 0), i
 
 
 def test_divexact():
     """2-adic exact division against Python: odd / even divisors, word-sized divisors, quotients of every length,
     32 or more trailing zero bits in the divisor (long-division route), zero numerator"""
-    rng = random.Random(33)
     L = S.lib()
-    cases = []
-    for _ in range(40):
-        db = rng.choice([1044, 1280, 522, 33, 32, 31, 1, 64, 700, 1043])
-        qb = rng.choice([0, 1, 31, 32, 33, 522, 544, 545, 1044, 1279])
-        d = max(1, rnd(rng, db)) | (1 << (db - 1))
-        if rng.random() < 0.5:
-            d = (d >> rng.choice([1, 2, 5, 31])) << rng.choice([1, 2, 5, 31])      # even divisors
-            d = max(d, 2)
-        q = rnd(rng, qb)
-        if (d * q).bit_length() > 2560:
-            continue
-        cases.append((d * q, d, q))
-    cases += [(0, 12345, 0), (7 << 40, 7 << 35, 32), ((1 << 1279) * 3, 3, 1 << 1279), ((1 << 64) * 5, 1 << 64, 5), (1 << 2000, 1 << 1000, 1 << 1000)]
-    # the two-digits-per-pass loop (one carry resolve per pair, pending words fed into the second chain): quotients and
-    # divisors of all-ones / sparse limbs (every hand-over word and ripple at its largest), divisors whose second limb is 0 or
-    # all ones (the 64-bit inverse), 31 trailing zero bits, odd and even digit counts, numerators that fill both planes
-    for _ in range(300):
-        db = rng.choice([1044, 1043, 1280, 1100, 65, 64, 63, 97, 160, 161, 320])
-        d = rnd(rng, db) | (1 << (db - 1)) | 1
-        kind = rng.randrange(6)
-        if kind == 0:
-            d = (1 << db) - 1
-        elif kind == 1:
-            d = (d >> 64 << 64) | (0xFFFFFFFF << 32) | (d & 0xFFFFFFFF) | 1
-        elif kind == 2:
-            d = (d >> 64 << 64) | (d & 0xFFFFFFFF) | 1                          # second limb zero
-        elif kind == 3:
-            d = ((d >> 31) << 31) | (1 << 31) if db > 40 else d                 # 31 trailing zero bits
-        qb = rng.choice([1, 32, 33, 63, 64, 65, 95, 96, 97, 522, 544, 545, 576, 1044, 1056, 1216, 1279])
-        q = rnd(rng, qb) | (1 << (qb - 1))
-        if rng.random() < 0.3:
-            q = (1 << qb) - 1
-        elif rng.random() < 0.2:
-            q = sum(1 << (32 * t_) for t_ in range(0, (qb + 31) // 32, 2)) % (1 << qb) or 1
-        if (d * q).bit_length() > 2560 - 2:
-            continue
-        cases.append((d * q, d, q))
+    cases, nql = PC.divexact_cases()
     n = len(cases)
-    nq = np.array([(q.bit_length() + 31) // 32 + (i % 3) for i, (_, _, q) in enumerate(cases)], dtype=np.int32)
+    nq = np.array(nql, dtype=np.int32)
     out = np.zeros(80 * n, dtype=np.uint32)
     L.sim_divexact21(S.P(S.pack([c[0] for c in cases], 80)), S.P(S.pack([c[1] for c in cases], 40)), S.P(out),
                      nq.ctypes.data_as(C.POINTER(C.c_int)), n)
@@ -297,20 +289,25 @@ def test_euclid_serve_protocol():
         assert abs(R0 * C1 + R1 * C0) == v1 or math.gcd(v1, r) != 1
 
 
+def _divrem(L, pn, pd, pairs):
+    """mp_divrem<pn, pd> on (num, den) pairs through the simulator: quotients and remainders"""
+    n = len(pairs)
+    q = np.zeros(40 * pn * n, dtype=np.uint32)
+    r = np.zeros(40 * pn * n, dtype=np.uint32)
+    getattr(L, "sim_divrem%d%d" % (pn, pd))(S.P(S.pack([p[0] for p in pairs], 40 * pn)), S.P(S.pack([p[1] for p in pairs], 40 * pd)),
+                                            S.P(q), S.P(r), n)
+    return S.unpack(q, 40 * pn), S.unpack(r, 40 * pn)
+
+
 def test_divrem_and_xgcd():
-    rng = random.Random(3)
     L = S.lib()
-    nums = [rnd(rng, rng.choice([2088, 2560, 1566, 1044, 64, 40, 2000])) for _ in range(24)] + [0, 5, M2 - 1, M2 - 1, 1 << 2559]
-    dens = [max(1, rnd(rng, rng.choice([1044, 1280, 522, 33, 32, 31, 1, 64, 700]))) for _ in range(24)] + [7, 7, 1, (1 << 1280) - 1, 3]
-    n = len(nums)
-    q = np.zeros(80 * n, dtype=np.uint32)
-    r = np.zeros(80 * n, dtype=np.uint32)
-    L.sim_divrem21(S.P(S.pack(nums, 80)), S.P(S.pack(dens, 40)), S.P(q), S.P(r), n)
-    assert S.unpack(q, 80) == [a // b for a, b in zip(nums, dens)]
-    assert S.unpack(r, 80) == [a % b for a, b in zip(nums, dens)]
-    xa = [rnd(rng, 1044) | 1 for _ in range(10)] + [rnd(rng, 1280) for _ in range(3)] + [12, 1 << 1000, 5, 1, 6 << 700]
-    ya = [rnd(rng, 1040) for _ in range(10)] + [rnd(rng, 600) for _ in range(3)] + [18, 3, 5, 1, 9 << 650]
-    xa, ya = [max(a, b) for a, b in zip(xa, ya)], [min(a, b) for a, b in zip(xa, ya)]
+    L.sim_flags.restype = C.c_uint
+    nums, dens, xa, ya = PC.divrem_xgcd_cases()
+    L.sim_flags()
+    q, r = _divrem(L, 2, 1, list(zip(nums, dens)))
+    assert q == [a // b for a, b in zip(nums, dens)]
+    assert r == [a % b for a, b in zip(nums, dens)]
+    assert L.sim_flags() & 8 == 0          # random operands do not reach the add-back of mp_divrem_norm (~2^-17 per digit)
     n = len(xa)
     d = np.zeros(40 * n, dtype=np.uint32)
     u = np.zeros(40 * n, dtype=np.uint32)
@@ -319,6 +316,57 @@ def test_divrem_and_xgcd():
     for dd, uu, ss, a, b in zip(S.unpack(d, 40), S.unpack(u, 40), sg, xa, ya):
         assert dd == math.gcd(a, b)
         assert (int(ss) * uu * b - dd) % a == 0
+
+
+@pytest.mark.parametrize("pn,pd", [(2, 1), (1, 1), (2, 2)])
+def test_divrem_add_back(pn, pd):
+    """every instantiation of mp_divrem on the families that reach the add-back (num = den Q - 1, num = den Q + den - 1:
+    the remainder is den - 1, divisors random, 0x80000000:00000000 followed by all ones, and all ones) and on num < den,
+    num == den, num == 0, word-sized divisors and (pd = 2) divisors below 64 bits.  That the family does reach the
+    add-back is checked, not assumed: mp_divrem_norm marks the route with CF_FLAG(8), which the simulator records; the
+    staged-divisor loop of pd = 2 carries no mark, so its digit estimate is restated in Python (prim_cases.staged_loop_overshoots)
+    and must land above the true digit in at least half of the family's cases."""
+    L = S.lib()
+    L.sim_flags.restype = C.c_uint
+    L.sim_status.restype = C.c_uint
+    addback, rest = PC.divrem_cases(pn, pd)
+    assert len(addback) >= 100
+    L.sim_flags()
+    L.sim_status()
+    q, r = _divrem(L, pn, pd, rest)
+    assert q == [a // b for a, b in rest] and r == [a % b for a, b in rest]
+    L.sim_flags()
+    pairs = [(n_, d_) for n_, d_, _ in addback]
+    q, r = _divrem(L, pn, pd, pairs)
+    assert q == [a // b for a, b in pairs] and r == [a % b for a, b in pairs]
+    if pd == 1:
+        assert L.sim_flags() & 8, "the add-back family did not reach the add-back of mp_divrem_norm"
+        # and it is the rule in the family, not one lucky case: each case alone
+        hit = 0
+        for pr in pairs[::7]:
+            _divrem(L, pn, pd, [pr])
+            hit += (L.sim_flags() >> 3) & 1
+        assert 2 * hit >= len(pairs[::7]), (hit, len(pairs[::7]))
+    else:
+        over = [PC.staged_loop_overshoots(n_, d_) for n_, d_ in pairs if d_.bit_length() >= 64]      # below: mp_divrem_cons
+        assert len(over) >= 100 and all(o is not None for o in over)
+        assert 2 * sum(1 for o in over if o) >= len(over), (sum(1 for o in over if o), len(over))
+    assert L.sim_status() == 0
+    # a zero divisor: quotient 0 as mp.hpp states, CF_ST_DIV_CAP in the status word, a normal return
+    q, r = _divrem(L, pn, pd, [(12345 << 700, 0)])
+    assert q == [0] and r == [12345 << 700]
+    assert L.sim_status() == PC.ST_DIV_CAP
+
+
+def test_divexact_by_zero_is_a_status():
+    L = S.lib()
+    L.sim_status.restype = C.c_uint
+    L.sim_status()
+    out = np.ones(80, dtype=np.uint32)
+    nq = np.array([3], dtype=np.int32)
+    L.sim_divexact21(S.P(S.pack([7 << 64], 80)), S.P(S.pack([0], 40)), S.P(out), nq.ctypes.data_as(C.POINTER(C.c_int)), 1)
+    assert S.unpack(out, 80) == [0]
+    assert L.sim_status() == PC.ST_DIV_CAP
 
 
 def _pool(name):
@@ -523,7 +571,6 @@ def test_euclid_wg_cofactors_and_stops():
     entry = "sim_euclid_wg"
     import ctypes as C
     L = S.lib()
-    rng = random.Random(31)
 
     def run(pairs, stops):
         n = len(pairs)
@@ -541,23 +588,12 @@ def test_euclid_wg_cofactors_and_stops():
         return res
 
     n = L.sim_wg_groups()
-    full, part = [], []
-    for bits in (33, 64, 65, 96, 200, 500, 1043, 1044, 1171, 1200):
-        for _ in range(2):
-            a = rnd(rng, bits) | (1 << (bits - 1))
-            full.append((a, rnd(rng, bits - 1) | 1))
-    a0 = rnd(rng, 1043) | (1 << 1042)
-    full += [(a0, 3), (a0, 5), (a0, 1 << 200), (a0, (1 << 252)), (a0, rnd(rng, 700) | 1), (a0, a0), (a0, 0), (a0, 1), (a0, a0 - 1),
-             (6 * (rnd(rng, 500) | 1), 10 * (rnd(rng, 480) | 1))]
+    full, part = PC.euclid_wg_cases(n)
     for i0 in range(0, len(full), n):
         chunk = full[i0:i0 + n]
         for (a, b), (x, y, cx, cy) in zip(chunk, run(chunk, [-1] * len(chunk))):
             assert x == math.gcd(a, b) and y == 0, (a.bit_length(), b.bit_length())
             assert (cx * b - x) % a == 0 and (cy * b) % a == 0
-    for _ in range(2 * n):
-        a = rnd(rng, 1043) | (1 << 1042)
-        b = rnd(rng, 1041)
-        part.append((a, b, rng.choice([530, 521, 700, 64, 1000, 33])))
     for i0 in range(0, len(part), n):
         chunk = part[i0:i0 + n]
         res = run([(a, b) for a, b, _ in chunk], [s for _, _, s in chunk])
@@ -696,23 +732,7 @@ def test_word_route_primitives():
     import ctypes as C
     import math
     import numpy as np
-    rng = P.SplitMix64(616)
-    ds = [2, 3, 29, 31, 255, 256, 257, 4099, 32749, 65521, 65535] + [2 + rng.below(65534) for _ in range(40)]
-    Ws = [d_ * d_ for d_ in ds] + [1, 2, 3, 0xFFFFFFFF, 0xFFFFFFFB, 0x80000000, 0x10001] + [1 + rng.below(0xFFFFFFFF) for _ in range(40)]
-    Ws = [w for w in Ws if 0 < w < (1 << 32)]
-    xs = []
-    for i, w in enumerate(Ws):
-        kind = i % 4
-        if kind == 0:
-            x = rng.bits(2560)
-        elif kind == 1:
-            x = (1 << 2560) - 1 - rng.bits(40)
-        elif kind == 2:
-            x = sum(1 << (32 * rng.below(80)) for _ in range(3)) * (1 + rng.below(1 << 16))
-            x %= 1 << 2560
-        else:
-            x = rng.bits(1044)
-        xs.append(x)
+    Ws, xs, ps, ms, as_ = PC.word_route_cases()
     xa = S.pack(xs, 80)
     wa = np.array(Ws, dtype=np.uint32)
     out = np.zeros(2 * len(Ws), dtype=np.uint32)
@@ -720,22 +740,19 @@ def test_word_route_primitives():
     for i, (x, w) in enumerate(zip(xs, Ws)):
         assert int(out[2 * i]) == (x % (1 << 1280)) % w, (i, w)
         assert int(out[2 * i + 1]) == x % w, (i, w)
+    # mp_divrem_word and mp_mod_word (any 32-bit word: the 64-bit Barrett reduction and the suffix scan over the lanes)
+    quot = np.zeros(80 * len(Ws), dtype=np.uint32)
+    out = np.zeros(2 * len(Ws), dtype=np.uint32)
+    S.lib().sim_divrem_word(S.P(xa), S.P(wa), S.P(quot), S.P(out), len(Ws))
+    assert S.unpack(quot, 80) == [x // w for x, w in zip(xs, Ws)]
+    assert [int(v) for v in out[0::2]] == [x % w for x, w in zip(xs, Ws)]
+    assert [int(v) for v in out[1::2]] == [x % w for x, w in zip(xs, Ws)]
     # mp_mod_primorial: the constant modulus 2*3*...*23 of the coprime-representative test (tabulated limb weights)
     M = 223092870
-    ps = [0, 1, M - 1, M, M + 1, (1 << 1280) - 1, (1 << 1279), (1 << 1043) - 1] + [rng.bits(1280) for _ in range(40)] + \
-         [rng.bits(1044) for _ in range(40)] + [M * rng.bits(1200) for _ in range(8)] + [sum(0xFFFFFFFF << (32 * i) for i in range(0, 40, 3))]
     pa = S.pack(ps, 40)
     pout = np.zeros(len(ps), dtype=np.uint32)
     S.lib().sim_mod_primorial(S.P(pa), S.P(pout), len(ps))
     assert [int(v) for v in pout] == [x % M for x in ps]
-    ms, as_ = [], []
-    for m_ in [2, 3, 4, 29, 30, 841, 65521, 65535, 46368, 28657] + [2 + rng.below(65534) for _ in range(300)]:
-        for a_ in {1, m_ - 1, max(1, m_ // 2), 1 + rng.below(m_ - 1), 1 + rng.below(m_ - 1)}:
-            if 0 < a_ < m_:
-                ms.append(m_)
-                as_.append(a_)
-    ms += [46368, 65535, 65534]            # consecutive Fibonacci numbers: the longest remainder sequences of 16-bit operands
-    as_ += [28657, 65534, 65533]
     ma, aa = np.array(ms, dtype=np.uint32), np.array(as_, dtype=np.uint32)
     g, inv = np.zeros(len(ms), dtype=np.uint32), np.zeros(len(ms), dtype=np.uint32)
     S.lib().sim_word_xgcd16(S.P(ma), S.P(aa), S.P(g), S.P(inv), len(ms))

@@ -14,6 +14,7 @@ from conftest import ROOT, load_json
 
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import pyref as P  # noqa: E402
+import prim_cases as PC  # noqa: E402
 import simlib as S8  # noqa: E402  (record packing helpers)
 import simwlib as W  # noqa: E402
 
@@ -26,26 +27,27 @@ def rb(rng, b):
     return rng.getrandbits(b) if b else 0
 
 
-def test_wide_mul_lincomb_shift():
-    L = W.lib()
-    rng = random.Random(5)
-    xs = [rb(rng, rng.choice([1, 31, 32, 33, 64, 65, 522, 1044, 1056, 2088, 2112])) for _ in range(60)] + [0, 1, (1 << 2112) - 1, (1 << 1056) - 1]
-    ys = [rb(rng, rng.choice([1, 31, 32, 33, 64, 65, 522, 1044, 1056, 1984])) for _ in range(60)] + [5, 0, (1 << 1984) - 1, (1 << 1056) - 1]
-    out = np.zeros(128 * len(xs), dtype=np.uint32)
-    L.simw_mul(W.P(W.pack(xs)), W.P(W.pack(ys)), W.P(out), len(xs))
-    assert W.unpack(out) == [(a * b) % W.M for a, b in zip(xs, ys)]
-    # linear combinations: the two's complement over the whole capacity (long runs of all-ones limbs: every carry ripple the
-    # generate / propagate ballots have to carry across lanes), all-ones operands, the widest multipliers
-    xs = [rb(rng, rng.choice([4000, 2000, 1044, 64, 63])) for _ in range(40)] + [W.M - 1, (1 << 1600) - 1, 1 << 3000]
-    ys = [rb(rng, rng.choice([3990, 1990, 1040, 60, 5])) for _ in range(40)] + [1, 1, 1]
-    for A, B in [(1, 1), (0x3FFFFFF, 0x3FFFFFF), (1, 0xFFFFFFFF), (65535, 3)]:
+def _check_wide_lincomb(L, cases):
+    groups = {}
+    for A, B, x, y in cases:
+        groups.setdefault((A, B), []).append((x, y))
+    for (A, B), pairs in groups.items():
+        xs, ys = [p[0] for p in pairs], [p[1] for p in pairs]
         r = np.zeros(128 * len(xs), dtype=np.uint32)
         s = np.zeros(128 * len(xs), dtype=np.uint32)
-        L.simw_lincomb(W.P(W.pack(xs)), W.P(W.pack(ys)), C.c_uint32(A), C.c_uint32(B), W.P(r), W.P(s), len(xs))
+        top = np.zeros(2 * len(xs), dtype=np.uint32)
+        L.simw_lincomb(W.P(W.pack(xs)), W.P(W.pack(ys)), C.c_uint32(A), C.c_uint32(B), W.P(r), W.P(s), W.P(top), len(xs))
         assert W.unpack(r) == [(A * a - B * b) % W.M for a, b in zip(xs, ys)], (A, B)
         assert W.unpack(s) == [(A * a + B * b) % W.M for a, b in zip(xs, ys)], (A, B)
-    vals = [rb(rng, 4096), rb(rng, 100), rb(rng, 1280), 0, 1, W.M - 1, rb(rng, 2100)]
-    for sh in [0, 1, 31, 32, 33, 63, 64, 65, 95, 96, 97, 160, 1279, 2000, 4095]:
+        assert [int(t) for t in top[0::2]] == [(A * a - B * b) // W.M + B for a, b in zip(xs, ys)], (A, B)
+        assert [int(t) for t in top[1::2]] == [(A * a + B * b) // W.M for a, b in zip(xs, ys)], (A, B)
+
+
+def _check_wide_shifts(L, cases):
+    groups = {}
+    for sh, v in cases:
+        groups.setdefault(sh, []).append(v)
+    for sh, vals in groups.items():
         l = np.zeros(128 * len(vals), dtype=np.uint32)
         r = np.zeros(128 * len(vals), dtype=np.uint32)
         bits = np.zeros(len(vals), dtype=np.int32)
@@ -53,8 +55,26 @@ def test_wide_mul_lincomb_shift():
         assert W.unpack(l) == [(a << sh) % W.M for a in vals], sh
         assert W.unpack(r) == [a >> sh for a in vals], sh
         assert [int(b) for b in bits] == [a.bit_length() for a in vals]
-    for a, b in [(5, 7), (7, 5), (1 << 4000, 1 << 4000), ((1 << 2000) + 1, 1 << 2000), (0, 0), (0, 1)]:
+
+
+def test_wide_mul_lincomb_shift():
+    L = W.lib()
+    xs, ys, lin, shifts, cmps = PC.wide_mul_lincomb_shift_cases()
+    out = np.zeros(128 * len(xs), dtype=np.uint32)
+    L.simw_mul(W.P(W.pack(xs)), W.P(W.pack(ys)), W.P(out), len(xs))
+    assert W.unpack(out) == [(a * b) % W.M for a, b in zip(xs, ys)]
+    _check_wide_lincomb(L, lin)
+    _check_wide_shifts(L, shifts)
+    for a, b in cmps:
         assert L.simw_cmp(W.P(W.pack([a])), W.P(W.pack([b]))) == (a > b) - (a < b)
+
+
+def test_wide_row_edges_and_capacity():
+    """2^4096 - 1 + 1 and 2^4096 - 1 - x, hand-over words and propagate runs across the row edges of the wavefront (lanes
+    15|16, 31|32, 47|48), shifts that move even and odd limb counts up to the top of the capacity"""
+    L = W.lib()
+    _check_wide_lincomb(L, PC.wide_lincomb_edge_cases())
+    _check_wide_shifts(L, PC.wide_shift_edge_cases())
 
 
 def test_wide_remainder_sequence():
@@ -64,24 +84,8 @@ def test_wide_remainder_sequence():
     Invariants: x == sx ux y0, y == sy uy y0 (mod x0); the gcd is kept; x >= y; a full sequence ends at y == 0, a partial
     one with the first remainder at or below its stop"""
     from math import gcd
-    rng = random.Random(31)
     L = W.lib()
-    cases = []
-    for bits in (1200, 1279, 640, 130, 129, 128, 127, 65, 64, 63, 33, 20):
-        for _ in range(6):
-            x = rb(rng, bits) | (1 << (bits - 1))
-            cases.append((x, rb(rng, bits), -1))
-            cases.append((x, rb(rng, max(1, bits - rng.randrange(1, 40))), -1))
-            cases.append((x, rb(rng, bits), bits // 2))
-            cases.append((x, rb(rng, bits) | 1, bits // 2 + rng.randrange(-8, 8)))
-    for gap in (27, 53, 64, 65, 127, 128, 129, 200, 640, 1100):          # far apart: long-division steps, empty views
-        x = rb(rng, 1200) | (1 << 1199)
-        cases.append((x, rb(rng, 1200 - gap) | 1, -1))
-        cases.append((rb(rng, 1200 - gap) | 1, x, -1))
-        cases.append((x, rb(rng, 1200 - gap) | 1, 600))
-    x = rb(rng, 900) | 1
-    cases += [(x, x, -1), (x, 0, -1), (0, x, -1), (1 << 1000, 1 << 500, -1), ((1 << 1000) - 1, (1 << 64) - 1, -1), (x, 1, -1), (1, 1, -1),
-              (x * 7, x * 3, -1), ((1 << 64), (1 << 64) - 1, -1), ((1 << 128) + 1, (1 << 64) + 1, 40), (x << 130, x << 129, -1)]
+    cases = PC.wide_euclid_cases()
     out, sg = np.zeros(512, dtype=np.uint32), np.zeros(2, dtype=np.int32)
     for x0, y0, stop in cases:
         ok = L.simw_euclid(W.P(W.pack([x0])), W.P(W.pack([y0])), stop, W.P(out), sg.ctypes.data_as(C.POINTER(C.c_int)))
@@ -101,43 +105,13 @@ def test_wide_remainder_sequence():
 
 def test_wide_divisions():
     L = W.lib()
-    rng = random.Random(6)
-    cases = []
-    for _ in range(200):
-        db = rng.choice([1044, 1043, 1056, 1024, 1025, 65, 64, 33, 32, 31, 1, 700])
-        nb = rng.choice([2088, 2080, 1044, 1500, db, db + 1, db + 31, db + 32, db + 33, 10, 0])
-        d = rb(rng, db) | (1 << (db - 1))
-        n = rb(rng, nb)
-        k = rng.randrange(5)
-        if k == 0:
-            d = (1 << db) - 1
-        if k == 1:
-            n = d * rb(rng, max(nb - db, 1)) + (d - 1)           # remainders at the top of their range
-        if k == 2:
-            n = d * rb(rng, max(nb - db, 1))                     # and zero
-        if n.bit_length() <= 2200:
-            cases.append((n, d))
-    cases += [(5, 7), ((1 << 2088) - 1, (1 << 1044) - 1), (1 << 1044, 1 << 1043), (1 << 2000, (1 << 1000) + 1)]
+    cases, exact, nql = PC.wide_division_cases()
     rem = np.zeros(128 * len(cases), dtype=np.uint32)
     assert L.simw_mod(W.P(W.pack([c[0] for c in cases])), W.P(W.pack([c[1] for c in cases])), W.P(rem), len(cases)) == 1
     assert W.unpack(rem) == [n % d for n, d in cases]
     # exact division, 2-adic with 64-bit digits
-    cases = []
-    for _ in range(250):
-        db = rng.choice([1044, 1043, 1280, 65, 64, 63, 97, 160, 33, 32, 1])
-        qb = rng.choice([1, 32, 33, 63, 64, 65, 522, 544, 576, 1044, 1056, 1279])
-        d = rb(rng, db) | (1 << (db - 1))
-        k = rng.randrange(6)
-        if k == 0:
-            d = (1 << db) - 1
-        if k == 1:
-            d = (d >> rng.choice([1, 5, 31, 40])) << rng.choice([1, 5, 31, 40]) or 2          # even divisors (< 64 trailing zeros)
-        q = rb(rng, qb) | (1 << (qb - 1))
-        if rng.random() < 0.3:
-            q = (1 << qb) - 1
-        if (d * q).bit_length() <= 3900 and (d & ((1 << 64) - 1)):
-            cases.append((d * q, d, q))
-    nq = np.array([(c[2].bit_length() + 63) // 64 + (i % 3) for i, c in enumerate(cases)], dtype=np.int32)
+    cases = exact
+    nq = np.array(nql, dtype=np.int32)
     quo = np.zeros(128 * len(cases), dtype=np.uint32)
     assert L.simw_divexact(W.P(W.pack([c[0] for c in cases])), W.P(W.pack([c[1] for c in cases])), nq.ctypes.data_as(C.POINTER(C.c_int)),
                            W.P(quo), len(cases)) == 1
