@@ -1,8 +1,8 @@
 // abi.hip -- the C ABI of include/cofhe_hip.h, in this order: the context, the block cache, the launch helpers (spans, the
 // two-build launch, flag words, the table-cache lookup), the workspace plans, the launchers (one launch site per kernel and
 // route; product_tree is the pairwise tree of them all) and the host-side tensor formats.  The kernels are declared in
-// kernels.hpp and defined in cofhe_hip.hip, wide.hip, comb.hip, affine.hip and matmul_left.hip; this file holds no device code
-// of its own.
+// kernels.hpp and defined in cofhe_hip.hip, wide.hip, comb.hip, affine.hip, matmul_left.hip and conv.hip; this file holds no device code
+// of its own.  conv.hip holds the two kernels of the convolution.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -16,6 +16,7 @@
 #include "ctx.hpp"
 #include "form_io.hpp"
 #include "kernels.hpp"
+#include "conv.hpp"
 #include "plain_mm.hpp"
 
 using namespace cofhe;
@@ -39,6 +40,7 @@ size_t bits_of(const uint32_t *w, int words) {
 
 // ---- the host side of the fixed-base comb: per context, its cached tables and its two option pins ----------------------
 // A side table keyed by the context pointer, not members of cofhe_hip_ctx: ctx.hpp is one of the files the kernel code hash reads.
+// The two option pins of the convolution live here for the same reason.
 namespace {
 struct CombTable {
     uint32_t base[REC_WORDS];
@@ -52,6 +54,8 @@ struct CombState {
     uint64_t clock = 0;
     uint32_t opt_width = 0;                      // "comb_width": 0 = the launcher decides
     uint64_t opt_chunk = 0;                      // "comb_chunk": 0 = the launcher decides
+    uint32_t opt_conv_route = 0;                 // "conv_route": 0 = the launcher decides, 1 direct wherever it does not decline, 2 gather
+    uint32_t opt_conv_chunk_rows = 0;            // "conv_chunk_rows": 0 = the launcher decides, else rows per chunk of the direct route
 };
 std::mutex g_comb_mu;
 std::unordered_map<const cofhe_hip_ctx *, CombState *> g_comb;
@@ -260,6 +264,12 @@ int cofhe_hip_ctx_set_option(cofhe_hip_ctx *ctx, const char *name, int64_t value
     } else if (n == "comb_chunk") {
         if (value < 0 || value > (1ll << 32)) return fail(COFHE_HIP_EINVAL, "comb_chunk: 0 (automatic) or a positive count");
         comb_state(ctx).opt_chunk = (uint64_t)value;
+    } else if (n == "conv_route") {
+        if (value < 0 || value > 2) return fail(COFHE_HIP_EINVAL, "conv_route: 0 (automatic), 1 (direct) or 2 (gather)");
+        comb_state(ctx).opt_conv_route = (uint32_t)value;
+    } else if (n == "conv_chunk_rows") {
+        if (value < 0 || value > 0xFFFFFFFFll) return fail(COFHE_HIP_EINVAL, "conv_chunk_rows: 0 (automatic) or a positive count");
+        comb_state(ctx).opt_conv_chunk_rows = (uint32_t)value;
     } else {
         return fail(COFHE_HIP_EINVAL, "unknown option: " + n);
     }
@@ -511,9 +521,10 @@ inline WsPlan plan_scal_matmul(uint32_t n, uint32_t m, uint32_t p, uint32_t exp_
 // the product-tree form of the matrix product, what lives in the workspace: tables, digits, their length, and the per-level
 // segment counts / offsets / totals of k_tree_plan (S_cap = (exp_bits + 2) p segments at most).  Entry lists, maps, the Horner
 // schedule and the two level buffers are sized by the totals read back from `info` and come from the block cache.
-inline WsPlan plan_scal_matmul_tree(uint32_t n, uint32_t m, uint32_t p, uint32_t exp_bits, uint32_t w) {
+// (nbase: the records the table is built over -- the n m 2 of the left operand, or the image of a convolution)
+inline WsPlan plan_tree_over(uint64_t nbase, uint32_t m, uint32_t p, uint32_t exp_bits, uint32_t w) {
     WsPlan q;
-    const uint64_t nbase = (uint64_t)n * m * 2, n_exps = (uint64_t)m * p;
+    const uint64_t n_exps = (uint64_t)m * p;
     const uint32_t tw = 1u << (w - 2);
     const size_t S_cap = (size_t)(exp_bits + 2) * p;
     q.add("table", tw > 1 ? (size_t)nbase * tw * REC_WORDS * 4 : 0);
@@ -523,6 +534,14 @@ inline WsPlan plan_scal_matmul_tree(uint32_t n, uint32_t m, uint32_t p, uint32_t
     q.add("offsets", (size_t)(TREE_LEVELS + 1) * (S_cap + 1) * 4);
     q.add("info", 256);
     return q;
+}
+inline WsPlan plan_scal_matmul_tree(uint32_t n, uint32_t m, uint32_t p, uint32_t exp_bits, uint32_t w) {
+    return plan_tree_over((uint64_t)n * m * 2, m, p, exp_bits, w);
+}
+// the convolution's direct route: the tree's plan for m = kh kw C, p = Co, with the table over the B H W C 2 IMAGE records --
+// every pixel once, not once per window it is in (no table at w = 2, as above: the image itself serves)
+inline WsPlan plan_conv2d(const ConvShape &s, uint32_t exp_bits, uint32_t w) {
+    return plan_tree_over((uint64_t)s.B * s.H * s.W * s.C * 2, conv_inner(s), s.Co, exp_bits, w);
 }
 inline WsPlan plan_accumulate_tree(uint32_t n, uint32_t m, uint32_t p) {
     WsPlan q;
@@ -1199,14 +1218,39 @@ int pow_table(cofhe_hip_ctx *ctx, const void *d_cts, uint64_t nbase, uint32_t tw
     return COFHE_HIP_OK;
 }
 
+// The window width of a product whose table is built over nbase records, each of which `uses` output columns read: a table
+// of 2^(w-2) odd powers per base costs that many compositions and saves ~bits (1/3 - 1/(w+1)) in each of its uses; the tables
+// stay under 1/8 of the device memory.  "wnaf_width" pins the choice.
+int wnaf_auto_width(cofhe_hip_ctx *ctx, uint64_t nbase, double uses, uint32_t exp_bits, uint32_t *width) {
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    uint32_t w = 2;
+    double best = uses * exp_bits / 3.0;                           // w = 2: plain NAF, no table
+    for (uint32_t cand = 3; cand <= 8; cand++) {
+        const uint64_t bytes = nbase * (1ull << (cand - 2)) * REC_WORDS * 4;
+        if (bytes > total_b / 8 || bytes > free_b / 2) break;
+        const double cost = (double)(1u << (cand - 2)) + uses * exp_bits / (cand + 1.0);
+        if (cost < best) {
+            best = cost;
+            w = cand;
+        }
+    }
+    if (ctx->opt_wnaf_width >= 2 && ctx->opt_wnaf_width <= 8) w = ctx->opt_wnaf_width;      // cofhe_hip_ctx_set_option
+    *width = w;
+    return COFHE_HIP_OK;
+}
+
 // The product-tree route (k_tree_*) at window width w for exponents of at most exp_bits bits.  *taken = false: declined --
 // only the digits and the plan have been computed, no output written -- and the caller runs the chains instead.
+// cv (null for the matrix product): the product is a convolution -- d_cts is the image, the table is built over ITS records,
+// and level 0 finds its leaves through conv_leaf (k_conv_level0); n = conv_rows, m = conv_inner, p = Co.  chunk_rows (a
+// convolution's "conv_chunk_rows"): that many rows per chunk, whatever fits and without the rounding.
 int matmul_tree_route(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_exp, const void *d_zero, void *d_out, uint32_t n, uint32_t m, uint32_t p,
-                      uint32_t w, uint32_t exp_bits, hipStream_t st, bool *taken) {
+                      uint32_t w, uint32_t exp_bits, hipStream_t st, bool *taken, const ConvShape *cv = nullptr, uint32_t chunk_rows = 0) {
     *taken = false;
-    const uint64_t nbase = (uint64_t)n * m * 2, n_exps = (uint64_t)m * p;
+    const uint64_t nbase = cv ? (uint64_t)cv->B * cv->H * cv->W * cv->C * 2 : (uint64_t)n * m * 2, n_exps = (uint64_t)m * p;
     const uint32_t tw = 1u << (w - 2);
-    const WsPlan tp = plan_scal_matmul_tree(n, m, p, exp_bits, w);
+    const WsPlan tp = cv ? plan_conv2d(*cv, exp_bits, w) : plan_scal_matmul_tree(n, m, p, exp_bits, w);
     if (int rc = ensure_workspace(ctx, tp.total, st)) return rc;
     uint8_t *ws = (uint8_t *)ctx->workspace;
     int8_t *digits = (int8_t *)(ws + tp.off("digits"));
@@ -1235,6 +1279,7 @@ int matmul_tree_route(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_exp, 
     const uint64_t budget = std::min<uint64_t>(free_b / 4, std::max<uint64_t>(ctx->pool_cap / 4, (uint64_t)1 << 30));
     uint64_t R = budget / (n1 * 2 * REC_WORDS * 4);
     if (R >= 16) R &= ~(uint64_t)15;                           // 2 R a multiple of 32: the groups of a workgroup share their element
+    if (chunk_rows) R = chunk_rows;
     if (R < 1) R = 1;
     if (R > n) R = n;
     // Long exponents make long trees (N_1 ~ p bits m / 2 (w + 1) elements per row): when fewer than 16 rows fit a chunk the
@@ -1243,7 +1288,7 @@ int matmul_tree_route(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_exp, 
     // The Horner chains address the top level's N_T elements through the op word's 21-bit base index (off_T[s] < N_T):
     // beyond 2^21 elements the tree is not taken, "matmul_tree" = 1 included, and the chains run instead
     const bool tree_fits = info[T] <= MM_INDEX_LIMIT;
-    const bool tree_pays = tree_fits && (R >= 16 || R == n || ctx->opt_matmul_tree == 1);
+    const bool tree_pays = tree_fits && (R >= 16 || R == n || ctx->opt_matmul_tree == 1 || chunk_rows);
     if (!tree_pays) return COFHE_HIP_OK;
     const uint32_t *table;
     if (int rc = pow_table(ctx, d_cts, nbase, tw, ws + tp.off("table"), st, &table)) return rc;
@@ -1273,6 +1318,14 @@ int matmul_tree_route(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_exp, 
             unsigned lb;
             if (items == 0) break;
             if (int rc = compose_blocks(items, &lb)) return rc;
+            if (cv && l == 0) {                                // the leaves of rows r0 .. r0 + rows - 1, from the image's table
+                ProfScope ps(ctx, "k_conv_level0", st);
+                hipLaunchKernelGGL(k_conv_level0, dim3(lb), dim3(WG_BLOCK), 0, st, *cv, table, (const uint32_t *)ctx->d_one, (const uint32_t *)b_ent.p,
+                                   (const uint32_t *)d_off, (const uint32_t *)(d_off + (S_cap + 1)), maps, info[1], r0, rows, tw,
+                                   (uint32_t *)b_lvl[0].p, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+                map_base += info[1];
+                continue;
+            }
             const uint32_t *src = l == 0 ? table + (uint64_t)r0 * m * 2 * tw * REC_WORDS : (const uint32_t *)b_lvl[(l - 1) & 1].p;
             ProfScope ps(ctx, "k_tree_level", st);
             hipLaunchKernelGGL(k_tree_level, dim3(lb), dim3(WG_BLOCK), 0, st, src, l == 0 ? 1u : 0u, (const uint32_t *)b_ent.p,
@@ -1352,27 +1405,13 @@ int cofhe_hip_scal_matmul_records(cofhe_hip_ctx *ctx, const void *d_cts, const v
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     WsUse use(ctx, st);
-    // window width: a table of 2^(w-2) odd powers per base costs that many compositions and is used by
-    // the p columns of its row, saving ~bits*(1/3 - 1/(w+1)) compositions in each; keep the tables under
-    // 1/8 of the device memory
+    // window width (wnaf_auto_width): a base's table is used by the p columns of its row
     const uint64_t nbase = (uint64_t)n * m * 2;
     uint32_t w = 2, exp_bits = 0;                              // exp_bits: longest exponent of the call
     if (m > 0) {
         // per base: 2^(w-2) compositions for the table, then ~bits/(w+1) per column -- needs the exponent length
         if (int rc = max_exp_bits(ctx, d_exp, (uint64_t)m * p, st, &exp_bits)) return rc;
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        double best = (double)p * exp_bits / 3.0;                      // w = 2: plain NAF, no table
-        for (uint32_t cand = 3; cand <= 8; cand++) {
-            const uint64_t bytes = nbase * (1ull << (cand - 2)) * REC_WORDS * 4;
-            if (bytes > total_b / 8 || bytes > free_b / 2) break;
-            const double cost = (double)(1u << (cand - 2)) + (double)p * exp_bits / (cand + 1.0);
-            if (cost < best) {
-                best = cost;
-                w = cand;
-            }
-        }
-        if (ctx->opt_wnaf_width >= 2 && ctx->opt_wnaf_width <= 8) w = ctx->opt_wnaf_width;      // cofhe_hip_ctx_set_option
+        if (int rc = wnaf_auto_width(ctx, nbase, (double)p, exp_bits, &w)) return rc;
     }
     if (m >= (1u << 21)) return fail(COFHE_HIP_EINVAL, "inner dimension beyond 2^21");
     // The product-tree form (matmul_tree_route) when there is something to pair up and enough outputs for the Horner
@@ -1431,6 +1470,75 @@ int cofhe_hip_matmul_plain_ct_records(cofhe_hip_ctx *ctx, const void *d_s, const
     if (int rc = transpose_launch(d_s, s_t.p, n, m, EXP_REC_WORDS, st)) return rc;
     if (int rc = cofhe_hip_scal_matmul_records(ctx, cts_t.p, s_t.p, d_zero, out_t.p, p, m, n, stream)) return rc;
     return transpose_launch(out_t.p, d_out, p, n, 2 * REC_WORDS, st);
+}
+
+namespace {
+ConvShape conv_shape_of(const cofhe_hip_conv2d_shape &a) {
+    return ConvShape{a.B, a.H, a.W, a.C, a.kh, a.kw, a.Co, a.sh, a.sw, a.ph, a.pw, 0u, 0u};
+}
+// the one launch site of k_gather_patches: the n x m patch matrix of the image (im2col), the principal form in the padding;
+// 16-byte pieces when both pointers allow them (a caller's pointer is only known to be 4-byte aligned)
+int gather_patches_launch(cofhe_hip_ctx *ctx, const ConvShape &s, const void *d_cts, void *d_patches, hipStream_t st) {
+    const uint32_t n = conv_rows(s), m = conv_inner(s);
+    const bool vec16 = (((uintptr_t)d_cts | (uintptr_t)d_patches) & 15) == 0;
+    const uint64_t total = (uint64_t)n * m * 2 * (vec16 ? REC_WORDS / 4 : REC_WORDS);
+    if (total == 0) return COFHE_HIP_OK;
+    const unsigned blocks = (unsigned)std::min<uint64_t>((total + 255) / 256, 64u * NUM_CUS);       // grid-stride beyond that
+    ProfScope ps(ctx, "k_gather_patches", st);
+    hipLaunchKernelGGL(k_gather_patches, dim3(blocks), dim3(256), 0, st, s, (const uint32_t *)d_cts, (const uint32_t *)ctx->d_one,
+                       (uint32_t *)d_patches, n, m, vec16 ? 1u : 0u);
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+}  // namespace
+
+int cofhe_hip_conv2d_out_shape(const cofhe_hip_conv2d_shape *shape, uint32_t *Ho, uint32_t *Wo) {
+    if (!shape || !Ho || !Wo) return fail(COFHE_HIP_EINVAL, "null argument");
+    ConvShape s = conv_shape_of(*shape);
+    if (const char *why = conv_shape_check(s)) return fail(COFHE_HIP_EINVAL, why);
+    *Ho = s.Ho;
+    *Wo = s.Wo;
+    return COFHE_HIP_OK;
+}
+
+// Two routes.  Direct: the product-tree route of the matrix product with the table built once over the image and level 0
+// reading its leaves through conv_leaf (plan "conv2d").  Gather: the patch matrix into a block of the block cache, then
+// cofhe_hip_scal_matmul_records unchanged (its own plans) -- when the direct route declines or is pinned off.
+int cofhe_hip_conv2d_plain_ct_records(cofhe_hip_ctx *ctx, const void *d_w, const void *d_cts, const void *d_zero, void *d_out,
+                                      const cofhe_hip_conv2d_shape *shape, void *stream) {
+    if (!shape) return fail(COFHE_HIP_EINVAL, "null argument");
+    ConvShape s = conv_shape_of(*shape);
+    if (const char *why = conv_shape_check(s)) return fail(COFHE_HIP_EINVAL, why);
+    const uint32_t n = conv_rows(s), m = conv_inner(s), p = s.Co;
+    if ((uint64_t)n * p == 0) return COFHE_HIP_OK;
+    const size_t ct_bytes = (size_t)2 * REC_WORDS * 4;
+    const size_t out_bytes = (size_t)n * p * ct_bytes, cts_bytes = (size_t)s.B * s.H * s.W * s.C * ct_bytes, w_bytes = (size_t)m * p * EXP_REC_WORDS * 4;
+    if (overlaps(d_out, out_bytes, d_cts, cts_bytes) || overlaps(d_out, out_bytes, d_w, w_bytes) || overlaps(d_out, out_bytes, d_zero, ct_bytes))
+        return fail(COFHE_HIP_EINVAL, "conv2d: the output overlaps an input");
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const CombState &opt = comb_state(ctx);
+    // automatic: the direct route where the matrix product itself takes its tree (something to pair up, enough outputs for the
+    // Horner chains to fill the GPU); small convolutions keep the chains, behind the gather
+    const bool direct = opt.opt_conv_route == 1 || (opt.opt_conv_route == 0 && m >= 8 && (uint64_t)n * p * 2 >= 4096);
+    if (direct && m > 0) {
+        WsUse use(ctx, st);
+        // window width: the table of a pixel is used by the p columns of every window the pixel is in
+        const uint64_t reuse = (uint64_t)((s.kh + s.sh - 1) / s.sh) * ((s.kw + s.sw - 1) / s.sw);
+        uint32_t w = 2, exp_bits = 0;
+        if (int rc = max_exp_bits(ctx, d_w, (uint64_t)m * p, st, &exp_bits)) return rc;
+        if (int rc = wnaf_auto_width(ctx, (uint64_t)s.B * s.H * s.W * s.C * 2, (double)reuse * p, exp_bits, &w)) return rc;
+        bool taken = false;
+        if (int rc = matmul_tree_route(ctx, d_cts, d_w, d_zero, d_out, n, m, p, w, exp_bits, st, &taken, &s, opt.opt_conv_chunk_rows)) return rc;
+        if (taken) return COFHE_HIP_OK;
+    }
+    DevBuf patches;
+    patches.stream = stream;
+    const size_t patch_bytes = (size_t)n * m * ct_bytes;
+    if (int rc = patches.get(ctx, patch_bytes ? patch_bytes : 4)) return rc;
+    if (int rc = gather_patches_launch(ctx, s, d_cts, patches.p, st)) return rc;
+    return cofhe_hip_scal_matmul_records(ctx, patches.p, d_w, d_zero, d_out, n, m, p, stream);
 }
 
 int cofhe_hip_matmul_plain_plain_records(cofhe_hip_ctx *ctx, const void *d_a, const void *d_b, void *d_out, uint32_t n, uint32_t m, uint32_t p,
@@ -1612,6 +1720,15 @@ int cofhe_hip_workspace_plan(const char *op, const uint64_t *args, uint32_t n_ar
     } else if (o == "scal_matmul_tree" && need(5)) {
         if (args[4] < 2 || args[4] > 8) return fail(COFHE_HIP_EINVAL, "scal_matmul_tree plan: w in 2..8");
         p = plan_scal_matmul_tree((uint32_t)args[0], (uint32_t)args[1], (uint32_t)args[2], (uint32_t)args[3], (uint32_t)args[4]);
+    } else if (o == "conv2d" && need(13)) {
+        // B, H, W, C, kh, kw, Co, sh, sw, ph, pw, exp_bits, w: the direct route of cofhe_hip_conv2d_plain_ct_records
+        for (int i = 0; i < 13; i++)
+            if (args[i] > 0xFFFFFFFFull) return fail(COFHE_HIP_EINVAL, "conv2d plan: argument out of range");
+        if (args[12] < 2 || args[12] > 8) return fail(COFHE_HIP_EINVAL, "conv2d plan: w in 2..8");
+        ConvShape cs{(uint32_t)args[0], (uint32_t)args[1], (uint32_t)args[2], (uint32_t)args[3], (uint32_t)args[4], (uint32_t)args[5], (uint32_t)args[6],
+                     (uint32_t)args[7], (uint32_t)args[8], (uint32_t)args[9], (uint32_t)args[10], 0u, 0u};
+        if (const char *why = conv_shape_check(cs)) return fail(COFHE_HIP_EINVAL, why);
+        p = plan_conv2d(cs, (uint32_t)args[11], (uint32_t)args[12]);
     } else if (o == "accumulate_tree" && need(3)) {
         p = plan_accumulate_tree((uint32_t)args[0], (uint32_t)args[1], (uint32_t)args[2]);
     } else if (o == "encrypt_chunk" && need(2)) {
@@ -1964,6 +2081,32 @@ int cofhe_hip_matmul_plain_ct_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *s
     if (int rc = cofhe_hip_matmul_plain_ct_records(ctx, de.p, dc.p, dz.p, dout.p, n, m, p, nullptr)) return rc;
     const uint32_t so[2] = {n, p};
     return finish(ctx, dout, nout, 2, so, out, outlen);
+}
+
+int cofhe_hip_conv2d_plain_ct_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *w, size_t lw, const uint8_t *cts, size_t lc, const uint8_t *zero,
+                                            size_t lz, uint32_t sh, uint32_t sw, uint32_t ph, uint32_t pw, uint8_t **out, size_t *outlen) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    uint32_t ndw, ndc, swp[8], sc[8];
+    uint64_t ne, nr;
+    HIPCHK(hipSetDevice(ctx->device));
+    DevBuf de, dc, dz, dout;
+    if (int rc = load_tensor(ctx, w, lw, 0, de, &ndw, swp, &ne)) return rc;
+    if (int rc = load_tensor(ctx, cts, lc, 2, dc, &ndc, sc, &nr)) return rc;
+    if (ndw != 4 || ndc != 4) return fail(COFHE_HIP_ESHAPE, "conv2d takes a 4-D filter tensor [kh, kw, C, Co] and a 4-D image tensor [B, H, W, C]");
+    if (swp[2] != sc[3]) return fail(COFHE_HIP_ESHAPE, "conv2d: the channels of the filters and of the image differ");
+    const cofhe_hip_conv2d_shape shp{sc[0], sc[1], sc[2], sc[3], swp[0], swp[1], swp[3], sh, sw, ph, pw};
+    uint32_t Ho = 0, Wo = 0;
+    if (int rc = cofhe_hip_conv2d_out_shape(&shp, &Ho, &Wo)) return rc;
+    uint32_t ndz, sz[8];
+    uint64_t nz;
+    if (!zero) return fail(COFHE_HIP_EINVAL, "conv2d needs the encryption of zero it starts from");
+    if (int rc = load_tensor(ctx, zero, lz, 2, dz, &ndz, sz, &nz)) return rc;
+    if (nz != 2) return fail(COFHE_HIP_EINVAL, "zero must be a one-element ciphertext tensor");
+    const uint32_t so[4] = {shp.B, Ho, Wo, shp.Co};
+    const uint64_t nout = (uint64_t)so[0] * Ho * Wo * so[3] * 2;
+    if (int rc = dout.get(ctx, nout ? nout * REC_WORDS * 4 : 4)) return rc;
+    if (int rc = cofhe_hip_conv2d_plain_ct_records(ctx, de.p, dc.p, dz.p, dout.p, &shp, nullptr)) return rc;
+    return finish(ctx, dout, nout, 4, so, out, outlen);
 }
 
 }  // extern "C"

@@ -3,12 +3,13 @@
 // (the latency kernels); wire.hip launches its own kernels.  A declaration that matches no definition is an
 // undefined symbol when the library is loaded (tests/test_cabi.py).  comb.hip holds the two kernels of the fixed-base comb,
 // affine.hip the ciphertext difference and the record inverse, matmul_left.hip the record transpose and the plaintext
-// matrix product.
+// matrix product, conv.hip the convolution's level 0 and its patch gather.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "comb.hpp"
+#include "conv.hpp"
 
 namespace cofhe_k {
 
@@ -131,4 +132,13 @@ __global__ void k_transpose_records(const uint32_t *__restrict__ in, uint32_t *_
                                     uint32_t vec16);
 __global__ void k_plain_matmul(const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, uint32_t *__restrict__ out, uint32_t n, uint32_t m,
                                uint32_t p, uint32_t kbits);
+
+// the convolution (conv.hip, conv.hpp): level 0 -> 1 of the product tree with its leaves read from the table of the image, and
+// the patch matrix n x m written out (vec16: 16-byte pieces)
+__global__ void k_conv_level0(cofhe::ConvShape s, const uint32_t *__restrict__ table, const uint32_t *__restrict__ one_rec,
+                              const uint32_t *__restrict__ ent0, const uint32_t *__restrict__ off_cur, const uint32_t *__restrict__ off_next,
+                              const uint32_t *__restrict__ map_next, uint32_t n_next, uint32_t row0, uint32_t rows, uint32_t tw,
+                              uint32_t *__restrict__ dst, const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status);
+__global__ void k_gather_patches(cofhe::ConvShape s, const uint32_t *__restrict__ cts, const uint32_t *__restrict__ one_rec,
+                                 uint32_t *__restrict__ out, uint32_t n, uint32_t m, uint32_t vec16);
 }  // namespace cofhe_k

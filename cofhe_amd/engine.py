@@ -131,6 +131,16 @@ class Engine:
                                                             C.byref(out), C.byref(n)))
         return self._take(out, n)
 
+    def conv2d_plain_ct_tensors(self, w: bytes, cts: bytes, zero: bytes, stride=(1, 1), pad=(0, 0)) -> bytes:
+        """w (plaintext tensor [kh, kw, C, Co]) over cts (ciphertext tensor [B, H, W, C]), channels last, from zero (1-element
+        ciphertext tensor); stride and zero padding as (rows, columns).  Returns the ciphertext tensor [B, Ho, Wo, Co]"""
+        out = C.POINTER(C.c_uint8)()
+        n = C.c_size_t()
+        _chk(self.L.cofhe_hip_conv2d_plain_ct_tensors_bytes(self.ctx, C.c_char_p(w), C.c_size_t(len(w)), C.c_char_p(cts), C.c_size_t(len(cts)),
+                                                            C.c_char_p(zero), C.c_size_t(len(zero)), C.c_uint32(stride[0]), C.c_uint32(stride[1]),
+                                                            C.c_uint32(pad[0]), C.c_uint32(pad[1]), C.byref(out), C.byref(n)))
+        return self._take(out, n)
+
     # ---- format conversion (host) ----------------------------------------------------------
     def bytes_to_records(self, t: bytes):
         import numpy as np
@@ -269,6 +279,19 @@ class Engine:
         _chk(self.L.cofhe_hip_matmul_plain_ct_records(self.ctx, C.c_void_p(d_s), C.c_void_p(d_cts), C.c_void_p(d_zero),
                                                       C.c_void_p(d_out), C.c_uint32(n), C.c_uint32(m), C.c_uint32(p),
                                                       C.c_void_p(stream)))
+
+    def conv2d_plain_ct_records(self, d_w, d_cts, d_zero, d_out, image, filters, stride=(1, 1), pad=(0, 0), stream=0):
+        """out [B, Ho, Wo, Co] = the convolution of the ciphertext image d_cts [B, H, W, C] = `image` with the plaintext filters
+        d_w [kh, kw, C, Co] = `filters` (exponent records), channels last, from the ciphertext d_zero; d_out must not overlap an
+        input.  Returns (Ho, Wo)"""
+        shp = _conv_shape(image, filters, stride, pad)
+        _chk(self.L.cofhe_hip_conv2d_plain_ct_records(self.ctx, C.c_void_p(d_w), C.c_void_p(d_cts), C.c_void_p(d_zero), C.c_void_p(d_out),
+                                                      C.byref(shp), C.c_void_p(stream)))
+        return conv2d_out_shape(image, filters, stride, pad)
+
+    def conv2d_out_shape(self, image, filters, stride=(1, 1), pad=(0, 0)):
+        """(Ho, Wo) of the convolution, or CofheHipError for a geometry it refuses (host only: the module's conv2d_out_shape)"""
+        return conv2d_out_shape(image, filters, stride, pad)
 
     def matmul_plain_plain_records(self, d_a, d_b, d_out, n, m, p, kbits, stream=0):
         """out = a (n x m) . b (m x p) mod 2^kbits on exponent records, outputs in [0, 2^k) with sign word 0; one launch,
@@ -479,6 +502,28 @@ def workspace_plan(op: str, *args):
     a = (C.c_uint64 * max(1, len(args)))(*[int(x) for x in args])
     _chk(L.cofhe_hip_workspace_plan(op.encode(), a, C.c_uint32(len(args)), regs, C.c_uint32(8), C.byref(n), C.byref(total)))
     return [(regs[i].name.decode(), int(regs[i].offset), int(regs[i].bytes)) for i in range(n.value)], int(total.value)
+
+
+class _ConvShape(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("B", "H", "W", "C", "kh", "kw", "Co", "sh", "sw", "ph", "pw")]
+
+
+def _conv_shape(image, filters, stride, pad):
+    B, H, W, Cin = image
+    kh, kw, Cf, Co = filters
+    if Cf != Cin:
+        raise CofheHipError(-2, "conv2d: the channels of the filters and of the image differ")
+    return _ConvShape(B, H, W, Cin, kh, kw, Co, stride[0], stride[1], pad[0], pad[1])
+
+
+def conv2d_out_shape(image, filters, stride=(1, 1), pad=(0, 0)):
+    """cofhe_hip_conv2d_out_shape (host only): (Ho, Wo) of image [B, H, W, C] under filters [kh, kw, C, Co]; raises
+    CofheHipError (COFHE_HIP_EINVAL) for a geometry the convolution refuses"""
+    L = load_library()
+    shp = _conv_shape(image, filters, stride, pad)
+    ho, wo = C.c_uint32(), C.c_uint32()
+    _chk(L.cofhe_hip_conv2d_out_shape(C.byref(shp), C.byref(ho), C.byref(wo)))
+    return int(ho.value), int(wo.value)
 
 
 COMB_POWERS, COMB_ENCRYPT, COMB_RERANDOMIZE = 0, 1, 2

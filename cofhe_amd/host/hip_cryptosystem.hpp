@@ -15,6 +15,7 @@
 #pragma once
 #include <gmp.h>
 
+#include <array>
 #include <atomic>
 #include <cstdint>
 #include <memory>
@@ -740,6 +741,44 @@ class HIPCryptoSystem {
         check(cofhe_hip_upload(ctx_, dex, ex.data(), ex.size() * 4, nullptr));
         DeviceTensor out = alloc({n, p}, n * p);
         check(cofhe_hip_matmul_plain_ct_records(ctx_, dex, cts.ptr_, zero.ptr_, out.ptr_, (uint32_t)n, (uint32_t)m, (uint32_t)p, nullptr));
+        return out;
+    }
+    // 2-D convolution, channels last: plaintext filters w [kh, kw, C, Co] over the ciphertext image cts [B, H, W, C] with
+    // strides and zero padding as {rows, columns}; res[b,oy,ox,co] = zero o prod cts[b, oy sh + dy - ph, ox sw + dx - pw, ci]^w[dy,dx,ci,co],
+    // a tensor [B, Ho, Wo, Co] -- the next layer's input as it is.  The reference has no convolution; the engine builds no patch
+    // matrix (cofhe_hip_conv2d_plain_ct_records).  A bias is add_plaintext_tensor on the result.  Starts from a fresh
+    // encryption of zero like the 2-D scal_ciphertext_tensors; pass `zero` to make the call reproducible.
+    Tensor<CipherText *> conv2d_plaintext_ciphertext_tensors(const PublicKey &pk, const Tensor<PlainText *> &w, const Tensor<CipherText *> &cts,
+                                                             const std::array<size_t, 2> &stride = {1, 1}, const std::array<size_t, 2> &pad = {0, 0},
+                                                             const CipherText *zero = nullptr) const {
+        if (w.ndim() != 4 || cts.ndim() != 4) throw std::invalid_argument("conv2d_plaintext_ciphertext_tensors: both operands must be 4D");
+        CipherText z = zero ? *zero : encrypt(pk, make_plaintext(0));
+        Tensor<CipherText *> zt(1, &z);
+        DeviceTensor out = conv2d_plaintext_ciphertext_tensors(w, upload(cts), upload(zt), stride, pad);
+        rerandomize_result(pk, out);           // one fresh r per output, as scal_ciphertext_tensors
+        return download(std::move(out));
+    }
+    // the same on resident operands; deterministic (no re-randomisation), like the other DeviceTensor members
+    DeviceTensor conv2d_plaintext_ciphertext_tensors(const Tensor<PlainText *> &w, const DeviceTensor &cts, const DeviceTensor &zero,
+                                                     const std::array<size_t, 2> &stride = {1, 1}, const std::array<size_t, 2> &pad = {0, 0}) const {
+        if (w.ndim() != 4 || cts.shape_.size() != 4) throw std::invalid_argument("conv2d_plaintext_ciphertext_tensors: both operands must be 4D");
+        if (w.shape()[2] != cts.shape_[3]) throw std::invalid_argument("conv2d_plaintext_ciphertext_tensors: the channels of the filters and of the image differ");
+        if (zero.n_ != 1) throw std::invalid_argument("conv2d_plaintext_ciphertext_tensors: zero must be one ciphertext");
+        const size_t dims[11] = {cts.shape_[0], cts.shape_[1], cts.shape_[2], cts.shape_[3], w.shape()[0], w.shape()[1], w.shape()[3],
+                                 stride[0], stride[1], pad[0], pad[1]};
+        for (size_t v : dims)
+            if (v > 0xFFFFFFFFull) throw std::invalid_argument("conv2d_plaintext_ciphertext_tensors: extent out of range");
+        const cofhe_hip_conv2d_shape shp{(uint32_t)dims[0], (uint32_t)dims[1], (uint32_t)dims[2], (uint32_t)dims[3], (uint32_t)dims[4], (uint32_t)dims[5],
+                                         (uint32_t)dims[6], (uint32_t)dims[7], (uint32_t)dims[8], (uint32_t)dims[9], (uint32_t)dims[10]};
+        uint32_t Ho = 0, Wo = 0;
+        check(cofhe_hip_conv2d_out_shape(&shp, &Ho, &Wo));
+        std::vector<uint32_t> ex = pack_exponents(w);
+        void *dex = nullptr;
+        check(cofhe_hip_malloc(ctx_, ex.size() * 4 + 4, &dex));
+        Guard g1{ctx_, dex};
+        check(cofhe_hip_upload(ctx_, dex, ex.data(), ex.size() * 4, nullptr));
+        DeviceTensor out = alloc({dims[0], Ho, Wo, dims[6]}, dims[0] * Ho * Wo * dims[6]);
+        check(cofhe_hip_conv2d_plain_ct_records(ctx_, dex, cts.ptr_, zero.ptr_, out.ptr_, &shp, nullptr));
         return out;
     }
     // a (n x m) . b (m x p) mod 2^k on the device (k_plain_matmul): the E D term of a matrix Beaver triplet and the C = A B of

@@ -668,6 +668,53 @@ static void bench_plain_ct_matmul(size_t n, size_t m, size_t p) {
     if (!ok) throw std::runtime_error("plaintext-left product mismatch");
 }
 
+// plaintext filters kh x kw x C x Co over an encrypted image B x H x W x C (channels last): encrypt, convolve, decrypt and
+// compare with the convolution of the plaintexts
+static void bench_conv2d(size_t B, size_t H, size_t W, size_t C, size_t kh, size_t kw, size_t Co, size_t sh, size_t sw, size_t ph, size_t pw) {
+    auto cs = make_cryptosystem(128, 128, Device::GPU);
+    using CS = decltype(cs);
+    auto sk = cs.keygen();
+    auto pk = cs.keygen(sk);
+    auto xval = [](size_t i) { return (float)(i % 11) - 4.0f; };
+    auto wval = [](size_t i) { return (float)(i % 7) - 3.0f; };               // weights of both signs, zeros among them
+    Tensor<CS::PlainText *> x({B, H, W, C}, nullptr), w({kh, kw, C, Co}, nullptr);
+    for (size_t i = 0; i < x.num_elements(); i++) x[i] = new CS::PlainText(cs.make_plaintext(xval(i)));
+    for (size_t i = 0; i < w.num_elements(); i++) w[i] = new CS::PlainText(cs.make_plaintext(wval(i)));
+    auto cx = cs.encrypt_tensor(pk, x);
+    Benchmark b("conv2d (plaintext filters over a ciphertext image)");
+    bool ok = true;
+    std::vector<size_t> oshape;
+    b.run([&]() {
+        auto res = cs.conv2d_plaintext_ciphertext_tensors(pk, w, cx, {sh, sw}, {ph, pw});
+        oshape = res.shape();
+        auto dec = cs.decrypt_tensor(sk, res);
+        const size_t Ho = oshape[1], Wo = oshape[2];
+        for (size_t bb = 0; bb < B; bb++)
+            for (size_t oy = 0; oy < Ho; oy++)
+                for (size_t ox = 0; ox < Wo; ox++)
+                    for (size_t co = 0; co < Co; co++) {
+                        float want = 0;
+                        for (size_t dy = 0; dy < kh; dy++)
+                            for (size_t dx = 0; dx < kw; dx++) {
+                                const size_t y = oy * sh + dy, xx = ox * sw + dx;
+                                if (y < ph || y - ph >= H || xx < pw || xx - pw >= W) continue;
+                                for (size_t ci = 0; ci < C; ci++)
+                                    want += xval(((bb * H + (y - ph)) * W + (xx - pw)) * C + ci) * wval(((dy * kw + dx) * C + ci) * Co + co);
+                            }
+                        if (cs.get_float_from_plaintext(*dec[((bb * Ho + oy) * Wo + ox) * Co + co]) != want) ok = false;
+                    }
+        free_all(res);
+        free_all(dec);
+    }, 1);
+    b.print_summary();
+    free_all(x); free_all(w); free_all(cx);
+    if (oshape.size() != 4 || oshape[0] != B || oshape[3] != Co) ok = false;
+    std::cout << "  decrypts to the convolution: " << (ok ? "yes" : "NO") << std::endl;
+    std::cout << "image: " << B << "x" << H << "x" << W << "x" << C << " filters: " << kh << "x" << kw << "x" << C << "x" << Co << " stride: " << sh << "," << sw
+              << " pad: " << ph << "," << pw << " out: " << (oshape.size() == 4 ? oshape[1] : 0) << "x" << (oshape.size() == 4 ? oshape[2] : 0) << std::endl;
+    if (!ok) throw std::runtime_error("convolution mismatch");
+}
+
 // the ciphertext x ciphertext matrix product twice on the same inputs: the reference's expansion into n m p element
 // products (2 n m p opened values) and one matrix triplet (LocalCipherTextMultiplier::set_matrix_triplets: n m + m p)
 static void bench_ciphertext_matmul_matrix(size_t n, size_t m, size_t p, size_t t, size_t parties) {
@@ -903,7 +950,7 @@ static void plaintexts_mode(const char *in, const char *out) {
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        std::cerr << "Usage: " << argv[0] << " <encrypt_decrypt|ciphertext_matadd|scal_matmul|threshold|ciphertext_matmul|fresh_randomness|affine|beaver_direct|plain_ct_matmul|ciphertext_matmul_matrix> [sizes]" << std::endl;
+        std::cerr << "Usage: " << argv[0] << " <encrypt_decrypt|ciphertext_matadd|scal_matmul|threshold|ciphertext_matmul|fresh_randomness|affine|beaver_direct|plain_ct_matmul|ciphertext_matmul_matrix|conv2d> [sizes]" << std::endl;
         return 1;
     }
     std::string mode = argv[1];
@@ -926,6 +973,11 @@ int main(int argc, char **argv) {
             bench_ciphertext_matmul(n, m, p, t, parties);
         } else if (mode == "plain_ct_matmul") {
             bench_plain_ct_matmul(argc > 2 ? std::stoul(argv[2]) : 3, argc > 3 ? std::stoul(argv[3]) : 5, argc > 4 ? std::stoul(argv[4]) : 4);
+        } else if (mode == "conv2d") {
+            // B H W C kh kw Co [sh sw ph pw]; by default stride 1 and "same" padding
+            auto arg = [&](int i, size_t dflt) { return argc > i ? std::stoul(argv[i]) : dflt; };
+            const size_t kh = arg(6, 3), kw = arg(7, 3);
+            bench_conv2d(arg(2, 1), arg(3, 6), arg(4, 6), arg(5, 2), kh, kw, arg(8, 2), arg(9, 1), arg(10, 1), arg(11, kh / 2), arg(12, kw / 2));
         } else if (mode == "ciphertext_matmul_matrix") {
             size_t n = argc > 2 ? std::stoul(argv[2]) : 4, m = argc > 3 ? std::stoul(argv[3]) : 4,
                    p = argc > 4 ? std::stoul(argv[4]) : 4, t = argc > 5 ? std::stoul(argv[5]) : 0,

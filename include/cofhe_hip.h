@@ -15,6 +15,8 @@
  *                                    reference's 2-D branch is ciphertext-left only
  *   cofhe_hip_matmul_plain_plain_... nothing: a plaintext matrix product mod 2^k, the E D term of a matrix Beaver
  *                                    triplet (include/smpc/ciphertext_multiplications.hpp:51-111 expands into elements)
+ *   cofhe_hip_conv2d_plain_ct_...    nothing: the reference has no convolution; with it, plaintext filters over an encrypted image
+ *                                    are a patch matrix built by the caller and the 2-D branch above
  *   cofhe_hip_decrypt_records        decrypt_tensor's per-element work, cpu_cryptosystem_tensor_ops.inl:21-33
  *   cofhe_hip_part_decrypt_records,  part_decrypt_tensor / combine_part_decryption_results_tensor,
  *   cofhe_hip_combine_part_...       cpu_cryptosystem_tensor_ops.inl:35-73 (cpu_cryptosystem_distributed.inl:231-285)
@@ -89,6 +91,11 @@ int cofhe_hip_trim(cofhe_hip_ctx *ctx, size_t keep_bytes);
  *   "matmul_segments"  >= 1: pieces the inner dimension is cut into when the product has few outputs
  *   "comb_width"       2..10: window width of the fixed-base comb (cofhe_hip_pow_fixed_base_many_records and kin)
  *   "comb_chunk"       >= 1: items per pass of the comb (capped where the 4 GiB workspace bound needs it)
+ *   "conv_route"       cofhe_hip_conv2d_plain_ct_records: 0 the launcher decides, 1 the direct route wherever it does not
+ *                      decline, 2 the gather route
+ *   "conv_chunk_rows"  >= 1: output positions per chunk of the convolution's direct route, taken as given (no rounding to a
+ *                      multiple of 16, no decline for being small): how a test reaches several chunks and workgroups that
+ *                      mix tree elements
  *   "profile_kernels"  != 0: cofhe_hip_scal_matmul_records brackets each of its kernels with HIP events on the launch
  *                      stream; cofhe_hip_profile_read(ctx, "k_tree_level" | "k_scal_matmul_wnaf" | "k_pow_table" | "k_wnaf_digits", ...)
  *                      waits for them and returns the summed duration and the launch count (clear != 0 drops all spans).
@@ -96,8 +103,9 @@ int cofhe_hip_trim(cofhe_hip_ctx *ctx, size_t keep_bytes);
  *                      and the kernels of the other entry points one named after the build launched: "k_compose_wg3" |
  *                      "k_compose_wg", "k_add_ct3" | "k_add_ct", "k_pow_shared_pair" | "k_pow_shared_wide" |
  *                      "k_pow_shared_solo" | "k_pow_shared" (ladders; "k_spread_records" when a
- *                      tensor's shared c1 ran one ladder), "k_decrypt3" | "k_decrypt" -- what a test reads to
- *                      see which route a call took
+ *                      tensor's shared c1 ran one ladder), "k_decrypt3" | "k_decrypt", "k_conv_level0" (one per chunk of the
+ *                      convolution's direct route; "k_tree_level" counts the levels above) | "k_gather_patches" (its
+ *                      gather route) -- what a test reads to see which route a call took
  * The results do not depend on them; tests pin them to drive every width through the parity checker. */
 int cofhe_hip_ctx_set_option(cofhe_hip_ctx *ctx, const char *name, int64_t value);
 int cofhe_hip_profile_read(cofhe_hip_ctx *ctx, const char *kernel, float *total_ms, uint32_t *launches, int clear);
@@ -164,6 +172,33 @@ int cofhe_hip_scal_matmul_records(cofhe_hip_ctx *ctx, const void *d_cts, const v
  * nothing written.  n p == 0: nothing to do; m == 0: zero everywhere. */
 int cofhe_hip_matmul_plain_ct_records(cofhe_hip_ctx *ctx, const void *d_s, const void *d_cts, const void *d_zero, void *d_out,
                                       uint32_t n, uint32_t m, uint32_t p, void *stream);
+/* 2-D convolution of a ciphertext image with plaintext filters, channels last (cofhe_amd/csrc/conv.hpp):
+ *   image d_cts [B, H, W, C] ciphertexts, filters d_w [kh, kw, C, Co] exponent records, output d_out [B, Ho, Wo, Co],
+ *   out[b,oy,ox,co] = zero o prod_{dy,dx,ci} cts[b, oy sh + dy - ph, ox sw + dx - pw, ci] ^ w[dy,dx,ci,co],
+ * factors outside the image left out (zero padding), Ho = (H + 2 ph - kh) / sh + 1 and Wo likewise, rounded down.  Read as
+ * matrices the filters are the m x p exponent matrix of cofhe_hip_scal_matmul_records (m = kh kw C, p = Co) and the output its
+ * n x p result (n = B Ho Wo), so a layer's output is the next layer's input and nothing is rearranged.  The reference has no
+ * convolution.  Two routes ("conv_route"): the direct one builds the table of odd powers ONCE over the image and lets level 0 of
+ * the product tree find its leaves in it -- no patch matrix (im2col), whose kh kw copies of every ciphertext would each get a
+ * table of their own; the gather route writes the patch matrix into a block of the block cache and runs
+ * cofhe_hip_scal_matmul_records on it unchanged, when the direct route declines (as the matrix product's tree does) or for small
+ * shapes.  The window width follows the matrix product's cost model with a pixel's table amortised over the
+ * ceil(kh/sh) ceil(kw/sw) windows it is in; "wnaf_width" pins it.  Zero weights cost nothing, so sum pooling or a strided
+ * subsampling written as a 0/1 filter run at their real cost.
+ * COFHE_HIP_EINVAL, nothing written: a stride of 0; ph >= kh or pw >= kw; kh > H + 2 ph or kw > W + 2 pw; m >= 2^21; B H W C
+ * above 2^31 - 1, n above 2^32 - 1, n m above 2^40 or 2 n p records beyond the launch limit; d_out overlapping d_w, d_cts or
+ * d_zero.  B Ho Wo Co == 0: nothing to do.  NOT purely stream-ordered: as cofhe_hip_scal_matmul_records, the call synchronises
+ * `stream` once or twice.  Not covered: dilation, groups / depthwise filters, ciphertext filters, and a per-channel bias, which
+ * is cofhe_hip_add_plain_records on the result. */
+typedef struct {
+    uint32_t B, H, W, C;       /* image */
+    uint32_t kh, kw, Co;       /* filters: kh x kw x C x Co */
+    uint32_t sh, sw, ph, pw;   /* strides, zero padding (rows, columns) */
+} cofhe_hip_conv2d_shape;
+/* host only, no GPU: validates the shape (COFHE_HIP_EINVAL for the refusals above) and gives the output extents */
+int cofhe_hip_conv2d_out_shape(const cofhe_hip_conv2d_shape *shape, uint32_t *Ho, uint32_t *Wo);
+int cofhe_hip_conv2d_plain_ct_records(cofhe_hip_ctx *ctx, const void *d_w, const void *d_cts, const void *d_zero, void *d_out,
+                                      const cofhe_hip_conv2d_shape *shape, void *stream);
 /* out[i,k] = sum_j a[i,j] b[j,k] mod 2^kbits on exponent records (a n x m, b m x p, out n x p; 32 words each: 31 of
  * magnitude and a sign word).  Negative inputs count as -mag mod 2^k and magnitudes of 2^k and above are reduced first; the
  * outputs lie in [0, 2^k) with sign word 0.  1 <= kbits <= 639 (the bound of the decryption table), any kbits in that range:
@@ -273,6 +308,11 @@ int cofhe_hip_time_compose(cofhe_hip_ctx *ctx, const void *d_a, const void *d_b,
  *      "decrypt"          args: n_ct, shared_c1 (0 / 1)       (cofhe_hip_decrypt_records: front = one record per ciphertext)
  *      "part_decrypt"     args: n_ct, shared_c1               (cofhe_hip_part_decrypt_records: no front)
  *      "scal_matmul"      args: n, m, p, exp_bits, w, segs
+ *      "scal_matmul_tree" args: n, m, p, exp_bits, w          (the product-tree route of the same)
+ *      "conv2d"           args: B, H, W, C, kh, kw, Co, sh, sw, ph, pw, exp_bits, w   (the direct route of
+ *                         cofhe_hip_conv2d_plain_ct_records: "table" is B H W C 2 2^(w-2) 672 bytes -- the image, not the patches;
+ *                         empty at w = 2, where the image itself is the table; the other regions as "scal_matmul_tree" with
+ *                         m = kh kw C, p = Co)
  *      "accumulate_tree"  args: n, m, p
  *      "encrypt_chunk"    args: n_elements, kbits
  *      "fixed_base"       args: n_powers, max_entries
@@ -337,6 +377,13 @@ int cofhe_hip_add_plaintext_tensor_bytes(cofhe_hip_ctx *ctx, const uint8_t *cts,
  * COFHE_HIP_ESHAPE when an operand is not 2-D or s.shape[1] != cts.shape[0]. */
 int cofhe_hip_matmul_plain_ct_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *s, size_t ls, const uint8_t *cts, size_t lc,
                                             const uint8_t *zero, size_t lz, uint8_t **out, size_t *outlen);
+/* w (plaintext tensor [kh, kw, C, Co]) over cts (ciphertext tensor [B, H, W, C]) from zero (1-element ciphertext tensor), strides
+ * sh, sw and zero padding ph, pw: the serialised twin of cofhe_hip_conv2d_plain_ct_records; the result is the 4-D ciphertext
+ * tensor [B, Ho, Wo, Co].  Incoming forms are validated (COFHE_HIP_EINVAL for a non-form, and for the geometry's refusals);
+ * COFHE_HIP_ESHAPE when an operand is not 4-D or w.shape[2] != cts.shape[3]. */
+int cofhe_hip_conv2d_plain_ct_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *w, size_t lw, const uint8_t *cts, size_t lc,
+                                            const uint8_t *zero, size_t lz, uint32_t sh, uint32_t sw, uint32_t ph, uint32_t pw,
+                                            uint8_t **out, size_t *outlen);
 /* s: plaintext tensor; 1-D x 1-D -> element-wise, 2-D x 2-D -> matmul (zero: 1-element tensor) */
 int cofhe_hip_scal_ciphertext_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *s, size_t ls,
                                             const uint8_t *cts, size_t lc, const uint8_t *zero, size_t lz,
