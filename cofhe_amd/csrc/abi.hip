@@ -2,7 +2,7 @@
 // two-build launch, flag words, the table-cache lookup), the workspace plans, the launchers (one launch site per kernel and
 // route; product_tree is the pairwise tree of them all) and the host-side tensor formats.  The kernels are declared in
 // kernels.hpp and defined in cofhe_hip.hip, wide.hip, comb.hip, affine.hip, matmul_left.hip and conv.hip; this file holds no device code
-// of its own.  conv.hip holds the two kernels of the convolution.
+// of its own.  conv.hip holds the three kernels of the convolution.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -1476,8 +1476,12 @@ namespace {
 ConvShape conv_shape_of(const cofhe_hip_conv2d_shape &a) {
     return ConvShape{a.B, a.H, a.W, a.C, a.kh, a.kw, a.Co, a.sh, a.sw, a.ph, a.pw, 0u, 0u};
 }
+ConvShape conv_geometry_of(const cofhe_hip_conv2d_geometry &a) {      // (no overloads: this file is extern "C")
+    return ConvShape{a.B, a.H, a.W, a.C, a.kh, a.kw, a.Co, a.sh, a.sw, a.ph, a.pw, 0u, 0u, a.dh, a.dw, a.groups};
+}
 // the one launch site of k_gather_patches: the n x m patch matrix of the image (im2col), the principal form in the padding;
-// 16-byte pieces when both pointers allow them (a caller's pointer is only known to be 4-byte aligned)
+// 16-byte pieces when both pointers allow them (a caller's pointer is only known to be 4-byte aligned).  s has no groups: the
+// patch matrix is dense over C
 int gather_patches_launch(cofhe_hip_ctx *ctx, const ConvShape &s, const void *d_cts, void *d_patches, hipStream_t st) {
     const uint32_t n = conv_rows(s), m = conv_inner(s);
     const bool vec16 = (((uintptr_t)d_cts | (uintptr_t)d_patches) & 15) == 0;
@@ -1490,24 +1494,28 @@ int gather_patches_launch(cofhe_hip_ctx *ctx, const ConvShape &s, const void *d_
     HIPCHK(hipGetLastError());
     return COFHE_HIP_OK;
 }
-}  // namespace
-
-int cofhe_hip_conv2d_out_shape(const cofhe_hip_conv2d_shape *shape, uint32_t *Ho, uint32_t *Wo) {
-    if (!shape || !Ho || !Wo) return fail(COFHE_HIP_EINVAL, "null argument");
-    ConvShape s = conv_shape_of(*shape);
-    if (const char *why = conv_shape_check(s)) return fail(COFHE_HIP_EINVAL, why);
-    *Ho = s.Ho;
-    *Wo = s.Wo;
+// the one launch site of k_expand_group_filters: the dense [kh, kw, C, Co] exponent tensor of the grouped filters d_w
+// [kh, kw, C / groups, Co] into d_dense (a block of the block cache), the zero exponent outside the blocks
+int expand_group_filters_launch(cofhe_hip_ctx *ctx, const ConvShape &s, const void *d_w, void *d_dense, hipStream_t st) {
+    const bool vec16 = ((uintptr_t)d_w & 15) == 0;
+    const uint64_t total = (uint64_t)s.kh * s.kw * s.C * s.Co * (vec16 ? EXP_REC_WORDS / 4 : EXP_REC_WORDS);
+    if (total == 0) return COFHE_HIP_OK;
+    const unsigned blocks = (unsigned)std::min<uint64_t>((total + 255) / 256, 64u * NUM_CUS);       // grid-stride beyond that
+    ProfScope ps(ctx, "k_expand_group_filters", st);
+    hipLaunchKernelGGL(k_expand_group_filters, dim3(blocks), dim3(256), 0, st, (const uint32_t *)d_w, (uint32_t *)d_dense, s.kh * s.kw, s.C, s.Co,
+                       s.groups, vec16 ? 1u : 0u);
+    HIPCHK(hipGetLastError());
     return COFHE_HIP_OK;
 }
 
+// THE convolution, behind every entry point: the full geometry, validated here before the context or a pointer is looked at.
 // Two routes.  Direct: the product-tree route of the matrix product with the table built once over the image and level 0
-// reading its leaves through conv_leaf (plan "conv2d").  Gather: the patch matrix into a block of the block cache, then
-// cofhe_hip_scal_matmul_records unchanged (its own plans) -- when the direct route declines or is pinned off.
-int cofhe_hip_conv2d_plain_ct_records(cofhe_hip_ctx *ctx, const void *d_w, const void *d_cts, const void *d_zero, void *d_out,
-                                      const cofhe_hip_conv2d_shape *shape, void *stream) {
-    if (!shape) return fail(COFHE_HIP_EINVAL, "null argument");
-    ConvShape s = conv_shape_of(*shape);
+// reading its leaves through conv_leaf (plans "conv2d", "conv2d_grouped"), m = kh kw C / groups.  Gather: the patch matrix into
+// a block of the block cache, then cofhe_hip_scal_matmul_records unchanged (its own plans) -- when the direct route declines or
+// is pinned off.  The patch matrix is dense over C, so with groups the gather route first expands the filters to the dense
+// [kh, kw, C, Co] tensor (k_expand_group_filters) and then costs what the block-diagonal filter always cost: `groups` times
+// the digits, the segment scans and the patch matrix of the direct route.
+int conv2d_run(cofhe_hip_ctx *ctx, const void *d_w, const void *d_cts, const void *d_zero, void *d_out, ConvShape s, void *stream) {
     if (const char *why = conv_shape_check(s)) return fail(COFHE_HIP_EINVAL, why);
     const uint32_t n = conv_rows(s), m = conv_inner(s), p = s.Co;
     if ((uint64_t)n * p == 0) return COFHE_HIP_OK;
@@ -1519,26 +1527,101 @@ int cofhe_hip_conv2d_plain_ct_records(cofhe_hip_ctx *ctx, const void *d_w, const
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     const CombState &opt = comb_state(ctx);
+    const bool grouped = s.groups > 1;
+    // the gather route works on the dense inner dimension: kh kw C < 2^21 and the dense patch matrix within the formats' bound
+    const uint64_t m_dense = (uint64_t)s.kh * s.kw * s.C;
+    const bool gather_fits = !grouped || (m_dense < (1ull << 21) && (uint64_t)n * m_dense <= CONV_PATCH_LIMIT);
     // automatic: the direct route where the matrix product itself takes its tree (something to pair up, enough outputs for the
-    // Horner chains to fill the GPU); small convolutions keep the chains, behind the gather
-    const bool direct = opt.opt_conv_route == 1 || (opt.opt_conv_route == 0 && m >= 8 && (uint64_t)n * p * 2 >= 4096);
+    // Horner chains to fill the GPU); small convolutions keep the chains, behind the gather.  With groups the direct route
+    // wherever it does not decline: the gather pays `groups` times the patch matrix, the digits and the scans there
+    // (DESIGN.md section 5 has the measurements)
+    const bool direct = opt.opt_conv_route == 1 || !gather_fits || (opt.opt_conv_route == 0 && (grouped || (m >= 8 && (uint64_t)n * p * 2 >= 4096)));
     if (direct && m > 0) {
         WsUse use(ctx, st);
-        // window width: the table of a pixel is used by the p columns of every window the pixel is in
+        // window width: the table of a pixel is used by the columns of its group in every window the pixel is in
         const uint64_t reuse = (uint64_t)((s.kh + s.sh - 1) / s.sh) * ((s.kw + s.sw - 1) / s.sw);
         uint32_t w = 2, exp_bits = 0;
         if (int rc = max_exp_bits(ctx, d_w, (uint64_t)m * p, st, &exp_bits)) return rc;
-        if (int rc = wnaf_auto_width(ctx, (uint64_t)s.B * s.H * s.W * s.C * 2, (double)reuse * p, exp_bits, &w)) return rc;
+        if (int rc = wnaf_auto_width(ctx, (uint64_t)s.B * s.H * s.W * s.C * 2, (double)reuse * (p / s.groups), exp_bits, &w)) return rc;
         bool taken = false;
         if (int rc = matmul_tree_route(ctx, d_cts, d_w, d_zero, d_out, n, m, p, w, exp_bits, st, &taken, &s, opt.opt_conv_chunk_rows)) return rc;
         if (taken) return COFHE_HIP_OK;
     }
-    DevBuf patches;
-    patches.stream = stream;
-    const size_t patch_bytes = (size_t)n * m * ct_bytes;
+    if (!gather_fits)
+        return fail(COFHE_HIP_EINVAL, "conv2d: the direct route declined and the dense patch matrix of the gather route does not fit");
+    const ConvShape ds = conv_dense(s);
+    DevBuf patches, dense;
+    patches.stream = dense.stream = stream;
+    const size_t patch_bytes = (size_t)n * m_dense * ct_bytes;
     if (int rc = patches.get(ctx, patch_bytes ? patch_bytes : 4)) return rc;
-    if (int rc = gather_patches_launch(ctx, s, d_cts, patches.p, st)) return rc;
-    return cofhe_hip_scal_matmul_records(ctx, patches.p, d_w, d_zero, d_out, n, m, p, stream);
+    if (int rc = gather_patches_launch(ctx, ds, d_cts, patches.p, st)) return rc;
+    if (grouped) {
+        const size_t dense_bytes = (size_t)m_dense * p * EXP_REC_WORDS * 4;
+        if (int rc = dense.get(ctx, dense_bytes ? dense_bytes : 4)) return rc;
+        if (int rc = expand_group_filters_launch(ctx, s, d_w, dense.p, st)) return rc;
+    }
+    return cofhe_hip_scal_matmul_records(ctx, patches.p, grouped ? dense.p : d_w, d_zero, d_out, n, (uint32_t)m_dense, p, stream);
+}
+// a pooling geometry: one filter per channel
+ConvShape pool_shape_of(const cofhe_hip_conv2d_geometry &a) {
+    ConvShape s = conv_geometry_of(a);
+    s.Co = s.C;
+    s.groups = s.C ? s.C : 1;
+    return s;
+}
+}  // namespace
+
+int cofhe_hip_conv2d_out_shape(const cofhe_hip_conv2d_shape *shape, uint32_t *Ho, uint32_t *Wo) {
+    if (!shape || !Ho || !Wo) return fail(COFHE_HIP_EINVAL, "null argument");
+    ConvShape s = conv_shape_of(*shape);
+    if (const char *why = conv_shape_check(s)) return fail(COFHE_HIP_EINVAL, why);
+    *Ho = s.Ho;
+    *Wo = s.Wo;
+    return COFHE_HIP_OK;
+}
+int cofhe_hip_conv2d_geometry_out_shape(const cofhe_hip_conv2d_geometry *geometry, uint32_t *Ho, uint32_t *Wo) {
+    if (!geometry || !Ho || !Wo) return fail(COFHE_HIP_EINVAL, "null argument");
+    ConvShape s = conv_geometry_of(*geometry);
+    if (const char *why = conv_shape_check(s)) return fail(COFHE_HIP_EINVAL, why);
+    *Ho = s.Ho;
+    *Wo = s.Wo;
+    return COFHE_HIP_OK;
+}
+
+int cofhe_hip_conv2d_plain_ct_records(cofhe_hip_ctx *ctx, const void *d_w, const void *d_cts, const void *d_zero, void *d_out,
+                                      const cofhe_hip_conv2d_shape *shape, void *stream) {
+    if (!shape) return fail(COFHE_HIP_EINVAL, "null argument");
+    return conv2d_run(ctx, d_w, d_cts, d_zero, d_out, conv_shape_of(*shape), stream);          // dh = dw = groups = 1
+}
+int cofhe_hip_conv2d_grouped_plain_ct_records(cofhe_hip_ctx *ctx, const void *d_w, const void *d_cts, const void *d_zero, void *d_out,
+                                              const cofhe_hip_conv2d_geometry *geometry, void *stream) {
+    if (!geometry) return fail(COFHE_HIP_EINVAL, "null argument");
+    return conv2d_run(ctx, d_w, d_cts, d_zero, d_out, conv_geometry_of(*geometry), stream);
+}
+
+// The depthwise convolution with [kh, kw, 1, C] filters of ones.  The filters are kh kw C exponent records made here, in a block
+// of the block cache: every word zero but the lowest byte of each record.  At exp_bits = 1 the window width stays 2, no table is
+// built, and the tree is kh kw - 1 compositions per output record plus the one with zero.
+int cofhe_hip_sum_pool2d_records(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_zero, void *d_out,
+                                 const cofhe_hip_conv2d_geometry *geometry, void *stream) {
+    if (!geometry) return fail(COFHE_HIP_EINVAL, "null argument");
+    ConvShape s = pool_shape_of(*geometry);
+    if (const char *why = conv_shape_check(s)) return fail(COFHE_HIP_EINVAL, why);
+    const uint64_t nout = (uint64_t)conv_rows(s) * s.Co;
+    if (nout == 0) return COFHE_HIP_OK;
+    const size_t ct_bytes = (size_t)2 * REC_WORDS * 4;
+    if (overlaps(d_out, nout * ct_bytes, d_cts, (size_t)s.B * s.H * s.W * s.C * ct_bytes) || overlaps(d_out, nout * ct_bytes, d_zero, ct_bytes))
+        return fail(COFHE_HIP_EINVAL, "sum_pool2d: the output overlaps an input");
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n_w = (size_t)conv_inner(s) * s.Co, rec_bytes = (size_t)EXP_REC_WORDS * 4;
+    DevBuf ones;
+    ones.stream = stream;
+    if (int rc = ones.get(ctx, n_w * rec_bytes)) return rc;
+    HIPCHK(hipMemsetAsync(ones.p, 0, n_w * rec_bytes, st));
+    HIPCHK(hipMemset2DAsync(ones.p, rec_bytes, 1, 1, n_w, st));         // one byte per record: magnitude 1, sign word 0
+    return conv2d_run(ctx, ones.p, d_cts, d_zero, d_out, s, stream);
 }
 
 int cofhe_hip_matmul_plain_plain_records(cofhe_hip_ctx *ctx, const void *d_a, const void *d_b, void *d_out, uint32_t n, uint32_t m, uint32_t p,
@@ -1729,6 +1812,17 @@ int cofhe_hip_workspace_plan(const char *op, const uint64_t *args, uint32_t n_ar
                      (uint32_t)args[7], (uint32_t)args[8], (uint32_t)args[9], (uint32_t)args[10], 0u, 0u};
         if (const char *why = conv_shape_check(cs)) return fail(COFHE_HIP_EINVAL, why);
         p = plan_conv2d(cs, (uint32_t)args[11], (uint32_t)args[12]);
+    } else if (o == "conv2d_grouped" && need(16)) {
+        // B, H, W, C, kh, kw, Co, sh, sw, ph, pw, dh, dw, groups, exp_bits, w: the direct route of
+        // cofhe_hip_conv2d_grouped_plain_ct_records
+        for (int i = 0; i < 16; i++)
+            if (args[i] > 0xFFFFFFFFull) return fail(COFHE_HIP_EINVAL, "conv2d_grouped plan: argument out of range");
+        if (args[15] < 2 || args[15] > 8) return fail(COFHE_HIP_EINVAL, "conv2d_grouped plan: w in 2..8");
+        ConvShape cs{(uint32_t)args[0], (uint32_t)args[1], (uint32_t)args[2], (uint32_t)args[3], (uint32_t)args[4], (uint32_t)args[5], (uint32_t)args[6],
+                     (uint32_t)args[7], (uint32_t)args[8], (uint32_t)args[9], (uint32_t)args[10], 0u, 0u,
+                     (uint32_t)args[11], (uint32_t)args[12], (uint32_t)args[13]};
+        if (const char *why = conv_shape_check(cs)) return fail(COFHE_HIP_EINVAL, why);
+        p = plan_conv2d(cs, (uint32_t)args[14], (uint32_t)args[15]);
     } else if (o == "accumulate_tree" && need(3)) {
         p = plan_accumulate_tree((uint32_t)args[0], (uint32_t)args[1], (uint32_t)args[2]);
     } else if (o == "encrypt_chunk" && need(2)) {
@@ -2083,30 +2177,63 @@ int cofhe_hip_matmul_plain_ct_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *s
     return finish(ctx, dout, nout, 2, so, out, outlen);
 }
 
-int cofhe_hip_conv2d_plain_ct_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *w, size_t lw, const uint8_t *cts, size_t lc, const uint8_t *zero,
-                                            size_t lz, uint32_t sh, uint32_t sw, uint32_t ph, uint32_t pw, uint8_t **out, size_t *outlen) {
+namespace {
+// the serialised twin of conv2d_run: w null = sum pooling over kh x kw windows (no filter tensor; Co = groups = C)
+int conv2d_bytes(cofhe_hip_ctx *ctx, const uint8_t *w, size_t lw, const uint8_t *cts, size_t lc, const uint8_t *zero, size_t lz,
+                 cofhe_hip_conv2d_geometry g, uint8_t **out, size_t *outlen) {
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    uint32_t ndw, ndc, swp[8], sc[8];
+    uint32_t ndw = 0, ndc, swp[8], sc[8];
     uint64_t ne, nr;
     HIPCHK(hipSetDevice(ctx->device));
     DevBuf de, dc, dz, dout;
-    if (int rc = load_tensor(ctx, w, lw, 0, de, &ndw, swp, &ne)) return rc;
+    if (w)
+        if (int rc = load_tensor(ctx, w, lw, 0, de, &ndw, swp, &ne)) return rc;
     if (int rc = load_tensor(ctx, cts, lc, 2, dc, &ndc, sc, &nr)) return rc;
-    if (ndw != 4 || ndc != 4) return fail(COFHE_HIP_ESHAPE, "conv2d takes a 4-D filter tensor [kh, kw, C, Co] and a 4-D image tensor [B, H, W, C]");
-    if (swp[2] != sc[3]) return fail(COFHE_HIP_ESHAPE, "conv2d: the channels of the filters and of the image differ");
-    const cofhe_hip_conv2d_shape shp{sc[0], sc[1], sc[2], sc[3], swp[0], swp[1], swp[3], sh, sw, ph, pw};
+    if (w && (ndw != 4 || ndc != 4))
+        return fail(COFHE_HIP_ESHAPE, "conv2d takes a 4-D filter tensor [kh, kw, C / groups, Co] and a 4-D image tensor [B, H, W, C]");
+    if (!w && ndc != 4) return fail(COFHE_HIP_ESHAPE, "sum_pool2d takes a 4-D image tensor [B, H, W, C]");
+    g.B = sc[0], g.H = sc[1], g.W = sc[2], g.C = sc[3];
+    if (w) {
+        g.kh = swp[0], g.kw = swp[1], g.Co = swp[3];
+        if (g.groups && swp[2] != g.C / g.groups) return fail(COFHE_HIP_ESHAPE, "conv2d: the channels of the filters and of the image differ");
+    } else {
+        g.Co = g.C;
+        g.groups = g.C ? g.C : 1;
+    }
     uint32_t Ho = 0, Wo = 0;
-    if (int rc = cofhe_hip_conv2d_out_shape(&shp, &Ho, &Wo)) return rc;
+    if (int rc = cofhe_hip_conv2d_geometry_out_shape(&g, &Ho, &Wo)) return rc;
     uint32_t ndz, sz[8];
     uint64_t nz;
     if (!zero) return fail(COFHE_HIP_EINVAL, "conv2d needs the encryption of zero it starts from");
     if (int rc = load_tensor(ctx, zero, lz, 2, dz, &ndz, sz, &nz)) return rc;
     if (nz != 2) return fail(COFHE_HIP_EINVAL, "zero must be a one-element ciphertext tensor");
-    const uint32_t so[4] = {shp.B, Ho, Wo, shp.Co};
+    const uint32_t so[4] = {g.B, Ho, Wo, g.Co};
     const uint64_t nout = (uint64_t)so[0] * Ho * Wo * so[3] * 2;
     if (int rc = dout.get(ctx, nout ? nout * REC_WORDS * 4 : 4)) return rc;
-    if (int rc = cofhe_hip_conv2d_plain_ct_records(ctx, de.p, dc.p, dz.p, dout.p, &shp, nullptr)) return rc;
+    if (w) {
+        if (int rc = cofhe_hip_conv2d_grouped_plain_ct_records(ctx, de.p, dc.p, dz.p, dout.p, &g, nullptr)) return rc;
+    } else {
+        if (int rc = cofhe_hip_sum_pool2d_records(ctx, dc.p, dz.p, dout.p, &g, nullptr)) return rc;
+    }
     return finish(ctx, dout, nout, 4, so, out, outlen);
+}
+}  // namespace
+
+int cofhe_hip_conv2d_plain_ct_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *w, size_t lw, const uint8_t *cts, size_t lc, const uint8_t *zero,
+                                            size_t lz, uint32_t sh, uint32_t sw, uint32_t ph, uint32_t pw, uint8_t **out, size_t *outlen) {
+    if (!w) return fail(COFHE_HIP_EINVAL, "null argument");
+    // dh = dw = groups = 1: conv2d_run then launches what cofhe_hip_conv2d_plain_ct_records launches
+    return conv2d_bytes(ctx, w, lw, cts, lc, zero, lz, cofhe_hip_conv2d_geometry{0, 0, 0, 0, 0, 0, 0, sh, sw, ph, pw, 1, 1, 1}, out, outlen);
+}
+int cofhe_hip_conv2d_grouped_plain_ct_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *w, size_t lw, const uint8_t *cts, size_t lc,
+                                                    const uint8_t *zero, size_t lz, uint32_t sh, uint32_t sw, uint32_t ph, uint32_t pw,
+                                                    uint32_t dh, uint32_t dw, uint32_t groups, uint8_t **out, size_t *outlen) {
+    if (!w) return fail(COFHE_HIP_EINVAL, "null argument");
+    return conv2d_bytes(ctx, w, lw, cts, lc, zero, lz, cofhe_hip_conv2d_geometry{0, 0, 0, 0, 0, 0, 0, sh, sw, ph, pw, dh, dw, groups}, out, outlen);
+}
+int cofhe_hip_sum_pool2d_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *cts, size_t lc, const uint8_t *zero, size_t lz, uint32_t kh, uint32_t kw,
+                                       uint32_t sh, uint32_t sw, uint32_t ph, uint32_t pw, uint8_t **out, size_t *outlen) {
+    return conv2d_bytes(ctx, nullptr, 0, cts, lc, zero, lz, cofhe_hip_conv2d_geometry{0, 0, 0, 0, kh, kw, 0, sh, sw, ph, pw, 1, 1, 1}, out, outlen);
 }
 
 }  // extern "C"

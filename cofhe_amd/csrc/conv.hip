@@ -1,7 +1,8 @@
-// conv.hip -- the two kernels of cofhe_hip_conv2d_plain_ct_records (launched by abi.hip, declared in kernels.hpp; the geometry
-// and the level-0 body: conv.hpp).  k_conv_level0 is level 0 -> 1 of the matrix product's tree with its leaves read straight
-// from the table of the IMAGE; k_gather_patches writes the patch matrix (im2col) for the route that runs the matrix product
-// unchanged.
+// conv.hip -- the kernels of cofhe_hip_conv2d_plain_ct_records and cofhe_hip_conv2d_grouped_plain_ct_records (launched by
+// abi.hip, declared in kernels.hpp; the geometry and the level-0 body: conv.hpp).  k_conv_level0 is level 0 -> 1 of the matrix
+// product's tree with its leaves read straight from the table of the IMAGE; k_gather_patches writes the patch matrix (im2col)
+// for the route that runs the matrix product unchanged, and k_expand_group_filters the dense filter that route needs when the
+// convolution has groups.
 #include <hip/hip_runtime.h>
 
 #include "conv.hpp"
@@ -50,6 +51,34 @@ __global__ void __launch_bounds__(256) k_gather_patches(ConvShape s, const uint3
         gather_body(s, (const uint4 *)cts, (const uint4 *)one_rec, (uint4 *)out, n, m, (uint32_t)REC_WORDS / 4);
     else
         gather_body(s, cts, one_rec, out, n, m, (uint32_t)REC_WORDS);
+}
+
+
+// dense[(t C + c) Co + co] = w[(t Cg + c % Cg) Co + co] when channel c lies in the group of column co (c / Cg == co / Cog), else
+// the zero exponent, for t < taps = kh kw: exponent records of `pieces` pieces of type T.  Consecutive threads take consecutive
+// pieces of one OUTPUT record.
+template <typename T>
+__device__ __forceinline__ void expand_body(const T *__restrict__ w, T *__restrict__ dense, uint32_t taps, uint32_t C, uint32_t Co, uint32_t groups,
+                                            uint32_t pieces) {
+    const uint32_t Cg = C / groups, Cog = Co / groups;
+    const uint64_t total = (uint64_t)taps * C * Co * pieces;
+    for (uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t e = idx / pieces;
+        const uint32_t piece = (uint32_t)(idx - e * pieces), co = (uint32_t)(e % Co);
+        const uint64_t tc = e / Co;
+        const uint32_t c = (uint32_t)(tc % C), t = (uint32_t)(tc / C);
+        T v{};
+        if (c / Cg == co / Cog) v = w[(((uint64_t)t * Cg + c % Cg) * Co + co) * pieces + piece];
+        dense[idx] = v;
+    }
+}
+// vec16: the launcher found w 16-byte aligned (dense, a block of the block cache, always is)
+__global__ void __launch_bounds__(256) k_expand_group_filters(const uint32_t *__restrict__ w, uint32_t *__restrict__ dense, uint32_t taps, uint32_t C,
+                                                              uint32_t Co, uint32_t groups, uint32_t vec16) {
+    if (vec16)
+        expand_body((const uint4 *)w, (uint4 *)dense, taps, C, Co, groups, (uint32_t)EXP_REC_WORDS / 4);
+    else
+        expand_body(w, dense, taps, C, Co, groups, (uint32_t)EXP_REC_WORDS);
 }
 
 }  // namespace cofhe_k

@@ -3,7 +3,7 @@
 // (the latency kernels); wire.hip launches its own kernels.  A declaration that matches no definition is an
 // undefined symbol when the library is loaded (tests/test_cabi.py).  comb.hip holds the two kernels of the fixed-base comb,
 // affine.hip the ciphertext difference and the record inverse, matmul_left.hip the record transpose and the plaintext
-// matrix product, conv.hip the convolution's level 0 and its patch gather.
+// matrix product, conv.hip the convolution's level 0, its patch gather and its filter expansion.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -134,11 +134,14 @@ __global__ void k_plain_matmul(const uint32_t *__restrict__ a, const uint32_t *_
                                uint32_t p, uint32_t kbits);
 
 // the convolution (conv.hip, conv.hpp): level 0 -> 1 of the product tree with its leaves read from the table of the image, and
-// the patch matrix n x m written out (vec16: 16-byte pieces)
+// the patch matrix n x m written out (vec16: 16-byte pieces); the dense [taps, C, Co] exponent tensor of a grouped
+// [taps, C / groups, Co] filter, zero outside the blocks, for the gather route of a convolution with groups
 __global__ void k_conv_level0(cofhe::ConvShape s, const uint32_t *__restrict__ table, const uint32_t *__restrict__ one_rec,
                               const uint32_t *__restrict__ ent0, const uint32_t *__restrict__ off_cur, const uint32_t *__restrict__ off_next,
                               const uint32_t *__restrict__ map_next, uint32_t n_next, uint32_t row0, uint32_t rows, uint32_t tw,
                               uint32_t *__restrict__ dst, const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status);
 __global__ void k_gather_patches(cofhe::ConvShape s, const uint32_t *__restrict__ cts, const uint32_t *__restrict__ one_rec,
                                  uint32_t *__restrict__ out, uint32_t n, uint32_t m, uint32_t vec16);
+__global__ void k_expand_group_filters(const uint32_t *__restrict__ w, uint32_t *__restrict__ dense, uint32_t taps, uint32_t C, uint32_t Co,
+                                       uint32_t groups, uint32_t vec16);
 }  // namespace cofhe_k

@@ -131,14 +131,30 @@ class Engine:
                                                             C.byref(out), C.byref(n)))
         return self._take(out, n)
 
-    def conv2d_plain_ct_tensors(self, w: bytes, cts: bytes, zero: bytes, stride=(1, 1), pad=(0, 0)) -> bytes:
-        """w (plaintext tensor [kh, kw, C, Co]) over cts (ciphertext tensor [B, H, W, C]), channels last, from zero (1-element
-        ciphertext tensor); stride and zero padding as (rows, columns).  Returns the ciphertext tensor [B, Ho, Wo, Co]"""
+    def conv2d_plain_ct_tensors(self, w: bytes, cts: bytes, zero: bytes, stride=(1, 1), pad=(0, 0), dilation=(1, 1), groups=1) -> bytes:
+        """w (plaintext tensor [kh, kw, C / groups, Co]) over cts (ciphertext tensor [B, H, W, C]), channels last, from zero
+        (1-element ciphertext tensor); stride, zero padding and dilation as (rows, columns).  Returns the ciphertext tensor
+        [B, Ho, Wo, Co]"""
         out = C.POINTER(C.c_uint8)()
         n = C.c_size_t()
-        _chk(self.L.cofhe_hip_conv2d_plain_ct_tensors_bytes(self.ctx, C.c_char_p(w), C.c_size_t(len(w)), C.c_char_p(cts), C.c_size_t(len(cts)),
-                                                            C.c_char_p(zero), C.c_size_t(len(zero)), C.c_uint32(stride[0]), C.c_uint32(stride[1]),
-                                                            C.c_uint32(pad[0]), C.c_uint32(pad[1]), C.byref(out), C.byref(n)))
+        head = (self.ctx, C.c_char_p(w), C.c_size_t(len(w)), C.c_char_p(cts), C.c_size_t(len(cts)), C.c_char_p(zero), C.c_size_t(len(zero)),
+                C.c_uint32(stride[0]), C.c_uint32(stride[1]), C.c_uint32(pad[0]), C.c_uint32(pad[1]))
+        if tuple(dilation) == (1, 1) and groups == 1:
+            _chk(self.L.cofhe_hip_conv2d_plain_ct_tensors_bytes(*head, C.byref(out), C.byref(n)))
+        else:
+            _chk(self.L.cofhe_hip_conv2d_grouped_plain_ct_tensors_bytes(*head, C.c_uint32(dilation[0]), C.c_uint32(dilation[1]), C.c_uint32(groups),
+                                                                        C.byref(out), C.byref(n)))
+        return self._take(out, n)
+
+    def sum_pool2d_tensors(self, cts: bytes, zero: bytes, kernel, stride=None, pad=(0, 0)) -> bytes:
+        """the sums over kernel = (kh, kw) windows of the ciphertext tensor cts [B, H, W, C], channel by channel, from zero;
+        stride defaults to the kernel.  Returns [B, Ho, Wo, C].  Average pooling: fold 1 / (kh kw) into the next layer's weights"""
+        stride = kernel if stride is None else stride
+        out = C.POINTER(C.c_uint8)()
+        n = C.c_size_t()
+        _chk(self.L.cofhe_hip_sum_pool2d_tensors_bytes(self.ctx, C.c_char_p(cts), C.c_size_t(len(cts)), C.c_char_p(zero), C.c_size_t(len(zero)),
+                                                       C.c_uint32(kernel[0]), C.c_uint32(kernel[1]), C.c_uint32(stride[0]), C.c_uint32(stride[1]),
+                                                       C.c_uint32(pad[0]), C.c_uint32(pad[1]), C.byref(out), C.byref(n)))
         return self._take(out, n)
 
     # ---- format conversion (host) ----------------------------------------------------------
@@ -280,18 +296,35 @@ class Engine:
                                                       C.c_void_p(d_out), C.c_uint32(n), C.c_uint32(m), C.c_uint32(p),
                                                       C.c_void_p(stream)))
 
-    def conv2d_plain_ct_records(self, d_w, d_cts, d_zero, d_out, image, filters, stride=(1, 1), pad=(0, 0), stream=0):
+    def conv2d_plain_ct_records(self, d_w, d_cts, d_zero, d_out, image, filters, stride=(1, 1), pad=(0, 0), stream=0, dilation=(1, 1), groups=1):
         """out [B, Ho, Wo, Co] = the convolution of the ciphertext image d_cts [B, H, W, C] = `image` with the plaintext filters
-        d_w [kh, kw, C, Co] = `filters` (exponent records), channels last, from the ciphertext d_zero; d_out must not overlap an
-        input.  Returns (Ho, Wo)"""
-        shp = _conv_shape(image, filters, stride, pad)
-        _chk(self.L.cofhe_hip_conv2d_plain_ct_records(self.ctx, C.c_void_p(d_w), C.c_void_p(d_cts), C.c_void_p(d_zero), C.c_void_p(d_out),
-                                                      C.byref(shp), C.c_void_p(stream)))
-        return conv2d_out_shape(image, filters, stride, pad)
+        d_w [kh, kw, C / groups, Co] = `filters` (exponent records), channels last, from the ciphertext d_zero; d_out must not
+        overlap an input.  Returns (Ho, Wo)"""
+        if tuple(dilation) == (1, 1) and groups == 1:
+            shp = _conv_shape(image, filters, stride, pad)
+            _chk(self.L.cofhe_hip_conv2d_plain_ct_records(self.ctx, C.c_void_p(d_w), C.c_void_p(d_cts), C.c_void_p(d_zero), C.c_void_p(d_out),
+                                                          C.byref(shp), C.c_void_p(stream)))
+        else:
+            geo = _conv_geometry(image, filters, stride, pad, dilation, groups)
+            _chk(self.L.cofhe_hip_conv2d_grouped_plain_ct_records(self.ctx, C.c_void_p(d_w), C.c_void_p(d_cts), C.c_void_p(d_zero),
+                                                                  C.c_void_p(d_out), C.byref(geo), C.c_void_p(stream)))
+        return conv2d_out_shape(image, filters, stride, pad, dilation, groups)
 
-    def conv2d_out_shape(self, image, filters, stride=(1, 1), pad=(0, 0)):
+    def conv2d_out_shape(self, image, filters, stride=(1, 1), pad=(0, 0), dilation=(1, 1), groups=1):
         """(Ho, Wo) of the convolution, or CofheHipError for a geometry it refuses (host only: the module's conv2d_out_shape)"""
-        return conv2d_out_shape(image, filters, stride, pad)
+        return conv2d_out_shape(image, filters, stride, pad, dilation, groups)
+
+    def sum_pool2d_records(self, d_cts, d_zero, d_out, image, kernel, stride=None, pad=(0, 0), stream=0):
+        """out [B, Ho, Wo, C] = the sums over kernel = (kh, kw) windows of the ciphertext image d_cts [B, H, W, C] = `image`,
+        channel by channel, from the ciphertext d_zero; stride defaults to the kernel.  Returns (Ho, Wo)"""
+        stride = kernel if stride is None else stride
+        B, H, W, Cin = image
+        geo = _ConvGeometry(B, H, W, Cin, kernel[0], kernel[1], Cin, stride[0], stride[1], pad[0], pad[1], 1, 1, max(Cin, 1))
+        _chk(self.L.cofhe_hip_sum_pool2d_records(self.ctx, C.c_void_p(d_cts), C.c_void_p(d_zero), C.c_void_p(d_out), C.byref(geo),
+                                                 C.c_void_p(stream)))
+        ho, wo = C.c_uint32(), C.c_uint32()
+        _chk(self.L.cofhe_hip_conv2d_geometry_out_shape(C.byref(geo), C.byref(ho), C.byref(wo)))
+        return int(ho.value), int(wo.value)
 
     def matmul_plain_plain_records(self, d_a, d_b, d_out, n, m, p, kbits, stream=0):
         """out = a (n x m) . b (m x p) mod 2^kbits on exponent records, outputs in [0, 2^k) with sign word 0; one launch,
@@ -516,13 +549,29 @@ def _conv_shape(image, filters, stride, pad):
     return _ConvShape(B, H, W, Cin, kh, kw, Co, stride[0], stride[1], pad[0], pad[1])
 
 
-def conv2d_out_shape(image, filters, stride=(1, 1), pad=(0, 0)):
-    """cofhe_hip_conv2d_out_shape (host only): (Ho, Wo) of image [B, H, W, C] under filters [kh, kw, C, Co]; raises
-    CofheHipError (COFHE_HIP_EINVAL) for a geometry the convolution refuses"""
+class _ConvGeometry(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("B", "H", "W", "C", "kh", "kw", "Co", "sh", "sw", "ph", "pw", "dh", "dw", "groups")]
+
+
+def _conv_geometry(image, filters, stride, pad, dilation, groups):
+    B, H, W, Cin = image
+    kh, kw, Cf, Co = filters
+    if groups > 0 and Cf != Cin // groups:
+        raise CofheHipError(-2, "conv2d: the channels of the filters and of the image differ")
+    return _ConvGeometry(B, H, W, Cin, kh, kw, Co, stride[0], stride[1], pad[0], pad[1], dilation[0], dilation[1], groups)
+
+
+def conv2d_out_shape(image, filters, stride=(1, 1), pad=(0, 0), dilation=(1, 1), groups=1):
+    """cofhe_hip_conv2d_out_shape / cofhe_hip_conv2d_geometry_out_shape (host only): (Ho, Wo) of image [B, H, W, C] under filters
+    [kh, kw, C / groups, Co]; raises CofheHipError (COFHE_HIP_EINVAL) for a geometry the convolution refuses"""
     L = load_library()
-    shp = _conv_shape(image, filters, stride, pad)
     ho, wo = C.c_uint32(), C.c_uint32()
-    _chk(L.cofhe_hip_conv2d_out_shape(C.byref(shp), C.byref(ho), C.byref(wo)))
+    if tuple(dilation) == (1, 1) and groups == 1:
+        shp = _conv_shape(image, filters, stride, pad)
+        _chk(L.cofhe_hip_conv2d_out_shape(C.byref(shp), C.byref(ho), C.byref(wo)))
+    else:
+        geo = _conv_geometry(image, filters, stride, pad, dilation, groups)
+        _chk(L.cofhe_hip_conv2d_geometry_out_shape(C.byref(geo), C.byref(ho), C.byref(wo)))
     return int(ho.value), int(wo.value)
 
 

@@ -781,6 +781,67 @@ class HIPCryptoSystem {
         check(cofhe_hip_conv2d_plain_ct_records(ctx_, dex, cts.ptr_, zero.ptr_, out.ptr_, &shp, nullptr));
         return out;
     }
+    // The same with dilation {rows, columns} and groups: filters w [kh, kw, C / groups, Co], output column co reads the channel
+    // block of group co / (Co / groups) (cofhe_hip_conv2d_grouped_plain_ct_records).  groups = C = Co is a depthwise
+    // convolution, 1 x 1 filters on top of that a per-channel scale.  Re-randomised like the overload above.
+    Tensor<CipherText *> conv2d_plaintext_ciphertext_tensors(const PublicKey &pk, const Tensor<PlainText *> &w, const Tensor<CipherText *> &cts,
+                                                             const std::array<size_t, 2> &stride, const std::array<size_t, 2> &pad,
+                                                             const std::array<size_t, 2> &dilation, size_t groups, const CipherText *zero = nullptr) const {
+        if (w.ndim() != 4 || cts.ndim() != 4) throw std::invalid_argument("conv2d_plaintext_ciphertext_tensors: both operands must be 4D");
+        CipherText z = zero ? *zero : encrypt(pk, make_plaintext(0));
+        Tensor<CipherText *> zt(1, &z);
+        DeviceTensor out = conv2d_plaintext_ciphertext_tensors(w, upload(cts), upload(zt), stride, pad, dilation, groups);
+        rerandomize_result(pk, out);
+        return download(std::move(out));
+    }
+    DeviceTensor conv2d_plaintext_ciphertext_tensors(const Tensor<PlainText *> &w, const DeviceTensor &cts, const DeviceTensor &zero,
+                                                     const std::array<size_t, 2> &stride, const std::array<size_t, 2> &pad,
+                                                     const std::array<size_t, 2> &dilation, size_t groups) const {
+        if (w.ndim() != 4 || cts.shape_.size() != 4) throw std::invalid_argument("conv2d_plaintext_ciphertext_tensors: both operands must be 4D");
+        if (groups == 0 || w.shape()[2] != cts.shape_[3] / groups)
+            throw std::invalid_argument("conv2d_plaintext_ciphertext_tensors: the filters' channels are not those of a group of the image");
+        if (zero.n_ != 1) throw std::invalid_argument("conv2d_plaintext_ciphertext_tensors: zero must be one ciphertext");
+        const cofhe_hip_conv2d_geometry geo = conv_geometry({cts.shape_[0], cts.shape_[1], cts.shape_[2], cts.shape_[3], w.shape()[0], w.shape()[1],
+                                                             w.shape()[3], stride[0], stride[1], pad[0], pad[1], dilation[0], dilation[1], groups});
+        uint32_t Ho = 0, Wo = 0;
+        check(cofhe_hip_conv2d_geometry_out_shape(&geo, &Ho, &Wo));
+        std::vector<uint32_t> ex = pack_exponents(w);
+        void *dex = nullptr;
+        check(cofhe_hip_malloc(ctx_, ex.size() * 4 + 4, &dex));
+        Guard g1{ctx_, dex};
+        check(cofhe_hip_upload(ctx_, dex, ex.data(), ex.size() * 4, nullptr));
+        DeviceTensor out = alloc({geo.B, Ho, Wo, geo.Co}, (size_t)geo.B * Ho * Wo * geo.Co);
+        check(cofhe_hip_conv2d_grouped_plain_ct_records(ctx_, dex, cts.ptr_, zero.ptr_, out.ptr_, &geo, nullptr));
+        return out;
+    }
+    // Sum pooling, channels last: res[b,oy,ox,c] = zero + sum over the kernel[0] x kernel[1] window at (oy stride[0] - pad[0],
+    // ox stride[1] - pad[1]) of cts[b, ., ., c], a tensor [B, Ho, Wo, C] (cofhe_hip_sum_pool2d_records: the depthwise convolution
+    // with filters of ones, kh kw - 1 additions per output).  Average pooling is this with 1 / (kh kw) folded into the next
+    // layer's plaintext weights: that inverse does not exist mod 2^k for an even window.  Re-randomised like conv2d.
+    Tensor<CipherText *> sum_pool2d_ciphertext_tensor(const PublicKey &pk, const Tensor<CipherText *> &cts, const std::array<size_t, 2> &kernel,
+                                                      const std::array<size_t, 2> &stride, const std::array<size_t, 2> &pad = {0, 0},
+                                                      const CipherText *zero = nullptr) const {
+        if (cts.ndim() != 4) throw std::invalid_argument("sum_pool2d_ciphertext_tensor: the operand must be 4D");
+        CipherText z = zero ? *zero : encrypt(pk, make_plaintext(0));
+        Tensor<CipherText *> zt(1, &z);
+        DeviceTensor out = sum_pool2d_ciphertext_tensor(upload(cts), upload(zt), kernel, stride, pad);
+        rerandomize_result(pk, out);
+        return download(std::move(out));
+    }
+    // the same on resident operands; deterministic
+    DeviceTensor sum_pool2d_ciphertext_tensor(const DeviceTensor &cts, const DeviceTensor &zero, const std::array<size_t, 2> &kernel,
+                                              const std::array<size_t, 2> &stride, const std::array<size_t, 2> &pad = {0, 0}) const {
+        if (cts.shape_.size() != 4) throw std::invalid_argument("sum_pool2d_ciphertext_tensor: the operand must be 4D");
+        if (zero.n_ != 1) throw std::invalid_argument("sum_pool2d_ciphertext_tensor: zero must be one ciphertext");
+        const size_t C = cts.shape_[3];
+        const cofhe_hip_conv2d_geometry geo = conv_geometry({cts.shape_[0], cts.shape_[1], cts.shape_[2], C, kernel[0], kernel[1], C, stride[0], stride[1],
+                                                             pad[0], pad[1], 1, 1, C ? C : 1});
+        uint32_t Ho = 0, Wo = 0;
+        check(cofhe_hip_conv2d_geometry_out_shape(&geo, &Ho, &Wo));
+        DeviceTensor out = alloc({geo.B, Ho, Wo, geo.C}, (size_t)geo.B * Ho * Wo * geo.C);
+        check(cofhe_hip_sum_pool2d_records(ctx_, cts.ptr_, zero.ptr_, out.ptr_, &geo, nullptr));
+        return out;
+    }
     // a (n x m) . b (m x p) mod 2^k on the device (k_plain_matmul): the E D term of a matrix Beaver triplet and the C = A B of
     // its generation.  The element-wise multiply_plaintext_tensors is a host loop and stays one.
     Tensor<PlainText *> matmul_plaintext_tensors(const Tensor<PlainText *> &a, const Tensor<PlainText *> &b) const {
@@ -1359,6 +1420,15 @@ class HIPCryptoSystem {
         std::string msg = cofhe_hip_last_error();
         if (rc == COFHE_HIP_ESHAPE || rc == COFHE_HIP_ENDIM || rc == COFHE_HIP_EINVAL) throw std::invalid_argument(msg);
         throw std::runtime_error(msg);
+    }
+    // the 14 extents of a convolution's geometry, each within 32 bits
+    static cofhe_hip_conv2d_geometry conv_geometry(const std::array<size_t, 14> &v) {
+        uint32_t u[14];
+        for (size_t i = 0; i < 14; i++) {
+            if (v[i] > 0xFFFFFFFFull) throw std::invalid_argument("convolution geometry: extent out of range");
+            u[i] = (uint32_t)v[i];
+        }
+        return cofhe_hip_conv2d_geometry{u[0], u[1], u[2], u[3], u[4], u[5], u[6], u[7], u[8], u[9], u[10], u[11], u[12], u[13]};
     }
     static bool try_put(const Mpz &v, uint32_t *dst, size_t words) {
         if (v.nbits() > words * 32) return false;

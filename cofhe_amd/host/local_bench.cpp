@@ -715,6 +715,99 @@ static void bench_conv2d(size_t B, size_t H, size_t W, size_t C, size_t kh, size
     if (!ok) throw std::runtime_error("convolution mismatch");
 }
 
+// the same with dilation and groups: filters kh x kw x C/G x Co, output column co reads the channels of group co / (Co / G)
+static void bench_conv2d_grouped(size_t B, size_t H, size_t W, size_t C, size_t kh, size_t kw, size_t Co, size_t G, size_t dh, size_t dw, size_t sh,
+                                 size_t sw, size_t ph, size_t pw) {
+    if (G == 0 || C % G || Co % G) throw std::invalid_argument("conv2d_grouped: groups must divide C and Co");
+    auto cs = make_cryptosystem(128, 128, Device::GPU);
+    using CS = decltype(cs);
+    auto sk = cs.keygen();
+    auto pk = cs.keygen(sk);
+    const size_t Cg = C / G, Cog = Co / G;
+    auto xval = [](size_t i) { return (float)(i % 11) - 4.0f; };
+    auto wval = [](size_t i) { return (float)(i % 7) - 3.0f; };               // weights of both signs, zeros among them
+    Tensor<CS::PlainText *> x({B, H, W, C}, nullptr), w({kh, kw, Cg, Co}, nullptr);
+    for (size_t i = 0; i < x.num_elements(); i++) x[i] = new CS::PlainText(cs.make_plaintext(xval(i)));
+    for (size_t i = 0; i < w.num_elements(); i++) w[i] = new CS::PlainText(cs.make_plaintext(wval(i)));
+    auto cx = cs.encrypt_tensor(pk, x);
+    Benchmark b("conv2d_grouped (plaintext filters in groups over a ciphertext image)");
+    bool ok = true;
+    std::vector<size_t> oshape;
+    b.run([&]() {
+        auto res = cs.conv2d_plaintext_ciphertext_tensors(pk, w, cx, {sh, sw}, {ph, pw}, {dh, dw}, G);
+        oshape = res.shape();
+        auto dec = cs.decrypt_tensor(sk, res);
+        const size_t Ho = oshape[1], Wo = oshape[2];
+        for (size_t bb = 0; bb < B; bb++)
+            for (size_t oy = 0; oy < Ho; oy++)
+                for (size_t ox = 0; ox < Wo; ox++)
+                    for (size_t co = 0; co < Co; co++) {
+                        float want = 0;
+                        for (size_t dy = 0; dy < kh; dy++)
+                            for (size_t dx = 0; dx < kw; dx++) {
+                                const size_t y = oy * sh + dy * dh, xx = ox * sw + dx * dw;
+                                if (y < ph || y - ph >= H || xx < pw || xx - pw >= W) continue;
+                                for (size_t ci = 0; ci < Cg; ci++)
+                                    want += xval(((bb * H + (y - ph)) * W + (xx - pw)) * C + (co / Cog) * Cg + ci) * wval(((dy * kw + dx) * Cg + ci) * Co + co);
+                            }
+                        if (cs.get_float_from_plaintext(*dec[((bb * Ho + oy) * Wo + ox) * Co + co]) != want) ok = false;
+                    }
+        free_all(res);
+        free_all(dec);
+    }, 1);
+    b.print_summary();
+    free_all(x); free_all(w); free_all(cx);
+    if (oshape.size() != 4 || oshape[0] != B || oshape[3] != Co) ok = false;
+    std::cout << "  decrypts to the grouped convolution: " << (ok ? "yes" : "NO") << std::endl;
+    std::cout << "image: " << B << "x" << H << "x" << W << "x" << C << " filters: " << kh << "x" << kw << "x" << Cg << "x" << Co << " groups: " << G
+              << " dilation: " << dh << "," << dw << " stride: " << sh << "," << sw << " pad: " << ph << "," << pw
+              << " out: " << (oshape.size() == 4 ? oshape[1] : 0) << "x" << (oshape.size() == 4 ? oshape[2] : 0) << std::endl;
+    if (!ok) throw std::runtime_error("grouped convolution mismatch");
+}
+
+// sum pooling over kh x kw windows of an encrypted image B x H x W x C: encrypt, pool, decrypt and compare with the window sums
+static void bench_sum_pool2d(size_t B, size_t H, size_t W, size_t C, size_t kh, size_t kw, size_t sh, size_t sw, size_t ph, size_t pw) {
+    auto cs = make_cryptosystem(128, 128, Device::GPU);
+    using CS = decltype(cs);
+    auto sk = cs.keygen();
+    auto pk = cs.keygen(sk);
+    auto xval = [](size_t i) { return (float)(i % 11) - 4.0f; };
+    Tensor<CS::PlainText *> x({B, H, W, C}, nullptr);
+    for (size_t i = 0; i < x.num_elements(); i++) x[i] = new CS::PlainText(cs.make_plaintext(xval(i)));
+    auto cx = cs.encrypt_tensor(pk, x);
+    Benchmark b("sum_pool2d (window sums of a ciphertext image)");
+    bool ok = true;
+    std::vector<size_t> oshape;
+    b.run([&]() {
+        auto res = cs.sum_pool2d_ciphertext_tensor(pk, cx, {kh, kw}, {sh, sw}, {ph, pw});
+        oshape = res.shape();
+        auto dec = cs.decrypt_tensor(sk, res);
+        const size_t Ho = oshape[1], Wo = oshape[2];
+        for (size_t bb = 0; bb < B; bb++)
+            for (size_t oy = 0; oy < Ho; oy++)
+                for (size_t ox = 0; ox < Wo; ox++)
+                    for (size_t c = 0; c < C; c++) {
+                        float want = 0;
+                        for (size_t dy = 0; dy < kh; dy++)
+                            for (size_t dx = 0; dx < kw; dx++) {
+                                const size_t y = oy * sh + dy, xx = ox * sw + dx;
+                                if (y < ph || y - ph >= H || xx < pw || xx - pw >= W) continue;
+                                want += xval(((bb * H + (y - ph)) * W + (xx - pw)) * C + c);
+                            }
+                        if (cs.get_float_from_plaintext(*dec[((bb * Ho + oy) * Wo + ox) * C + c]) != want) ok = false;
+                    }
+        free_all(res);
+        free_all(dec);
+    }, 1);
+    b.print_summary();
+    free_all(x); free_all(cx);
+    if (oshape.size() != 4 || oshape[0] != B || oshape[3] != C) ok = false;
+    std::cout << "  decrypts to the window sums: " << (ok ? "yes" : "NO") << std::endl;
+    std::cout << "image: " << B << "x" << H << "x" << W << "x" << C << " window: " << kh << "x" << kw << " stride: " << sh << "," << sw << " pad: " << ph << ","
+              << pw << " out: " << (oshape.size() == 4 ? oshape[1] : 0) << "x" << (oshape.size() == 4 ? oshape[2] : 0) << std::endl;
+    if (!ok) throw std::runtime_error("sum pooling mismatch");
+}
+
 // the ciphertext x ciphertext matrix product twice on the same inputs: the reference's expansion into n m p element
 // products (2 n m p opened values) and one matrix triplet (LocalCipherTextMultiplier::set_matrix_triplets: n m + m p)
 static void bench_ciphertext_matmul_matrix(size_t n, size_t m, size_t p, size_t t, size_t parties) {
@@ -950,7 +1043,7 @@ static void plaintexts_mode(const char *in, const char *out) {
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        std::cerr << "Usage: " << argv[0] << " <encrypt_decrypt|ciphertext_matadd|scal_matmul|threshold|ciphertext_matmul|fresh_randomness|affine|beaver_direct|plain_ct_matmul|ciphertext_matmul_matrix|conv2d> [sizes]" << std::endl;
+        std::cerr << "Usage: " << argv[0] << " <encrypt_decrypt|ciphertext_matadd|scal_matmul|threshold|ciphertext_matmul|fresh_randomness|affine|beaver_direct|plain_ct_matmul|ciphertext_matmul_matrix|conv2d|conv2d_grouped|sum_pool2d> [sizes]" << std::endl;
         return 1;
     }
     std::string mode = argv[1];
@@ -978,6 +1071,17 @@ int main(int argc, char **argv) {
             auto arg = [&](int i, size_t dflt) { return argc > i ? std::stoul(argv[i]) : dflt; };
             const size_t kh = arg(6, 3), kw = arg(7, 3);
             bench_conv2d(arg(2, 1), arg(3, 6), arg(4, 6), arg(5, 2), kh, kw, arg(8, 2), arg(9, 1), arg(10, 1), arg(11, kh / 2), arg(12, kw / 2));
+        } else if (mode == "conv2d_grouped") {
+            // B H W C kh kw Co groups [dh dw sh sw ph pw]; by default no dilation, stride 1 and "same" padding
+            auto arg = [&](int i, size_t dflt) { return argc > i ? std::stoul(argv[i]) : dflt; };
+            const size_t kh = arg(6, 3), kw = arg(7, 3), dh = arg(10, 1), dw = arg(11, 1);
+            bench_conv2d_grouped(arg(2, 1), arg(3, 6), arg(4, 6), arg(5, 4), kh, kw, arg(8, 4), arg(9, 4), dh, dw, arg(12, 1), arg(13, 1),
+                                 arg(14, (kh - 1) * dh / 2), arg(15, (kw - 1) * dw / 2));
+        } else if (mode == "sum_pool2d") {
+            // B H W C kh kw [sh sw ph pw]; by default the stride is the window and there is no padding
+            auto arg = [&](int i, size_t dflt) { return argc > i ? std::stoul(argv[i]) : dflt; };
+            const size_t kh = arg(6, 2), kw = arg(7, 2);
+            bench_sum_pool2d(arg(2, 1), arg(3, 6), arg(4, 6), arg(5, 2), kh, kw, arg(8, kh), arg(9, kw), arg(10, 0), arg(11, 0));
         } else if (mode == "ciphertext_matmul_matrix") {
             size_t n = argc > 2 ? std::stoul(argv[2]) : 4, m = argc > 3 ? std::stoul(argv[3]) : 4,
                    p = argc > 4 ? std::stoul(argv[4]) : 4, t = argc > 5 ? std::stoul(argv[5]) : 0,

@@ -17,6 +17,8 @@
  *                                    triplet (include/smpc/ciphertext_multiplications.hpp:51-111 expands into elements)
  *   cofhe_hip_conv2d_plain_ct_...    nothing: the reference has no convolution; with it, plaintext filters over an encrypted image
  *                                    are a patch matrix built by the caller and the 2-D branch above
+ *   cofhe_hip_conv2d_grouped_...,    nothing: the same with dilation and groups (depthwise filters, per-channel scales), and sum
+ *   cofhe_hip_sum_pool2d_...         pooling as the depthwise convolution with filters of ones
  *   cofhe_hip_decrypt_records        decrypt_tensor's per-element work, cpu_cryptosystem_tensor_ops.inl:21-33
  *   cofhe_hip_part_decrypt_records,  part_decrypt_tensor / combine_part_decryption_results_tensor,
  *   cofhe_hip_combine_part_...       cpu_cryptosystem_tensor_ops.inl:35-73 (cpu_cryptosystem_distributed.inl:231-285)
@@ -91,8 +93,9 @@ int cofhe_hip_trim(cofhe_hip_ctx *ctx, size_t keep_bytes);
  *   "matmul_segments"  >= 1: pieces the inner dimension is cut into when the product has few outputs
  *   "comb_width"       2..10: window width of the fixed-base comb (cofhe_hip_pow_fixed_base_many_records and kin)
  *   "comb_chunk"       >= 1: items per pass of the comb (capped where the 4 GiB workspace bound needs it)
- *   "conv_route"       cofhe_hip_conv2d_plain_ct_records: 0 the launcher decides, 1 the direct route wherever it does not
- *                      decline, 2 the gather route
+ *   "conv_route"       cofhe_hip_conv2d_plain_ct_records, cofhe_hip_conv2d_grouped_plain_ct_records and
+ *                      cofhe_hip_sum_pool2d_records: 0 the launcher decides, 1 the direct route wherever it does not decline, 2 the
+ *                      gather route (with groups: wherever its dense patch matrix fits)
  *   "conv_chunk_rows"  >= 1: output positions per chunk of the convolution's direct route, taken as given (no rounding to a
  *                      multiple of 16, no decline for being small): how a test reaches several chunks and workgroups that
  *                      mix tree elements
@@ -105,7 +108,8 @@ int cofhe_hip_trim(cofhe_hip_ctx *ctx, size_t keep_bytes);
  *                      "k_pow_shared_solo" | "k_pow_shared" (ladders; "k_spread_records" when a
  *                      tensor's shared c1 ran one ladder), "k_decrypt3" | "k_decrypt", "k_conv_level0" (one per chunk of the
  *                      convolution's direct route; "k_tree_level" counts the levels above) | "k_gather_patches" (its
- *                      gather route) -- what a test reads to see which route a call took
+ *                      gather route, after "k_expand_group_filters" when the convolution has groups) -- what a test reads to see
+ *                      which route a call took
  * The results do not depend on them; tests pin them to drive every width through the parity checker. */
 int cofhe_hip_ctx_set_option(cofhe_hip_ctx *ctx, const char *name, int64_t value);
 int cofhe_hip_profile_read(cofhe_hip_ctx *ctx, const char *kernel, float *total_ms, uint32_t *launches, int clear);
@@ -188,8 +192,8 @@ int cofhe_hip_matmul_plain_ct_records(cofhe_hip_ctx *ctx, const void *d_s, const
  * COFHE_HIP_EINVAL, nothing written: a stride of 0; ph >= kh or pw >= kw; kh > H + 2 ph or kw > W + 2 pw; m >= 2^21; B H W C
  * above 2^31 - 1, n above 2^32 - 1, n m above 2^40 or 2 n p records beyond the launch limit; d_out overlapping d_w, d_cts or
  * d_zero.  B Ho Wo Co == 0: nothing to do.  NOT purely stream-ordered: as cofhe_hip_scal_matmul_records, the call synchronises
- * `stream` once or twice.  Not covered: dilation, groups / depthwise filters, ciphertext filters, and a per-channel bias, which
- * is cofhe_hip_add_plain_records on the result. */
+ * `stream` once or twice.  Dilation and groups / depthwise filters: cofhe_hip_conv2d_grouped_plain_ct_records below.  Not
+ * covered: ciphertext filters, and a per-channel bias, which is cofhe_hip_add_plain_records on the result. */
 typedef struct {
     uint32_t B, H, W, C;       /* image */
     uint32_t kh, kw, Co;       /* filters: kh x kw x C x Co */
@@ -199,6 +203,39 @@ typedef struct {
 int cofhe_hip_conv2d_out_shape(const cofhe_hip_conv2d_shape *shape, uint32_t *Ho, uint32_t *Wo);
 int cofhe_hip_conv2d_plain_ct_records(cofhe_hip_ctx *ctx, const void *d_w, const void *d_cts, const void *d_zero, void *d_out,
                                       const cofhe_hip_conv2d_shape *shape, void *stream);
+/* The same convolution with dilation and groups:
+ *   filters d_w [kh, kw, C / groups, Co];  with Cg = C / groups, Cog = Co / groups,
+ *   out[b,oy,ox,co] = zero o prod_{dy,dx,ci<Cg} cts[b, oy sh + dy dh - ph, ox sw + dx dw - pw, (co / Cog) Cg + ci] ^ w[dy,dx,ci,co],
+ * Ho = (H + 2 ph - ((kh - 1) dh + 1)) / sh + 1 and Wo likewise.  groups = C = Co is a depthwise convolution; kh = kw = 1 on top of
+ * that a per-channel scale (a folded batch norm).  dh = dw = groups = 1 is cofhe_hip_conv2d_plain_ct_records, launch for launch.
+ * The matrix view has m = kh kw C / groups: the digits, the segment scans, the filter upload and the 2^21 limit are those of the
+ * grouped filter, not of the block-diagonal dense one.  The direct route reads each leaf from the channel block of its column's
+ * group (a segment of the product tree belongs to one column).  The gather route expands the filters to the dense
+ * [kh, kw, C, Co] tensor in a block of the block cache ("k_expand_group_filters") and runs unchanged; it needs kh kw C < 2^21 and
+ * n kh kw C <= 2^40 -- where that does not hold the direct route is forced, and if the direct route then declines the call
+ * returns COFHE_HIP_EINVAL and says so.  With groups > 1 the automatic choice is the direct route wherever it does not decline.
+ * Further COFHE_HIP_EINVAL, nothing written, checked before the context or a pointer is looked at: a dilation of 0; groups of 0;
+ * C or Co not a multiple of groups; with keff = (k - 1) d + 1 in place of k in the refusals above: padding not smaller than keff,
+ * keff beyond the padded extent.  A dilated window may lie wholly in the padding: legal, and its outputs are zero.  The overlap
+ * check of d_out uses the grouped filter size. */
+typedef struct {
+    uint32_t B, H, W, C;       /* image */
+    uint32_t kh, kw, Co;       /* filters: kh x kw x C / groups x Co */
+    uint32_t sh, sw, ph, pw;   /* strides, zero padding (rows, columns) */
+    uint32_t dh, dw, groups;   /* dilation (rows, columns), groups */
+} cofhe_hip_conv2d_geometry;
+/* host only, no GPU: validates the geometry (COFHE_HIP_EINVAL for every refusal) and gives the output extents */
+int cofhe_hip_conv2d_geometry_out_shape(const cofhe_hip_conv2d_geometry *geometry, uint32_t *Ho, uint32_t *Wo);
+int cofhe_hip_conv2d_grouped_plain_ct_records(cofhe_hip_ctx *ctx, const void *d_w, const void *d_cts, const void *d_zero, void *d_out,
+                                              const cofhe_hip_conv2d_geometry *geometry, void *stream);
+/* Sum pooling: out[b,oy,ox,c] = zero o prod_{dy,dx} cts[b, oy sh + dy dh - ph, ox sw + dx dw - pw, c], the depthwise convolution
+ * with [kh, kw, 1, C] filters of ones, which are made on the device in a block of the block cache.  geometry->Co and
+ * geometry->groups are ignored and taken as C.  Exponents of one bit build no table, so an output costs kh kw - 1 compositions
+ * per record and the one with zero.  Average pooling is this with the scale 1 / (kh kw) folded into the next layer's plaintext
+ * weights: the inverse of kh kw does not exist mod 2^k for an even window.  Refusals, routes and synchronisation as
+ * cofhe_hip_conv2d_grouped_plain_ct_records. */
+int cofhe_hip_sum_pool2d_records(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_zero, void *d_out,
+                                 const cofhe_hip_conv2d_geometry *geometry, void *stream);
 /* out[i,k] = sum_j a[i,j] b[j,k] mod 2^kbits on exponent records (a n x m, b m x p, out n x p; 32 words each: 31 of
  * magnitude and a sign word).  Negative inputs count as -mag mod 2^k and magnitudes of 2^k and above are reduced first; the
  * outputs lie in [0, 2^k) with sign word 0.  1 <= kbits <= 639 (the bound of the decryption table), any kbits in that range:
@@ -313,6 +350,9 @@ int cofhe_hip_time_compose(cofhe_hip_ctx *ctx, const void *d_a, const void *d_b,
  *                         cofhe_hip_conv2d_plain_ct_records: "table" is B H W C 2 2^(w-2) 672 bytes -- the image, not the patches;
  *                         empty at w = 2, where the image itself is the table; the other regions as "scal_matmul_tree" with
  *                         m = kh kw C, p = Co)
+ *      "conv2d_grouped"   args: B, H, W, C, kh, kw, Co, sh, sw, ph, pw, dh, dw, groups, exp_bits, w   (the direct route of
+ *                         cofhe_hip_conv2d_grouped_plain_ct_records: the table of "conv2d"; the other regions as
+ *                         "scal_matmul_tree" with m = kh kw C / groups, p = Co)
  *      "accumulate_tree"  args: n, m, p
  *      "encrypt_chunk"    args: n_elements, kbits
  *      "fixed_base"       args: n_powers, max_entries
@@ -384,6 +424,14 @@ int cofhe_hip_matmul_plain_ct_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *s
 int cofhe_hip_conv2d_plain_ct_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *w, size_t lw, const uint8_t *cts, size_t lc,
                                             const uint8_t *zero, size_t lz, uint32_t sh, uint32_t sw, uint32_t ph, uint32_t pw,
                                             uint8_t **out, size_t *outlen);
+/* the serialised twin of cofhe_hip_conv2d_grouped_plain_ct_records: w is the plaintext tensor [kh, kw, C / groups, Co];
+ * COFHE_HIP_ESHAPE when an operand is not 4-D or w.shape[2] != cts.shape[3] / groups */
+int cofhe_hip_conv2d_grouped_plain_ct_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *w, size_t lw, const uint8_t *cts, size_t lc,
+                                                    const uint8_t *zero, size_t lz, uint32_t sh, uint32_t sw, uint32_t ph, uint32_t pw,
+                                                    uint32_t dh, uint32_t dw, uint32_t groups, uint8_t **out, size_t *outlen);
+/* the serialised twin of cofhe_hip_sum_pool2d_records over kh x kw windows: cts [B, H, W, C] -> [B, Ho, Wo, C] */
+int cofhe_hip_sum_pool2d_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *cts, size_t lc, const uint8_t *zero, size_t lz, uint32_t kh,
+                                       uint32_t kw, uint32_t sh, uint32_t sw, uint32_t ph, uint32_t pw, uint8_t **out, size_t *outlen);
 /* s: plaintext tensor; 1-D x 1-D -> element-wise, 2-D x 2-D -> matmul (zero: 1-element tensor) */
 int cofhe_hip_scal_ciphertext_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *s, size_t ls,
                                             const uint8_t *cts, size_t lc, const uint8_t *zero, size_t lz,

@@ -2,7 +2,9 @@
 gpurun; one JSON line per operation, copied to profiles/).  Sizes follow SURVEY.md section 8(d):
 C2 matadd 128x128, C3 scal_matmul 256^3 (ramp exponents) and with 128-bit exponents (smaller n),
 C5 matadd 1024x1024, 1-D scal with k-bit exponents, negation, decryption, threshold decryption,
-accumulation of the ct x ct product."""
+accumulation of the ct x ct product.  --conv-only: only the depthwise convolution and the sum pooling, each against the
+block-diagonal dense filter through the ungrouped entry (the way these layers were written before the convolution had groups),
+the two alternating in one run; --out FILE also writes those lines to FILE."""
 import json
 import os
 import sys
@@ -52,6 +54,62 @@ def dev_i32(a):
 def fresh(n):
     return encrypt_tensor_gpu(eng, torch, prm, [rng.bits(K) for _ in range(n)], rng.bits(960), dev)
 
+
+# ---- depthwise convolution and sum pooling against the block-diagonal dense filter -------------------------------------------
+def conv_groups_ops(runs=5):
+    """"conv2d_depthwise": a 3 x 3 depthwise layer over (1, 28, 28, 64), pad 1, int8 weights; "sum_pool2d": 2 x 2 windows at stride 2
+    over the same image.  Each against the dense [kh, kw, C, C] filter that is zero outside the diagonal through
+    conv2d_plain_ct_records without groups, which gives the same records (checked).  Alternating, `runs` windows each (a quarter of a second of calls
+    or more per window) after a warm-up of both; the median and the extremes of each, and the ratio of the medians"""
+    image = (1, 28, 28, 64)
+    C_ = image[3]
+    cts, zero = fresh(int(np.prod(image))), fresh(1)
+    lines = []
+    for op, kernel, stride, pad, ones in (("conv2d_depthwise", (3, 3), (1, 1), (1, 1), False), ("sum_pool2d", (2, 2), (2, 2), (0, 0), True)):
+        taps = kernel[0] * kernel[1]
+        wg = [1] * (taps * C_) if ones else [int(rng.bits(8)) - 128 for _ in range(taps * C_)]
+        dense = [wg[t * C_ + co] if ci == co else 0 for t in range(taps) for ci in range(C_) for co in range(C_)]
+        dwg, dwd = dev_i32(exp_records(wg)), dev_i32(exp_records(dense))
+        ho, wo = eng.conv2d_out_shape(image, (*kernel, 1, C_), stride, pad, (1, 1), C_)
+        out_g = torch.zeros(ho * wo * C_ * 336, dtype=torch.int32, device=dev)
+        out_d = torch.zeros_like(out_g)
+        if ones:
+            grouped = lambda: eng.sum_pool2d_records(cts.data_ptr(), zero.data_ptr(), out_g.data_ptr(), image, kernel, stride, pad)  # noqa: E731
+        else:
+            grouped = lambda: eng.conv2d_plain_ct_records(dwg.data_ptr(), cts.data_ptr(), zero.data_ptr(), out_g.data_ptr(), image,  # noqa: E731
+                                                          (*kernel, 1, C_), stride, pad, groups=C_)
+        dense_fn = lambda: eng.conv2d_plain_ct_records(dwd.data_ptr(), cts.data_ptr(), zero.data_ptr(), out_d.data_ptr(), image,  # noqa: E731
+                                                       (*kernel, C_, C_), stride, pad)
+        for route in (0, 1, 2):
+            eng.set_option("conv_route", route)
+            grouped(), dense_fn()
+            torch.cuda.synchronize()
+            same = bool(torch.equal(out_g, out_d))
+            # enough calls per timed window for a quarter of a second of work, from one call of each timed alone
+            rg, rd = (max(3, int(0.25 / timed(fn)) + 1) for fn in (grouped, dense_fn))
+            tg, td = [], []
+            for _ in range(runs):
+                tg.append(timed(grouped, reps=rg))
+                td.append(timed(dense_fn, reps=rd))
+            eng.set_option("conv_route", 0)
+            med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+            d = {"op": op, "image": list(image), "kernel": list(kernel), "stride": list(stride), "pad": list(pad), "conv_route": route,
+                 "grouped_ms": round(med(tg) * 1e3, 3), "grouped_ms_min_max": [round(min(tg) * 1e3, 3), round(max(tg) * 1e3, 3)],
+                 "dense_block_diagonal_ms": round(med(td) * 1e3, 3), "dense_ms_min_max": [round(min(td) * 1e3, 3), round(max(td) * 1e3, 3)],
+                 "dense_over_grouped": round(med(td) / med(tg), 3), "same_records": same, "runs": runs, "calls_per_window": [rg, rd], "device_status": eng.device_status()}
+            print(json.dumps(d), flush=True)
+            lines.append(d)
+    return lines
+
+
+if "--conv-only" in sys.argv:
+    res = conv_groups_ops()
+    if "--out" in sys.argv:
+        path = sys.argv[sys.argv.index("--out") + 1]
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as fh:
+            json.dump(res, fh, indent=1)
+    sys.exit(0 if all(r["same_records"] and r["device_status"] == 0 for r in res) else 1)
 
 # ---- matadd C2 / C5 ---------------------------------------------------------------------------
 for side in ((128,) if (QUICK or "big" in SKIP) else (128, 1024)):
@@ -231,3 +289,6 @@ for (n, m, p, kind) in shapes:
     emit("scal_ciphertext_tensors 2-D, %s exponents" % kind, [n, m, p], sec, n * p, "output-ciphertexts/s",
          macs_per_s=round(n * m * p / sec, 1), kernel="k_wnaf_digits + k_pow_table + k_scal_matmul_wnaf")
     del cts, out
+
+# ---- depthwise convolution, sum pooling -----------------------------------------------------------
+conv_groups_ops(runs=3)
