@@ -1,8 +1,8 @@
 // abi.hip -- the C ABI of include/cofhe_hip.h, in this order: the context, the block cache, the launch helpers (spans, the
 // two-build launch, flag words, the table-cache lookup), the workspace plans, the launchers (one launch site per kernel and
 // route; product_tree is the pairwise tree of them all) and the host-side tensor formats.  The kernels are declared in
-// kernels.hpp and defined in cofhe_hip.hip, wide.hip, comb.hip, affine.hip, matmul_left.hip and conv.hip; this file holds no device code
-// of its own.  conv.hip holds the three kernels of the convolution.
+// kernels.hpp and defined in cofhe_hip.hip, wide.hip, comb.hip, affine.hip, matmul_left.hip, conv.hip and pow_dot.hip; this file holds
+// no device code of its own.  conv.hip holds the three kernels of the convolution, pow_dot.hip the two of the polynomial evaluation.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -18,6 +18,7 @@
 #include "kernels.hpp"
 #include "conv.hpp"
 #include "plain_mm.hpp"
+#include "poly_shift.hpp"
 
 using namespace cofhe;
 using namespace cofhe_k;
@@ -1641,6 +1642,75 @@ int cofhe_hip_matmul_plain_plain_records(cofhe_hip_ctx *ctx, const void *d_a, co
     return COFHE_HIP_OK;
 }
 
+// ---- polynomial evaluation from one opened value (pow_dot.hip) -------------------------------------------------------------
+static_assert(COFHE_HIP_POLY_MAX_DEGREE == POLY_MAX_DEGREE, "the header's bound is the kernel's");
+// touches no shared state of the context (no workspace, no table, no flag word): no lock
+int cofhe_hip_pow_dot_records(cofhe_hip_ctx *ctx, const void *d_bases, const void *d_exps, void *d_out, uint64_t n_ct, uint32_t d, void *stream) {
+    if (d == 0 || d > (uint32_t)POLY_MAX_DEGREE) return fail(COFHE_HIP_EINVAL, "pow_dot: 1 <= d <= 8 bases per record");
+    if (n_ct == 0) return COFHE_HIP_OK;
+    if (!d_bases || !d_exps || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
+    if (n_ct > (1ull << 36)) return fail(COFHE_HIP_EINVAL, "work size out of range");
+    const size_t out_bytes = (size_t)n_ct * 2 * REC_WORDS * 4, exp_bytes = (size_t)n_ct * EXP_REC_WORDS * 4;
+    // k_pow_dot keeps the running product in the output record
+    if (overlaps(d_out, out_bytes, d_bases, d * out_bytes) || overlaps(d_out, out_bytes, d_exps, d * exp_bytes))
+        return fail(COFHE_HIP_EINVAL, "pow_dot: the output overlaps an input");
+    unsigned blocks;
+    if (int rc = compose_blocks(2 * n_ct, &blocks)) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    {
+        ProfScope ps(ctx, "k_pow_dot", st);
+        hipLaunchKernelGGL(k_pow_dot, dim3(blocks), dim3(WG_BLOCK), 0, st, (const uint32_t *)d_bases, (const uint32_t *)d_exps, (uint32_t *)d_out,
+                           n_ct, d, (const uint32_t *)ctx->d_one, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+    }
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+
+int cofhe_hip_poly_shift_records(cofhe_hip_ctx *ctx, const void *d_coef, const void *d_x, void *d_q, uint64_t n, uint32_t d, uint32_t kbits,
+                                 void *stream) {
+    if (kbits == 0 || kbits > 32u * PMM_MAX_LIMBS || 2 * kbits + 1 > (uint32_t)PLIMBS * 32) return fail(COFHE_HIP_EINVAL, "k out of range");
+    if (d > (uint32_t)POLY_MAX_DEGREE) return fail(COFHE_HIP_EINVAL, "poly_shift: degree beyond 8");
+    if (n == 0) return COFHE_HIP_OK;
+    if (!d_coef || !d_x || !d_q) return fail(COFHE_HIP_EINVAL, "null argument");
+    const uint64_t blocks = (n + PSH_THREADS - 1) / PSH_THREADS;
+    if (blocks > 0x7FFFFFFFull) return fail(COFHE_HIP_EINVAL, "work size out of range");
+    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4;
+    if (overlaps(d_q, (size_t)(d + 1) * n * exp_bytes, d_coef, (size_t)(d + 1) * exp_bytes) || overlaps(d_q, (size_t)(d + 1) * n * exp_bytes, d_x, n * exp_bytes))
+        return fail(COFHE_HIP_EINVAL, "poly_shift: the output overlaps an input");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    {
+        ProfScope ps(ctx, "k_poly_shift", st);
+        hipLaunchKernelGGL(k_poly_shift, dim3((unsigned)blocks), dim3(PSH_THREADS), 0, st, (const uint32_t *)d_coef, (const uint32_t *)d_x,
+                           (uint32_t *)d_q, n, d, kbits);
+    }
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+
+// Needs no workspace plan of its own: the d + 1 exponent tensors q_0 .. q_d are one block of the block cache, and the plaintext
+// addend that closes the call carves the workspace by the plan "comb" (kind 3).
+int cofhe_hip_poly_close_records(cofhe_hip_ctx *ctx, const void *d_coef, const void *d_e, const void *d_powers, const uint32_t *f_record,
+                                 void *d_out, uint64_t n_ct, uint32_t d, uint32_t kbits, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (d == 0 || d > (uint32_t)POLY_MAX_DEGREE) return fail(COFHE_HIP_EINVAL, "poly_close: 1 <= d <= 8");
+    if (kbits > 32u * PMM_MAX_LIMBS) return fail(COFHE_HIP_EINVAL, "k out of range");
+    if (int rc = comb_check(3, n_ct, 0, kbits, 0, 0)) return rc;
+    if (n_ct == 0) return COFHE_HIP_OK;
+    if (!d_coef || !d_e || !d_powers || !f_record || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
+    const size_t out_bytes = (size_t)n_ct * 2 * REC_WORDS * 4, exp_bytes = (size_t)EXP_REC_WORDS * 4;
+    if (overlaps(d_out, out_bytes, d_powers, d * out_bytes) || overlaps(d_out, out_bytes, d_coef, (d + 1) * exp_bytes) ||
+        overlaps(d_out, out_bytes, d_e, n_ct * exp_bytes))
+        return fail(COFHE_HIP_EINVAL, "poly_close: the output overlaps an input");
+    DevBuf q;                                     // q_0 | q_1 .. q_d, power-major
+    q.stream = stream;
+    if (int rc = q.get(ctx, (size_t)(d + 1) * n_ct * exp_bytes)) return rc;
+    if (int rc = cofhe_hip_poly_shift_records(ctx, d_coef, d_e, q.p, n_ct, d, kbits, stream)) return rc;
+    if (int rc = cofhe_hip_pow_dot_records(ctx, d_powers, (const uint8_t *)q.p + n_ct * exp_bytes, d_out, n_ct, d, stream)) return rc;
+    return cofhe_hip_add_plain_records(ctx, d_out, q.p, nullptr, nullptr, nullptr, f_record, d_out, n_ct, kbits, 0, stream);
+}
+
 namespace {
 // the table f^(-2^j), j < k, of the decryption kernels (built on first use, cached in the context)
 int ensure_ftab(cofhe_hip_ctx *ctx, const uint32_t *f_record, uint32_t kbits, void *stream) {
@@ -2234,6 +2304,26 @@ int cofhe_hip_conv2d_grouped_plain_ct_tensors_bytes(cofhe_hip_ctx *ctx, const ui
 int cofhe_hip_sum_pool2d_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *cts, size_t lc, const uint8_t *zero, size_t lz, uint32_t kh, uint32_t kw,
                                        uint32_t sh, uint32_t sw, uint32_t ph, uint32_t pw, uint8_t **out, size_t *outlen) {
     return conv2d_bytes(ctx, nullptr, 0, cts, lc, zero, lz, cofhe_hip_conv2d_geometry{0, 0, 0, 0, kh, kw, 0, sh, sw, ph, pw, 1, 1, 1}, out, outlen);
+}
+
+int cofhe_hip_poly_close_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *coef, size_t lcoef, const uint8_t *e, size_t le, const uint8_t *powers,
+                                       size_t lp, const uint32_t *f_record, uint32_t kbits, uint8_t **out, size_t *outlen) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    uint32_t ndk, nde, ndp, sk[8], se[8], sp[8];
+    uint64_t nk, ne, nr;
+    HIPCHK(hipSetDevice(ctx->device));
+    DevBuf dk, de, dp, dout;
+    if (int rc = load_tensor(ctx, coef, lcoef, 0, dk, &ndk, sk, &nk)) return rc;
+    if (int rc = load_tensor(ctx, e, le, 0, de, &nde, se, &ne)) return rc;
+    if (int rc = load_tensor(ctx, powers, lp, 2, dp, &ndp, sp, &nr)) return rc;
+    if (ndk != 1 || nk < 2 || nk > (uint64_t)POLY_MAX_DEGREE + 1)
+        return fail(COFHE_HIP_ESHAPE, "poly_close: the coefficients are a 1-D plaintext tensor of 2 to 9 elements");
+    const uint32_t d = (uint32_t)nk - 1;
+    if (ndp != nde + 1 || sp[0] != d || memcmp(sp + 1, se, 4 * nde) != 0 || nr != 2 * ne * d)
+        return fail(COFHE_HIP_ESHAPE, "poly_close: the powers are a ciphertext tensor [d, shape of e]");
+    if (int rc = dout.get(ctx, ne ? ne * 2 * REC_WORDS * 4 : 4)) return rc;
+    if (int rc = cofhe_hip_poly_close_records(ctx, dk.p, de.p, dp.p, f_record, dout.p, ne, d, kbits, nullptr)) return rc;
+    return finish(ctx, dout, 2 * ne, nde, se, out, outlen);
 }
 
 }  // extern "C"

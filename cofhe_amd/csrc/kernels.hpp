@@ -3,7 +3,8 @@
 // (the latency kernels); wire.hip launches its own kernels.  A declaration that matches no definition is an
 // undefined symbol when the library is loaded (tests/test_cabi.py).  comb.hip holds the two kernels of the fixed-base comb,
 // affine.hip the ciphertext difference and the record inverse, matmul_left.hip the record transpose and the plaintext
-// matrix product, conv.hip the convolution's level 0, its patch gather and its filter expansion.
+// matrix product, conv.hip the convolution's level 0, its patch gather and its filter expansion, pow_dot.hip the multi-exponentiation
+// and the Taylor shift of the polynomial evaluation.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -144,4 +145,12 @@ __global__ void k_gather_patches(cofhe::ConvShape s, const uint32_t *__restrict_
                                  uint32_t *__restrict__ out, uint32_t n, uint32_t m, uint32_t vec16);
 __global__ void k_expand_group_filters(const uint32_t *__restrict__ w, uint32_t *__restrict__ dense, uint32_t taps, uint32_t C, uint32_t Co,
                                        uint32_t groups, uint32_t vec16);
+
+// polynomial evaluation from one opened value (pow_dot.hip; pow_dot.hpp, poly_shift.hpp): out[2e+h] = prod_{i<d} bases[(i n_ct + e) 2 + h]
+// ^ exps[i n_ct + e] by one ladder per record whose squarings the d bases share, and the Taylor shift q[i n + e] =
+// sum_{j>=i} C(j,i) coef[j] x[e]^(j-i) mod 2^kbits on exponent records, one thread per element
+__global__ void k_pow_dot(const uint32_t *__restrict__ bases, const uint32_t *__restrict__ exps, uint32_t *__restrict__ out, uint64_t n_ct, uint32_t d,
+                          const uint32_t *__restrict__ one_rec, const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status);
+__global__ void k_poly_shift(const uint32_t *__restrict__ coef, const uint32_t *__restrict__ x, uint32_t *__restrict__ q, uint64_t n, uint32_t d,
+                             uint32_t kbits);
 }  // namespace cofhe_k

@@ -112,6 +112,19 @@ class Engine:
                                                          C.byref(out), C.byref(n)))
         return self._take(out, n)
 
+    def poly_close_tensors(self, coef: bytes, e: bytes, powers: bytes, f_record, kbits: int) -> bytes:
+        """coef (plaintext tensor [d + 1]), e (plaintext tensor of the opened values x - a) and powers (ciphertext tensor
+        [d, shape of e] of the power tuples [a^i]) -> the ciphertext tensor of p(x), of e's shape; f_record: host uint32[168]"""
+        import numpy as np
+        f = np.ascontiguousarray(f_record, dtype=np.uint32)
+        assert f.size == 168
+        out = C.POINTER(C.c_uint8)()
+        n = C.c_size_t()
+        _chk(self.L.cofhe_hip_poly_close_tensors_bytes(self.ctx, C.c_char_p(coef), C.c_size_t(len(coef)), C.c_char_p(e), C.c_size_t(len(e)),
+                                                       C.c_char_p(powers), C.c_size_t(len(powers)), f.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                       C.c_uint32(kbits), C.byref(out), C.byref(n)))
+        return self._take(out, n)
+
     def scal_ciphertext_tensors(self, s: bytes, cts: bytes, zero: bytes = None) -> bytes:
         out = C.POINTER(C.c_uint8)()
         n = C.c_size_t()
@@ -332,6 +345,29 @@ class Engine:
         _chk(self.L.cofhe_hip_matmul_plain_plain_records(self.ctx, C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_out),
                                                          C.c_uint32(n), C.c_uint32(m), C.c_uint32(p), C.c_uint32(kbits),
                                                          C.c_void_p(stream)))
+
+    def pow_dot_records(self, d_bases, d_exps, d_out, n_ciphertexts, d, stream=0):
+        """out[e] = prod_{i<d} bases[i][e]^exps[i][e]: d ciphertext tensors and d exponent tensors of n elements, power-major,
+        one ladder per record with shared squarings (1 <= d <= 8); d_out must not overlap an input"""
+        _chk(self.L.cofhe_hip_pow_dot_records(self.ctx, C.c_void_p(d_bases), C.c_void_p(d_exps), C.c_void_p(d_out),
+                                              C.c_uint64(n_ciphertexts), C.c_uint32(d), C.c_void_p(stream)))
+
+    def poly_shift_records(self, d_coef, d_x, d_q, n, d, kbits, stream=0):
+        """q[i n + e] = sum_{j>=i} C(j,i) coef[j] x[e]^(j-i) mod 2^kbits, i <= d, on exponent records (coef: d + 1, x: n,
+        q: (d + 1) n, power-major); outputs in [0, 2^k) with sign word 0"""
+        _chk(self.L.cofhe_hip_poly_shift_records(self.ctx, C.c_void_p(d_coef), C.c_void_p(d_x), C.c_void_p(d_q), C.c_uint64(n),
+                                                 C.c_uint32(d), C.c_uint32(kbits), C.c_void_p(stream)))
+
+    def poly_close_records(self, d_coef, d_e, d_powers, f_record, d_out, n_ciphertexts, d, kbits, stream=0):
+        """the closing step of a polynomial evaluation: out[e] = (prod_{i=1..d} powers[i-1][e]^q_i(e[e])) o f^q_0(e[e]) with q the
+        Taylor shift of coef (d + 1 exponent records) at the opened values e (n exponent records); powers: d tensors [a^i],
+        power-major; f_record: host uint32[168]; d_out must not overlap an input"""
+        import numpy as np
+        f = np.ascontiguousarray(f_record, dtype=np.uint32)
+        assert f.size == 168
+        _chk(self.L.cofhe_hip_poly_close_records(self.ctx, C.c_void_p(d_coef), C.c_void_p(d_e), C.c_void_p(d_powers),
+                                                 f.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(d_out), C.c_uint64(n_ciphertexts),
+                                                 C.c_uint32(d), C.c_uint32(kbits), C.c_void_p(stream)))
 
     def decrypt_records(self, d_cts, d_sk, f_record, d_out, n_ciphertexts, kbits, stream=0):
         """f_record: host numpy uint32[168]; d_out: n * (ceil(k/32) + 1) words"""

@@ -948,6 +948,85 @@ class HIPCryptoSystem {
         return plaintext_addend(pk, ct, pt, 2);
     }
 
+    // ---- polynomials on ciphertext tensors from one opened value (cofhe_hip.h: power tuples) -----------------------------------
+    // res[e] = prod_{i<d} bases[i][e]^exps[i][e]: d ciphertext tensors and d plaintext tensors of one shape, one ladder per record
+    // whose squarings the d bases share (cofhe_hip_pow_dot_records), 1 <= d <= 8.  The reference has no such operation.
+    Tensor<CipherText *> pow_dot_ciphertext_tensors(const PublicKey &pk, const Vector<Tensor<PlainText *>> &exps,
+                                                    const Vector<Tensor<CipherText *>> &bases) const {
+        const size_t d = bases.size();
+        if (d == 0 || d > COFHE_HIP_POLY_MAX_DEGREE || exps.size() != d) throw std::invalid_argument("pow_dot_ciphertext_tensors: 1 to 8 bases, as many exponent tensors");
+        const size_t E = bases[0].num_elements();
+        std::vector<uint32_t> ex(d * E * EXPW, 0);
+        for (size_t i = 0; i < d; i++) {
+            if (exps[i].num_elements() != E) throw std::invalid_argument("Tensor shapes must be equal");
+            for (size_t e = 0; e < E; e++) pack_exponent(*exps[i][e], &ex[(i * E + e) * EXPW]);
+        }
+        DeviceTensor db = stack(bases);
+        void *dex = nullptr;
+        check(cofhe_hip_malloc(ctx_, ex.size() * 4 + 4, &dex)); Guard g1{ctx_, dex};
+        check(cofhe_hip_upload(ctx_, dex, ex.data(), ex.size() * 4, nullptr));
+        DeviceTensor out = alloc(bases[0].is_zero_degree() ? std::vector<size_t>{1} : bases[0].shape(), E);
+        check(cofhe_hip_pow_dot_records(ctx_, db.ptr_, dex, out.ptr_, E, (uint32_t)d, nullptr));
+        check(cofhe_hip_stream_sync(ctx_, nullptr));          // `ex` goes with this frame
+        rerandomize_result(pk, out);
+        return download(std::move(out));
+    }
+    // the Taylor shift of p = sum_j coef[j] X^j at every x[e] mod 2^k: d + 1 tensors of x's shape, res[i][e] = q_i(x[e]) =
+    // sum_{j>=i} C(j,i) coef[j] x[e]^(j-i) (cofhe_hip_poly_shift_records); res[0] is p(x)
+    Vector<Tensor<PlainText *>> poly_shift_plaintext_tensor(const Tensor<PlainText *> &coef, const Tensor<PlainText *> &x) const {
+        const size_t d1 = coef.num_elements(), E = x.num_elements();
+        if (d1 == 0 || d1 > COFHE_HIP_POLY_MAX_DEGREE + 1) throw std::invalid_argument("poly_shift_plaintext_tensor: 1 to 9 coefficients");
+        std::vector<uint32_t> ec(d1 * EXPW, 0), ex(E * EXPW, 0), eq(d1 * E * EXPW, 0);
+        for (size_t j = 0; j < d1; j++) pack_exponent(*coef[j], &ec[j * EXPW]);
+        for (size_t e = 0; e < E; e++) pack_exponent(*x[e], &ex[e * EXPW]);
+        void *dc = nullptr, *dx = nullptr, *dq = nullptr;
+        check(cofhe_hip_malloc(ctx_, ec.size() * 4 + 4, &dc)); Guard g1{ctx_, dc};
+        check(cofhe_hip_malloc(ctx_, ex.size() * 4 + 4, &dx)); Guard g2{ctx_, dx};
+        check(cofhe_hip_malloc(ctx_, eq.size() * 4 + 4, &dq)); Guard g3{ctx_, dq};
+        check(cofhe_hip_upload(ctx_, dc, ec.data(), ec.size() * 4, nullptr));
+        check(cofhe_hip_upload(ctx_, dx, ex.data(), ex.size() * 4, nullptr));
+        check(cofhe_hip_poly_shift_records(ctx_, dc, dx, dq, E, (uint32_t)(d1 - 1), k_, nullptr));
+        check(cofhe_hip_download(ctx_, eq.data(), dq, eq.size() * 4, nullptr));
+        Vector<Tensor<PlainText *>> res;
+        for (size_t i = 0; i < d1; i++) {
+            Tensor<PlainText *> t(x.is_zero_degree() ? std::vector<size_t>{1} : x.shape(), nullptr);
+            for (size_t e = 0; e < E; e++) {
+                Mpz v;
+                mpz_import(v.get(), EXPW - 1, -1, 4, 0, 0, &eq[(i * E + e) * EXPW]);
+                t[e] = new PlainText(std::move(v));
+            }
+            res.push_back(t);
+        }
+        return res;
+    }
+    // the closing step of a polynomial evaluation: res[e] = (prod_{i=1..d} powers[i-1][e]^q_i(e[e])) o f^q_0(e[e]), an encryption
+    // of p(x[e]) mod 2^k when powers[i-1][e] = [a_e^i] and e[e] = x[e] - a_e (cofhe_hip_poly_close_records: the shift, one
+    // shared-squarings ladder per record and the plaintext addend, on the device from end to end).  coef: d + 1 coefficients,
+    // pre-scaled by the caller so that every term carries one fixed-point scale.  Re-randomised in PerElement mode.
+    Tensor<CipherText *> poly_close_ciphertext_tensor(const PublicKey &pk, const Tensor<PlainText *> &coef, const Tensor<PlainText *> &e,
+                                                      const Vector<Tensor<CipherText *>> &powers) const {
+        const size_t d = powers.size(), E = e.num_elements();
+        if (d == 0 || d > COFHE_HIP_POLY_MAX_DEGREE || coef.num_elements() != d + 1)
+            throw std::invalid_argument("poly_close_ciphertext_tensor: d + 1 coefficients for d tensors of powers, 1 <= d <= 8");
+        for (size_t i = 0; i < d; i++)
+            if (powers[i].num_elements() != E) throw std::invalid_argument("Tensor shapes must be equal");
+        std::vector<uint32_t> ec((d + 1) * EXPW, 0), ee(E * EXPW, 0), frec(REC, 0);
+        for (size_t j = 0; j <= d; j++) pack_exponent(*coef[j], &ec[j * EXPW]);
+        for (size_t i = 0; i < E; i++) pack_exponent(*e[i], &ee[i * EXPW]);
+        pack_form(f_, frec.data());
+        DeviceTensor dp = stack(powers);
+        void *dc = nullptr, *de = nullptr;
+        check(cofhe_hip_malloc(ctx_, ec.size() * 4 + 4, &dc)); Guard g1{ctx_, dc};
+        check(cofhe_hip_malloc(ctx_, ee.size() * 4 + 4, &de)); Guard g2{ctx_, de};
+        check(cofhe_hip_upload(ctx_, dc, ec.data(), ec.size() * 4, nullptr));
+        check(cofhe_hip_upload(ctx_, de, ee.data(), ee.size() * 4, nullptr));
+        DeviceTensor out = alloc(e.is_zero_degree() ? std::vector<size_t>{1} : e.shape(), E);
+        check(cofhe_hip_poly_close_records(ctx_, dc, de, dp.ptr_, frec.data(), out.ptr_, E, (uint32_t)d, k_, nullptr));
+        check(cofhe_hip_stream_sync(ctx_, nullptr));          // `ec` and `ee` go with this frame
+        rerandomize_result(pk, out);
+        return download(std::move(out));
+    }
+
     // ---- device-resident variants -------------------------------------------------------------
     // the block behind a tensor whose elements are, in order, ALL the elements of one device block (the result of
     // a previous operation handed back unchanged); nullptr otherwise
@@ -1480,6 +1559,26 @@ class HIPCryptoSystem {
         d.n_ = n;
         check(cofhe_hip_malloc(ctx_, n * 2 * REC * 4, &d.ptr_));
         return d;
+    }
+    // d tensors of E ciphertexts each as ONE device tensor [d, E], tensor-major: the layout of the bases of
+    // cofhe_hip_pow_dot_records.  The records of a resident tensor are taken from its block, not rebuilt from GMP integers.
+    DeviceTensor stack(const Vector<Tensor<CipherText *>> &ts) const {
+        const size_t d = ts.size(), E = d ? ts[0].num_elements() : 0;
+        std::vector<uint32_t> recs(d * E * 2 * REC, 0);
+        for (size_t i = 0; i < d; i++) {
+            if (ts[i].num_elements() != E) throw std::invalid_argument("Tensor shapes must be equal");
+            uint32_t *dst = &recs[i * E * 2 * REC];
+            const Tensor<CipherText *> &t = ts[i];
+            std::shared_ptr<DeviceBlock> b = whole_block(t);
+            if (b && b->ctx == ctx_)
+                std::memcpy(dst, b->records(), E * 2 * REC * 4);
+            else
+                pack_forms(2 * E, dst, [&](size_t r) -> const QFI & { const CipherText &c = *t[r >> 1]; return (r & 1) ? c.c2() : c.c1(); });
+        }
+        DeviceTensor out = alloc({d, E}, d * E);
+        check(cofhe_hip_upload(ctx_, out.ptr_, recs.data(), recs.size() * 4, nullptr));
+        check(cofhe_hip_stream_sync(ctx_, nullptr));
+        return out;
     }
 
     Tensor<PlainText *> plaintext_tensor_op(const Tensor<PlainText *> &a, const Tensor<PlainText *> &b, bool mul) const {

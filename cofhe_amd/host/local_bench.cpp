@@ -530,6 +530,143 @@ static void bench_beaver_direct(size_t n) {
     if (!ok) throw std::runtime_error("beaver product mismatch");
 }
 
+// a polynomial activation on a ciphertext tensor from one opened value per element
+// (LocalCipherTextMultiplier::evaluate_polynomial_ciphertext_tensor), through the single-key and the 2-of-3 threshold client:
+// degree 3 with a negative coefficient over n elements, checked against p(x) mod 2^k from GMP on the host; prints
+// client.decrypted_elements(), which must equal the element count
+static void bench_poly_activation(size_t n, int runs) {
+    auto cs = make_cryptosystem(128, 128, Device::GPU);
+    using CS = decltype(cs);
+    auto sk = cs.keygen();
+    const uint32_t k = cs.message_bits();
+    Mpz c[4] = {Mpz(5ul), Mpz(3ul), Mpz(7ul), Mpz(11ul)};
+    c[1].neg();
+    mpz_fdiv_r_2exp(c[1].get(), c[1].get(), k);                 // -3 mod 2^k
+    Tensor<CS::PlainText *> coef(4, nullptr), px(n, nullptr);
+    for (size_t j = 0; j < 4; j++) coef[j] = &c[j];
+    std::vector<Mpz> want(n);
+    for (size_t i = 0; i < n; i++) {
+        // 0, 1, 2^k - 1, 2^(k-1), small values of both signs, then uniform ones
+        Mpz x = i < 2 ? Mpz((unsigned long)i) : i < 8 ? cs.make_plaintext((float)((long)i - 5)) : cs.random_plaintext(k);
+        if (i == 2 || i == 3) mpz_ui_pow_ui(x.get(), 2, i == 2 ? k : k - 1);
+        if (i == 2) mpz_sub_ui(x.get(), x.get(), 1);
+        for (int j = 3; j >= 0; j--) {                          // Horner mod 2^k
+            mpz_mul(want[i].get(), want[i].get(), x.get());
+            mpz_add(want[i].get(), want[i].get(), c[j].get());
+            mpz_fdiv_r_2exp(want[i].get(), want[i].get(), k);
+        }
+        px[i] = new CS::PlainText(x);
+    }
+    bool ok = true;
+    for (int threshold = 0; threshold < 2; threshold++) {
+        std::unique_ptr<LocalSMPCClient<CS>> client(threshold ? new LocalSMPCClient<CS>(cs, sk, 2, 3) : new LocalSMPCClient<CS>(cs, sk));
+        LocalCipherTextMultiplier<CS> mul(*client);
+        auto cx = cs.encrypt_tensor(client->network_public_key(), px);
+        cs.synchronize();
+        auto t0 = Clock::now();
+        auto res = mul.evaluate_polynomial_ciphertext_tensor(coef, cx);
+        cs.synchronize();
+        const double ms = std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
+        auto dec = cs.decrypt_tensor(sk, res);
+        bool pass = client->decrypted_elements() == n;
+        for (size_t i = 0; i < n; i++)
+            if (!(*dec.at(i) == want[i])) pass = false;
+        if (!threshold) std::ofstream("local_bench_poly_activation.bin", std::ios::binary) << cs.serialize_ciphertext_tensor(res);
+        std::cout << "  " << (threshold ? "threshold 2 of 3" : "secret key") << ": degree 3 over " << n << " elements, decrypted_elements "
+                  << client->decrypted_elements() << ", " << ms << " ms (host wall clock, tuple generation and the decryption included): "
+                  << (pass ? "ok" : "FAILED") << std::endl;
+        ok = ok && pass;
+        free_all(res); free_all(dec);
+        if (!threshold) {
+            // the parts on their own: the square of the tensor and of one 0-D element, the Taylor shift (q_0 = p(x)), and the
+            // two-base power product [x]^2 o [x]^3 = [5 x]
+            const auto &pk = client->network_public_key();
+            auto sq = mul.square_ciphertext_tensor(cx);
+            auto sq0 = mul.square_ciphertext_tensor(Tensor<CS::CipherText *>(cx[1 % n]));
+            auto dsq = cs.decrypt_tensor(sk, sq);
+            auto dsq0 = cs.decrypt(sk, *sq0.get_value());
+            auto q = cs.poly_shift_plaintext_tensor(coef, px);
+            Mpz two(2ul), three(3ul);
+            Vector<Tensor<CS::PlainText *>> exps{Tensor<CS::PlainText *>(n, &two), Tensor<CS::PlainText *>(n, &three)};
+            Vector<Tensor<CS::CipherText *>> bases{cx, cx};
+            auto dot = cs.pow_dot_ciphertext_tensors(pk, exps, bases);
+            auto ddot = cs.decrypt_tensor(sk, dot);
+            bool parts = q.size() == 4 && sq0.is_zero_degree();
+            for (size_t i = 0; i < n; i++) {
+                Mpz x2, x5;
+                mpz_mul(x2.get(), px[i]->get(), px[i]->get());
+                mpz_fdiv_r_2exp(x2.get(), x2.get(), k);
+                mpz_mul_ui(x5.get(), px[i]->get(), 5);
+                mpz_fdiv_r_2exp(x5.get(), x5.get(), k);
+                if (!(*dsq.at(i) == x2) || !(*ddot.at(i) == x5) || !(*q[0].at(i) == want[i])) parts = false;
+                if (i == 1 % n && !(dsq0 == x2)) parts = false;
+            }
+            std::cout << "  square (1-D and 0-D), poly_shift_plaintext_tensor, pow_dot_ciphertext_tensors: " << (parts ? "ok" : "FAILED") << std::endl;
+            ok = ok && parts;
+            delete sq0.get_value();
+            free_all(sq); free_all(dsq); free_all(dot); free_all(ddot);
+            for (auto &t : q) free_all(t);
+        }
+        free_all(cx);
+    }
+    {
+        Mpz ad = cs.discriminant();
+        ad.neg();
+        std::ofstream("local_bench_absdelta.txt") << ad.str() << "\n";
+    }
+    if (runs > 0) {
+        // x^3 twice on the same input, single-key client: the polynomial (0, 0, 0, 1) with one opened value per element, and
+        // (x * x) * x by two chained Beaver products with direct differences (four opened values per element, two rounds);
+        // alternating, `runs` timed calls each after a warm-up of both; medians and extremes on one line for tools/bench_ops.py
+        LocalSMPCClient<CS> client(cs, sk);
+        LocalCipherTextMultiplier<CS> mul(client);
+        mul.set_direct_differences(true);
+        Mpz zero(0ul), one(1ul);
+        Tensor<CS::PlainText *> cube(4, &zero);
+        cube[3] = &one;
+        auto cx = cs.encrypt_tensor(client.network_public_key(), px);
+        std::vector<double> ms[2];
+        size_t opened[2] = {0, 0};
+        bool same = true;
+        for (int pass = 0; pass <= runs; pass++)
+            for (int chained = 0; chained < 2; chained++) {
+                const size_t before = client.decrypted_elements();
+                cs.synchronize();
+                auto t0 = Clock::now();
+                Tensor<CS::CipherText *> res;
+                if (chained) {
+                    auto sq = mul.multiply_ciphertext_tensors(cx, cx);
+                    res = mul.multiply_ciphertext_tensors(sq, cx);
+                    free_all(sq);
+                } else {
+                    res = mul.evaluate_polynomial_ciphertext_tensor(cube, cx);
+                }
+                cs.synchronize();
+                if (pass) ms[chained].push_back(std::chrono::duration<double, std::milli>(Clock::now() - t0).count());
+                opened[chained] = client.decrypted_elements() - before;
+                auto dec = cs.decrypt_tensor(sk, res);
+                for (size_t i = 0; i < n; i++) {
+                    Mpz w;
+                    mpz_pow_ui(w.get(), px[i]->get(), 3);
+                    mpz_fdiv_r_2exp(w.get(), w.get(), k);
+                    if (!(*dec.at(i) == w)) same = false;
+                }
+                free_all(res); free_all(dec);
+            }
+        free_all(cx);
+        for (auto &v : ms) std::sort(v.begin(), v.end());
+        std::cout << "compare_json: {\"E\": " << n << ", \"degree\": 3, \"runs\": " << runs << ", \"poly_ms\": " << ms[0][ms[0].size() / 2]
+                  << ", \"poly_ms_min_max\": [" << ms[0].front() << ", " << ms[0].back() << "], \"chained_products_ms\": " << ms[1][ms[1].size() / 2]
+                  << ", \"chained_ms_min_max\": [" << ms[1].front() << ", " << ms[1].back() << "], \"chained_over_poly\": "
+                  << ms[1][ms[1].size() / 2] / ms[0][ms[0].size() / 2] << ", \"opened_poly\": " << opened[0] << ", \"opened_chained\": " << opened[1]
+                  << ", \"agree\": " << (same ? "true" : "false") << "}" << std::endl;
+        ok = ok && same;
+    }
+    std::cout << "  agree: " << (ok ? "yes" : "NO") << std::endl;
+    free_all(px);
+    if (!ok) throw std::runtime_error("polynomial activation mismatch");
+}
+
 // threshold decryption end to end (the reference has no local benchmark for it; the calls are the
 // ones PartialDecryptionRequestHandler / SMPCClient make, partial_decryption_request_handler.hpp:140,
 // smpc_client.hpp:137): share sk t-out-of-n, every party of the first threshold set runs
@@ -1043,7 +1180,7 @@ static void plaintexts_mode(const char *in, const char *out) {
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        std::cerr << "Usage: " << argv[0] << " <encrypt_decrypt|ciphertext_matadd|scal_matmul|threshold|ciphertext_matmul|fresh_randomness|affine|beaver_direct|plain_ct_matmul|ciphertext_matmul_matrix|conv2d|conv2d_grouped|sum_pool2d> [sizes]" << std::endl;
+        std::cerr << "Usage: " << argv[0] << " <encrypt_decrypt|ciphertext_matadd|scal_matmul|threshold|ciphertext_matmul|fresh_randomness|affine|beaver_direct|plain_ct_matmul|ciphertext_matmul_matrix|conv2d|conv2d_grouped|sum_pool2d|poly_activation> [sizes]" << std::endl;
         return 1;
     }
     std::string mode = argv[1];
@@ -1096,6 +1233,9 @@ int main(int argc, char **argv) {
             bench_affine(argc > 2 ? std::stoul(argv[2]) : 64);
         } else if (mode == "beaver_direct") {
             bench_beaver_direct(argc > 2 ? std::stoul(argv[2]) : 8);
+        } else if (mode == "poly_activation") {
+            // elements [runs]: with runs > 0 also the timed comparison with two chained Beaver products
+            bench_poly_activation(argc > 2 ? std::stoul(argv[2]) : 64, argc > 3 ? std::stoi(argv[3]) : 0);
         } else if (mode == "formats") {
             bench_formats();
         } else if (mode == "threads") {

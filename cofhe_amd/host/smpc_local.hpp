@@ -22,6 +22,11 @@
 //   E = Dec(X - A), D = Dec(Y - B);  X Y = E [B] + [A] D + [C] + E D
 // which opens n m + m p values, and spends a plaintext-left product (matmul_plaintext_ciphertext_tensors), a ciphertext-left
 // product (scal_ciphertext_tensors) and a plaintext matrix product mod 2^k (matmul_plaintext_tensors).
+//
+// Polynomials (evaluate_polynomial_ciphertext_tensor, square_ciphertext_tensor; the reference has no such flow).  A degree-d
+// polynomial with plaintext coefficients by chained products opens 2 (d - 1) values per element in d - 1 rounds.  With a power
+// tuple ([a], .., [a^d]) per element:  e = Dec(x - a);  [p(x)] = prod_i [a^i]^(q_i(e)) o f^(q_0(e)),  q the Taylor shift of p at
+// e mod 2^k -- one opened value and one round whatever d (poly_close_ciphertext_tensor, on the device from end to end).
 #pragma once
 #include "hip_cryptosystem.hpp"
 
@@ -89,6 +94,34 @@ class LocalSMPCClient {
         for (size_t i = 0; i < n * m; i++) delete pa[i];
         for (size_t i = 0; i < m * p; i++) delete pb[i];
         for (size_t i = 0; i < n * p; i++) delete pc[i];
+        return t;
+    }
+
+    // power tuples for n elements: the d ciphertext tensors [a], [a^2], .., [a^d] (n elements each), a uniform in Z/2^k per
+    // element and used once; the caller owns the elements.  The powers are multiply_plaintext_tensors' products, reduced mod
+    // 2^k as they grow (an encryption reduces its plaintext anyway; unreduced, a^8 outgrows an exponent record).  Like the
+    // triplets, the tuples of the networked system would come from a protocol between the nodes.
+    Vector<Tensor<CipherText *>> get_beavers_power_tuples(size_t n, size_t d) {
+        Tensor<PlainText *> pa(n, nullptr), pw(n, nullptr);
+        for (size_t i = 0; i < n; i++) {
+            pa[i] = new PlainText(cs_.random_plaintext(cs_.message_bits()));
+            pw[i] = new PlainText(*pa[i]);
+        }
+        Vector<Tensor<CipherText *>> t;
+        for (size_t j = 1; j <= d; j++) {
+            t.push_back(cs_.encrypt_tensor(pk_, pw));
+            if (j == d) break;
+            auto next = cs_.multiply_plaintext_tensors(pw, pa);
+            for (size_t i = 0; i < n; i++) {
+                mpz_fdiv_r_2exp(next[i]->get(), next[i]->get(), cs_.message_bits());
+                delete pw[i];
+            }
+            pw = next;
+        }
+        for (size_t i = 0; i < n; i++) {
+            delete pa[i];
+            delete pw[i];
+        }
         return t;
     }
 
@@ -170,6 +203,43 @@ class LocalCipherTextMultiplier {
             return res;
         }
         throw std::runtime_error("Not implemented");
+    }
+
+    // p(x) element-wise for p = sum_j coef[j] X^j with plaintext coefficients (d + 1 of them, 1 <= d <= 8), over the integers
+    // mod 2^k: with a power tuple ([a], .., [a^d]) per element, ONE opened value e = Dec(x - a) and one round whatever d, where
+    // d - 1 chained products open 2 (d - 1) values in d - 1 rounds.  The reference has no such operation (ComputeOperation's
+    // POLYNOMIAL_EVALUATION is commented out, include/node/compute_request_handler.hpp:74).  Fixed-point scales are the
+    // caller's: coef[j] comes pre-scaled so that every term carries one scale.  0-D and 1-D tensors; higher ranks are
+    // flattened and the result reshaped.
+    Tensor<CipherText *> evaluate_polynomial_ciphertext_tensor(const Tensor<PlainText *> &coef, const Tensor<CipherText *> &x) {
+        if (x.is_zero_degree()) {
+            Tensor<CipherText *> r = evaluate_polynomial_ciphertext_tensor(coef, Tensor<CipherText *>(1, x.get_value()));
+            return Tensor<CipherText *>(r.at(0));
+        }
+        if (coef.num_elements() < 2) throw std::invalid_argument("evaluate_polynomial_ciphertext_tensor: a polynomial of degree 1 to 8");
+        auto &cs = client_m.crypto_system();
+        const auto &pk = client_m.network_public_key();
+        const size_t n = x.num_elements(), d = coef.num_elements() - 1;
+        Tensor<CipherText *> flat = x;
+        flat.flatten();
+        auto powers = client_m.get_beavers_power_tuples(n, d);
+        auto x_sub_a = cs.sub_ciphertext_tensors(pk, flat, powers[0]);
+        auto e = client_m.decrypt_tensor(x_sub_a);
+        auto ct = cs.poly_close_ciphertext_tensor(pk, coef, e, powers);
+        for (size_t i = 0; i < n; i++) {
+            for (auto &p : powers) delete p[i];
+            delete x_sub_a[i];
+            delete e[i];
+        }
+        ct.reshape(x.shape());
+        return ct;
+    }
+    // x^2 element-wise: the polynomial (0, 0, 1), one opened value per element where the Beaver product x * x opens two
+    Tensor<CipherText *> square_ciphertext_tensor(const Tensor<CipherText *> &x) {
+        PlainText zero(0ul), one(1ul);
+        Tensor<PlainText *> coef(3, &zero);
+        coef[2] = &one;
+        return evaluate_polynomial_ciphertext_tensor(coef, x);
     }
 
     // element-wise products of two 1-D ciphertext tensors (:115-160), same order of calls

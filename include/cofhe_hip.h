@@ -19,6 +19,9 @@
  *                                    are a patch matrix built by the caller and the 2-D branch above
  *   cofhe_hip_conv2d_grouped_...,    nothing: the same with dilation and groups (depthwise filters, per-channel scales), and sum
  *   cofhe_hip_sum_pool2d_...         pooling as the depthwise convolution with filters of ones
+ *   cofhe_hip_pow_dot_records,       nothing: a polynomial with plaintext coefficients on a ciphertext tensor from ONE opened
+ *   cofhe_hip_poly_shift_records,    value per element (power tuples); ComputeOperation's POLYNOMIAL_EVALUATION is commented out
+ *   cofhe_hip_poly_close_...         (include/node/compute_request_handler.hpp:74)
  *   cofhe_hip_decrypt_records        decrypt_tensor's per-element work, cpu_cryptosystem_tensor_ops.inl:21-33
  *   cofhe_hip_part_decrypt_records,  part_decrypt_tensor / combine_part_decryption_results_tensor,
  *   cofhe_hip_combine_part_...       cpu_cryptosystem_tensor_ops.inl:35-73 (cpu_cryptosystem_distributed.inl:231-285)
@@ -243,6 +246,41 @@ int cofhe_hip_sum_pool2d_records(cofhe_hip_ctx *ctx, const void *d_cts, const vo
  * inputs.  The E D term of a matrix Beaver triplet, and the C = A B of its generation. */
 int cofhe_hip_matmul_plain_plain_records(cofhe_hip_ctx *ctx, const void *d_a, const void *d_b, void *d_out, uint32_t n, uint32_t m,
                                          uint32_t p, uint32_t kbits, void *stream);
+/* ---- polynomial evaluation from one opened value (cofhe_amd/csrc/pow_dot.hip) ----
+ * p(X) = sum_{j<=d} c_j X^j with plaintext coefficients on a ciphertext [x], over the integers mod 2^k.  A POWER TUPLE of an
+ * element is ([a], [a^2], .., [a^d]) with a uniform in Z/2^k, used once.  With the ONE opened value e = Dec(x - a), x = a + e and
+ *   [p(x)] = (prod_{i=1..d} [a^i]^(q_i(e))) o f^(q_0(e)),   q_i(e) = sum_{j>=i} C(j,i) c_j e^(j-i) mod 2^k   (q_0 = p(e)):
+ * one opened value and one round per element whatever d, where d - 1 chained Beaver products open 2 (d - 1) values in d - 1
+ * rounds.  The reference has no such operation (ComputeOperation carries a commented-out POLYNOMIAL_EVALUATION,
+ * include/node/compute_request_handler.hpp:74).  Fixed-point scales are the caller's: the c_j come pre-scaled so that every
+ * term of p carries one scale. */
+#define COFHE_HIP_POLY_MAX_DEGREE 8
+/* out[2e+h] = prod_{i<d} bases[(i n_ct + e) 2 + h] ^ exps[i n_ct + e], e < n_ct, h in {0, 1}: d ciphertext tensors of n_ct
+ * ciphertexts, power-major, each raised element by element to its own exponent tensor (d n_ct exponent records, sign
+ * honoured, magnitudes up to 992 bits) and multiplied together -- by ONE ladder per record whose squarings the d bases share:
+ * bits + d bits / 3 compositions per record where d calls of cofhe_hip_pow_records and d - 1 additions run d (bits + bits / 3)
+ * + d - 1.  Exponents that are all zero give the principal form; d = 1 gives cofhe_hip_pow_records' records.  One launch
+ * ("k_pow_dot" under "profile_kernels"), purely stream-ordered: no workspace, no read-back, no lock.  COFHE_HIP_EINVAL, nothing
+ * written: d = 0 or d > COFHE_HIP_POLY_MAX_DEGREE; d_out overlapping d_bases or d_exps (the running products live in d_out).
+ * n_ct = 0 does nothing. */
+int cofhe_hip_pow_dot_records(cofhe_hip_ctx *ctx, const void *d_bases, const void *d_exps, void *d_out, uint64_t n_ct, uint32_t d,
+                              void *stream);
+/* q[i n + e] = sum_{j>=i} C(j,i) coef[j] x[e]^(j-i) mod 2^kbits, i = 0 .. d: the Taylor shift of the polynomial at every x[e], by
+ * repeated synthetic division.  coef: d + 1 exponent records shared by the tensor, x: n, q: (d + 1) n, power-major.  Inputs
+ * enter as residues mod 2^kbits and outputs lie in [0, 2^kbits) with sign word 0, as in cofhe_hip_matmul_plain_plain_records;
+ * 1 <= kbits <= 639, 0 <= d <= COFHE_HIP_POLY_MAX_DEGREE (d = 0 copies c_0), else COFHE_HIP_EINVAL.  One launch
+ * ("k_poly_shift"), purely stream-ordered.  d_q must not overlap the inputs. */
+int cofhe_hip_poly_shift_records(cofhe_hip_ctx *ctx, const void *d_coef, const void *d_x, void *d_q, uint64_t n, uint32_t d, uint32_t kbits,
+                                 void *stream);
+/* The closing step: out[e] = (prod_{i=1..d} powers[i-1][e]^(q_i(e[e]))) o f^(q_0(e[e])), an encryption of p(x[e]) mod 2^kbits when
+ * powers[i-1][e] = [a_e^i] and e[e] = x[e] - a_e.  d_coef: d + 1 exponent records; d_e: n_ct; d_powers: d tensors of n_ct
+ * ciphertexts, power-major; f_record: HOST record of f.  Three steps on `stream`: cofhe_hip_poly_shift_records into a block
+ * of the block cache (which goes back behind the work queued on `stream`), cofhe_hip_pow_dot_records over q_1 .. q_d, and the
+ * plaintext addend of cofhe_hip_add_plain_records (mode 0, no randomness) for f^(q_0) against the cached table of f.  Uses
+ * the block cache and, through the addend, the workspace plan "comb" (kind 3): it has no plan name of its own.  No read-back.
+ * 1 <= d <= COFHE_HIP_POLY_MAX_DEGREE; d_out must not overlap an input (COFHE_HIP_EINVAL). */
+int cofhe_hip_poly_close_records(cofhe_hip_ctx *ctx, const void *d_coef, const void *d_e, const void *d_powers, const uint32_t *f_record,
+                                 void *d_out, uint64_t n_ct, uint32_t d, uint32_t kbits, void *stream);
 /* decryption: for each of n ciphertexts, m with c2 o (c1^sk)^-1 = f^m.  sk: one exponent record on
  * the device; f_record: HOST pointer to the 168-word record of f = (2^(2k), 2^(k+1), 1 - Delta_K)
  * (its table of f^(-2^j) is built on first use and cached in the context).  d_out receives
@@ -432,6 +470,12 @@ int cofhe_hip_conv2d_grouped_plain_ct_tensors_bytes(cofhe_hip_ctx *ctx, const ui
 /* the serialised twin of cofhe_hip_sum_pool2d_records over kh x kw windows: cts [B, H, W, C] -> [B, Ho, Wo, C] */
 int cofhe_hip_sum_pool2d_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *cts, size_t lc, const uint8_t *zero, size_t lz, uint32_t kh,
                                        uint32_t kw, uint32_t sh, uint32_t sw, uint32_t ph, uint32_t pw, uint8_t **out, size_t *outlen);
+/* the serialised twin of cofhe_hip_poly_close_records: coef a 1-D plaintext tensor [d + 1], e a plaintext tensor of any shape,
+ * powers the ciphertext tensor [d, shape of e]; the result is a ciphertext tensor of e's shape.  Incoming forms are validated
+ * (COFHE_HIP_EINVAL for a non-form); COFHE_HIP_ESHAPE when the shapes do not fit.  f_record: HOST record of f. */
+int cofhe_hip_poly_close_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *coef, size_t lcoef, const uint8_t *e, size_t le,
+                                       const uint8_t *powers, size_t lp, const uint32_t *f_record, uint32_t kbits, uint8_t **out,
+                                       size_t *outlen);
 /* s: plaintext tensor; 1-D x 1-D -> element-wise, 2-D x 2-D -> matmul (zero: 1-element tensor) */
 int cofhe_hip_scal_ciphertext_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *s, size_t ls,
                                             const uint8_t *cts, size_t lc, const uint8_t *zero, size_t lz,

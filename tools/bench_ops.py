@@ -4,7 +4,9 @@ C2 matadd 128x128, C3 scal_matmul 256^3 (ramp exponents) and with 128-bit expone
 C5 matadd 1024x1024, 1-D scal with k-bit exponents, negation, decryption, threshold decryption,
 accumulation of the ct x ct product.  --conv-only: only the depthwise convolution and the sum pooling, each against the
 block-diagonal dense filter through the ungrouped entry (the way these layers were written before the convolution had groups),
-the two alternating in one run; --out FILE also writes those lines to FILE."""
+the two alternating in one run; --out FILE also writes those lines to FILE.  --poly-only: only the polynomial evaluation, by the
+same method: cofhe_hip_pow_dot_records against the ladders and additions it replaces, and the one-opened-value protocol against
+chained Beaver products (through local_bench); written to profiles/r12_poly/poly_time.json, or to --out FILE."""
 import json
 import os
 import sys
@@ -109,6 +111,71 @@ if "--conv-only" in sys.argv:
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         with open(path, "w") as fh:
             json.dump(res, fh, indent=1)
+    sys.exit(0 if all(r["same_records"] and r["device_status"] == 0 for r in res) else 1)
+
+# ---- polynomial evaluation: the shared-squarings ladder against the composed route, the protocol against chained products ----
+def poly_ops(runs=5):
+    """"pow_dot": cofhe_hip_pow_dot_records against d calls of cofhe_hip_pow_records plus d - 1 cofhe_hip_add_ciphertext_records on
+    the same operands, E = 4096, d in {2, 4}, full k-bit exponents, equal output records (checked).  Alternating, `runs` windows
+    each (a quarter of a second of calls or more per window) after a warm-up of both; the median and the extremes of each, and
+    the ratio of the medians.  "poly_activation": the host harness's comparison of evaluate_polynomial_ciphertext_tensor
+    (degree 3) with two chained multiply_ciphertext_tensors with direct differences, E = 256, single-key client (local_bench
+    poly_activation 256 <runs> alternates the two in its own process and prints the line)"""
+    import subprocess
+    E = 4096
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    lines = []
+    for d in (2, 4):
+        bases = torch.cat([fresh(E) for _ in range(d)]).contiguous()
+        ex = dev_i32(exp_records([rng.bits(K) | (1 << (K - 1)) for _ in range(d * E)]))
+        ct_bytes, ex_bytes = E * 336 * 4, E * 32 * 4
+        out_d, out_c = torch.zeros(E * 336, dtype=torch.int32, device=dev), torch.zeros(E * 336, dtype=torch.int32, device=dev)
+        terms = torch.zeros(d * E * 336, dtype=torch.int32, device=dev)
+
+        def dot():
+            eng.pow_dot_records(bases.data_ptr(), ex.data_ptr(), out_d.data_ptr(), E, d)
+
+        def composed():
+            for i in range(d):
+                eng.pow_records(bases.data_ptr() + i * ct_bytes, ex.data_ptr() + i * ex_bytes, terms.data_ptr() + i * ct_bytes, E)
+            eng.add_ciphertext_records(terms.data_ptr(), terms.data_ptr() + ct_bytes, out_c.data_ptr(), E)
+            for i in range(2, d):
+                eng.add_ciphertext_records(out_c.data_ptr(), terms.data_ptr() + i * ct_bytes, out_c.data_ptr(), E)
+
+        dot(), composed()
+        torch.cuda.synchronize()
+        same = bool(torch.equal(out_d, out_c))
+        rd, rc = (max(3, int(0.25 / timed(fn)) + 1) for fn in (dot, composed))
+        td, tc = [], []
+        for _ in range(runs):
+            td.append(timed(dot, reps=rd))
+            tc.append(timed(composed, reps=rc))
+        line = {"op": "pow_dot", "E": E, "d": d, "exponent_bits": K, "pow_dot_ms": round(med(td) * 1e3, 3),
+                "pow_dot_ms_min_max": [round(min(td) * 1e3, 3), round(max(td) * 1e3, 3)], "composed_ms": round(med(tc) * 1e3, 3),
+                "composed_ms_min_max": [round(min(tc) * 1e3, 3), round(max(tc) * 1e3, 3)], "composed_over_pow_dot": round(med(tc) / med(td), 3),
+                "predicted_by_composition_count": round((d * (K + K / 3) + d - 1) / (K + d * K / 3), 2), "same_records": same, "runs": runs,
+                "calls_per_window": [rd, rc], "device_status": eng.device_status()}
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+        del bases, ex, out_d, out_c, terms
+    exe = os.path.join(ROOT, "cofhe_amd", "host", "local_bench")
+    r = subprocess.run([exe, "poly_activation", "256", str(runs)], capture_output=True, text=True, cwd=os.environ.get("TMPDIR", "/tmp"))
+    line = {"op": "poly_activation", "same_records": False, "device_status": 0, "exit_status": r.returncode}
+    for ln in r.stdout.splitlines():
+        if ln.startswith("compare_json: "):
+            line.update(json.loads(ln[len("compare_json: "):]))
+            line["same_records"] = bool(line.pop("agree")) and r.returncode == 0
+    print(json.dumps(line), flush=True)
+    lines.append(line)
+    return lines
+
+
+if "--poly-only" in sys.argv:
+    res = poly_ops()
+    path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "r12_poly", "poly_time.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as fh:
+        json.dump(res, fh, indent=1)
     sys.exit(0 if all(r["same_records"] and r["device_status"] == 0 for r in res) else 1)
 
 # ---- matadd C2 / C5 ---------------------------------------------------------------------------
