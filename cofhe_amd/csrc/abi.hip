@@ -1,8 +1,9 @@
 // abi.hip -- the C ABI of include/cofhe_hip.h, in this order: the context, the block cache, the launch helpers (spans, the
 // two-build launch, flag words, the table-cache lookup), the workspace plans, the launchers (one launch site per kernel and
 // route; product_tree is the pairwise tree of them all) and the host-side tensor formats.  The kernels are declared in
-// kernels.hpp and defined in cofhe_hip.hip, wide.hip, comb.hip, affine.hip, matmul_left.hip, conv.hip and pow_dot.hip; this file holds
-// no device code of its own.  conv.hip holds the three kernels of the convolution, pow_dot.hip the two of the polynomial evaluation.
+// kernels.hpp and defined in cofhe_hip.hip, wide.hip, comb.hip, affine.hip, matmul_left.hip, conv.hip, pow_dot.hip and divide.hip; this
+// file holds no device code of its own.  conv.hip holds the three kernels of the convolution, pow_dot.hip the two of the polynomial
+// evaluation, divide.hip the signed floor division of the division by public divisors.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -19,6 +20,7 @@
 #include "conv.hpp"
 #include "plain_mm.hpp"
 #include "poly_shift.hpp"
+#include "plain_div.hpp"
 
 using namespace cofhe;
 using namespace cofhe_k;
@@ -1711,6 +1713,52 @@ int cofhe_hip_poly_close_records(cofhe_hip_ctx *ctx, const void *d_coef, const v
     return cofhe_hip_add_plain_records(ctx, d_out, q.p, nullptr, nullptr, nullptr, f_record, d_out, n_ct, kbits, 0, stream);
 }
 
+// ---- division by public divisors from one opened value (divide.hip) --------------------------------------------------------
+static_assert(COFHE_HIP_DIV_MAX_KBITS == PDV_MAX_KBITS, "the header's bound is the kernel's");
+// touches no shared state of the context but the status word, which the kernel sets atomically: no lock
+int cofhe_hip_divfloor_plain_records(cofhe_hip_ctx *ctx, const void *d_v, const void *d_div, uint64_t n_div, void *d_q, uint64_t n,
+                                     uint32_t kbits, void *stream) {
+    if (kbits == 0 || kbits > PDV_MAX_KBITS) return fail(COFHE_HIP_EINVAL, "k out of range");
+    if (n_div == 0 || n % n_div != 0) return fail(COFHE_HIP_EINVAL, "divfloor: the element count is a multiple of the divisor count, which is not 0");
+    if (n == 0) return COFHE_HIP_OK;
+    if (!d_v || !d_div || !d_q) return fail(COFHE_HIP_EINVAL, "null argument");
+    const uint64_t blocks = (n + PDV_GROUPS - 1) / PDV_GROUPS;
+    if (blocks > 0x7FFFFFFFull) return fail(COFHE_HIP_EINVAL, "work size out of range");
+    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4;
+    if (overlaps(d_q, n * exp_bytes, d_v, n * exp_bytes) || overlaps(d_q, n * exp_bytes, d_div, n_div * exp_bytes))
+        return fail(COFHE_HIP_EINVAL, "divfloor: the output overlaps an input");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    {
+        ProfScope ps(ctx, "k_plain_divfloor", st);
+        hipLaunchKernelGGL(k_plain_divfloor, dim3((unsigned)blocks), dim3(PDV_THREADS), 0, st, (const uint32_t *)d_v, (const uint32_t *)d_div,
+                           n_div, (uint32_t *)d_q, n, kbits, ctx->d_status);
+    }
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+
+// Needs no workspace plan of its own: the quotients of the opened values are one block of the block cache, and the plaintext
+// addend that closes the call carves the workspace by the plan "comb" (kind 3).
+int cofhe_hip_div_close_records(cofhe_hip_ctx *ctx, const void *d_e, const void *d_div, uint64_t n_div, const void *d_rq, const uint32_t *f_record,
+                                void *d_out, uint64_t n_ct, uint32_t kbits, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (kbits == 0 || kbits > PDV_MAX_KBITS) return fail(COFHE_HIP_EINVAL, "k out of range");
+    if (n_div == 0 || n_ct % n_div != 0) return fail(COFHE_HIP_EINVAL, "div_close: the element count is a multiple of the divisor count, which is not 0");
+    if (int rc = comb_check(3, n_ct, 0, kbits, 0, 0)) return rc;
+    if (n_ct == 0) return COFHE_HIP_OK;
+    if (!d_e || !d_div || !d_rq || !f_record || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
+    const size_t out_bytes = (size_t)n_ct * 2 * REC_WORDS * 4, exp_bytes = (size_t)EXP_REC_WORDS * 4;
+    if (overlaps(d_out, out_bytes, d_rq, out_bytes) || overlaps(d_out, out_bytes, d_e, n_ct * exp_bytes) ||
+        overlaps(d_out, out_bytes, d_div, n_div * exp_bytes))
+        return fail(COFHE_HIP_EINVAL, "div_close: the output overlaps an input");
+    DevBuf q;                                     // e_q = floor(s(e) / D)
+    q.stream = stream;
+    if (int rc = q.get(ctx, n_ct * exp_bytes)) return rc;
+    if (int rc = cofhe_hip_divfloor_plain_records(ctx, d_e, d_div, n_div, q.p, n_ct, kbits, stream)) return rc;
+    return cofhe_hip_add_plain_records(ctx, d_rq, q.p, nullptr, nullptr, nullptr, f_record, d_out, n_ct, kbits, 0, stream);
+}
+
 namespace {
 // the table f^(-2^j), j < k, of the decryption kernels (built on first use, cached in the context)
 int ensure_ftab(cofhe_hip_ctx *ctx, const uint32_t *f_record, uint32_t kbits, void *stream) {
@@ -2323,6 +2371,46 @@ int cofhe_hip_poly_close_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *coef, 
         return fail(COFHE_HIP_ESHAPE, "poly_close: the powers are a ciphertext tensor [d, shape of e]");
     if (int rc = dout.get(ctx, ne ? ne * 2 * REC_WORDS * 4 : 4)) return rc;
     if (int rc = cofhe_hip_poly_close_records(ctx, dk.p, de.p, dp.p, f_record, dout.p, ne, d, kbits, nullptr)) return rc;
+    return finish(ctx, dout, 2 * ne, nde, se, out, outlen);
+}
+
+int cofhe_hip_div_close_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *e, size_t le, const uint8_t *div, size_t ldiv, const uint8_t *rq,
+                                      size_t lrq, const uint32_t *f_record, uint32_t kbits, uint8_t **out, size_t *outlen) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (kbits == 0 || kbits > PDV_MAX_KBITS) return fail(COFHE_HIP_EINVAL, "k out of range");
+    // the divisors are public host values: read and judged here, as the kernel judges them
+    uint32_t ndd, sd[8], *hdiv = nullptr;
+    uint64_t nd;
+    if (int rc = cofhe_hip_bytes_to_exponents(div, ldiv, &ndd, sd, &hdiv, &nd)) return rc;
+    struct Free {
+        uint32_t *p;
+        ~Free() { free(p); }
+    } guard{hdiv};
+    const int L = pmm_limbs(kbits);
+    for (uint64_t i = 0; i < nd; i++) {
+        const uint32_t *rec = hdiv + i * EXP_REC_WORDS;
+        uint32_t any = 0;
+        for (int l = 0; l < L; l++) any |= l == L - 1 ? rec[l] & pmm_top_mask(kbits) : rec[l];
+        if (rec[EXP_MAG_WORDS] != 0 || any == 0 || ((rec[(kbits - 1) >> 5] >> ((kbits - 1) & 31)) & 1u))
+            return fail(COFHE_HIP_EINVAL, "div_close: a divisor D needs 1 <= D < 2^(k-1)");
+    }
+    uint32_t nde, ndr, se[8], sr[8];
+    uint64_t ne, nr;
+    HIPCHK(hipSetDevice(ctx->device));
+    DevBuf de, dd, dr, dout;
+    if (int rc = load_tensor(ctx, e, le, 0, de, &nde, se, &ne)) return rc;
+    if (int rc = load_tensor(ctx, rq, lrq, 2, dr, &ndr, sr, &nr)) return rc;
+    if (ndr != nde || memcmp(sr, se, 4 * nde) != 0 || nr != 2 * ne)
+        return fail(COFHE_HIP_ESHAPE, "div_close: [r_q] is a ciphertext tensor of e's shape");
+    // one divisor, one per channel (the last dimension of e) or one per element
+    const bool per_channel = nde >= 1 && ndd == 1 && sd[0] == se[nde - 1];
+    const bool per_element = ndd == nde && memcmp(sd, se, 4 * nde) == 0;
+    if (nd == 0 || !(nd == 1 || per_channel || per_element))
+        return fail(COFHE_HIP_ESHAPE, "div_close: the divisors are one element, e's last dimension or e's shape");
+    if (int rc = dd.get(ctx, nd * EXP_REC_WORDS * 4)) return rc;
+    HIPCHK(hipMemcpy(dd.p, hdiv, nd * EXP_REC_WORDS * 4, hipMemcpyHostToDevice));
+    if (int rc = dout.get(ctx, ne ? ne * 2 * REC_WORDS * 4 : 4)) return rc;
+    if (int rc = cofhe_hip_div_close_records(ctx, de.p, dd.p, nd, dr.p, f_record, dout.p, ne, kbits, nullptr)) return rc;
     return finish(ctx, dout, 2 * ne, nde, se, out, outlen);
 }
 

@@ -4,7 +4,7 @@
 // undefined symbol when the library is loaded (tests/test_cabi.py).  comb.hip holds the two kernels of the fixed-base comb,
 // affine.hip the ciphertext difference and the record inverse, matmul_left.hip the record transpose and the plaintext
 // matrix product, conv.hip the convolution's level 0, its patch gather and its filter expansion, pow_dot.hip the multi-exponentiation
-// and the Taylor shift of the polynomial evaluation.
+// and the Taylor shift of the polynomial evaluation, divide.hip the signed floor division on exponent records.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -153,4 +153,9 @@ __global__ void k_pow_dot(const uint32_t *__restrict__ bases, const uint32_t *__
                           const uint32_t *__restrict__ one_rec, const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status);
 __global__ void k_poly_shift(const uint32_t *__restrict__ coef, const uint32_t *__restrict__ x, uint32_t *__restrict__ q, uint64_t n, uint32_t d,
                              uint32_t kbits);
+
+// division by public divisors from one opened value (divide.hip; plain_div.hpp): q[e] = floor(s(v[e]) / div[e mod n_div]) mod
+// 2^kbits on exponent records, s the centred residue, one limb group per element
+__global__ void k_plain_divfloor(const uint32_t *__restrict__ v, const uint32_t *__restrict__ div, uint64_t n_div, uint32_t *__restrict__ q,
+                                 uint64_t n, uint32_t kbits, uint32_t *__restrict__ status);
 }  // namespace cofhe_k

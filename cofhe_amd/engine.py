@@ -125,6 +125,20 @@ class Engine:
                                                        C.c_uint32(kbits), C.byref(out), C.byref(n)))
         return self._take(out, n)
 
+    def div_close_tensors_bytes(self, e: bytes, div: bytes, rq: bytes, f_record, kbits: int) -> bytes:
+        """e (plaintext tensor of the opened values x - r), div (plaintext tensor of one divisor, of e's last dimension or of e's
+        shape) and rq (ciphertext tensor [r_q] of e's shape) -> the ciphertext tensor of floor(x / div) or one less, of e's
+        shape; a divisor outside [1, 2^(kbits-1)) is refused; f_record: host uint32[168]"""
+        import numpy as np
+        f = np.ascontiguousarray(f_record, dtype=np.uint32)
+        assert f.size == 168
+        out = C.POINTER(C.c_uint8)()
+        n = C.c_size_t()
+        _chk(self.L.cofhe_hip_div_close_tensors_bytes(self.ctx, C.c_char_p(e), C.c_size_t(len(e)), C.c_char_p(div), C.c_size_t(len(div)),
+                                                      C.c_char_p(rq), C.c_size_t(len(rq)), f.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                      C.c_uint32(kbits), C.byref(out), C.byref(n)))
+        return self._take(out, n)
+
     def scal_ciphertext_tensors(self, s: bytes, cts: bytes, zero: bytes = None) -> bytes:
         out = C.POINTER(C.c_uint8)()
         n = C.c_size_t()
@@ -368,6 +382,23 @@ class Engine:
         _chk(self.L.cofhe_hip_poly_close_records(self.ctx, C.c_void_p(d_coef), C.c_void_p(d_e), C.c_void_p(d_powers),
                                                  f.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(d_out), C.c_uint64(n_ciphertexts),
                                                  C.c_uint32(d), C.c_uint32(kbits), C.c_void_p(stream)))
+
+    def divfloor_plain_records(self, d_v, d_div, n_div, d_q, n, kbits, stream=0):
+        """q[e] = floor(s(v[e]) / div[e mod n_div]) mod 2^kbits on exponent records, s the centred residue (v: n, div: n_div,
+        q: n); 1 <= div < 2^(kbits-1), else quotient 0 and bit 4 of device_status; outputs in [0, 2^k) with sign word 0"""
+        _chk(self.L.cofhe_hip_divfloor_plain_records(self.ctx, C.c_void_p(d_v), C.c_void_p(d_div), C.c_uint64(n_div), C.c_void_p(d_q),
+                                                     C.c_uint64(n), C.c_uint32(kbits), C.c_void_p(stream)))
+
+    def div_close_records(self, d_e, d_div, n_div, d_rq, f_record, d_out, n_ciphertexts, kbits, stream=0):
+        """the closing step of a division by public divisors: out[e] = (c1, c2 o f^e_q) of rq[e] with e_q = floor(s(e[e]) /
+        div[e mod n_div]) mod 2^kbits; e: n exponent records of the opened values x - r, rq: the [r_q] of the division pairs;
+        f_record: host uint32[168]; d_out must not overlap an input"""
+        import numpy as np
+        f = np.ascontiguousarray(f_record, dtype=np.uint32)
+        assert f.size == 168
+        _chk(self.L.cofhe_hip_div_close_records(self.ctx, C.c_void_p(d_e), C.c_void_p(d_div), C.c_uint64(n_div), C.c_void_p(d_rq),
+                                                f.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(d_out), C.c_uint64(n_ciphertexts),
+                                                C.c_uint32(kbits), C.c_void_p(stream)))
 
     def decrypt_records(self, d_cts, d_sk, f_record, d_out, n_ciphertexts, kbits, stream=0):
         """f_record: host numpy uint32[168]; d_out: n * (ceil(k/32) + 1) words"""

@@ -817,7 +817,8 @@ class HIPCryptoSystem {
     // Sum pooling, channels last: res[b,oy,ox,c] = zero + sum over the kernel[0] x kernel[1] window at (oy stride[0] - pad[0],
     // ox stride[1] - pad[1]) of cts[b, ., ., c], a tensor [B, Ho, Wo, C] (cofhe_hip_sum_pool2d_records: the depthwise convolution
     // with filters of ones, kh kw - 1 additions per output).  Average pooling is this with 1 / (kh kw) folded into the next
-    // layer's plaintext weights: that inverse does not exist mod 2^k for an even window.  Re-randomised like conv2d.
+    // layer's plaintext weights (that inverse does not exist mod 2^k for an even window), or the division by kh kw of
+    // LocalCipherTextMultiplier::avg_pool2d_ciphertext_tensor (smpc_local.hpp).  Re-randomised like conv2d.
     Tensor<CipherText *> sum_pool2d_ciphertext_tensor(const PublicKey &pk, const Tensor<CipherText *> &cts, const std::array<size_t, 2> &kernel,
                                                       const std::array<size_t, 2> &stride, const std::array<size_t, 2> &pad = {0, 0},
                                                       const CipherText *zero = nullptr) const {
@@ -1025,6 +1026,69 @@ class HIPCryptoSystem {
         check(cofhe_hip_stream_sync(ctx_, nullptr));          // `ec` and `ee` go with this frame
         rerandomize_result(pk, out);
         return download(std::move(out));
+    }
+    // public divisors are host values: 1 <= D < 2^(k-1) for every one of them, and their count divides the element count n
+    // (element e takes divisor e mod count: one divisor, one per channel of a channels-last tensor, or one per element)
+    void check_divisors(const Tensor<PlainText *> &div, size_t n) const {
+        const size_t nd = div.num_elements();
+        if (nd == 0 || n % nd != 0) throw std::invalid_argument("divisors: their count must divide the element count");
+        for (size_t i = 0; i < nd; i++)
+            if (div[i]->sgn() <= 0 || div[i]->nbits() > k_ - 1) throw std::invalid_argument("divisors: 1 <= D < 2^(k-1)");
+    }
+    // res[e] = floor(s(v[e]) / div[e mod count]) mod 2^k, s the centred residue in [-2^(k-1), 2^(k-1)): the signed floor division
+    // of cofhe_hip_divfloor_plain_records (k_plain_divfloor), of v's shape.  Both halves of a division pair and the quotient
+    // of an opened value come from here.
+    Tensor<PlainText *> divide_plaintext_tensor(const Tensor<PlainText *> &v, const Tensor<PlainText *> &div) const {
+        const size_t E = v.num_elements(), nd = div.num_elements();
+        check_divisors(div, E);
+        std::vector<uint32_t> ev(E * EXPW, 0), ed(nd * EXPW, 0), eq(E * EXPW, 0);
+        for (size_t e = 0; e < E; e++) pack_exponent(*v[e], &ev[e * EXPW]);
+        for (size_t i = 0; i < nd; i++) pack_exponent(*div[i], &ed[i * EXPW]);
+        void *dv = nullptr, *dd = nullptr, *dq = nullptr;
+        check(cofhe_hip_malloc(ctx_, ev.size() * 4 + 4, &dv)); Guard g1{ctx_, dv};
+        check(cofhe_hip_malloc(ctx_, ed.size() * 4 + 4, &dd)); Guard g2{ctx_, dd};
+        check(cofhe_hip_malloc(ctx_, eq.size() * 4 + 4, &dq)); Guard g3{ctx_, dq};
+        check(cofhe_hip_upload(ctx_, dv, ev.data(), ev.size() * 4, nullptr));
+        check(cofhe_hip_upload(ctx_, dd, ed.data(), ed.size() * 4, nullptr));
+        check(cofhe_hip_divfloor_plain_records(ctx_, dv, dd, nd, dq, E, k_, nullptr));
+        check(cofhe_hip_download(ctx_, eq.data(), dq, eq.size() * 4, nullptr));
+        Tensor<PlainText *> t(v.is_zero_degree() ? std::vector<size_t>{1} : v.shape(), nullptr);
+        for (size_t e = 0; e < E; e++) {
+            Mpz q;
+            mpz_import(q.get(), EXPW - 1, -1, 4, 0, 0, &eq[e * EXPW]);
+            t[e] = new PlainText(std::move(q));
+        }
+        return t;
+    }
+    // the closing step of a division by public divisors: res[e] = (c1, c2 o f^(e_q)) of rq[e], e_q = floor(s(e[e]) / div[e mod
+    // count]) mod 2^k -- an encryption of floor(s(x[e]) / D) or one less when rq[e] = [r_q] of the element's division pair and
+    // e[e] = x[e] - r without a wrap (cofhe_hip_div_close_records: the division and the plaintext addend, on the device from
+    // end to end; include/cofhe_hip.h states the contract).  Re-randomised in PerElement mode.
+    Tensor<CipherText *> div_close_ciphertext_tensor(const PublicKey &pk, const Tensor<PlainText *> &e, const Tensor<PlainText *> &div,
+                                                     const Tensor<CipherText *> &rq) const {
+        if (rq.num_elements() != e.num_elements()) throw std::invalid_argument("Tensor shapes must be equal");
+        DeviceTensor out = div_close_ciphertext_tensor(e, div, upload(rq));
+        rerandomize_result(pk, out);
+        return download(std::move(out));
+    }
+    // the same on a resident [r_q]; deterministic
+    DeviceTensor div_close_ciphertext_tensor(const Tensor<PlainText *> &e, const Tensor<PlainText *> &div, const DeviceTensor &rq) const {
+        const size_t E = e.num_elements(), nd = div.num_elements();
+        if (rq.n_ != E) throw std::invalid_argument("Tensor shapes must be equal");
+        check_divisors(div, E);
+        std::vector<uint32_t> ee(E * EXPW, 0), ed(nd * EXPW, 0), frec(REC, 0);
+        for (size_t i = 0; i < E; i++) pack_exponent(*e[i], &ee[i * EXPW]);
+        for (size_t i = 0; i < nd; i++) pack_exponent(*div[i], &ed[i * EXPW]);
+        pack_form(f_, frec.data());
+        void *de = nullptr, *dd = nullptr;
+        check(cofhe_hip_malloc(ctx_, ee.size() * 4 + 4, &de)); Guard g1{ctx_, de};
+        check(cofhe_hip_malloc(ctx_, ed.size() * 4 + 4, &dd)); Guard g2{ctx_, dd};
+        check(cofhe_hip_upload(ctx_, de, ee.data(), ee.size() * 4, nullptr));
+        check(cofhe_hip_upload(ctx_, dd, ed.data(), ed.size() * 4, nullptr));
+        DeviceTensor out = alloc(e.is_zero_degree() ? std::vector<size_t>{1} : e.shape(), E);
+        check(cofhe_hip_div_close_records(ctx_, de, dd, nd, rq.ptr_, frec.data(), out.ptr_, E, k_, nullptr));
+        check(cofhe_hip_stream_sync(ctx_, nullptr));          // `ee` and `ed` go with this frame
+        return out;
     }
 
     // ---- device-resident variants -------------------------------------------------------------

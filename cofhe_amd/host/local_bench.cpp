@@ -667,6 +667,155 @@ static void bench_poly_activation(size_t n, int runs) {
     if (!ok) throw std::runtime_error("polynomial activation mismatch");
 }
 
+// division of a ciphertext tensor by public divisors from one opened value per element
+// (LocalCipherTextMultiplier::divide_ciphertext_tensor_by_plaintext), through the single-key and the 2-of-3 threshold client:
+// a scalar divisor, a per-channel divisor (4 channels) and truncate by 2^16 over n elements with |x| < 2^40 of both signs (a
+// wrap then has probability below 2^-80 per element at k = 128); every decrypted element must be floor(x / D) from GMP on the
+// host or one less; prints client.decrypted_elements() per call, which must equal the element count.  runs > 0: the median
+// wall clock of `runs` scalar divisions on one line for tools/bench_ops.py
+static void bench_divide(size_t n, int runs) {
+    auto cs = make_cryptosystem(128, 128, Device::GPU);
+    using CS = decltype(cs);
+    auto sk = cs.keygen();
+    const uint32_t k = cs.message_bits();
+    const size_t C = n % 4 == 0 ? 4 : 1;
+    Tensor<CS::PlainText *> px(n, nullptr);
+    std::vector<Mpz> xs(n);                                         // signed values
+    for (size_t i = 0; i < n; i++) {
+        // 0, 1, -1, the ends of the range, then uniform ones of both signs
+        Mpz x = i < 2 ? Mpz((unsigned long)i) : cs.random_plaintext(40);
+        if (i == 3 || i == 4) {
+            mpz_set_ui(x.get(), 0);
+            mpz_setbit(x.get(), 40);
+            mpz_sub_ui(x.get(), x.get(), 1);
+        }
+        if (i == 2) mpz_set_ui(x.get(), 1);
+        if (i == 2 || i == 4 || (i > 4 && i % 2)) x.neg();
+        xs[i] = x;
+        Mpz m;
+        mpz_fdiv_r_2exp(m.get(), x.get(), k);
+        px[i] = new CS::PlainText(m);
+    }
+    Mpz seven(7ul), per_channel[4] = {Mpz(3ul), Mpz(1000003ul), Mpz(1ul), Mpz(2ul)};
+    mpz_mul_2exp(per_channel[1].get(), per_channel[1].get(), 20);   // beyond one limb
+    Tensor<CS::PlainText *> dscalar(1, &seven), dchan(C, nullptr);
+    for (size_t c = 0; c < C; c++) dchan[c] = &per_channel[c];
+    const uint32_t t_bits = 16;
+    // res decrypts to floor(x / D) or one less, as residues mod 2^k
+    auto agrees = [&](const Tensor<CS::PlainText *> &dec, const Tensor<CS::PlainText *> &div) {
+        bool pass = true;
+        for (size_t i = 0; i < n; i++) {
+            Mpz q, q1, a, b;
+            mpz_fdiv_q(q.get(), xs[i].get(), div[i % div.num_elements()]->get());
+            mpz_sub_ui(q1.get(), q.get(), 1);
+            mpz_fdiv_r_2exp(a.get(), q.get(), k);
+            mpz_fdiv_r_2exp(b.get(), q1.get(), k);
+            if (!(*dec.at(i) == a) && !(*dec.at(i) == b)) pass = false;
+        }
+        return pass;
+    };
+    bool ok = true;
+    for (int threshold = 0; threshold < 2; threshold++) {
+        std::unique_ptr<LocalSMPCClient<CS>> client(threshold ? new LocalSMPCClient<CS>(cs, sk, 2, 3) : new LocalSMPCClient<CS>(cs, sk));
+        LocalCipherTextMultiplier<CS> mul(*client);
+        auto cx = cs.encrypt_tensor(client->network_public_key(), px);
+        Mpz two_t;
+        mpz_setbit(two_t.get(), t_bits);
+        Tensor<CS::PlainText *> dtrunc(1, &two_t);
+        const char *names[3] = {"scalar divisor 7", "per-channel divisors", "truncate by 2^16"};
+        for (int what = 0; what < 3; what++) {
+            const size_t before = client->decrypted_elements();
+            cs.synchronize();
+            auto t0 = Clock::now();
+            auto res = what == 0 ? mul.divide_ciphertext_tensor_by_plaintext(cx, dscalar)
+                       : what == 1 ? mul.divide_ciphertext_tensor_by_plaintext(cx, dchan)
+                                   : mul.truncate_ciphertext_tensor(cx, t_bits);
+            cs.synchronize();
+            const double ms = std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
+            const size_t opened = client->decrypted_elements() - before;
+            auto dec = cs.decrypt_tensor(sk, res);
+            const bool pass = opened == n && agrees(dec, what == 0 ? dscalar : what == 1 ? dchan : dtrunc);
+            if (!threshold && what == 0) std::ofstream("local_bench_divide.bin", std::ios::binary) << cs.serialize_ciphertext_tensor(res);
+            std::cout << "  " << (threshold ? "threshold 2 of 3" : "secret key") << ": " << names[what] << " over " << n << " elements, opened_values "
+                      << opened << ", " << ms << " ms (host wall clock, pair generation and the decryption included): " << (pass ? "ok" : "FAILED")
+                      << std::endl;
+            ok = ok && pass;
+            free_all(res); free_all(dec);
+        }
+        if (!threshold) {
+            // the parts on their own: one 0-D element, the plaintext division, an invalid divisor, and the mean of 2 x 2 windows
+            auto q0 = mul.divide_ciphertext_tensor_by_plaintext(Tensor<CS::CipherText *>(cx[2 % n]), Tensor<CS::PlainText *>(&seven));
+            auto dq0 = cs.decrypt(sk, *q0.get_value());
+            auto pq = cs.divide_plaintext_tensor(px, dscalar);
+            bool parts = q0.is_zero_degree();
+            for (size_t i = 0; i < n; i++) {
+                Mpz q, a, b;
+                mpz_fdiv_q(q.get(), xs[i].get(), seven.get());
+                mpz_fdiv_r_2exp(a.get(), q.get(), k);
+                mpz_sub_ui(q.get(), q.get(), 1);
+                mpz_fdiv_r_2exp(b.get(), q.get(), k);
+                if (!(*pq.at(i) == a)) parts = false;
+                if (i == 2 % n && !(dq0 == a) && !(dq0 == b)) parts = false;
+            }
+            Mpz zero(0ul);
+            bool refused = false;
+            try {
+                (void)mul.divide_ciphertext_tensor_by_plaintext(cx, Tensor<CS::PlainText *>(1, &zero));
+            } catch (const std::invalid_argument &) {
+                refused = true;
+            }
+            parts = parts && refused;
+            if (n % 4 == 0) {
+                Tensor<CS::CipherText *> img = cx;
+                img.reshape({1, 2, 2, n / 4});
+                auto avg = mul.avg_pool2d_ciphertext_tensor(img, {2, 2}, {2, 2});
+                auto davg = cs.decrypt_tensor(sk, avg);
+                for (size_t c = 0; c < n / 4; c++) {
+                    Mpz s, q, a, b;
+                    for (size_t p = 0; p < 4; p++) mpz_add(s.get(), s.get(), xs[p * (n / 4) + c].get());
+                    mpz_fdiv_q_ui(q.get(), s.get(), 4);
+                    mpz_fdiv_r_2exp(a.get(), q.get(), k);
+                    mpz_sub_ui(q.get(), q.get(), 1);
+                    mpz_fdiv_r_2exp(b.get(), q.get(), k);
+                    if (!(*davg[c] == a) && !(*davg[c] == b)) parts = false;
+                }
+                free_all(avg); free_all(davg);
+            }
+            std::cout << "  0-D division, divide_plaintext_tensor, the refusal of divisor 0, avg_pool2d: " << (parts ? "ok" : "FAILED") << std::endl;
+            ok = ok && parts;
+            delete q0.get_value();
+            free_all(pq);
+        }
+        free_all(cx);
+    }
+    {
+        Mpz ad = cs.discriminant();
+        ad.neg();
+        std::ofstream("local_bench_absdelta.txt") << ad.str() << "\n";
+    }
+    if (runs > 0) {
+        LocalSMPCClient<CS> client(cs, sk);
+        LocalCipherTextMultiplier<CS> mul(client);
+        auto cx = cs.encrypt_tensor(client.network_public_key(), px);
+        std::vector<double> ms;
+        for (int pass = 0; pass <= runs; pass++) {
+            cs.synchronize();
+            auto t0 = Clock::now();
+            auto res = mul.divide_ciphertext_tensor_by_plaintext(cx, dscalar);
+            cs.synchronize();
+            if (pass) ms.push_back(std::chrono::duration<double, std::milli>(Clock::now() - t0).count());
+            free_all(res);
+        }
+        free_all(cx);
+        std::sort(ms.begin(), ms.end());
+        std::cout << "divide_json: {\"E\": " << n << ", \"runs\": " << runs << ", \"divide_ms\": " << ms[ms.size() / 2] << ", \"divide_ms_min_max\": ["
+                  << ms.front() << ", " << ms.back() << "]}" << std::endl;
+    }
+    std::cout << "  agree: " << (ok ? "yes" : "NO") << std::endl;
+    free_all(px);
+    if (!ok) throw std::runtime_error("division mismatch");
+}
+
 // threshold decryption end to end (the reference has no local benchmark for it; the calls are the
 // ones PartialDecryptionRequestHandler / SMPCClient make, partial_decryption_request_handler.hpp:140,
 // smpc_client.hpp:137): share sk t-out-of-n, every party of the first threshold set runs
@@ -1180,7 +1329,7 @@ static void plaintexts_mode(const char *in, const char *out) {
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        std::cerr << "Usage: " << argv[0] << " <encrypt_decrypt|ciphertext_matadd|scal_matmul|threshold|ciphertext_matmul|fresh_randomness|affine|beaver_direct|plain_ct_matmul|ciphertext_matmul_matrix|conv2d|conv2d_grouped|sum_pool2d|poly_activation> [sizes]" << std::endl;
+        std::cerr << "Usage: " << argv[0] << " <encrypt_decrypt|ciphertext_matadd|scal_matmul|threshold|ciphertext_matmul|fresh_randomness|affine|beaver_direct|plain_ct_matmul|ciphertext_matmul_matrix|conv2d|conv2d_grouped|sum_pool2d|poly_activation|divide> [sizes]" << std::endl;
         return 1;
     }
     std::string mode = argv[1];
@@ -1236,6 +1385,9 @@ int main(int argc, char **argv) {
         } else if (mode == "poly_activation") {
             // elements [runs]: with runs > 0 also the timed comparison with two chained Beaver products
             bench_poly_activation(argc > 2 ? std::stoul(argv[2]) : 64, argc > 3 ? std::stoi(argv[3]) : 0);
+        } else if (mode == "divide") {
+            // elements [runs]: with runs > 0 also the timed scalar division
+            bench_divide(argc > 2 ? std::stoul(argv[2]) : 64, argc > 3 ? std::stoi(argv[3]) : 0);
         } else if (mode == "formats") {
             bench_formats();
         } else if (mode == "threads") {

@@ -27,6 +27,11 @@
 // polynomial with plaintext coefficients by chained products opens 2 (d - 1) values per element in d - 1 rounds.  With a power
 // tuple ([a], .., [a^d]) per element:  e = Dec(x - a);  [p(x)] = prod_i [a^i]^(q_i(e)) o f^(q_0(e)),  q the Taylor shift of p at
 // e mod 2^k -- one opened value and one round whatever d (poly_close_ciphertext_tensor, on the device from end to end).
+//
+// Division by public divisors (divide_ciphertext_tensor_by_plaintext, truncate_ciphertext_tensor, avg_pool2d_ciphertext_tensor;
+// the reference's ComputeOperation::DIVIDE answers "Not implemented").  With a division pair ([r], [r_q]), r_q = floor(s(r) / D),
+// per element:  e = Dec(x - r);  [y] = [r_q] o f^(floor(s(e) / D)),  s the centred residue mod 2^k -- one opened value, no
+// encryption, no ladder; y is floor(x / D) or one less unless s(r) + s(e) wraps (probability |x| / 2^k per element).
 #pragma once
 #include "hip_cryptosystem.hpp"
 
@@ -121,6 +126,23 @@ class LocalSMPCClient {
         for (size_t i = 0; i < n; i++) {
             delete pa[i];
             delete pw[i];
+        }
+        return t;
+    }
+
+    // division pairs for n elements and the public divisors div (element i takes divisor i mod count): {[r], [r_q]} with r
+    // uniform in Z/2^k per element and r_q = floor(s(r) / D) mod 2^k (divide_plaintext_tensor), used once; the caller owns the
+    // elements.  Like the triplets, the pairs of the networked system would come from a protocol between the nodes.
+    Vector<Tensor<CipherText *>> get_division_pairs(size_t n, const Tensor<PlainText *> &div) {
+        Tensor<PlainText *> pr(n, nullptr);
+        for (size_t i = 0; i < n; i++) pr[i] = new PlainText(cs_.random_plaintext(cs_.message_bits()));
+        auto prq = cs_.divide_plaintext_tensor(pr, div);
+        Vector<Tensor<CipherText *>> t;
+        t.push_back(cs_.encrypt_tensor(pk_, pr));
+        t.push_back(cs_.encrypt_tensor(pk_, prq));
+        for (size_t i = 0; i < n; i++) {
+            delete pr[i];
+            delete prq[i];
         }
         return t;
     }
@@ -240,6 +262,57 @@ class LocalCipherTextMultiplier {
         Tensor<PlainText *> coef(3, &zero);
         coef[2] = &one;
         return evaluate_polynomial_ciphertext_tensor(coef, x);
+    }
+
+    // floor(x / D) element-wise for public divisors D, 1 <= D < 2^(k-1), x read as its centred residue: with a division pair
+    // ([r], [r_q]) per element, ONE opened value e = Dec(x - r) and one round; the result is the floor quotient or one less
+    // unless s(r) + s(e) wraps, which has probability |x| / 2^k per element (the caller keeps |x| <= 2^(k-1-sigma)).  div holds
+    // one divisor, or one per channel of a channels-last tensor (its count divides x's), or one per element.  0-D and 1-D
+    // tensors; higher ranks are flattened and the result reshaped.
+    Tensor<CipherText *> divide_ciphertext_tensor_by_plaintext(const Tensor<CipherText *> &x, const Tensor<PlainText *> &div) {
+        if (x.is_zero_degree()) {
+            Tensor<CipherText *> r = divide_ciphertext_tensor_by_plaintext(Tensor<CipherText *>(1, x.get_value()), div);
+            return Tensor<CipherText *>(r.at(0));
+        }
+        auto &cs = client_m.crypto_system();
+        const auto &pk = client_m.network_public_key();
+        const size_t n = x.num_elements();
+        Tensor<PlainText *> d = div.is_zero_degree() ? Tensor<PlainText *>(1, div.get_value()) : div;
+        d.flatten();
+        cs.check_divisors(d, n);
+        Tensor<CipherText *> flat = x;
+        flat.flatten();
+        auto pairs = client_m.get_division_pairs(n, d);
+        auto x_sub_r = cs.sub_ciphertext_tensors(pk, flat, pairs[0]);
+        auto e = client_m.decrypt_tensor(x_sub_r);
+        auto ct = cs.div_close_ciphertext_tensor(pk, e, d, pairs[1]);
+        for (size_t i = 0; i < n; i++) {
+            for (auto &p : pairs) delete p[i];
+            delete x_sub_r[i];
+            delete e[i];
+        }
+        ct.reshape(x.shape());
+        return ct;
+    }
+    // floor(x / 2^t): the rescale after a product of two fixed-point values, 1 <= t <= k - 2
+    Tensor<CipherText *> truncate_ciphertext_tensor(const Tensor<CipherText *> &x, uint32_t t) {
+        if (t == 0 || t + 2 > client_m.crypto_system().message_bits()) throw std::invalid_argument("truncate_ciphertext_tensor: 1 <= t <= k - 2");
+        PlainText D;
+        mpz_setbit(D.get(), t);
+        return divide_ciphertext_tensor_by_plaintext(x, Tensor<PlainText *>(1, &D));
+    }
+    // average pooling, channels last: sum_pool2d_ciphertext_tensor over kernel[0] x kernel[1] windows, then the division by
+    // kernel[0] kernel[1]: the floor of the mean or one less.  Padding counts as zeros in the mean.
+    Tensor<CipherText *> avg_pool2d_ciphertext_tensor(const Tensor<CipherText *> &x, const std::array<size_t, 2> &kernel,
+                                                      const std::array<size_t, 2> &stride, const std::array<size_t, 2> &pad = {0, 0}) {
+        auto &cs = client_m.crypto_system();
+        auto sums = cs.sum_pool2d_ciphertext_tensor(client_m.network_public_key(), x, kernel, stride, pad);
+        PlainText D((unsigned long)(kernel[0] * kernel[1]));
+        auto res = divide_ciphertext_tensor_by_plaintext(sums, Tensor<PlainText *>(1, &D));
+        Tensor<CipherText *> flat = sums;
+        flat.flatten();
+        for (size_t i = 0; i < flat.num_elements(); i++) delete flat[i];
+        return res;
     }
 
     // element-wise products of two 1-D ciphertext tensors (:115-160), same order of calls

@@ -22,6 +22,9 @@
  *   cofhe_hip_pow_dot_records,       nothing: a polynomial with plaintext coefficients on a ciphertext tensor from ONE opened
  *   cofhe_hip_poly_shift_records,    value per element (power tuples); ComputeOperation's POLYNOMIAL_EVALUATION is commented out
  *   cofhe_hip_poly_close_...         (include/node/compute_request_handler.hpp:74)
+ *   cofhe_hip_divfloor_plain_...,    nothing: a ciphertext tensor divided by public divisors (rescale, mean, average pool) from ONE
+ *   cofhe_hip_div_close_...          opened value per element (division pairs); ComputeOperation::DIVIDE answers "Not implemented"
+ *                                    (include/node/compute_request_handler.hpp:73, 343-344)
  *   cofhe_hip_decrypt_records        decrypt_tensor's per-element work, cpu_cryptosystem_tensor_ops.inl:21-33
  *   cofhe_hip_part_decrypt_records,  part_decrypt_tensor / combine_part_decryption_results_tensor,
  *   cofhe_hip_combine_part_...       cpu_cryptosystem_tensor_ops.inl:35-73 (cpu_cryptosystem_distributed.inl:231-285)
@@ -281,6 +284,36 @@ int cofhe_hip_poly_shift_records(cofhe_hip_ctx *ctx, const void *d_coef, const v
  * 1 <= d <= COFHE_HIP_POLY_MAX_DEGREE; d_out must not overlap an input (COFHE_HIP_EINVAL). */
 int cofhe_hip_poly_close_records(cofhe_hip_ctx *ctx, const void *d_coef, const void *d_e, const void *d_powers, const uint32_t *f_record,
                                  void *d_out, uint64_t n_ct, uint32_t d, uint32_t kbits, void *stream);
+/* ---- division by public divisors from one opened value (cofhe_amd/csrc/divide.hip) ----
+ * Plaintexts live in Z/2^k; s(v) is the centred residue of v in [-2^(k-1), 2^(k-1)); D is a public divisor, 1 <= D < 2^(k-1).
+ * A DIVISION PAIR of an element is ([r], [r_q]) with r uniform in Z/2^k and r_q = floor(s(r) / D) mod 2^k, used once.  With the
+ * ONE opened value e = Dec([x] - [r]) -- uniform whatever x is, so it hides x perfectly --
+ *   [y] = [r_q] o f^(e_q) = (c1, c2 o f^(e_q)) of [r_q],   e_q = floor(s(e) / D) mod 2^k:
+ * no encryption, no ladder.  If s(x) = s(r) + s(e) over the integers, floor(s(x) / D) - s(y) is 0 or 1: the floor quotient or
+ * one less.  Otherwise the sum wrapped, which happens with probability |s(x)| / 2^k over r and puts the result off by about
+ * 2^k / D.  THE CALLER'S CONTRACT: |x| <= 2^(k-1-sigma) gives a failure probability of at most 2^(-sigma-1) per element (k = 128
+ * with 64-bit values: 2^-64).  The reference has no such operation (ComputeOperation::DIVIDE answers "Not implemented",
+ * include/node/compute_request_handler.hpp:73, 343-344). */
+#define COFHE_HIP_DIV_MAX_KBITS 639
+/* q[e] = floor(s(v[e]) / div[e mod n_div]) mod 2^kbits, e < n, on exponent records: the signed floor division, one 8-lane limb
+ * group per element.  v enters as a residue mod 2^kbits as in cofhe_hip_matmul_plain_plain_records (sign word honoured,
+ * magnitudes of 2^kbits and above reduced, -0 fine) and is negative when bit kbits - 1 of the residue is set; q lies in
+ * [0, 2^kbits) with sign word 0.  div: n_div records, element e reads divisor e mod n_div (n_div = 1: a scalar; the channel
+ * count of a channels-last tensor: per channel; n: element-wise).  An INVALID divisor (sign word set, residue 0, or 2^(kbits-1)
+ * and above) gives quotient 0 and sets the division bit (4) of cofhe_hip_device_status.  One launch ("k_plain_divfloor" under
+ * "profile_kernels"), purely stream-ordered: no workspace, no read-back, no lock.  COFHE_HIP_EINVAL, nothing written: kbits = 0 or
+ * kbits > COFHE_HIP_DIV_MAX_KBITS; n_div = 0; n no multiple of n_div; d_q overlapping an input.  n = 0 does nothing. */
+int cofhe_hip_divfloor_plain_records(cofhe_hip_ctx *ctx, const void *d_v, const void *d_div, uint64_t n_div, void *d_q, uint64_t n,
+                                     uint32_t kbits, void *stream);
+/* The closing step: out[e] = (c1, c2 o f^(e_q[e])) of rq[e], e_q[e] = floor(s(e[e]) / div[e mod n_div]) mod 2^kbits, an encryption
+ * of floor(s(x[e]) / D) or one less when rq[e] = [r_q] of the element's division pair and e[e] = x[e] - r (see above).  d_e: n_ct
+ * exponent records; d_div: n_div; d_rq: n_ct ciphertexts; f_record: HOST record of f.  Two steps on `stream`:
+ * cofhe_hip_divfloor_plain_records into a block of the block cache (which goes back behind the work queued on `stream`), and the
+ * plaintext addend of cofhe_hip_add_plain_records (mode 0, no randomness) on d_rq against the cached table of f.  Uses the block
+ * cache and, through the addend, the workspace plan "comb" (kind 3).  No read-back.  d_out must not overlap an input
+ * (COFHE_HIP_EINVAL, as for the refusals above). */
+int cofhe_hip_div_close_records(cofhe_hip_ctx *ctx, const void *d_e, const void *d_div, uint64_t n_div, const void *d_rq,
+                                const uint32_t *f_record, void *d_out, uint64_t n_ct, uint32_t kbits, void *stream);
 /* decryption: for each of n ciphertexts, m with c2 o (c1^sk)^-1 = f^m.  sk: one exponent record on
  * the device; f_record: HOST pointer to the 168-word record of f = (2^(2k), 2^(k+1), 1 - Delta_K)
  * (its table of f^(-2^j) is built on first use and cached in the context).  d_out receives
@@ -476,6 +509,12 @@ int cofhe_hip_sum_pool2d_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *cts, s
 int cofhe_hip_poly_close_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *coef, size_t lcoef, const uint8_t *e, size_t le,
                                        const uint8_t *powers, size_t lp, const uint32_t *f_record, uint32_t kbits, uint8_t **out,
                                        size_t *outlen);
+/* the serialised twin of cofhe_hip_div_close_records: e a plaintext tensor of any shape, div a plaintext tensor of one element, of
+ * e's last dimension (1-D: per channel) or of e's shape, rq the ciphertext tensor [r_q] of e's shape; the result is a ciphertext
+ * tensor of e's shape.  The divisors are host values here: one that is not in [1, 2^(kbits-1)) is COFHE_HIP_EINVAL.  Incoming
+ * forms are validated (COFHE_HIP_EINVAL for a non-form); COFHE_HIP_ESHAPE when the shapes do not fit.  f_record: HOST record of f. */
+int cofhe_hip_div_close_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *e, size_t le, const uint8_t *div, size_t ldiv, const uint8_t *rq,
+                                      size_t lrq, const uint32_t *f_record, uint32_t kbits, uint8_t **out, size_t *outlen);
 /* s: plaintext tensor; 1-D x 1-D -> element-wise, 2-D x 2-D -> matmul (zero: 1-element tensor) */
 int cofhe_hip_scal_ciphertext_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *s, size_t ls,
                                             const uint8_t *cts, size_t lc, const uint8_t *zero, size_t lz,

@@ -6,7 +6,9 @@ accumulation of the ct x ct product.  --conv-only: only the depthwise convolutio
 block-diagonal dense filter through the ungrouped entry (the way these layers were written before the convolution had groups),
 the two alternating in one run; --out FILE also writes those lines to FILE.  --poly-only: only the polynomial evaluation, by the
 same method: cofhe_hip_pow_dot_records against the ladders and additions it replaces, and the one-opened-value protocol against
-chained Beaver products (through local_bench); written to profiles/r12_poly/poly_time.json, or to --out FILE."""
+chained Beaver products (through local_bench); written to profiles/r12_poly/poly_time.json, or to --out FILE.  --div-only: only
+the division by public divisors: k_plain_divfloor alone from its "profile_kernels" spans, the closing step next to a decryption,
+and the protocol through local_bench with the kernel's share of it; written to profiles/r13_div/div_time.json, or to --out FILE."""
 import json
 import os
 import sys
@@ -178,6 +180,73 @@ if "--poly-only" in sys.argv:
         json.dump(res, fh, indent=1)
     sys.exit(0 if all(r["same_records"] and r["device_status"] == 0 for r in res) else 1)
 
+# ---- division by public divisors: the kernel alone, the closing step, the protocol ------------------------------------------
+def div_ops(runs=5):
+    """"plain_divfloor": k_plain_divfloor alone at E = 16384 and E = 256, k-bit numerators, divisors of 16 bits (the word route of
+    mp_divrem) and of 64 bits (its long division), from the spans of "profile_kernels" (20 launches each after a warm-up) next
+    to the wall clock of the call.  "div_close": cofhe_hip_div_close_records at E = 256 by the wall clock, its kernel's span, and
+    cofhe_hip_decrypt_records over the same 256 ciphertexts for scale.  "divide": divide_ciphertext_tensor_by_plaintext over 256
+    elements through the host harness, single-key client, pair generation and the decryption included (local_bench divide 256
+    <runs> prints the line), and the share of it that the kernel's two launches (r_q of the pairs, e_q of the opened values) take"""
+    import subprocess
+    lines = []
+    f_rec = form_record(hx(prm["f"]["a"]), hx(prm["f"]["b"]), hx(prm["f"]["c"]))
+    kernel_ms = {}
+    for E in (16384, 256):
+        v = dev_i32(exp_records([rng.bits(K) for _ in range(E)]))
+        q = torch.zeros(E * 32, dtype=torch.int32, device=dev)
+        for dbits in (16, 64):
+            dv = dev_i32(exp_records([rng.bits(dbits) | (1 << (dbits - 1))]))
+            call = lambda: eng.divfloor_plain_records(v.data_ptr(), dv.data_ptr(), 1, q.data_ptr(), E, K)  # noqa: E731
+            wall = timed(call, reps=20)
+            eng.profile_read("k_plain_divfloor", clear=True)
+            eng.set_option("profile_kernels", 1)
+            for _ in range(20):
+                call()
+            torch.cuda.synchronize()
+            eng.set_option("profile_kernels", 0)
+            ms, launches = eng.profile_read("k_plain_divfloor", clear=True)
+            kernel_ms[(E, dbits)] = ms / launches
+            line = {"op": "plain_divfloor", "E": E, "kbits": K, "divisor_bits": dbits, "kernel_ms": round(ms / launches, 4), "launches": launches,
+                    "call_wall_ms": round(wall * 1e3, 4), "elements_per_s": round(E / (ms / launches) * 1e3, 1), "device_status": eng.device_status()}
+            print(json.dumps(line), flush=True)
+            lines.append(line)
+    E = 256
+    rq, out = fresh(E), torch.zeros(E * 336, dtype=torch.int32, device=dev)
+    e = dev_i32(exp_records([rng.bits(K) for _ in range(E)]))
+    dv = dev_i32(exp_records([7]))
+    close = lambda: eng.div_close_records(e.data_ptr(), dv.data_ptr(), 1, rq.data_ptr(), f_rec, out.data_ptr(), E, K)  # noqa: E731
+    t_close = [timed(close, reps=10) for _ in range(runs)]
+    dsk = dev_i32(exp_records([hx(prm["sk"])]))
+    pt = torch.zeros(E * ((K + 31) // 32 + 1), dtype=torch.int32, device=dev)
+    t_dec = [timed(lambda: eng.decrypt_records(out.data_ptr(), dsk.data_ptr(), f_rec, pt.data_ptr(), E, K), reps=10) for _ in range(runs)]
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    line = {"op": "div_close", "E": E, "kbits": K, "div_close_ms": round(med(t_close) * 1e3, 3),
+            "div_close_ms_min_max": [round(min(t_close) * 1e3, 3), round(max(t_close) * 1e3, 3)], "kernel_ms": round(kernel_ms[(E, 16)], 4),
+            "kernel_share_of_close": round(kernel_ms[(E, 16)] / (med(t_close) * 1e3), 4), "decrypt_ms": round(med(t_dec) * 1e3, 3),
+            "decrypt_ms_min_max": [round(min(t_dec) * 1e3, 3), round(max(t_dec) * 1e3, 3)], "runs": runs, "device_status": eng.device_status()}
+    print(json.dumps(line), flush=True)
+    lines.append(line)
+    exe = os.path.join(ROOT, "cofhe_amd", "host", "local_bench")
+    r = subprocess.run([exe, "divide", "256", str(runs)], capture_output=True, text=True, cwd=os.environ.get("TMPDIR", "/tmp"))
+    line = {"op": "divide", "device_status": 0, "exit_status": r.returncode, "agree": "agree: yes" in r.stdout}
+    for ln in r.stdout.splitlines():
+        if ln.startswith("divide_json: "):
+            line.update(json.loads(ln[len("divide_json: "):]))
+            line["kernel_share_of_protocol"] = round(2 * kernel_ms[(256, 16)] / line["divide_ms"], 5)
+    print(json.dumps(line), flush=True)
+    lines.append(line)
+    return lines
+
+
+if "--div-only" in sys.argv:
+    res = div_ops()
+    path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "r13_div", "div_time.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as fh:
+        json.dump(res, fh, indent=1)
+    sys.exit(0 if all(r["device_status"] == 0 and r.get("exit_status", 0) == 0 and r.get("agree", True) for r in res) else 1)
+
 # ---- matadd C2 / C5 ---------------------------------------------------------------------------
 for side in ((128,) if (QUICK or "big" in SKIP) else (128, 1024)):
     E = side * side
@@ -257,6 +326,14 @@ sec = timed(lambda: eng.add_plain_records(cts.data_ptr(), pm.data_ptr(), f_rec, 
                                           pk_record=pk_rec), reps=3)
 emit("add_plaintext_tensor with fresh randomness (cofhe_hip_add_plain_records, d_r)", [E], sec, E, "ciphertexts/s",
      kernel="k_comb_first + k_compose_pairs tree")
+# the division by a public divisor: the signed floor division on exponent records alone, and the closing step on [r_q]
+pdiv, pquot = dev_i32(exp_records([(1 << 64) + 13])), torch.zeros(E * 32, dtype=torch.int32, device=dev)
+sec = timed(lambda: eng.divfloor_plain_records(pm.data_ptr(), pdiv.data_ptr(), 1, pquot.data_ptr(), E, K), reps=10)
+emit("divide_plaintext_tensor (cofhe_hip_divfloor_plain_records, 65-bit divisor)", [E], sec, E, "elements/s", kernel="k_plain_divfloor")
+sec = timed(lambda: eng.div_close_records(pm.data_ptr(), pdiv.data_ptr(), 1, cts.data_ptr(), f_rec, out.data_ptr(), E, K), reps=3)
+emit("div_close_ciphertext_tensor (cofhe_hip_div_close_records)", [E], sec, E, "ciphertexts/s",
+     kernel="k_plain_divfloor + k_comb_first + k_compose_pairs tree")
+del pdiv, pquot
 ha, hb = (eng.records_to_bytes(t.cpu().numpy().view(np.uint32), [128, 128]) for t in (cts, other))
 t0 = time.perf_counter()
 hc = eng.sub_ciphertext_tensors(ha, hb)
