@@ -128,8 +128,9 @@ int cofhe_hip_stream_sync(cofhe_hip_ctx *ctx, void *stream);
  * silently: 1 = remainder sequence, 2 = reduction, 4 = division (by zero / no end).  clear != 0 resets it.
  * Synchronises `stream`. */
 int cofhe_hip_device_status(cofhe_hip_ctx *ctx, uint32_t *word, int clear, void *stream);
-/* *all_valid = 1 when every one of the n form records is a reduced form of the context's discriminant
- * (a, c > 0, |b| <= a <= c, canonical sign, b^2 - 4ac = Delta).  cofhe_hip_unpack_tensor_device and the *_bytes
+/* *all_valid = 1 when every one of the n form records is a reduced, primitive form of the context's discriminant
+ * (a, c > 0, |b| <= a <= c, canonical sign, b^2 - 4ac = Delta, and a, b, c not all even: for a CL_HSM2k discriminant
+ * that is gcd(a, b, c) = 1, for one with an odd square factor it is necessary only).  cofhe_hip_unpack_tensor_device and the *_bytes
  * operations run this on everything they deserialise; records produced by the kernels themselves need no check.
  * Synchronises `stream`. */
 int cofhe_hip_validate_records(cofhe_hip_ctx *ctx, const void *d_records, uint64_t n_records, int *all_valid, void *stream);

@@ -308,6 +308,18 @@ void sim_reduce(uint32_t *a, uint32_t *b, int *bneg, uint32_t *cc, int count) {
         }
     });
 }
+// the form gate (qf.hpp: qf_form_faults, what k_validate_forms reports on): verdicts[i] = the failed clauses of record i,
+// one bit each (QF_BAD_*), 0 = the record may enter the arithmetic
+void sim_validate(const uint32_t *recs, int n, const uint32_t *absdelta, uint32_t *verdicts) {
+    run_group([&](Ctx &c) {
+        for (int i = 0; i < n; i++) {
+            QForm f;
+            qf_load(c, f, recs + (size_t)REC_WORDS * i);
+            const uint32_t bad = qf_form_faults(c, f, absdelta);
+            if (c.gl == 0) verdicts[i] = bad;
+        }
+    });
+}
 // out[i] = base[i] ^ exps[i]  (exponent records of 32 words, qf.hpp) -- the binary ladder,
 // the sign / zero handling and qf_inverse
 void sim_pow(const uint32_t *base, const uint32_t *exps, const uint32_t *one, uint32_t *out, int count, int half_dbits,

@@ -85,6 +85,28 @@ def record_form(r):
     return a, (-b if r[160] else b), c
 
 
+def raw_record(a: int, b_mag: int, sign_word: int, c: int) -> np.ndarray:
+    """a record word for word: any sign word, any magnitudes that fit the planes (what the form gate has to judge)"""
+    r = np.zeros(REC_WORDS, dtype=np.uint32)
+    r[0:40] = to_limbs(a, 40)
+    r[40:80] = to_limbs(b_mag, 40)
+    r[80:160] = to_limbs(c, 80)
+    r[160] = sign_word
+    return r
+
+
+def validate(raw, delta, L=None):
+    """the form gate (qf.hpp: qf_form_faults) on the host simulator: raw = [(a, |b|, sign word, c)]; returns one word per
+    record, the failed clauses (bit i = clause i of form_gate_cases.CLAUSES), 0 for a record the gate lets through"""
+    L = L or lib()
+    n = len(raw)
+    recs = np.concatenate([raw_record(*r) for r in raw])
+    ad = to_limbs(-delta, 80)
+    out = np.full(n, 0xFFFFFFFF, dtype=np.uint32)
+    L.sim_validate(P(recs), n, P(ad), P(out))
+    return [int(v) for v in out]
+
+
 def compose(forms1, forms2, half_dbits, delta=None):
     """delta: the (negative) discriminant; when omitted it is derived from the first form"""
     n = len(forms1)

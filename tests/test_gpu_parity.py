@@ -476,7 +476,7 @@ def test_wire_format_on_device_rejects_malformed(params128):
     # the arithmetic: wrong discriminant, not reduced (a > c), non-canonical sign (b = -a)
     g = _random_tensor(d, 1, 9, nbase=1)[0][0]
     for forged in (P.Form((1 << 900) + 12345, 7, 5), P.Form(g.c, -g.b, g.a) if g.a != g.c else P.Form(g.a + 1, g.b, g.c),
-                   P.Form(g.a, g.b, g.c + 1)):
+                   P.Form(g.a, g.b, g.c + 1), P.Form(4, -4, 1 - d // 16)):
         data = P.serialize_ciphertext_tensor([1], [(forged, g)])
         with pytest.raises(CofheHipError, match="not a reduced form"):
             unpack(data)

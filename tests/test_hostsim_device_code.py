@@ -477,6 +477,13 @@ def test_malformed_forms_end_with_a_status_not_a_hang():
     assert len(got) == len(xs)            # returned
     st = L.sim_status()
     assert st & 0x7, "at least one safety cap must have been reported"
+    # a non-primitive form of the right discriminant, (2, 0, |Delta| / 8), which the gate refuses since it checks parity:
+    # what the arithmetic does with it is not specified, only that it returns (both orders, and squared)
+    two = (2, 0, -d // 8)
+    assert two[1] ** 2 - 4 * two[0] * two[2] == d
+    gf = (good.a, good.b, good.c)
+    assert len(S.compose([two, gf, two], [gf, two, two], half, delta=d)) == 3
+    L.sim_status()
     # the simulator is still healthy: a valid composition afterwards is exact
     w = P.compose(good, good)
     assert S.compose([(good.a, good.b, good.c)], [(good.a, good.b, good.c)], half, delta=d) == [(w.a, w.b, w.c)]
