@@ -1,9 +1,10 @@
 // abi.hip -- the C ABI of include/cofhe_hip.h, in this order: the context, the block cache, the launch helpers (spans, the
 // two-build launch, flag words, the table-cache lookup), the workspace plans, the launchers (one launch site per kernel and
 // route; product_tree is the pairwise tree of them all) and the host-side tensor formats.  The kernels are declared in
-// kernels.hpp and defined in cofhe_hip.hip, wide.hip, comb.hip, affine.hip, matmul_left.hip, conv.hip, pow_dot.hip and divide.hip; this
-// file holds no device code of its own.  conv.hip holds the three kernels of the convolution, pow_dot.hip the two of the polynomial
-// evaluation, divide.hip the signed floor division of the division by public divisors.
+// kernels.hpp and defined in cofhe_hip.hip, wide.hip, comb.hip, affine.hip, matmul_left.hip, conv.hip, pow_dot.hip, divide.hip and
+// lut.hip; this file holds no device code of its own.  conv.hip holds the three kernels of the convolution, pow_dot.hip the two of
+// the polynomial evaluation, divide.hip the signed floor division of the division by public divisors, lut.hip the two copies of
+// the table lookups.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -21,6 +22,7 @@
 #include "plain_mm.hpp"
 #include "poly_shift.hpp"
 #include "plain_div.hpp"
+#include "lut.hpp"
 
 using namespace cofhe;
 using namespace cofhe_k;
@@ -1757,6 +1759,97 @@ int cofhe_hip_div_close_records(cofhe_hip_ctx *ctx, const void *d_e, const void 
     if (int rc = q.get(ctx, n_ct * exp_bytes)) return rc;
     if (int rc = cofhe_hip_divfloor_plain_records(ctx, d_e, d_div, n_div, q.p, n_ct, kbits, stream)) return rc;
     return cofhe_hip_add_plain_records(ctx, d_rq, q.p, nullptr, nullptr, nullptr, f_record, d_out, n_ct, kbits, 0, stream);
+}
+
+// ---- table lookups from one opened value (lut.hip) -------------------------------------------------------------------------
+static_assert(COFHE_HIP_LUT_MAX_BITS == LUT_MAX_BITS, "the header's bound is the kernels'");
+namespace {
+// what every lookup entry point refuses before it looks at a pointer: the table width, and element i reading table i mod n_tab
+int lut_check(uint32_t bits, uint64_t n_tab, uint64_t n) {
+    if (bits == 0 || bits > LUT_MAX_BITS) return fail(COFHE_HIP_EINVAL, "lut: a table has 2^bits entries, 1 <= bits <= 12");
+    if (n_tab == 0 || n % n_tab != 0) return fail(COFHE_HIP_EINVAL, "lut: the element count is a multiple of the table count, which is not 0");
+    if (n > (1ull << 36)) return fail(COFHE_HIP_EINVAL, "lut: too many items");
+    return COFHE_HIP_OK;
+}
+}  // namespace
+// touches no shared state of the context: no lock.  16-byte pieces when the table and the output allow them (a caller's
+// pointer is only known to be 4-byte aligned)
+int cofhe_hip_lut_rotate_records(cofhe_hip_ctx *ctx, const void *d_table, uint64_t n_tab, const void *d_r, void *d_out, uint64_t n, uint32_t bits,
+                                 void *stream) {
+    if (int rc = lut_check(bits, n_tab, n)) return rc;
+    if (n == 0) return COFHE_HIP_OK;
+    if (!d_table || !d_r || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
+    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4, out_bytes = (n << bits) * exp_bytes;
+    if (overlaps(d_out, out_bytes, d_table, (n_tab << bits) * exp_bytes) || overlaps(d_out, out_bytes, d_r, n * exp_bytes))
+        return fail(COFHE_HIP_EINVAL, "lut_rotate: the output overlaps an input");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const bool vec16 = (((uintptr_t)d_table | (uintptr_t)d_out) & 15) == 0;
+    const uint64_t total = (n << bits) * (vec16 ? EXP_REC_WORDS / 4 : EXP_REC_WORDS);
+    const unsigned blocks = (unsigned)std::min<uint64_t>((total + 255) / 256, 64u * NUM_CUS);       // grid-stride beyond that
+    {
+        ProfScope ps(ctx, "k_lut_rotate", st);
+        hipLaunchKernelGGL(k_lut_rotate, dim3(blocks), dim3(256), 0, st, (const uint32_t *)d_table, n_tab, (const uint32_t *)d_r, (uint32_t *)d_out, n,
+                           bits, vec16 ? 1u : 0u);
+    }
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+
+// Needs no workspace plan of its own: the rotated rows are one block of the block cache, and the fresh encryption that follows
+// carves the workspace by the plan "comb" (kind 1) over n 2^bits plaintexts.
+int cofhe_hip_lut_tuples_records(cofhe_hip_ctx *ctx, const void *d_table, uint64_t n_tab, const void *d_r, const void *d_rho, const uint32_t *h_record,
+                                 const uint32_t *pk_record, const uint32_t *f_record, void *d_out, uint64_t n, uint32_t bits, uint32_t kbits,
+                                 void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (int rc = lut_check(bits, n_tab, n)) return rc;
+    if (bits > kbits) return fail(COFHE_HIP_EINVAL, "lut: bits <= k");
+    if (int rc = comb_check(1, n << bits, 0, kbits, 0, 0)) return rc;
+    if (n == 0) return COFHE_HIP_OK;
+    if (!d_table || !d_r || !d_rho || !h_record || !pk_record || !f_record || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
+    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4, rows_bytes = (n << bits) * exp_bytes, out_bytes = (n << bits) * 2 * REC_WORDS * 4;
+    if (overlaps(d_out, out_bytes, d_table, (n_tab << bits) * exp_bytes) || overlaps(d_out, out_bytes, d_r, n * exp_bytes) ||
+        overlaps(d_out, out_bytes, d_rho, rows_bytes))
+        return fail(COFHE_HIP_EINVAL, "lut_tuples: the output overlaps an input");
+    DevBuf rows;                                  // T_j = g[(j + r) mod 2^bits], the plaintexts of the tuples
+    rows.stream = stream;
+    if (int rc = rows.get(ctx, rows_bytes)) return rc;
+    if (int rc = cofhe_hip_lut_rotate_records(ctx, d_table, n_tab, d_r, rows.p, n, bits, stream)) return rc;
+    return cofhe_hip_encrypt_fresh_records(ctx, rows.p, d_rho, h_record, pk_record, f_record, d_out, n << bits, kbits, stream);
+}
+
+// touches no shared state of the context: no lock.  One wavefront per output ciphertext, 16-byte pieces when the tuples and the
+// output allow them
+int cofhe_hip_lut_select_records(cofhe_hip_ctx *ctx, const void *d_e, const void *d_tuples, void *d_out, uint64_t n, uint32_t bits, void *stream) {
+    if (int rc = lut_check(bits, 1, n)) return rc;
+    if (n == 0) return COFHE_HIP_OK;
+    if (!d_e || !d_tuples || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
+    const size_t ct_bytes = (size_t)2 * REC_WORDS * 4, out_bytes = n * ct_bytes;
+    if (overlaps(d_out, out_bytes, d_e, n * EXP_REC_WORDS * 4) || overlaps(d_out, out_bytes, d_tuples, (n << bits) * ct_bytes))
+        return fail(COFHE_HIP_EINVAL, "lut_select: the output overlaps an input");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const bool vec16 = (((uintptr_t)d_tuples | (uintptr_t)d_out) & 15) == 0;
+    const unsigned blocks = (unsigned)std::min<uint64_t>((n + LUT_SELECT_WAVES - 1) / LUT_SELECT_WAVES, 0x7FFFFFFFull);      // grid-stride beyond that
+    {
+        ProfScope ps(ctx, "k_lut_select", st);
+        hipLaunchKernelGGL(k_lut_select, dim3(blocks), dim3(LUT_SELECT_THREADS), 0, st, (const uint32_t *)d_e, (const uint32_t *)d_tuples,
+                           (uint32_t *)d_out, n, bits, vec16 ? 1u : 0u);
+    }
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+
+// host only: the tuples of opened values of shape S are a tensor of shape S + [2^bits]
+int cofhe_hip_lut_tuples_shape_bits(uint32_t ndim_e, const uint32_t *shape_e, uint32_t ndim_t, const uint32_t *shape_t, uint32_t *bits) {
+    if (!bits || (ndim_e && !shape_e) || (ndim_t && !shape_t)) return fail(COFHE_HIP_EINVAL, "null argument");
+    uint32_t b = 0;
+    if (ndim_t >= 1)
+        while (b <= LUT_MAX_BITS && (1u << b) != shape_t[ndim_t - 1]) b++;
+    if (ndim_e > 7 || ndim_t != ndim_e + 1 || (ndim_e && memcmp(shape_t, shape_e, 4 * ndim_e) != 0) || b == 0 || b > LUT_MAX_BITS)
+        return fail(COFHE_HIP_ESHAPE, "lut_select: the tuples are a ciphertext tensor of e's shape and a last dimension of 2^bits, 1 <= bits <= 12");
+    *bits = b;
+    return COFHE_HIP_OK;
 }
 
 namespace {

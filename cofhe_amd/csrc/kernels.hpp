@@ -4,7 +4,8 @@
 // undefined symbol when the library is loaded (tests/test_cabi.py).  comb.hip holds the two kernels of the fixed-base comb,
 // affine.hip the ciphertext difference and the record inverse, matmul_left.hip the record transpose and the plaintext
 // matrix product, conv.hip the convolution's level 0, its patch gather and its filter expansion, pow_dot.hip the multi-exponentiation
-// and the Taylor shift of the polynomial evaluation, divide.hip the signed floor division on exponent records.
+// and the Taylor shift of the polynomial evaluation, divide.hip the signed floor division on exponent records, lut.hip the row
+// rotation and the entry selection of the table lookups.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -158,4 +159,12 @@ __global__ void k_poly_shift(const uint32_t *__restrict__ coef, const uint32_t *
 // 2^kbits on exponent records, s the centred residue, one limb group per element
 __global__ void k_plain_divfloor(const uint32_t *__restrict__ v, const uint32_t *__restrict__ div, uint64_t n_div, uint32_t *__restrict__ q,
                                  uint64_t n, uint32_t kbits, uint32_t *__restrict__ status);
+
+// table lookups from one opened value (lut.hip; lut.hpp): the plaintext rows out[i 2^bits + j] = table[(i mod n_tab) 2^bits +
+// ((j + r[i]) mod 2^bits)] on exponent records (a grid-stride loop over 16-byte pieces, 8 lanes per record), and the closing copy
+// out[i] = tuples[i 2^bits + (e[i] mod 2^bits)] of ciphertexts (one wavefront per output ciphertext); vec16: every table / tuple / out pointer is 16-byte aligned
+__global__ void k_lut_rotate(const uint32_t *__restrict__ table, uint64_t n_tab, const uint32_t *__restrict__ r, uint32_t *__restrict__ out,
+                             uint64_t n, uint32_t bits, uint32_t vec16);
+__global__ void k_lut_select(const uint32_t *__restrict__ e, const uint32_t *__restrict__ tuples, uint32_t *__restrict__ out, uint64_t n,
+                             uint32_t bits, uint32_t vec16);
 }  // namespace cofhe_k

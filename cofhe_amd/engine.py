@@ -139,6 +139,42 @@ class Engine:
                                                       C.c_uint32(kbits), C.byref(out), C.byref(n)))
         return self._take(out, n)
 
+    def lut_select_tensors_bytes(self, e: bytes, tuples: bytes) -> bytes:
+        """e (plaintext tensor of the opened values x - r, shape S, at most 7 dimensions) and tuples (ciphertext tensor of the
+        lookup tuples' entries, shape S + [2^bits], 1 <= bits <= 12) -> the ciphertext tensor of the entries e mod 2^bits, shape S.
+        Composed here from unpack_tensor_device (which validates the incoming forms), lut_tuples_shape_bits (COFHE_HIP_ESHAPE when
+        the tuples' shape is anything else), lut_select_records and pack_tensor_device: the library has no entry point of its own
+        for it."""
+        held = []
+
+        def load(t, kind):
+            # every integer owns an 8-byte table entry: the record count is bounded by the length
+            cap = (len(t) // 8) // (3 if kind else 1) + 1
+            raw = self.malloc(len(t) + 4)
+            held.append(raw)
+            recs = self.malloc(cap * 4 * (REC_WORDS if kind else EXP_REC_WORDS))
+            held.append(recs)
+            self.upload(raw, t)
+            shape, n = self.unpack_tensor_device(raw, len(t), kind, recs, cap)
+            return recs, shape, n
+
+        try:
+            de, se, ne = load(e, 0)
+            dt, st, nt = load(tuples, 2)
+            bits = self.lut_tuples_shape_bits(se, st)
+            assert nt == 2 * (ne << bits)                             # the counts are the shapes' products
+            dout = self.malloc(max(ne, 1) * 2 * REC_WORDS * 4)
+            held.append(dout)
+            self.lut_select_records(de, dt, dout, ne, bits)
+            cap = self.packed_size_bound(2 * ne, 2, len(se))
+            packed = self.malloc(cap)
+            held.append(packed)
+            ln = self.pack_tensor_device(dout, 2 * ne, 2, se, packed, cap)
+            return self.download(packed, ln, dtype="uint8").tobytes()
+        finally:
+            for p in held:
+                self.free(p)
+
     def scal_ciphertext_tensors(self, s: bytes, cts: bytes, zero: bytes = None) -> bytes:
         out = C.POINTER(C.c_uint8)()
         n = C.c_size_t()
@@ -399,6 +435,36 @@ class Engine:
         _chk(self.L.cofhe_hip_div_close_records(self.ctx, C.c_void_p(d_e), C.c_void_p(d_div), C.c_uint64(n_div), C.c_void_p(d_rq),
                                                 f.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(d_out), C.c_uint64(n_ciphertexts),
                                                 C.c_uint32(kbits), C.c_void_p(stream)))
+
+    def lut_rotate_records(self, d_table, n_tab, d_r, d_out, n, bits, stream=0):
+        """out[i 2^bits + j] = table[(i mod n_tab) 2^bits + ((j + r[i]) mod 2^bits)] on exponent records (table: n_tab 2^bits, r: n,
+        out: n 2^bits): the plaintext rows of the lookup tuples; 1 <= bits <= 12; d_out must not overlap an input"""
+        _chk(self.L.cofhe_hip_lut_rotate_records(self.ctx, C.c_void_p(d_table), C.c_uint64(n_tab), C.c_void_p(d_r), C.c_void_p(d_out),
+                                                 C.c_uint64(n), C.c_uint32(bits), C.c_void_p(stream)))
+
+    def lut_tuples_records(self, d_table, n_tab, d_r, d_rho, h_record, pk_record, f_record, d_out, n, bits, kbits, stream=0):
+        """the entries of n lookup tuples: lut_rotate_records, then encrypt_fresh_records over the n 2^bits rows with the randomness
+        rho (n 2^bits exponent records, each used once); h_record, pk_record, f_record: host uint32[168]; d_out: n 2^bits
+        ciphertexts"""
+        import numpy as np
+        recs = [np.ascontiguousarray(r, dtype=np.uint32) for r in (h_record, pk_record, f_record)]
+        assert all(r.size == 168 for r in recs)
+        _chk(self.L.cofhe_hip_lut_tuples_records(self.ctx, C.c_void_p(d_table), C.c_uint64(n_tab), C.c_void_p(d_r), C.c_void_p(d_rho),
+                                                 *[r.ctypes.data_as(C.POINTER(C.c_uint32)) for r in recs], C.c_void_p(d_out), C.c_uint64(n),
+                                                 C.c_uint32(bits), C.c_uint32(kbits), C.c_void_p(stream)))
+
+    def lut_tuples_shape_bits(self, shape_e, shape_t) -> int:
+        """host only: bits of the tuples (shape_t = shape_e + [2^bits]) that go with opened values of shape_e; COFHE_HIP_ESHAPE otherwise"""
+        bits = C.c_uint32()
+        _chk(self.L.cofhe_hip_lut_tuples_shape_bits(C.c_uint32(len(shape_e)), (C.c_uint32 * max(len(shape_e), 1))(*shape_e), C.c_uint32(len(shape_t)),
+                                                    (C.c_uint32 * max(len(shape_t), 1))(*shape_t), C.byref(bits)))
+        return bits.value
+
+    def lut_select_records(self, d_e, d_tuples, d_out, n, bits, stream=0):
+        """the closing step of a lookup: out[i] = tuples[i 2^bits + (e[i] mod 2^bits)], ciphertexts copied byte for byte; e: n
+        exponent records of the opened values x - r; d_out must not overlap an input"""
+        _chk(self.L.cofhe_hip_lut_select_records(self.ctx, C.c_void_p(d_e), C.c_void_p(d_tuples), C.c_void_p(d_out), C.c_uint64(n),
+                                                 C.c_uint32(bits), C.c_void_p(stream)))
 
     def decrypt_records(self, d_cts, d_sk, f_record, d_out, n_ciphertexts, kbits, stream=0):
         """f_record: host numpy uint32[168]; d_out: n * (ceil(k/32) + 1) words"""

@@ -1090,6 +1090,82 @@ class HIPCryptoSystem {
         check(cofhe_hip_stream_sync(ctx_, nullptr));          // `ee` and `ed` go with this frame
         return out;
     }
+    // ---- table lookups from one opened value (cofhe_hip_lut_*; include/cofhe_hip.h states the protocol) ----
+    // the width b of a public lookup table for n elements: `table` is [2^b] (one table) or [n_tab, 2^b] (element i takes table
+    // i mod n_tab, n a multiple of n_tab), 1 <= b <= COFHE_HIP_LUT_MAX_BITS, b <= k
+    uint32_t lut_table_bits(const Tensor<PlainText *> &table, size_t n) const {
+        if (table.is_zero_degree() || table.ndim() < 1 || table.ndim() > 2) throw std::invalid_argument("lookup table: [2^b] or [n_tab, 2^b]");
+        return lut_bits(table.shape().back(), table.num_elements() / (table.shape().back() ? table.shape().back() : 1), n);
+    }
+    // the plaintext rows of the lookup tuples: res[i, j] = table[i mod n_tab, (j + r[i]) mod 2^b], a tensor [n, 2^b] for the n
+    // masks r (cofhe_hip_lut_rotate_records, k_lut_rotate); entries are copied as they are, sign included
+    Tensor<PlainText *> lut_rotate_plaintext_tensor(const Tensor<PlainText *> &table, const Tensor<PlainText *> &r) const {
+        const size_t n = r.num_elements();
+        const uint32_t b = lut_table_bits(table, n);
+        const size_t n_tab = table.num_elements() >> b;
+        std::vector<uint32_t> et = pack_exponents(table), er = pack_exponents(r), rows((n << b) * EXPW, 0);
+        void *dt = nullptr, *dr = nullptr, *drows = nullptr;
+        check(cofhe_hip_malloc(ctx_, et.size() * 4 + 4, &dt)); Guard g1{ctx_, dt};
+        check(cofhe_hip_malloc(ctx_, er.size() * 4 + 4, &dr)); Guard g2{ctx_, dr};
+        check(cofhe_hip_malloc(ctx_, rows.size() * 4 + 4, &drows)); Guard g3{ctx_, drows};
+        check(cofhe_hip_upload(ctx_, dt, et.data(), et.size() * 4, nullptr));
+        check(cofhe_hip_upload(ctx_, dr, er.data(), er.size() * 4, nullptr));
+        check(cofhe_hip_lut_rotate_records(ctx_, dt, n_tab, dr, drows, n, b, nullptr));
+        check(cofhe_hip_download(ctx_, rows.data(), drows, rows.size() * 4, nullptr));
+        Tensor<PlainText *> t(std::vector<size_t>{n, (size_t)1 << b}, nullptr);
+        for (size_t i = 0; i < (n << b); i++) {
+            Mpz v;
+            mpz_import(v.get(), EXPW - 1, -1, 4, 0, 0, &rows[i * EXPW]);
+            if (rows[i * EXPW + EXPW - 1]) v.neg();
+            t[i] = new PlainText(std::move(v));
+        }
+        return t;
+    }
+    // the entries of the lookup tuples: res[i, j] = a FRESH encryption of table[i mod n_tab, (j + r[i]) mod 2^b], a tensor
+    // [n, 2^b] (cofhe_hip_lut_tuples_records: the rotation and the fresh-randomness comb, on the device from end to end).  Every
+    // entry has its own randomness WHATEVER the randomness mode: under a shared r the tuple would give the rotation away.
+    Tensor<CipherText *> lut_tuples_ciphertext_tensor(const PublicKey &pk, const Tensor<PlainText *> &table, const Tensor<PlainText *> &r) const {
+        const size_t n = r.num_elements();
+        const uint32_t b = lut_table_bits(table, n);
+        const size_t n_tab = table.num_elements() >> b;
+        std::vector<uint32_t> et = pack_exponents(table), er = pack_exponents(r), rho = draw_randomness(n << b), hrec(REC, 0), pkrec(REC, 0), frec(REC, 0);
+        pack_form(h_, hrec.data());
+        pack_form(pk, pkrec.data());
+        pack_form(f_, frec.data());
+        void *dt = nullptr, *dr = nullptr, *drho = nullptr;
+        check(cofhe_hip_malloc(ctx_, et.size() * 4 + 4, &dt)); Guard g1{ctx_, dt};
+        check(cofhe_hip_malloc(ctx_, er.size() * 4 + 4, &dr)); Guard g2{ctx_, dr};
+        check(cofhe_hip_malloc(ctx_, rho.size() * 4 + 4, &drho)); Guard g3{ctx_, drho};
+        check(cofhe_hip_upload(ctx_, dt, et.data(), et.size() * 4, nullptr));
+        check(cofhe_hip_upload(ctx_, dr, er.data(), er.size() * 4, nullptr));
+        check(cofhe_hip_upload(ctx_, drho, rho.data(), rho.size() * 4, nullptr));
+        DeviceTensor out = alloc(std::vector<size_t>{n, (size_t)1 << b}, n << b);
+        check(cofhe_hip_lut_tuples_records(ctx_, dt, n_tab, dr, drho, hrec.data(), pkrec.data(), frec.data(), out.ptr_, n, b, k_, nullptr));
+        check(cofhe_hip_stream_sync(ctx_, nullptr));          // the host vectors go with this frame
+        return download(std::move(out));
+    }
+    // encrypt_tensor with its own randomness per ciphertext WHATEVER the randomness mode: the masks [r] of the lookup tuples
+    Tensor<CipherText *> encrypt_tensor_per_element(const PublicKey &pk, const Tensor<PlainText *> &pts) const { return encrypt_tensor_fresh(pk, pts); }
+    // the closing step of a lookup: res[i] = tuples[i, e[i] mod 2^b], of e's shape, for the opened values e = x - r and the
+    // tuple entries [n, 2^b] of the masks r (cofhe_hip_lut_select_records: a copy).  The result is a fresh ciphertext already,
+    // so it gets no re-randomisation pass in any mode.
+    Tensor<CipherText *> lut_select_ciphertext_tensor(const Tensor<PlainText *> &e, const Tensor<CipherText *> &tuples) const {
+        return download(lut_select_ciphertext_tensor(e, upload(tuples)));
+    }
+    // the same on resident tuples
+    DeviceTensor lut_select_ciphertext_tensor(const Tensor<PlainText *> &e, const DeviceTensor &tuples) const {
+        const size_t E = e.num_elements();
+        if (E == 0 || tuples.n_ % E != 0) throw std::invalid_argument("lookup tuples: 2^b entries for every opened value");
+        const uint32_t b = lut_bits(tuples.n_ / E, 1, E);
+        std::vector<uint32_t> ee = pack_exponents(e);
+        void *de = nullptr;
+        check(cofhe_hip_malloc(ctx_, ee.size() * 4 + 4, &de)); Guard g1{ctx_, de};
+        check(cofhe_hip_upload(ctx_, de, ee.data(), ee.size() * 4, nullptr));
+        DeviceTensor out = alloc(e.is_zero_degree() ? std::vector<size_t>{1} : e.shape(), E);
+        check(cofhe_hip_lut_select_records(ctx_, de, tuples.ptr_, out.ptr_, E, b, nullptr));
+        check(cofhe_hip_stream_sync(ctx_, nullptr));          // `ee` goes with this frame
+        return out;
+    }
 
     // ---- device-resident variants -------------------------------------------------------------
     // the block behind a tensor whose elements are, in order, ALL the elements of one device block (the result of
@@ -1558,6 +1634,14 @@ class HIPCryptoSystem {
         void *p;
         ~Guard() { if (p) cofhe_hip_free(ctx, p); }
     };
+    // b of a lookup table of `size` entries, n_tab of them for n elements: size = 2^b, 1 <= b <= COFHE_HIP_LUT_MAX_BITS, b <= k
+    uint32_t lut_bits(size_t size, size_t n_tab, size_t n) const {
+        uint32_t b = 0;
+        while (b <= COFHE_HIP_LUT_MAX_BITS && ((size_t)1 << b) != size) b++;
+        if (b == 0 || b > COFHE_HIP_LUT_MAX_BITS || b > k_) throw std::invalid_argument("lookup table: 2^b entries, 1 <= b <= 12, b <= k");
+        if (n_tab == 0 || n % n_tab != 0) throw std::invalid_argument("lookup tables: their count must divide the element count");
+        return b;
+    }
     static void check(int rc) {
         if (rc == COFHE_HIP_OK) return;
         std::string msg = cofhe_hip_last_error();

@@ -816,6 +816,158 @@ static void bench_divide(size_t n, int runs) {
     if (!ok) throw std::runtime_error("division mismatch");
 }
 
+// table lookups on a ciphertext tensor from one opened value per element (LocalCipherTextMultiplier::lookup_ciphertext_tensor),
+// through the single-key and the 2-of-3 threshold client: a random 8-bit table, relu and max at 8 bits over n elements of the
+// whole signed 8-bit range, and a 2 x 2 max pool of them (n a multiple of 4); every decrypted element must EQUAL the plaintext
+// computation; prints the opened values per call (n for a lookup, 3 per output for the 2 x 2 pool) and whether all c1 of one
+// tuple tensor are pairwise distinct in the default randomness mode.  runs > 0: the median wall clock of `runs` relu calls on
+// one line for tools/bench_ops.py
+static void bench_lookup(size_t n, int runs) {
+    auto cs = make_cryptosystem(128, 128, Device::GPU);
+    using CS = decltype(cs);
+    auto sk = cs.keygen();
+    const uint32_t k = cs.message_bits(), bits = 8;
+    const long half = 1L << (bits - 1);
+    // signed values: the ends of the range, 0, -1, 1, then uniform ones
+    std::vector<long> xs(n), ys(n);
+    const long fixed[5] = {-half, half - 1, 0, -1, 1};
+    for (size_t i = 0; i < n; i++) {
+        xs[i] = i < 5 ? fixed[i] : (long)mpz_get_ui(cs.random_plaintext(bits).get()) - half;
+        ys[i] = i < 5 ? fixed[4 - i] : (long)mpz_get_ui(cs.random_plaintext(bits).get()) - half;
+    }
+    auto residue = [&](long v) {                                    // v mod 2^k
+        Mpz m((unsigned long)(v < 0 ? -v : v));
+        if (v < 0) m.neg();
+        mpz_fdiv_r_2exp(m.get(), m.get(), k);
+        return m;
+    };
+    auto plain = [&](const std::vector<long> &v) {
+        Tensor<CS::PlainText *> t(v.size(), nullptr);
+        for (size_t i = 0; i < v.size(); i++) t[i] = new CS::PlainText(residue(v[i]));
+        return t;
+    };
+    auto px = plain(xs), py = plain(ys);
+    std::vector<Mpz> g((size_t)1 << bits);                          // any public function: 256 uniform k-bit plaintexts
+    Tensor<CS::PlainText *> table(g.size(), nullptr);
+    for (size_t j = 0; j < g.size(); j++) {
+        g[j] = cs.random_plaintext(k);
+        table[j] = &g[j];
+    }
+    auto equals = [&](const Tensor<CS::PlainText *> &dec, const std::vector<Mpz> &want) {
+        bool pass = dec.num_elements() == want.size();
+        for (size_t i = 0; pass && i < want.size(); i++) pass = *dec[i] == want[i];
+        return pass;
+    };
+    bool ok = true;
+    for (int threshold = 0; threshold < 2; threshold++) {
+        std::unique_ptr<LocalSMPCClient<CS>> client(threshold ? new LocalSMPCClient<CS>(cs, sk, 2, 3) : new LocalSMPCClient<CS>(cs, sk));
+        LocalCipherTextMultiplier<CS> mul(*client);
+        auto cx = cs.encrypt_tensor(client->network_public_key(), px), cy = cs.encrypt_tensor(client->network_public_key(), py);
+        const char *who = threshold ? "threshold 2 of 3" : "secret key";
+        const char *names[3] = {"random 8-bit table", "relu at 8 bits", "max at 8 bits"};
+        for (int what = 0; what < 3; what++) {
+            std::vector<Mpz> want(n);
+            for (size_t i = 0; i < n; i++)
+                want[i] = what == 0 ? g[(size_t)(xs[i] & ((1L << bits) - 1))] : residue(what == 1 ? std::max(xs[i], 0L) : std::max(xs[i], ys[i]));
+            const size_t before = client->decrypted_elements();
+            cs.synchronize();
+            auto t0 = Clock::now();
+            auto res = what == 0 ? mul.lookup_ciphertext_tensor(table, cx) : what == 1 ? mul.relu_ciphertext_tensor(cx, bits)
+                                                                                       : mul.max_ciphertext_tensors(cx, cy, bits);
+            cs.synchronize();
+            const double ms = std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
+            const size_t opened = client->decrypted_elements() - before;
+            auto dec = cs.decrypt_tensor(sk, res);
+            const bool pass = opened == n && equals(dec, want);
+            if (!threshold && what == 1) std::ofstream("local_bench_lookup.bin", std::ios::binary) << cs.serialize_ciphertext_tensor(res);
+            std::cout << "  " << who << ": " << names[what] << " over " << n << " elements, opened_values " << opened << ", " << ms
+                      << " ms (host wall clock, tuple generation and the decryption included): " << (pass ? "ok" : "FAILED") << std::endl;
+            ok = ok && pass;
+            free_all(res); free_all(dec);
+        }
+        if (n % 4 == 0) {
+            Tensor<CS::CipherText *> img = cx;
+            img.reshape({1, 2, 2, n / 4});
+            const size_t before = client->decrypted_elements();
+            auto pooled = mul.max_pool2d_ciphertext_tensor(img, {2, 2}, {2, 2}, bits);
+            const size_t opened = client->decrypted_elements() - before;
+            auto dec = cs.decrypt_tensor(sk, pooled);
+            std::vector<Mpz> want(n / 4);
+            for (size_t c = 0; c < n / 4; c++) {
+                long m = xs[c];
+                for (size_t p = 1; p < 4; p++) m = std::max(m, xs[p * (n / 4) + c]);
+                want[c] = residue(m);
+            }
+            const bool pass = opened == 3 * (n / 4) && equals(dec, want);
+            std::cout << "  " << who << ": 2 x 2 max pool, opened_values " << opened << " for " << n / 4 << " outputs, two rounds: " << (pass ? "ok" : "FAILED")
+                      << std::endl;
+            ok = ok && pass;
+            free_all(pooled); free_all(dec);
+        }
+        if (!threshold) {
+            // the parts on their own: one 0-D element, the plaintext rows, the refusals, and the randomness of a tuple tensor
+            auto y0 = mul.lookup_ciphertext_tensor(table, Tensor<CS::CipherText *>(cx[1 % n]));
+            bool parts = y0.is_zero_degree() && cs.decrypt(sk, *y0.get_value()) == g[(size_t)(xs[1 % n] & ((1L << bits) - 1))];
+            delete y0.get_value();
+            Mpz three(3ul);
+            auto rows = cs.lut_rotate_plaintext_tensor(table, Tensor<CS::PlainText *>(1, &three));
+            for (size_t j = 0; j < g.size(); j++) parts = parts && *rows[j] == g[(j + 3) % g.size()];
+            free_all(rows);
+            int refused = 0;
+            try {
+                (void)mul.lookup_ciphertext_tensor(Tensor<CS::PlainText *>(3, &three), cx);       // 3 entries: no power of two
+            } catch (const std::invalid_argument &) {
+                refused++;
+            }
+            try {
+                (void)mul.relu_ciphertext_tensor(cx, 13);
+            } catch (const std::invalid_argument &) {
+                refused++;
+            }
+            parts = parts && refused == 2;
+            std::cout << "  0-D lookup, lut_rotate_plaintext_tensor, the refusals of 3 entries and of 13 bits: " << (parts ? "ok" : "FAILED") << std::endl;
+            ok = ok && parts;
+            const bool default_mode = cs.tensor_randomness() == TensorRandomness::None;
+            auto tuples = client->get_lookup_tuples(4, table);
+            std::set<std::string> seen;
+            for (auto &t : tuples)
+                for (size_t i = 0; i < t.num_elements(); i++) seen.insert(t[i]->c1().a().str() + " " + t[i]->c1().b().str());
+            const bool distinct = default_mode && seen.size() == 4 + 4 * g.size();
+            std::cout << "  " << 4 + 4 * g.size() << " ciphertexts of the tuples of 4 elements, default randomness mode, distinct c1: "
+                      << (distinct ? "yes" : "NO") << std::endl;
+            ok = ok && distinct;
+            for (auto &t : tuples) free_all(t);
+        }
+        free_all(cx); free_all(cy);
+    }
+    {
+        Mpz ad = cs.discriminant();
+        ad.neg();
+        std::ofstream("local_bench_absdelta.txt") << ad.str() << "\n";
+    }
+    if (runs > 0) {
+        LocalSMPCClient<CS> client(cs, sk);
+        LocalCipherTextMultiplier<CS> mul(client);
+        auto cx = cs.encrypt_tensor(client.network_public_key(), px);
+        std::vector<double> ms;
+        for (int pass = 0; pass <= runs; pass++) {
+            cs.synchronize();
+            auto t0 = Clock::now();
+            auto res = mul.relu_ciphertext_tensor(cx, bits);
+            cs.synchronize();
+            if (pass) ms.push_back(std::chrono::duration<double, std::milli>(Clock::now() - t0).count());
+            free_all(res);
+        }
+        free_all(cx);
+        std::sort(ms.begin(), ms.end());
+        std::cout << "lookup_json: {\"E\": " << n << ", \"bits\": " << bits << ", \"runs\": " << runs << ", \"relu_ms\": " << ms[ms.size() / 2]
+                  << ", \"relu_ms_min_max\": [" << ms.front() << ", " << ms.back() << "]}" << std::endl;
+    }
+    std::cout << "  agree: " << (ok ? "yes" : "NO") << std::endl;
+    free_all(px); free_all(py);
+    if (!ok) throw std::runtime_error("lookup mismatch");
+}
+
 // threshold decryption end to end (the reference has no local benchmark for it; the calls are the
 // ones PartialDecryptionRequestHandler / SMPCClient make, partial_decryption_request_handler.hpp:140,
 // smpc_client.hpp:137): share sk t-out-of-n, every party of the first threshold set runs
@@ -1329,7 +1481,7 @@ static void plaintexts_mode(const char *in, const char *out) {
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        std::cerr << "Usage: " << argv[0] << " <encrypt_decrypt|ciphertext_matadd|scal_matmul|threshold|ciphertext_matmul|fresh_randomness|affine|beaver_direct|plain_ct_matmul|ciphertext_matmul_matrix|conv2d|conv2d_grouped|sum_pool2d|poly_activation|divide> [sizes]" << std::endl;
+        std::cerr << "Usage: " << argv[0] << " <encrypt_decrypt|ciphertext_matadd|scal_matmul|threshold|ciphertext_matmul|fresh_randomness|affine|beaver_direct|plain_ct_matmul|ciphertext_matmul_matrix|conv2d|conv2d_grouped|sum_pool2d|poly_activation|divide|lookup> [sizes]" << std::endl;
         return 1;
     }
     std::string mode = argv[1];
@@ -1388,6 +1540,9 @@ int main(int argc, char **argv) {
         } else if (mode == "divide") {
             // elements [runs]: with runs > 0 also the timed scalar division
             bench_divide(argc > 2 ? std::stoul(argv[2]) : 64, argc > 3 ? std::stoi(argv[3]) : 0);
+        } else if (mode == "lookup") {
+            // elements [runs]: with runs > 0 also the timed relu
+            bench_lookup(argc > 2 ? std::stoul(argv[2]) : 64, argc > 3 ? std::stoi(argv[3]) : 0);
         } else if (mode == "formats") {
             bench_formats();
         } else if (mode == "threads") {

@@ -32,6 +32,11 @@
 // the reference's ComputeOperation::DIVIDE answers "Not implemented").  With a division pair ([r], [r_q]), r_q = floor(s(r) / D),
 // per element:  e = Dec(x - r);  [y] = [r_q] o f^(floor(s(e) / D)),  s the centred residue mod 2^k -- one opened value, no
 // encryption, no ladder; y is floor(x / D) or one less unless s(r) + s(e) wraps (probability |x| / 2^k per element).
+//
+// Table lookups (lookup_ciphertext_tensor, relu_ciphertext_tensor, max_ciphertext_tensors, max_pool2d_ciphertext_tensor; the
+// reference has no comparison).  With a lookup tuple ([r], [T_0], .., [T_{2^b - 1}]), T_j = g[(j + r) mod 2^b], per element:
+// e = Dec(x - r);  [y] = [T_{e mod 2^b}] -- one opened value, one round, y = g[x mod 2^b] exactly for ANY public table g of 2^b
+// plaintexts, and the closing step is a copy.  Every [T_j] carries its own randomness whatever the randomness mode.
 #pragma once
 #include "hip_cryptosystem.hpp"
 
@@ -144,6 +149,22 @@ class LocalSMPCClient {
             delete pr[i];
             delete prq[i];
         }
+        return t;
+    }
+
+    // lookup tuples for n elements and the public table(s) `table` ([2^b], or [n_tab, 2^b] with element i taking table i mod
+    // n_tab): {[r] (n elements), [T] (n 2^b elements, [n, 2^b])} with r uniform in Z/2^k per element and T[i, j] = table[(j +
+    // r_i) mod 2^b], used once; the caller owns the elements.  [r] and every [T_j] are encrypted with their OWN randomness
+    // whatever the randomness mode: entries that shared c1 would give the rotation, and with the opened value x mod 2^b, away.
+    // Like the triplets, the tuples of the networked system would come from a protocol between the nodes.
+    Vector<Tensor<CipherText *>> get_lookup_tuples(size_t n, const Tensor<PlainText *> &table) {
+        (void)cs_.lut_table_bits(table, n);                      // refuse before anything is drawn
+        Tensor<PlainText *> pr(n, nullptr);
+        for (size_t i = 0; i < n; i++) pr[i] = new PlainText(cs_.random_plaintext(cs_.message_bits()));
+        Vector<Tensor<CipherText *>> t;
+        t.push_back(cs_.encrypt_tensor_per_element(pk_, pr));
+        t.push_back(cs_.lut_tuples_ciphertext_tensor(pk_, table, pr));
+        for (size_t i = 0; i < n; i++) delete pr[i];
         return t;
     }
 
@@ -312,6 +333,120 @@ class LocalCipherTextMultiplier {
         Tensor<CipherText *> flat = sums;
         flat.flatten();
         for (size_t i = 0; i < flat.num_elements(); i++) delete flat[i];
+        return res;
+    }
+
+    // g[x mod 2^b] element-wise for a public table g of 2^b plaintexts ([2^b], or [n_tab, 2^b] with element i taking table i mod
+    // n_tab), 1 <= b <= 12, b <= k: with a lookup tuple per element, ONE opened value e = Dec(x - r), one round, exact, no
+    // failure probability; the closing step copies the entry e mod 2^b of the element's tuple.  x must lie in the b-bit range
+    // for the result to be g[x]; a b-bit signed value is read as its two's-complement index.  A tuple is 2^b ciphertexts (1344
+    // bytes each on the device) per element.  0-D and 1-D tensors; higher ranks are flattened and the result reshaped.
+    Tensor<CipherText *> lookup_ciphertext_tensor(const Tensor<PlainText *> &table, const Tensor<CipherText *> &x) {
+        if (x.is_zero_degree()) {
+            Tensor<CipherText *> r = lookup_ciphertext_tensor(table, Tensor<CipherText *>(1, x.get_value()));
+            return Tensor<CipherText *>(r.at(0));
+        }
+        auto &cs = client_m.crypto_system();
+        const auto &pk = client_m.network_public_key();
+        const size_t n = x.num_elements();
+        Tensor<CipherText *> flat = x;
+        flat.flatten();
+        auto tuples = client_m.get_lookup_tuples(n, table);
+        auto x_sub_r = cs.sub_ciphertext_tensors(pk, flat, tuples[0]);
+        auto e = client_m.decrypt_tensor(x_sub_r);
+        auto ct = cs.lut_select_ciphertext_tensor(e, tuples[1]);
+        for (auto &t : tuples)
+            for (size_t i = 0; i < t.num_elements(); i++) delete t[i];
+        for (size_t i = 0; i < n; i++) {
+            delete x_sub_r[i];
+            delete e[i];
+        }
+        ct.reshape(x.shape());
+        return ct;
+    }
+    // max(x, 0) for `bits`-bit signed values x, exactly: the table holds v for 0 < v < 2^(bits-1) and 0 otherwise
+    Tensor<CipherText *> relu_ciphertext_tensor(const Tensor<CipherText *> &x, uint32_t bits) {
+        if (bits == 0 || bits > COFHE_HIP_LUT_MAX_BITS) throw std::invalid_argument("relu_ciphertext_tensor: 1 <= bits <= 12");
+        const size_t size = (size_t)1 << bits;
+        std::vector<PlainText> vals(size);
+        Tensor<PlainText *> table(size, nullptr);
+        for (size_t v = 0; v < size; v++) {
+            if (v < size / 2) mpz_set_ui(vals[v].get(), (unsigned long)v);
+            table[v] = &vals[v];
+        }
+        return lookup_ciphertext_tensor(table, x);
+    }
+    // max(a, b) element-wise for `bits`-bit signed values: b + relu(a - b), the difference a (bits + 1)-bit signed value, so
+    // 1 <= bits <= 11; one opened value per element
+    Tensor<CipherText *> max_ciphertext_tensors(const Tensor<CipherText *> &a, const Tensor<CipherText *> &b, uint32_t bits) {
+        if (bits == 0 || bits + 1 > COFHE_HIP_LUT_MAX_BITS) throw std::invalid_argument("max_ciphertext_tensors: 1 <= bits <= 11");
+        auto &cs = client_m.crypto_system();
+        const auto &pk = client_m.network_public_key();
+        auto diff = cs.sub_ciphertext_tensors(pk, a, b);
+        auto pos = relu_ciphertext_tensor(diff, bits + 1);
+        auto res = cs.add_ciphertext_tensors(pk, b, pos);
+        if (diff.is_zero_degree()) {
+            delete diff.get_value();
+            delete pos.get_value();
+        } else {
+            for (size_t i = 0; i < diff.num_elements(); i++) {
+                delete diff[i];
+                delete pos[i];
+            }
+        }
+        return res;
+    }
+    // max pooling of `bits`-bit signed values, channels last ([B, H, W, C] -> [B, Ho, Wo, C]), no padding: a pairwise tournament
+    // over the kernel[0] kernel[1] taps of a window, ceil(log2(taps)) rounds of ONE batched max_ciphertext_tensors call each (an
+    // odd tap passes through), taps - 1 lookups and opened values per output.  The taps are gathered by pointer arithmetic on
+    // the host tensor; nothing is copied.
+    Tensor<CipherText *> max_pool2d_ciphertext_tensor(const Tensor<CipherText *> &x, const std::array<size_t, 2> &kernel,
+                                                      const std::array<size_t, 2> &stride, uint32_t bits) {
+        if (x.is_zero_degree() || x.ndim() != 4) throw std::invalid_argument("max_pool2d_ciphertext_tensor: a [B, H, W, C] tensor");
+        const size_t B = x.shape()[0], H = x.shape()[1], W = x.shape()[2], C = x.shape()[3], kh = kernel[0], kw = kernel[1];
+        if (kh == 0 || kw == 0 || stride[0] == 0 || stride[1] == 0 || kh > H || kw > W)
+            throw std::invalid_argument("max_pool2d_ciphertext_tensor: the window lies inside the image, the strides are not 0");
+        const size_t Ho = (H - kh) / stride[0] + 1, Wo = (W - kw) / stride[1] + 1, n_out = B * Ho * Wo * C;
+        struct Tap {
+            Tensor<CipherText *> t;
+            bool owned;                              // a result of an earlier round, not elements of x
+        };
+        std::vector<Tap> taps;
+        for (size_t dy = 0; dy < kh; dy++)
+            for (size_t dx = 0; dx < kw; dx++) {
+                Tensor<CipherText *> t(n_out, nullptr);
+                size_t o = 0;
+                for (size_t b = 0; b < B; b++)
+                    for (size_t oy = 0; oy < Ho; oy++)
+                        for (size_t ox = 0; ox < Wo; ox++)
+                            for (size_t c = 0; c < C; c++) t[o++] = x[((b * H + oy * stride[0] + dy) * W + ox * stride[1] + dx) * C + c];
+                taps.push_back(Tap{t, false});
+            }
+        while (taps.size() > 1) {
+            const size_t pairs = taps.size() / 2;
+            Tensor<CipherText *> lhs(pairs * n_out, nullptr), rhs(pairs * n_out, nullptr);
+            for (size_t p = 0; p < pairs; p++)
+                for (size_t i = 0; i < n_out; i++) {
+                    lhs[p * n_out + i] = taps[2 * p].t[i];
+                    rhs[p * n_out + i] = taps[2 * p + 1].t[i];
+                }
+            auto m = max_ciphertext_tensors(lhs, rhs, bits);
+            std::vector<Tap> next;
+            for (size_t p = 0; p < pairs; p++) {
+                Tensor<CipherText *> t(n_out, nullptr);
+                for (size_t i = 0; i < n_out; i++) t[i] = m[p * n_out + i];
+                next.push_back(Tap{t, true});
+            }
+            for (size_t p = 0; p < 2 * pairs; p++)
+                if (taps[p].owned)
+                    for (size_t i = 0; i < n_out; i++) delete taps[p].t[i];
+            if (taps.size() % 2) next.push_back(taps.back());
+            taps = std::move(next);
+        }
+        Tensor<CipherText *> res = taps[0].t;
+        if (!taps[0].owned)                          // a 1 x 1 window: the caller owns copies, as of every result tensor
+            for (size_t i = 0; i < n_out; i++) res[i] = new CipherText(*res[i]);
+        res.reshape({B, Ho, Wo, C});
         return res;
     }
 

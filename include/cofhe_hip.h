@@ -25,6 +25,9 @@
  *   cofhe_hip_divfloor_plain_...,    nothing: a ciphertext tensor divided by public divisors (rescale, mean, average pool) from ONE
  *   cofhe_hip_div_close_...          opened value per element (division pairs); ComputeOperation::DIVIDE answers "Not implemented"
  *                                    (include/node/compute_request_handler.hpp:73, 343-344)
+ *   cofhe_hip_lut_rotate_...,        nothing: ANY public function of a b-bit value on a ciphertext tensor, exactly (ReLU, max, max
+ *   cofhe_hip_lut_tuples_...,        pooling), from ONE opened value per element (lookup tuples); the reference has no comparison
+ *   cofhe_hip_lut_select_...         and no table lookup
  *   cofhe_hip_decrypt_records        decrypt_tensor's per-element work, cpu_cryptosystem_tensor_ops.inl:21-33
  *   cofhe_hip_part_decrypt_records,  part_decrypt_tensor / combine_part_decryption_results_tensor,
  *   cofhe_hip_combine_part_...       cpu_cryptosystem_tensor_ops.inl:35-73 (cpu_cryptosystem_distributed.inl:231-285)
@@ -315,6 +318,47 @@ int cofhe_hip_divfloor_plain_records(cofhe_hip_ctx *ctx, const void *d_v, const 
  * (COFHE_HIP_EINVAL, as for the refusals above). */
 int cofhe_hip_div_close_records(cofhe_hip_ctx *ctx, const void *d_e, const void *d_div, uint64_t n_div, const void *d_rq,
                                 const uint32_t *f_record, void *d_out, uint64_t n_ct, uint32_t kbits, void *stream);
+/* ---- table lookups from one opened value (cofhe_amd/csrc/lut.hip) ----
+ * For values known to lie in a b-bit range, 1 <= b <= COFHE_HIP_LUT_MAX_BITS, b <= k, ANY public function of them given as a table
+ * g of 2^b plaintexts is evaluated exactly, in one round, with no failure probability.  A LOOKUP TUPLE of an element is
+ * ([r], [T_0], .., [T_{2^b - 1}]) with r uniform in Z/2^k and T_j = g[(j + r) mod 2^b], used once.  With the ONE opened value
+ * e = Dec([x] - [r]) -- uniform whatever x is, so it hides x perfectly --
+ *   [y] = [T_{e mod 2^b}],   y = g[x mod 2^b],
+ * since (e + r) mod 2^b = x mod 2^b: the closing step is a copy, no homomorphic arithmetic.  A b-bit SIGNED value is read as its
+ * two's-complement index: the caller's choice of g.  EVERY [T_j] MUST CARRY ITS OWN RANDOMNESS: under one shared r the quotient
+ * c2_j o c2_j'^-1 = f^(T_j - T_j') is publicly decodable, which reveals the rotation and, with e, x mod 2^b; so the tuples are made
+ * by the fresh-randomness comb (cofhe_hip_lut_tuples_records) and by nothing else.  A tuple is 2^b * 1344 bytes per element.
+ * "The index of a record" below: the low b bits of its value mod 2^k, read from word 0 and the sign word -- m mod 2^b, or
+ * (2^b - m mod 2^b) mod 2^b under a set sign word; -0 and magnitudes of 2^k and above follow the same rule.
+ * All three records entry points: purely stream-ordered, no read-back of their own; 16-byte accesses when the pointers allow them,
+ * 4-byte ones otherwise.  COFHE_HIP_EINVAL, nothing written: bits = 0 or bits > COFHE_HIP_LUT_MAX_BITS; n_tab = 0; n no multiple of
+ * n_tab; an output overlapping an input.  n = 0 does nothing. */
+#define COFHE_HIP_LUT_MAX_BITS 12
+/* the plaintext rows: out[i 2^bits + j] = table[(i mod n_tab) 2^bits + ((j + r[i]) mod 2^bits)], i < n, j < 2^bits, exponent records
+ * copied word for word.  d_table: n_tab 2^bits records (n_tab = 1: one table; n: one per element); d_r: n records, of which the
+ * index is used; d_out: n 2^bits records.  One launch ("k_lut_rotate" under "profile_kernels"), no workspace, no lock. */
+int cofhe_hip_lut_rotate_records(cofhe_hip_ctx *ctx, const void *d_table, uint64_t n_tab, const void *d_r, void *d_out, uint64_t n,
+                                 uint32_t bits, void *stream);
+/* the tuples' entries: out[i 2^bits + j] = (h^rho, pk^rho o f^(T_j mod 2^kbits)) with rho = rho[i 2^bits + j] and T the rows of
+ * cofhe_hip_lut_rotate_records, which it runs into a block of the block cache (it goes back behind the work queued on `stream`);
+ * then cofhe_hip_encrypt_fresh_records over the n 2^bits plaintexts, whose bytes these are (the plan "comb", kind 1, and its one
+ * read-back of the longest exponent).  d_rho: n 2^bits exponent records of the caller's randomness, each used once; h_record,
+ * pk_record, f_record: HOST records.  Also COFHE_HIP_EINVAL: bits > kbits, kbits out of the comb's range. */
+int cofhe_hip_lut_tuples_records(cofhe_hip_ctx *ctx, const void *d_table, uint64_t n_tab, const void *d_r, const void *d_rho,
+                                 const uint32_t *h_record, const uint32_t *pk_record, const uint32_t *f_record, void *d_out, uint64_t n,
+                                 uint32_t bits, uint32_t kbits, void *stream);
+/* The closing step: out[i] = tuples[i 2^bits + (e[i] mod 2^bits)], i < n, ciphertexts of 1344 bytes copied byte for byte, one
+ * wavefront each.  d_e: n exponent records of the opened values x - r; d_tuples: n 2^bits ciphertexts; d_out: n.  One launch
+ * ("k_lut_select" under "profile_kernels"), no workspace, no lock.  The result is a fresh ciphertext already: a caller in
+ * per-element randomness mode has nothing to re-randomise.  It has NO serialised twin (no cofhe_hip_lut_select_tensors_bytes):
+ * tensors that arrive as bytes go through cofhe_hip_unpack_tensor_device (kind 0 for e of shape S, kind 2 for the tuples of shape
+ * S + [2^bits]; it validates the incoming forms), cofhe_hip_lut_tuples_shape_bits, this call and cofhe_hip_pack_tensor_device, as
+ * Engine.lut_select_tensors_bytes does. */
+int cofhe_hip_lut_select_records(cofhe_hip_ctx *ctx, const void *d_e, const void *d_tuples, void *d_out, uint64_t n, uint32_t bits,
+                                 void *stream);
+/* host only, no GPU: *bits of the tuples that go with opened values of shape shape_e[ndim_e], ndim_e <= 7.  COFHE_HIP_ESHAPE unless
+ * shape_t is shape_e with one more, last dimension of 2^bits entries, 1 <= bits <= COFHE_HIP_LUT_MAX_BITS. */
+int cofhe_hip_lut_tuples_shape_bits(uint32_t ndim_e, const uint32_t *shape_e, uint32_t ndim_t, const uint32_t *shape_t, uint32_t *bits);
 /* decryption: for each of n ciphertexts, m with c2 o (c1^sk)^-1 = f^m.  sk: one exponent record on
  * the device; f_record: HOST pointer to the 168-word record of f = (2^(2k), 2^(k+1), 1 - Delta_K)
  * (its table of f^(-2^j) is built on first use and cached in the context).  d_out receives

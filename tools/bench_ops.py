@@ -8,7 +8,10 @@ the two alternating in one run; --out FILE also writes those lines to FILE.  --p
 same method: cofhe_hip_pow_dot_records against the ladders and additions it replaces, and the one-opened-value protocol against
 chained Beaver products (through local_bench); written to profiles/r12_poly/poly_time.json, or to --out FILE.  --div-only: only
 the division by public divisors: k_plain_divfloor alone from its "profile_kernels" spans, the closing step next to a decryption,
-and the protocol through local_bench with the kernel's share of it; written to profiles/r13_div/div_time.json, or to --out FILE."""
+and the protocol through local_bench with the kernel's share of it; written to profiles/r13_div/div_time.json, or to --out FILE.
+--lut-only: only the table lookups: k_lut_select next to a device-to-device copy of the same bytes, the parts of a ReLU over 256
+elements (tuple generation, decryption, selection), and the protocol through local_bench next to the degree-3 polynomial of the
+same run; written to profiles/r14_lut/lut_time.json, or to --out FILE."""
 import json
 import os
 import sys
@@ -247,6 +250,143 @@ if "--div-only" in sys.argv:
         json.dump(res, fh, indent=1)
     sys.exit(0 if all(r["device_status"] == 0 and r.get("exit_status", 0) == 0 and r.get("agree", True) for r in res) else 1)
 
+# ---- table lookups: the selection next to a plain copy, the parts of a ReLU, the protocol ------------------------------------
+def lut_ops(runs=5):
+    """"lut_select": cofhe_hip_lut_select_records at E = 16384, b = 8 (a tuple buffer of E 2^b 1344 bytes = 5.6 GB of arbitrary
+    words: the kernel moves bytes) next to a contiguous device-to-device copy of the same E 1344 bytes (torch's copy_ of a
+    contiguous tensor, which is one hipMemcpyAsync), both by device events around 16 calls, alternating, `runs` windows each.
+    Every call of a window reads another source: the select another set of opened values, the copy another slice of the tuple
+    buffer, 16 x 22 MB in all, more than the 256 MiB Infinity Cache keeps.  "lut_select_large": the same buffer read as E = 262144
+    elements at b = 4, 352 MB each way per call, 32 calls a window, where the time of a launch no longer shows.  "lut_rotate": the rows of 256 elements at b = 8.
+    "relu_parts": the three device steps of a ReLU over 256 elements at b = 8 by the wall clock: the tuples (rotation and 65536
+    fresh encryptions), the decryption of the 256 opened values, the selection.  "relu": relu_ciphertext_tensor over 256
+    elements through the host harness (local_bench lookup 256 <runs>), and "poly_activation" the degree-3 polynomial over 256
+    elements by the same harness in the same run"""
+    import subprocess
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    lines = []
+    f_rec, h_rec, pk_rec = (form_record(hx(prm[n]["a"]), hx(prm[n]["b"]), hx(prm[n]["c"])) for n in ("f", "h", "pk"))
+    E, b, CTW, SETS = 16384, 8, 336, 16
+    tuples = torch.empty((E << b) * CTW, dtype=torch.int32, device=dev).random_()
+    es = [dev_i32(exp_records([rng.bits(K) for _ in range(E)])) for _ in range(SETS)]
+    out, dst = torch.zeros(E * CTW, dtype=torch.int32, device=dev), torch.zeros(E * CTW, dtype=torch.int32, device=dev)
+    srcs = [tuples[j * 16 * E * CTW:(j * 16 + 1) * E * CTW] for j in range(SETS)]      # 16 slices of E ciphertexts, 350 MB apart
+
+    def window(fn):
+        fn(0)
+        torch.cuda.synchronize()
+        a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for j in range(SETS):
+            fn(j)
+        z.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(z) / SETS
+
+    sel = lambda j: eng.lut_select_records(es[j].data_ptr(), tuples.data_ptr(), out.data_ptr(), E, b)  # noqa: E731
+    cpy = lambda j: dst.copy_(srcs[j])  # noqa: E731
+    sel(3)
+    torch.cuda.synchronize()
+    # the opened values are below 2^k with sign word 0: the entry is word 0's low byte
+    e3 = es[3].cpu().view(E, 32)[:, 0].to(torch.int64) & 255
+    want = tuples.view(E << b, CTW)[(torch.arange(E) << b).to(dev) + e3.to(dev)]
+    same = bool(torch.equal(out.view(E, CTW), want))
+    del want
+    ts, tc = [], []
+    for _ in range(runs):
+        ts.append(window(sel))
+        tc.append(window(cpy))
+    nbytes = E * CTW * 4
+    line = {"op": "lut_select", "E": E, "bits": b, "bytes_moved_each_way": nbytes, "select_ms": round(med(ts), 4),
+            "select_ms_min_max": [round(min(ts), 4), round(max(ts), 4)], "copy_ms": round(med(tc), 4),
+            "copy_ms_min_max": [round(min(tc), 4), round(max(tc), 4)], "select_over_copy": round(med(ts) / med(tc), 3),
+            "select_GB_per_s_read_plus_write": round(2 * nbytes / med(ts) / 1e6, 1), "same_records": same, "runs": runs, "calls_per_window": SETS,
+            "device_status": eng.device_status()}
+    print(json.dumps(line), flush=True)
+    lines.append(line)
+    del srcs, out, dst, es
+    # the same buffer read as 16 times the elements at b = 4: 352 MB each way per call, where a launch no longer shows
+    E2, b2, SETS2 = E << 4, b - 4, 4
+    es2 = []
+    for _ in range(SETS2):
+        rec = np.zeros((E2, 32), dtype=np.uint32)
+        rec[:, :4] = np.random.default_rng(len(es2)).integers(0, 1 << 32, (E2, 4), dtype=np.uint64).astype(np.uint32)
+        es2.append(dev_i32(rec.reshape(-1)))
+    out, dst = torch.zeros(E2 * CTW, dtype=torch.int32, device=dev), torch.zeros(E2 * CTW, dtype=torch.int32, device=dev)
+    srcs = [tuples[j * 4 * E2 * CTW:(j * 4 + 1) * E2 * CTW] for j in range(SETS2)]
+
+    def window2(fn, rounds=8):
+        fn(0)
+        torch.cuda.synchronize()
+        a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for i in range(rounds * SETS2):
+            fn(i % SETS2)
+        z.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(z) / (rounds * SETS2)
+
+    sel2 = lambda j: eng.lut_select_records(es2[j].data_ptr(), tuples.data_ptr(), out.data_ptr(), E2, b2)  # noqa: E731
+    cpy2 = lambda j: dst.copy_(srcs[j])  # noqa: E731
+    ts, tc = [], []
+    for _ in range(runs):
+        ts.append(window2(sel2))
+        tc.append(window2(cpy2))
+    nbytes = E2 * CTW * 4
+    line = {"op": "lut_select_large", "E": E2, "bits": b2, "bytes_moved_each_way": nbytes, "select_ms": round(med(ts), 4),
+            "select_ms_min_max": [round(min(ts), 4), round(max(ts), 4)], "copy_ms": round(med(tc), 4),
+            "copy_ms_min_max": [round(min(tc), 4), round(max(tc), 4)], "select_over_copy": round(med(ts) / med(tc), 3),
+            "select_GB_per_s_read_plus_write": round(2 * nbytes / med(ts) / 1e6, 1), "copy_GB_per_s_read_plus_write": round(2 * nbytes / med(tc) / 1e6, 1),
+            "runs": runs, "calls_per_window": 8 * SETS2, "device_status": eng.device_status()}
+    print(json.dumps(line), flush=True)
+    lines.append(line)
+    del tuples, srcs, out, dst, es2
+    E = 256
+    table = dev_i32(exp_records([v if v < 128 else 0 for v in range(1 << b)]))
+    r = dev_i32(exp_records([rng.bits(K) for _ in range(E)]))
+    rho = dev_i32(exp_records([rng.bits(960) for _ in range(E << b)]))
+    rows = torch.zeros((E << b) * 32, dtype=torch.int32, device=dev)
+    tup = torch.zeros((E << b) * CTW, dtype=torch.int32, device=dev)
+    out = torch.zeros(E * CTW, dtype=torch.int32, device=dev)
+    e = dev_i32(exp_records([rng.bits(K) for _ in range(E)]))
+    dsk = dev_i32(exp_records([hx(prm["sk"])]))
+    pt = torch.zeros(E * ((K + 31) // 32 + 1), dtype=torch.int32, device=dev)
+    t_rot = [timed(lambda: eng.lut_rotate_records(table.data_ptr(), 1, r.data_ptr(), rows.data_ptr(), E, b), reps=20) for _ in range(runs)]
+    t_tup = [timed(lambda: eng.lut_tuples_records(table.data_ptr(), 1, r.data_ptr(), rho.data_ptr(), h_rec, pk_rec, f_rec, tup.data_ptr(), E, b, K),
+                   reps=2) for _ in range(runs)]
+    t_sel = [timed(lambda: eng.lut_select_records(e.data_ptr(), tup.data_ptr(), out.data_ptr(), E, b), reps=20) for _ in range(runs)]
+    t_dec = [timed(lambda: eng.decrypt_records(out.data_ptr(), dsk.data_ptr(), f_rec, pt.data_ptr(), E, K), reps=5) for _ in range(runs)]
+    line = {"op": "lut_rotate", "E": E, "bits": b, "rotate_ms": round(med(t_rot) * 1e3, 4), "runs": runs, "device_status": eng.device_status()}
+    print(json.dumps(line), flush=True)
+    lines.append(line)
+    line = {"op": "relu_parts", "E": E, "bits": b, "kbits": K, "tuples_ms": round(med(t_tup) * 1e3, 3),
+            "tuples_ms_min_max": [round(min(t_tup) * 1e3, 3), round(max(t_tup) * 1e3, 3)], "fresh_encryptions": E << b,
+            "decrypt_ms": round(med(t_dec) * 1e3, 3), "decrypt_ms_min_max": [round(min(t_dec) * 1e3, 3), round(max(t_dec) * 1e3, 3)],
+            "select_ms": round(med(t_sel) * 1e3, 4), "select_ms_min_max": [round(min(t_sel) * 1e3, 4), round(max(t_sel) * 1e3, 4)],
+            "tuple_bytes": (E << b) * CTW * 4, "runs": runs, "device_status": eng.device_status()}
+    print(json.dumps(line), flush=True)
+    lines.append(line)
+    exe = os.path.join(ROOT, "cofhe_amd", "host", "local_bench")
+    for mode, tag, op in (("lookup", "lookup_json: ", "relu"), ("poly_activation", "compare_json: ", "poly_activation")):
+        p = subprocess.run([exe, mode, "256", str(runs)], capture_output=True, text=True, cwd=os.environ.get("TMPDIR", "/tmp"))
+        line = {"op": op, "device_status": 0, "exit_status": p.returncode, "agree": "agree: yes" in p.stdout if mode == "lookup" else None}
+        for ln in p.stdout.splitlines():
+            if ln.startswith(tag):
+                line.update(json.loads(ln[len(tag):]))
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    return lines
+
+
+if "--lut-only" in sys.argv:
+    res = lut_ops()
+    path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "r14_lut", "lut_time.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as fh:
+        json.dump(res, fh, indent=1)
+    sys.exit(0 if all(r["device_status"] == 0 and r.get("exit_status", 0) == 0 and r.get("agree") is not False and r.get("same_records", True)
+                      for r in res) else 1)
+
 # ---- matadd C2 / C5 ---------------------------------------------------------------------------
 for side in ((128,) if (QUICK or "big" in SKIP) else (128, 1024)):
     E = side * side
@@ -334,6 +474,15 @@ sec = timed(lambda: eng.div_close_records(pm.data_ptr(), pdiv.data_ptr(), 1, cts
 emit("div_close_ciphertext_tensor (cofhe_hip_div_close_records)", [E], sec, E, "ciphertexts/s",
      kernel="k_plain_divfloor + k_comb_first + k_compose_pairs tree")
 del pdiv, pquot
+# a table lookup at b = 4: the rows of the tuples and the closing copy (the tuples' ciphertexts: E 2^4 of arbitrary words)
+lbits = 4
+ltab, lrows = dev_i32(exp_records(list(range(1 << lbits)))), torch.zeros((E << lbits) * 32, dtype=torch.int32, device=dev)
+sec = timed(lambda: eng.lut_rotate_records(ltab.data_ptr(), 1, pm.data_ptr(), lrows.data_ptr(), E, lbits), reps=10)
+emit("lut_rotate_plaintext_tensor (cofhe_hip_lut_rotate_records, b = 4)", [E, 1 << lbits], sec, E << lbits, "records/s", kernel="k_lut_rotate")
+ltup = torch.empty((E << lbits) * 336, dtype=torch.int32, device=dev).random_()
+sec = timed(lambda: eng.lut_select_records(pm.data_ptr(), ltup.data_ptr(), out.data_ptr(), E, lbits), reps=10)
+emit("lut_select_ciphertext_tensor (cofhe_hip_lut_select_records, b = 4)", [E], sec, E, "ciphertexts/s", kernel="k_lut_select")
+del ltab, lrows, ltup
 ha, hb = (eng.records_to_bytes(t.cpu().numpy().view(np.uint32), [128, 128]) for t in (cts, other))
 t0 = time.perf_counter()
 hc = eng.sub_ciphertext_tensors(ha, hb)
