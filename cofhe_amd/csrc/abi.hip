@@ -2156,8 +2156,10 @@ int form_bytes_to_records(const uint8_t *bytes, size_t len, int forms_per_elem, 
         const IntView &a = ints[3 * i], &b = ints[3 * i + 1], &cc = ints[3 * i + 2];
         bool ok = put_limbs(rec + REC_A, PLIMBS, a) && put_limbs(rec + REC_B, PLIMBS, b) &&
                   put_limbs(rec + REC_C, 2 * PLIMBS, cc);
-        // a and c of a form are positive: their flag is set only for the value zero
+        // a and c of a form are positive: zero is refused, and so is the flag on a non-zero a or c, which the reference's
+        // reader would negate (a flagged zero is refused as zero)
         if (ok && (bits_of(rec + REC_A, PLIMBS) == 0 || bits_of(rec + REC_C, 2 * PLIMBS) == 0)) ok = false;
+        if (ok && (a.neg || cc.neg)) ok = false;
         if (!ok) {
             free(r);
             return fail(COFHE_HIP_EINVAL, "form coefficient outside the supported range");

@@ -9,125 +9,38 @@
 // magnitude.  The reader takes each length from the next offset and the last one from the buffer
 // size (:429-434, :472-477).
 //
+// The flag means "negative" on b and on exponents only (a flagged zero reads as +0); a and c of a form are positive, and a flag
+// on a non-zero a or c is refused (wire.hpp).
+//
+// The per-thread bodies of k_unpack, k_widths and k_pack live in wire.hpp, which the CPU tests compile for the host.
 // Unpacking is one thread per destination word of the record array (coalesced stores, byte loads
 // served by L2); packing is bit lengths -> exclusive prefix sum of the slot widths (three small
 // kernels) -> one thread per 4 output bytes.  All HBM-bound byte shuffling: no LDS, no MFMA.
 #include <cstring>
 
 #include "ctx.hpp"
+#include "wire.hpp"
 
 using namespace cofhe;
 
 namespace {
 
-constexpr uint64_t OFFMASK = ~(1ull << 63);
-constexpr int EXP_MAG_WORDS_W = 31, EXP_REC_WORDS_W = 32;      // exponent records (qf.hpp)
+constexpr uint64_t OFFMASK = WIRE_OFFMASK;
 
-// kind 2 / 1: forms, 2 or 1 per element (3 integers each); kind 0: plaintext exponents (1 integer)
-struct Geometry {
-    int ints_per_rec;      // integers per destination record: 3 (a, b, c) or 1
-    int rec_words;         // 168 or 32
-};
-__host__ __device__ inline Geometry geometry(int kind) { return kind == 0 ? Geometry{1, EXP_REC_WORDS_W} : Geometry{3, REC_WORDS}; }
-
-// destination of integer `which` of a record: first word, capacity in words
-__device__ inline void slot_of(int kind, int which, int &first, int &cap) {
-    if (kind == 0) {
-        first = 0;
-        cap = EXP_MAG_WORDS_W;
-    } else if (which == 0) {
-        first = REC_A;
-        cap = 40;
-    } else if (which == 1) {
-        first = REC_B;
-        cap = 40;
-    } else {
-        first = REC_C;
-        cap = 80;
-    }
-}
-
-__device__ inline void int_span(const uint64_t *__restrict__ off, uint64_t idx, uint64_t count, uint64_t body_len,
-                                uint64_t &st, uint64_t &en, bool &flag) {
-    const uint64_t o = off[idx];
-    st = o & OFFMASK;
-    flag = (o >> 63) != 0;
-    en = idx + 1 < count ? (off[idx + 1] & OFFMASK) : body_len;
-}
-
-// err bits: 1 corrupt offset table, 2 value wider than its limb plane, 4 a or c of a form is zero
+// one thread per destination word of the record array; err: WIRE_ERR_* bits of every thread ORed together
 __global__ void k_unpack(const uint8_t *__restrict__ body, const uint64_t *__restrict__ off, uint64_t body_len,
                          uint64_t n_rec, int kind, uint32_t *__restrict__ rec, uint32_t *__restrict__ err) {
-    const Geometry gm = geometry(kind);
     const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t r = tid / gm.rec_words;
-    const int w = (int)(tid % gm.rec_words);
-    if (r >= n_rec) return;
-    const uint64_t count = n_rec * gm.ints_per_rec;
-    const int sign_word = kind == 0 ? EXP_MAG_WORDS_W : REC_SIGN;
-    uint32_t val = 0;
-    if (w == sign_word) {
-        // sign of b (forms) / of the exponent: the flag also marks zero, which is not negative
-        const uint64_t idx = r * gm.ints_per_rec + (kind == 0 ? 0 : 1);
-        uint64_t st, en;
-        bool flag;
-        int_span(off, idx, count, body_len, st, en, flag);
-        bool nonzero = false;
-        if (flag && st <= en && en <= body_len)
-            for (uint64_t i = st; i < en; i++) nonzero |= body[i] != 0;
-        val = (flag && nonzero) ? 1u : 0u;
-    } else if (w < sign_word) {
-        int which = 0, first, cap;
-        if (kind != 0) which = w < REC_B ? 0 : w < REC_C ? 1 : 2;
-        slot_of(kind, which, first, cap);
-        const uint64_t idx = r * gm.ints_per_rec + which;
-        uint64_t st, en;
-        bool flag;
-        int_span(off, idx, count, body_len, st, en, flag);
-        if (st > en || en > body_len) {
-            atomicOr(err, 1u);
-            return;
-        }
-        const uint64_t len = en - st;
-        const uint64_t b0 = (uint64_t)(w - first) * 4;
-        for (int i = 0; i < 4; i++)
-            if (b0 + i < len) val |= (uint32_t)body[st + b0 + i] << (8 * i);
-        if (w - first == cap - 1) {                  // top word of the plane: nothing may lie above it
-            bool over = false;
-            for (uint64_t i = (uint64_t)cap * 4; i < len; i++) over |= body[st + i] != 0;
-            if (over) atomicOr(err, 2u);
-        }
-        if (w == first && kind != 0 && which != 1) { // a and c are positive
-            bool nonzero = false;
-            for (uint64_t i = 0; i < len; i++) nonzero |= body[st + i] != 0;
-            if (!nonzero) atomicOr(err, 4u);
-        }
-    }
-    rec[r * gm.rec_words + w] = val;
+    const UnpackWord u = wire_unpack_word(body, off, body_len, n_rec, kind, tid);
+    if (u.err) atomicOr(err, u.err);
+    if (u.store) rec[tid] = u.val;
 }
 
 // width[j] = slot bytes of integer j, flag bit in bit 63 (same packing as the offset table)
 __global__ void k_widths(const uint32_t *__restrict__ rec, uint64_t n_rec, int kind, uint64_t *__restrict__ width) {
-    const Geometry gm = geometry(kind);
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n_rec * gm.ints_per_rec) return;
-    const uint64_t r = j / gm.ints_per_rec;
-    const int which = (int)(j % gm.ints_per_rec);
-    int first, cap;
-    slot_of(kind, which, first, cap);
-    const uint32_t *p = rec + r * gm.rec_words + first;
-    uint32_t bits = 0;
-    for (int i = cap - 1; i >= 0; i--) {
-        const uint32_t v = p[i];
-        if (v) {
-            bits = (uint32_t)i * 32 + 32 - __clz(v);
-            break;
-        }
-    }
-    const uint32_t sign = rec[r * gm.rec_words + (kind == 0 ? EXP_MAG_WORDS_W : REC_SIGN)];
-    const bool signed_slot = kind == 0 || which == 1;
-    const bool flag = bits == 0 || (signed_slot && sign != 0);
-    width[j] = (uint64_t)((bits ? bits : 1) / 8 + 1) | (flag ? (1ull << 63) : 0ull);
+    if (j >= n_rec * geometry(kind).ints_per_rec) return;
+    width[j] = wire_width(rec, kind, j);
 }
 
 // exclusive prefix sum of the low 63 bits, flag bit carried through: off[j] = sum_{i<j} width[i] | flag[j]
@@ -191,22 +104,8 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_offsets(const uint64_t *__restri
 // one thread per (integer, group of 4 output bytes)
 __global__ void k_pack(const uint32_t *__restrict__ rec, const uint64_t *__restrict__ off, const uint64_t *__restrict__ width,
                        uint64_t n_rec, int kind, int max_words, uint8_t *__restrict__ body) {
-    const Geometry gm = geometry(kind);
     const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t j = tid / max_words;
-    const int w = (int)(tid % max_words);
-    if (j >= n_rec * gm.ints_per_rec) return;
-    const uint64_t r = j / gm.ints_per_rec;
-    const int which = (int)(j % gm.ints_per_rec);
-    int first, cap;
-    slot_of(kind, which, first, cap);
-    const uint64_t len = width[j] & OFFMASK;
-    const uint64_t b0 = (uint64_t)w * 4;
-    if (b0 >= len) return;
-    const uint32_t v = w < cap ? rec[r * gm.rec_words + first + w] : 0u;      // the slot may be one byte longer than the plane
-    uint8_t *dst = body + (off[j] & OFFMASK) + b0;
-    for (int i = 0; i < 4; i++)
-        if (b0 + i < len) dst[i] = (uint8_t)(v >> (8 * i));
+    wire_pack_group(rec, off, width, n_rec, kind, max_words, body, tid);
 }
 
 // scratch from the context's block cache (cofhe_hip_malloc): hipMalloc / hipFree would synchronise the device several
@@ -284,7 +183,7 @@ int cofhe_hip_unpack_tensor_device(cofhe_hip_ctx *ctx, const void *d_bytes, size
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     if (e & 1) return fail(COFHE_HIP_EINVAL, "corrupt offset table");
     if (e & 2) return fail(COFHE_HIP_EINVAL, kind == 0 ? "exponent wider than 992 bits" : "form coefficient outside the supported range");
-    if (e & 4) return fail(COFHE_HIP_EINVAL, "form coefficient outside the supported range");
+    if (e & 4) return fail(COFHE_HIP_EINVAL, "form coefficient outside the supported range");      // a or c zero, or flagged
     if (kind != 0) {
         // data from outside: every form must be a reduced form of the context's discriminant -- the kernels assume it
         int valid = 1;
@@ -341,7 +240,7 @@ int cofhe_hip_pack_tensor_device(cofhe_hip_ctx *ctx, const void *d_records, uint
     *len = hdrlen + body_len;
     if (capacity < hdrlen + body_len) return fail(COFHE_HIP_EINVAL, "output buffer too small");
     HIPCHK(hipMemcpyAsync(dst + tab, offs.p, 8ull * count, hipMemcpyDeviceToDevice, st));
-    const int max_words = kind == 0 ? EXP_MAG_WORDS_W + 1 : 81;       // 4-byte groups per slot, incl. the extra byte
+    const int max_words = wire_pack_groups(kind);
     const uint64_t threads = count * (uint64_t)max_words;
     hipLaunchKernelGGL(k_pack, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, (const uint32_t *)d_records,
                        (const uint64_t *)offs.p, (const uint64_t *)width.p, n_records, kind, max_words, dst + hdrlen);

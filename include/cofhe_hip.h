@@ -488,7 +488,13 @@ int cofhe_hip_workspace_plan(const char *op, const uint64_t *args, uint32_t n_ar
 int cofhe_hip_timer_start(cofhe_hip_ctx *ctx, void *stream, void **timer);
 int cofhe_hip_timer_stop(cofhe_hip_ctx *ctx, void *timer, void *stream, float *ms);
 
-/* ---- binary tensor format <-> records (host side, no GPU work) ---- */
+/* ---- binary tensor format <-> records (host side, no GPU work) ----
+ * The format: u32 ndim; u32 shape[ndim]; one u64 per integer -- its byte offset in the body, bit 63 set when the value is not
+ * positive --; the body of little-endian magnitudes, bits/8 + 1 bytes each as written, any length as read (missing bytes are
+ * zero, bytes beyond the limb plane must be zero).  Bit 63 means "negative" on b of a form and on an exponent, where a flagged
+ * zero is the reference's zero and reads as +0.  a and c of a form are positive: zero is refused, and so is bit 63 on a non-zero
+ * a or c (the reference's reader would negate it), by these readers and by cofhe_hip_unpack_tensor_device alike:
+ * COFHE_HIP_EINVAL, "form coefficient outside the supported range". */
 /* ciphertext tensor bytes -> malloc'd record array (free with cofhe_hip_host_free) */
 int cofhe_hip_bytes_to_records(const uint8_t *bytes, size_t len, uint32_t *ndim, uint32_t shape[8],
                                uint32_t **records, uint64_t *n_records);

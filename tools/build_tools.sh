@@ -12,3 +12,8 @@ $H --offload-arch=gfx950 -O2 -std=c++17 -o build/inst_bench tools/inst_bench.hip
 $H --offload-arch=gfx950 -O2 -std=c++17 -Wno-unused-value $WG_TIMING_FLAGS -o build/wg_timing tools/wg_timing.hip cofhe_amd/csrc/abi.hip cofhe_amd/csrc/wire.hip cofhe_amd/csrc/wide.hip &
 wait
 ls -la build/wg_timing build/traffic_calib build/inst_bench
+# the static instruction mix of the built objects x the measured issue costs (tools/gpu_counters.sh takes these when present:
+# object files do not always travel to the GPU box)
+INST_BENCH=${INST_BENCH:-profiles/r02_microbench/inst_bench_run3.txt}
+python3 tools/issue_weights.py part0 k_compose_wg $INST_BENCH > build/issue_weights_compose.json
+python3 tools/issue_weights.py part2 k_tree_level $INST_BENCH > build/issue_weights_matmul.json

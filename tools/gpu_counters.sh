@@ -7,20 +7,29 @@ TAG=${1:-x}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/counters_$TAG
 mkdir -p $OUT
 INST_BENCH=${INST_BENCH:-profiles/r02_microbench/inst_bench_run3.txt}
-# static instruction mix x measured issue costs (no GPU needed, done first so a later failure keeps it)
-python3 tools/issue_weights.py part0 k_compose_wg $INST_BENCH > $OUT/issue_weights_compose.json
-python3 tools/issue_weights.py part2 k_tree_level $INST_BENCH > $OUT/issue_weights_matmul.json
+# static instruction mix x measured issue costs (no GPU needed, done first so a later failure keeps it).  It reads the objects
+# of the build (cofhe_amd/csrc/obj), so tools/build_tools.sh computes it where the library was built; computed here otherwise
+if [ -f build/issue_weights_compose.json ] && [ -f build/issue_weights_matmul.json ]; then
+  cp build/issue_weights_compose.json build/issue_weights_matmul.json $OUT/
+else
+  python3 tools/issue_weights.py part0 k_compose_wg $INST_BENCH > $OUT/issue_weights_compose.json
+  python3 tools/issue_weights.py part2 k_tree_level $INST_BENCH > $OUT/issue_weights_matmul.json
+fi
 bash tools/codeobj_report.sh > $OUT/codeobj_report.txt 2>&1 || true
 # the two helper binaries are cross-compiled in the build container (tools/build_tools.sh -> build/, which travels with the
 # snapshot); built here only when missing (minutes of GPU-box time)
 if [ -x build/traffic_calib ]; then cp build/traffic_calib $OUT/traffic_calib; else hipcc --offload-arch=gfx950 -O3 -std=c++17 -o $OUT/traffic_calib tools/traffic_calib.hip; fi
 # in-kernel clock: diagnostic build with s_memtime / s_memrealtime stamps (no stamp executes in the product kernel)
-if [ -x build/wg_timing ]; then cp build/wg_timing $OUT/wg_timing; else hipcc --offload-arch=gfx950 -O2 -std=c++17 -Wno-unused-value -o $OUT/wg_timing tools/wg_timing.hip cofhe_amd/csrc/abi.hip cofhe_amd/csrc/wire.hip cofhe_amd/csrc/wide.hip; fi
-timeout -k 10 300 python3 tools/wg_timing.py gen $OUT
-timeout -k 10 300 $OUT/wg_timing $OUT/delta.bin $OUT/a.bin $OUT/b.bin 3 > $OUT/wg.csv 2> $OUT/wg_timing.txt || (tail -5 $OUT/wg_timing.txt; exit 1)
-grep '^CLOCK_JSON' $OUT/wg_timing.txt | sed 's/^CLOCK_JSON //' > $OUT/clock.json
-python3 tools/wg_timing.py report $OUT/wg.csv > $OUT/wg_report.txt || true
-echo "clock: $(cat $OUT/clock.json)"
+if [ -x build/wg_timing ]; then
+  cp build/wg_timing $OUT/wg_timing
+  timeout -k 10 300 python3 tools/wg_timing.py gen $OUT
+  timeout -k 10 300 $OUT/wg_timing $OUT/delta.bin $OUT/a.bin $OUT/b.bin 3 > $OUT/wg.csv 2> $OUT/wg_timing.txt || (tail -5 $OUT/wg_timing.txt; exit 1)
+  grep '^CLOCK_JSON' $OUT/wg_timing.txt | sed 's/^CLOCK_JSON //' > $OUT/clock.json
+  python3 tools/wg_timing.py report $OUT/wg.csv > $OUT/wg_report.txt || true
+  echo "clock: $(cat $OUT/clock.json)"
+else
+  echo "build/wg_timing is missing (tools/build_tools.sh): this profile goes without the in-kernel clock; clock_ghz_grbm stands in"
+fi
 export TMPDIR=/tmp
 cd /tmp
 B="python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-family2"
