@@ -282,6 +282,7 @@ class HIPCryptoSystem {
         generate_parameters();
         open_device();
         compute_generator();
+        pack_generators();
         init_mpf();
     }
     // Existing parameters: N (odd, as generated above) and the generator h of the system.
@@ -292,11 +293,12 @@ class HIPCryptoSystem {
         gmp_randseed_ui(rng_, seed);
         derive_from_N();
         open_device();
+        pack_generators();
         init_mpf();
     }
     HIPCryptoSystem(const HIPCryptoSystem &o)
         : sec_level_(o.sec_level_), k_(o.k_), device_(o.device_), N_(o.N_), deltaK_(o.deltaK_), delta_(o.delta_),
-          f_(o.f_), h_(o.h_), exponent_bound_(o.exponent_bound_), rerandomize_(o.rerandomize_),
+          f_(o.f_), h_(o.h_), f_rec_(o.f_rec_), h_rec_(o.h_rec_), exponent_bound_(o.exponent_bound_), rerandomize_(o.rerandomize_),
           tensor_randomness_(o.tensor_randomness_) {
         gmp_randinit_mt(rng_);
         gmp_randseed_ui(rng_, std::random_device{}());     // a copy draws fresh randomness (hpp:37-40)
@@ -412,11 +414,7 @@ class HIPCryptoSystem {
 
     // ---- encryption (GPU: c1 = h^r, c2 = f^m o pk^r; one r per tensor, tensor_ops.inl:7-15) --
     CipherText encrypt(const PublicKey &pk, const PlainText &pt) const {
-        Tensor<PlainText *> t(1, const_cast<PlainText *>(&pt));
-        Tensor<CipherText *> r = encrypt_tensor(pk, t);
-        CipherText out = *r.at(0);
-        delete r.at(0);
-        return out;
+        return single(encrypt_tensor(pk, Tensor<PlainText *>(1, const_cast<PlainText *>(&pt))));
     }
     Tensor<CipherText *> encrypt_tensor(const PublicKey &pk, const Tensor<PlainText *> &pts) const {
         if (tensor_randomness_ == TensorRandomness::PerElement) return encrypt_tensor_fresh(pk, pts);
@@ -427,63 +425,29 @@ class HIPCryptoSystem {
         }
         // c1 = h^r and pk^r once per tensor (two ladders), then one fixed-base kernel for all f^(m_i) o pk^r
         const size_t E = pts.num_elements();
-        std::vector<uint32_t> base(2 * REC, 0), ex(2 * EXPW, 0), plain(E * EXPW, 0), frec(REC, 0);
-        pack_form(h_, &base[0]);
-        pack_form(pk, &base[REC]);
+        const std::array<uint32_t, REC> pkrec = record_of(pk);
+        std::vector<uint32_t> base(h_rec_.begin(), h_rec_.end()), ex(2 * EXPW, 0);
+        base.insert(base.end(), pkrec.begin(), pkrec.end());
         pack_exponent(r, &ex[0]);
         pack_exponent(r, &ex[EXPW]);
-        Tensor<PlainText *> pflat = pts;
-        if (!pts.is_zero_degree()) pflat.flatten();
-        for (size_t i = 0; i < E; i++) pack_exponent(*pflat[i], &plain[i * EXPW]);
-        pack_form(f_, frec.data());
-        void *db = nullptr, *de = nullptr, *dhp = nullptr, *dpl = nullptr;
-        check(cofhe_hip_malloc(ctx_, base.size() * 4, &db)); Guard g1{ctx_, db};
-        check(cofhe_hip_malloc(ctx_, ex.size() * 4, &de)); Guard g2{ctx_, de};
-        check(cofhe_hip_malloc(ctx_, base.size() * 4, &dhp)); Guard g3{ctx_, dhp};
-        check(cofhe_hip_malloc(ctx_, plain.size() * 4 + 4, &dpl)); Guard g4{ctx_, dpl};
-        check(cofhe_hip_upload(ctx_, db, base.data(), base.size() * 4, nullptr));
-        check(cofhe_hip_upload(ctx_, de, ex.data(), ex.size() * 4, nullptr));
-        check(cofhe_hip_upload(ctx_, dpl, plain.data(), plain.size() * 4, nullptr));
-        // h^r and pk^r: fixed bases -> product trees over the cached tables h^(2^j), pk^(2^j)
-        check(cofhe_hip_pow_fixed_base_records(ctx_, 2, base.data(), ex.data(), dhp, nullptr));
-        DeviceTensor out = alloc(pts.is_zero_degree() ? std::vector<size_t>{1} : pts.shape(), E);
-        check(cofhe_hip_encrypt_records(ctx_, dpl, dhp, frec.data(), out.ptr_, E, k_, nullptr));
+        Staged plain = stage(pack_exponents(pts)), hp = device_buffer(base.size() * 4);
+        // h^r and pk^r: fixed bases -> product trees over the cached tables h^(2^j), pk^(2^j); both operands are host records
+        check(cofhe_hip_pow_fixed_base_records(ctx_, 2, base.data(), ex.data(), hp.ptr, nullptr));
+        DeviceTensor out = alloc(shape_of(pts), E);
+        check(cofhe_hip_encrypt_records(ctx_, plain.ptr, hp.ptr, f_rec_.data(), out.ptr_, E, k_, nullptr));
         return download(std::move(out));
     }
     // decryption, all on the GPU: c2 o (c1^sk)^-1 = f^m, m read off bit by bit from the 2-adic
     // valuation visible in the reduced form (kernel k_decrypt; DESIGN.md, "unpinned")
     PlainText decrypt(const SecretKey &sk, const CipherText &ct) const {
-        Tensor<CipherText *> t(1, const_cast<CipherText *>(&ct));
-        Tensor<PlainText *> r = decrypt_tensor(sk, t);
-        PlainText out = *r.at(0);
-        delete r.at(0);
-        return out;
+        return single(decrypt_tensor(sk, Tensor<CipherText *>(1, const_cast<CipherText *>(&ct))));
     }
     Tensor<PlainText *> decrypt_tensor(const SecretKey &sk, const Tensor<CipherText *> &cts) const {
-        const size_t E = cts.num_elements();
+        const size_t E = cts.num_elements(), ow = (k_ + 31) / 32 + 1;
         DeviceTensor dc = upload(cts);
-        std::vector<uint32_t> ex(EXPW, 0), frec(REC, 0);
-        pack_exponent(sk, ex.data());
-        pack_form(f_, frec.data());
-        const size_t ow = (k_ + 31) / 32 + 1;
-        void *dsk = nullptr, *dout = nullptr;
-        check(cofhe_hip_malloc(ctx_, EXPW * 4, &dsk)); Guard g1{ctx_, dsk};
-        check(cofhe_hip_malloc(ctx_, E * ow * 4, &dout)); Guard g3{ctx_, dout};
-        check(cofhe_hip_upload(ctx_, dsk, ex.data(), EXPW * 4, nullptr));
-        check(cofhe_hip_decrypt_records(ctx_, dc.ptr_, dsk, frec.data(), dout, E, k_, nullptr));
-        std::vector<uint32_t> words(E * ow);
-        check(cofhe_hip_download(ctx_, words.data(), dout, words.size() * 4, nullptr));
-        DeviceBlock::throw_on_device_status(ctx_);
-        Tensor<PlainText *> out(cts.is_zero_degree() ? std::vector<size_t>{1} : cts.shape(), nullptr);
-        Tensor<PlainText *> flat = out;
-        flat.flatten();
-        for (size_t i = 0; i < E; i++) {
-            if (words[i * ow + ow - 1] != 0) throw std::runtime_error("ciphertext does not decrypt into <f>");
-            Mpz m;
-            mpz_import(m.get(), ow - 1, -1, 4, 0, 0, &words[i * ow]);
-            flat[i] = new PlainText(std::move(m));
-        }
-        return out;
+        Staged dsk = stage(exponent_record(sk)), dout = device_buffer(E * ow * 4);
+        check(cofhe_hip_decrypt_records(ctx_, dc.ptr_, dsk.ptr, f_rec_.data(), dout.ptr, E, k_, nullptr));
+        return read_plaintexts(dout.ptr, E, ow, shape_of(cts), false, "ciphertext does not decrypt into <f>");
     }
 
     // ---- threshold decryption (reference: cpu_cryptosystem_distributed.inl, tensor_ops.inl:35-73) ---
@@ -521,29 +485,16 @@ class HIPCryptoSystem {
     }
     // d_i = c1^share for every element: one GPU power ladder per ciphertext (kernel k_pow, stride 2)
     PartDecryptionResult part_decrypt(const SecretKeyShare &sks, const CipherText &ct) const {
-        Tensor<CipherText *> t(1, const_cast<CipherText *>(&ct));
-        Tensor<PartDecryptionResult *> r = part_decrypt_tensor(sks, t);
-        PartDecryptionResult out = *r.at(0);
-        delete r.at(0);
-        return out;
+        return single(part_decrypt_tensor(sks, Tensor<CipherText *>(1, const_cast<CipherText *>(&ct))));
     }
     Tensor<PartDecryptionResult *> part_decrypt_tensor(const SecretKeyShare &sks, const Tensor<CipherText *> &cts) const {
         const size_t E = cts.num_elements();
         DeviceTensor dc = upload(cts);
-        std::vector<uint32_t> ex(EXPW, 0), recs(E * REC);
-        pack_exponent(sks, ex.data());
-        void *dsh = nullptr, *dout = nullptr;
-        check(cofhe_hip_malloc(ctx_, EXPW * 4, &dsh)); Guard g1{ctx_, dsh};
-        check(cofhe_hip_malloc(ctx_, recs.size() * 4 + 4, &dout)); Guard g2{ctx_, dout};
-        check(cofhe_hip_upload(ctx_, dsh, ex.data(), EXPW * 4, nullptr));
-        check(cofhe_hip_part_decrypt_records(ctx_, dc.ptr_, dsh, dout, E, nullptr));
-        check(cofhe_hip_download(ctx_, recs.data(), dout, recs.size() * 4, nullptr));
-        DeviceBlock::throw_on_device_status(ctx_);
-        Tensor<PartDecryptionResult *> out(cts.is_zero_degree() ? std::vector<size_t>{1} : cts.shape(), nullptr);
-        Tensor<PartDecryptionResult *> flat = out;
-        flat.flatten();
-        COFHE_HOST_PARALLEL_FOR
-        for (size_t i = 0; i < E; i++) flat[i] = new PartDecryptionResult(unpack_form(&recs[i * REC]));
+        Staged dsh = stage(exponent_record(sks)), dout = device_buffer(E * REC * 4);
+        check(cofhe_hip_part_decrypt_records(ctx_, dc.ptr_, dsh.ptr, dout.ptr, E, nullptr));
+        std::vector<QFI> d = read_forms(dout.ptr, E);
+        Tensor<PartDecryptionResult *> out(shape_of(cts), nullptr);
+        for (size_t i = 0; i < E; i++) out[i] = new PartDecryptionResult(std::move(d[i]));
         return out;
     }
     // m = dlog_f(c2 o (d_0 o d_1^-1 o ... o d_(t-1)^-1)^-1), lambda = (1, -1, ..., -1)
@@ -552,46 +503,27 @@ class HIPCryptoSystem {
         Tensor<CipherText *> t(1, const_cast<CipherText *>(&ct));
         Vector<Tensor<PartDecryptionResult *>> ps;
         for (const auto &p : pdrs) ps.push_back(Tensor<PartDecryptionResult *>(1, const_cast<PartDecryptionResult *>(&p)));
-        Tensor<PlainText *> r = combine_part_decryption_results_tensor(t, ps);
-        PlainText out = *r.at(0);
-        delete r.at(0);
-        return out;
+        return single(combine_part_decryption_results_tensor(t, ps));
     }
     Tensor<PlainText *> combine_part_decryption_results_tensor(const Tensor<CipherText *> &cts,
                                                                const Vector<Tensor<PartDecryptionResult *>> &pdrs) const {
         const size_t E = cts.num_elements(), T = pdrs.size();
         if (T == 0) throw std::invalid_argument("no partial decryptions");
         DeviceTensor dc = upload(cts);
-        std::vector<uint32_t> recs(T * E * REC, 0), frec(REC, 0);
+        std::vector<uint32_t> recs(T * E * REC, 0);
         for (size_t j = 0; j < T; j++) {
             if (pdrs[j].num_elements() != E) throw std::invalid_argument("Tensor shapes must be equal");
             Tensor<PartDecryptionResult *> flat = pdrs[j];
             flat.flatten();
             pack_forms(E, &recs[j * E * REC], [&](size_t i) -> const QFI & { return *flat[i]; });
         }
-        pack_form(f_, frec.data());
         std::vector<int32_t> lambda(T, -1);
         lambda[0] = 1;
         const size_t ow = (k_ + 31) / 32 + 1;
-        void *dp = nullptr, *dout = nullptr;
-        check(cofhe_hip_malloc(ctx_, recs.size() * 4 + 4, &dp)); Guard g1{ctx_, dp};
-        check(cofhe_hip_malloc(ctx_, E * ow * 4 + 4, &dout)); Guard g2{ctx_, dout};
-        check(cofhe_hip_upload(ctx_, dp, recs.data(), recs.size() * 4, nullptr));
-        check(cofhe_hip_combine_part_decryptions_records(ctx_, dc.ptr_, dp, (uint32_t)T, lambda.data(), frec.data(), dout,
+        Staged dp = stage(std::move(recs)), dout = device_buffer(E * ow * 4);
+        check(cofhe_hip_combine_part_decryptions_records(ctx_, dc.ptr_, dp.ptr, (uint32_t)T, lambda.data(), f_rec_.data(), dout.ptr,
                                                          E, k_, nullptr));
-        std::vector<uint32_t> words(E * ow);
-        check(cofhe_hip_download(ctx_, words.data(), dout, words.size() * 4, nullptr));
-        DeviceBlock::throw_on_device_status(ctx_);
-        Tensor<PlainText *> out(pdrs[0].is_zero_degree() ? std::vector<size_t>{1} : pdrs[0].shape(), nullptr);
-        Tensor<PlainText *> flat = out;
-        flat.flatten();
-        for (size_t i = 0; i < E; i++) {
-            if (words[i * ow + ow - 1] != 0) throw std::runtime_error("partial decryptions do not combine into <f>");
-            Mpz m;
-            mpz_import(m.get(), ow - 1, -1, 4, 0, 0, &words[i * ow]);
-            flat[i] = new PlainText(std::move(m));
-        }
-        return out;
+        return read_plaintexts(dout.ptr, E, ow, shape_of(pdrs[0]), false, "partial decryptions do not combine into <f>");
     }
     // binary format of a partial-decryption tensor (cpu_cryptosystem.inl:510-635)
     String serialize_part_decryption_result_tensor(const Tensor<PartDecryptionResult *> &t) const {
@@ -686,14 +618,11 @@ class HIPCryptoSystem {
             return Tensor<CipherText *>(new CipherText(scal_ciphertext(pk, *s.get_value(), *cts.get_value())));
         std::vector<uint32_t> ex = pack_exponents(s);
         DeviceTensor dc = upload(cts);
-        void *dex = nullptr;
-        check(cofhe_hip_malloc(ctx_, ex.size() * 4, &dex));
-        Guard g1{ctx_, dex};
-        check(cofhe_hip_upload(ctx_, dex, ex.data(), ex.size() * 4, nullptr));
+        Staged dex = stage(std::move(ex));
         if (s.is_column_vector() && cts.is_column_vector()) {
             if (s.shape()[0] != cts.shape()[0]) throw std::invalid_argument("Vector sizes must be equal");
             DeviceTensor out = alloc(cts.shape(), cts.num_elements());
-            check(cofhe_hip_pow_records(ctx_, dc.ptr_, dex, out.ptr_, cts.num_elements(), nullptr));
+            check(cofhe_hip_pow_records(ctx_, dc.ptr_, dex.ptr, out.ptr_, cts.num_elements(), nullptr));
             rerandomize_result(pk, out);
             return download(std::move(out));
         }
@@ -704,11 +633,9 @@ class HIPCryptoSystem {
         // There is no faithful result to reproduce, so the call is refused -- with a message of its own, not add's.
         if (s.shape()[0] != m)
             throw std::invalid_argument("scal_ciphertext_tensors: inner dimensions differ (plaintext rows != ciphertext columns)");
-        CipherText z = zero ? *zero : encrypt(pk, make_plaintext(0));
-        Tensor<CipherText *> zt(1, &z);
-        DeviceTensor dz = upload(zt);
+        DeviceTensor dz = zero_tensor(pk, zero);
         DeviceTensor out = alloc({n, p}, n * p);
-        check(cofhe_hip_scal_matmul_records(ctx_, dc.ptr_, dex, dz.ptr_, out.ptr_, (uint32_t)n, (uint32_t)m, (uint32_t)p,
+        check(cofhe_hip_scal_matmul_records(ctx_, dc.ptr_, dex.ptr, dz.ptr_, out.ptr_, (uint32_t)n, (uint32_t)m, (uint32_t)p,
                                             nullptr));
         rerandomize_result(pk, out);           // one fresh r per output (the reference's branch reuses one per row)
         return download(std::move(out));
@@ -721,9 +648,7 @@ class HIPCryptoSystem {
     Tensor<CipherText *> matmul_plaintext_ciphertext_tensors(const PublicKey &pk, const Tensor<PlainText *> &s,
                                                              const Tensor<CipherText *> &cts, const CipherText *zero = nullptr) const {
         if (s.ndim() != 2 || cts.ndim() != 2) throw std::invalid_argument("matmul_plaintext_ciphertext_tensors: both operands must be 2D");
-        CipherText z = zero ? *zero : encrypt(pk, make_plaintext(0));
-        Tensor<CipherText *> zt(1, &z);
-        DeviceTensor out = matmul_plaintext_ciphertext_tensors(s, upload(cts), upload(zt));
+        DeviceTensor out = matmul_plaintext_ciphertext_tensors(s, upload(cts), zero_tensor(pk, zero));
         rerandomize_result(pk, out);           // one fresh r per output, as scal_ciphertext_tensors
         return download(std::move(out));
     }
@@ -734,13 +659,9 @@ class HIPCryptoSystem {
         if (cts.shape_[0] != m)
             throw std::invalid_argument("matmul_plaintext_ciphertext_tensors: inner dimensions differ (plaintext columns != ciphertext rows)");
         if (zero.n_ != 1) throw std::invalid_argument("matmul_plaintext_ciphertext_tensors: zero must be one ciphertext");
-        std::vector<uint32_t> ex = pack_exponents(s);
-        void *dex = nullptr;
-        check(cofhe_hip_malloc(ctx_, ex.size() * 4 + 4, &dex));
-        Guard g1{ctx_, dex};
-        check(cofhe_hip_upload(ctx_, dex, ex.data(), ex.size() * 4, nullptr));
+        Staged dex = stage(pack_exponents(s));
         DeviceTensor out = alloc({n, p}, n * p);
-        check(cofhe_hip_matmul_plain_ct_records(ctx_, dex, cts.ptr_, zero.ptr_, out.ptr_, (uint32_t)n, (uint32_t)m, (uint32_t)p, nullptr));
+        check(cofhe_hip_matmul_plain_ct_records(ctx_, dex.ptr, cts.ptr_, zero.ptr_, out.ptr_, (uint32_t)n, (uint32_t)m, (uint32_t)p, nullptr));
         return out;
     }
     // 2-D convolution, channels last: plaintext filters w [kh, kw, C, Co] over the ciphertext image cts [B, H, W, C] with
@@ -752,11 +673,8 @@ class HIPCryptoSystem {
                                                              const std::array<size_t, 2> &stride = {1, 1}, const std::array<size_t, 2> &pad = {0, 0},
                                                              const CipherText *zero = nullptr) const {
         if (w.ndim() != 4 || cts.ndim() != 4) throw std::invalid_argument("conv2d_plaintext_ciphertext_tensors: both operands must be 4D");
-        CipherText z = zero ? *zero : encrypt(pk, make_plaintext(0));
-        Tensor<CipherText *> zt(1, &z);
-        DeviceTensor out = conv2d_plaintext_ciphertext_tensors(w, upload(cts), upload(zt), stride, pad);
-        rerandomize_result(pk, out);           // one fresh r per output, as scal_ciphertext_tensors
-        return download(std::move(out));
+        if (w.shape()[2] != cts.shape()[3]) throw std::invalid_argument("conv2d_plaintext_ciphertext_tensors: the channels of the filters and of the image differ");
+        return conv2d_plaintext_ciphertext_tensors(pk, w, cts, stride, pad, {1, 1}, 1, zero);      // re-randomised there: one fresh r per output
     }
     // the same on resident operands; deterministic (no re-randomisation), like the other DeviceTensor members
     DeviceTensor conv2d_plaintext_ciphertext_tensors(const Tensor<PlainText *> &w, const DeviceTensor &cts, const DeviceTensor &zero,
@@ -764,22 +682,7 @@ class HIPCryptoSystem {
         if (w.ndim() != 4 || cts.shape_.size() != 4) throw std::invalid_argument("conv2d_plaintext_ciphertext_tensors: both operands must be 4D");
         if (w.shape()[2] != cts.shape_[3]) throw std::invalid_argument("conv2d_plaintext_ciphertext_tensors: the channels of the filters and of the image differ");
         if (zero.n_ != 1) throw std::invalid_argument("conv2d_plaintext_ciphertext_tensors: zero must be one ciphertext");
-        const size_t dims[11] = {cts.shape_[0], cts.shape_[1], cts.shape_[2], cts.shape_[3], w.shape()[0], w.shape()[1], w.shape()[3],
-                                 stride[0], stride[1], pad[0], pad[1]};
-        for (size_t v : dims)
-            if (v > 0xFFFFFFFFull) throw std::invalid_argument("conv2d_plaintext_ciphertext_tensors: extent out of range");
-        const cofhe_hip_conv2d_shape shp{(uint32_t)dims[0], (uint32_t)dims[1], (uint32_t)dims[2], (uint32_t)dims[3], (uint32_t)dims[4], (uint32_t)dims[5],
-                                         (uint32_t)dims[6], (uint32_t)dims[7], (uint32_t)dims[8], (uint32_t)dims[9], (uint32_t)dims[10]};
-        uint32_t Ho = 0, Wo = 0;
-        check(cofhe_hip_conv2d_out_shape(&shp, &Ho, &Wo));
-        std::vector<uint32_t> ex = pack_exponents(w);
-        void *dex = nullptr;
-        check(cofhe_hip_malloc(ctx_, ex.size() * 4 + 4, &dex));
-        Guard g1{ctx_, dex};
-        check(cofhe_hip_upload(ctx_, dex, ex.data(), ex.size() * 4, nullptr));
-        DeviceTensor out = alloc({dims[0], Ho, Wo, dims[6]}, dims[0] * Ho * Wo * dims[6]);
-        check(cofhe_hip_conv2d_plain_ct_records(ctx_, dex, cts.ptr_, zero.ptr_, out.ptr_, &shp, nullptr));
-        return out;
+        return conv2d_plaintext_ciphertext_tensors(w, cts, zero, stride, pad, {1, 1}, 1);      // the same launches (cofhe_hip.h)
     }
     // The same with dilation {rows, columns} and groups: filters w [kh, kw, C / groups, Co], output column co reads the channel
     // block of group co / (Co / groups) (cofhe_hip_conv2d_grouped_plain_ct_records).  groups = C = Co is a depthwise
@@ -788,9 +691,7 @@ class HIPCryptoSystem {
                                                              const std::array<size_t, 2> &stride, const std::array<size_t, 2> &pad,
                                                              const std::array<size_t, 2> &dilation, size_t groups, const CipherText *zero = nullptr) const {
         if (w.ndim() != 4 || cts.ndim() != 4) throw std::invalid_argument("conv2d_plaintext_ciphertext_tensors: both operands must be 4D");
-        CipherText z = zero ? *zero : encrypt(pk, make_plaintext(0));
-        Tensor<CipherText *> zt(1, &z);
-        DeviceTensor out = conv2d_plaintext_ciphertext_tensors(w, upload(cts), upload(zt), stride, pad, dilation, groups);
+        DeviceTensor out = conv2d_plaintext_ciphertext_tensors(w, upload(cts), zero_tensor(pk, zero), stride, pad, dilation, groups);
         rerandomize_result(pk, out);
         return download(std::move(out));
     }
@@ -805,13 +706,9 @@ class HIPCryptoSystem {
                                                              w.shape()[3], stride[0], stride[1], pad[0], pad[1], dilation[0], dilation[1], groups});
         uint32_t Ho = 0, Wo = 0;
         check(cofhe_hip_conv2d_geometry_out_shape(&geo, &Ho, &Wo));
-        std::vector<uint32_t> ex = pack_exponents(w);
-        void *dex = nullptr;
-        check(cofhe_hip_malloc(ctx_, ex.size() * 4 + 4, &dex));
-        Guard g1{ctx_, dex};
-        check(cofhe_hip_upload(ctx_, dex, ex.data(), ex.size() * 4, nullptr));
+        Staged dex = stage(pack_exponents(w));
         DeviceTensor out = alloc({geo.B, Ho, Wo, geo.Co}, (size_t)geo.B * Ho * Wo * geo.Co);
-        check(cofhe_hip_conv2d_grouped_plain_ct_records(ctx_, dex, cts.ptr_, zero.ptr_, out.ptr_, &geo, nullptr));
+        check(cofhe_hip_conv2d_grouped_plain_ct_records(ctx_, dex.ptr, cts.ptr_, zero.ptr_, out.ptr_, &geo, nullptr));
         return out;
     }
     // Sum pooling, channels last: res[b,oy,ox,c] = zero + sum over the kernel[0] x kernel[1] window at (oy stride[0] - pad[0],
@@ -823,9 +720,7 @@ class HIPCryptoSystem {
                                                       const std::array<size_t, 2> &stride, const std::array<size_t, 2> &pad = {0, 0},
                                                       const CipherText *zero = nullptr) const {
         if (cts.ndim() != 4) throw std::invalid_argument("sum_pool2d_ciphertext_tensor: the operand must be 4D");
-        CipherText z = zero ? *zero : encrypt(pk, make_plaintext(0));
-        Tensor<CipherText *> zt(1, &z);
-        DeviceTensor out = sum_pool2d_ciphertext_tensor(upload(cts), upload(zt), kernel, stride, pad);
+        DeviceTensor out = sum_pool2d_ciphertext_tensor(upload(cts), zero_tensor(pk, zero), kernel, stride, pad);
         rerandomize_result(pk, out);
         return download(std::move(out));
     }
@@ -849,22 +744,9 @@ class HIPCryptoSystem {
         if (a.ndim() != 2 || b.ndim() != 2) throw std::invalid_argument("matmul_plaintext_tensors: both operands must be 2D");
         const size_t n = a.shape()[0], m = a.shape()[1], p = b.shape()[1];
         if (b.shape()[0] != m) throw std::invalid_argument("matmul_plaintext_tensors: inner dimensions differ");
-        std::vector<uint32_t> ea = pack_exponents(a), eb = pack_exponents(b), eo(n * p * EXPW, 0);
-        void *da = nullptr, *db = nullptr, *dout = nullptr;
-        check(cofhe_hip_malloc(ctx_, ea.size() * 4 + 4, &da)); Guard g1{ctx_, da};
-        check(cofhe_hip_malloc(ctx_, eb.size() * 4 + 4, &db)); Guard g2{ctx_, db};
-        check(cofhe_hip_malloc(ctx_, eo.size() * 4 + 4, &dout)); Guard g3{ctx_, dout};
-        check(cofhe_hip_upload(ctx_, da, ea.data(), ea.size() * 4, nullptr));
-        check(cofhe_hip_upload(ctx_, db, eb.data(), eb.size() * 4, nullptr));
-        check(cofhe_hip_matmul_plain_plain_records(ctx_, da, db, dout, (uint32_t)n, (uint32_t)m, (uint32_t)p, k_, nullptr));
-        check(cofhe_hip_download(ctx_, eo.data(), dout, eo.size() * 4, nullptr));
-        Tensor<PlainText *> res(std::vector<size_t>{n, p}, nullptr);
-        for (size_t i = 0; i < n * p; i++) {
-            Mpz v;
-            mpz_import(v.get(), EXPW - 1, -1, 4, 0, 0, &eo[i * EXPW]);
-            res[i] = new PlainText(std::move(v));
-        }
-        return res;
+        Staged da = stage(pack_exponents(a)), db = stage(pack_exponents(b)), dout = device_buffer(n * p * EXPW * 4);
+        check(cofhe_hip_matmul_plain_plain_records(ctx_, da.ptr, db.ptr, dout.ptr, (uint32_t)n, (uint32_t)m, (uint32_t)p, k_, nullptr));
+        return read_plaintexts(dout.ptr, n * p, EXPW, {n, p}, false);
     }
 
     // res[i,k] = zero o prod_j x[i,j,k] for x of n*m*p ciphertexts (flat, row-major): the
@@ -918,10 +800,7 @@ class HIPCryptoSystem {
         Tensor<CipherText *> t1(1, const_cast<CipherText *>(&ct1)), t2(1, const_cast<CipherText *>(&ct2));
         DeviceTensor a = upload(t1), b = upload(t2);
         DeviceTensor d = sub_ciphertext_tensors(a, b);
-        Tensor<CipherText *> r = download(d);                      // eager copy: the element outlives the block
-        CipherText out = *r.at(0);
-        delete r.at(0);
-        return rerandomized(pk, out);
+        return rerandomized(pk, single(download(d)));              // eager copy: the element outlives the block
     }
     // (c1^-1, c2^-1): an encryption of -m mod 2^k at no composition.  Not the ciphertext negate_ciphertext_tensor returns
     // (ct^(2^k - 1), tensor_ops.inl:135-195, kept as it is); the plaintexts agree.  Deterministic in every mode.
@@ -960,15 +839,12 @@ class HIPCryptoSystem {
         std::vector<uint32_t> ex(d * E * EXPW, 0);
         for (size_t i = 0; i < d; i++) {
             if (exps[i].num_elements() != E) throw std::invalid_argument("Tensor shapes must be equal");
-            for (size_t e = 0; e < E; e++) pack_exponent(*exps[i][e], &ex[(i * E + e) * EXPW]);
+            pack_exponents(exps[i], ex.data() + i * E * EXPW);
         }
         DeviceTensor db = stack(bases);
-        void *dex = nullptr;
-        check(cofhe_hip_malloc(ctx_, ex.size() * 4 + 4, &dex)); Guard g1{ctx_, dex};
-        check(cofhe_hip_upload(ctx_, dex, ex.data(), ex.size() * 4, nullptr));
-        DeviceTensor out = alloc(bases[0].is_zero_degree() ? std::vector<size_t>{1} : bases[0].shape(), E);
-        check(cofhe_hip_pow_dot_records(ctx_, db.ptr_, dex, out.ptr_, E, (uint32_t)d, nullptr));
-        check(cofhe_hip_stream_sync(ctx_, nullptr));          // `ex` goes with this frame
+        Staged dex = stage(std::move(ex));
+        DeviceTensor out = alloc(shape_of(bases[0]), E);
+        check(cofhe_hip_pow_dot_records(ctx_, db.ptr_, dex.ptr, out.ptr_, E, (uint32_t)d, nullptr));
         rerandomize_result(pk, out);
         return download(std::move(out));
     }
@@ -977,25 +853,13 @@ class HIPCryptoSystem {
     Vector<Tensor<PlainText *>> poly_shift_plaintext_tensor(const Tensor<PlainText *> &coef, const Tensor<PlainText *> &x) const {
         const size_t d1 = coef.num_elements(), E = x.num_elements();
         if (d1 == 0 || d1 > COFHE_HIP_POLY_MAX_DEGREE + 1) throw std::invalid_argument("poly_shift_plaintext_tensor: 1 to 9 coefficients");
-        std::vector<uint32_t> ec(d1 * EXPW, 0), ex(E * EXPW, 0), eq(d1 * E * EXPW, 0);
-        for (size_t j = 0; j < d1; j++) pack_exponent(*coef[j], &ec[j * EXPW]);
-        for (size_t e = 0; e < E; e++) pack_exponent(*x[e], &ex[e * EXPW]);
-        void *dc = nullptr, *dx = nullptr, *dq = nullptr;
-        check(cofhe_hip_malloc(ctx_, ec.size() * 4 + 4, &dc)); Guard g1{ctx_, dc};
-        check(cofhe_hip_malloc(ctx_, ex.size() * 4 + 4, &dx)); Guard g2{ctx_, dx};
-        check(cofhe_hip_malloc(ctx_, eq.size() * 4 + 4, &dq)); Guard g3{ctx_, dq};
-        check(cofhe_hip_upload(ctx_, dc, ec.data(), ec.size() * 4, nullptr));
-        check(cofhe_hip_upload(ctx_, dx, ex.data(), ex.size() * 4, nullptr));
-        check(cofhe_hip_poly_shift_records(ctx_, dc, dx, dq, E, (uint32_t)(d1 - 1), k_, nullptr));
-        check(cofhe_hip_download(ctx_, eq.data(), dq, eq.size() * 4, nullptr));
+        Staged dc = stage(pack_exponents(coef)), dx = stage(pack_exponents(x)), dq = device_buffer(d1 * E * EXPW * 4);
+        check(cofhe_hip_poly_shift_records(ctx_, dc.ptr, dx.ptr, dq.ptr, E, (uint32_t)(d1 - 1), k_, nullptr));
+        const Tensor<PlainText *> q = read_plaintexts(dq.ptr, d1 * E, EXPW, {d1 * E}, false);      // tensor-major: q_i of every element, i = 0..d
         Vector<Tensor<PlainText *>> res;
         for (size_t i = 0; i < d1; i++) {
-            Tensor<PlainText *> t(x.is_zero_degree() ? std::vector<size_t>{1} : x.shape(), nullptr);
-            for (size_t e = 0; e < E; e++) {
-                Mpz v;
-                mpz_import(v.get(), EXPW - 1, -1, 4, 0, 0, &eq[(i * E + e) * EXPW]);
-                t[e] = new PlainText(std::move(v));
-            }
+            Tensor<PlainText *> t(shape_of(x), nullptr);
+            for (size_t e = 0; e < E; e++) t[e] = q[i * E + e];
             res.push_back(t);
         }
         return res;
@@ -1011,19 +875,11 @@ class HIPCryptoSystem {
             throw std::invalid_argument("poly_close_ciphertext_tensor: d + 1 coefficients for d tensors of powers, 1 <= d <= 8");
         for (size_t i = 0; i < d; i++)
             if (powers[i].num_elements() != E) throw std::invalid_argument("Tensor shapes must be equal");
-        std::vector<uint32_t> ec((d + 1) * EXPW, 0), ee(E * EXPW, 0), frec(REC, 0);
-        for (size_t j = 0; j <= d; j++) pack_exponent(*coef[j], &ec[j * EXPW]);
-        for (size_t i = 0; i < E; i++) pack_exponent(*e[i], &ee[i * EXPW]);
-        pack_form(f_, frec.data());
+        std::vector<uint32_t> ec = pack_exponents(coef), ee = pack_exponents(e);
         DeviceTensor dp = stack(powers);
-        void *dc = nullptr, *de = nullptr;
-        check(cofhe_hip_malloc(ctx_, ec.size() * 4 + 4, &dc)); Guard g1{ctx_, dc};
-        check(cofhe_hip_malloc(ctx_, ee.size() * 4 + 4, &de)); Guard g2{ctx_, de};
-        check(cofhe_hip_upload(ctx_, dc, ec.data(), ec.size() * 4, nullptr));
-        check(cofhe_hip_upload(ctx_, de, ee.data(), ee.size() * 4, nullptr));
-        DeviceTensor out = alloc(e.is_zero_degree() ? std::vector<size_t>{1} : e.shape(), E);
-        check(cofhe_hip_poly_close_records(ctx_, dc, de, dp.ptr_, frec.data(), out.ptr_, E, (uint32_t)d, k_, nullptr));
-        check(cofhe_hip_stream_sync(ctx_, nullptr));          // `ec` and `ee` go with this frame
+        Staged dc = stage(std::move(ec)), de = stage(std::move(ee));
+        DeviceTensor out = alloc(shape_of(e), E);
+        check(cofhe_hip_poly_close_records(ctx_, dc.ptr, de.ptr, dp.ptr_, f_rec_.data(), out.ptr_, E, (uint32_t)d, k_, nullptr));
         rerandomize_result(pk, out);
         return download(std::move(out));
     }
@@ -1041,24 +897,9 @@ class HIPCryptoSystem {
     Tensor<PlainText *> divide_plaintext_tensor(const Tensor<PlainText *> &v, const Tensor<PlainText *> &div) const {
         const size_t E = v.num_elements(), nd = div.num_elements();
         check_divisors(div, E);
-        std::vector<uint32_t> ev(E * EXPW, 0), ed(nd * EXPW, 0), eq(E * EXPW, 0);
-        for (size_t e = 0; e < E; e++) pack_exponent(*v[e], &ev[e * EXPW]);
-        for (size_t i = 0; i < nd; i++) pack_exponent(*div[i], &ed[i * EXPW]);
-        void *dv = nullptr, *dd = nullptr, *dq = nullptr;
-        check(cofhe_hip_malloc(ctx_, ev.size() * 4 + 4, &dv)); Guard g1{ctx_, dv};
-        check(cofhe_hip_malloc(ctx_, ed.size() * 4 + 4, &dd)); Guard g2{ctx_, dd};
-        check(cofhe_hip_malloc(ctx_, eq.size() * 4 + 4, &dq)); Guard g3{ctx_, dq};
-        check(cofhe_hip_upload(ctx_, dv, ev.data(), ev.size() * 4, nullptr));
-        check(cofhe_hip_upload(ctx_, dd, ed.data(), ed.size() * 4, nullptr));
-        check(cofhe_hip_divfloor_plain_records(ctx_, dv, dd, nd, dq, E, k_, nullptr));
-        check(cofhe_hip_download(ctx_, eq.data(), dq, eq.size() * 4, nullptr));
-        Tensor<PlainText *> t(v.is_zero_degree() ? std::vector<size_t>{1} : v.shape(), nullptr);
-        for (size_t e = 0; e < E; e++) {
-            Mpz q;
-            mpz_import(q.get(), EXPW - 1, -1, 4, 0, 0, &eq[e * EXPW]);
-            t[e] = new PlainText(std::move(q));
-        }
-        return t;
+        Staged dv = stage(pack_exponents(v)), dd = stage(pack_exponents(div)), dq = device_buffer(E * EXPW * 4);
+        check(cofhe_hip_divfloor_plain_records(ctx_, dv.ptr, dd.ptr, nd, dq.ptr, E, k_, nullptr));
+        return read_plaintexts(dq.ptr, E, EXPW, shape_of(v), false);
     }
     // the closing step of a division by public divisors: res[e] = (c1, c2 o f^(e_q)) of rq[e], e_q = floor(s(e[e]) / div[e mod
     // count]) mod 2^k -- an encryption of floor(s(x[e]) / D) or one less when rq[e] = [r_q] of the element's division pair and
@@ -1076,18 +917,9 @@ class HIPCryptoSystem {
         const size_t E = e.num_elements(), nd = div.num_elements();
         if (rq.n_ != E) throw std::invalid_argument("Tensor shapes must be equal");
         check_divisors(div, E);
-        std::vector<uint32_t> ee(E * EXPW, 0), ed(nd * EXPW, 0), frec(REC, 0);
-        for (size_t i = 0; i < E; i++) pack_exponent(*e[i], &ee[i * EXPW]);
-        for (size_t i = 0; i < nd; i++) pack_exponent(*div[i], &ed[i * EXPW]);
-        pack_form(f_, frec.data());
-        void *de = nullptr, *dd = nullptr;
-        check(cofhe_hip_malloc(ctx_, ee.size() * 4 + 4, &de)); Guard g1{ctx_, de};
-        check(cofhe_hip_malloc(ctx_, ed.size() * 4 + 4, &dd)); Guard g2{ctx_, dd};
-        check(cofhe_hip_upload(ctx_, de, ee.data(), ee.size() * 4, nullptr));
-        check(cofhe_hip_upload(ctx_, dd, ed.data(), ed.size() * 4, nullptr));
-        DeviceTensor out = alloc(e.is_zero_degree() ? std::vector<size_t>{1} : e.shape(), E);
-        check(cofhe_hip_div_close_records(ctx_, de, dd, nd, rq.ptr_, frec.data(), out.ptr_, E, k_, nullptr));
-        check(cofhe_hip_stream_sync(ctx_, nullptr));          // `ee` and `ed` go with this frame
+        Staged de = stage(pack_exponents(e)), dd = stage(pack_exponents(div));
+        DeviceTensor out = alloc(shape_of(e), E);
+        check(cofhe_hip_div_close_records(ctx_, de.ptr, dd.ptr, nd, rq.ptr_, f_rec_.data(), out.ptr_, E, k_, nullptr));
         return out;
     }
     // ---- table lookups from one opened value (cofhe_hip_lut_*; include/cofhe_hip.h states the protocol) ----
@@ -1103,23 +935,9 @@ class HIPCryptoSystem {
         const size_t n = r.num_elements();
         const uint32_t b = lut_table_bits(table, n);
         const size_t n_tab = table.num_elements() >> b;
-        std::vector<uint32_t> et = pack_exponents(table), er = pack_exponents(r), rows((n << b) * EXPW, 0);
-        void *dt = nullptr, *dr = nullptr, *drows = nullptr;
-        check(cofhe_hip_malloc(ctx_, et.size() * 4 + 4, &dt)); Guard g1{ctx_, dt};
-        check(cofhe_hip_malloc(ctx_, er.size() * 4 + 4, &dr)); Guard g2{ctx_, dr};
-        check(cofhe_hip_malloc(ctx_, rows.size() * 4 + 4, &drows)); Guard g3{ctx_, drows};
-        check(cofhe_hip_upload(ctx_, dt, et.data(), et.size() * 4, nullptr));
-        check(cofhe_hip_upload(ctx_, dr, er.data(), er.size() * 4, nullptr));
-        check(cofhe_hip_lut_rotate_records(ctx_, dt, n_tab, dr, drows, n, b, nullptr));
-        check(cofhe_hip_download(ctx_, rows.data(), drows, rows.size() * 4, nullptr));
-        Tensor<PlainText *> t(std::vector<size_t>{n, (size_t)1 << b}, nullptr);
-        for (size_t i = 0; i < (n << b); i++) {
-            Mpz v;
-            mpz_import(v.get(), EXPW - 1, -1, 4, 0, 0, &rows[i * EXPW]);
-            if (rows[i * EXPW + EXPW - 1]) v.neg();
-            t[i] = new PlainText(std::move(v));
-        }
-        return t;
+        Staged dt = stage(pack_exponents(table)), dr = stage(pack_exponents(r)), drows = device_buffer((n << b) * EXPW * 4);
+        check(cofhe_hip_lut_rotate_records(ctx_, dt.ptr, n_tab, dr.ptr, drows.ptr, n, b, nullptr));
+        return read_plaintexts(drows.ptr, n << b, EXPW, {n, (size_t)1 << b}, true);
     }
     // the entries of the lookup tuples: res[i, j] = a FRESH encryption of table[i mod n_tab, (j + r[i]) mod 2^b], a tensor
     // [n, 2^b] (cofhe_hip_lut_tuples_records: the rotation and the fresh-randomness comb, on the device from end to end).  Every
@@ -1128,20 +946,10 @@ class HIPCryptoSystem {
         const size_t n = r.num_elements();
         const uint32_t b = lut_table_bits(table, n);
         const size_t n_tab = table.num_elements() >> b;
-        std::vector<uint32_t> et = pack_exponents(table), er = pack_exponents(r), rho = draw_randomness(n << b), hrec(REC, 0), pkrec(REC, 0), frec(REC, 0);
-        pack_form(h_, hrec.data());
-        pack_form(pk, pkrec.data());
-        pack_form(f_, frec.data());
-        void *dt = nullptr, *dr = nullptr, *drho = nullptr;
-        check(cofhe_hip_malloc(ctx_, et.size() * 4 + 4, &dt)); Guard g1{ctx_, dt};
-        check(cofhe_hip_malloc(ctx_, er.size() * 4 + 4, &dr)); Guard g2{ctx_, dr};
-        check(cofhe_hip_malloc(ctx_, rho.size() * 4 + 4, &drho)); Guard g3{ctx_, drho};
-        check(cofhe_hip_upload(ctx_, dt, et.data(), et.size() * 4, nullptr));
-        check(cofhe_hip_upload(ctx_, dr, er.data(), er.size() * 4, nullptr));
-        check(cofhe_hip_upload(ctx_, drho, rho.data(), rho.size() * 4, nullptr));
+        Staged dt = stage(pack_exponents(table)), dr = stage(pack_exponents(r)), drho = stage(draw_randomness(n << b));
+        const std::array<uint32_t, REC> pkrec = record_of(pk);
         DeviceTensor out = alloc(std::vector<size_t>{n, (size_t)1 << b}, n << b);
-        check(cofhe_hip_lut_tuples_records(ctx_, dt, n_tab, dr, drho, hrec.data(), pkrec.data(), frec.data(), out.ptr_, n, b, k_, nullptr));
-        check(cofhe_hip_stream_sync(ctx_, nullptr));          // the host vectors go with this frame
+        check(cofhe_hip_lut_tuples_records(ctx_, dt.ptr, n_tab, dr.ptr, drho.ptr, h_rec_.data(), pkrec.data(), f_rec_.data(), out.ptr_, n, b, k_, nullptr));
         return download(std::move(out));
     }
     // encrypt_tensor with its own randomness per ciphertext WHATEVER the randomness mode: the masks [r] of the lookup tuples
@@ -1157,13 +965,9 @@ class HIPCryptoSystem {
         const size_t E = e.num_elements();
         if (E == 0 || tuples.n_ % E != 0) throw std::invalid_argument("lookup tuples: 2^b entries for every opened value");
         const uint32_t b = lut_bits(tuples.n_ / E, 1, E);
-        std::vector<uint32_t> ee = pack_exponents(e);
-        void *de = nullptr;
-        check(cofhe_hip_malloc(ctx_, ee.size() * 4 + 4, &de)); Guard g1{ctx_, de};
-        check(cofhe_hip_upload(ctx_, de, ee.data(), ee.size() * 4, nullptr));
-        DeviceTensor out = alloc(e.is_zero_degree() ? std::vector<size_t>{1} : e.shape(), E);
-        check(cofhe_hip_lut_select_records(ctx_, de, tuples.ptr_, out.ptr_, E, b, nullptr));
-        check(cofhe_hip_stream_sync(ctx_, nullptr));          // `ee` goes with this frame
+        Staged de = stage(pack_exponents(e));
+        DeviceTensor out = alloc(shape_of(e), E);
+        check(cofhe_hip_lut_select_records(ctx_, de.ptr, tuples.ptr_, out.ptr_, E, b, nullptr));
         return out;
     }
 
@@ -1186,7 +990,7 @@ class HIPCryptoSystem {
                 DeviceTensor d;
                 d.ctx_ = ctx_;
                 d.ptr_ = b->dptr;
-                d.shape_ = t.is_zero_degree() ? std::vector<size_t>{} : t.shape();
+                d.shape_ = t.shape();                  // empty for a 0-D tensor
                 d.n_ = E;
                 d.keep_ = b;
                 return d;
@@ -1194,9 +998,8 @@ class HIPCryptoSystem {
         }
         std::vector<uint32_t> recs(E * 2 * REC, 0);
         pack_forms(2 * E, recs.data(), [&](size_t i) -> const QFI & { const CipherText &e = *t[i >> 1]; return (i & 1) ? e.c2() : e.c1(); });
-        DeviceTensor d = alloc(t.is_zero_degree() ? std::vector<size_t>{} : t.shape(), E);
-        check(cofhe_hip_upload(ctx_, d.ptr_, recs.data(), recs.size() * 4, nullptr));
-        check(cofhe_hip_stream_sync(ctx_, nullptr));
+        DeviceTensor d = alloc(t.shape(), E);
+        fill(d, recs);
         return d;
     }
     // hands the device tensor over to a Tensor<CipherText *> whose elements reference it (no transfer, no GMP work:
@@ -1249,12 +1052,11 @@ class HIPCryptoSystem {
         if (b && b->ctx == ctx_) {
             // resident result: the wire format is written by the GPU (wire.hip) and only those bytes cross PCIe
             const size_t cap = cofhe_hip_packed_size_bound(E * 2, 2, (uint32_t)shape.size());
-            void *dby = nullptr;
-            check(cofhe_hip_malloc(ctx_, cap, &dby)); Guard g1{ctx_, dby};
+            Staged dby = device_buffer(cap);
             size_t len = 0;
-            check(cofhe_hip_pack_tensor_device(ctx_, b->dptr, E * 2, 2, (uint32_t)shape.size(), shape.data(), dby, cap, &len, nullptr));
+            check(cofhe_hip_pack_tensor_device(ctx_, b->dptr, E * 2, 2, (uint32_t)shape.size(), shape.data(), dby.ptr, cap, &len, nullptr));
             String s(len, '\0');
-            check(cofhe_hip_download(ctx_, &s[0], dby, len, nullptr));
+            check(cofhe_hip_download(ctx_, &s[0], dby.ptr, len, nullptr));
             DeviceBlock::throw_on_device_status(ctx_);       // the bytes leave the process: never with a cap bit set
             return s;
         }
@@ -1292,13 +1094,12 @@ class HIPCryptoSystem {
             E *= dim;
         }
         if (E == 0 || data.size() < 4 + 4ull * nd + 16 * E) return deserialize_ciphertext_tensor_host(data);      // the host parser words the error
-        void *dby = nullptr;
-        check(cofhe_hip_malloc(ctx_, data.size(), &dby)); Guard g1{ctx_, dby};
-        check(cofhe_hip_upload(ctx_, dby, data.data(), data.size(), nullptr));
+        Staged dby = device_buffer(data.size());
+        check(cofhe_hip_upload(ctx_, dby.ptr, data.data(), data.size(), nullptr));      // the caller's bytes: they outlive dby
         DeviceTensor d = alloc(sh, E);
         uint32_t ndim = 0, shape[8];
         uint64_t n = 0;
-        check(cofhe_hip_unpack_tensor_device(ctx_, dby, data.size(), 2, d.ptr_, E * 2, &ndim, shape, &n, nullptr));
+        check(cofhe_hip_unpack_tensor_device(ctx_, dby.ptr, data.size(), 2, d.ptr_, E * 2, &ndim, shape, &n, nullptr));
         return download(std::move(d));
     }
     Tensor<CipherText *> deserialize_ciphertext_tensor_host(const String &data) const {
@@ -1319,15 +1120,11 @@ class HIPCryptoSystem {
 
     // base^e through the context's fixed-base table of `base` (h, public keys)
     QFI pow_fixed_base(const QFI &base, const Mpz &e) const {
-        std::vector<uint32_t> b(REC, 0), x(EXPW, 0), r(REC);
-        pack_form(base, b.data());
-        pack_exponent(e, x.data());
-        void *dout = nullptr;
-        check(cofhe_hip_malloc(ctx_, REC * 4, &dout)); Guard g1{ctx_, dout};
-        check(cofhe_hip_pow_fixed_base_record(ctx_, b.data(), x.data(), dout, nullptr));
-        check(cofhe_hip_download(ctx_, r.data(), dout, REC * 4, nullptr));
-        DeviceBlock::throw_on_device_status(ctx_);
-        return unpack_form(r.data());
+        const std::array<uint32_t, REC> b = record_of(base);
+        const std::vector<uint32_t> x = exponent_record(e);
+        Staged dout = device_buffer(REC * 4);
+        check(cofhe_hip_pow_fixed_base_record(ctx_, b.data(), x.data(), dout.ptr, nullptr));
+        return read_forms(dout.ptr, 1)[0];
     }
     // form-level helpers (also used by the tests): element-wise powers / products on the GPU
     std::vector<QFI> pow_forms(const std::vector<QFI> &bases, const std::vector<Mpz> &exps) const {
@@ -1337,18 +1134,9 @@ class HIPCryptoSystem {
             pack_form(bases[i], &recs[i * REC]);
             pack_exponent(exps[i], &ex[i * EXPW]);
         }
-        void *db = nullptr, *de = nullptr, *dout = nullptr;
-        check(cofhe_hip_malloc(ctx_, recs.size() * 4, &db)); Guard g1{ctx_, db};
-        check(cofhe_hip_malloc(ctx_, ex.size() * 4, &de)); Guard g2{ctx_, de};
-        check(cofhe_hip_malloc(ctx_, recs.size() * 4, &dout)); Guard g3{ctx_, dout};
-        check(cofhe_hip_upload(ctx_, db, recs.data(), recs.size() * 4, nullptr));
-        check(cofhe_hip_upload(ctx_, de, ex.data(), ex.size() * 4, nullptr));
-        check(cofhe_hip_pow_form_records(ctx_, db, de, dout, n, nullptr));
-        check(cofhe_hip_download(ctx_, recs.data(), dout, recs.size() * 4, nullptr));
-        DeviceBlock::throw_on_device_status(ctx_);
-        std::vector<QFI> out(n);
-        for (size_t i = 0; i < n; i++) out[i] = unpack_form(&recs[i * REC]);
-        return out;
+        Staged db = stage(std::move(recs)), de = stage(std::move(ex)), dout = device_buffer(n * REC * 4);
+        check(cofhe_hip_pow_form_records(ctx_, db.ptr, de.ptr, dout.ptr, n, nullptr));
+        return read_forms(dout.ptr, n);
     }
     std::vector<QFI> compose_forms(const std::vector<QFI> &x, const std::vector<QFI> &y) const {
         const size_t n = x.size();
@@ -1357,18 +1145,9 @@ class HIPCryptoSystem {
             pack_form(x[i], &rx[i * REC]);
             pack_form(y[i], &ry[i * REC]);
         }
-        void *dx = nullptr, *dy = nullptr, *dout = nullptr;
-        check(cofhe_hip_malloc(ctx_, rx.size() * 4, &dx)); Guard g1{ctx_, dx};
-        check(cofhe_hip_malloc(ctx_, rx.size() * 4, &dy)); Guard g2{ctx_, dy};
-        check(cofhe_hip_malloc(ctx_, rx.size() * 4, &dout)); Guard g3{ctx_, dout};
-        check(cofhe_hip_upload(ctx_, dx, rx.data(), rx.size() * 4, nullptr));
-        check(cofhe_hip_upload(ctx_, dy, ry.data(), ry.size() * 4, nullptr));
-        check(cofhe_hip_compose_records(ctx_, dx, dy, dout, n, nullptr));
-        check(cofhe_hip_download(ctx_, rx.data(), dout, rx.size() * 4, nullptr));
-        DeviceBlock::throw_on_device_status(ctx_);
-        std::vector<QFI> out(n);
-        for (size_t i = 0; i < n; i++) out[i] = unpack_form(&rx[i * REC]);
-        return out;
+        Staged dx = stage(std::move(rx)), dy = stage(std::move(ry)), dout = device_buffer(n * REC * 4);
+        check(cofhe_hip_compose_records(ctx_, dx.ptr, dy.ptr, dout.ptr, n, nullptr));
+        return read_forms(dout.ptr, n);
     }
 
     // ---- text formats of single values (reference: cpu_cryptosystem.inl:124-227): decimal integers separated by
@@ -1565,14 +1344,9 @@ class HIPCryptoSystem {
     }
     void rerandomize_into(const PublicKey &pk, const DeviceTensor &in, DeviceTensor &out) const {
         if (in.n_ == 0) return;
-        std::vector<uint32_t> ex = draw_randomness(in.n_), hrec(REC, 0), pkrec(REC, 0);
-        pack_form(h_, hrec.data());
-        pack_form(pk, pkrec.data());
-        void *dr = nullptr;
-        check(cofhe_hip_malloc(ctx_, ex.size() * 4, &dr)); Guard g1{ctx_, dr};
-        check(cofhe_hip_upload(ctx_, dr, ex.data(), ex.size() * 4, nullptr));
-        check(cofhe_hip_rerandomize_records(ctx_, in.ptr_, dr, hrec.data(), pkrec.data(), out.ptr_, in.n_, nullptr));
-        check(cofhe_hip_stream_sync(ctx_, nullptr));          // `ex` goes with this frame
+        Staged dr = stage(draw_randomness(in.n_));
+        const std::array<uint32_t, REC> pkrec = record_of(pk);
+        check(cofhe_hip_rerandomize_records(ctx_, in.ptr_, dr.ptr, h_rec_.data(), pkrec.data(), out.ptr_, in.n_, nullptr));
     }
     // a result of this object (its own block, nobody else's view) re-randomised in place in PerElement mode
     void rerandomize_result(const PublicKey &pk, DeviceTensor &t) const {
@@ -1587,53 +1361,105 @@ class HIPCryptoSystem {
         if (ct.is_zero_degree() != pt.is_zero_degree() || ct.shape() != pt.shape()) throw std::invalid_argument("Tensor shapes must be equal");
         const size_t E = ct.num_elements();
         const bool fresh = tensor_randomness_ == TensorRandomness::PerElement;
-        Tensor<PlainText *> pflat = pt;
-        pflat.flatten();
-        std::vector<uint32_t> plain(E * EXPW, 0), ex, hrec(REC, 0), pkrec(REC, 0), frec(REC, 0);
-        for (size_t i = 0; i < E; i++) pack_exponent(*pflat[i], &plain[i * EXPW]);
-        pack_form(f_, frec.data());
-        void *dpl = nullptr, *dr = nullptr;
-        check(cofhe_hip_malloc(ctx_, plain.size() * 4 + 4, &dpl)); Guard g1{ctx_, dpl};
-        check(cofhe_hip_upload(ctx_, dpl, plain.data(), plain.size() * 4, nullptr));
-        Guard g2{ctx_, nullptr};
-        if (fresh && E) {
-            ex = draw_randomness(E);
-            pack_form(h_, hrec.data());
-            pack_form(pk, pkrec.data());
-            check(cofhe_hip_malloc(ctx_, ex.size() * 4, &dr));
-            g2.p = dr;
-            check(cofhe_hip_upload(ctx_, dr, ex.data(), ex.size() * 4, nullptr));
-        }
+        // without fresh randomness there is no block of r (a null pointer) and the records of h and pk are not read
+        Staged dpl = stage(pack_exponents(pt)), dr = fresh && E ? stage(draw_randomness(E)) : Staged();
+        const std::array<uint32_t, REC> pkrec = dr.ptr ? record_of(pk) : std::array<uint32_t, REC>{};
         DeviceTensor in = upload(ct);
         DeviceTensor out = alloc(ct.shape(), E);
-        check(cofhe_hip_add_plain_records(ctx_, in.ptr_, dpl, dr, hrec.data(), pkrec.data(), frec.data(), out.ptr_, E, k_, mode, nullptr));
-        check(cofhe_hip_stream_sync(ctx_, nullptr));          // `plain` and `ex` go with this frame
+        check(cofhe_hip_add_plain_records(ctx_, in.ptr_, dpl.ptr, dr.ptr, h_rec_.data(), pkrec.data(), f_rec_.data(), out.ptr_, E, k_, mode, nullptr));
         return download(std::move(out));
     }
     Tensor<CipherText *> encrypt_tensor_fresh(const PublicKey &pk, const Tensor<PlainText *> &pts) const {
         const size_t E = pts.num_elements();
-        std::vector<uint32_t> ex = draw_randomness(E), plain(E * EXPW, 0), hrec(REC, 0), pkrec(REC, 0), frec(REC, 0);
-        Tensor<PlainText *> pflat = pts;
-        if (!pts.is_zero_degree()) pflat.flatten();
-        for (size_t i = 0; i < E; i++) pack_exponent(*pflat[i], &plain[i * EXPW]);
-        pack_form(h_, hrec.data());
-        pack_form(pk, pkrec.data());
-        pack_form(f_, frec.data());
-        void *dr = nullptr, *dpl = nullptr;
-        check(cofhe_hip_malloc(ctx_, ex.size() * 4 + 4, &dr)); Guard g1{ctx_, dr};
-        check(cofhe_hip_malloc(ctx_, plain.size() * 4 + 4, &dpl)); Guard g2{ctx_, dpl};
-        check(cofhe_hip_upload(ctx_, dr, ex.data(), ex.size() * 4, nullptr));
-        check(cofhe_hip_upload(ctx_, dpl, plain.data(), plain.size() * 4, nullptr));
-        DeviceTensor out = alloc(pts.is_zero_degree() ? std::vector<size_t>{1} : pts.shape(), E);
-        check(cofhe_hip_encrypt_fresh_records(ctx_, dpl, dr, hrec.data(), pkrec.data(), frec.data(), out.ptr_, E, k_, nullptr));
-        check(cofhe_hip_stream_sync(ctx_, nullptr));
+        Staged dr = stage(draw_randomness(E)), dpl = stage(pack_exponents(pts));
+        const std::array<uint32_t, REC> pkrec = record_of(pk);
+        DeviceTensor out = alloc(shape_of(pts), E);
+        check(cofhe_hip_encrypt_fresh_records(ctx_, dpl.ptr, dr.ptr, h_rec_.data(), pkrec.data(), f_rec_.data(), out.ptr_, E, k_, nullptr));
         return download(std::move(out));
     }
-    struct Guard {
-        cofhe_hip_ctx *ctx;
-        void *p;
-        ~Guard() { if (p) cofhe_hip_free(ctx, p); }
+
+    // ---- staging: what every member that reaches the device is made of ---------------------------------------------------------
+    // A device block together with the host words copied into it.  cofhe_hip_upload is an asynchronous copy from pageable memory,
+    // so the words must outlive it: the destructor waits for the stream the copy (and the kernels that read the block) ran on and
+    // only then frees the block and lets the words go.  An error of that wait surfaces at the next call that checks the stream --
+    // the download of the records, at the latest.  Without words (device_buffer) it is a block the device writes and a download
+    // reads: there is no host memory to protect, the free is ordered on the stream like every free of the block cache, no wait.
+    struct Staged {
+        cofhe_hip_ctx *ctx = nullptr;
+        void *ptr = nullptr;
+        std::vector<uint32_t> words;
+        Staged() = default;
+        Staged(Staged &&o) noexcept : ctx(o.ctx), ptr(o.ptr), words(std::move(o.words)) { o.ptr = nullptr; }      // the words keep their address
+        Staged(const Staged &) = delete;
+        Staged &operator=(const Staged &) = delete;
+        ~Staged() {
+            if (!ptr) return;
+            if (!words.empty()) cofhe_hip_stream_sync(ctx, nullptr);
+            cofhe_hip_free(ctx, ptr);
+        }
     };
+    Staged device_buffer(size_t bytes) const {
+        Staged s;
+        s.ctx = ctx_;
+        check(cofhe_hip_malloc(ctx_, bytes, &s.ptr));          // 0 bytes give a block of 4
+        return s;
+    }
+    Staged stage(std::vector<uint32_t> &&words) const {
+        Staged s = device_buffer(words.size() * 4);
+        s.words = std::move(words);
+        check(cofhe_hip_upload(ctx_, s.ptr, s.words.data(), s.words.size() * 4, nullptr));
+        return s;
+    }
+    // records from the host into a tensor's own block; waits for the copy, so `recs` may go when this returns
+    void fill(DeviceTensor &d, const std::vector<uint32_t> &recs) const {
+        check(cofhe_hip_upload(ctx_, d.ptr_, recs.data(), recs.size() * 4, nullptr));
+        synchronize();
+    }
+    // the shape of a result of t's: a 0-D tensor gives one element
+    template <typename T>
+    static std::vector<size_t> shape_of(const Tensor<T> &t) { return t.is_zero_degree() ? std::vector<size_t>{1} : t.shape(); }
+    // the element of a one-element result tensor, by value; the heap object goes
+    template <typename T>
+    static T single(const Tensor<T *> &r) {
+        T out = *r.at(0);
+        delete r.at(0);
+        return out;
+    }
+    // the uploaded one-element tensor a product starts from: `zero`, or a fresh encryption of zero
+    DeviceTensor zero_tensor(const PublicKey &pk, const CipherText *zero) const {
+        CipherText z = zero ? *zero : encrypt(pk, make_plaintext(0));
+        return upload(Tensor<CipherText *>(1, &z));
+    }
+    // n plaintexts of `words` words each, read from the device into a tensor of `shape`: the magnitude is the words below the top
+    // one; the top word is the sign when sign_word is set and ignored otherwise.  not_in_f, given for values that kernels read
+    // off ciphertext records (the two decryptions), is thrown for a top word that is not 0, after the device status word has
+    // had its say.
+    Tensor<PlainText *> read_plaintexts(const void *d, size_t n, size_t words, const std::vector<size_t> &shape, bool sign_word,
+                                        const char *not_in_f = nullptr) const {
+        std::vector<uint32_t> w(n * words);
+        check(cofhe_hip_download(ctx_, w.data(), d, w.size() * 4, nullptr));
+        if (not_in_f) DeviceBlock::throw_on_device_status(ctx_);
+        Tensor<PlainText *> out(shape, nullptr);
+        for (size_t i = 0; i < n; i++) {
+            const uint32_t top = w[i * words + words - 1];
+            if (not_in_f && top != 0) throw std::runtime_error(not_in_f);
+            Mpz v;
+            mpz_import(v.get(), words - 1, -1, 4, 0, 0, &w[i * words]);
+            if (sign_word && top) v.neg();
+            out[i] = new PlainText(std::move(v));
+        }
+        return out;
+    }
+    // n form records read from the device, never with a cap bit set in the status word
+    std::vector<QFI> read_forms(const void *d, size_t n) const {
+        std::vector<uint32_t> recs(n * REC);
+        check(cofhe_hip_download(ctx_, recs.data(), d, recs.size() * 4, nullptr));
+        DeviceBlock::throw_on_device_status(ctx_);
+        std::vector<QFI> out(n);
+        COFHE_HOST_PARALLEL_FOR
+        for (size_t i = 0; i < n; i++) out[i] = unpack_form(&recs[i * REC]);
+        return out;
+    }
     // b of a lookup table of `size` entries, n_tab of them for n elements: size = 2^b, 1 <= b <= COFHE_HIP_LUT_MAX_BITS, b <= k
     uint32_t lut_bits(size_t size, size_t n_tab, size_t n) const {
         uint32_t b = 0;
@@ -1695,10 +1521,24 @@ class HIPCryptoSystem {
         mpz_export(rec, &cnt, -1, 4, 0, 0, e.get());
         rec[31] = e.sgn() < 0 ? 1u : 0u;
     }
+    static std::vector<uint32_t> exponent_record(const Mpz &e) {
+        std::vector<uint32_t> ex(EXPW, 0);
+        pack_exponent(e, ex.data());
+        return ex;
+    }
+    // the elements of s in row-major order, whatever its shape, into consecutive (zeroed) exponent records
+    static void pack_exponents(const Tensor<PlainText *> &s, uint32_t *recs) {
+        for (size_t i = 0; i < s.num_elements(); i++) pack_exponent(*s[i], recs + i * EXPW);
+    }
     static std::vector<uint32_t> pack_exponents(const Tensor<PlainText *> &s) {
         std::vector<uint32_t> ex(s.num_elements() * EXPW, 0);
-        for (size_t i = 0; i < s.num_elements(); i++) pack_exponent(*s[i], &ex[i * EXPW]);
+        pack_exponents(s, ex.data());
         return ex;
+    }
+    static std::array<uint32_t, REC> record_of(const QFI &f) {
+        std::array<uint32_t, REC> rec{};
+        pack_form(f, rec.data());
+        return rec;
     }
     DeviceTensor alloc(const std::vector<size_t> &shape, size_t n) const {
         DeviceTensor d;
@@ -1724,8 +1564,7 @@ class HIPCryptoSystem {
                 pack_forms(2 * E, dst, [&](size_t r) -> const QFI & { const CipherText &c = *t[r >> 1]; return (r & 1) ? c.c2() : c.c1(); });
         }
         DeviceTensor out = alloc({d, E}, d * E);
-        check(cofhe_hip_upload(ctx_, out.ptr_, recs.data(), recs.size() * 4, nullptr));
-        check(cofhe_hip_stream_sync(ctx_, nullptr));
+        fill(out, recs);
         return out;
     }
 
@@ -1830,6 +1669,11 @@ class HIPCryptoSystem {
         mpz_setbit(e.get(), k_ + 1);
         h_ = pow_forms({QFI(a, b, c)}, {e})[0];
     }
+    // the records of f and h, packed once where both are known; nothing writes them after construction (threads share the object)
+    void pack_generators() {
+        f_rec_ = record_of(f_);
+        h_rec_ = record_of(h_);
+    }
     void init_mpf() {
         mpf_init(scaling_factor_); mpf_init(mM_); mpf_init(mM_half_);
         mpf_set_d(scaling_factor_, 2); mpf_set_d(mM_, 2);
@@ -1842,6 +1686,7 @@ class HIPCryptoSystem {
     int device_;
     Mpz N_, deltaK_, delta_;
     QFI f_, h_;
+    std::array<uint32_t, REC> f_rec_{}, h_rec_{};
     Mpz exponent_bound_;
     cofhe_hip_ctx *ctx_ = nullptr;
     std::shared_ptr<cofhe_hip_ctx> ctx_owner_;

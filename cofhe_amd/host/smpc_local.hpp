@@ -255,27 +255,11 @@ class LocalCipherTextMultiplier {
     // caller's: coef[j] comes pre-scaled so that every term carries one scale.  0-D and 1-D tensors; higher ranks are
     // flattened and the result reshaped.
     Tensor<CipherText *> evaluate_polynomial_ciphertext_tensor(const Tensor<PlainText *> &coef, const Tensor<CipherText *> &x) {
-        if (x.is_zero_degree()) {
-            Tensor<CipherText *> r = evaluate_polynomial_ciphertext_tensor(coef, Tensor<CipherText *>(1, x.get_value()));
-            return Tensor<CipherText *>(r.at(0));
-        }
         if (coef.num_elements() < 2) throw std::invalid_argument("evaluate_polynomial_ciphertext_tensor: a polynomial of degree 1 to 8");
-        auto &cs = client_m.crypto_system();
-        const auto &pk = client_m.network_public_key();
-        const size_t n = x.num_elements(), d = coef.num_elements() - 1;
-        Tensor<CipherText *> flat = x;
-        flat.flatten();
-        auto powers = client_m.get_beavers_power_tuples(n, d);
-        auto x_sub_a = cs.sub_ciphertext_tensors(pk, flat, powers[0]);
-        auto e = client_m.decrypt_tensor(x_sub_a);
-        auto ct = cs.poly_close_ciphertext_tensor(pk, coef, e, powers);
-        for (size_t i = 0; i < n; i++) {
-            for (auto &p : powers) delete p[i];
-            delete x_sub_a[i];
-            delete e[i];
-        }
-        ct.reshape(x.shape());
-        return ct;
+        return open_and_close(x, client_m.get_beavers_power_tuples(x.num_elements(), coef.num_elements() - 1),
+                              [&](const Tensor<PlainText *> &e, const Vector<Tensor<CipherText *>> &powers) {
+                                  return client_m.crypto_system().poly_close_ciphertext_tensor(client_m.network_public_key(), coef, e, powers);
+                              });
     }
     // x^2 element-wise: the polynomial (0, 0, 1), one opened value per element where the Beaver product x * x opens two
     Tensor<CipherText *> square_ciphertext_tensor(const Tensor<CipherText *> &x) {
@@ -291,29 +275,14 @@ class LocalCipherTextMultiplier {
     // one divisor, or one per channel of a channels-last tensor (its count divides x's), or one per element.  0-D and 1-D
     // tensors; higher ranks are flattened and the result reshaped.
     Tensor<CipherText *> divide_ciphertext_tensor_by_plaintext(const Tensor<CipherText *> &x, const Tensor<PlainText *> &div) {
-        if (x.is_zero_degree()) {
-            Tensor<CipherText *> r = divide_ciphertext_tensor_by_plaintext(Tensor<CipherText *>(1, x.get_value()), div);
-            return Tensor<CipherText *>(r.at(0));
-        }
         auto &cs = client_m.crypto_system();
-        const auto &pk = client_m.network_public_key();
-        const size_t n = x.num_elements();
         Tensor<PlainText *> d = div.is_zero_degree() ? Tensor<PlainText *>(1, div.get_value()) : div;
         d.flatten();
-        cs.check_divisors(d, n);
-        Tensor<CipherText *> flat = x;
-        flat.flatten();
-        auto pairs = client_m.get_division_pairs(n, d);
-        auto x_sub_r = cs.sub_ciphertext_tensors(pk, flat, pairs[0]);
-        auto e = client_m.decrypt_tensor(x_sub_r);
-        auto ct = cs.div_close_ciphertext_tensor(pk, e, d, pairs[1]);
-        for (size_t i = 0; i < n; i++) {
-            for (auto &p : pairs) delete p[i];
-            delete x_sub_r[i];
-            delete e[i];
-        }
-        ct.reshape(x.shape());
-        return ct;
+        cs.check_divisors(d, x.num_elements());
+        return open_and_close(x, client_m.get_division_pairs(x.num_elements(), d),
+                              [&](const Tensor<PlainText *> &e, const Vector<Tensor<CipherText *>> &pairs) {
+                                  return cs.div_close_ciphertext_tensor(client_m.network_public_key(), e, d, pairs[1]);
+                              });
     }
     // floor(x / 2^t): the rescale after a product of two fixed-point values, 1 <= t <= k - 2
     Tensor<CipherText *> truncate_ciphertext_tensor(const Tensor<CipherText *> &x, uint32_t t) {
@@ -342,27 +311,10 @@ class LocalCipherTextMultiplier {
     // for the result to be g[x]; a b-bit signed value is read as its two's-complement index.  A tuple is 2^b ciphertexts (1344
     // bytes each on the device) per element.  0-D and 1-D tensors; higher ranks are flattened and the result reshaped.
     Tensor<CipherText *> lookup_ciphertext_tensor(const Tensor<PlainText *> &table, const Tensor<CipherText *> &x) {
-        if (x.is_zero_degree()) {
-            Tensor<CipherText *> r = lookup_ciphertext_tensor(table, Tensor<CipherText *>(1, x.get_value()));
-            return Tensor<CipherText *>(r.at(0));
-        }
-        auto &cs = client_m.crypto_system();
-        const auto &pk = client_m.network_public_key();
-        const size_t n = x.num_elements();
-        Tensor<CipherText *> flat = x;
-        flat.flatten();
-        auto tuples = client_m.get_lookup_tuples(n, table);
-        auto x_sub_r = cs.sub_ciphertext_tensors(pk, flat, tuples[0]);
-        auto e = client_m.decrypt_tensor(x_sub_r);
-        auto ct = cs.lut_select_ciphertext_tensor(e, tuples[1]);
-        for (auto &t : tuples)
-            for (size_t i = 0; i < t.num_elements(); i++) delete t[i];
-        for (size_t i = 0; i < n; i++) {
-            delete x_sub_r[i];
-            delete e[i];
-        }
-        ct.reshape(x.shape());
-        return ct;
+        return open_and_close(x, client_m.get_lookup_tuples(x.num_elements(), table),
+                              [&](const Tensor<PlainText *> &e, const Vector<Tensor<CipherText *>> &tuples) {
+                                  return client_m.crypto_system().lut_select_ciphertext_tensor(e, tuples[1]);
+                              });
     }
     // max(x, 0) for `bits`-bit signed values x, exactly: the table holds v for 0 < v < 2^(bits-1) and 0 otherwise
     Tensor<CipherText *> relu_ciphertext_tensor(const Tensor<CipherText *> &x, uint32_t bits) {
@@ -498,6 +450,29 @@ class LocalCipherTextMultiplier {
     }
 
   private:
+    // The protocol of one opened value, behind the polynomial, the division and the lookup: e = Dec(x - material[0]) element-wise,
+    // then close(e, material) makes the result, which takes x's shape.  material is what the client handed out for x's elements,
+    // the mask first; it is used once, so every element of it is freed here, with the difference and the opened values.  A 0-D x
+    // is one element and comes back 0-D; higher ranks are flattened and the result reshaped.
+    template <typename Close>
+    Tensor<CipherText *> open_and_close(const Tensor<CipherText *> &x, Vector<Tensor<CipherText *>> material, Close close) {
+        auto &cs = client_m.crypto_system();
+        Tensor<CipherText *> flat = x.is_zero_degree() ? Tensor<CipherText *>(1, x.get_value()) : x;
+        flat.flatten();
+        auto x_sub_m = cs.sub_ciphertext_tensors(client_m.network_public_key(), flat, material[0]);
+        auto e = client_m.decrypt_tensor(x_sub_m);
+        Tensor<CipherText *> ct = close(e, material);
+        for (auto &t : material)
+            for (size_t i = 0; i < t.num_elements(); i++) delete t[i];
+        for (size_t i = 0; i < e.num_elements(); i++) {
+            delete x_sub_m[i];
+            delete e[i];
+        }
+        if (x.is_zero_degree()) return Tensor<CipherText *>(ct.at(0));
+        ct.reshape(x.shape());
+        return ct;
+    }
+
     // the same product with x - a, y - b by subtraction and e*d as a plaintext addend: per element 2 compositions for the
     // differences (plus the folded c1) and one comb tree for f^(ed), against 2 (k + 1) + 2 compositions and an encryption
     Tensor<CipherText *> vector_mul_direct(const Tensor<CipherText *> &ct1, const Tensor<CipherText *> &ct2, size_t n) {
