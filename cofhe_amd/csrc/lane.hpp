@@ -152,6 +152,7 @@ CF_DEV uint32_t shfl_down1(Ctx &c, uint32_t v, uint32_t fill) {    // value of l
 CF_DEV uint32_t shfl_xor1(Ctx &c, uint32_t v) { return shfl(c, v, c.gl ^ 1); }
 CF_DEV uint32_t shfl_xor2(Ctx &c, uint32_t v) { return shfl(c, v, c.gl ^ 2); }
 CF_DEV uint32_t shfl_mirror(Ctx &c, uint32_t v) { return shfl(c, v, (G - 1) - c.gl); }   // lane i <- lane 7-i
+CF_DEV uint32_t shfl_down4(Ctx &c, uint32_t v) { return shfl(c, v, c.gl + G / 2); }     // lanes 0..3 <- lanes 4..7; lanes 4..7: unspecified
 CF_DEV uint32_t bcast_first(Ctx &c, uint32_t v) { return shfl(c, v, 0); }
 CF_DEV uint32_t bcast_last(Ctx &c, uint32_t v) { return shfl(c, v, G - 1); }
 CF_DEV uint32_t ballot8(Ctx &c, bool p) {
@@ -232,6 +233,11 @@ CF_DEV uint32_t shfl_xor2(Ctx &, uint32_t v) {      // quad_perm:[2,3,0,1]
 }
 CF_DEV uint32_t shfl_mirror(Ctx &, uint32_t v) {    // lane i <- lane G-1-i of its group
     return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141, 0xF, 0xF, true);   // row_half_mirror
+}
+// lanes 0..3 of the group <- lanes 4..7 (row_shl:4); what lanes 4..7 receive belongs to the next group of the row, or is
+// their own value at the end of the row: unspecified, the callers ignore it
+CF_DEV uint32_t shfl_down4(Ctx &, uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x104, 0xF, 0xF, false);
 }
 // broadcast from the first / last lane of the group: two DPP moves (~6 issue cycles) instead of a
 // ds_bpermute (21-28 cycles measured, tools/inst_bench.hip): a quad broadcast, then the half-row mirror written only

@@ -484,6 +484,72 @@ CF_DEV Mp<P + Q> mp_mul(Ctx &c, const Mp<P> &x, const Mp<Q> &y) {
     return r;
 }
 
+// Two LOW products in one pass: lanes 0..3 of the result hold x0 * y0 mod 2^640, lanes 4..7 hold x1 * y1 mod 2^640 (each in the
+// half-group's own chunk order: lane gl owns output chunk gl & 3 of product gl >> 2).  For callers that need a product only
+// modulo a power of two -- the numerators of a 2-adic exact division whose quotient is half a plane (qf.hpp: nucomp_m12).
+// A product modulo 2^640 has four output chunks, and output chunk oc takes the terms x[oc - k] * y[k], k <= oc, only: no
+// second-plane accumulator, nothing to re-target, G / 2 iterations for both products whatever the operands hold.  A lane
+// past its last term multiplies by a chunk of zeros (an address select, no exec-mask region).  Carries stay inside each
+// half-group; what leaves chunk 3 is dropped.  Only limbs 0..19 of the operands are read.
+constexpr int LOW2_CHUNKS = G / 2;
+constexpr int LOW2_BITS = LOW2_CHUNKS * CH * 32;        // 640
+CF_DEV Mp<1> mp_mul_low2(Ctx &c, const Mp<1> &x0, const Mp<1> &y0, const Mp<1> &x1, const Mp<1> &y1) {
+    constexpr int H = LOW2_CHUNKS;
+    static_assert(G == 8 && 4 * PLIMBS + G <= SCRATCH_WORDS && G * (CH + 1) <= SCRATCH_WORDS, "scratch too small");
+    CF_STAT(g_stats.muls += 1);
+    uint32_t *s = c.scratch();
+    CF_UNROLL for (int j = 0; j < CH; j++) {
+        s[c.gl * CH + j] = x0.v[0][j];
+        s[PLIMBS + c.gl * CH + j] = y0.v[0][j];
+        s[2 * PLIMBS + c.gl * CH + j] = x1.v[0][j];
+        s[3 * PLIMBS + c.gl * CH + j] = y1.v[0][j];
+    }
+    s[4 * PLIMBS + c.gl] = 0u;                          // the chunk of zeros (G >= CH words)
+    group_sync(c);
+    const int oc = c.gl & (H - 1);
+    const uint32_t *sx = s + 2 * (c.gl >> 2) * PLIMBS, *sy = sx + PLIMBS;
+    uint32_t w[2 * CH + 1];
+    CF_UNROLL for (int i = 0; i < 2 * CH + 1; i++) w[i] = 0;
+    CF_NOUNROLL for (int k = 0; k < H; k++) {
+        const uint32_t *px = sx + ((oc - k) & (H - 1)) * CH;
+        const uint32_t *py = (k <= oc) ? sy + k * CH : s + 4 * PLIMBS;
+        uint32_t xc[CH], yc[CH];
+        CF_UNROLL for (int j = 0; j < CH; j++) {
+            xc[j] = px[j];
+            yc[j] = py[j];
+        }
+        chunk_mac(w, xc, yc);
+    }
+    group_sync(c);
+    // chunk oc receives limbs 5..9 of chunk oc-1 and the overflow word of chunk oc-2 of its own product
+    CF_UNROLL for (int i = 0; i < CH + 1; i++) s[c.gl * (CH + 1) + i] = w[CH + i];
+    group_sync(c);
+    Mp<1> r;
+    uint32_t cy = 0;
+    CF_UNROLL for (int j = 0; j < CH; j++) {
+        const uint32_t up = (oc >= 1) ? s[(oc >= 1 ? c.gl - 1 : 0) * (CH + 1) + j] : 0u;
+        const uint32_t ov = (j == 0 && oc >= 2) ? s[(oc >= 2 ? c.gl - 2 : 0) * (CH + 1) + CH] : 0u;
+        const uint64_t t = (uint64_t)w[j] + up + ov + cy;
+        r.v[0][j] = (uint32_t)t;
+        cy = (uint32_t)(t >> 32);
+    }
+    group_sync(c);
+    // the word every lane hands to the next chunk of its half, then the single bits that remain: a bit travels at most from
+    // chunk 0 to chunk 3, so H - 1 passes end it; the second pass is already rare (it needs a sum that wraps)
+    for (int pass = 0; pass < H - 1; pass++) {
+        const uint32_t got = shfl_up1(c, cy, 0u);
+        const uint32_t in = (oc == 0) ? 0u : got;
+        if (!any_lane(c, in != 0)) break;
+        cy = in;
+        CF_UNROLL for (int j = 0; j < CH; j++) {
+            const uint32_t t = r.v[0][j] + cy;
+            cy = (t < cy) ? 1u : 0u;
+            r.v[0][j] = t;
+        }
+    }
+    return r;
+}
+
 // ---------------------------------------------------------------------------- division
 // conservative floor(n / d) for d <= 2^32: never above the true quotient, at most 2 below
 CF_DEV uint64_t div64_lower(uint64_t n, uint64_t d) {

@@ -118,9 +118,106 @@ CF_DEV SMp<QP> sdiv_exact(Ctx &c, const SMp<P> &n, const Mp<1> &v) {
     return r;
 }
 
-// M1 = (v2 R - m C)/v1, M2 = (s R + c2d C)/v1 for one remainder/cofactor pair
-CF_DEV void nucomp_m12(Ctx &c, SMp<1> &M1, SMp<2> &M2, const Mp<1> &R, const SMp<1> &C, const Mp<1> &v1,
-                       const Mp<1> &v2, const SMp<1> &m, const SMp<1> &s, const Mp<2> &c2d) {
+// ---- M1 and M2 from low-half products ------------------------------------------------------------------------------------
+// M = (A +- B) / v1 is exact and divided 2-adically (mp_divexact): after the tz trailing zero bits of v1 are shifted out of
+// both operands, bit i of the quotient depends on bits 0..i of the shifted numerator only.  So the low nb + 1 bits of the
+// quotient need the numerator modulo 2^(nb + 1 + tz) and nothing above.  With |M| < 2^nb those nb + 1 bits are M in two's
+// complement -- bit nb is the sign -- and A +- B modulo 2^640 is a wrap-around addition of two LOW products (mp_mul_low2).
+//
+// The bound, from bit lengths alone.  |A +- B| <= A + B < 2^(bits A) + 2^(bits B) <= 2^(max + 1), where bits A <= the sum of
+// its factors' bit lengths and max is the larger of the two sums; v1 >= 2^(bits(v1) - 1); hence
+//     |M| < 2^nb,   nb = max(bits(x0) + bits(y0), bits(x1) + bits(y1)) - bits(v1) + 2      (nb < 0: M == 0, nothing is divided),
+// and the low half serves when   nb + 1 + tz <= 640   and   tz < 32   (mp_divexact divides by long division beyond that).
+// For M1 the factor pairs are (v2, R), (m, C); for M2 they are (s, R), (c2d, C).  Random forms of a 2088-bit discriminant
+// give nb ~ 525; a form with a small first coefficient has a two-plane c2d, fails the bound for M2 and takes the full
+// products below.
+CF_DEV int m12_bound(int bx0, int by0, int bx1, int by1, int bv1) {
+    const int t0 = bx0 + by0, t1 = bx1 + by1;
+    return (t0 > t1 ? t0 : t1) - bv1 + 2;
+}
+CF_DEV bool m12_low_half_serves(int nb, uint32_t v1_limb0) {
+    if (v1_limb0 == 0) return false;
+    return nb + 1 + __builtin_ctz(v1_limb0) <= LOW2_BITS;
+}
+// (lanes 0..3 of pp) +- (lanes 4..7 of pp) modulo 2^640, divided by v1, as sign and magnitude; |quotient| < 2^nb, and
+// neg0 is the sign of the first term.  Lanes 4..7 of the result are zero.
+CF_DEV SMp<1> m12_low_quot(Ctx &c, const Mp<1> &pp, bool sub, int neg0, const Mp<1> &v1, int nb) {
+    if (nb < 0) {                                                // the quotient is zero (as a digit count of zero in sdiv_exact)
+        SMp<1> z;
+        mp_zero(z.m);
+        z.neg = 0;
+        return z;
+    }
+    const bool low = c.gl < LOW2_CHUNKS;
+    const uint32_t flip = sub ? 0xFFFFFFFFu : 0u;
+    Mp<1> n;
+    uint32_t hi[1];
+    {
+        uint32_t cy = (sub && c.gl == 0) ? 1u : 0u;            // two's complement: -B == ~B + 1 over the 640 bits
+        CF_UNROLL for (int j = 0; j < CH; j++) {
+            const uint64_t t = (uint64_t)pp.v[0][j] + (shfl_down4(c, pp.v[0][j]) ^ flip) + cy;
+            n.v[0][j] = (uint32_t)t;
+            cy = (uint32_t)(t >> 32);
+        }
+        hi[0] = low ? cy : 0u;
+    }
+    CF_UNROLL for (int j = 0; j < CH; j++) n.v[0][j] = low ? n.v[0][j] : 0u;
+    (void)mp_resolve(c, n, hi);                                  // lane 3 hands its word to lane 4: beyond 2^640, cleared
+    CF_UNROLL for (int j = 0; j < CH; j++) n.v[0][j] = low ? n.v[0][j] : 0u;
+    Mp<1> q;
+    mp_divexact(c, n, v1, q, (nb + 32) >> 5);
+    // keep bits 0..nb; bit nb is the sign; a negative value is negated into its magnitude: (~q & mask) + 1
+    const int topl = nb >> 5;
+    const uint32_t topmask = (2u << (nb & 31)) - 1u;             // nb & 31 == 31: 2u << 31 == 0, all ones
+    uint32_t sbit = 0;
+    CF_UNROLL for (int j = 0; j < CH; j++) sbit |= (c.gl * CH + j == topl) ? (q.v[0][j] >> (nb & 31)) & 1u : 0u;
+    const bool neg = ballot8(c, sbit != 0) != 0;
+    const uint32_t inv = neg ? 0xFFFFFFFFu : 0u;
+    SMp<1> r;
+    {
+        uint32_t cy = (neg && c.gl == 0) ? 1u : 0u;
+        CF_UNROLL for (int j = 0; j < CH; j++) {
+            const int l = c.gl * CH + j;
+            const uint32_t mask = l < topl ? 0xFFFFFFFFu : (l == topl ? topmask : 0u);
+            const uint64_t t = (uint64_t)((q.v[0][j] ^ inv) & mask) + cy;
+            r.m.v[0][j] = (uint32_t)t;
+            cy = (uint32_t)(t >> 32);
+        }
+        hi[0] = cy;
+    }
+    (void)mp_resolve(c, r.m, hi);
+    r.neg = neg0 ^ (neg ? 1 : 0);
+    return r;
+}
+
+#ifdef COFHE_M12_FULL
+constexpr bool M12_LOW_HALF = false;       // A/B builds (tools/build_variant.sh): the full products only
+#else
+constexpr bool M12_LOW_HALF = true;
+#endif
+
+// M1 = (v2 R - m C)/v1, M2 = (s R + c2d C)/v1 for one remainder/cofactor pair; lv1, lv2 = bits(v1), bits(v2).  Returns true
+// when both came from low-half products -- M2 then fits one plane (its upper plane is zero).  That route is taken only when
+// try_low and every active group of the wavefront passes the bound (one scalar branch; the full products are the complete
+// route and serve everything).
+CF_DEV bool nucomp_m12(Ctx &c, SMp<1> &M1, SMp<2> &M2, const Mp<1> &R, const SMp<1> &C, const Mp<1> &v1,
+                       const Mp<1> &v2, const SMp<1> &m, const SMp<1> &s, const Mp<2> &c2d, int lv1, int lv2, bool try_low) {
+    if (M12_LOW_HALF && try_low) {
+        const int bR = mp_bitlen(c, R), bC = mp_bitlen(c, C.m);
+        const int nb1 = m12_bound(lv2, bR, mp_bitlen(c, m.m), bC, lv1);
+        const int nb2 = m12_bound(mp_bitlen(c, s.m), bR, mp_bitlen(c, c2d), bC, lv1);
+        const uint32_t v1w = bcast_first(c, v1.v[0][0]);
+        const bool ok = m12_low_half_serves(nb1, v1w) && m12_low_half_serves(nb2, v1w);
+        if (CF_LIKELY(!any_lane(c, !ok))) {
+            const Mp<1> pa = mp_mul_low2(c, v2, R, m.m, C.m);
+            M1 = m12_low_quot(c, pa, m.neg == C.neg, 0, v1, nb1);                  // v2 R - m C
+            const Mp<1> pb = mp_mul_low2(c, s.m, R, mp_resize<1>(c2d), C.m);
+            const SMp<1> q2 = m12_low_quot(c, pb, s.neg != C.neg, s.neg, v1, nb2);  // s R + c2d C
+            M2.m = mp_resize<2>(q2.m);
+            M2.neg = q2.neg;
+            return true;
+        }
+    }
     SMp<1> Rs{R, 0};
     SMp<1> v2s{v2, 0};
     SMp<2> t1 = smp_mul(c, v2s, Rs);
@@ -135,14 +232,22 @@ CF_DEV void nucomp_m12(Ctx &c, SMp<1> &M1, SMp<2> &M2, const Mp<1> &R, const SMp
     SMp<2> n2;
     smp_add(c, n2, t3, t4);
     M2 = sdiv_exact<2>(c, n2, v1);
+    return false;
 }
 
-// R*M1 + C*M2 (signed, double width)
-CF_DEV SMp<2> nucomp_dot(Ctx &c, const Mp<1> &R, const SMp<1> &C, const SMp<1> &M1, const SMp<2> &M2) {
+// R*M1 + C*M2 (signed, double width); m2_one_plane (wavefront-uniform): M2 is known to fit a plane (nucomp_m12 returned true)
+CF_DEV SMp<2> nucomp_dot(Ctx &c, const Mp<1> &R, const SMp<1> &C, const SMp<1> &M1, const SMp<2> &M2, bool m2_one_plane) {
     SMp<1> Rs{R, 0};
     SMp<2> p1 = smp_mul(c, Rs, M1);
-    SMp<3> p2w = smp_mul(c, C, M2);
-    SMp<2> p2{mp_resize<2>(p2w.m), p2w.neg};
+    SMp<2> p2;
+    if (M12_LOW_HALF && CF_LIKELY(m2_one_plane)) {
+        const SMp<1> M2l{mp_resize<1>(M2.m), M2.neg};
+        p2 = smp_mul(c, C, M2l);
+    } else {
+        SMp<3> p2w = smp_mul(c, C, M2);
+        p2.m = mp_resize<2>(p2w.m);
+        p2.neg = p2w.neg;
+    }
     SMp<2> r;
     smp_add(c, r, p1, p2);
     return r;
@@ -495,9 +600,9 @@ CF_DEV void qf_compose(Ctx &c, QForm &out, const QForm &fa, const QForm &fb, con
 
     SMp<1> M1;
     SMp<2> M2;
-    nucomp_m12(c, M1, M2, pe.y, C1, v1, v2, m, s, c2d);
-    SMp<2> an = nucomp_dot(c, pe.y, C1, M1, M2);
-    SMp<2> bs = nucomp_dot(c, pe.x, C0, M1, M2);
+    const bool m2_one_plane = nucomp_m12(c, M1, M2, pe.y, C1, v1, v2, m, s, c2d, lv1, lv2, true);
+    SMp<2> an = nucomp_dot(c, pe.y, C1, M1, M2, m2_one_plane);
+    SMp<2> bs = nucomp_dot(c, pe.x, C0, M1, M2, m2_one_plane);
     // b' = -sg * 2 * bs - b1
     SMp<2> bn;
     {
@@ -524,8 +629,8 @@ CF_DEV void qf_compose(Ctx &c, QForm &out, const QForm &fa, const QForm &fb, con
         // a' or b' wider than a plane (tiny v1*v2, e.g. inverse pairs): c' from the other pair
         SMp<1> M1p;
         SMp<2> M2p;
-        nucomp_m12(c, M1p, M2p, pe.x, C0, v1, v2, m, s, c2d);
-        cn = nucomp_dot(c, pe.x, C0, M1p, M2p);
+        (void)nucomp_m12(c, M1p, M2p, pe.x, C0, v1, v2, m, s, c2d, lv1, lv2, false);     // a cold route: the full products
+        cn = nucomp_dot(c, pe.x, C0, M1p, M2p, false);
     }
 
     CF_PHASE(6);
