@@ -1,6 +1,7 @@
 """GPU: division of ciphertext tensors by public divisors from one opened value (cofhe_amd/csrc/divide.hip): k_plain_divfloor
 against Python integers, the closing step and its bytes entry point against the plaintext addend byte for byte and through
 decryption, the whole protocol at the ABI, the refusals, and the protocol through the C++ host layer."""
+import json
 import os
 import random
 import subprocess
@@ -273,3 +274,16 @@ def test_division_through_the_host_layer(tmp_path):
     assert "avg_pool2d: ok" in r.stdout, r.stdout
     delta = -int(open(tmp_path / "local_bench_absdelta.txt").read().strip())
     assert O.check_tensor(delta, open(tmp_path / "local_bench_divide.bin", "rb").read()) == 1
+
+
+def test_division_timed_leg_through_the_host_layer(tmp_path):
+    """local_bench divide 8 1: the timed scalar division that tools/bench_ops.py reads, at the smallest size that keeps the
+    per-channel divisors and the 2 x 2 average pool (a multiple of 4)"""
+    exe = os.path.join(ROOT, "cofhe_amd", "host", "local_bench")
+    r = subprocess.run([exe, "divide", "8", "1"], cwd=tmp_path, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr
+    assert "agree: yes" in r.stdout, r.stdout
+    assert "FAILED" not in r.stdout, r.stdout
+    (line,) = [ln for ln in r.stdout.splitlines() if ln.startswith("divide_json: ")]
+    j = json.loads(line[len("divide_json: "):])
+    assert list(j) == ["E", "runs", "divide_ms", "divide_ms_min_max"]

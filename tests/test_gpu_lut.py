@@ -1,6 +1,7 @@
 """GPU: table lookups on ciphertext tensors from one opened value (cofhe_amd/csrc/lut.hip): k_lut_rotate and k_lut_select
 against Python integers, the tuples entry point against the fresh encryption byte for byte, the whole protocol at the ABI
 through decryption, the bytes entry point, the refusals, and the protocol through the C++ host layer."""
+import json
 import os
 import random
 import subprocess
@@ -313,3 +314,17 @@ def test_lookups_through_the_host_layer(tmp_path):
     assert "distinct c1: yes" in r.stdout, r.stdout
     delta = -int(open(tmp_path / "local_bench_absdelta.txt").read().strip())
     assert O.check_tensor(delta, open(tmp_path / "local_bench_lookup.bin", "rb").read()) == 1
+
+
+def test_lookups_timed_leg_through_the_host_layer(tmp_path):
+    """local_bench lookup 8 1: the timed relu that tools/bench_ops.py reads, at the smallest size that keeps the five fixed
+    values and the 2 x 2 max pool (a multiple of 4)"""
+    exe = os.path.join(ROOT, "cofhe_amd", "host", "local_bench")
+    r = subprocess.run([exe, "lookup", "8", "1"], cwd=tmp_path, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr
+    assert "agree: yes" in r.stdout, r.stdout
+    assert "FAILED" not in r.stdout, r.stdout
+    (line,) = [ln for ln in r.stdout.splitlines() if ln.startswith("lookup_json: ")]
+    j = json.loads(line[len("lookup_json: "):])
+    assert list(j) == ["E", "bits", "runs", "relu_ms", "relu_ms_min_max"]
+    assert j["bits"] == 8

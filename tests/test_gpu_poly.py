@@ -2,6 +2,7 @@
 the C++/GMP oracle byte for byte (a sum of the oracle's scal_1d results), its refusals, k_poly_shift against Python integers,
 the closing step and its bytes entry point against the oracle and through decryption, and the protocol through the C++ host
 layer."""
+import json
 import os
 import random
 import subprocess
@@ -256,3 +257,18 @@ def test_polynomial_activation_through_the_host_layer(tmp_path):
     assert "pow_dot_ciphertext_tensors: ok" in r.stdout, r.stdout
     delta = -int(open(tmp_path / "local_bench_absdelta.txt").read().strip())
     assert O.check_tensor(delta, open(tmp_path / "local_bench_poly_activation.bin", "rb").read()) == 1
+
+
+def test_polynomial_activation_timed_leg_through_the_host_layer(tmp_path):
+    """local_bench poly_activation 8 1: the timed comparison that tools/bench_ops.py reads, at the smallest size that still has
+    all eight special inputs: x^3 by the polynomial opens one value per element, by two chained products four"""
+    exe = os.path.join(ROOT, "cofhe_amd", "host", "local_bench")
+    r = subprocess.run([exe, "poly_activation", "8", "1"], cwd=tmp_path, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr
+    assert "agree: yes" in r.stdout, r.stdout
+    assert "FAILED" not in r.stdout, r.stdout
+    (line,) = [ln for ln in r.stdout.splitlines() if ln.startswith("compare_json: ")]
+    j = json.loads(line[len("compare_json: "):])
+    assert list(j) == ["E", "degree", "runs", "poly_ms", "poly_ms_min_max", "chained_products_ms", "chained_ms_min_max",
+                       "chained_over_poly", "opened_poly", "opened_chained", "agree"]
+    assert j["E"] == 8 and j["opened_poly"] == 8 and j["opened_chained"] == 32 and j["agree"] is True
