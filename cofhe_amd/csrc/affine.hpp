@@ -17,7 +17,7 @@ CF_DEV void qf_sub_records(Ctx &c, QForm &r, const uint32_t *a_rec, const uint32
     qf_load(c, x, a_rec);
     qf_load(c, y, b_rec);
     qf_inverse(c, y);
-    qf_compose<true, COFHE_ADD_WORD_ROUTE>(c, r, x, y, dd);
+    qf_compose<true, COFHE_ADD_WORD_ROUTE, false>(c, r, x, y, dd);
 }
 
 // out = in^-1 on one form record (in == out allowed)

@@ -41,11 +41,12 @@ __device__ __forceinline__ Ctx make_ctx(uint32_t *lds) {
 // are served by its wavefront 0 (mp.hpp: euclid_run_wg).  Groups beyond n recompute
 // the last item and skip the store, so every thread reaches every barrier.
 // One composition per limb group (tensor addition).  Two builds of the same body: k_compose_wg leaves room for four
-// workgroups per CU (128 registers per lane, 305 of the function's values spilled; 266 before M1 and M2 came from low-half
-// products, qf.hpp: the second route costs registers and 38 KB of code, and still saves 3.4 % of the launch,
-// profiles/r05_low_half/) -- the form for grids of many residency
+// workgroups per CU (128 registers per lane, 271 of the function's values spilled; 266 before M1 and M2 came from low-half
+// products, 305 with them, qf.hpp: that second route cost registers and 38 KB of code and still saved 3.4 % of the launch,
+// profiles/r05_low_half/; the one-plane a', b' and the low-half c' gave 34 of them back, cost 23 KB more and saved another
+// 4.4 %, profiles/r16_one_plane/) -- the form for grids of many residency
 // rounds and for the 1024 workgroups of a 128x128 launch, which fill the chip exactly once; k_compose_wg3 asks for three
-// (168 registers, 126 spills) and is 6-9 % faster per workgroup, which pays whenever the whole grid is resident at three per
+// (168 registers, 98 spills) and is 6-9 % faster per workgroup, which pays whenever the whole grid is resident at three per
 // CU anyway: launches of up to 768 workgroups, 24 576 compositions (64x64: 0.255 -> 0.239 ms, 110x111: 0.316 -> 0.288 ms;
 // at 1024 workgroups it needs a second round: 0.49 ms.  profiles/r04_a/sizes_wps234.txt; two per CU, no spills at all, is no
 // faster than three).
@@ -149,7 +150,7 @@ __device__ __forceinline__ Ctx make_wg_ctx(uint32_t *lds) {
             qf_load(c, l_, (dummy_rec));                          \
             r_ = l_;                                              \
         }                                                         \
-        qf_compose<true, false>(c, result, l_, r_, dd);                  \
+        qf_compose<true, false, false>(c, result, l_, r_, dd);                  \
     }
 
 // out[g] = base[g * base_stride]^exp[...]  (binary ladder; exponent 0 -> principal form, negative ->
@@ -200,7 +201,7 @@ __global__ void __launch_bounds__(WG_BLOCK, COFHE_WPS) k_pow(const uint32_t *__r
         } else {
             rhs = l_;
         }
-        qf_compose<true, false>(c, r, l_, rhs, dd);
+        qf_compose<true, false, false>(c, r, l_, rhs, dd);
         if (has) {
             qf_store(c, r, accp);
             if (!mul_phase && dgt != 0) {
@@ -304,7 +305,7 @@ __global__ void __launch_bounds__(WG_BLOCK, COFHE_WPS) k_square_chain(const uint
     if (writer) qf_store(c, acc, table);
     for (uint32_t j = 1; j < len; j++) {
         QForm r;
-        qf_compose<true, false>(c, r, acc, acc, dd);
+        qf_compose<true, false, false>(c, r, acc, acc, dd);
         acc = r;
         if (writer) qf_store(c, acc, table + (uint64_t)j * REC_WORDS);
     }
@@ -390,7 +391,7 @@ __global__ void __launch_bounds__(WG_BLOCK, COFHE_WPS) k_compose_pairs(const uin
         if (g0 < total) qf_store(c, a_one ? b : a, out + g * REC_WORDS);
         return;
     }
-    qf_compose<true, false>(c, r, a, b, dd);
+    qf_compose<true, false, false>(c, r, a, b, dd);
     if (g0 < total) qf_store(c, r, out + g * REC_WORDS);
 }
 #endif
@@ -420,7 +421,7 @@ __global__ void __launch_bounds__(WG_BLOCK, COFHE_WPS) k_accumulate(const uint32
         QForm l_, rhs, r;
         qf_load(c, l_, (j == 0 || !alive) ? zero + h * REC_WORDS : (const uint32_t *)accp);
         qf_load(c, rhs, x + ((((uint64_t)i * m + j) * p + k) * 2 + h) * REC_WORDS);
-        qf_compose<true, false>(c, r, l_, rhs, dd);
+        qf_compose<true, false, false>(c, r, l_, rhs, dd);
         if (alive) qf_store(c, r, accp);
     }
     if (m == 0 && alive) {
@@ -524,7 +525,7 @@ __device__ __forceinline__ void k_pow_table_body(const uint32_t *__restrict__ ba
             qf_load(c, l_, out + (uint64_t)(d - 1) * REC_WORDS);
             qf_load(c, r_, out + (uint64_t)(tw - 1) * REC_WORDS);
         }
-        qf_compose<true, false>(c, r, l_, r_, dd);
+        qf_compose<true, false, false>(c, r, l_, r_, dd);
         if (alive) qf_store(c, r, out + (uint64_t)(d == 0 ? tw - 1 : d) * REC_WORDS);
     }
 }
@@ -672,7 +673,7 @@ __device__ __forceinline__ void k_scal_matmul_wnaf_body(const uint32_t *__restri
         } else {
             r_ = l_;
         }
-        qf_compose<true, COFHE_MATMUL_WORD_ROUTE>(c, r2, l_, r_, dd);
+        qf_compose<true, COFHE_MATMUL_WORD_ROUTE, false>(c, r2, l_, r_, dd);
         if (has) qf_store(c, r2, accp);
     }
 }
@@ -876,7 +877,7 @@ __global__ void __launch_bounds__(WG_BLOCK, COFHE_WPS) k_tree_level(const uint32
         return;
     }
     if (paired) element(b, base + 2 * q + 1); else b = a;
-    qf_compose<true, false>(c, r, a, b, dd);
+    qf_compose<true, false, false>(c, r, a, b, dd);
     if (g0 < total) qf_store(c, paired ? r : a, out);
 }
 #endif
@@ -964,7 +965,7 @@ __device__ __forceinline__ void pow_shared_body(Ctx &c, const uint32_t *__restri
         } else {
             r_ = l_;
         }
-        qf_compose<WG, false>(c, r, l_, r_, dd);
+        qf_compose<WG, false, false>(c, r, l_, r_, dd);
         qf_store(c, r, dst);
         if (ts < table_steps) ts++;
     }

@@ -32,7 +32,7 @@ __global__ void __launch_bounds__(WG_BLOCK, COFHE_WPS) k_comb_table(uint32_t *__
     QForm a, b, r;
     qf_load(c, a, row + (u - 1) * REC_WORDS);
     qf_load(c, b, row + (uint64_t)(half - 1) * REC_WORDS);
-    qf_compose<true, false>(c, r, a, b, dd);
+    qf_compose<true, false, false>(c, r, a, b, dd);
     if (g0 < total) qf_store(c, r, row + (u + half - 1) * REC_WORDS);
 }
 
@@ -76,7 +76,7 @@ __global__ void __launch_bounds__(WG_BLOCK, COFHE_WPS) k_comb_first(CombShape s,
         return;
     }
     QForm r;
-    qf_compose<true, false>(c, r, x[0], x[1], dd);
+    qf_compose<true, false, false>(c, r, x[0], x[1], dd);
     if (g0 < total) qf_store(c, r, out + g * REC_WORDS);
 }
 

@@ -136,7 +136,7 @@ CF_DEV void conv_level0_body(Ctx &c, uint64_t wg, const ConvShape &s, const uint
         return;
     }
     if (paired) element(b, base + 2 * q + 1); else b = a;
-    qf_compose<true, false>(c, r, a, b, dd);
+    qf_compose<true, false, false>(c, r, a, b, dd);
     if (g0 < total) qf_store(c, paired ? r : a, out);
 }
 

@@ -550,6 +550,144 @@ CF_DEV Mp<1> mp_mul_low2(Ctx &c, const Mp<1> &x0, const Mp<1> &y0, const Mp<1> &
     return r;
 }
 
+// Two FULL products of half-plane operands in one pass: p0 = x0 * y0, p1 = x1 * y1 for operands below 2^640, each result one
+// plane in the usual chunk order (qf.hpp: nucomp_dot_half).  Only limbs 0..19 of the operands are read.  A product of two
+// four-chunk numbers has output chunks 0..7 with 1, 2, 3, 4, 3, 2, 1, 0 terms; lane gl takes chunk gl of the first product
+// and chunk (gl + 4) & 7 of the second, which is four real terms for every lane (1 + 3, 2 + 2, 3 + 1, 4 + 0, ...): four
+// iterations for both products, no lane multiplies a chunk of zeros.  A lane runs ONE accumulator through its terms of the
+// first product and on through those of the second, and keeps a copy of it from the iteration its first product ended at
+// (11 selects per iteration; the second product's chunk is the difference, 11 subtractions once) -- against the 22 selects
+// per iteration with which mp_mul re-targets its two accumulators.  The second result comes back to the usual order through
+// the LDS slice (lane gl reads what lane (gl + 4) & 7 wrote).  Fixed trip count whatever the operands hold.
+struct MpPair {
+    Mp<1> p0, p1;
+};
+CF_DEV MpPair mp_mul_half2(Ctx &c, const Mp<1> &x0, const Mp<1> &y0, const Mp<1> &x1, const Mp<1> &y1) {
+    constexpr int H = LOW2_CHUNKS, HL = H * CH, W = 2 * CH + 1;
+    static_assert(G == 8 && 4 * HL <= SCRATCH_WORDS && G * (CH + 1) + G * W <= SCRATCH_WORDS, "scratch too small");
+    CF_STAT(g_stats.muls += 1);
+    uint32_t *s = c.scratch();
+    if (c.gl < H) {
+        CF_UNROLL for (int j = 0; j < CH; j++) {
+            s[c.gl * CH + j] = x0.v[0][j];
+            s[HL + c.gl * CH + j] = y0.v[0][j];
+            s[2 * HL + c.gl * CH + j] = x1.v[0][j];
+            s[3 * HL + c.gl * CH + j] = y1.v[0][j];
+        }
+    }
+    const int oc1 = (c.gl + H) & (G - 1);                  // this lane's output chunk of the second product
+    uint32_t w0[W], w1[W];
+    group_sync(c);
+    // output chunk oc of a product takes x[oc - k] * y[k] for k = max(0, oc - 3) .. min(3, oc)
+    const int n0 = c.gl < H ? c.gl + 1 : G - 1 - c.gl;     // terms of the first product's chunk gl; the second's has H - n0
+    const int k0 = c.gl < H ? 0 : c.gl - (H - 1), k1 = oc1 < H ? 0 : oc1 - (H - 1);
+    {
+        uint32_t w[W];
+        CF_UNROLL for (int i = 0; i < W; i++) w[i] = w0[i] = 0;
+        CF_NOUNROLL for (int t = 0; t < H; t++) {
+            const bool first = t < n0;
+            const int k = first ? k0 + t : k1 + t - n0;
+            const uint32_t *px = s + (first ? 0 : 2 * HL) + ((first ? c.gl : oc1) - k) * CH;
+            const uint32_t *py = s + (first ? HL : 3 * HL) + k * CH;
+            uint32_t xc[CH], yc[CH];
+            CF_UNROLL for (int j = 0; j < CH; j++) {
+                xc[j] = px[j];
+                yc[j] = py[j];
+            }
+            chunk_mac(w, xc, yc);
+            const bool last_of_first = (t + 1 == n0);       // never for the lane whose first chunk has no term: w0 stays zero
+            CF_UNROLL for (int i = 0; i < W; i++) w0[i] = last_of_first ? w[i] : w0[i];
+        }
+        uint32_t bw = 0;
+        CF_UNROLL for (int i = 0; i < W; i++) {
+            const uint64_t d = (uint64_t)w[i] - w0[i] - bw;
+            w1[i] = (uint32_t)d;
+            bw = (uint32_t)(d >> 63);
+        }
+    }
+    group_sync(c);
+    // chunk cc receives limbs 5..9 of chunk cc-1 and the overflow word of chunk cc-2 of its own product; the second
+    // product's windows are written whole, at their chunk's place
+    uint32_t *s1 = s + G * (CH + 1);
+    CF_UNROLL for (int i = 0; i < CH + 1; i++) s[c.gl * (CH + 1) + i] = w0[CH + i];
+    CF_UNROLL for (int i = 0; i < W; i++) s1[oc1 * W + i] = w1[i];
+    group_sync(c);
+    Mp<2> r;
+    uint32_t hi[2];
+    {
+        uint32_t cy = 0, cz = 0;
+        CF_UNROLL for (int j = 0; j < CH; j++) {
+            const uint32_t up = (c.gl >= 1) ? s[(c.gl >= 1 ? c.gl - 1 : 0) * (CH + 1) + j] : 0u;
+            const uint32_t ov = (j == 0 && c.gl >= 2) ? s[(c.gl >= 2 ? c.gl - 2 : 0) * (CH + 1) + CH] : 0u;
+            const uint64_t t = (uint64_t)w0[j] + up + ov + cy;
+            r.v[0][j] = (uint32_t)t;
+            cy = (uint32_t)(t >> 32);
+            const uint32_t up1 = (c.gl >= 1) ? s1[(c.gl >= 1 ? c.gl - 1 : 0) * W + CH + j] : 0u;
+            const uint32_t ov1 = (j == 0 && c.gl >= 2) ? s1[(c.gl >= 2 ? c.gl - 2 : 0) * W + 2 * CH] : 0u;
+            const uint64_t u = (uint64_t)s1[c.gl * W + j] + up1 + ov1 + cz;
+            r.v[1][j] = (uint32_t)u;
+            cz = (uint32_t)(u >> 32);
+        }
+        hi[0] = cy;
+        hi[1] = cz;
+    }
+    group_sync(c);
+    // the two results as the planes of one value: nothing passes between them, each product is below 2^1280
+    (void)mp_resolve_sparse(c, r, hi);
+    MpPair pp;
+    CF_UNROLL for (int j = 0; j < CH; j++) {
+        pp.p0.v[0][j] = r.v[0][j];
+        pp.p1.v[0][j] = r.v[1][j];
+    }
+    return pp;
+}
+
+// x * x modulo 2^1280: output chunk gl takes the terms x[gl - k] * x[k], k <= gl, only -- one accumulator, no second plane,
+// nothing to re-target; a lane past its last term multiplies by a chunk of zeros (the address select of mp_mul_low2).  What
+// leaves chunk 7 is dropped.  For the numerator of a 2-adic exact division whose quotient fits the plane (qf.hpp: nucomp_c_low).
+// Only the non-zero chunks of x are visited, as in mp_mul: the trip count is the group's, so a wavefront pays for the longest
+// of its groups.
+CF_DEV Mp<1> mp_sqr_low(Ctx &c, const Mp<1> &x) {
+    static_assert(PLIMBS + G <= SCRATCH_WORDS && G * (CH + 1) <= SCRATCH_WORDS, "scratch too small");
+    CF_STAT(g_stats.muls += 1);
+    uint32_t *s = c.scratch();
+    CF_UNROLL for (int j = 0; j < CH; j++) s[c.gl * CH + j] = x.v[0][j];
+    s[PLIMBS + c.gl] = 0u;                                  // the chunk of zeros (G >= CH words)
+    group_sync(c);
+    const int kx = (mp_bitlen(c, x) + CH * 32 - 1) / (CH * 32);
+    uint32_t w[2 * CH + 1];
+    CF_UNROLL for (int i = 0; i < 2 * CH + 1; i++) w[i] = 0;
+    CF_NOUNROLL for (int k = 0; k < kx; k++) {
+        const uint32_t *px = s + ((c.gl - k) & (G - 1)) * CH;
+        const uint32_t *py = (k <= c.gl) ? s + k * CH : s + PLIMBS;
+        uint32_t xc[CH], yc[CH];
+        CF_UNROLL for (int j = 0; j < CH; j++) {
+            xc[j] = px[j];
+            yc[j] = py[j];
+        }
+        chunk_mac(w, xc, yc);
+    }
+    group_sync(c);
+    CF_UNROLL for (int i = 0; i < CH + 1; i++) s[c.gl * (CH + 1) + i] = w[CH + i];
+    group_sync(c);
+    Mp<1> r;
+    uint32_t hi[1];
+    {
+        uint32_t cy = 0;
+        CF_UNROLL for (int j = 0; j < CH; j++) {
+            const uint32_t up = (c.gl >= 1) ? s[(c.gl >= 1 ? c.gl - 1 : 0) * (CH + 1) + j] : 0u;
+            const uint32_t ov = (j == 0 && c.gl >= 2) ? s[(c.gl >= 2 ? c.gl - 2 : 0) * (CH + 1) + CH] : 0u;
+            const uint64_t t = (uint64_t)w[j] + up + ov + cy;
+            r.v[0][j] = (uint32_t)t;
+            cy = (uint32_t)(t >> 32);
+        }
+        hi[0] = cy;
+    }
+    group_sync(c);
+    (void)mp_resolve_sparse(c, r, hi);
+    return r;
+}
+
 // ---------------------------------------------------------------------------- division
 // conservative floor(n / d) for d <= 2^32: never above the true quotient, at most 2 below
 CF_DEV uint64_t div64_lower(uint64_t n, uint64_t d) {

@@ -87,7 +87,7 @@ __global__ void __launch_bounds__(WG_BLOCK, COFHE_WPS) k_pow_dot(const uint32_t 
         } else {
             rhs = l_;
         }
-        qf_compose<true, false>(c, r, l_, rhs, dd);
+        qf_compose<true, false, false>(c, r, l_, rhs, dd);
         if (has) qf_store(c, r, accp);
     }
     if (alive && all_zero) {

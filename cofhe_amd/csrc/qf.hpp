@@ -253,12 +253,155 @@ CF_DEV SMp<2> nucomp_dot(Ctx &c, const Mp<1> &R, const SMp<1> &C, const SMp<1> &
     return r;
 }
 
+// ---- a' and b' in one plane ------------------------------------------------------------------------------------------------
+// After a partial sequence of some rounds R, C, M1 and M2 are all near the fourth root of |Delta|: half-plane numbers whose
+// products fit one plane.  With every operand at most 640 bits and
+//     bits(R) + bits(M1) <= 1277   and   bits(C) + bits(M2) <= 1277
+// both products are below 2^1277 and R M1 + C M2 is a signed value below 2^1278 in magnitude: the two products come from one
+// pass (mp_mul_half2) and the signed addition runs on one plane.  For b' = -+2 bs - b1 the doubled dot is below 2^1279, and
+// with bits(b1) <= 1279 the difference stays below 2^1280 in magnitude: b' is computed in the plane as well.  A partial
+// sequence of no rounds (R0 = v1, C0 = 0) has a full-plane R0 for discriminants of cryptographic size, fails the bound and
+// takes the double-width route, which is the complete one.  On this route the upper planes of a' and b' are zero by
+// construction; nothing tests them.
+#ifdef COFHE_DOT_FULL
+constexpr bool DOT_ONE_PLANE = false;      // A/B builds (tools/build_variant.sh): the double-width dots only
+#else
+constexpr bool DOT_ONE_PLANE = true;
+#endif
+constexpr int DOT1_PRODUCT_BITS = PLIMBS * 32 - 3;          // 1277
+CF_DEV bool dot_one_plane_serves(int bR, int bC, int bM1, int bM2) {
+    return bR <= LOW2_BITS && bC <= LOW2_BITS && bM1 <= LOW2_BITS && bM2 <= LOW2_BITS && bR + bM1 <= DOT1_PRODUCT_BITS &&
+           bC + bM2 <= DOT1_PRODUCT_BITS;
+}
+// R*M1 + C*M2 within the bound above
+CF_DEV SMp<1> nucomp_dot_half(Ctx &c, const Mp<1> &R, const SMp<1> &C, const SMp<1> &M1, const SMp<1> &M2) {
+    const MpPair pp = mp_mul_half2(c, R, M1.m, C.m, M2.m);
+    const SMp<1> p1{pp.p0, M1.neg}, p2{pp.p1, C.neg ^ M2.neg};
+    SMp<1> r;
+    smp_add(c, r, p1, p2);
+    return r;
+}
+
+// a' = R1 M1 + C1 M2 and b' = -sign(C1) 2 (R0 M1 + C0 M2) - b1 for M1, M2 of the pair (R1, C1).  Returns true
+// (wavefront-uniform) when both came from the one-plane route: the upper planes of an and bn are then zero.  That route is
+// taken only when m2_one_plane (nucomp_m12 returned true: M2 fits a plane) and every active group of the wavefront passes the
+// bound -- one scalar branch, as in nucomp_m12; the double-width dots serve everything.
+template <bool ONE_PLANE = true>
+CF_DEV bool nucomp_ab(Ctx &c, SMp<2> &an, SMp<2> &bn, const Mp<1> &R1, const SMp<1> &C1, const Mp<1> &R0, const SMp<1> &C0,
+                      const SMp<1> &M1, const SMp<2> &M2, const SMp<1> &b1, bool m2_one_plane) {
+    const int sg_neg = C1.neg;             // det(R0 C1 - R1 C0) has the sign of C1
+    if (ONE_PLANE && DOT_ONE_PLANE && CF_LIKELY(m2_one_plane)) {
+        const SMp<1> M2l{mp_resize<1>(M2.m), M2.neg};
+        const int bM1 = mp_bitlen(c, M1.m), bM2 = mp_bitlen(c, M2l.m);
+        const bool ok = dot_one_plane_serves(mp_bitlen(c, R1), mp_bitlen(c, C1.m), bM1, bM2) &&
+                        dot_one_plane_serves(mp_bitlen(c, R0), mp_bitlen(c, C0.m), bM1, bM2) &&
+                        mp_bitlen(c, b1.m) <= PLIMBS * 32 - 1;
+        if (CF_LIKELY(!any_lane(c, !ok))) {
+            const SMp<1> a1 = nucomp_dot_half(c, R1, C1, M1, M2l);
+            const SMp<1> bs = nucomp_dot_half(c, R0, C0, M1, M2l);
+            SMp<1> two_bs, bw;
+            (void)mp_add(c, two_bs.m, bs.m, bs.m);
+            two_bs.neg = bs.neg ^ (sg_neg ? 0 : 1);
+            smp_sub(c, bw, two_bs, b1);
+            an.m = mp_resize<2>(a1.m);
+            an.neg = a1.neg;
+            bn.m = mp_resize<2>(bw.m);
+            bn.neg = bw.neg;
+            return true;
+        }
+    }
+    an = nucomp_dot(c, R1, C1, M1, M2, m2_one_plane);
+    const SMp<2> bs = nucomp_dot(c, R0, C0, M1, M2, m2_one_plane);
+    SMp<2> two_bs;
+    (void)mp_add(c, two_bs.m, bs.m, bs.m);
+    two_bs.neg = bs.neg ^ (sg_neg ? 0 : 1);
+    const SMp<2> b1w{mp_resize<2>(b1.m), b1.neg};
+    smp_sub(c, bn, two_bs, b1w);
+    return false;
+}
+
 // ---------------------------------------------------------------------------- composition
 // Discriminant as the kernels see it: 80 little-endian words of |Delta| and its half bit length.
 struct QDisc {
     const uint32_t *absdelta;      // 2 planes, same limb order as Mp<2>
     int half_dbits;                // ceil(bits(|Delta|) / 2)
 };
+
+// ---- c' from the low half --------------------------------------------------------------------------------------------------
+// c' = (b'^2 + |Delta|) / (4 a') is exact and divided 2-adically, as M1 and M2 are above.  b'^2 + |Delta| < 2^(max + 1) with
+// max = max(2 bits(b'), bits|Delta|), the shift by two takes two bits off and a' >= 2^(bits(a') - 1), hence
+//     c' < 2^nbc,   nbc = max(2 bits(b'), bits|Delta|) - bits(a').
+// After the tz trailing zero bits of a' are shifted out of both operands, bits 0..nbc-1 of the quotient depend on the shifted
+// numerator modulo 2^nbc only, that is on (b'^2 + |Delta|) >> 2 modulo 2^(nbc + tz), that is on b'^2 + |Delta| modulo
+// 2^(nbc + 2 + tz).  So when   nbc + 2 + tz <= 1280   and   tz < 32   one plane of the numerator is enough: b'^2 modulo 2^1280
+// (mp_sqr_low: no second plane), plus plane 0 of |Delta| with the carry dropped, shifted by two, divided over one plane with
+// (nbc + 31) / 32 digits; the digits above bit nbc of the last limb come from bits the plane does not hold and are masked
+// off.  Random forms of a 2088-bit discriminant give nbc ~ 1046.
+#ifdef COFHE_C_FULL
+constexpr bool C_LOW_HALF = false;         // A/B builds (tools/build_variant.sh): c' from the double-width numerator only
+#else
+constexpr bool C_LOW_HALF = true;
+#endif
+CF_DEV int c_low_bound(int bb, int dbits, int ba) {
+    const int t = 2 * bb > dbits ? 2 * bb : dbits;
+    return t - ba;
+}
+CF_DEV bool c_low_serves(int nbc, uint32_t a_limb0) {
+    if (a_limb0 == 0 || nbc <= 0) return false;
+    return nbc + 2 + __builtin_ctz(a_limb0) <= PLIMBS * 32;
+}
+// bits(|Delta|) from its half bit length and one word of it
+CF_DEV int qdisc_bits(const QDisc &dd) {
+    const int top = 2 * dd.half_dbits - 1;                 // bits(|Delta|) is 2 half_dbits or one less: this bit decides
+    if (top < 0 || top >= 2 * PLIMBS * 32) return top < 0 ? 0 : 2 * PLIMBS * 32;      // never for a context's discriminant
+    return top + (int)((dd.absdelta[top >> 5] >> (top & 31)) & 1u);
+}
+// c' < 2^nbc of a one-plane a' > 0 and |b'| within c_low_serves
+CF_DEV Mp<1> nucomp_c_low(Ctx &c, const Mp<1> &aw, const Mp<1> &bw, const QDisc &dd, int nbc) {
+    Mp<1> num = mp_sqr_low(c, bw);
+    uint32_t hi[1];
+    {
+        uint32_t cy = 0;
+        CF_UNROLL for (int j = 0; j < CH; j++) {
+            const uint64_t t = (uint64_t)num.v[0][j] + dd.absdelta[c.gl * CH + j] + cy;
+            num.v[0][j] = (uint32_t)t;
+            cy = (uint32_t)(t >> 32);
+        }
+        hi[0] = cy;
+    }
+    (void)mp_resolve_sparse(c, num, hi);                    // what leaves the plane is dropped
+    num = mp_shr_small(c, num, 2);
+    Mp<1> q;
+    mp_divexact(c, num, aw, q, (nbc + 31) >> 5);
+    const int topl = nbc >> 5;
+    const uint32_t topmask = (1u << (nbc & 31)) - 1u;
+    CF_UNROLL for (int j = 0; j < CH; j++) {
+        const int l = c.gl * CH + j;
+        q.v[0][j] &= l < topl ? 0xFFFFFFFFu : (l == topl ? topmask : 0u);
+    }
+    return q;
+}
+// c' = (b'^2 + |Delta|) / (4 a') for one-plane a' > 0 and |b'|.  Returns true when it came from the low half, which is taken
+// only when every active group of the wavefront passes the bound (one scalar branch); the double-width numerator is the
+// complete route.
+template <bool ONE_PLANE = true>
+CF_DEV bool nucomp_c(Ctx &c, Mp<2> &cn, const Mp<1> &aw, const Mp<1> &bw, const QDisc &dd) {
+    if (ONE_PLANE && C_LOW_HALF) {
+        const int nbc = c_low_bound(mp_bitlen(c, bw), qdisc_bits(dd), mp_bitlen(c, aw));
+        const bool ok = c_low_serves(nbc, bcast_first(c, aw.v[0][0]));
+        if (CF_LIKELY(!any_lane(c, !ok))) {
+            cn = mp_resize<2>(nucomp_c_low(c, aw, bw, dd, nbc));
+            return true;
+        }
+    }
+    Mp<2> num = mp_mul(c, bw, bw), dl;
+    CF_UNROLL for (int p = 0; p < 2; p++)
+        CF_UNROLL for (int j = 0; j < CH; j++) dl.v[p][j] = dd.absdelta[p * PLIMBS + c.gl * CH + j];
+    (void)mp_add(c, num, num, dl);
+    num = mp_shr_small(c, num, 2);
+    mp_divexact(c, num, aw, cn, (mp_bitlen(c, num) - mp_bitlen(c, aw) + 1 + 31) / 32);              // exact: b'^2 - Delta == 4 a' c'
+    return false;
+}
 
 // The two big remainder sequences of a composition.  WG: 0 = inside the limb group (euclid_run), 1 = served by wavefront 0 of
 // the workgroup (euclid_run_wg: every thread of the workgroup must then reach both calls).  (A dedicated fifth serving
@@ -376,7 +519,12 @@ CF_DEV_COLD bool qf_word_factor_residue(Ctx &c, Mp<1> &r, Mp<1> &v1, Mp<1> &v2, 
 // there a round that waits for the general formula costs ~2 % on average and the inlined route's registers cost as much
 // or more (encrypt_tensor 128x128 8.0 -> 9.6 ms with the route in k_compose_pairs,
 // profiles/r03_b/ops_word_route_everywhere.jsonl).  The host simulator runs both.
-template <int WG = 0, bool WORD_ROUTE = true>
+// ONE_PLANE: a', b' from one-plane dots and c' from the low half (nucomp_ab, nucomp_c) where the bounds allow.  On in the
+// tensor-addition kernels only (k_compose_wg, k_compose_wg3, k_add_ct: -4.4 % of a 128x128 launch, 34 spills fewer).  Inlined
+// into every sequence kernel the routes made decryption, the ladders and the encryption trees 1-10 % slower and cost them
+// 50-160 more spilled values each (profiles/r16_one_plane/ops_ab_unrestricted.json), so those pass false and keep the
+// double-width tail.  The host simulator runs the routes (its default).
+template <int WG = 0, bool WORD_ROUTE = true, bool ONE_PLANE = true>
 CF_DEV void qf_compose(Ctx &c, QForm &out, const QForm &fa, const QForm &fb, const QDisc &dd) {
     const int half_dbits = dd.half_dbits;
     CF_PHASE(0);
@@ -596,34 +744,18 @@ CF_DEV void qf_compose(Ctx &c, QForm &out, const QForm &fa, const QForm &fb, con
     c.t_wait = 0; c.t_apply = 0; c.n_rounds = 0; c.t_serve = 0;
 #endif
     const SMp<1> C0{pe.ux, pe.sx < 0}, C1{pe.uy, pe.sy < 0};
-    const int sg_neg = C1.neg;             // det(R0 C1 - R1 C0) has the sign of C1
 
     SMp<1> M1;
     SMp<2> M2;
     const bool m2_one_plane = nucomp_m12(c, M1, M2, pe.y, C1, v1, v2, m, s, c2d, lv1, lv2, true);
-    SMp<2> an = nucomp_dot(c, pe.y, C1, M1, M2, m2_one_plane);
-    SMp<2> bs = nucomp_dot(c, pe.x, C0, M1, M2, m2_one_plane);
-    // b' = -sg * 2 * bs - b1
-    SMp<2> bn;
-    {
-        SMp<2> two_bs;
-        (void)mp_add(c, two_bs.m, bs.m, bs.m);
-        two_bs.neg = bs.neg ^ (sg_neg ? 0 : 1);
-        SMp<2> b1w{mp_resize<2>(b1.m), b1.neg};
-        smp_sub(c, bn, two_bs, b1w);
-    }
+    // a' and b' = -sg * 2 * bs - b1
+    SMp<2> an, bn;
+    const bool ab_one_plane = nucomp_ab<ONE_PLANE>(c, an, bn, pe.y, C1, pe.x, C0, M1, M2, b1, m2_one_plane);
     SMp<2> cn;
     CF_PHASE(5);
-    if (CF_LIKELY(mp_high_planes_zero(c, an.m, 1) && mp_high_planes_zero(c, bn.m, 1))) {
+    if (CF_LIKELY(ab_one_plane || (mp_high_planes_zero(c, an.m, 1) && mp_high_planes_zero(c, bn.m, 1)))) {
         // usual case (a', b' near sqrt|Delta|): c' = (b'^2 + |Delta|) / (4 a')
-        const Mp<1> bw = mp_resize<1>(bn.m);
-        Mp<2> num = mp_mul(c, bw, bw), dl;
-        CF_UNROLL for (int p = 0; p < 2; p++)
-            CF_UNROLL for (int j = 0; j < CH; j++) dl.v[p][j] = dd.absdelta[p * PLIMBS + c.gl * CH + j];
-        (void)mp_add(c, num, num, dl);
-        num = mp_shr_small(c, num, 2);
-        const Mp<1> aw = mp_resize<1>(an.m);
-        mp_divexact(c, num, aw, cn.m, (mp_bitlen(c, num) - mp_bitlen(c, aw) + 1 + 31) / 32);      // exact: b'^2 - Delta == 4 a' c'
+        (void)nucomp_c<ONE_PLANE>(c, cn.m, mp_resize<1>(an.m), mp_resize<1>(bn.m), dd);
         cn.neg = 0;
     } else {
         // a' or b' wider than a plane (tiny v1*v2, e.g. inverse pairs): c' from the other pair

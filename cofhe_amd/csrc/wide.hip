@@ -36,7 +36,7 @@ __device__ __forceinline__ void compose_wide_or_fallback(uint32_t *lds, WForm &o
         QForm a, b, r;
         qf_load(c, a, ra);
         qf_load(c, b, rb);
-        qf_compose<0, false>(c, r, a, b, dd);
+        qf_compose<0, false, false>(c, r, a, b, dd);
         qf_store(c, r, ro);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

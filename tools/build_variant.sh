@@ -4,7 +4,8 @@
 # source tree (e.g. an export of an earlier commit: git archive HEAD cofhe_amd/csrc include | tar -x -C /tmp/base_src;
 # SRC=/tmp/base_src); a tree from before the C ABI moved to abi.hip is built with that tree's own build().
 # Switches of the device headers: -DCOFHE_M12_FULL (qf.hpp: M1 and M2 from the full products only, the arithmetic of before
-# the low-half route: tools/build_variant.sh m12_full -DCOFHE_M12_FULL).
+# the low-half route: tools/build_variant.sh m12_full -DCOFHE_M12_FULL); -DCOFHE_DOT_FULL (a' and b' from the double-width
+# dots only), -DCOFHE_C_FULL (c' from the double-width numerator only).
 set -e
 cd "$(dirname "$0")/.."
 name=$1; shift
