@@ -153,6 +153,8 @@ CF_DEV uint32_t shfl_xor1(Ctx &c, uint32_t v) { return shfl(c, v, c.gl ^ 1); }
 CF_DEV uint32_t shfl_xor2(Ctx &c, uint32_t v) { return shfl(c, v, c.gl ^ 2); }
 CF_DEV uint32_t shfl_mirror(Ctx &c, uint32_t v) { return shfl(c, v, (G - 1) - c.gl); }   // lane i <- lane 7-i
 CF_DEV uint32_t shfl_down4(Ctx &c, uint32_t v) { return shfl(c, v, c.gl + G / 2); }     // lanes 0..3 <- lanes 4..7; lanes 4..7: unspecified
+CF_DEV uint32_t shfl_up4(Ctx &c, uint32_t v) { return shfl(c, v, c.gl + G / 2); }       // lanes 4..7 <- lanes 0..3; lanes 0..3: unspecified
+CF_DEV uint32_t bcast_half_first(Ctx &c, uint32_t v) { return shfl(c, v, c.gl & (G / 2)); }   // every lane <- lane 0 of its own half
 CF_DEV uint32_t bcast_first(Ctx &c, uint32_t v) { return shfl(c, v, 0); }
 CF_DEV uint32_t bcast_last(Ctx &c, uint32_t v) { return shfl(c, v, G - 1); }
 CF_DEV uint32_t ballot8(Ctx &c, bool p) {
@@ -238,6 +240,15 @@ CF_DEV uint32_t shfl_mirror(Ctx &, uint32_t v) {    // lane i <- lane G-1-i of i
 // their own value at the end of the row: unspecified, the callers ignore it
 CF_DEV uint32_t shfl_down4(Ctx &, uint32_t v) {
     return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x104, 0xF, 0xF, false);
+}
+// lanes 4..7 of the group <- lanes 0..3 (row_shr:4); what lanes 0..3 receive belongs to the previous group of the row, or is
+// their own value at the start of the row: unspecified, the callers ignore it
+CF_DEV uint32_t shfl_up4(Ctx &, uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x114, 0xF, 0xF, false);
+}
+// every lane <- lane 0 of its own half of the group (a half is a quad): quad_perm:[0,0,0,0]
+CF_DEV uint32_t bcast_half_first(Ctx &, uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x00, 0xF, 0xF, true);
 }
 // broadcast from the first / last lane of the group: two DPP moves (~6 issue cycles) instead of a
 // ds_bpermute (21-28 cycles measured, tools/inst_bench.hip): a quad broadcast, then the half-row mirror written only

@@ -647,6 +647,17 @@ CF_DEV MpPair mp_mul_half2(Ctx &c, const Mp<1> &x0, const Mp<1> &y0, const Mp<1>
 // leaves chunk 7 is dropped.  For the numerator of a 2-adic exact division whose quotient fits the plane (qf.hpp: nucomp_c_low).
 // Only the non-zero chunks of x are visited, as in mp_mul: the trip count is the group's, so a wavefront pays for the longest
 // of its groups.
+//
+// Round 7: every chunk pair once.  Output chunk gl is 2 * sum_{i < gl - i} x[i] x[gl - i], plus x[gl / 2]^2 when gl is even.
+// The (gl + 1) / 2 <= 4 off-diagonal terms go into the 11-word window first -- four products below 2^320 --, the window is
+// doubled (below 2^323), and the diagonal term is added after the doubling (below 2^324 of the window's 2^352): at most five
+// chunk products per lane where the plain sum above runs one per non-zero chunk of x (seven for the b' of the reference
+// parameters), with a fixed trip count.  -DCOFHE_SQR_FULL compiles the plain sum back (A/B builds, tools/build_variant.sh).
+#ifdef COFHE_SQR_FULL
+constexpr bool SQR_EACH_PAIR_ONCE = false;
+#else
+constexpr bool SQR_EACH_PAIR_ONCE = true;
+#endif
 CF_DEV Mp<1> mp_sqr_low(Ctx &c, const Mp<1> &x) {
     static_assert(PLIMBS + G <= SCRATCH_WORDS && G * (CH + 1) <= SCRATCH_WORDS, "scratch too small");
     CF_STAT(g_stats.muls += 1);
@@ -654,18 +665,44 @@ CF_DEV Mp<1> mp_sqr_low(Ctx &c, const Mp<1> &x) {
     CF_UNROLL for (int j = 0; j < CH; j++) s[c.gl * CH + j] = x.v[0][j];
     s[PLIMBS + c.gl] = 0u;                                  // the chunk of zeros (G >= CH words)
     group_sync(c);
-    const int kx = (mp_bitlen(c, x) + CH * 32 - 1) / (CH * 32);
     uint32_t w[2 * CH + 1];
     CF_UNROLL for (int i = 0; i < 2 * CH + 1; i++) w[i] = 0;
-    CF_NOUNROLL for (int k = 0; k < kx; k++) {
-        const uint32_t *px = s + ((c.gl - k) & (G - 1)) * CH;
-        const uint32_t *py = (k <= c.gl) ? s + k * CH : s + PLIMBS;
-        uint32_t xc[CH], yc[CH];
-        CF_UNROLL for (int j = 0; j < CH; j++) {
-            xc[j] = px[j];
-            yc[j] = py[j];
+    if constexpr (SQR_EACH_PAIR_ONCE) {
+        const int noff = (c.gl + 1) >> 1;
+        CF_NOUNROLL for (int k = 0; k < G / 2; k++) {
+            const uint32_t *px = s + ((c.gl - k) & (G - 1)) * CH;
+            const uint32_t *py = (k < noff) ? s + k * CH : s + PLIMBS;
+            uint32_t xc[CH], yc[CH];
+            CF_UNROLL for (int j = 0; j < CH; j++) {
+                xc[j] = px[j];
+                yc[j] = py[j];
+            }
+            chunk_mac(w, xc, yc);
         }
-        chunk_mac(w, xc, yc);
+        CF_UNROLL for (int i = 2 * CH; i > 0; i--) w[i] = (w[i] << 1) | (w[i - 1] >> 31);
+        w[0] <<= 1;
+        {
+            const uint32_t *px = s + (c.gl >> 1) * CH;
+            const uint32_t *py = (c.gl & 1) ? s + PLIMBS : px;
+            uint32_t xc[CH], yc[CH];
+            CF_UNROLL for (int j = 0; j < CH; j++) {
+                xc[j] = px[j];
+                yc[j] = py[j];
+            }
+            chunk_mac(w, xc, yc);
+        }
+    } else {
+        const int kx = (mp_bitlen(c, x) + CH * 32 - 1) / (CH * 32);
+        CF_NOUNROLL for (int k = 0; k < kx; k++) {
+            const uint32_t *px = s + ((c.gl - k) & (G - 1)) * CH;
+            const uint32_t *py = (k <= c.gl) ? s + k * CH : s + PLIMBS;
+            uint32_t xc[CH], yc[CH];
+            CF_UNROLL for (int j = 0; j < CH; j++) {
+                xc[j] = px[j];
+                yc[j] = py[j];
+            }
+            chunk_mac(w, xc, yc);
+        }
     }
     group_sync(c);
     CF_UNROLL for (int i = 0; i < CH + 1; i++) s[c.gl * (CH + 1) + i] = w[CH + i];
@@ -1115,9 +1152,22 @@ CF_DEV void mp_divrem(Ctx &c, Mp<PN> &num, const Mp<PD> &den, Mp<PN> &quot) {
 // limbs to produce (group-uniform upper bound on the length of the quotient).  ~70 issue slots per digit
 // against ~130 for the normalised long division.  A num that den does not divide gives a meaningless
 // quotient (never a hang: the trip count is fixed).
+//
+// A one-plane numerator (PN == 1) has no high limbs, and none are kept (round 7): the top lane shifts in zero, and the word
+// and the borrow that leave the plane are dropped.  Digit i of a 2-adic quotient depends on the numerator modulo
+// 2^(32 (i + 1)) only.  What leaves the plane in step j, or would enter it, has weight 2^1280 of the ORIGINAL numerator; after
+// step j it sits at limb 39 of the running value and moves down one limb per step, so with nq <= 40 it is never in limb 0
+// (or, for the second digit of a pair, limb 1) when a digit is taken there: all nq digits are those of num modulo 2^1280.
+// For an exact division with a quotient of nq limbs that is the quotient; the low callers (qf.hpp) ask for no more.
+#ifdef COFHE_DIVEXACT_HIGH
+constexpr bool DIVEXACT_HIGH_ALWAYS = true;    // A/B builds (tools/build_variant.sh): the high-limb bookkeeping for PN == 1 too
+#else
+constexpr bool DIVEXACT_HIGH_ALWAYS = false;
+#endif
 template <int PN, int PQ>
 CF_DEV void mp_divexact(Ctx &c, const Mp<PN> &num, const Mp<1> &den, Mp<PQ> &quot, int nq) {
     static_assert((PN + PQ) * PLIMBS <= SCRATCH_WORDS, "scratch too small");
+    constexpr bool HIGH = PN > 1 || DIVEXACT_HIGH_ALWAYS;
     mp_zero(quot);
     if (nq <= 0) return;
     if (nq > PQ * PLIMBS) nq = PQ * PLIMBS;
@@ -1135,8 +1185,10 @@ CF_DEV void mp_divexact(Ctx &c, const Mp<PN> &num, const Mp<1> &den, Mp<PQ> &quo
     uint32_t dinv = d0;                // d0 * d0 == 1 (mod 8); each Newton step doubles the valid bits
     CF_UNROLL for (int i = 0; i < 4; i++) dinv *= 2u - d0 * dinv;
     uint32_t *sn = c.scratch(), *sq = sn + PN * PLIMBS;
-    CF_UNROLL for (int p = 0; p < PN; p++)
-        CF_UNROLL for (int j = 0; j < CH; j++) sn[p * PLIMBS + c.gl * CH + j] = Nn.v[p][j];
+    if constexpr (HIGH) {
+        CF_UNROLL for (int p = 0; p < PN; p++)
+            CF_UNROLL for (int j = 0; j < CH; j++) sn[p * PLIMBS + c.gl * CH + j] = Nn.v[p][j];
+    }
     CF_UNROLL for (int p = 0; p < PQ; p++)
         CF_UNROLL for (int j = 0; j < CH; j++) sq[p * PLIMBS + c.gl * CH + j] = 0u;
     group_sync(c);
@@ -1164,8 +1216,11 @@ CF_DEV void mp_divexact(Ctx &c, const Mp<PN> &num, const Mp<1> &den, Mp<PQ> &quo
         // first digit: lane-local chains, then the neighbours' words (the top lane's goes into the high-limb bookkeeping)
         uint32_t r1[CH];
         const uint32_t hi1 = lincomb_plane<true>(r1, 1u, S.v[0], q0, D.v[0], c.gl == 0 ? q0 : 0u);
-        const int64_t v1 = (int64_t)high(i) + adj + (int64_t)bcast_last(c, hi1) - (int64_t)q0;
-        const int64_t adj1 = v1 >> 32;                                      // floor
+        int64_t v1 = 0, adj1 = 0;
+        if constexpr (HIGH) {
+            v1 = (int64_t)high(i) + adj + (int64_t)bcast_last(c, hi1) - (int64_t)q0;
+            adj1 = v1 >> 32;                                                // floor
+        }
         const uint32_t inc = shfl_up1(c, hi1, 0u);
         const uint32_t r0 = r1[0] + inc;
         const uint32_t bit = r0 < inc ? 1u : 0u;                            // belongs to limb 1 of this lane: limb 0 after the shift
@@ -1177,8 +1232,11 @@ CF_DEV void mp_divexact(Ctx &c, const Mp<PN> &num, const Mp<1> &den, Mp<PQ> &quo
         uint32_t hi2[1];
         hi2[0] = lincomb_plane<true>(T.v[0], 1u, s2, q1, D.v[0], c.gl == 0 ? q1 : bit);
         const uint32_t cw = mp_resolve(c, T, hi2);
-        const int64_t v2 = (int64_t)high(i + 1) + adj1 + (int64_t)cw - (int64_t)q1;
-        adj = v2 >> 32;
+        int64_t v2 = 0;
+        if constexpr (HIGH) {
+            v2 = (int64_t)high(i + 1) + adj1 + (int64_t)cw - (int64_t)q1;
+            adj = v2 >> 32;
+        }
         const uint32_t up = shfl_down1(c, T.v[0][0], (uint32_t)v2);
         CF_UNROLL for (int j = 0; j + 1 < CH; j++) S.v[0][j] = T.v[0][j + 1];
         S.v[0][CH - 1] = up;
@@ -1192,8 +1250,11 @@ CF_DEV void mp_divexact(Ctx &c, const Mp<PN> &num, const Mp<1> &den, Mp<PQ> &quo
         const uint32_t q = bcast_first(c, S.v[0][0]) * dinv;
         Mp<1> T;
         const uint32_t cw = mp_lincomb_sub_carry(c, T, 1u, S, q, D);      // S - q D == T + (cw - q) * 2^1280, T[0] == 0
-        const int64_t v = (int64_t)high(i) + adj + (int64_t)cw - (int64_t)q;
-        adj = v >> 32;                                                       // floor
+        int64_t v = 0;
+        if constexpr (HIGH) {
+            v = (int64_t)high(i) + adj + (int64_t)cw - (int64_t)q;
+            adj = v >> 32;                                                   // floor
+        }
         const uint32_t up = shfl_down1(c, T.v[0][0], (uint32_t)v);
         CF_UNROLL for (int j = 0; j + 1 < CH; j++) S.v[0][j] = T.v[0][j + 1];
         S.v[0][CH - 1] = up;
@@ -1203,6 +1264,139 @@ CF_DEV void mp_divexact(Ctx &c, const Mp<PN> &num, const Mp<1> &den, Mp<PQ> &quo
     CF_UNROLL for (int p = 0; p < PQ; p++)
         CF_UNROLL for (int j = 0; j < CH; j++) quot.v[p][j] = sq[p * PLIMBS + c.gl * CH + j];
     group_sync(c);
+}
+
+// ---- two half-plane values side by side (round 7) --------------------------------------------------------------------------
+// A "pair" is one Mp<1> that holds a value modulo 2^640 in lanes 0..3 and another in lanes 4..7, each in its half's own chunk
+// order (what mp_mul_low2 returns).  Nothing passes from lane 3 to lane 4.
+
+// mp_resolve for a pair: hi is the word each lane hands to the next chunk OF ITS HALF; what leaves chunk 3 of a half is
+// dropped.  The single bits that remain are resolved from the two ballots as in mp_resolve, with the chain cut between bit 3
+// and bit 4: lane 3's generate bit is taken out of the carry-in mask and its propagate bit out of the propagate mask.  (That
+// is enough: a carry out of position 3 of pm + y would then need y3 and a carry into position 3 together, and y3 -- lane 2
+// generates -- means lane 2 does not propagate, so a carry into position 3 would need lane 1 to generate and a carry into
+// position 2, and so on down to position 0, which nothing enters.)
+CF_DEV void mp_resolve_pair(Ctx &c, Mp<1> &r, uint32_t hi) {
+    CF_STAT(g_stats.resolves += 1);
+    const bool first = (c.gl & (LOW2_CHUNKS - 1)) == 0;
+    const uint32_t got = shfl_up1(c, hi, 0u);
+    const uint32_t inc = first ? 0u : got;
+    uint64_t t = (uint64_t)r.v[0][0] + inc;
+    r.v[0][0] = (uint32_t)t;
+    uint32_t cy = (uint32_t)(t >> 32);
+    uint32_t all = r.v[0][0];
+    CF_UNROLL for (int j = 1; j < CH; j++) {
+        t = (uint64_t)r.v[0][j] + cy;
+        r.v[0][j] = (uint32_t)t;
+        cy = (uint32_t)(t >> 32);
+        all &= r.v[0][j];
+    }
+    const uint32_t cut = 1u << (LOW2_CHUNKS - 1);
+    const uint32_t gm = ballot8(c, cy != 0) & ~cut;
+    const uint32_t pm = ballot8(c, all == 0xFFFFFFFFu && cy == 0) & ~cut;
+    const uint32_t y = gm << 1;
+    const uint32_t cin = y | (((pm + y) ^ pm) ^ y);
+    uint32_t mine = (cin >> c.gl) & 1u;
+    {
+        const uint32_t s0 = r.v[0][0] + mine;
+        mine = (s0 < mine) ? 1u : 0u;
+        r.v[0][0] = s0;
+    }
+    if (CF_UNLIKELY(any_lane(c, mine != 0))) {
+        CF_UNROLL for (int j = 1; j < CH; j++) {
+            const uint32_t s = r.v[0][j] + mine;
+            mine = (s < mine) ? 1u : 0u;
+            r.v[0][j] = s;
+        }
+    }
+}
+
+// x >> n for 0 <= n < 32 in both halves of a pair: the top limb of each half takes zeros
+CF_DEV Mp<1> mp_shr_small_pair(Ctx &c, const Mp<1> &x, int n) {
+    Mp<1> y;
+    const uint32_t ls = (uint32_t)(32 - n) & 31u;
+    const uint32_t keep = n ? 0xFFFFFFFFu : 0u;
+    const uint32_t got = shfl_down1(c, x.v[0][0], 0u);
+    const uint32_t nxt = (c.gl & (LOW2_CHUNKS - 1)) == LOW2_CHUNKS - 1 ? 0u : got;
+    CF_UNROLL for (int j = 0; j < CH; j++) {
+        const uint32_t up = (j + 1 < CH) ? x.v[0][j + 1 < CH ? j + 1 : 0] : nxt;
+        y.v[0][j] = (x.v[0][j] >> n) | ((up << ls) & keep);
+    }
+    return y;
+}
+
+// Two 2-adic divisions by the same divisor in one pass of the Hensel loop of mp_divexact: num is a pair (n0 | n1), and limbs
+// 0..nq-1 of each half of the result are the nq low limbs of (n_h >> tz) / (den >> tz) modulo 2^(32 nq), tz < 32 the trailing
+// zero bits of den (limb 0 of den must not be zero); the limbs from nq on are zero.  nq <= 20 digits (group-uniform; the
+// caller passes the larger of its two digit counts and masks each half to its own length).  For the quotients of exact
+// divisions that are known to fit a half plane (qf.hpp: nucomp_m12).
+//
+// The divisor (den >> tz) modulo 2^640 is copied into lanes 4..7, every half takes its digit pair from its own two lowest
+// limbs (broadcast inside the quad), the lane-local chains of lincomb_plane are those of mp_divexact, and the limb shift
+// and the carry resolve stay inside each half.  There is no high-limb bookkeeping: what leaves a half is dropped and its top
+// lane shifts in zero, by the argument at mp_divexact with 2^640 for 2^1280 and nq <= 20.  Bits 640 - tz and above of a
+// shifted half are not the numerator's (they are zeros here), so only the low 640 - tz bits of each quotient mean anything.
+CF_DEV Mp<1> mp_divexact_pair(Ctx &c, const Mp<1> &num, const Mp<1> &den, int nq) {
+    constexpr int H = LOW2_CHUNKS, HL = H * CH;
+    static_assert(G == 8 && PLIMBS <= SCRATCH_WORDS, "scratch too small");
+    Mp<1> quot;
+    mp_zero(quot);
+    if (nq <= 0) return quot;
+    if (nq > HL) nq = HL;
+    const int oc = c.gl & (H - 1);
+    const bool low = c.gl < H;
+    const uint32_t d0raw = bcast_first(c, den.v[0][0]);
+    const int tz = __builtin_ctz(d0raw | 0x80000000u);                  // limb 0 of zero is the caller's to exclude
+    const Mp<1> Df = mp_shr_small(c, den, tz);                          // lane 3's top limb takes its bits from lane 4: den's own
+    Mp<1> D;
+    CF_UNROLL for (int j = 0; j < CH; j++) {
+        const uint32_t upper = shfl_up4(c, Df.v[0][j]);
+        D.v[0][j] = low ? Df.v[0][j] : upper;
+    }
+    Mp<1> S = mp_shr_small_pair(c, num, tz);
+    const uint32_t d0 = bcast_first(c, D.v[0][0]);
+    uint32_t dinv = d0;                // d0 * d0 == 1 (mod 8); each Newton step doubles the valid bits
+    CF_UNROLL for (int i = 0; i < 4; i++) dinv *= 2u - d0 * dinv;
+    const uint64_t d64 = ((uint64_t)bcast_first(c, D.v[0][1]) << 32) | d0;
+    uint64_t dinv64 = dinv;
+    dinv64 *= 2ull - d64 * dinv64;                                          // 32 -> 64 valid bits
+    uint32_t *sq = c.scratch() + (low ? 0 : HL);                            // this half's digits
+    int i = 0;
+    for (; i + 1 < nq; i += 2) {
+        CF_STAT(g_stats.divsteps += 2);
+        const uint64_t s01 = ((uint64_t)bcast_half_first(c, S.v[0][1]) << 32) | bcast_half_first(c, S.v[0][0]);
+        const uint64_t q = s01 * dinv64;
+        const uint32_t q0 = (uint32_t)q, q1 = (uint32_t)(q >> 32);
+        uint32_t r1[CH];
+        const uint32_t hi1 = lincomb_plane<true>(r1, 1u, S.v[0], q0, D.v[0], oc == 0 ? q0 : 0u);
+        const uint32_t got = shfl_up1(c, hi1, 0u);
+        const uint32_t inc = oc == 0 ? 0u : got;
+        const uint32_t r0 = r1[0] + inc;
+        const uint32_t bit = r0 < inc ? 1u : 0u;                            // belongs to limb 1 of this lane: limb 0 after the shift
+        uint32_t s2[CH];
+        const uint32_t dn = shfl_down1(c, r0, 0u);
+        s2[CH - 1] = oc == H - 1 ? 0u : dn;                                 // the limb shift; the top lane of a half takes zero
+        CF_UNROLL for (int j = 0; j + 1 < CH; j++) s2[j] = r1[j + 1];
+        Mp<1> T;
+        const uint32_t hi2 = lincomb_plane<true>(T.v[0], 1u, s2, q1, D.v[0], oc == 0 ? q1 : bit);
+        mp_resolve_pair(c, T, hi2);
+        const uint32_t dn2 = shfl_down1(c, T.v[0][0], 0u);
+        CF_UNROLL for (int j = 0; j + 1 < CH; j++) S.v[0][j] = T.v[0][j + 1];
+        S.v[0][CH - 1] = oc == H - 1 ? 0u : dn2;
+        if (oc == 0) {
+            sq[i] = q0;
+            sq[i + 1] = q1;
+        }
+    }
+    if (i < nq) {                                                           // an odd last digit: nothing is left to update
+        CF_STAT(g_stats.divsteps++);
+        const uint32_t q = bcast_half_first(c, S.v[0][0]) * dinv;
+        if (oc == 0) sq[i] = q;
+    }
+    group_sync(c);
+    CF_UNROLL for (int j = 0; j < CH; j++) quot.v[0][j] = (oc * CH + j < nq) ? sq[oc * CH + j] : 0u;
+    group_sync(c);
+    return quot;
 }
 
 // ---------------------------------------------------------------------------- signed helpers

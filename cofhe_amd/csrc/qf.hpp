@@ -190,16 +190,81 @@ CF_DEV SMp<1> m12_low_quot(Ctx &c, const Mp<1> &pp, bool sub, int neg0, const Mp
     return r;
 }
 
+// Both quotients from one paired division (round 7).  pa and pb are pairs (mp.hpp) of low products: lanes 0..3 hold the two
+// terms of M1's numerator, lanes 4..7 those of M2's, so one lane-wise wrap-around addition gives both numerators modulo 2^640
+// -- the complement mask and the +1 chosen per half, nothing crossing from lane 3 to lane 4 --, mp_divexact_pair divides both
+// by v1 in one pass of the digit loop with the larger of the two digit counts, and one epilogue masks each half to its own
+// nb + 1 bits, takes its sign from its own bit nb and negates its magnitude.  sub0 / sub1: the half's second term is
+// subtracted; nb0 / nb1: |quotient| < 2^nb of the half (below zero: that quotient is zero, whatever the other is).  Returns
+// |M1| in lanes 0..3 and |M2| in lanes 4..7; neg0 / neg1 are set when the quotient as computed (first term taken positive)
+// is negative.
+struct M12Pair {
+    Mp<1> m;
+    int neg0, neg1;
+};
+CF_DEV M12Pair m12_low_quot_pair(Ctx &c, const Mp<1> &pa, const Mp<1> &pb, bool sub0, bool sub1, const Mp<1> &v1, int nb0, int nb1) {
+    const bool low = c.gl < LOW2_CHUNKS;
+    const bool first = (c.gl & (LOW2_CHUNKS - 1)) == 0;
+    const bool sub = low ? sub0 : sub1;
+    const int nb = low ? nb0 : nb1;
+    const uint32_t flip = sub ? 0xFFFFFFFFu : 0u;
+    Mp<1> n;
+    {
+        uint32_t cy = (sub && first) ? 1u : 0u;                  // two's complement: -B == ~B + 1 over the 640 bits of the half
+        CF_UNROLL for (int j = 0; j < CH; j++) {
+            const uint64_t t = (uint64_t)pa.v[0][j] + (pb.v[0][j] ^ flip) + cy;
+            n.v[0][j] = (uint32_t)t;
+            cy = (uint32_t)(t >> 32);
+        }
+        mp_resolve_pair(c, n, cy);
+    }
+    const int nbmax = nb0 > nb1 ? nb0 : nb1;
+    const Mp<1> q = mp_divexact_pair(c, n, v1, nbmax < 0 ? 0 : (nbmax + 32) >> 5);
+    // keep bits 0..nb of the half; bit nb is the sign; a negative value is negated into its magnitude: (~q & mask) + 1
+    const int topl = nb < 0 ? -1 : nb >> 5;                      // nb < 0: every limb of the half is masked away
+    const uint32_t topmask = (2u << (nb & 31)) - 1u;             // nb & 31 == 31: 2u << 31 == 0, all ones
+    const int base = (c.gl & (LOW2_CHUNKS - 1)) * CH;
+    uint32_t sbit = 0;
+    CF_UNROLL for (int j = 0; j < CH; j++) sbit |= (base + j == topl) ? (q.v[0][j] >> (nb & 31)) & 1u : 0u;
+    const uint32_t sb = ballot8(c, sbit != 0);
+    M12Pair r;
+    r.neg0 = (sb & ((1u << LOW2_CHUNKS) - 1u)) != 0 ? 1 : 0;
+    r.neg1 = (sb >> LOW2_CHUNKS) != 0 ? 1 : 0;
+    const bool neg = (low ? r.neg0 : r.neg1) != 0;
+    const uint32_t inv = neg ? 0xFFFFFFFFu : 0u;
+    {
+        uint32_t cy = (neg && first) ? 1u : 0u;
+        CF_UNROLL for (int j = 0; j < CH; j++) {
+            const int l = base + j;
+            const uint32_t mask = l < topl ? 0xFFFFFFFFu : (l == topl ? topmask : 0u);
+            const uint64_t t = (uint64_t)((q.v[0][j] ^ inv) & mask) + cy;
+            r.m.v[0][j] = (uint32_t)t;
+            cy = (uint32_t)(t >> 32);
+        }
+        mp_resolve_pair(c, r.m, cy);
+    }
+    return r;
+}
+
 #ifdef COFHE_M12_FULL
 constexpr bool M12_LOW_HALF = false;       // A/B builds (tools/build_variant.sh): the full products only
 #else
 constexpr bool M12_LOW_HALF = true;
 #endif
+#ifdef COFHE_M12_SINGLE_DIV
+constexpr bool M12_PAIRED_DIV = false;     // A/B builds: the low-half route with one division per quotient, as in round 5
+#else
+constexpr bool M12_PAIRED_DIV = true;
+#endif
 
 // M1 = (v2 R - m C)/v1, M2 = (s R + c2d C)/v1 for one remainder/cofactor pair; lv1, lv2 = bits(v1), bits(v2).  Returns true
 // when both came from low-half products -- M2 then fits one plane (its upper plane is zero).  That route is taken only when
 // try_low and every active group of the wavefront passes the bound (one scalar branch; the full products are the complete
-// route and serve everything).
+// route and serve everything).  PAIRED: both quotients of the low route from one paired division (m12_low_quot_pair); without
+// it one division each, as in round 5.  Like ONE_PLANE (qf_compose) it is on in the tensor-addition kernels only: compiled
+// into every sequence kernel it made the ladders 0.7-1.1 % and the encryption trees 2-3 % slower, more than their two-run
+// spread (profiles/r17_paired_div/ops_ab_unrestricted.json).
+template <bool PAIRED = true>
 CF_DEV bool nucomp_m12(Ctx &c, SMp<1> &M1, SMp<2> &M2, const Mp<1> &R, const SMp<1> &C, const Mp<1> &v1,
                        const Mp<1> &v2, const SMp<1> &m, const SMp<1> &s, const Mp<2> &c2d, int lv1, int lv2, bool try_low) {
     if (M12_LOW_HALF && try_low) {
@@ -209,6 +274,22 @@ CF_DEV bool nucomp_m12(Ctx &c, SMp<1> &M1, SMp<2> &M2, const Mp<1> &R, const SMp
         const uint32_t v1w = bcast_first(c, v1.v[0][0]);
         const bool ok = m12_low_half_serves(nb1, v1w) && m12_low_half_serves(nb2, v1w);
         if (CF_LIKELY(!any_lane(c, !ok))) {
+            if constexpr (PAIRED && M12_PAIRED_DIV) {
+                const Mp<1> pr = mp_mul_low2(c, v2, R, s.m, R);                         // v2 R | s R
+                const Mp<1> pc = mp_mul_low2(c, m.m, C.m, mp_resize<1>(c2d), C.m);      // m C | c2d C
+                // v2 R - m C in lanes 0..3, sign(s) (|s| R +- c2d |C|) in lanes 4..7
+                const M12Pair qq = m12_low_quot_pair(c, pr, pc, m.neg == C.neg, s.neg != C.neg, v1, nb1, nb2);
+                const bool lowh = c.gl < LOW2_CHUNKS;
+                CF_UNROLL for (int j = 0; j < CH; j++) {
+                    const uint32_t down = shfl_down4(c, qq.m.v[0][j]);
+                    M1.m.v[0][j] = lowh ? qq.m.v[0][j] : 0u;
+                    M2.m.v[0][j] = lowh ? down : 0u;
+                    M2.m.v[1][j] = 0u;
+                }
+                M1.neg = qq.neg0;
+                M2.neg = s.neg ^ qq.neg1;
+                return true;
+            }
             const Mp<1> pa = mp_mul_low2(c, v2, R, m.m, C.m);
             M1 = m12_low_quot(c, pa, m.neg == C.neg, 0, v1, nb1);                  // v2 R - m C
             const Mp<1> pb = mp_mul_low2(c, s.m, R, mp_resize<1>(c2d), C.m);
@@ -747,7 +828,7 @@ CF_DEV void qf_compose(Ctx &c, QForm &out, const QForm &fa, const QForm &fb, con
 
     SMp<1> M1;
     SMp<2> M2;
-    const bool m2_one_plane = nucomp_m12(c, M1, M2, pe.y, C1, v1, v2, m, s, c2d, lv1, lv2, true);
+    const bool m2_one_plane = nucomp_m12<ONE_PLANE>(c, M1, M2, pe.y, C1, v1, v2, m, s, c2d, lv1, lv2, true);
     // a' and b' = -sg * 2 * bs - b1
     SMp<2> an, bn;
     const bool ab_one_plane = nucomp_ab<ONE_PLANE>(c, an, bn, pe.y, C1, pe.x, C0, M1, M2, b1, m2_one_plane);

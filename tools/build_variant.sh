@@ -5,7 +5,10 @@
 # SRC=/tmp/base_src); a tree from before the C ABI moved to abi.hip is built with that tree's own build().
 # Switches of the device headers: -DCOFHE_M12_FULL (qf.hpp: M1 and M2 from the full products only, the arithmetic of before
 # the low-half route: tools/build_variant.sh m12_full -DCOFHE_M12_FULL); -DCOFHE_DOT_FULL (a' and b' from the double-width
-# dots only), -DCOFHE_C_FULL (c' from the double-width numerator only).
+# dots only), -DCOFHE_C_FULL (c' from the double-width numerator only).  Each part of round 7 back to the code before it:
+# -DCOFHE_M12_SINGLE_DIV (qf.hpp: the low-half route of M1 and M2 with one division per quotient instead of the paired one),
+# -DCOFHE_DIVEXACT_HIGH (mp.hpp: mp_divexact keeps the high-limb bookkeeping for a one-plane numerator too),
+# -DCOFHE_SQR_FULL (mp.hpp: mp_sqr_low multiplies every chunk pair twice, one chunk product per non-zero chunk).
 set -e
 cd "$(dirname "$0")/.."
 name=$1; shift
