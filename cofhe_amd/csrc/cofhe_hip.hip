@@ -41,12 +41,14 @@ __device__ __forceinline__ Ctx make_ctx(uint32_t *lds) {
 // are served by its wavefront 0 (mp.hpp: euclid_run_wg).  Groups beyond n recompute
 // the last item and skip the store, so every thread reaches every barrier.
 // One composition per limb group (tensor addition).  Two builds of the same body: k_compose_wg leaves room for four
-// workgroups per CU (128 registers per lane, 268 of the function's values spilled; 266 before M1 and M2 came from low-half
+// workgroups per CU (128 registers per lane, 288 of the function's values spilled; 266 before M1 and M2 came from low-half
 // products, 305 with them, qf.hpp: that second route cost registers and 38 KB of code and still saved 3.4 % of the launch,
 // profiles/r05_low_half/; the one-plane a', b' and the low-half c' gave 34 of them back, cost 23 KB more and saved another
 // 4.4 %, profiles/r16_one_plane/; M1 and M2 from one paired division, mp_divexact without high limbs over one plane and the
 // square from every chunk pair once left the spills where they were, 271 -> 268, and the code 18 KB smaller: the launch
-// figures of both builds are in profiles/r17_paired_div/) -- the form for grids of many residency
+// figures of both builds are in profiles/r17_paired_div/; r = y1 m mod a1 from the remainder-only division, mp.hpp:
+// mp_rem_norm, took 268 -> 288 with the scratch frame 308 -> 316 bytes and the code 0.6 KB larger, k_add_ct 357 -> 339, the
+// three-per-CU builds unchanged; the launch figures of both builds are in profiles/r18_rem_norm/) -- the form for grids of many residency
 // rounds and for the 1024 workgroups of a 128x128 launch, which fill the chip exactly once; k_compose_wg3 asks for three
 // (168 registers, 131 spills; 98 before the paired division) and is 6-9 % faster per workgroup, which pays whenever the whole grid is resident at three per
 // CU anyway: launches of up to 768 workgroups, 24 576 compositions (64x64: 0.255 -> 0.239 ms, 110x111: 0.316 -> 0.288 ms;

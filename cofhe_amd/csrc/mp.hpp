@@ -21,7 +21,7 @@
 namespace cofhe {
 
 #if defined(COFHE_HOSTSIM)
-struct SimStats { long batches, batch_steps, divsteps, muls, divrems, resolves, bits_gained; };
+struct SimStats { long batches, batch_steps, divsteps, muls, divrems, resolves, bits_gained, rem_steps, rem_addbacks, rem_fallbacks; };
 inline SimStats g_stats;
 #define CF_STAT(x) do { if (c.gl == 0) { x; } } while (0)
 #else
@@ -327,6 +327,36 @@ CF_DEV uint32_t mp_lincomb_sub_carry(Ctx &c, Mp<P> &r, uint32_t A, const Mp<P> &
     CF_UNROLL for (int p = 0; p < P; p++)
         hi[p] = lincomb_plane<true>(r.v[p], A, x.v[p], B, y.v[p], (p == 0 && c.gl == 0) ? B : 0u);
     return mp_resolve(c, r, hi);
+}
+
+// The same for a difference whose RESULT is known to be an ordinary non-negative number below 2^(1280 P) -- the digit step of
+// mp_rem_norm, 0 <= S - q D < D -- resolved like a sum.  1*S + q*~D + q is a sum of non-negative terms, so mp_resolve_sparse
+// is exact for it whatever the limbs are: it adds the neighbour's word into limb 0 and one carry into limb 1, and hands the
+// whole plane to mp_resolve when some lane's limb 1 is all ones before that hand-over.  What decides is how often that is.  In
+// the Euclid differences it is the rule (the cancelled high limbs are all ones by construction).  Here every lane's chunk
+// ends as a chunk of the remainder T: a limb 1 that is all ones beforehand needs either a limb 1 of T that is zero together
+// with a limb 0 of T below the word that came in (the carry went through), or a limb 1 of T that is all ones and no carry:
+// about 2^-32 each per lane for random limbs of a remainder, 2^-28 per step over the eight lanes.  Two ways in are not rare.
+// A digit estimate one too large (about 2^-17 per digit): S - q D is then negative, its high limbs are all ones, the general
+// resolve runs, and the add-back follows.  And the zero limbs under the shifted operands: D = den << s and the staged
+// numerator have s / 32 zero limbs at the bottom, so in the last steps lane g >= 1 holds zeros in its limbs 0 and 1 (step k,
+// k + 5 g + 1 < s / 32), takes the word q from below and meets the first case.  For a divisor of 1044 bits (s / 32 == 7) that is
+// the last step alone, one general resolve in 33 digits; a divisor of a few words takes it on most of its steps and is no
+// worse off than before.  So the common digit pays ~7 instructions for its carries instead of ~37.
+template <int P>
+CF_DEV uint32_t mp_lincomb_sub_carry_sparse(Ctx &c, Mp<P> &r, uint32_t A, const Mp<P> &x, uint32_t B, const Mp<P> &y) {
+    uint32_t hi[P];
+    CF_UNROLL for (int p = 0; p < P; p++)
+        hi[p] = lincomb_plane<true>(r.v[p], A, x.v[p], B, y.v[p], (p == 0 && c.gl == 0) ? B : 0u);
+#if defined(COFHE_HOSTSIM)
+    {                                       // the simulator counts the steps that take the general resolve (tests/test_remnorm_cpu.py)
+        uint32_t ones = 0;
+        CF_UNROLL for (int p = 0; p < P; p++) ones |= (r.v[p][1] == 0xFFFFFFFFu) ? 1u : 0u;
+        const bool fb = any_lane(c, ones != 0);
+        CF_STAT(g_stats.rem_fallbacks += fb ? 1 : 0);
+    }
+#endif
+    return mp_resolve_sparse(c, r, hi);
 }
 
 template <int P>
@@ -1067,6 +1097,79 @@ CF_DEV void mp_divrem_norm(Ctx &c, Mp<PN> &num, const Mp<1> &den, int db, Mp<PN>
     CF_UNROLL for (int p = 0; p < PN; p++)
         CF_UNROLL for (int j = 0; j < CH; j++) quot.v[p][j] = sq[p * PLIMBS + c.gl * CH + j];
     group_sync(c);
+    const Mp<1> R = s ? mp_shr(c, S, s) : S;
+    num = mp_resize<PN>(R);
+}
+
+// num <- num mod den, nothing else: the division above for a caller that throws the quotient away (qf.hpp: smod).  Same digit
+// estimate, same add-back, same trip count, same early return and final shift; what a digit no longer pays for:
+//   - the quotient: no second LDS region, no zeroing, no store per digit, no reload;
+//   - the numerator limb: num << s is constant over the loop, so it is staged shifted, once -- the bit shift in registers
+//     (PN planes and one word), the limb shift as the store address above sw zero words -- and a digit reads sn[k - 1] with one
+//     load, no range selects and no funnel shift (the top limb K of num << s is at most 40 PN + sw: inside the staged words);
+//   - the generate / propagate resolve: the difference is resolved like a sum (mp_lincomb_sub_carry_sparse, where the
+//     argument stands).
+#ifdef COFHE_REM_QUOT
+constexpr bool REM_NORM = false;           // A/B builds (tools/build_variant.sh): smod through mp_divrem, as before round 8
+#else
+constexpr bool REM_NORM = true;
+#endif
+template <int PN>
+CF_DEV void mp_rem_norm(Ctx &c, Mp<PN> &num, const Mp<1> &den, int db) {
+    static_assert(PN * PLIMBS + 1 + (PLIMBS - 1) <= SCRATCH_WORDS, "scratch too small");
+    const int nb = mp_bitlen(c, num);
+    if (nb < db) return;
+    const int s = PLIMBS * 32 - db;
+    const Mp<1> D = s ? mp_shl(c, den, s) : den;
+    const uint32_t d39 = bcast_last(c, D.v[0][CH - 1]), d38 = bcast_last(c, D.v[0][CH - 2]);
+    const double rd = 1.0 / ((double)d39 * 4294967296.0 + (double)d38);
+    uint32_t *sn = c.scratch();
+    const int sw = s >> 5, sb = s & 31;                         // sw <= 38: db >= 33
+    {
+        const uint32_t rs = (uint32_t)(32 - sb) & 31u, keep = sb ? 0xFFFFFFFFu : 0u;
+        uint32_t below = 0;                                     // the limb under lane 0 of the plane
+        CF_UNROLL for (int j = 0; j < CH; j++)
+            if (c.gl * CH + j < sw) sn[c.gl * CH + j] = 0u;
+        CF_UNROLL for (int p = 0; p < PN; p++) {
+            const uint32_t prv = shfl_up1(c, num.v[p][CH - 1], below);
+            CF_UNROLL for (int j = 0; j < CH; j++) {
+                const uint32_t lo = j ? num.v[p][j ? j - 1 : 0] : prv;
+                sn[sw + p * PLIMBS + c.gl * CH + j] = (num.v[p][j] << sb) | ((lo >> rs) & keep);
+            }
+            if (p + 1 < PN) below = bcast_last(c, num.v[p][CH - 1]);
+        }
+        if (c.gl == G - 1) sn[sw + PN * PLIMBS] = (num.v[PN - 1][CH - 1] >> rs) & keep;
+    }
+    group_sync(c);
+    const int K = (nb + s - 1) >> 5;              // top limb of num << s  (K >= 39 because nb >= db)
+    Mp<1> S;
+    CF_UNROLL for (int j = 0; j < CH; j++) S.v[0][j] = sn[K - (PLIMBS - 1) + c.gl * CH + j];
+    uint32_t top = 0;
+    for (int k = K - (PLIMBS - 1);; k--) {
+        CF_STAT(g_stats.divsteps++);
+        CF_STAT(g_stats.rem_steps++);
+        const uint32_t l39 = bcast_last(c, S.v[0][CH - 1]), l38 = bcast_last(c, S.v[0][CH - 2]);
+        double x = (((double)top * 4294967296.0 + (double)l39) * 4294967296.0 + (double)l38) * rd;
+        x += x * 1.7763568394002505e-15;          // (1 + 2^-49): never below the true digit
+        uint64_t qd = (uint64_t)x;
+        if (qd > 0xFFFFFFFFull) qd = 0xFFFFFFFFull;
+        if (CF_LIKELY(qd != 0)) {
+            Mp<1> T;
+            const uint32_t cw = mp_lincomb_sub_carry_sparse(c, T, 1u, S, (uint32_t)qd, D);
+            int64_t nt = (int64_t)top + (int64_t)cw - (int64_t)qd;   // top word of S - q D: 0, or -1 if q is one too large
+            S = T;
+            for (int fix = 0; CF_UNLIKELY(nt < 0) && fix < 4; fix++) {       // the estimate is at most one too large
+                CF_FLAG(8u);
+                CF_STAT(g_stats.rem_addbacks++);
+                nt += (int64_t)mp_add(c, S, S, D);
+            }
+        }
+        if (k == 0) break;
+        top = bcast_last(c, S.v[0][CH - 1]);
+        const uint32_t up = shfl_up1(c, S.v[0][CH - 1], sn[k - 1]);
+        CF_UNROLL for (int j = CH - 1; j >= 1; j--) S.v[0][j] = S.v[0][j - 1];
+        S.v[0][0] = up;
+    }
     const Mp<1> R = s ? mp_shr(c, S, s) : S;
     num = mp_resize<PN>(R);
 }

@@ -94,11 +94,28 @@ CF_DEV void qf_reduce(Ctx &c, Mp<P> &a, SMp<P> &b, Mp<P> &cc) {
 }
 
 // ---------------------------------------------------------------------------- helpers
-// |t| mod v as a residue in [0, v) of the signed value t
-template <int P>
+// |t| mod v as a residue in [0, v) of the signed value t.  REM_ONLY (with two planes and a divisor beyond one word): the
+// remainder alone from mp_rem_norm, no quotient computed; a zero divisor or one of a single word goes the way of mp_divrem.
+template <bool REM_ONLY = false, int P>
 CF_DEV Mp<1> smod(Ctx &c, const SMp<P> &t, const Mp<1> &v) {
-    Mp<P> rem = t.m, q;
-    mp_divrem(c, rem, v, q);
+    Mp<P> rem = t.m;
+    if constexpr (REM_ONLY && REM_NORM && P == 2) {
+        const int db = mp_bitlen(c, v);
+        CF_STAT(g_stats.divrems++);
+        if (CF_LIKELY(db > 32)) {
+            mp_rem_norm(c, rem, v, db);
+        } else if (db == 0) {                                    // as mp_divrem: flagged, the numerator stays
+            CF_STATUS(c, CF_ST_DIV_CAP);
+        } else {                                                 // the word path of mp_divrem
+            const WordDiv d = worddiv_make(mp_get_limb(c, v, 0));
+            Mp<P> q = rem;
+            const uint32_t w = mp_divrem_word(c, q, d);
+            mp_set_word(c, rem, w);
+        }
+    } else {
+        Mp<P> q;
+        mp_divrem(c, rem, v, q);
+    }
     Mp<1> r = mp_resize<1>(rem);
     if (t.neg && !mp_is_zero(c, r)) {
         Mp<1> u;
@@ -604,7 +621,8 @@ CF_DEV_COLD bool qf_word_factor_residue(Ctx &c, Mp<1> &r, Mp<1> &v1, Mp<1> &v2, 
 // tensor-addition kernels only (k_compose_wg, k_compose_wg3, k_add_ct: -4.4 % of a 128x128 launch, 34 spills fewer).  Inlined
 // into every sequence kernel the routes made decryption, the ladders and the encryption trees 1-10 % slower and cost them
 // 50-160 more spilled values each (profiles/r16_one_plane/ops_ab_unrestricted.json), so those pass false and keep the
-// double-width tail.  The host simulator runs the routes (its default).
+// double-width tail.  The host simulator runs the routes (its default).  Round 8 put r = y1 m mod a1 under the same flag: the
+// remainder alone (smod<true>: mp_rem_norm) in the tensor-addition kernels, mp_divrem with its quotient in the others.
 template <int WG = 0, bool WORD_ROUTE = true, bool ONE_PLANE = true>
 CF_DEV void qf_compose(Ctx &c, QForm &out, const QForm &fa, const QForm &fb, const QDisc &dd) {
     const int half_dbits = dd.half_dbits;
@@ -706,7 +724,7 @@ CF_DEV void qf_compose(Ctx &c, QForm &out, const QForm &fa, const QForm &fb, con
     const SMp<1> y1{e.ux, e.sx < 0};
     {
         SMp<2> t = smp_mul(c, y1, m);
-        r = smod(c, t, v1);
+        r = smod<ONE_PLANE>(c, t, v1);             // the remainder alone in the tensor-addition kernels (round 8)
     }
     bool general = false;
     if (CF_UNLIKELY(!mp_is_word(c, e.x, 1))) {

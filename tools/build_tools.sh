@@ -9,7 +9,11 @@ mkdir -p build
 H=/opt/rocm/bin/hipcc
 $H --offload-arch=gfx950 -O3 -std=c++17 -o build/traffic_calib tools/traffic_calib.hip &
 $H --offload-arch=gfx950 -O2 -std=c++17 -o build/inst_bench tools/inst_bench.hip &
-$H --offload-arch=gfx950 -O2 -std=c++17 -Wno-unused-value $WG_TIMING_FLAGS -o build/wg_timing tools/wg_timing.hip cofhe_amd/csrc/abi.hip cofhe_amd/csrc/wire.hip cofhe_amd/csrc/wide.hip &
+# wg_timing.hip compiles the kernels of cofhe_hip.hip itself (with the stamps) and takes every other translation unit of the
+# library from the objects of the last build (python __graft_entry__.py): abi.hip refers to the kernels of all of them
+OBJ=${OBJ:-cofhe_amd/csrc/obj}
+($H --offload-arch=gfx950 -O2 -std=c++17 -fPIC -Wno-unused-value $WG_TIMING_FLAGS -c tools/wg_timing.hip -o build/wg_timing.o &&
+ $H --offload-arch=gfx950 -fPIC -o build/wg_timing build/wg_timing.o $(ls $OBJ/*.o | grep -v '/part[0-9]\.o$') -ldl) &
 wait
 ls -la build/wg_timing build/traffic_calib build/inst_bench
 # the static instruction mix of the built objects x the measured issue costs (tools/gpu_counters.sh takes these when present:

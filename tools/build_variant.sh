@@ -9,6 +9,8 @@
 # -DCOFHE_M12_SINGLE_DIV (qf.hpp: the low-half route of M1 and M2 with one division per quotient instead of the paired one),
 # -DCOFHE_DIVEXACT_HIGH (mp.hpp: mp_divexact keeps the high-limb bookkeeping for a one-plane numerator too),
 # -DCOFHE_SQR_FULL (mp.hpp: mp_sqr_low multiplies every chunk pair twice, one chunk product per non-zero chunk).
+# Round 8 back to the code before it: -DCOFHE_REM_QUOT (mp.hpp: r = y1 m mod a1 through mp_divrem with its quotient instead of
+# mp_rem_norm: tools/build_variant.sh rem_quot -DCOFHE_REM_QUOT).
 set -e
 cd "$(dirname "$0")/.."
 name=$1; shift
