@@ -1,10 +1,10 @@
 // abi.hip -- the C ABI of include/cofhe_hip.h, in this order: the context, the block cache, the launch helpers (spans, the
 // two-build launch, flag words, the table-cache lookup), the workspace plans, the launchers (one launch site per kernel and
 // route; product_tree is the pairwise tree of them all) and the host-side tensor formats.  The kernels are declared in
-// kernels.hpp and defined in cofhe_hip.hip, wide.hip, comb.hip, affine.hip, matmul_left.hip, conv.hip, pow_dot.hip, divide.hip and
-// lut.hip; this file holds no device code of its own.  conv.hip holds the three kernels of the convolution, pow_dot.hip the two of
+// kernels.hpp and defined in cofhe_hip.hip, wide.hip, comb.hip, affine.hip, matmul_left.hip, conv.hip, pow_dot.hip, divide.hip,
+// lut.hip and spline.hip; this file holds no device code of its own.  conv.hip holds the three kernels of the convolution, pow_dot.hip the two of
 // the polynomial evaluation, divide.hip the signed floor division of the division by public divisors, lut.hip the two copies of
-// the table lookups.
+// the table lookups, spline.hip the three kernels of the piecewise-polynomial activations.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -23,6 +23,7 @@
 #include "poly_shift.hpp"
 #include "plain_div.hpp"
 #include "lut.hpp"
+#include "spline.hpp"
 
 using namespace cofhe;
 using namespace cofhe_k;
@@ -1849,6 +1850,126 @@ int cofhe_hip_lut_tuples_shape_bits(uint32_t ndim_e, const uint32_t *shape_e, ui
     if (ndim_e > 7 || ndim_t != ndim_e + 1 || (ndim_e && memcmp(shape_t, shape_e, 4 * ndim_e) != 0) || b == 0 || b > LUT_MAX_BITS)
         return fail(COFHE_HIP_ESHAPE, "lut_select: the tuples are a ciphertext tensor of e's shape and a last dimension of 2^bits, 1 <= bits <= 12");
     *bits = b;
+    return COFHE_HIP_OK;
+}
+
+// ---- piecewise-polynomial activations from one opened value (spline.hip) ---------------------------------------------------
+static_assert(COFHE_HIP_SPLINE_MAX_TUPLE == SPLINE_MAX_TUPLE, "the header's bound is the kernels'");
+namespace {
+// what every spline entry point refuses before it looks at a pointer: the window, the degree, the tuple size, and element i
+// reading table i mod n_tab
+int spline_check(uint32_t bits, uint32_t shift, uint32_t d, uint32_t kbits, uint64_t n_tab, uint64_t n) {
+    if (kbits == 0 || kbits > 32u * PMM_MAX_LIMBS - 1u) return fail(COFHE_HIP_EINVAL, "k out of range");
+    if (!spline_shape_ok(bits, shift, d, kbits))
+        return fail(COFHE_HIP_EINVAL, "spline: 2^bits pieces of degree d, bits >= 1, 1 <= d <= 8, 2^bits (d + 1) <= 4096, shift + bits <= k");
+    if (n_tab == 0 || n % n_tab != 0) return fail(COFHE_HIP_EINVAL, "spline: the element count is a multiple of the table count, which is not 0");
+    if (n > (1ull << 36) / SPLINE_MAX_TUPLE) return fail(COFHE_HIP_EINVAL, "spline: too many items");
+    return COFHE_HIP_OK;
+}
+}  // namespace
+// touches no shared state of the context: no lock
+int cofhe_hip_spline_rows_records(cofhe_hip_ctx *ctx, const void *d_pieces, uint64_t n_tab, const void *d_r, void *d_out, uint64_t n, uint32_t bits,
+                                  uint32_t shift, uint32_t d, uint32_t kbits, void *stream) {
+    if (int rc = spline_check(bits, shift, d, kbits, n_tab, n)) return rc;
+    if (n == 0) return COFHE_HIP_OK;
+    if (!d_pieces || !d_r || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
+    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4, row_bytes = (size_t)(d + 1) * exp_bytes, out_bytes = (n << bits) * row_bytes;
+    if (overlaps(d_out, out_bytes, d_pieces, (n_tab << bits) * row_bytes) || overlaps(d_out, out_bytes, d_r, n * exp_bytes))
+        return fail(COFHE_HIP_EINVAL, "spline_rows: the output overlaps an input");
+    const uint64_t blocks = ((n << bits) + SPL_THREADS - 1) / SPL_THREADS;
+    if (blocks > 0x7FFFFFFFull) return fail(COFHE_HIP_EINVAL, "work size out of range");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    {
+        ProfScope ps(ctx, "k_spline_rows", st);
+        hipLaunchKernelGGL(k_spline_rows, dim3((unsigned)blocks), dim3(SPL_THREADS), 0, st, (const uint32_t *)d_pieces, n_tab, (const uint32_t *)d_r,
+                           (uint32_t *)d_out, n, bits, shift, d, kbits);
+    }
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+
+// Needs no workspace plan of its own: the rows are one block of the block cache, and the fresh encryption that follows carves
+// the workspace by the plan "comb" (kind 1) over n 2^bits (d + 1) plaintexts.
+int cofhe_hip_spline_tuples_records(cofhe_hip_ctx *ctx, const void *d_pieces, uint64_t n_tab, const void *d_r, const void *d_rho,
+                                    const uint32_t *h_record, const uint32_t *pk_record, const uint32_t *f_record, void *d_out, uint64_t n,
+                                    uint32_t bits, uint32_t shift, uint32_t d, uint32_t kbits, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (int rc = spline_check(bits, shift, d, kbits, n_tab, n)) return rc;
+    const uint64_t per = (uint64_t)(d + 1) << bits;
+    if (int rc = comb_check(1, n * per, 0, kbits, 0, 0)) return rc;
+    if (n == 0) return COFHE_HIP_OK;
+    if (!d_pieces || !d_r || !d_rho || !h_record || !pk_record || !f_record || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
+    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4, rows_bytes = n * per * exp_bytes, out_bytes = n * per * 2 * REC_WORDS * 4;
+    if (overlaps(d_out, out_bytes, d_pieces, n_tab * per * exp_bytes) || overlaps(d_out, out_bytes, d_r, n * exp_bytes) ||
+        overlaps(d_out, out_bytes, d_rho, rows_bytes))
+        return fail(COFHE_HIP_EINVAL, "spline_tuples: the output overlaps an input");
+    DevBuf rows;                                  // q_{j,c}: the plaintexts of the tuples
+    rows.stream = stream;
+    if (int rc = rows.get(ctx, rows_bytes)) return rc;
+    if (int rc = cofhe_hip_spline_rows_records(ctx, d_pieces, n_tab, d_r, rows.p, n, bits, shift, d, kbits, stream)) return rc;
+    return cofhe_hip_encrypt_fresh_records(ctx, rows.p, d_rho, h_record, pk_record, f_record, d_out, n * per, kbits, stream);
+}
+
+// touches no shared state of the context: no lock
+int cofhe_hip_spline_powers_records(cofhe_hip_ctx *ctx, const void *d_e, void *d_out, uint64_t n, uint32_t d, uint32_t kbits, void *stream) {
+    if (int rc = spline_check(1, 0, d, kbits, 1, n)) return rc;
+    if (n == 0) return COFHE_HIP_OK;
+    if (!d_e || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
+    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4;
+    if (overlaps(d_out, (size_t)d * n * exp_bytes, d_e, n * exp_bytes)) return fail(COFHE_HIP_EINVAL, "spline_powers: the output overlaps the input");
+    const uint64_t blocks = (n + SPL_THREADS - 1) / SPL_THREADS;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    {
+        ProfScope ps(ctx, "k_spline_powers", st);
+        hipLaunchKernelGGL(k_spline_powers, dim3((unsigned)blocks), dim3(SPL_THREADS), 0, st, (const uint32_t *)d_e, (uint32_t *)d_out, n, d, kbits);
+    }
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+
+// the powers of the opened values are one block of the block cache; the status word is set by the kernel through Ctx
+int cofhe_hip_spline_close_records(cofhe_hip_ctx *ctx, const void *d_e, const void *d_tuples, void *d_out, uint64_t n, uint32_t bits,
+                                   uint32_t shift, uint32_t d, uint32_t kbits, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (int rc = spline_check(bits, shift, d, kbits, 1, n)) return rc;
+    if (n == 0) return COFHE_HIP_OK;
+    if (!d_e || !d_tuples || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
+    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4, ct_bytes = (size_t)2 * REC_WORDS * 4, out_bytes = n * ct_bytes;
+    if (overlaps(d_out, out_bytes, d_e, n * exp_bytes) || overlaps(d_out, out_bytes, d_tuples, (((uint64_t)(d + 1) * n) << bits) * ct_bytes))
+        return fail(COFHE_HIP_EINVAL, "spline_close: the output overlaps an input");
+    unsigned blocks;
+    if (int rc = compose_blocks(2 * n, &blocks)) return rc;
+    DevBuf powers;                                // e, e^2, .., e^d mod 2^k, power-major
+    powers.stream = stream;
+    if (int rc = powers.get(ctx, (size_t)d * n * exp_bytes)) return rc;
+    if (int rc = cofhe_hip_spline_powers_records(ctx, d_e, powers.p, n, d, kbits, stream)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    {
+        ProfScope ps(ctx, "k_spline_close", st);
+        hipLaunchKernelGGL(k_spline_close, dim3(blocks), dim3(WG_BLOCK), 0, st, (const uint32_t *)d_e, (const uint32_t *)powers.p,
+                           (const uint32_t *)d_tuples, (uint32_t *)d_out, n, bits, shift, d, kbits, (const uint32_t *)ctx->d_absdelta,
+                           ctx->half_dbits, ctx->d_status);
+    }
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+
+// host only: the tuples of opened values of shape S are a tensor of shape S + [2^bits, d + 1]
+int cofhe_hip_spline_tuples_shape(uint32_t ndim_e, const uint32_t *shape_e, uint32_t ndim_t, const uint32_t *shape_t, uint32_t *bits, uint32_t *d) {
+    if (!bits || !d || (ndim_e && !shape_e) || (ndim_t && !shape_t)) return fail(COFHE_HIP_EINVAL, "null argument");
+    uint32_t b = 0, dd = 0;
+    if (ndim_t >= 2) {
+        while (b <= 12u && (1u << b) != shape_t[ndim_t - 2]) b++;
+        dd = shape_t[ndim_t - 1] - 1u;                           // 0 entries: wraps to a degree that is refused
+    }
+    if (ndim_e > 6 || ndim_t != ndim_e + 2 || (ndim_e && memcmp(shape_t, shape_e, 4 * ndim_e) != 0) || b == 0 || b > 12u || dd == 0 ||
+        dd > (uint32_t)POLY_MAX_DEGREE || ((uint64_t)(dd + 1) << b) > SPLINE_MAX_TUPLE)
+        return fail(COFHE_HIP_ESHAPE, "spline_close: the tuples are a ciphertext tensor of e's shape and two last dimensions [2^bits, d + 1], "
+                                      "bits >= 1, 1 <= d <= 8, 2^bits (d + 1) <= 4096");
+    *bits = b;
+    *d = dd;
     return COFHE_HIP_OK;
 }
 

@@ -5,7 +5,8 @@
 // affine.hip the ciphertext difference and the record inverse, matmul_left.hip the record transpose and the plaintext
 // matrix product, conv.hip the convolution's level 0, its patch gather and its filter expansion, pow_dot.hip the multi-exponentiation
 // and the Taylor shift of the polynomial evaluation, divide.hip the signed floor division on exponent records, lut.hip the row
-// rotation and the entry selection of the table lookups.
+// rotation and the entry selection of the table lookups, spline.hip the rows, the powers and the closing walk of the
+// piecewise-polynomial activations.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -167,4 +168,16 @@ __global__ void k_lut_rotate(const uint32_t *__restrict__ table, uint64_t n_tab,
                              uint64_t n, uint32_t bits, uint32_t vec16);
 __global__ void k_lut_select(const uint32_t *__restrict__ e, const uint32_t *__restrict__ tuples, uint32_t *__restrict__ out, uint64_t n,
                              uint32_t bits, uint32_t vec16);
+
+// piecewise-polynomial activations from one opened value (spline.hip; spline.hpp): the plaintext rows out[(i 2^bits + j) (d + 1) + c]
+// = coefficient c of the Taylor shift of piece (j + rho_i) mod 2^bits of table i mod n_tab at r_i minus the piece's origin, rho_i =
+// bits shift .. shift + bits - 1 of r_i (one thread per element and row); the powers out[(c - 1) n + i] = e[i]^c mod 2^kbits, c = 1
+// .. d (one thread per element); and the closing walk out[i] = q_0 o prod_c q_c^powers[(c - 1) n + i] over row j(e[i]) of the
+// element's tuple, read in place (one limb group per output record, the walk of k_pow_dot)
+__global__ void k_spline_rows(const uint32_t *__restrict__ pieces, uint64_t n_tab, const uint32_t *__restrict__ r, uint32_t *__restrict__ out,
+                              uint64_t n, uint32_t bits, uint32_t shift, uint32_t d, uint32_t kbits);
+__global__ void k_spline_powers(const uint32_t *__restrict__ e, uint32_t *__restrict__ out, uint64_t n, uint32_t d, uint32_t kbits);
+__global__ void k_spline_close(const uint32_t *__restrict__ e, const uint32_t *__restrict__ powers, const uint32_t *__restrict__ tuples,
+                               uint32_t *__restrict__ out, uint64_t n, uint32_t bits, uint32_t shift, uint32_t d, uint32_t kbits,
+                               const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status);
 }  // namespace cofhe_k

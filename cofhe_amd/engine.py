@@ -175,6 +175,42 @@ class Engine:
             for p in held:
                 self.free(p)
 
+    def spline_close_tensors_bytes(self, e: bytes, tuples: bytes, shift: int, kbits: int) -> bytes:
+        """e (plaintext tensor of the opened values x - r, shape S, at most 6 dimensions) and tuples (ciphertext tensor of the spline
+        tuples' entries, shape S + [2^bits, d + 1]) -> the ciphertext tensor of the spline's values, shape S; shift: the segment-width
+        bits of the table.  Composed here from unpack_tensor_device (which validates the incoming forms), spline_tuples_shape
+        (COFHE_HIP_ESHAPE when the tuples' shape is anything else), spline_close_records and pack_tensor_device, exactly as
+        lut_select_tensors_bytes is: the library has no entry point of its own for it."""
+        held = []
+
+        def load(t, kind):
+            # every integer owns an 8-byte table entry: the record count is bounded by the length
+            cap = (len(t) // 8) // (3 if kind else 1) + 1
+            raw = self.malloc(len(t) + 4)
+            held.append(raw)
+            recs = self.malloc(cap * 4 * (REC_WORDS if kind else EXP_REC_WORDS))
+            held.append(recs)
+            self.upload(raw, t)
+            shape, n = self.unpack_tensor_device(raw, len(t), kind, recs, cap)
+            return recs, shape, n
+
+        try:
+            de, se, ne = load(e, 0)
+            dt, st, nt = load(tuples, 2)
+            bits, d = self.spline_tuples_shape(se, st)
+            assert nt == 2 * (ne << bits) * (d + 1)                   # the counts are the shapes' products
+            dout = self.malloc(max(ne, 1) * 2 * REC_WORDS * 4)
+            held.append(dout)
+            self.spline_close_records(de, dt, dout, ne, bits, shift, d, kbits)
+            cap = self.packed_size_bound(2 * ne, 2, len(se))
+            packed = self.malloc(cap)
+            held.append(packed)
+            ln = self.pack_tensor_device(dout, 2 * ne, 2, se, packed, cap)
+            return self.download(packed, ln, dtype="uint8").tobytes()
+        finally:
+            for p in held:
+                self.free(p)
+
     def scal_ciphertext_tensors(self, s: bytes, cts: bytes, zero: bytes = None) -> bytes:
         out = C.POINTER(C.c_uint8)()
         n = C.c_size_t()
@@ -465,6 +501,45 @@ class Engine:
         exponent records of the opened values x - r; d_out must not overlap an input"""
         _chk(self.L.cofhe_hip_lut_select_records(self.ctx, C.c_void_p(d_e), C.c_void_p(d_tuples), C.c_void_p(d_out), C.c_uint64(n),
                                                  C.c_uint32(bits), C.c_void_p(stream)))
+
+    def spline_rows_records(self, d_pieces, n_tab, d_r, d_out, n, bits, shift, d, kbits, stream=0):
+        """the plaintext rows of n spline tuples on exponent records: out[(i 2^bits + j) (d + 1) + c] = coefficient c of the Taylor
+        shift of piece (j + rho_i) mod 2^bits of table i mod n_tab at r_i minus the piece's origin, rho_i = bits shift .. shift + bits
+        - 1 of r_i mod 2^kbits (pieces: n_tab 2^bits (d + 1), r: n, out: n 2^bits (d + 1)); d_out must not overlap an input"""
+        _chk(self.L.cofhe_hip_spline_rows_records(self.ctx, C.c_void_p(d_pieces), C.c_uint64(n_tab), C.c_void_p(d_r), C.c_void_p(d_out),
+                                                  C.c_uint64(n), C.c_uint32(bits), C.c_uint32(shift), C.c_uint32(d), C.c_uint32(kbits),
+                                                  C.c_void_p(stream)))
+
+    def spline_tuples_records(self, d_pieces, n_tab, d_r, d_rho, h_record, pk_record, f_record, d_out, n, bits, shift, d, kbits, stream=0):
+        """the entries of n spline tuples: spline_rows_records, then encrypt_fresh_records over the n 2^bits (d + 1) rows with the
+        randomness rho (as many exponent records, each used once); h_record, pk_record, f_record: host uint32[168]; d_out:
+        n 2^bits (d + 1) ciphertexts"""
+        import numpy as np
+        recs = [np.ascontiguousarray(r, dtype=np.uint32) for r in (h_record, pk_record, f_record)]
+        assert all(r.size == 168 for r in recs)
+        _chk(self.L.cofhe_hip_spline_tuples_records(self.ctx, C.c_void_p(d_pieces), C.c_uint64(n_tab), C.c_void_p(d_r), C.c_void_p(d_rho),
+                                                    *[r.ctypes.data_as(C.POINTER(C.c_uint32)) for r in recs], C.c_void_p(d_out), C.c_uint64(n),
+                                                    C.c_uint32(bits), C.c_uint32(shift), C.c_uint32(d), C.c_uint32(kbits), C.c_void_p(stream)))
+
+    def spline_tuples_shape(self, shape_e, shape_t):
+        """host only: (bits, d) of the tuples (shape_t = shape_e + [2^bits, d + 1]) that go with opened values of shape_e;
+        COFHE_HIP_ESHAPE otherwise"""
+        bits, d = C.c_uint32(), C.c_uint32()
+        _chk(self.L.cofhe_hip_spline_tuples_shape(C.c_uint32(len(shape_e)), (C.c_uint32 * max(len(shape_e), 1))(*shape_e), C.c_uint32(len(shape_t)),
+                                                  (C.c_uint32 * max(len(shape_t), 1))(*shape_t), C.byref(bits), C.byref(d)))
+        return bits.value, d.value
+
+    def spline_powers_records(self, d_e, d_out, n, d, kbits, stream=0):
+        """out[(c - 1) n + i] = e[i]^c mod 2^kbits, c = 1 .. d, on exponent records (e: n, out: d n, power-major)"""
+        _chk(self.L.cofhe_hip_spline_powers_records(self.ctx, C.c_void_p(d_e), C.c_void_p(d_out), C.c_uint64(n), C.c_uint32(d),
+                                                    C.c_uint32(kbits), C.c_void_p(stream)))
+
+    def spline_close_records(self, d_e, d_tuples, d_out, n, bits, shift, d, kbits, stream=0):
+        """the closing step of a spline: out[i] = [q_{j,0}] o prod_{c=1..d} [q_{j,c}]^(e[i]^c mod 2^kbits) over row j = bits shift ..
+        shift + bits - 1 of e[i] of element i's tuple; e: n exponent records of the opened values x - r, tuples: n 2^bits (d + 1)
+        ciphertexts; d_out must not overlap an input"""
+        _chk(self.L.cofhe_hip_spline_close_records(self.ctx, C.c_void_p(d_e), C.c_void_p(d_tuples), C.c_void_p(d_out), C.c_uint64(n),
+                                                   C.c_uint32(bits), C.c_uint32(shift), C.c_uint32(d), C.c_uint32(kbits), C.c_void_p(stream)))
 
     def decrypt_records(self, d_cts, d_sk, f_record, d_out, n_ciphertexts, kbits, stream=0):
         """f_record: host numpy uint32[168]; d_out: n * (ceil(k/32) + 1) words"""

@@ -971,6 +971,69 @@ class HIPCryptoSystem {
         return out;
     }
 
+    // ---- piecewise-polynomial activations from one opened value (cofhe_hip_spline_*; include/cofhe_hip.h states the protocol
+    // and the caller's contract; spline_table.hpp builds tables) ----
+    // the degree d and the table count of a spline table for n elements: `table` is [2^bits, d + 1] (one table) or [n_tab, 2^bits,
+    // d + 1] (element i takes table i mod n_tab, n a multiple of n_tab); bits >= 1, 1 <= d <= 8, 2^bits (d + 1) <= 4096,
+    // shift + bits <= k
+    struct SplineShape {
+        uint32_t d;
+        size_t n_tab;
+    };
+    SplineShape spline_table_shape(const Tensor<PlainText *> &table, size_t n, uint32_t bits, uint32_t shift) const {
+        if (table.is_zero_degree() || table.ndim() < 2 || table.ndim() > 3) throw std::invalid_argument("spline table: [2^bits, d + 1] or [n_tab, 2^bits, d + 1]");
+        const size_t pieces = table.shape()[table.ndim() - 2], coefs = table.shape().back();
+        if (bits == 0 || bits > 12 || pieces != (size_t)1 << bits || coefs < 2 || coefs > COFHE_HIP_POLY_MAX_DEGREE + 1 ||
+            (coefs << bits) > COFHE_HIP_SPLINE_MAX_TUPLE || (size_t)shift + bits > k_)
+            throw std::invalid_argument("spline table: 2^bits pieces of d + 1 coefficients, bits >= 1, 1 <= d <= 8, 2^bits (d + 1) <= 4096, shift + bits <= k");
+        const size_t n_tab = table.ndim() == 3 ? table.shape()[0] : 1;
+        if (n_tab == 0 || n % n_tab != 0) throw std::invalid_argument("spline tables: their count must divide the element count");
+        return SplineShape{(uint32_t)coefs - 1, n_tab};
+    }
+    // the plaintext rows of the spline tuples: res[i, j, .] = the Taylor shift of piece (j + rho_i) mod 2^bits at r[i] minus the
+    // piece's origin, a tensor [n, 2^bits, d + 1] for the n masks r (cofhe_hip_spline_rows_records, k_spline_rows)
+    Tensor<PlainText *> spline_rows_plaintext_tensor(const Tensor<PlainText *> &table, const Tensor<PlainText *> &r, uint32_t bits, uint32_t shift) const {
+        const size_t n = r.num_elements();
+        const SplineShape s = spline_table_shape(table, n, bits, shift);
+        const size_t per = (size_t)(s.d + 1) << bits;
+        Staged dt = stage(pack_exponents(table)), dr = stage(pack_exponents(r)), drows = device_buffer(n * per * EXPW * 4);
+        check(cofhe_hip_spline_rows_records(ctx_, dt.ptr, s.n_tab, dr.ptr, drows.ptr, n, bits, shift, s.d, k_, nullptr));
+        return read_plaintexts(drows.ptr, n * per, EXPW, {n, (size_t)1 << bits, (size_t)s.d + 1}, true);
+    }
+    // the entries of the spline tuples: FRESH encryptions of those rows, a tensor [n, 2^bits, d + 1]
+    // (cofhe_hip_spline_tuples_records: the rows and the fresh-randomness comb, on the device from end to end).  Every entry has
+    // its own randomness WHATEVER the randomness mode: under a shared r the tuple would give the rotation away.
+    Tensor<CipherText *> spline_tuples_ciphertext_tensor(const PublicKey &pk, const Tensor<PlainText *> &table, const Tensor<PlainText *> &r,
+                                                         uint32_t bits, uint32_t shift) const {
+        const size_t n = r.num_elements();
+        const SplineShape s = spline_table_shape(table, n, bits, shift);
+        const size_t per = (size_t)(s.d + 1) << bits;
+        Staged dt = stage(pack_exponents(table)), dr = stage(pack_exponents(r)), drho = stage(draw_randomness(n * per));
+        const std::array<uint32_t, REC> pkrec = record_of(pk);
+        DeviceTensor out = alloc(std::vector<size_t>{n, (size_t)1 << bits, (size_t)s.d + 1}, n * per);
+        check(cofhe_hip_spline_tuples_records(ctx_, dt.ptr, s.n_tab, dr.ptr, drho.ptr, h_rec_.data(), pkrec.data(), f_rec_.data(), out.ptr_, n, bits,
+                                              shift, s.d, k_, nullptr));
+        return download(std::move(out));
+    }
+    // the closing step of a spline: res[i] = [q_{j,0}] o prod_c [q_{j,c}]^(e[i]^c), j the segment of e[i], of e's shape, for the
+    // opened values e = x - r and the tuple entries [n, 2^bits, d + 1] of the masks r (cofhe_hip_spline_close_records).  Its
+    // randomness is the tuple entries' own, so it gets no re-randomisation pass in any mode.
+    Tensor<CipherText *> spline_close_ciphertext_tensor(const Tensor<PlainText *> &e, const Tensor<CipherText *> &tuples, uint32_t bits,
+                                                        uint32_t shift) const {
+        return download(spline_close_ciphertext_tensor(e, upload(tuples), bits, shift));
+    }
+    // the same on resident tuples
+    DeviceTensor spline_close_ciphertext_tensor(const Tensor<PlainText *> &e, const DeviceTensor &tuples, uint32_t bits, uint32_t shift) const {
+        const size_t E = e.num_elements();
+        if (E == 0 || bits == 0 || bits > 12 || tuples.n_ % (E << bits) != 0 || tuples.n_ / (E << bits) < 2)
+            throw std::invalid_argument("spline tuples: 2^bits rows of d + 1 entries for every opened value");
+        const uint32_t d = (uint32_t)(tuples.n_ / (E << bits)) - 1;
+        Staged de = stage(pack_exponents(e));
+        DeviceTensor out = alloc(shape_of(e), E);
+        check(cofhe_hip_spline_close_records(ctx_, de.ptr, tuples.ptr_, out.ptr_, E, bits, shift, d, k_, nullptr));
+        return out;
+    }
+
     // ---- device-resident variants -------------------------------------------------------------
     // the block behind a tensor whose elements are, in order, ALL the elements of one device block (the result of
     // a previous operation handed back unchanged); nullptr otherwise

@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -30,6 +31,7 @@
 
 #include "hip_cryptosystem.hpp"
 #include "smpc_local.hpp"
+#include "spline_table.hpp"
 
 using namespace CoFHE;
 
@@ -1016,6 +1018,152 @@ static void bench_lookup(const Args &arg) {
     if (!ok) throw std::runtime_error("lookup mismatch");
 }
 
+// a piecewise-polynomial activation on a ciphertext tensor from one opened value per element
+// (LocalCipherTextMultiplier::evaluate_spline_ciphertext_tensor), through the single-key and the 2-of-3 threshold client: the
+// logistic sigmoid on [-8, 8) as 2^bits pieces of degree d over a (shift + bits)-bit window, 40 fraction bits out
+// (make_spline_table), over n elements outside the lowest segment.  Every decrypted element must EQUAL the table's own value on
+// the element's piece or on the piece below, and lie within the builder's reported error of the sigmoid; prints the opened
+// values per call, the worst error, and whether all c1 of one tuple tensor are pairwise distinct in the default randomness mode.
+// runs > 0: the median wall clock of tuple generation, opening (difference and decryption) and closing on one line for
+// tools/bench_ops.py
+static void bench_spline(const Args &arg) {
+    const size_t n = arg(2, 256);
+    const int runs = arg.integer(3, 0);
+    const uint32_t bits = (uint32_t)arg(4, 5), shift = (uint32_t)arg(5, 11), d = (uint32_t)arg(6, 2);
+    if (shift + bits < 4 || shift + bits > 40) throw std::invalid_argument("spline: a window of 4 to 40 bits");
+    const uint32_t in_frac = shift + bits - 4, out_frac = 40;          // the window is [-8, 8)
+    Fixture fx;
+    auto &cs = fx.cs;
+    const auto &sk = fx.sk;
+    const uint32_t k = cs.message_bits();
+    auto sigmoid = [](double v) { return 1.0 / (1.0 + std::exp(-v)); };
+    const SplineTable st = make_spline_table(sigmoid, bits, shift, d, in_frac, out_frac);
+    Owned<PT> table = st.tensor<PT>();
+    const long half = 1L << (bits - 1), seg = 1L << shift;
+    const long lo = -(half - 1) * seg, hi = half * seg;                // everything but the lowest segment
+    // the ends of the range, 0, -1, 1, both sides of a segment boundary, then uniform ones
+    std::vector<long> xs(n);
+    const long fixed[8] = {lo, hi - 1, 0, -1, 1, seg - 1, seg, -seg};
+    for (size_t i = 0; i < n; i++)
+        xs[i] = i < 8 ? std::min(std::max(fixed[i], lo), hi - 1) : lo + (long)(mpz_get_ui(cs.random_plaintext(62).get()) % (unsigned long)(hi - lo));
+    auto residue = [&](long v) {                                    // v mod 2^k
+        Mpz m((unsigned long)(v < 0 ? -v : v));
+        if (v < 0) m.neg();
+        mpz_fdiv_r_2exp(m.get(), m.get(), k);
+        return m;
+    };
+    auto sigma_of = [&](long x) { return x >= 0 ? x / seg : -((-x + seg - 1) / seg); };
+    auto piece_of = [&](long sigma) { return (uint32_t)(sigma & ((1L << bits) - 1)); };
+    auto piece_value = [&](long x, long sigma) {                    // S_p(x) mod 2^k for the piece p of origin sigma 2^shift
+        Mpz acc;
+        for (uint32_t i = d + 1; i-- > 0;) {
+            const int64_t c = st.coef[(size_t)piece_of(sigma) * (d + 1) + i];
+            mpz_mul_si(acc.get(), acc.get(), x - sigma * seg);
+            if (c < 0) mpz_sub_ui(acc.get(), acc.get(), (unsigned long)(0 - (uint64_t)c));
+            else mpz_add_ui(acc.get(), acc.get(), (unsigned long)c);
+        }
+        mpz_fdiv_r_2exp(acc.get(), acc.get(), k);
+        return acc;
+    };
+    Owned<PT> px = plain_tensor(fx, {n}, [&](size_t i) { return residue(xs[i]); });
+    bool ok = true;
+    double worst = 0;
+    // every element is its own piece's value or the value of the piece below, and that value is close to the sigmoid
+    auto check = [&](const Tensor<CT *> &res) {
+        Owned<PT> dec = cs.decrypt_tensor(sk, res);
+        bool good = dec->num_elements() == n;
+        for (size_t i = 0; good && i < n; i++) {
+            const long so = sigma_of(xs[i]);
+            const bool own = *dec[i] == piece_value(xs[i], so), below = shift != 0 && *dec[i] == piece_value(xs[i], so - 1);
+            good = own || below;
+            const long su = own ? so : so - 1;
+            const double err = (double)std::fabs(st.value(piece_of(su), (long double)(xs[i] - su * seg)) -
+                                                 (long double)sigmoid((double)std::ldexp((long double)xs[i], -(int)in_frac)));
+            worst = std::max(worst, err);
+        }
+        return good;
+    };
+    for_both_clients(fx, [&](Client &client, Multiplier &mul, const std::string &who, bool threshold) {
+        Owned<CT> cx = cs.encrypt_tensor(client.network_public_key(), px);
+        const size_t before = client.decrypted_elements();
+        cs.synchronize();
+        auto [ms, res] = timed(cs, [&]() -> Owned<CT> { return mul.evaluate_spline_ciphertext_tensor(table, cx, bits, shift); });
+        const size_t opened = client.decrypted_elements() - before;
+        const bool pass = check(res) && opened == n;
+        if (!threshold) write_ciphertexts(fx, "local_bench_spline.bin", res);
+        std::cout << "  " << who << ": sigmoid, " << ((size_t)1 << bits) << " pieces of degree " << d << " over a " << shift + bits << "-bit window, " << n
+                  << " elements, opened_values " << opened << ", " << ms << " ms (host wall clock, tuple generation and the decryption included): "
+                  << (pass ? "ok" : "FAILED") << std::endl;
+        ok = ok && pass;
+        if (threshold) return;
+        // the parts on their own: one 0-D element, the plaintext rows, the refusals, and the randomness of a tuple tensor
+        Owned<CT> y0 = mul.evaluate_spline_ciphertext_tensor(table, Tensor<CT *>(cx[1 % n]), bits, shift);
+        const long s1 = sigma_of(xs[1 % n]);
+        const Mpz v0 = cs.decrypt(sk, *y0->get_value());
+        bool parts = y0->is_zero_degree() && (v0 == piece_value(xs[1 % n], s1) || v0 == piece_value(xs[1 % n], s1 - 1));
+        // row 0 of the mask r = 0 is piece 0 shifted by nothing: the table's own coefficients mod 2^k
+        Mpz zero;
+        Owned<PT> rows = cs.spline_rows_plaintext_tensor(table, Tensor<PT *>(1, &zero), bits, shift);
+        parts = parts && rows->num_elements() == ((size_t)(d + 1) << bits);
+        for (uint32_t i = 0; parts && i <= d; i++) {
+            Mpz c = *table[i];
+            mpz_fdiv_r_2exp(c.get(), c.get(), k);
+            parts = *rows[i] == c;
+        }
+        int refused = 0;
+        try {
+            (void)mul.evaluate_spline_ciphertext_tensor(table, cx, bits + 1, shift);       // the table has 2^bits pieces
+        } catch (const std::invalid_argument &) {
+            refused++;
+        }
+        try {
+            (void)mul.evaluate_spline_ciphertext_tensor(table, cx, bits, k - bits + 1);    // the window leaves k
+        } catch (const std::invalid_argument &) {
+            refused++;
+        }
+        parts = parts && refused == 2 && client.decrypted_elements() == before + n + 1;     // refused before anything was drawn
+        std::cout << "  0-D spline, spline_rows_plaintext_tensor, the refusals of a wrong piece count and of a window beyond k: " << (parts ? "ok" : "FAILED")
+                  << std::endl;
+        ok = ok && parts;
+        const bool default_mode = cs.tensor_randomness() == TensorRandomness::None;
+        auto tuples = client.get_spline_tuples(4, table, bits, shift);
+        size_t count = 0;
+        for (auto &t : tuples) count += t.num_elements();
+        const size_t want_count = 4 + 4 * ((size_t)(d + 1) << bits);
+        const bool distinct = default_mode && count == want_count && distinct_c1(tuples);
+        std::cout << "  " << want_count << " ciphertexts of the tuples of 4 elements, default randomness mode, distinct c1: " << (distinct ? "yes" : "NO")
+                  << std::endl;
+        ok = ok && distinct;
+        for (auto &t : tuples) free_all(t);
+    });
+    ok = ok && worst <= st.max_error;
+    std::cout << "spline_error: worst " << worst << " reported " << st.max_error << std::endl;
+    write_absdelta(fx);
+    if (runs > 0) {
+        Client client(cs, sk);
+        const auto &pk = client.network_public_key();
+        Owned<CT> cx = cs.encrypt_tensor(pk, px);
+        std::vector<double> t_tuples, t_open, t_close;
+        for (int pass = 0; pass <= runs; pass++) {                  // a warm-up pass, then the timed ones, each from a drained stream
+            cs.synchronize();
+            auto a = timed(cs, [&]() { return client.get_spline_tuples(n, table, bits, shift); });
+            auto b = timed(cs, [&]() -> Owned<PT> {
+                Owned<CT> diff = cs.sub_ciphertext_tensors(pk, cx, a.second[0]);
+                return client.decrypt_tensor(diff);
+            });
+            auto c = timed(cs, [&]() -> Owned<CT> { return cs.spline_close_ciphertext_tensor(b.second, a.second[1], bits, shift); });
+            for (auto &t : a.second) free_all(t);
+            if (pass) t_tuples.push_back(a.first), t_open.push_back(b.first), t_close.push_back(c.first);
+        }
+        for (auto *v : {&t_tuples, &t_open, &t_close}) std::sort(v->begin(), v->end());
+        std::cout << "spline_json: {\"E\": " << n << ", \"bits\": " << bits << ", \"shift\": " << shift << ", \"degree\": " << d << ", \"runs\": " << runs << ", "
+                  << MsJson{"tuples_ms", "tuples_ms_min_max", t_tuples} << ", " << MsJson{"open_ms", "open_ms_min_max", t_open} << ", "
+                  << MsJson{"close_ms", "close_ms_min_max", t_close} << "}" << std::endl;
+    }
+    std::cout << "  agree: " << (ok ? "yes" : "NO") << std::endl;
+    if (!ok) throw std::runtime_error("spline mismatch");
+}
+
 // threshold decryption end to end (the reference has no local benchmark for it; the calls are the
 // ones PartialDecryptionRequestHandler / SMPCClient make, partial_decryption_request_handler.hpp:140,
 // smpc_client.hpp:137): share sk t-out-of-n, every party of the first threshold set runs
@@ -1389,6 +1537,7 @@ static const struct Mode {
     {"poly_activation", "[elements=64 [runs=0]]", bench_poly_activation},
     {"divide", "[elements=64 [runs=0]]", bench_divide},
     {"lookup", "[elements=64 [runs=0]]", bench_lookup},
+    {"spline", "[elements=256 [runs=0 [bits=5 [shift=11 [degree=2]]]]]", bench_spline},
     {"formats", "", bench_formats},
     {"threads", "[rounds=4]", bench_threads},
     {"plaintexts", "<in> <out>", plaintexts_mode},

@@ -37,6 +37,12 @@
 // reference has no comparison).  With a lookup tuple ([r], [T_0], .., [T_{2^b - 1}]), T_j = g[(j + r) mod 2^b], per element:
 // e = Dec(x - r);  [y] = [T_{e mod 2^b}] -- one opened value, one round, y = g[x mod 2^b] exactly for ANY public table g of 2^b
 // plaintexts, and the closing step is a copy.  Every [T_j] carries its own randomness whatever the randomness mode.
+//
+// Piecewise-polynomial activations (evaluate_spline_ciphertext_tensor: sigmoid, tanh, GELU, exp, 1/x as splines; the reference
+// has none).  With a spline tuple ([r], [q_{j,i}], j < 2^b, i <= d), q_{j,.} the Taylor shift of piece (j + seg(r)) mod 2^b at r
+// minus the piece's origin, per element:  e = Dec(x - r);  j = seg(e);  [y] = [q_{j,0}] o prod_{i=1..d} [q_{j,i}]^(e^i) -- one
+// opened value, one round, 2^b (d + 1) ciphertexts per element for a (t + b)-bit window; y is the value at x of the element's
+// own piece or of the piece below (the carry of the low t bits is lost), so a piece serves two segments.
 #pragma once
 #include "hip_cryptosystem.hpp"
 
@@ -164,6 +170,23 @@ class LocalSMPCClient {
         Vector<Tensor<CipherText *>> t;
         t.push_back(cs_.encrypt_tensor_per_element(pk_, pr));
         t.push_back(cs_.lut_tuples_ciphertext_tensor(pk_, table, pr));
+        for (size_t i = 0; i < n; i++) delete pr[i];
+        return t;
+    }
+
+    // spline tuples for n elements and the public spline table(s) `table` ([2^bits, d + 1], or [n_tab, 2^bits, d + 1] with
+    // element i taking table i mod n_tab): {[r] (n elements), [q] (n 2^bits (d + 1) elements, [n, 2^bits, d + 1])} with r uniform
+    // in Z/2^k per element and q[i, j, .] the Taylor shift of piece (j + rho_i) mod 2^bits at r_i minus the piece's origin, used
+    // once; the caller owns the elements.  [r] and every [q] are encrypted with their OWN randomness whatever the randomness
+    // mode, for the reason given for the lookups.  Like the triplets, the tuples of the networked system would come from a
+    // protocol between the nodes.
+    Vector<Tensor<CipherText *>> get_spline_tuples(size_t n, const Tensor<PlainText *> &table, uint32_t bits, uint32_t shift) {
+        (void)cs_.spline_table_shape(table, n, bits, shift);     // refuse before anything is drawn
+        Tensor<PlainText *> pr(n, nullptr);
+        for (size_t i = 0; i < n; i++) pr[i] = new PlainText(cs_.random_plaintext(cs_.message_bits()));
+        Vector<Tensor<CipherText *>> t;
+        t.push_back(cs_.encrypt_tensor_per_element(pk_, pr));
+        t.push_back(cs_.spline_tuples_ciphertext_tensor(pk_, table, pr, bits, shift));
         for (size_t i = 0; i < n; i++) delete pr[i];
         return t;
     }
@@ -314,6 +337,21 @@ class LocalCipherTextMultiplier {
         return open_and_close(x, client_m.get_lookup_tuples(x.num_elements(), table),
                               [&](const Tensor<PlainText *> &e, const Vector<Tensor<CipherText *>> &tuples) {
                                   return client_m.crypto_system().lut_select_ciphertext_tensor(e, tuples[1]);
+                              });
+    }
+    // A piecewise polynomial element-wise, over the (shift + bits)-bit window of x: `table` holds 2^bits pieces of d + 1
+    // coefficients ([2^bits, d + 1], or [n_tab, 2^bits, d + 1] with element i taking table i mod n_tab; make_spline_table of
+    // spline_table.hpp builds one from a function), piece p evaluating sum_i c[p][i] (x - o(p))^i mod 2^k from its origin
+    // o(p) = sigma(p) 2^shift.  With a spline tuple per element, ONE opened value e = Dec(x - r) and one round; the tuple is
+    // 2^bits (d + 1) ciphertexts per element, not 2^(shift + bits).  The result is the value of the element's own piece or of the
+    // piece below (the carry of the low shift bits is lost; shift = 0: always its own), so every piece must approximate the
+    // function on two segments, and x must stay out of the lowest segment.  0-D and 1-D tensors; higher ranks are flattened and
+    // the result reshaped.
+    Tensor<CipherText *> evaluate_spline_ciphertext_tensor(const Tensor<PlainText *> &table, const Tensor<CipherText *> &x, uint32_t bits,
+                                                           uint32_t shift) {
+        return open_and_close(x, client_m.get_spline_tuples(x.num_elements(), table, bits, shift),
+                              [&](const Tensor<PlainText *> &e, const Vector<Tensor<CipherText *>> &tuples) {
+                                  return client_m.crypto_system().spline_close_ciphertext_tensor(e, tuples[1], bits, shift);
                               });
     }
     // max(x, 0) for `bits`-bit signed values x, exactly: the table holds v for 0 < v < 2^(bits-1) and 0 otherwise

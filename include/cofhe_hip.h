@@ -28,6 +28,9 @@
  *   cofhe_hip_lut_rotate_...,        nothing: ANY public function of a b-bit value on a ciphertext tensor, exactly (ReLU, max, max
  *   cofhe_hip_lut_tuples_...,        pooling), from ONE opened value per element (lookup tuples); the reference has no comparison
  *   cofhe_hip_lut_select_...         and no table lookup
+ *   cofhe_hip_spline_rows_...,       nothing: a piecewise polynomial (sigmoid, tanh, GELU, exp, 1/x as splines) over a (shift + bits)-bit
+ *   cofhe_hip_spline_tuples_...,     window on a ciphertext tensor from ONE opened value per element (spline tuples of 2^bits (d + 1)
+ *   cofhe_hip_spline_close_...       ciphertexts, not 2^(shift + bits)); the reference has no such operation
  *   cofhe_hip_decrypt_records        decrypt_tensor's per-element work, cpu_cryptosystem_tensor_ops.inl:21-33
  *   cofhe_hip_part_decrypt_records,  part_decrypt_tensor / combine_part_decryption_results_tensor,
  *   cofhe_hip_combine_part_...       cpu_cryptosystem_tensor_ops.inl:35-73 (cpu_cryptosystem_distributed.inl:231-285)
@@ -359,6 +362,63 @@ int cofhe_hip_lut_select_records(cofhe_hip_ctx *ctx, const void *d_e, const void
 /* host only, no GPU: *bits of the tuples that go with opened values of shape shape_e[ndim_e], ndim_e <= 7.  COFHE_HIP_ESHAPE unless
  * shape_t is shape_e with one more, last dimension of 2^bits entries, 1 <= bits <= COFHE_HIP_LUT_MAX_BITS. */
 int cofhe_hip_lut_tuples_shape_bits(uint32_t ndim_e, const uint32_t *shape_e, uint32_t ndim_t, const uint32_t *shape_t, uint32_t *bits);
+/* ---- piecewise-polynomial activations from one opened value (cofhe_amd/csrc/spline.hip) ----
+ * A SPLINE TABLE over a window of W = shift + bits <= k bits is 2^bits pieces of d + 1 plaintext coefficients, 1 <= d <=
+ * COFHE_HIP_POLY_MAX_DEGREE, 2^bits (d + 1) <= COFHE_HIP_SPLINE_MAX_TUPLE.  Piece p has the origin o(p) = sigma(p) 2^shift, sigma(p) the
+ * bits-bit two's-complement reading of p, and evaluates S_p(x) = sum_i c[p][i] (x - o(p))^i mod 2^k; the segment of x is
+ * seg(x) = floor((x mod 2^W) / 2^shift).  A SPLINE TUPLE of an element is ([r], [q_{j,i}], j < 2^bits, i <= d), used once: r uniform in
+ * Z/2^k, rho = seg(r), p_j = (j + rho) mod 2^bits, and q_{j,.} the Taylor shift of piece p_j at (r - o(p_j)) mod 2^k, that is
+ * sum_i q_{j,i} E^i = sum_i c[p_j][i] (E + r - o(p_j))^i.  With the ONE opened value e = Dec([x] - [r]) -- uniform whatever x is, so
+ * it hides x perfectly -- and j = seg(e),
+ *   [y] = [q_{j,0}] o prod_{i=1..d} [q_{j,i}]^(e^i mod 2^k),   y = S_{p'}(x) mod 2^k,   p' = (seg(x) - c) mod 2^bits,
+ * c = [(e mod 2^shift) + (r mod 2^shift) >= 2^shift]: the element's own piece or the one below (the carry of the low shift bits is
+ * lost, as in the division's "floor quotient or one less"; the wrap of k never matters, since 2^W divides 2^k).  The tuple holds
+ * 2^bits (d + 1) ciphertexts where a lookup over the same window holds 2^(shift + bits).  THE CALLER'S CONTRACT: piece p approximates
+ * the function on [o(p), o(p) + 2^(shift + 1)), two segments; x stays out of the lowest segment (sigma = -2^(bits - 1)), where the
+ * piece below wraps round to the top piece; fixed-point scales are the caller's, as for the polynomials.  shift = 0 has no carry:
+ * the result is exact on the element's own piece.  EVERY [q_{j,i}] MUST CARRY ITS OWN RANDOMNESS, for the reason given for the
+ * lookups: under a shared c1 the quotients of the c2 are publicly decodable and give the rotation away; so the tuples are made by
+ * the fresh-randomness comb (cofhe_hip_spline_tuples_records) and by nothing else.  The reference has no such operation.
+ * "The segment of a record" below: bits shift .. shift + bits - 1 of its value mod 2^k (sign word honoured, -0 and magnitudes of
+ * 2^k and above reduced, as in cofhe_hip_matmul_plain_plain_records); the field may straddle a word and lie in any word.
+ * All three records entry points: stream-ordered, no read-back of their own.  COFHE_HIP_EINVAL, nothing written: bits = 0; d = 0 or
+ * d > COFHE_HIP_POLY_MAX_DEGREE; 2^bits (d + 1) > COFHE_HIP_SPLINE_MAX_TUPLE; shift + bits > kbits; kbits outside 1 .. 639; n_tab = 0;
+ * n no multiple of n_tab; an output overlapping an input.  n = 0 does nothing. */
+#define COFHE_HIP_SPLINE_MAX_TUPLE 4096
+/* the plaintext rows: out[(i 2^bits + j) (d + 1) + c] = q_{j,c} of element i, i < n, j < 2^bits, c <= d, exponent records in
+ * [0, 2^kbits) with sign word 0.  d_pieces: n_tab tables of 2^bits (d + 1) records, piece-major (n_tab = 1: one table; n: one per
+ * element; element i reads table i mod n_tab); d_r: n records.  One launch ("k_spline_rows" under "profile_kernels"), one thread
+ * per element and row, no workspace, no lock. */
+int cofhe_hip_spline_rows_records(cofhe_hip_ctx *ctx, const void *d_pieces, uint64_t n_tab, const void *d_r, void *d_out, uint64_t n,
+                                  uint32_t bits, uint32_t shift, uint32_t d, uint32_t kbits, void *stream);
+/* the tuples' entries: out[m] = (h^rho[m], pk^rho[m] o f^(row[m])) with row the output of cofhe_hip_spline_rows_records, which it runs
+ * into a block of the block cache (it goes back behind the work queued on `stream`); then cofhe_hip_encrypt_fresh_records over the
+ * n 2^bits (d + 1) plaintexts, whose bytes these are (the plan "comb", kind 1, and its one read-back of the longest exponent).
+ * d_rho: n 2^bits (d + 1) exponent records of the caller's randomness, each used once; h_record, pk_record, f_record: HOST records. */
+int cofhe_hip_spline_tuples_records(cofhe_hip_ctx *ctx, const void *d_pieces, uint64_t n_tab, const void *d_r, const void *d_rho,
+                                    const uint32_t *h_record, const uint32_t *pk_record, const uint32_t *f_record, void *d_out, uint64_t n,
+                                    uint32_t bits, uint32_t shift, uint32_t d, uint32_t kbits, void *stream);
+/* the powers of the opened values: out[(c - 1) n + i] = e[i]^c mod 2^kbits, c = 1 .. d, i < n, exponent records in [0, 2^kbits) with
+ * sign word 0, power-major: the layout cofhe_hip_pow_dot_records reads its exponents in.  One launch ("k_spline_powers" under
+ * "profile_kernels"), one thread per element, no workspace, no lock.  COFHE_HIP_EINVAL: d = 0 or d > COFHE_HIP_POLY_MAX_DEGREE,
+ * kbits outside 1 .. 639, d_out overlapping d_e. */
+int cofhe_hip_spline_powers_records(cofhe_hip_ctx *ctx, const void *d_e, void *d_out, uint64_t n, uint32_t d, uint32_t kbits, void *stream);
+/* The closing step: out[i] = [q_{j,0}] o prod_{c=1..d} [q_{j,c}]^(e[i]^c mod 2^kbits), j the segment of e[i], i < n.  d_e: n exponent
+ * records of the opened values x - r; d_tuples: n 2^bits (d + 1) ciphertexts; d_out: n.  Two launches: cofhe_hip_spline_powers_records
+ * into a block of the block cache (which goes back behind the work queued on `stream`), and "k_spline_close", which runs the walk
+ * of cofhe_hip_pow_dot_records with the bases read in place from row j of the element's tuple -- no gather copy -- and
+ * [q_{j,0}] as the last composition of every record; e[i] = 0 gives [q_{j,0}] itself.  A sequence kernel: it reports
+ * through cofhe_hip_device_status.  It has NO serialised twin: tensors that arrive as bytes go through
+ * cofhe_hip_unpack_tensor_device (kind 0 for e of shape S, kind 2 for the tuples of shape S + [2^bits, d + 1]; it validates the
+ * incoming forms), cofhe_hip_spline_tuples_shape, this call and cofhe_hip_pack_tensor_device, as Engine.spline_close_tensors_bytes
+ * does. */
+int cofhe_hip_spline_close_records(cofhe_hip_ctx *ctx, const void *d_e, const void *d_tuples, void *d_out, uint64_t n, uint32_t bits,
+                                   uint32_t shift, uint32_t d, uint32_t kbits, void *stream);
+/* host only, no GPU: *bits and *d of the tuples that go with opened values of shape shape_e[ndim_e], ndim_e <= 6.  COFHE_HIP_ESHAPE
+ * (and *bits, *d left alone) unless shape_t is shape_e with two more, last dimensions [2^bits, d + 1], bits >= 1, 1 <= d <=
+ * COFHE_HIP_POLY_MAX_DEGREE, 2^bits (d + 1) <= COFHE_HIP_SPLINE_MAX_TUPLE. */
+int cofhe_hip_spline_tuples_shape(uint32_t ndim_e, const uint32_t *shape_e, uint32_t ndim_t, const uint32_t *shape_t, uint32_t *bits,
+                                  uint32_t *d);
 /* decryption: for each of n ciphertexts, m with c2 o (c1^sk)^-1 = f^m.  sk: one exponent record on
  * the device; f_record: HOST pointer to the 168-word record of f = (2^(2k), 2^(k+1), 1 - Delta_K)
  * (its table of f^(-2^j) is built on first use and cached in the context).  d_out receives
