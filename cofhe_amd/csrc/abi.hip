@@ -1,8 +1,9 @@
 // abi.hip -- the C ABI of include/cofhe_hip.h, in this order: the context, the block cache, the launch helpers (spans, the
 // two-build launch, flag words, the table-cache lookup), the workspace plans, the launchers (one launch site per kernel and
 // route; product_tree is the pairwise tree of them all) and the host-side tensor formats.  The kernels are declared in
-// kernels.hpp and defined in cofhe_hip.hip, wide.hip, comb.hip, affine.hip, matmul_left.hip, conv.hip, pow_dot.hip, divide.hip,
-// lut.hip and spline.hip; this file holds no device code of its own.  conv.hip holds the three kernels of the convolution, pow_dot.hip the two of
+// kernels.hpp and defined in cofhe_hip.hip, wide.hip, comb.hip, affine.hip, matmul_left.hip, conv.hip, conv_ct.hip, pow_dot.hip,
+// divide.hip, lut.hip and spline.hip; this file holds no device code of its own.  conv.hip holds the three kernels of the
+// convolution, conv_ct.hip the two that ciphertext filters add, pow_dot.hip the two of
 // the polynomial evaluation, divide.hip the signed floor division of the division by public divisors, lut.hip the two copies of
 // the table lookups, spline.hip the three kernels of the piecewise-polynomial activations.
 #include <hip/hip_runtime.h>
@@ -1450,6 +1451,23 @@ bool overlaps(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
     return a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
 }
+// out (n x p) = zero o s (n x m) . cts (m x p) with s^T (m x n exponent records) as given -- by a transposition
+// (cofhe_hip_matmul_plain_ct_records) or written transposed in the first place (cofhe_hip_conv2d_ct_filters_records):
+// out^T (p x n) = cts^T (p x m) . s^T through cofhe_hip_scal_matmul_records, whose routes, width choice, options and
+// synchronisations are the call's.  The two temporaries come from the block cache and go back behind the work queued on
+// `stream`.  The caller holds the context lock, has set the device and has checked n p > 0, m < 2^21 and the launch limit.
+int plain_ct_transposed(cofhe_hip_ctx *ctx, const void *d_st, const void *d_cts, const void *d_zero, void *d_out, uint32_t n, uint32_t m, uint32_t p,
+                        void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const size_t ct_bytes = (size_t)2 * REC_WORDS * 4, cts_bytes = (size_t)m * p * ct_bytes;
+    DevBuf cts_t, out_t;                         // cts^T (p x m), out^T (p x n)
+    cts_t.stream = out_t.stream = stream;
+    if (int rc = cts_t.get(ctx, cts_bytes ? cts_bytes : 4)) return rc;
+    if (int rc = out_t.get(ctx, (size_t)n * p * ct_bytes)) return rc;
+    if (int rc = transpose_launch(d_cts, cts_t.p, m, p, 2 * REC_WORDS, st)) return rc;
+    if (int rc = cofhe_hip_scal_matmul_records(ctx, cts_t.p, d_st, d_zero, out_t.p, p, m, n, stream)) return rc;
+    return transpose_launch(out_t.p, d_out, p, n, 2 * REC_WORDS, st);
+}
 }  // namespace
 
 // Needs no workspace plan of its own: the temporaries are three blocks of the block cache, and the product it calls carves
@@ -1466,16 +1484,11 @@ int cofhe_hip_matmul_plain_ct_records(cofhe_hip_ctx *ctx, const void *d_s, const
     unsigned blocks;
     if (int rc = compose_blocks((uint64_t)n * p * 2, &blocks)) return rc;
     HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    DevBuf cts_t, s_t, out_t;                    // cts^T (p x m), s^T (m x n), out^T (p x n)
-    cts_t.stream = s_t.stream = out_t.stream = stream;
-    if (int rc = cts_t.get(ctx, cts_bytes ? cts_bytes : 4)) return rc;
+    DevBuf s_t;                                  // s^T (m x n)
+    s_t.stream = stream;
     if (int rc = s_t.get(ctx, s_bytes ? s_bytes : 4)) return rc;
-    if (int rc = out_t.get(ctx, out_bytes)) return rc;
-    if (int rc = transpose_launch(d_cts, cts_t.p, m, p, 2 * REC_WORDS, st)) return rc;
-    if (int rc = transpose_launch(d_s, s_t.p, n, m, EXP_REC_WORDS, st)) return rc;
-    if (int rc = cofhe_hip_scal_matmul_records(ctx, cts_t.p, s_t.p, d_zero, out_t.p, p, m, n, stream)) return rc;
-    return transpose_launch(out_t.p, d_out, p, n, 2 * REC_WORDS, st);
+    if (int rc = transpose_launch(d_s, s_t.p, n, m, EXP_REC_WORDS, (hipStream_t)stream)) return rc;
+    return plain_ct_transposed(ctx, s_t.p, d_cts, d_zero, d_out, n, m, p, stream);
 }
 
 namespace {
@@ -1568,6 +1581,25 @@ int conv2d_run(cofhe_hip_ctx *ctx, const void *d_w, const void *d_cts, const voi
     }
     return cofhe_hip_scal_matmul_records(ctx, patches.p, grouped ? dense.p : d_w, d_zero, d_out, n, (uint32_t)m_dense, p, stream);
 }
+// the one launch site of k_gather_patch_exponents: the m x n TRANSPOSED patch matrix of the plaintext image d_img (exponent
+// records), the zero exponent in the padding; 16-byte pieces when both pointers allow them.  s has no groups
+int gather_patch_exponents_launch(cofhe_hip_ctx *ctx, const ConvShape &s, const void *d_img, void *d_st, hipStream_t st) {
+    const uint32_t n = conv_rows(s), m = conv_inner(s);
+    const bool vec16 = (((uintptr_t)d_img | (uintptr_t)d_st) & 15) == 0;
+    const uint64_t total = (uint64_t)n * m * (vec16 ? EXP_REC_WORDS / 4 : EXP_REC_WORDS);
+    if (total == 0) return COFHE_HIP_OK;
+    const unsigned blocks = (unsigned)std::min<uint64_t>((total + 255) / 256, 64u * NUM_CUS);       // grid-stride beyond that
+    ProfScope ps(ctx, "k_gather_patch_exponents", st);
+    hipLaunchKernelGGL(k_gather_patch_exponents, dim3(blocks), dim3(256), 0, st, s, (const uint32_t *)d_img, (uint32_t *)d_st, n, m, vec16 ? 1u : 0u);
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+// what the two entry points with a PLAINTEXT image check before the context or a pointer is looked at: the geometry, and that
+// it has no groups (with groups the patch matrix differs per column group); fills Ho, Wo
+const char *conv_plain_image_check(ConvShape &s) {
+    if (const char *why = conv_shape_check(s)) return why;
+    return s.groups != 1 ? "conv2d: a plaintext image (ciphertext filters, the plaintext convolution) takes groups = 1" : nullptr;
+}
 // a pooling geometry: one filter per channel
 ConvShape pool_shape_of(const cofhe_hip_conv2d_geometry &a) {
     ConvShape s = conv_geometry_of(a);
@@ -1645,6 +1677,51 @@ int cofhe_hip_matmul_plain_plain_records(cofhe_hip_ctx *ctx, const void *d_a, co
                        (uint32_t *)d_out, n, m, p, kbits);
     HIPCHK(hipGetLastError());
     return COFHE_HIP_OK;
+}
+
+// the one launch site of k_plain_conv2d
+int cofhe_hip_conv2d_plain_plain_records(cofhe_hip_ctx *ctx, const void *d_img, const void *d_w, void *d_out,
+                                         const cofhe_hip_conv2d_geometry *geometry, uint32_t kbits, void *stream) {
+    if (!geometry) return fail(COFHE_HIP_EINVAL, "null argument");
+    ConvShape s = conv_geometry_of(*geometry);
+    if (const char *why = conv_plain_image_check(s)) return fail(COFHE_HIP_EINVAL, why);
+    if (kbits == 0 || kbits > 32u * PMM_MAX_LIMBS || 2 * kbits + 1 > (uint32_t)PLIMBS * 32) return fail(COFHE_HIP_EINVAL, "k out of range");
+    const uint32_t n = conv_rows(s), m = conv_inner(s), p = s.Co;
+    if ((uint64_t)n * p == 0) return COFHE_HIP_OK;
+    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4, out_bytes = (size_t)n * p * exp_bytes;
+    if (overlaps(d_out, out_bytes, d_img, (size_t)s.B * s.H * s.W * s.C * exp_bytes) || overlaps(d_out, out_bytes, d_w, (size_t)m * p * exp_bytes))
+        return fail(COFHE_HIP_EINVAL, "conv2d_plain_plain: the output overlaps an input");
+    const uint32_t gx = (n + PMM_TILE - 1) / PMM_TILE, gy = (p + PMM_TILE - 1) / PMM_TILE;
+    if (gy > 65535u) return fail(COFHE_HIP_EINVAL, "work size out of range");
+    HIPCHK(hipSetDevice(ctx->device));
+    ProfScope ps(ctx, "k_plain_conv2d", (hipStream_t)stream);
+    hipLaunchKernelGGL(k_plain_conv2d, dim3(gx, gy), dim3(PMM_THREADS), 0, (hipStream_t)stream, s, (const uint32_t *)d_img, (const uint32_t *)d_w,
+                       (uint32_t *)d_out, kbits);
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+
+// Needs no workspace plan of its own, like cofhe_hip_matmul_plain_ct_records: the transposed patch matrix of the image is
+// written straight into the block that product transposes its left operand into, and the rest is that product's
+int cofhe_hip_conv2d_ct_filters_records(cofhe_hip_ctx *ctx, const void *d_img_exps, const void *d_filters_cts, const void *d_zero, void *d_out,
+                                        const cofhe_hip_conv2d_geometry *geometry, void *stream) {
+    if (!geometry) return fail(COFHE_HIP_EINVAL, "null argument");
+    ConvShape s = conv_geometry_of(*geometry);
+    if (const char *why = conv_plain_image_check(s)) return fail(COFHE_HIP_EINVAL, why);      // m < 2^21 and the launch limit among it
+    const uint32_t n = conv_rows(s), m = conv_inner(s), p = s.Co;
+    if ((uint64_t)n * p == 0) return COFHE_HIP_OK;
+    const size_t ct_bytes = (size_t)2 * REC_WORDS * 4, exp_bytes = (size_t)EXP_REC_WORDS * 4, out_bytes = (size_t)n * p * ct_bytes;
+    if (overlaps(d_out, out_bytes, d_img_exps, (size_t)s.B * s.H * s.W * s.C * exp_bytes) ||
+        overlaps(d_out, out_bytes, d_filters_cts, (size_t)m * p * ct_bytes) || overlaps(d_out, out_bytes, d_zero, ct_bytes))
+        return fail(COFHE_HIP_EINVAL, "conv2d_ct_filters: the output overlaps an input");
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t st_bytes = (size_t)n * m * exp_bytes;
+    DevBuf s_t;                                  // S^T (m x n): the patch matrix of the image, transposed
+    s_t.stream = stream;
+    if (int rc = s_t.get(ctx, st_bytes ? st_bytes : 4)) return rc;
+    if (int rc = gather_patch_exponents_launch(ctx, s, d_img_exps, s_t.p, (hipStream_t)stream)) return rc;
+    return plain_ct_transposed(ctx, s_t.p, d_filters_cts, d_zero, d_out, n, m, p, stream);
 }
 
 // ---- polynomial evaluation from one opened value (pow_dot.hip) -------------------------------------------------------------

@@ -15,7 +15,8 @@
 // then gives zero.  G = C = Co is a depthwise convolution, with all-ones filters sum pooling (cofhe_hip_sum_pool2d_records),
 // with kh = kw = 1 a per-channel scale.
 //
-// Not here: a per-channel bias (cofhe_hip_add_plain_records on the result), ciphertext filters and max pooling.
+// Not here: a per-channel bias (cofhe_hip_add_plain_records on the result) and max pooling.  Ciphertext filters over a
+// plaintext image, and the plaintext convolution of their Beaver triplet: plain_conv.hpp, on this geometry.
 #pragma once
 #include "form_io.hpp"
 

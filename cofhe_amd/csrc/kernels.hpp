@@ -3,7 +3,8 @@
 // (the latency kernels); wire.hip launches its own kernels.  A declaration that matches no definition is an
 // undefined symbol when the library is loaded (tests/test_cabi.py).  comb.hip holds the two kernels of the fixed-base comb,
 // affine.hip the ciphertext difference and the record inverse, matmul_left.hip the record transpose and the plaintext
-// matrix product, conv.hip the convolution's level 0, its patch gather and its filter expansion, pow_dot.hip the multi-exponentiation
+// matrix product, conv.hip the convolution's level 0, its patch gather and its filter expansion, conv_ct.hip the plaintext
+// convolution and the patch gather of a plaintext image for ciphertext filters, pow_dot.hip the multi-exponentiation
 // and the Taylor shift of the polynomial evaluation, divide.hip the signed floor division on exponent records, lut.hip the row
 // rotation and the entry selection of the table lookups, spline.hip the rows, the powers and the closing walk of the
 // piecewise-polynomial activations.
@@ -147,6 +148,14 @@ __global__ void k_gather_patches(cofhe::ConvShape s, const uint32_t *__restrict_
                                  uint32_t *__restrict__ out, uint32_t n, uint32_t m, uint32_t vec16);
 __global__ void k_expand_group_filters(const uint32_t *__restrict__ w, uint32_t *__restrict__ dense, uint32_t taps, uint32_t C, uint32_t Co,
                                        uint32_t groups, uint32_t vec16);
+
+// the convolution with ciphertext filters and its Beaver triplet (conv_ct.hip, plain_conv.hpp): out = img * w mod 2^kbits on
+// exponent records, an implicit GEMM with its left tile read through conv_leaf, and the transposed patch matrix m x n of a
+// plaintext image written out, zero records in the padding (vec16: 16-byte pieces)
+__global__ void k_plain_conv2d(cofhe::ConvShape s, const uint32_t *__restrict__ img, const uint32_t *__restrict__ w, uint32_t *__restrict__ out,
+                               uint32_t kbits);
+__global__ void k_gather_patch_exponents(cofhe::ConvShape s, const uint32_t *__restrict__ img, uint32_t *__restrict__ out, uint32_t n, uint32_t m,
+                                         uint32_t vec16);
 
 // polynomial evaluation from one opened value (pow_dot.hip; pow_dot.hpp, poly_shift.hpp): out[2e+h] = prod_{i<d} bases[(i n_ct + e) 2 + h]
 // ^ exps[i n_ct + e] by one ladder per record whose squarings the d bases share, and the Taylor shift q[i n + e] =

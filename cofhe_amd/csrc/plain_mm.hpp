@@ -79,21 +79,23 @@ PMM_DEV void pmm_mac(uint32_t (&acc)[LMAX], const uint32_t *a, int a_stride, con
 
 // The two phases of one step of 16 along the inner dimension, for thread tid of the workgroup that owns the output tile at
 // (i0, k0); a workgroup barrier separates them, and another follows pmm_accumulate.  lds: 2 * pmm_tile_words(L) words.
+// one thread's element of a tile buffer (t = buffer + tid): the residue of rec, or zero for a null rec -- an element beyond the
+// matrix, or the padding of a convolution (plain_conv.hpp)
+template <int LMAX>
+PMM_DEV void pmm_stage_one(uint32_t *t, const uint32_t *rec, int L, uint32_t kbits) {
+    if (rec) {
+        pmm_reduce<LMAX>(rec, L, kbits, t, PMM_THREADS);
+    } else {
+        for (int l = 0; l < L; l++) t[l * PMM_THREADS] = 0;
+    }
+}
 template <int LMAX>
 PMM_DEV void pmm_stage(uint32_t *lds, const uint32_t *a, const uint32_t *b, uint32_t n, uint32_t m, uint32_t p, uint32_t i0, uint32_t k0,
                        uint32_t j0, int tid, int L, uint32_t kbits) {
     const uint32_t r = (uint32_t)tid / PMM_TILE, c = (uint32_t)tid % PMM_TILE;
-    uint32_t *ta = lds + tid, *tb = lds + pmm_tile_words(L) + tid;
-    if (i0 + r < n && j0 + c < m) {
-        pmm_reduce<LMAX>(a + ((uint64_t)(i0 + r) * m + (j0 + c)) * PMM_REC_WORDS, L, kbits, ta, PMM_THREADS);
-    } else {
-        for (int l = 0; l < L; l++) ta[l * PMM_THREADS] = 0;
-    }
-    if (j0 + r < m && k0 + c < p) {
-        pmm_reduce<LMAX>(b + ((uint64_t)(j0 + r) * p + (k0 + c)) * PMM_REC_WORDS, L, kbits, tb, PMM_THREADS);
-    } else {
-        for (int l = 0; l < L; l++) tb[l * PMM_THREADS] = 0;
-    }
+    pmm_stage_one<LMAX>(lds + tid, i0 + r < n && j0 + c < m ? a + ((uint64_t)(i0 + r) * m + (j0 + c)) * PMM_REC_WORDS : nullptr, L, kbits);
+    pmm_stage_one<LMAX>(lds + pmm_tile_words(L) + tid, j0 + r < m && k0 + c < p ? b + ((uint64_t)(j0 + r) * p + (k0 + c)) * PMM_REC_WORDS : nullptr,
+                        L, kbits);
 }
 template <int LMAX>
 PMM_DEV void pmm_accumulate(const uint32_t *lds, uint32_t (&acc)[LMAX], int tid, int L) {

@@ -245,6 +245,48 @@ class Engine:
                                                                         C.byref(out), C.byref(n)))
         return self._take(out, n)
 
+    def conv2d_ct_filters_tensors(self, img: bytes, filters: bytes, zero: bytes, stride=(1, 1), pad=(0, 0), dilation=(1, 1)) -> bytes:
+        """the plaintext tensor img [B, H, W, C] under the ciphertext tensor filters [kh, kw, C, Co], channels last, from zero
+        (1-element ciphertext tensor); stride, zero padding and dilation as (rows, columns).  Returns the ciphertext tensor
+        [B, Ho, Wo, Co]: the E * [Bf] term of a convolution Beaver triplet.  Composed here from unpack_tensor_device (which
+        validates the incoming forms), conv2d_ct_filters_records and pack_tensor_device, as lut_select_tensors_bytes is: the
+        library has no entry point of its own for it.  COFHE_HIP_ESHAPE when an operand is not 4-D or the channels differ"""
+        held = []
+
+        def load(t, kind):
+            # every integer owns an 8-byte table entry: the record count is bounded by the length
+            cap = (len(t) // 8) // (3 if kind else 1) + 1
+            raw = self.malloc(len(t) + 4)
+            held.append(raw)
+            recs = self.malloc(cap * 4 * (REC_WORDS if kind else EXP_REC_WORDS))
+            held.append(recs)
+            self.upload(raw, t)
+            shape, n = self.unpack_tensor_device(raw, len(t), kind, recs, cap)
+            return recs, shape, n
+
+        try:
+            di, si, _ = load(img, 0)
+            df, sf, _ = load(filters, 2)
+            if len(si) != 4 or len(sf) != 4:
+                raise CofheHipError(-2, "conv2d_ct_filters takes a 4-D image tensor [B, H, W, C] and a 4-D filter tensor [kh, kw, C, Co]")
+            ho, wo = conv2d_out_shape(si, sf, stride, pad, dilation, 1)          # ESHAPE when the channels differ
+            dz, _, nz = load(zero, 2)
+            if nz != 2:
+                raise CofheHipError(-1, "zero must be a one-element ciphertext tensor")
+            so = [si[0], ho, wo, sf[3]]
+            nout = 2 * so[0] * ho * wo * so[3]
+            dout = self.malloc(max(nout, 1) * REC_WORDS * 4)
+            held.append(dout)
+            self.conv2d_ct_filters_records(di, df, dz, dout, si, sf, stride, pad, dilation=dilation)
+            cap = self.packed_size_bound(nout, 2, 4)
+            packed = self.malloc(cap)
+            held.append(packed)
+            ln = self.pack_tensor_device(dout, nout, 2, so, packed, cap)
+            return self.download(packed, ln, dtype="uint8").tobytes()
+        finally:
+            for p in held:
+                self.free(p)
+
     def sum_pool2d_tensors(self, cts: bytes, zero: bytes, kernel, stride=None, pad=(0, 0)) -> bytes:
         """the sums over kernel = (kh, kw) windows of the ciphertext tensor cts [B, H, W, C], channel by channel, from zero;
         stride defaults to the kernel.  Returns [B, Ho, Wo, C].  Average pooling: fold 1 / (kh kw) into the next layer's weights"""
@@ -431,6 +473,25 @@ class Engine:
         _chk(self.L.cofhe_hip_matmul_plain_plain_records(self.ctx, C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_out),
                                                          C.c_uint32(n), C.c_uint32(m), C.c_uint32(p), C.c_uint32(kbits),
                                                          C.c_void_p(stream)))
+
+    def conv2d_plain_plain_records(self, d_img, d_w, d_out, image, filters, kbits, stride=(1, 1), pad=(0, 0), stream=0, dilation=(1, 1)):
+        """out [B, Ho, Wo, Co] = the convolution mod 2^kbits of the plaintext image d_img [B, H, W, C] = `image` with the plaintext
+        filters d_w [kh, kw, C, Co] = `filters`, all exponent records, channels last; outputs in [0, 2^k) with sign word 0; one
+        launch, purely stream-ordered.  The E * D term of a convolution Beaver triplet.  Returns (Ho, Wo)"""
+        geo = _conv_geometry(image, filters, stride, pad, dilation, 1)
+        _chk(self.L.cofhe_hip_conv2d_plain_plain_records(self.ctx, C.c_void_p(d_img), C.c_void_p(d_w), C.c_void_p(d_out), C.byref(geo),
+                                                         C.c_uint32(kbits), C.c_void_p(stream)))
+        return conv2d_out_shape(image, filters, stride, pad, dilation, 1)
+
+    def conv2d_ct_filters_records(self, d_img_exps, d_filters_cts, d_zero, d_out, image, filters, stride=(1, 1), pad=(0, 0), stream=0,
+                                  dilation=(1, 1)):
+        """out [B, Ho, Wo, Co] = the convolution of the PLAINTEXT image d_img_exps [B, H, W, C] = `image` (exponent records) with the
+        CIPHERTEXT filters d_filters_cts [kh, kw, C, Co] = `filters`, channels last, from the ciphertext d_zero; d_out must not
+        overlap an input.  The E * [Bf] term of a convolution Beaver triplet.  Returns (Ho, Wo)"""
+        geo = _conv_geometry(image, filters, stride, pad, dilation, 1)
+        _chk(self.L.cofhe_hip_conv2d_ct_filters_records(self.ctx, C.c_void_p(d_img_exps), C.c_void_p(d_filters_cts), C.c_void_p(d_zero),
+                                                        C.c_void_p(d_out), C.byref(geo), C.c_void_p(stream)))
+        return conv2d_out_shape(image, filters, stride, pad, dilation, 1)
 
     def pow_dot_records(self, d_bases, d_exps, d_out, n_ciphertexts, d, stream=0):
         """out[e] = prod_{i<d} bases[i][e]^exps[i][e]: d ciphertext tensors and d exponent tensors of n elements, power-major,

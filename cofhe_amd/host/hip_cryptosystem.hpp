@@ -748,6 +748,54 @@ class HIPCryptoSystem {
         check(cofhe_hip_matmul_plain_plain_records(ctx_, da.ptr, db.ptr, dout.ptr, (uint32_t)n, (uint32_t)m, (uint32_t)p, k_, nullptr));
         return read_plaintexts(dout.ptr, n * p, EXPW, {n, p}, false);
     }
+    // img [B, H, W, C] * w [kh, kw, C, Co] mod 2^k on the device (k_plain_conv2d), channels last, strides, zero padding and
+    // dilation as {rows, columns}: a tensor [B, Ho, Wo, Co].  The E * D term of a convolution Beaver triplet and the
+    // C = A * Bf of its generation; mirrors matmul_plaintext_tensors.
+    Tensor<PlainText *> conv2d_plaintext_tensors(const Tensor<PlainText *> &img, const Tensor<PlainText *> &w, const std::array<size_t, 2> &stride = {1, 1},
+                                                 const std::array<size_t, 2> &pad = {0, 0}, const std::array<size_t, 2> &dilation = {1, 1}) const {
+        if (img.ndim() != 4 || w.ndim() != 4) throw std::invalid_argument("conv2d_plaintext_tensors: both operands must be 4D");
+        if (w.shape()[2] != img.shape()[3]) throw std::invalid_argument("conv2d_plaintext_tensors: the channels of the filters and of the image differ");
+        const cofhe_hip_conv2d_geometry geo = conv_geometry({img.shape()[0], img.shape()[1], img.shape()[2], img.shape()[3], w.shape()[0], w.shape()[1],
+                                                             w.shape()[3], stride[0], stride[1], pad[0], pad[1], dilation[0], dilation[1], 1});
+        uint32_t Ho = 0, Wo = 0;
+        check(cofhe_hip_conv2d_geometry_out_shape(&geo, &Ho, &Wo));
+        const size_t nout = (size_t)geo.B * Ho * Wo * geo.Co;
+        Staged di = stage(pack_exponents(img)), dw = stage(pack_exponents(w)), dout = device_buffer(nout * EXPW * 4);
+        check(cofhe_hip_conv2d_plain_plain_records(ctx_, di.ptr, dw.ptr, dout.ptr, &geo, k_, nullptr));
+        return read_plaintexts(dout.ptr, nout, EXPW, {geo.B, Ho, Wo, geo.Co}, false);
+    }
+    // 2-D convolution with CIPHERTEXT filters, channels last: the plaintext image img [B, H, W, C] under the ciphertext filters
+    // filters [kh, kw, C, Co]; res[b,oy,ox,co] = zero o prod filters[dy,dx,ci,co]^img[b, oy sh + dy dh - ph, ox sw + dx dw - pw, ci],
+    // a tensor [B, Ho, Wo, Co] (cofhe_hip_conv2d_ct_filters_records: the patch matrix of the image is written once, transposed,
+    // and a filter's table of odd powers serves every output position).  The E * [Bf] term of a convolution Beaver triplet
+    // (LocalCipherTextMultiplier::conv2d_ciphertext_tensors).  Starts from a fresh encryption of zero and is re-randomised like
+    // matmul_plaintext_ciphertext_tensors; pass `zero` to make the start reproducible.
+    Tensor<CipherText *> conv2d_ciphertext_filters_tensors(const PublicKey &pk, const Tensor<PlainText *> &img, const Tensor<CipherText *> &filters,
+                                                           const std::array<size_t, 2> &stride = {1, 1}, const std::array<size_t, 2> &pad = {0, 0},
+                                                           const std::array<size_t, 2> &dilation = {1, 1}, const CipherText *zero = nullptr) const {
+        if (img.ndim() != 4 || filters.ndim() != 4) throw std::invalid_argument("conv2d_ciphertext_filters_tensors: both operands must be 4D");
+        DeviceTensor out = conv2d_ciphertext_filters_tensors(img, upload(filters), zero_tensor(pk, zero), stride, pad, dilation);
+        rerandomize_result(pk, out);           // one fresh r per output
+        return download(std::move(out));
+    }
+    // the same on resident operands; deterministic (no re-randomisation), like the other DeviceTensor members
+    DeviceTensor conv2d_ciphertext_filters_tensors(const Tensor<PlainText *> &img, const DeviceTensor &filters, const DeviceTensor &zero,
+                                                   const std::array<size_t, 2> &stride = {1, 1}, const std::array<size_t, 2> &pad = {0, 0},
+                                                   const std::array<size_t, 2> &dilation = {1, 1}) const {
+        if (img.ndim() != 4 || filters.shape_.size() != 4) throw std::invalid_argument("conv2d_ciphertext_filters_tensors: both operands must be 4D");
+        if (filters.shape_[2] != img.shape()[3])
+            throw std::invalid_argument("conv2d_ciphertext_filters_tensors: the channels of the filters and of the image differ");
+        if (zero.n_ != 1) throw std::invalid_argument("conv2d_ciphertext_filters_tensors: zero must be one ciphertext");
+        const cofhe_hip_conv2d_geometry geo = conv_geometry({img.shape()[0], img.shape()[1], img.shape()[2], img.shape()[3], filters.shape_[0],
+                                                             filters.shape_[1], filters.shape_[3], stride[0], stride[1], pad[0], pad[1], dilation[0],
+                                                             dilation[1], 1});
+        uint32_t Ho = 0, Wo = 0;
+        check(cofhe_hip_conv2d_geometry_out_shape(&geo, &Ho, &Wo));
+        Staged dex = stage(pack_exponents(img));
+        DeviceTensor out = alloc({geo.B, Ho, Wo, geo.Co}, (size_t)geo.B * Ho * Wo * geo.Co);
+        check(cofhe_hip_conv2d_ct_filters_records(ctx_, dex.ptr, filters.ptr_, zero.ptr_, out.ptr_, &geo, nullptr));
+        return out;
+    }
 
     // res[i,k] = zero o prod_j x[i,j,k] for x of n*m*p ciphertexts (flat, row-major): the
     // accumulation loop of the ciphertext x ciphertext matrix product

@@ -292,26 +292,37 @@ struct ConvGeometry {
     size_t B, H, W, C, kh, kw, Co, groups, dh, dw, sh, sw, ph, pw;
 };
 
-// the B x Ho x Wo x Co outputs of xval and wval over flat indices
-template <typename X, typename Wt>
-std::vector<float> conv_reference(const ConvGeometry &g, size_t Ho, size_t Wo, X xval, Wt wval) {
+// term(o, xi, wi) for every product of the convolution: output o gains image element xi times filter element wi (flat indices)
+template <typename Term>
+void conv_terms(const ConvGeometry &g, size_t Ho, size_t Wo, Term term) {
     const size_t Cg = g.C / g.groups, Cog = g.Co / g.groups;
-    std::vector<float> out(g.B * Ho * Wo * g.Co);
     for (size_t bb = 0; bb < g.B; bb++)
         for (size_t oy = 0; oy < Ho; oy++)
             for (size_t ox = 0; ox < Wo; ox++)
-                for (size_t co = 0; co < g.Co; co++) {
-                    float want = 0;
+                for (size_t co = 0; co < g.Co; co++)
                     for (size_t dy = 0; dy < g.kh; dy++)
                         for (size_t dx = 0; dx < g.kw; dx++) {
                             const size_t y = oy * g.sh + dy * g.dh, xx = ox * g.sw + dx * g.dw;
                             if (y < g.ph || y - g.ph >= g.H || xx < g.pw || xx - g.pw >= g.W) continue;
                             for (size_t ci = 0; ci < Cg; ci++)
-                                want += xval(((bb * g.H + (y - g.ph)) * g.W + (xx - g.pw)) * g.C + (co / Cog) * Cg + ci) *
-                                        wval(((dy * g.kw + dx) * Cg + ci) * g.Co + co);
+                                term(((bb * Ho + oy) * Wo + ox) * g.Co + co, ((bb * g.H + (y - g.ph)) * g.W + (xx - g.pw)) * g.C + (co / Cog) * Cg + ci,
+                                     ((dy * g.kw + dx) * Cg + ci) * g.Co + co);
                         }
-                    out[((bb * Ho + oy) * Wo + ox) * g.Co + co] = want;
-                }
+}
+
+// the B x Ho x Wo x Co outputs of xval and wval over flat indices
+template <typename X, typename Wt>
+std::vector<float> conv_reference(const ConvGeometry &g, size_t Ho, size_t Wo, X xval, Wt wval) {
+    std::vector<float> out(g.B * Ho * Wo * g.Co);
+    conv_terms(g, Ho, Wo, [&](size_t o, size_t xi, size_t wi) { out[o] += xval(xi) * wval(wi); });
+    return out;
+}
+
+// the same for plaintexts, exactly, mod 2^k
+std::vector<Mpz> conv_reference_mod(const ConvGeometry &g, size_t Ho, size_t Wo, const Tensor<PT *> &x, const Tensor<PT *> &w, uint32_t k) {
+    std::vector<Mpz> out(g.B * Ho * Wo * g.Co);
+    conv_terms(g, Ho, Wo, [&](size_t o, size_t xi, size_t wi) { mpz_addmul(out[o].get(), x[xi]->get(), w[wi]->get()); });
+    for (auto &v : out) mpz_fdiv_r_2exp(v.get(), v.get(), k);
     return out;
 }
 
@@ -1349,6 +1360,97 @@ static void bench_ciphertext_matmul_matrix(const Args &arg) {
     if (!(ok[0] && ok[1])) throw std::runtime_error("ciphertext matmul mismatch");
 }
 
+// an encrypted image B x H x W x C under ENCRYPTED filters kh x kw x C x Co (channels last) through one convolution Beaver
+// triplet (LocalCipherTextMultiplier::conv2d_ciphertext_tensors): uniform operands in Z/2^k, the result decrypted and compared
+// with the exact convolution of the plaintexts mod 2^k; the opened values counted next to what element triplets (2 n m p) and a
+// matrix triplet on the patch matrix (n m + m p) would open for the layer.  Also the E * [Bf] term on its own from a fixed
+// Enc(0) -- the plaintext image under the encrypted filters, deterministic --, written with its operands for the parity checker
+// (local_bench_cconv_*.bin).  B H W C kh kw Co [sh sw ph pw dh dw [t parties [runs]]]; runs > 0: the phases of the flow, timed
+static void bench_conv2d_ciphertext(const Args &arg) {
+    const ConvGeometry g{arg(2, 1), arg(3, 5), arg(4, 4), arg(5, 2), arg(6, 3), arg(7, 2), arg(8, 2), 1, arg(13, 1), arg(14, 1),
+                         arg(9, 1), arg(10, 1), arg(11, 0), arg(12, 0)};
+    const size_t t = arg(15, 0), parties = arg(16, 3);
+    const int runs = arg.integer(17, 0);
+    const std::array<size_t, 2> stride{g.sh, g.sw}, pad{g.ph, g.pw}, dilation{g.dh, g.dw};
+    Fixture fx;
+    auto &cs = fx.cs;
+    const uint32_t k = cs.message_bits();
+    auto client = make_client(fx, t, parties);
+    Multiplier mul(*client);
+    const auto &pk = client->network_public_key();
+    auto uniform = [&](size_t) { return cs.random_plaintext(k); };
+    Owned<PT> px = plain_tensor(fx, {g.B, g.H, g.W, g.C}, uniform), pw = plain_tensor(fx, {g.kh, g.kw, g.C, g.Co}, uniform);
+    Owned<CT> cx = cs.encrypt_tensor(pk, px), cw = cs.encrypt_tensor(pk, pw);
+    const size_t before = client->decrypted_elements();
+    cs.synchronize();
+    auto flow = timed(cs, [&]() -> Owned<CT> { return mul.conv2d_ciphertext_tensors(cx, cw, stride, pad, dilation); });
+    const size_t opened = client->decrypted_elements() - before;
+    const std::vector<size_t> oshape = flow.second->shape();
+    if (oshape.size() != 4 || oshape[0] != g.B || oshape[3] != g.Co) throw std::runtime_error("conv2d_ciphertext: the output is not B x . x . x Co");
+    const size_t Ho = oshape[1], Wo = oshape[2], n = g.B * Ho * Wo, m = g.kh * g.kw * g.C, p = g.Co;
+    const std::vector<Mpz> want = conv_reference_mod(g, Ho, Wo, px, pw, k);
+    const bool flow_ok = decrypts_to(fx, flow.second, want);
+    auto zero = cs.encrypt(pk, cs.make_plaintext(0));
+    Owned<CT> term = cs.conv2d_ciphertext_filters_tensors(pk, px, cw, stride, pad, dilation, &zero);
+    const bool term_ok = term->shape() == oshape && decrypts_to(fx, term, want);
+    write_bytes("local_bench_cconv_img.bin", cs.serialize_plaintext_tensor(px));
+    write_bytes("local_bench_cconv_w.bin", cs.serialize_plaintext_tensor(pw));
+    write_ciphertexts(fx, "local_bench_cconv_image_cts.bin", cx);
+    write_ciphertexts(fx, "local_bench_cconv_filters.bin", cw);
+    write_ciphertext(fx, "local_bench_cconv_zero.bin", zero);
+    write_ciphertexts(fx, "local_bench_cconv_term.bin", term);
+    write_ciphertexts(fx, "local_bench_cconv_out.bin", flow.second);
+    write_absdelta(fx);
+    std::cout << "  conv flow: decrypted_elements " << opened << ", " << flow.first << " ms: " << (flow_ok ? "ok" : "FAILED") << std::endl;
+    std::cout << "  the same layer would open 2 n m p = " << 2 * n * m * p << " values with element triplets, n m + m p = " << n * m + m * p
+              << " with a matrix triplet on the patch matrix" << std::endl;
+    std::cout << "  plaintext image under the encrypted filters (E * [Bf] alone, from a fixed Enc(0)): " << (term_ok ? "ok" : "FAILED") << std::endl;
+    std::cout << "  (host wall clock, triplet generation and decryptions included; " << client_label(t, parties) << ")" << std::endl;
+    bool ok = flow_ok && term_ok && opened == px->num_elements() + pw->num_elements();
+    if (runs > 0) {
+        // the flow phase by phase on the same inputs, spelled as conv2d_ciphertext_tensors spells it, and the whole call; a warm-up
+        // pass and `runs` timed ones, medians and extremes on one line
+        enum { TRIPLET, OPEN, E_BF, A_D, E_D, TOTAL, PHASES };
+        std::vector<double> ms[PHASES];
+        for (int pass = 0; pass <= runs; pass++) {
+            double at[PHASES];
+            cs.synchronize();
+            auto trip = timed(cs, [&] { return client->get_beavers_conv2d_triplet(px->shape(), pw->shape(), stride, pad, dilation); });
+            Owned<CT> a(trip.second[0]), bf(trip.second[1]), c(trip.second[2]);
+            at[TRIPLET] = trip.first;
+            auto open = timed(cs, [&] {
+                Owned<CT> xa = cs.sub_ciphertext_tensors(pk, cx, a), wb = cs.sub_ciphertext_tensors(pk, cw, bf);
+                Owned<PT> e = client->decrypt_tensor(xa);
+                return std::make_pair(std::move(e), Owned<PT>(client->decrypt_tensor(wb)));
+            });
+            at[OPEN] = open.first;
+            const Owned<PT> &e = open.second.first, &d = open.second.second;
+            auto e_bf = timed(cs, [&]() -> Owned<CT> { return cs.conv2d_ciphertext_filters_tensors(pk, e, bf, stride, pad, dilation); });
+            at[E_BF] = e_bf.first;
+            auto a_d = timed(cs, [&]() -> Owned<CT> { return cs.conv2d_plaintext_ciphertext_tensors(pk, d, a, stride, pad, dilation, 1); });
+            at[A_D] = a_d.first;
+            auto e_d = timed(cs, [&]() -> Owned<PT> { return cs.conv2d_plaintext_tensors(e, d, stride, pad, dilation); });
+            at[E_D] = e_d.first;
+            auto whole = timed(cs, [&]() -> Owned<CT> { return mul.conv2d_ciphertext_tensors(cx, cw, stride, pad, dilation); });
+            at[TOTAL] = whole.first;
+            if (!decrypts_to(fx, whole.second, want)) ok = false;
+            if (pass)
+                for (int ph = 0; ph < PHASES; ph++) ms[ph].push_back(at[ph]);
+        }
+        for (auto &v : ms) std::sort(v.begin(), v.end());
+        std::cout << "conv2d_ciphertext_json: {\"image\": [" << g.B << ", " << g.H << ", " << g.W << ", " << g.C << "], \"filters\": [" << g.kh << ", " << g.kw
+                  << ", " << g.C << ", " << g.Co << "], \"out\": [" << Ho << ", " << Wo << "], \"runs\": " << runs << ", \"opened\": " << opened << ", "
+                  << MsJson{"triplet_ms", "triplet_ms_min_max", ms[TRIPLET]} << ", " << MsJson{"open_ms", "open_ms_min_max", ms[OPEN]} << ", "
+                  << MsJson{"e_bf_ms", "e_bf_ms_min_max", ms[E_BF]} << ", " << MsJson{"a_d_ms", "a_d_ms_min_max", ms[A_D]} << ", "
+                  << MsJson{"e_d_ms", "e_d_ms_min_max", ms[E_D]} << ", " << MsJson{"total_ms", "total_ms_min_max", ms[TOTAL]} << "}" << std::endl;
+    }
+    std::cout << "  agree: " << (ok ? "yes" : "NO") << std::endl;
+    std::cout << "image: " << g.B << "x" << g.H << "x" << g.W << "x" << g.C << " filters: " << g.kh << "x" << g.kw << "x" << g.C << "x" << g.Co
+              << " stride: " << g.sh << "," << g.sw << " pad: " << g.ph << "," << g.pw << " dilation: " << g.dh << "," << g.dw << " out: " << Ho << "x" << Wo
+              << std::endl;
+    if (!ok) throw std::runtime_error("ciphertext convolution mismatch");
+}
+
 // text formats of single values and the binary plaintext-tensor format (cpu_cryptosystem.inl:124-318): written to
 // files for the parity checker, and read back
 static void bench_formats(const Args &) {
@@ -1534,6 +1636,7 @@ static const struct Mode {
     {"conv2d", "[B=1 H=6 W=6 C=2 kh=3 kw=3 Co=2 [sh=1 sw=1 ph=kh/2 pw=kw/2]]", bench_conv2d},
     {"conv2d_grouped", "[B=1 H=6 W=6 C=4 kh=3 kw=3 Co=4 groups=4 [dh=1 dw=1 sh=1 sw=1 ph=(kh-1)*dh/2 pw=(kw-1)*dw/2]]", bench_conv2d_grouped},
     {"sum_pool2d", "[B=1 H=6 W=6 C=2 kh=2 kw=2 [sh=kh sw=kw ph=0 pw=0]]", bench_sum_pool2d},
+    {"conv2d_ciphertext", "[B=1 H=5 W=4 C=2 kh=3 kw=2 Co=2 [sh=1 sw=1 ph=0 pw=0 dh=1 dw=1 [t=0 parties=3 [runs=0]]]]", bench_conv2d_ciphertext},
     {"poly_activation", "[elements=64 [runs=0]]", bench_poly_activation},
     {"divide", "[elements=64 [runs=0]]", bench_divide},
     {"lookup", "[elements=64 [runs=0]]", bench_lookup},

@@ -23,6 +23,11 @@
 // which opens n m + m p values, and spends a plaintext-left product (matmul_plaintext_ciphertext_tensors), a ciphertext-left
 // product (scal_ciphertext_tensors) and a plaintext matrix product mod 2^k (matmul_plaintext_tensors).
 //
+// Convolution triplets (conv2d_ciphertext_tensors: an encrypted image under encrypted filters; the reference has no convolution).
+// Convolution is bilinear, so the identity above holds with * for the product:  [A] image-shaped, [Bf] filter-shaped,
+// [C] = [A * Bf];  E = Dec(X - A), D = Dec(Wf - Bf);  X * Wf = E * [Bf] + [A] * D + [C] + E * D -- B H W C + kh kw C Co opened
+// values, every pixel once, where a matrix triplet on the patch matrix opens each pixel kh kw times.
+//
 // Polynomials (evaluate_polynomial_ciphertext_tensor, square_ciphertext_tensor; the reference has no such flow).  A degree-d
 // polynomial with plaintext coefficients by chained products opens 2 (d - 1) values per element in d - 1 rounds.  With a power
 // tuple ([a], .., [a^d]) per element:  e = Dec(x - a);  [p(x)] = prod_i [a^i]^(q_i(e)) o f^(q_0(e)),  q the Taylor shift of p at
@@ -110,6 +115,25 @@ class LocalSMPCClient {
         for (size_t i = 0; i < n * m; i++) delete pa[i];
         for (size_t i = 0; i < m * p; i++) delete pb[i];
         for (size_t i = 0; i < n * p; i++) delete pc[i];
+        return t;
+    }
+
+    // one convolution triplet: {[A] (image_shape [B, H, W, C]), [Bf] (filter_shape [kh, kw, C, Co]), [C] = [A * Bf mod 2^k]
+    // ([B, Ho, Wo, Co])} for the geometry given, A and Bf uniform in Z/2^k; the caller owns the elements and uses the triplet once
+    Vector<Tensor<CipherText *>> get_beavers_conv2d_triplet(const std::vector<size_t> &image_shape, const std::vector<size_t> &filter_shape,
+                                                            const std::array<size_t, 2> &stride, const std::array<size_t, 2> &pad,
+                                                            const std::array<size_t, 2> &dilation) {
+        Tensor<PlainText *> pa(image_shape, nullptr), pb(filter_shape, nullptr);
+        for (size_t i = 0; i < pa.num_elements(); i++) pa[i] = new PlainText(cs_.random_plaintext(cs_.message_bits()));
+        for (size_t i = 0; i < pb.num_elements(); i++) pb[i] = new PlainText(cs_.random_plaintext(cs_.message_bits()));
+        auto pc = cs_.conv2d_plaintext_tensors(pa, pb, stride, pad, dilation);
+        Vector<Tensor<CipherText *>> t;
+        t.push_back(cs_.encrypt_tensor(pk_, pa));
+        t.push_back(cs_.encrypt_tensor(pk_, pb));
+        t.push_back(cs_.encrypt_tensor(pk_, pc));
+        for (size_t i = 0; i < pa.num_elements(); i++) delete pa[i];
+        for (size_t i = 0; i < pb.num_elements(); i++) delete pb[i];
+        for (size_t i = 0; i < pc.num_elements(); i++) delete pc[i];
         return t;
     }
 
@@ -269,6 +293,51 @@ class LocalCipherTextMultiplier {
             return res;
         }
         throw std::runtime_error("Not implemented");
+    }
+
+    // 2-D convolution of a ciphertext image x [B, H, W, C] with CIPHERTEXT filters w [kh, kw, C, Co], channels last, groups = 1:
+    // one convolution triplet {[A], [Bf], [C] = [A * Bf]} and, convolution being bilinear, matrix_mul_triplet step for step:
+    //   E = Dec(x - A), D = Dec(w - Bf);  [x * w] = (E * [Bf]) o ([A] * D) o [C] o f^(E * D)
+    // which opens B H W C + kh kw C Co values, where the matrix triplet on the patch matrix opens n m + m p (every pixel kh kw
+    // times, and the padding as encryptions of zero).  A batch B shares the one [Bf] and the one opened D: that is how many
+    // images under the same private filters are meant to be run.  The reference has no convolution.
+    Tensor<CipherText *> conv2d_ciphertext_tensors(const Tensor<CipherText *> &x, const Tensor<CipherText *> &w, const std::array<size_t, 2> &stride = {1, 1},
+                                                   const std::array<size_t, 2> &pad = {0, 0}, const std::array<size_t, 2> &dilation = {1, 1}) {
+        if (x.ndim() != 4 || w.ndim() != 4) throw std::invalid_argument("conv2d_ciphertext_tensors: both operands must be 4D");
+        if (w.shape()[2] != x.shape()[3]) throw std::invalid_argument("conv2d_ciphertext_tensors: the channels of the filters and of the image differ");
+        auto &cs = client_m.crypto_system();
+        const auto &pk = client_m.network_public_key();
+        auto triplet = client_m.get_beavers_conv2d_triplet(x.shape(), w.shape(), stride, pad, dilation);
+        auto &a_tensor = triplet[0], &b_tensor = triplet[1], &c_tensor = triplet[2];
+        auto x_sub_a = cs.sub_ciphertext_tensors(pk, x, a_tensor);
+        auto w_sub_b = cs.sub_ciphertext_tensors(pk, w, b_tensor);
+        auto e = client_m.decrypt_tensor(x_sub_a);
+        auto d = client_m.decrypt_tensor(w_sub_b);
+        auto e_b = cs.conv2d_ciphertext_filters_tensors(pk, e, b_tensor, stride, pad, dilation);
+        auto a_d = cs.conv2d_plaintext_ciphertext_tensors(pk, d, a_tensor, stride, pad, dilation, 1);
+        auto s1 = cs.add_ciphertext_tensors(pk, e_b, a_d);
+        auto s2 = cs.add_ciphertext_tensors(pk, s1, c_tensor);
+        auto e_d = cs.conv2d_plaintext_tensors(e, d, stride, pad, dilation);
+        auto ct = cs.add_plaintext_tensor(pk, s2, e_d);
+        for (size_t i = 0; i < x.num_elements(); i++) {
+            delete a_tensor[i];
+            delete x_sub_a[i];
+            delete e[i];
+        }
+        for (size_t i = 0; i < w.num_elements(); i++) {
+            delete b_tensor[i];
+            delete w_sub_b[i];
+            delete d[i];
+        }
+        for (size_t i = 0; i < ct.num_elements(); i++) {
+            delete c_tensor[i];
+            delete e_b[i];
+            delete a_d[i];
+            delete s1[i];
+            delete s2[i];
+            delete e_d[i];
+        }
+        return ct;
     }
 
     // p(x) element-wise for p = sum_j coef[j] X^j with plaintext coefficients (d + 1 of them, 1 <= d <= 8), over the integers

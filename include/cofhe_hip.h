@@ -19,6 +19,8 @@
  *                                    are a patch matrix built by the caller and the 2-D branch above
  *   cofhe_hip_conv2d_grouped_...,    nothing: the same with dilation and groups (depthwise filters, per-channel scales), and sum
  *   cofhe_hip_sum_pool2d_...         pooling as the depthwise convolution with filters of ones
+ *   cofhe_hip_conv2d_ct_filters_..., nothing: ciphertext filters over an opened image and the plaintext convolution mod 2^k, the
+ *   cofhe_hip_conv2d_plain_plain_... E * [Bf] and E * D terms of a convolution Beaver triplet
  *   cofhe_hip_pow_dot_records,       nothing: a polynomial with plaintext coefficients on a ciphertext tensor from ONE opened
  *   cofhe_hip_poly_shift_records,    value per element (power tuples); ComputeOperation's POLYNOMIAL_EVALUATION is commented out
  *   cofhe_hip_poly_close_...         (include/node/compute_request_handler.hpp:74)
@@ -205,8 +207,9 @@ int cofhe_hip_matmul_plain_ct_records(cofhe_hip_ctx *ctx, const void *d_s, const
  * COFHE_HIP_EINVAL, nothing written: a stride of 0; ph >= kh or pw >= kw; kh > H + 2 ph or kw > W + 2 pw; m >= 2^21; B H W C
  * above 2^31 - 1, n above 2^32 - 1, n m above 2^40 or 2 n p records beyond the launch limit; d_out overlapping d_w, d_cts or
  * d_zero.  B Ho Wo Co == 0: nothing to do.  NOT purely stream-ordered: as cofhe_hip_scal_matmul_records, the call synchronises
- * `stream` once or twice.  Dilation and groups / depthwise filters: cofhe_hip_conv2d_grouped_plain_ct_records below.  Not
- * covered: ciphertext filters, and a per-channel bias, which is cofhe_hip_add_plain_records on the result. */
+ * `stream` once or twice.  Dilation and groups / depthwise filters: cofhe_hip_conv2d_grouped_plain_ct_records below;
+ * ciphertext filters: cofhe_hip_conv2d_ct_filters_records.  Not covered: a per-channel bias, which is
+ * cofhe_hip_add_plain_records on the result. */
 typedef struct {
     uint32_t B, H, W, C;       /* image */
     uint32_t kh, kw, Co;       /* filters: kh x kw x C x Co */
@@ -256,6 +259,41 @@ int cofhe_hip_sum_pool2d_records(cofhe_hip_ctx *ctx, const void *d_cts, const vo
  * inputs.  The E D term of a matrix Beaver triplet, and the C = A B of its generation. */
 int cofhe_hip_matmul_plain_plain_records(cofhe_hip_ctx *ctx, const void *d_a, const void *d_b, void *d_out, uint32_t n, uint32_t m,
                                          uint32_t p, uint32_t kbits, void *stream);
+/* ---- convolution with CIPHERTEXT filters from one convolution Beaver triplet (cofhe_amd/csrc/plain_conv.hpp) ----
+ * Convolution is bilinear, so the matrix-triplet identity carries over: with a triplet [A] (image-shaped), [Bf] (filter-shaped),
+ * [C] = [A * Bf mod 2^k] (output-shaped) and the opened E = Dec(X - A), D = Dec(Wf - Bf),
+ *   [X * Wf] = (E * [Bf]) o ([A] * D) o [C] o f^(E * D),
+ * which opens B H W C + kh kw C Co values where a matrix triplet on the patch matrix opens n m + m p (every pixel kh kw times) and
+ * element triplets 2 n m p.  [A] * D is cofhe_hip_conv2d_grouped_plain_ct_records; the two entry points below are E * D (also the
+ * C = A * Bf of the triplet's generation) and E * [Bf].  groups = 1 only: with groups the patch matrix differs per column group.
+ * The geometry is cofhe_hip_conv2d_geometry's: channels last, strides, zero padding, dilation.
+ *
+ * out[b,oy,ox,co] = sum_{dy,dx,ci} img[b, oy sh + dy dh - ph, ox sw + dx dw - pw, ci] w[dy,dx,ci,co] mod 2^kbits on exponent
+ * records: image d_img [B, H, W, C], filters d_w [kh, kw, C, Co], output d_out [B, Ho, Wo, Co], terms outside the image left out.
+ * An implicit GEMM on the tile of cofhe_hip_matmul_plain_plain_records with the same residue rules (sign word honoured,
+ * magnitudes of 2^k and above reduced, outputs in [0, 2^k) with sign word 0, every word of every output record written); no
+ * patch matrix is written.  One launch ("k_plain_conv2d"), purely stream-ordered: no workspace, no read-back.
+ * COFHE_HIP_EINVAL, nothing written, checked before the context or a pointer is looked at: every refusal of
+ * cofhe_hip_conv2d_geometry_out_shape; groups != 1; kbits outside 1..639; d_out overlapping d_img or d_w; Co above 16 * 65535.
+ * B Ho Wo Co == 0: nothing to do. */
+int cofhe_hip_conv2d_plain_plain_records(cofhe_hip_ctx *ctx, const void *d_img, const void *d_w, void *d_out,
+                                         const cofhe_hip_conv2d_geometry *geometry, uint32_t kbits, void *stream);
+/* out[b,oy,ox,co] = zero o prod_{dy,dx,ci} filters[dy,dx,ci,co] ^ img[b, oy sh + dy dh - ph, ox sw + dx dw - pw, ci]: a PLAINTEXT
+ * image d_img_exps [B, H, W, C] (exponent records) under CIPHERTEXT filters d_filters_cts [kh, kw, C, Co], output d_out
+ * [B, Ho, Wo, Co] ciphertexts, zero 1 ct.  Read as matrices this is cofhe_hip_matmul_plain_ct_records with the n x m patch matrix
+ * of the image on the left (n = B Ho Wo, m = kh kw C) and the filters as its m x p ciphertext matrix (p = Co).  The patch matrix is
+ * written once, already transposed and with the zero exponent in the padding ("k_gather_patch_exponents"), into the block that
+ * product would transpose its left operand into -- one pass over n m exponent records less than that call on a pre-gathered
+ * patch matrix, and the same bytes.  Everything else is inherited from cofhe_hip_scal_matmul_records on the shape (p, m, n): the
+ * routes, the width choice, the options and the one or two synchronisations of `stream` (NOT purely stream-ordered); a
+ * filter's table of odd powers is built once and serves all n output positions, and zero exponents cost nothing, so padding is
+ * free.  The temporaries (n m exponent records, 2 m p and 2 n p form records) come from the context's block cache and go back
+ * behind the work queued on `stream`.  A batch B shares the one filter tensor.
+ * COFHE_HIP_EINVAL, nothing written, checked before the context or a pointer is looked at: every refusal of
+ * cofhe_hip_conv2d_geometry_out_shape; groups != 1; d_out overlapping d_img_exps, d_filters_cts or d_zero.
+ * B Ho Wo Co == 0: nothing to do. */
+int cofhe_hip_conv2d_ct_filters_records(cofhe_hip_ctx *ctx, const void *d_img_exps, const void *d_filters_cts, const void *d_zero,
+                                        void *d_out, const cofhe_hip_conv2d_geometry *geometry, void *stream);
 /* ---- polynomial evaluation from one opened value (cofhe_amd/csrc/pow_dot.hip) ----
  * p(X) = sum_{j<=d} c_j X^j with plaintext coefficients on a ciphertext [x], over the integers mod 2^k.  A POWER TUPLE of an
  * element is ([a], [a^2], .., [a^d]) with a uniform in Z/2^k, used once.  With the ONE opened value e = Dec(x - a), x = a + e and
@@ -611,6 +649,9 @@ int cofhe_hip_conv2d_plain_ct_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *w
 int cofhe_hip_conv2d_grouped_plain_ct_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *w, size_t lw, const uint8_t *cts, size_t lc,
                                                     const uint8_t *zero, size_t lz, uint32_t sh, uint32_t sw, uint32_t ph, uint32_t pw,
                                                     uint32_t dh, uint32_t dw, uint32_t groups, uint8_t **out, size_t *outlen);
+/* cofhe_hip_conv2d_ct_filters_records has no serialised twin here: on serialised tensors it is composed from
+ * cofhe_hip_unpack_tensor_device (which validates the incoming forms), the records entry and cofhe_hip_pack_tensor_device, as the
+ * lookups' and the splines' closing steps are (cofhe_amd/engine.py: Engine.conv2d_ct_filters_tensors). */
 /* the serialised twin of cofhe_hip_sum_pool2d_records over kh x kw windows: cts [B, H, W, C] -> [B, Ho, Wo, C] */
 int cofhe_hip_sum_pool2d_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *cts, size_t lc, const uint8_t *zero, size_t lz, uint32_t kh,
                                        uint32_t kw, uint32_t sh, uint32_t sw, uint32_t ph, uint32_t pw, uint8_t **out, size_t *outlen);
