@@ -2,10 +2,11 @@
 // two-build launch, flag words, the table-cache lookup), the workspace plans, the launchers (one launch site per kernel and
 // route; product_tree is the pairwise tree of them all) and the host-side tensor formats.  The kernels are declared in
 // kernels.hpp and defined in cofhe_hip.hip, wide.hip, comb.hip, affine.hip, matmul_left.hip, conv.hip, conv_ct.hip, pow_dot.hip,
-// divide.hip, lut.hip and spline.hip; this file holds no device code of its own.  conv.hip holds the three kernels of the
+// divide.hip, lut.hip, spline.hip and view.hip; this file holds no device code of its own.  conv.hip holds the three kernels of the
 // convolution, conv_ct.hip the two that ciphertext filters add, pow_dot.hip the two of
 // the polynomial evaluation, divide.hip the signed floor division of the division by public divisors, lut.hip the two copies of
-// the table lookups, spline.hip the three kernels of the piecewise-polynomial activations.
+// the table lookups, spline.hip the three kernels of the piecewise-polynomial activations, view.hip the two that rearrange
+// resident tensors.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -25,6 +26,7 @@
 #include "plain_div.hpp"
 #include "lut.hpp"
 #include "spline.hpp"
+#include "view.hpp"
 
 using namespace cofhe;
 using namespace cofhe_k;
@@ -63,6 +65,7 @@ struct CombState {
     uint64_t opt_chunk = 0;                      // "comb_chunk": 0 = the launcher decides
     uint32_t opt_conv_route = 0;                 // "conv_route": 0 = the launcher decides, 1 direct wherever it does not decline, 2 gather
     uint32_t opt_conv_chunk_rows = 0;            // "conv_chunk_rows": 0 = the launcher decides, else rows per chunk of the direct route
+    uint32_t opt_view_grid_blocks = 0;           // "view_grid_blocks": 0 = the launcher decides, else the grid of k_view_records and k_gather_records
 };
 std::mutex g_comb_mu;
 std::unordered_map<const cofhe_hip_ctx *, CombState *> g_comb;
@@ -277,6 +280,9 @@ int cofhe_hip_ctx_set_option(cofhe_hip_ctx *ctx, const char *name, int64_t value
     } else if (n == "conv_chunk_rows") {
         if (value < 0 || value > 0xFFFFFFFFll) return fail(COFHE_HIP_EINVAL, "conv_chunk_rows: 0 (automatic) or a positive count");
         comb_state(ctx).opt_conv_chunk_rows = (uint32_t)value;
+    } else if (n == "view_grid_blocks") {
+        if (value < 0 || value > (1 << 20)) return fail(COFHE_HIP_EINVAL, "view_grid_blocks: 0 (automatic) or a workgroup count up to 2^20");
+        comb_state(ctx).opt_view_grid_blocks = (uint32_t)value;
     } else {
         return fail(COFHE_HIP_EINVAL, "unknown option: " + n);
     }
@@ -1927,6 +1933,183 @@ int cofhe_hip_lut_tuples_shape_bits(uint32_t ndim_e, const uint32_t *shape_e, ui
     if (ndim_e > 7 || ndim_t != ndim_e + 1 || (ndim_e && memcmp(shape_t, shape_e, 4 * ndim_e) != 0) || b == 0 || b > LUT_MAX_BITS)
         return fail(COFHE_HIP_ESHAPE, "lut_select: the tuples are a ciphertext tensor of e's shape and a last dimension of 2^bits, 1 <= bits <= 12");
     *bits = b;
+    return COFHE_HIP_OK;
+}
+
+// ---- rearranging resident tensors: affine views and index gathers (view.hip, view.hpp) --------------------------------------
+namespace {
+// a descriptor of a dense row-major source of shape[ndim] with nothing mapped yet, and its closing step: the box is the whole
+// destination
+int view_begin(const uint64_t *shape, uint32_t ndim, cofhe_hip_view *v) {
+    if (!v || (ndim && !shape)) return fail(COFHE_HIP_EINVAL, "null argument");
+    if (ndim > (uint32_t)VIEW_MAX_DIMS) return fail(COFHE_HIP_EINVAL, "view: more than 8 axes");
+    memset(v, 0, sizeof *v);
+    v->src_ndim = ndim;
+    for (uint32_t a = 0; a < ndim; a++) v->src_extent[a] = shape[a];
+    return COFHE_HIP_OK;
+}
+int view_end(cofhe_hip_view *v) {
+    for (uint32_t d = 0; d < v->out_ndim; d++) {
+        v->dst_extent[d] = v->out_extent[d];
+        v->dst_start[d] = 0;
+    }
+    if (const char *why = view_check(*v, nullptr, nullptr, nullptr, nullptr)) return fail(COFHE_HIP_EINVAL, why);
+    return COFHE_HIP_OK;
+}
+// the grid of the two kernels for n records of `pieces` pieces: as many workgroups as one pass needs, 64 per CU at the most (the
+// kernels stride beyond that), or the pin of "view_grid_blocks"
+unsigned view_blocks(const cofhe_hip_ctx *ctx, uint64_t n, uint32_t pieces) {
+    if (const uint32_t pin = comb_state(ctx).opt_view_grid_blocks) return pin;
+    const uint64_t per = pieces >= 64u ? VIEW_WAVES : VIEW_THREADS / VIEW_GROUP;
+    return (unsigned)std::min<uint64_t>((n + per - 1) / per, 64u * NUM_CUS);
+}
+}  // namespace
+
+int cofhe_hip_view_check(const cofhe_hip_view *view, uint64_t *n_src, uint64_t *n_box, uint64_t *n_dst, int *needs_fill) {
+    if (!view) return fail(COFHE_HIP_EINVAL, "null argument");
+    if (const char *why = view_check(*view, n_src, n_box, n_dst, needs_fill)) return fail(COFHE_HIP_EINVAL, why);
+    return COFHE_HIP_OK;
+}
+int cofhe_hip_view_permute(const uint64_t *shape, uint32_t ndim, const uint32_t *perm, cofhe_hip_view *view) {
+    if (int rc = view_begin(shape, ndim, view)) return rc;
+    if (ndim && !perm) return fail(COFHE_HIP_EINVAL, "null argument");
+    uint32_t seen = 0;
+    view->out_ndim = ndim;
+    for (uint32_t d = 0; d < ndim; d++) {
+        if (perm[d] >= ndim || (seen >> perm[d] & 1u)) return fail(COFHE_HIP_EINVAL, "view_permute: not a permutation of the axes");
+        seen |= 1u << perm[d];
+        view->out_extent[d] = shape[perm[d]];
+        view->map[perm[d]][d] = 1;
+    }
+    return view_end(view);
+}
+int cofhe_hip_view_slice(const uint64_t *shape, uint32_t ndim, const int64_t *start, const int64_t *stop, const int64_t *step,
+                         cofhe_hip_view *view) {
+    if (int rc = view_begin(shape, ndim, view)) return rc;
+    if (ndim && (!start || !stop || !step)) return fail(COFHE_HIP_EINVAL, "null argument");
+    view->out_ndim = ndim;
+    for (uint32_t d = 0; d < ndim; d++) {
+        if (shape[d] > (1ull << 62)) return fail(COFHE_HIP_EINVAL, "view_slice: extent out of range");
+        const int64_t n = (int64_t)shape[d], a = start[d], b = stop[d], s = step[d];
+        if (s == 0 || s > INT32_MAX || s < -INT32_MAX) return fail(COFHE_HIP_EINVAL, "view_slice: a step is 0 or beyond 31 bits");
+        const bool ok = s > 0 ? (a >= 0 && a <= n && b >= 0 && b <= n) : (b >= -1 && b <= n - 1 && a >= -1 && a <= n - 1);
+        if (!ok) return fail(COFHE_HIP_EINVAL, "view_slice: a bound lies outside its axis");
+        const uint64_t span = s > 0 ? (b > a ? (uint64_t)(b - a) : 0) : (a > b ? (uint64_t)(a - b) : 0), mag = (uint64_t)(s > 0 ? s : -s);
+        view->out_extent[d] = (span + mag - 1) / mag;
+        view->start[d] = a;
+        view->map[d][d] = (int32_t)s;
+    }
+    return view_end(view);
+}
+int cofhe_hip_view_pad(const uint64_t *shape, uint32_t ndim, const uint64_t *lo, const uint64_t *hi, cofhe_hip_view *view) {
+    if (int rc = view_begin(shape, ndim, view)) return rc;
+    if (ndim && (!lo || !hi)) return fail(COFHE_HIP_EINVAL, "null argument");
+    view->out_ndim = ndim;
+    for (uint32_t d = 0; d < ndim; d++) {
+        if (shape[d] > (1ull << 48) || lo[d] > (1ull << 48) || hi[d] > (1ull << 48)) return fail(COFHE_HIP_EINVAL, "view_pad: extent out of range");
+        view->out_extent[d] = lo[d] + shape[d] + hi[d];
+        view->start[d] = -(int64_t)lo[d];
+        view->map[d][d] = 1;
+    }
+    return view_end(view);
+}
+int cofhe_hip_view_broadcast(const uint64_t *shape, uint32_t ndim, const uint64_t *out_shape, uint32_t out_ndim, cofhe_hip_view *view) {
+    if (int rc = view_begin(shape, ndim, view)) return rc;
+    if (out_ndim && !out_shape) return fail(COFHE_HIP_EINVAL, "null argument");
+    if (out_ndim > (uint32_t)VIEW_MAX_DIMS || out_ndim < ndim) return fail(COFHE_HIP_EINVAL, "view_broadcast: the output has fewer axes than the source, or more than 8");
+    view->out_ndim = out_ndim;
+    for (uint32_t d = 0; d < out_ndim; d++) view->out_extent[d] = out_shape[d];
+    for (uint32_t a = 0; a < ndim; a++) {
+        const uint32_t d = out_ndim - ndim + a;
+        if (shape[a] == out_shape[d])
+            view->map[a][d] = 1;
+        else if (shape[a] != 1)
+            return fail(COFHE_HIP_EINVAL, "view_broadcast: a source extent is neither 1 nor the output's");
+    }
+    return view_end(view);
+}
+int cofhe_hip_view_window_taps(const cofhe_hip_conv2d_geometry *geometry, cofhe_hip_view *view) {
+    if (!geometry || !view) return fail(COFHE_HIP_EINVAL, "null argument");
+    ConvShape s = pool_shape_of(*geometry);
+    if (const char *why = conv_shape_check(s)) return fail(COFHE_HIP_EINVAL, why);
+    if ((s.sh | s.sw | s.dh | s.dw) > (uint32_t)INT32_MAX) return fail(COFHE_HIP_EINVAL, "view_window_taps: a stride or a dilation beyond 31 bits");
+    const uint64_t shape[4] = {s.B, s.H, s.W, s.C};
+    if (int rc = view_begin(shape, 4, view)) return rc;
+    const uint64_t out[6] = {s.kh, s.kw, s.B, s.Ho, s.Wo, s.C};
+    view->out_ndim = 6;
+    for (int d = 0; d < 6; d++) view->out_extent[d] = out[d];
+    view->map[0][2] = 1;                         // b
+    view->map[1][0] = (int32_t)s.dh;             // y = oy sh + dy dh - ph
+    view->map[1][3] = (int32_t)s.sh;
+    view->start[1] = -(int64_t)s.ph;
+    view->map[2][1] = (int32_t)s.dw;             // x = ox sw + dx dw - pw
+    view->map[2][4] = (int32_t)s.sw;
+    view->start[2] = -(int64_t)s.pw;
+    view->map[3][5] = 1;                         // c
+    return view_end(view);
+}
+int cofhe_hip_view_into(cofhe_hip_view *view, const uint64_t *dst_shape, const uint64_t *dst_start) {
+    if (!view) return fail(COFHE_HIP_EINVAL, "null argument");
+    if (view->out_ndim > (uint32_t)VIEW_MAX_DIMS) return fail(COFHE_HIP_EINVAL, "view: more than 8 axes");
+    if (view->out_ndim && (!dst_shape || !dst_start)) return fail(COFHE_HIP_EINVAL, "null argument");
+    cofhe_hip_view v = *view;
+    for (uint32_t d = 0; d < v.out_ndim; d++) {
+        v.dst_extent[d] = dst_shape[d];
+        v.dst_start[d] = dst_start[d];
+    }
+    if (const char *why = view_check(v, nullptr, nullptr, nullptr, nullptr)) return fail(COFHE_HIP_EINVAL, why);
+    *view = v;
+    return COFHE_HIP_OK;
+}
+
+// touches no shared state of the context but the option pin: no lock.  One launch; the descriptor travels as a kernel argument
+int cofhe_hip_view_records(cofhe_hip_ctx *ctx, const cofhe_hip_view *view, const void *d_src, const void *d_fill, void *d_dst, uint32_t words,
+                           void *stream) {
+    if (!ctx || !view) return fail(COFHE_HIP_EINVAL, "null argument");
+    uint64_t n_src = 0, n_box = 0, n_dst = 0;
+    int needs_fill = 0;
+    if (const char *why = view_check(*view, &n_src, &n_box, &n_dst, &needs_fill)) return fail(COFHE_HIP_EINVAL, why);
+    if (words == 0) return fail(COFHE_HIP_EINVAL, "view_records: a record of 0 words");
+    if (needs_fill && !d_fill) return fail(COFHE_HIP_EINVAL, "view_records: the view reads outside its source and there is no fill record");
+    if (n_box == 0) return COFHE_HIP_OK;
+    if (!d_dst || (n_src && !d_src)) return fail(COFHE_HIP_EINVAL, "null argument");
+    const size_t rec_bytes = (size_t)words * 4;
+    if (overlaps(d_dst, n_dst * rec_bytes, d_src, n_src * rec_bytes) || (d_fill && overlaps(d_dst, n_dst * rec_bytes, d_fill, rec_bytes)))
+        return fail(COFHE_HIP_EINVAL, "view_records: the destination overlaps the source or the fill record");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const bool vec16 = words % 4 == 0 && (((uintptr_t)d_src | (uintptr_t)d_fill | (uintptr_t)d_dst) & 15) == 0;
+    const unsigned blocks = view_blocks(ctx, n_box, vec16 ? words / 4 : words);
+    {
+        ProfScope ps(ctx, "k_view_records", st);
+        hipLaunchKernelGGL(k_view_records, dim3(blocks), dim3(VIEW_THREADS), 0, st, *view, (const uint32_t *)d_src, (const uint32_t *)d_fill,
+                           (uint32_t *)d_dst, words, vec16 ? 1u : 0u);
+    }
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+
+int cofhe_hip_gather_records(cofhe_hip_ctx *ctx, const void *d_src, uint64_t n_src, const void *d_index, const void *d_fill, void *d_dst,
+                             uint64_t n_out, uint32_t words, void *stream) {
+    if (!ctx) return fail(COFHE_HIP_EINVAL, "null argument");
+    if (words == 0) return fail(COFHE_HIP_EINVAL, "gather_records: a record of 0 words");
+    if (n_src > COFHE_HIP_GATHER_KEEP || n_out > VIEW_MAX_ELEMENTS) return fail(COFHE_HIP_EINVAL, "gather_records: too many records");
+    if (n_out == 0) return COFHE_HIP_OK;
+    if (!d_dst || !d_index || (n_src && !d_src)) return fail(COFHE_HIP_EINVAL, "null argument");
+    const size_t rec_bytes = (size_t)words * 4, out_bytes = n_out * rec_bytes;
+    if (overlaps(d_dst, out_bytes, d_src, n_src * rec_bytes) || overlaps(d_dst, out_bytes, d_index, n_out * 4) ||
+        (d_fill && overlaps(d_dst, out_bytes, d_fill, rec_bytes)))
+        return fail(COFHE_HIP_EINVAL, "gather_records: the destination overlaps the source, the indices or the fill record");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const bool vec16 = words % 4 == 0 && (((uintptr_t)d_src | (uintptr_t)d_fill | (uintptr_t)d_dst) & 15) == 0;
+    const unsigned blocks = view_blocks(ctx, n_out, vec16 ? words / 4 : words);
+    {
+        ProfScope ps(ctx, "k_gather_records", st);
+        hipLaunchKernelGGL(k_gather_records, dim3(blocks), dim3(VIEW_THREADS), 0, st, (const uint32_t *)d_src, n_src, (const uint32_t *)d_index,
+                           (const uint32_t *)d_fill, (uint32_t *)d_dst, n_out, words, vec16 ? 1u : 0u, ctx->d_status);
+    }
+    HIPCHK(hipGetLastError());
     return COFHE_HIP_OK;
 }
 

@@ -7,13 +7,14 @@
 // convolution and the patch gather of a plaintext image for ciphertext filters, pow_dot.hip the multi-exponentiation
 // and the Taylor shift of the polynomial evaluation, divide.hip the signed floor division on exponent records, lut.hip the row
 // rotation and the entry selection of the table lookups, spline.hip the rows, the powers and the closing walk of the
-// piecewise-polynomial activations.
+// piecewise-polynomial activations, view.hip the affine view and the index gather that rearrange resident tensors.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "comb.hpp"
 #include "conv.hpp"
+#include "view.hpp"
 
 namespace cofhe_k {
 
@@ -189,4 +190,14 @@ __global__ void k_spline_powers(const uint32_t *__restrict__ e, uint32_t *__rest
 __global__ void k_spline_close(const uint32_t *__restrict__ e, const uint32_t *__restrict__ powers, const uint32_t *__restrict__ tuples,
                                uint32_t *__restrict__ out, uint64_t n, uint32_t bits, uint32_t shift, uint32_t d, uint32_t kbits,
                                const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status);
+
+// rearranging resident tensors (view.hip; view.hpp): the box of an affine view, dst[view_dest(i)] = src[view_source(i)] or the fill
+// record, and the index gather dst[i] = src[index[i]] with its two sentinels (an index beyond the source: the fill record and
+// CF_ST_BAD_INDEX); records of `words` words, one wavefront per record of 64 pieces or more and eight lanes per shorter one;
+// vec16: src, fill and dst are 16-byte aligned and words is a multiple of 4
+__global__ void k_view_records(cofhe_hip_view v, const uint32_t *__restrict__ src, const uint32_t *__restrict__ fill, uint32_t *__restrict__ dst,
+                               uint32_t words, uint32_t vec16);
+__global__ void k_gather_records(const uint32_t *__restrict__ src, uint64_t n_src, const uint32_t *__restrict__ index,
+                                 const uint32_t *__restrict__ fill, uint32_t *__restrict__ dst, uint64_t n_out, uint32_t words, uint32_t vec16,
+                                 uint32_t *__restrict__ status);
 }  // namespace cofhe_k

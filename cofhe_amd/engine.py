@@ -563,6 +563,64 @@ class Engine:
         _chk(self.L.cofhe_hip_lut_select_records(self.ctx, C.c_void_p(d_e), C.c_void_p(d_tuples), C.c_void_p(d_out), C.c_uint64(n),
                                                  C.c_uint32(bits), C.c_void_p(stream)))
 
+    def view_records(self, view, d_src, d_fill, d_dst, words, stream=0):
+        """the box of an affine view (a View; module functions view_permute and kin build them) of records of `words` dwords:
+        dst[view_dest(i)] = src[view_source(i)], or the one record at d_fill (0: none, for a view that needs no fill) where the view
+        reads outside its source; the rest of the destination is not written.  A byte-for-byte copy: nothing is re-randomised."""
+        _chk(self.L.cofhe_hip_view_records(self.ctx, C.byref(view), C.c_void_p(d_src), C.c_void_p(d_fill), C.c_void_p(d_dst), C.c_uint32(words),
+                                           C.c_void_p(stream)))
+
+    def gather_records(self, d_src, n_src, d_index, d_fill, d_dst, n_out, words, stream=0):
+        """dst[i] = src[index[i]] for the n_out uint32 at d_index: GATHER_FILL writes the record at d_fill, GATHER_KEEP leaves dst[i]
+        alone, another index >= n_src writes the fill record (with d_fill 0: leaves dst[i] alone) and sets bit 32 of the status word"""
+        _chk(self.L.cofhe_hip_gather_records(self.ctx, C.c_void_p(d_src), C.c_uint64(n_src), C.c_void_p(d_index), C.c_void_p(d_fill),
+                                             C.c_void_p(d_dst), C.c_uint64(n_out), C.c_uint32(words), C.c_void_p(stream)))
+
+    def view_tensor_bytes(self, data: bytes, view, fill: bytes = None, kind: int = 2) -> bytes:
+        """a serialised tensor (kind 2 ciphertexts / 1 partial decryptions / 0 plaintexts) whose shape is the view's source ->
+        the serialised tensor of the view's destination shape; `fill`: a serialised one-element tensor of the same kind, for a
+        view that reads outside its source.  Composed here from unpack_tensor_device (which validates the incoming forms),
+        view_records and pack_tensor_device: the library has no entry point of its own for it.  The destination outside the
+        view's box is not written, so a view placed in a larger destination (view_into) is refused."""
+        per = {2: 2, 1: 1, 0: 1}[kind]                               # records per element
+        rec_words = REC_WORDS if kind else EXP_REC_WORDS
+        n_src, n_box, n_dst, needs_fill = view_check(view)
+        if n_box != n_dst:
+            raise CofheHipError(-1, "view_tensor_bytes: the view's box is not its whole destination")
+        held = []
+
+        def load(t):
+            cap = (len(t) // 8) // (3 if kind else 1) + 1
+            raw = self.malloc(len(t) + 4)
+            held.append(raw)
+            recs = self.malloc(cap * 4 * rec_words)
+            held.append(recs)
+            self.upload(raw, t)
+            shape, n = self.unpack_tensor_device(raw, len(t), kind, recs, cap)
+            return recs, shape, n
+
+        try:
+            dsrc, shape, n = load(data)
+            if list(shape) != [int(view.src_extent[a]) for a in range(view.src_ndim)] or n != per * n_src:
+                raise CofheHipError(-2, "view_tensor_bytes: the tensor's shape is not the view's source")
+            dfill = 0
+            if fill is not None:
+                dfill, _, nf = load(fill)
+                if nf != per:
+                    raise CofheHipError(-2, "view_tensor_bytes: the fill is a tensor of one element")
+            out_shape = [int(view.dst_extent[d]) for d in range(view.out_ndim)]
+            dout = self.malloc(max(n_dst, 1) * per * rec_words * 4)
+            held.append(dout)
+            self.view_records(view, dsrc, dfill, dout, per * rec_words)
+            cap = self.packed_size_bound(per * n_dst, kind, len(out_shape))
+            packed = self.malloc(cap)
+            held.append(packed)
+            ln = self.pack_tensor_device(dout, per * n_dst, kind, out_shape, packed, cap)
+            return self.download(packed, ln, dtype="uint8").tobytes()
+        finally:
+            for p in held:
+                self.free(p)
+
     def spline_rows_records(self, d_pieces, n_tab, d_r, d_out, n, bits, shift, d, kbits, stream=0):
         """the plaintext rows of n spline tuples on exponent records: out[(i 2^bits + j) (d + 1) + c] = coefficient c of the Taylor
         shift of piece (j + rho_i) mod 2^bits of table i mod n_tab at r_i minus the piece's origin, rho_i = bits shift .. shift + bits
@@ -758,7 +816,8 @@ class Engine:
         _chk(self.L.cofhe_hip_ctx_set_option(self.ctx, C.c_char_p(name.encode()), C.c_int64(value)))
 
     def device_status(self, clear=True, stream=0) -> int:
-        """status word of the kernels (bit 1: Euclid cap, 2: reduction cap, 4: division): 0 unless a record was not a form"""
+        """status word of the kernels (bit 1: Euclid cap, 2: reduction cap, 4: division; 32: gather_records met an index beyond
+        its source and wrote the fill record): 0 unless a record was not a form or an index was bad"""
         w = C.c_uint32()
         _chk(self.L.cofhe_hip_device_status(self.ctx, C.byref(w), C.c_int(1 if clear else 0), C.c_void_p(stream)))
         return w.value
@@ -842,6 +901,84 @@ def conv2d_out_shape(image, filters, stride=(1, 1), pad=(0, 0), dilation=(1, 1),
         geo = _conv_geometry(image, filters, stride, pad, dilation, groups)
         _chk(L.cofhe_hip_conv2d_geometry_out_shape(C.byref(geo), C.byref(ho), C.byref(wo)))
     return int(ho.value), int(wo.value)
+
+
+VIEW_MAX_DIMS = 8
+GATHER_FILL, GATHER_KEEP = 0xFFFFFFFF, 0xFFFFFFFE
+
+
+class View(C.Structure):
+    """cofhe_hip_view: the box out_extent of a dense row-major source src_extent, source coordinate c_a = start[a] + sum_d
+    map[a][d] o_d, placed at dst_start inside a dense row-major destination dst_extent (include/cofhe_hip.h)"""
+    _fields_ = [("out_ndim", C.c_uint32), ("src_ndim", C.c_uint32), ("out_extent", C.c_uint64 * 8), ("src_extent", C.c_uint64 * 8),
+                ("start", C.c_int64 * 8), ("map", (C.c_int32 * 8) * 8), ("dst_extent", C.c_uint64 * 8), ("dst_start", C.c_uint64 * 8)]
+
+    @property
+    def out_shape(self):
+        return [int(self.out_extent[d]) for d in range(self.out_ndim)]
+
+    @property
+    def dst_shape(self):
+        return [int(self.dst_extent[d]) for d in range(self.out_ndim)]
+
+
+def _u64s(values):
+    return (C.c_uint64 * max(1, len(values)))(*[int(x) for x in values])
+
+
+def _i64s(values):
+    return (C.c_int64 * max(1, len(values)))(*[int(x) for x in values])
+
+
+def view_check(view):
+    """cofhe_hip_view_check (host only): (n_src, n_box, n_dst, needs_fill); raises CofheHipError (COFHE_HIP_EINVAL) for more than 8
+    axes, a box outside its destination or a source coordinate that can leave 64 bits"""
+    ns, nb, nd, nf = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_int()
+    _chk(load_library().cofhe_hip_view_check(C.byref(view), C.byref(ns), C.byref(nb), C.byref(nd), C.byref(nf)))
+    return int(ns.value), int(nb.value), int(nd.value), bool(nf.value)
+
+
+def view_permute(shape, perm):
+    """output axis d is source axis perm[d] (numpy.transpose)"""
+    v = View()
+    _chk(load_library().cofhe_hip_view_permute(_u64s(shape), C.c_uint32(len(shape)), (C.c_uint32 * max(1, len(perm)))(*perm), C.byref(v)))
+    return v
+
+
+def view_slice(shape, start, stop, step):
+    """src[start:stop:step] per axis, bounds in range; with a negative step a stop of -1 means down to and including element 0"""
+    v = View()
+    _chk(load_library().cofhe_hip_view_slice(_u64s(shape), C.c_uint32(len(shape)), _i64s(start), _i64s(stop), _i64s(step), C.byref(v)))
+    return v
+
+
+def view_pad(shape, lo, hi):
+    v = View()
+    _chk(load_library().cofhe_hip_view_pad(_u64s(shape), C.c_uint32(len(shape)), _u64s(lo), _u64s(hi), C.byref(v)))
+    return v
+
+
+def view_broadcast(shape, out_shape):
+    """numpy's rule, right-aligned"""
+    v = View()
+    _chk(load_library().cofhe_hip_view_broadcast(_u64s(shape), C.c_uint32(len(shape)), _u64s(out_shape), C.c_uint32(len(out_shape)), C.byref(v)))
+    return v
+
+
+def view_window_taps(image, kernel, stride=(1, 1), pad=(0, 0), dilation=(1, 1)):
+    """[B, H, W, C] -> [kh, kw, B, Ho, Wo, C]: tap (dy, dx) of every window, the fill record in the padding"""
+    B, H, W, Cin = image
+    geo = _ConvGeometry(B, H, W, Cin, kernel[0], kernel[1], Cin, stride[0], stride[1], pad[0], pad[1], dilation[0], dilation[1], 1)
+    v = View()
+    _chk(load_library().cofhe_hip_view_window_taps(C.byref(geo), C.byref(v)))
+    return v
+
+
+def view_into(view, dst_shape, dst_start):
+    """the same view with its box at dst_start inside a destination of dst_shape (a new View)"""
+    v = View.from_buffer_copy(view)
+    _chk(load_library().cofhe_hip_view_into(C.byref(v), _u64s(dst_shape), _u64s(dst_start)))
+    return v
 
 
 COMB_POWERS, COMB_ENCRYPT, COMB_RERANDOMIZE = 0, 1, 2

@@ -103,6 +103,7 @@ struct DeviceBlock {
     void *dptr = nullptr;
     size_t n_ct = 0;
     std::vector<uint32_t> host;          // records, downloaded on demand
+    std::shared_ptr<std::atomic<uint64_t>> downloads;     // the cryptosystem's count of such downloads (block_downloads())
     std::once_flag fetched;
     std::mutex mat_mu;                   // serialises the lazy CipherText objects of THIS block (not of every block)
     DeviceBlock(std::shared_ptr<cofhe_hip_ctx> c, void *p, size_t n) : owner(std::move(c)), ctx(owner.get()), dptr(p), n_ct(n) {}
@@ -118,6 +119,7 @@ struct DeviceBlock {
     const uint32_t *records() {
         std::call_once(fetched, [this]() {              // never throws: an exception would leave the flag unset
             host.resize(n_ct * 2 * 168);
+            if (downloads) downloads->fetch_add(1, std::memory_order_relaxed);
             if (cofhe_hip_download(ctx, host.data(), dptr, host.size() * 4, nullptr) != COFHE_HIP_OK) {
                 poison = cofhe_hip_last_error();
                 if (poison.empty()) poison = "cofhe_hip: download failed";
@@ -135,8 +137,11 @@ struct DeviceBlock {
             return e.empty() ? std::string("cofhe_hip: status read failed") : e;
         }
         if (w == 0) return std::string();
+        if (w == 32u)          // CF_ST_BAD_INDEX alone
+            return "cofhe_hip: device status word 32 (an index gather met an index beyond its source and wrote the fill record; results discarded)";
         return "cofhe_hip: device status word " + std::to_string(w) +
-               " (a loop cap was hit: an operand was not a reduced form of this discriminant; results discarded)";
+               " (a loop cap was hit: an operand was not a reduced form of this discriminant; results discarded)" +
+               (w & 32u ? "; bit 32: an index gather met an index beyond its source" : "");
     }
     static void throw_on_device_status(cofhe_hip_ctx *ctx) {
         const std::string m = device_status_message(ctx);
@@ -299,7 +304,7 @@ class HIPCryptoSystem {
     HIPCryptoSystem(const HIPCryptoSystem &o)
         : sec_level_(o.sec_level_), k_(o.k_), device_(o.device_), N_(o.N_), deltaK_(o.deltaK_), delta_(o.delta_),
           f_(o.f_), h_(o.h_), f_rec_(o.f_rec_), h_rec_(o.h_rec_), exponent_bound_(o.exponent_bound_), rerandomize_(o.rerandomize_),
-          tensor_randomness_(o.tensor_randomness_) {
+          resident_gather_(o.resident_gather_), tensor_randomness_(o.tensor_randomness_) {
         gmp_randinit_mt(rng_);
         gmp_randseed_ui(rng_, std::random_device{}());     // a copy draws fresh randomness (hpp:37-40)
         open_device();
@@ -1107,11 +1112,54 @@ class HIPCryptoSystem {
                 return d;
             }
         }
+        if (resident_gather_ && E != 0) {
+            DeviceTensor d;
+            if (gather_resident(t, d)) return d;
+        }
         std::vector<uint32_t> recs(E * 2 * REC, 0);
         pack_forms(2 * E, recs.data(), [&](size_t i) -> const QFI & { const CipherText &e = *t[i >> 1]; return (i & 1) ? e.c2() : e.c1(); });
         DeviceTensor d = alloc(t.shape(), E);
         fill(d, recs);
         return d;
+    }
+    // The device route of upload(): a tensor that is no whole block, but whose elements are all non-null, not host-dirty and
+    // resident in this context, in at most 8 distinct blocks -- a column of a triplet block, a transposed or replicated result,
+    // the taps of a pooling window.  One index array per source block (COFHE_HIP_GATHER_KEEP at the elements of the others),
+    // staged, and one cofhe_hip_gather_records per block into the one result: no record crosses PCIe and no GMP object is
+    // made.  The bytes are those of the host path (set_resident_gather(false)).  The status word is sticky, so a failed
+    // computation in a source block is still reported when data next leaves the device.  False: not such a tensor.
+    void set_resident_gather(bool on) { resident_gather_ = on; }
+    bool resident_gather() const { return resident_gather_; }
+    // DeviceBlock record downloads (the whole-block transfer behind the first read of a lazy element, the host path of upload
+    // and of serialize) of this cryptosystem's blocks since construction
+    uint64_t block_downloads() const { return downloads_->load(std::memory_order_relaxed); }
+    bool gather_resident(const Tensor<CipherText *> &t, DeviceTensor &out) const {
+        constexpr size_t MAX_BLOCKS = 8;
+        const size_t E = t.num_elements();
+        std::shared_ptr<DeviceBlock> blocks[MAX_BLOCKS];
+        size_t nb = 0;
+        std::vector<uint32_t> which(E);
+        for (size_t i = 0; i < E; i++) {
+            if (!t[i]) return false;
+            const std::shared_ptr<DeviceBlock> &b = t[i]->block();
+            if (!b || b->ctx != ctx_ || t[i]->block_index() >= b->n_ct || b->n_ct > COFHE_HIP_GATHER_KEEP) return false;
+            size_t j = 0;
+            while (j < nb && blocks[j] != b) j++;
+            if (j == nb) {
+                if (nb == MAX_BLOCKS) return false;
+                blocks[nb++] = b;
+            }
+            which[i] = (uint32_t)j;
+        }
+        out = alloc(t.shape(), E);
+        for (size_t j = 0; j < nb; j++) {
+            std::vector<uint32_t> index(E, COFHE_HIP_GATHER_KEEP);
+            for (size_t i = 0; i < E; i++)
+                if (which[i] == j) index[i] = (uint32_t)t[i]->block_index();
+            Staged di = stage(std::move(index));
+            check(cofhe_hip_gather_records(ctx_, blocks[j]->dptr, blocks[j]->n_ct, di.ptr, nullptr, out.ptr_, E, 2 * REC, nullptr));
+        }
+        return true;
     }
     // hands the device tensor over to a Tensor<CipherText *> whose elements reference it (no transfer, no GMP work:
     // values appear when somebody reads them); the caller owns the elements as with every other result tensor
@@ -1122,6 +1170,7 @@ class HIPCryptoSystem {
         std::shared_ptr<DeviceBlock> blk = d.keep_;
         if (!blk) {
             blk = std::make_shared<DeviceBlock>(ctx_owner_, d.ptr_, d.n_);
+            blk->downloads = downloads_;
             d.ptr_ = nullptr;                          // ownership moved into the block
         }
         for (size_t i = 0; i < d.n_; i++) flat[i] = new CipherText(blk, i);
@@ -1152,6 +1201,170 @@ class HIPCryptoSystem {
         DeviceTensor r = alloc(a.shape_, a.n_);
         check(cofhe_hip_sub_ciphertext_records(ctx_, a.ptr_, b.ptr_, r.ptr_, a.n_, nullptr));
         return r;
+    }
+    // ---- rearranging resident tensors (cofhe_hip_view_records, cofhe_hip_gather_records; include/cofhe_hip.h states the
+    // descriptor) ----
+    // Every result element is a byte-for-byte COPY of an element of x or of `fill`: nothing is composed and NOTHING IS
+    // RE-RANDOMISED, in any randomness mode -- a copy shares its randomness with its source, and c2 o c2'^-1 of the two is the
+    // principal form.  A caller that hands both a copy and its original (or two copies) to another party calls
+    // rerandomize_ciphertext_tensor on what leaves first.  Each operation exists on DeviceTensor and on Tensor<CipherText *>
+    // (upload, operate, hand over: the lazy download that moves nothing).  Shape errors throw std::invalid_argument.
+    //
+    // the general entry: the view's source is x (the shapes must agree), the result is the view's whole destination, which the
+    // view's box must cover (a box inside a larger destination is what concat_ciphertext_tensors issues); `fill`: one element,
+    // needed when the view reads outside x
+    DeviceTensor view_ciphertext_tensor(const DeviceTensor &x, const cofhe_hip_view &view, const DeviceTensor *fill = nullptr) const {
+        uint64_t n_src = 0, n_box = 0, n_dst = 0;
+        int needs_fill = 0;
+        check(cofhe_hip_view_check(&view, &n_src, &n_box, &n_dst, &needs_fill));
+        if (n_box != n_dst) throw std::invalid_argument("view: the box must cover the whole destination");
+        DeviceTensor out = alloc(extents(view.dst_extent, view.out_ndim), n_dst);
+        view_into(x, view, fill, out);
+        return out;
+    }
+    Tensor<CipherText *> view_ciphertext_tensor(const Tensor<CipherText *> &x, const cofhe_hip_view &view, const CipherText *fill = nullptr) const {
+        if (!fill) return download(view_ciphertext_tensor(upload(x), view));
+        const DeviceTensor f = upload(Tensor<CipherText *>(1, const_cast<CipherText *>(fill)));
+        return download(view_ciphertext_tensor(upload(x), view, &f));
+    }
+    // result axis d is axis perm[d] of x (numpy.transpose)
+    DeviceTensor permute_ciphertext_tensor(const DeviceTensor &x, const std::vector<size_t> &perm) const {
+        if (perm.size() != x.shape_.size()) throw std::invalid_argument("permute: one entry per axis");
+        std::vector<uint32_t> p(perm.begin(), perm.end());
+        for (size_t d = 0; d < perm.size(); d++)
+            if (perm[d] >= perm.size()) throw std::invalid_argument("permute: not a permutation of the axes");
+        cofhe_hip_view v;
+        check(cofhe_hip_view_permute(shape64(x).data(), (uint32_t)perm.size(), p.data(), &v));
+        return view_ciphertext_tensor(x, v);
+    }
+    Tensor<CipherText *> permute_ciphertext_tensor(const Tensor<CipherText *> &x, const std::vector<size_t> &perm) const {
+        return download(permute_ciphertext_tensor(upload(x), perm));
+    }
+    DeviceTensor transpose_ciphertext_tensor(const DeviceTensor &x) const {
+        if (x.shape_.size() != 2) throw std::invalid_argument("transpose: a 2-D tensor");
+        return permute_ciphertext_tensor(x, {1, 0});
+    }
+    Tensor<CipherText *> transpose_ciphertext_tensor(const Tensor<CipherText *> &x) const { return download(transpose_ciphertext_tensor(upload(x))); }
+    // x[start[0]:stop[0]:step[0], ...]: bounds within their axes, steps != 0; with a negative step a stop of -1 means "down to and
+    // including element 0"
+    DeviceTensor slice_ciphertext_tensor(const DeviceTensor &x, const std::vector<int64_t> &start, const std::vector<int64_t> &stop,
+                                         const std::vector<int64_t> &step) const {
+        const size_t nd = x.shape_.size();
+        if (start.size() != nd || stop.size() != nd || step.size() != nd) throw std::invalid_argument("slice: one bound and one step per axis");
+        cofhe_hip_view v;
+        check(cofhe_hip_view_slice(shape64(x).data(), (uint32_t)nd, start.data(), stop.data(), step.data(), &v));
+        return view_ciphertext_tensor(x, v);
+    }
+    Tensor<CipherText *> slice_ciphertext_tensor(const Tensor<CipherText *> &x, const std::vector<int64_t> &start, const std::vector<int64_t> &stop,
+                                                 const std::vector<int64_t> &step) const {
+        return download(slice_ciphertext_tensor(upload(x), start, stop, step));
+    }
+    DeviceTensor flip_ciphertext_tensor(const DeviceTensor &x, size_t axis) const {
+        const size_t nd = x.shape_.size();
+        if (axis >= nd) throw std::invalid_argument("flip: no such axis");
+        std::vector<int64_t> start(nd, 0), stop(x.shape_.begin(), x.shape_.end()), step(nd, 1);
+        start[axis] = (int64_t)x.shape_[axis] - 1;
+        stop[axis] = -1;
+        step[axis] = -1;
+        return slice_ciphertext_tensor(x, start, stop, step);
+    }
+    Tensor<CipherText *> flip_ciphertext_tensor(const Tensor<CipherText *> &x, size_t axis) const { return download(flip_ciphertext_tensor(upload(x), axis)); }
+    // numpy's rule, right-aligned: every extent of x equals the extent of `shape` it is aligned with, or is 1
+    DeviceTensor broadcast_ciphertext_tensor(const DeviceTensor &x, const std::vector<size_t> &shape) const {
+        std::vector<uint64_t> out(shape.begin(), shape.end());
+        cofhe_hip_view v;
+        check(cofhe_hip_view_broadcast(shape64(x).data(), (uint32_t)x.shape_.size(), out.data(), (uint32_t)out.size(), &v));
+        return view_ciphertext_tensor(x, v);
+    }
+    Tensor<CipherText *> broadcast_ciphertext_tensor(const Tensor<CipherText *> &x, const std::vector<size_t> &shape) const {
+        return download(broadcast_ciphertext_tensor(upload(x), shape));
+    }
+    // lo[d] elements of `fill` before and hi[d] after x on every axis
+    DeviceTensor pad_ciphertext_tensor(const DeviceTensor &x, const std::vector<size_t> &lo, const std::vector<size_t> &hi, const DeviceTensor &fill) const {
+        const size_t nd = x.shape_.size();
+        if (lo.size() != nd || hi.size() != nd) throw std::invalid_argument("pad: one width per axis and side");
+        std::vector<uint64_t> l(lo.begin(), lo.end()), h(hi.begin(), hi.end());
+        cofhe_hip_view v;
+        check(cofhe_hip_view_pad(shape64(x).data(), (uint32_t)nd, l.data(), h.data(), &v));
+        return view_ciphertext_tensor(x, v, &fill);
+    }
+    Tensor<CipherText *> pad_ciphertext_tensor(const Tensor<CipherText *> &x, const std::vector<size_t> &lo, const std::vector<size_t> &hi,
+                                               const CipherText &fill) const {
+        return download(pad_ciphertext_tensor(upload(x), lo, hi, upload(Tensor<CipherText *>(1, const_cast<CipherText *>(&fill)))));
+    }
+    // the parts side by side along `axis` (their other extents agree): the result is allocated once, and every part is one view
+    // call that writes its box
+    DeviceTensor concat_ciphertext_tensors(const std::vector<const DeviceTensor *> &parts, size_t axis) const {
+        if (parts.empty() || !parts[0]) throw std::invalid_argument("concat: no parts");
+        std::vector<size_t> shape = parts[0]->shape_;
+        if (axis >= shape.size()) throw std::invalid_argument("concat: no such axis");
+        shape[axis] = 0;
+        for (const DeviceTensor *p : parts) {
+            if (!p || p->shape_.size() != shape.size()) throw std::invalid_argument("Tensor shapes must be equal");
+            for (size_t d = 0; d < shape.size(); d++)
+                if (d != axis && p->shape_[d] != shape[d]) throw std::invalid_argument("Tensor shapes must be equal");
+            shape[axis] += p->shape_[axis];
+        }
+        size_t n = 1;
+        for (size_t e : shape) n *= e;
+        DeviceTensor out = alloc(shape, n);
+        std::vector<uint64_t> dst(shape.begin(), shape.end()), at(shape.size(), 0);
+        std::vector<uint32_t> ident(shape.size());
+        for (size_t d = 0; d < ident.size(); d++) ident[d] = (uint32_t)d;
+        for (const DeviceTensor *p : parts) {
+            cofhe_hip_view v;
+            check(cofhe_hip_view_permute(shape64(*p).data(), (uint32_t)ident.size(), ident.data(), &v));
+            check(cofhe_hip_view_into(&v, dst.data(), at.data()));
+            view_into(*p, v, nullptr, out);
+            at[axis] += p->shape_[axis];
+        }
+        return out;
+    }
+    Tensor<CipherText *> concat_ciphertext_tensors(const Vector<Tensor<CipherText *>> &parts, size_t axis) const {
+        std::vector<DeviceTensor> held;
+        held.reserve(parts.size());
+        for (const Tensor<CipherText *> &p : parts) held.push_back(upload(p));
+        std::vector<const DeviceTensor *> ptrs;
+        for (const DeviceTensor &d : held) ptrs.push_back(&d);
+        return download(concat_ciphertext_tensors(ptrs, axis));
+    }
+    // the taps of every pooling / convolution window of x [B, H, W, C]: [kh, kw, B, Ho, Wo, C], `fill` in the padding (needed when a
+    // pad is not 0)
+    DeviceTensor window_taps_ciphertext_tensor(const DeviceTensor &x, const std::array<size_t, 2> &kernel, const std::array<size_t, 2> &stride,
+                                               const std::array<size_t, 2> &pad = {0, 0}, const std::array<size_t, 2> &dilation = {1, 1},
+                                               const DeviceTensor *fill = nullptr) const {
+        if (x.shape_.size() != 4) throw std::invalid_argument("window taps: the image is [B, H, W, C]");
+        const cofhe_hip_conv2d_geometry g = conv_geometry({x.shape_[0], x.shape_[1], x.shape_[2], x.shape_[3], kernel[0], kernel[1], x.shape_[3],
+                                                           stride[0], stride[1], pad[0], pad[1], dilation[0], dilation[1], 1});
+        cofhe_hip_view v;
+        check(cofhe_hip_view_window_taps(&g, &v));
+        return view_ciphertext_tensor(x, v, fill);
+    }
+    Tensor<CipherText *> window_taps_ciphertext_tensor(const Tensor<CipherText *> &x, const std::array<size_t, 2> &kernel,
+                                                       const std::array<size_t, 2> &stride, const std::array<size_t, 2> &pad = {0, 0},
+                                                       const std::array<size_t, 2> &dilation = {1, 1}, const CipherText *fill = nullptr) const {
+        if (!fill) return download(window_taps_ciphertext_tensor(upload(x), kernel, stride, pad, dilation));
+        const DeviceTensor f = upload(Tensor<CipherText *>(1, const_cast<CipherText *>(fill)));
+        return download(window_taps_ciphertext_tensor(upload(x), kernel, stride, pad, dilation, &f));
+    }
+    // res[i] = x[indices[i]] over the elements of x in row-major order, a 1-D tensor; an index of COFHE_HIP_GATHER_FILL takes
+    // `fill`.  An index beyond x is refused here, before anything runs.
+    DeviceTensor gather_ciphertext_tensor(const DeviceTensor &x, const std::vector<uint32_t> &indices, const DeviceTensor *fill = nullptr) const {
+        for (uint32_t ix : indices) {
+            if (ix == COFHE_HIP_GATHER_FILL ? fill == nullptr : ix >= x.n_)
+                throw std::invalid_argument(ix == COFHE_HIP_GATHER_FILL ? "gather: a fill index and no fill element" : "gather: an index beyond the tensor");
+        }
+        if (fill && fill->n_ != 1) throw std::invalid_argument("gather: the fill is one element");
+        DeviceTensor out = alloc({indices.size()}, indices.size());
+        if (indices.empty()) return out;
+        Staged di = stage(std::vector<uint32_t>(indices));
+        check(cofhe_hip_gather_records(ctx_, x.ptr_, x.n_, di.ptr, fill ? fill->ptr_ : nullptr, out.ptr_, indices.size(), 2 * REC, nullptr));
+        return out;
+    }
+    Tensor<CipherText *> gather_ciphertext_tensor(const Tensor<CipherText *> &x, const std::vector<uint32_t> &indices, const CipherText *fill = nullptr) const {
+        if (!fill) return download(gather_ciphertext_tensor(upload(x), indices));
+        const DeviceTensor f = upload(Tensor<CipherText *>(1, const_cast<CipherText *>(fill)));
+        return download(gather_ciphertext_tensor(upload(x), indices, &f));
     }
     void synchronize() const { check(cofhe_hip_stream_sync(ctx_, nullptr)); }
 
@@ -1441,6 +1654,8 @@ class HIPCryptoSystem {
         return CipherText(r[0], r[1]);
     }
     bool rerandomize_ = true;
+    bool resident_gather_ = true;                          // upload(): elements of resident blocks are gathered on the device
+    std::shared_ptr<std::atomic<uint64_t>> downloads_ = std::make_shared<std::atomic<uint64_t>>(0);
     TensorRandomness tensor_randomness_ = TensorRandomness::None;
     // n exponent records of r_i, uniform below exponent_bound
     std::vector<uint32_t> draw_randomness(size_t n) const {
@@ -1658,6 +1873,15 @@ class HIPCryptoSystem {
         d.n_ = n;
         check(cofhe_hip_malloc(ctx_, n * 2 * REC * 4, &d.ptr_));
         return d;
+    }
+    static std::vector<size_t> extents(const uint64_t *e, uint32_t nd) { return std::vector<size_t>(e, e + nd); }
+    static std::vector<uint64_t> shape64(const DeviceTensor &x) { return std::vector<uint64_t>(x.shape_.begin(), x.shape_.end()); }
+    // one view call: the box of `view`, whose source is x, into the resident tensor `out`, whose shape is the view's destination
+    void view_into(const DeviceTensor &x, const cofhe_hip_view &view, const DeviceTensor *fill, DeviceTensor &out) const {
+        if (view.src_ndim > COFHE_HIP_VIEW_MAX_DIMS || extents(view.src_extent, view.src_ndim) != x.shape_)
+            throw std::invalid_argument("view: the descriptor's source is not the tensor's shape");
+        if (fill && fill->n_ != 1) throw std::invalid_argument("view: the fill is one element");
+        check(cofhe_hip_view_records(ctx_, &view, x.ptr_, fill ? fill->ptr_ : nullptr, out.ptr_, 2 * REC, nullptr));
     }
     // d tensors of E ciphertexts each as ONE device tensor [d, E], tensor-major: the layout of the bases of
     // cofhe_hip_pow_dot_records.  The records of a resident tensor are taken from its block, not rebuilt from GMP integers.

@@ -338,17 +338,22 @@ struct Args {
 };
 
 // a warm-up pass and `runs` timed passes of fn (a ciphertext tensor, freed after its pass), each from a drained stream; the
-// times come back sorted
-template <typename F>
-std::vector<double> median_runs(const CS &cs, int runs, F fn) {
+// times come back sorted.  before() runs in front of every pass, outside its clock.
+template <typename F, typename P>
+std::vector<double> median_runs(const CS &cs, int runs, F fn, P before) {
     std::vector<double> ms;
     for (int pass = 0; pass <= runs; pass++) {
+        before();
         cs.synchronize();
         auto run = timed(cs, [&]() -> Owned<CT> { return fn(); });
         if (pass) ms.push_back(run.first);
     }
     std::sort(ms.begin(), ms.end());
     return ms;
+}
+template <typename F>
+std::vector<double> median_runs(const CS &cs, int runs, F fn) {
+    return median_runs(cs, runs, fn, []() {});
 }
 
 struct ConvResult {
@@ -1618,6 +1623,166 @@ static void plaintexts_mode(const Args &arg) {
     }
 }
 
+// Rearranging resident tensors (view_ciphertext_tensor and kin, the device route of upload): an image of distinct small values
+// is encrypted, and everything below runs on the RESULT of add_ciphertext_tensors(x, x), a resident block -- a permutation of the
+// axes, a slice with a negative step, a padding, a broadcast, a concatenation with a flipped copy, the window taps of the
+// geometry and an index gather; then the three columns of an [n, 3] block through upload, and max_pool2d with the geometry's
+// padding on 4-bit values.  Prints block_downloads (the record downloads before the first decryption: 0 when nothing left the
+// device), decrypts everything, compares with host loops and prints "<name> ok" per operation; last, the upload of the three
+// columns of a 4096 x 3 block with the device route on and off (medians over fresh blocks).
+static void bench_rearrange(const Args &arg) {
+    const size_t B = arg(2, 1), H = arg(3, 5), W = arg(4, 4), C = arg(5, 2), kh = arg(6, 3), kw = arg(7, 2);
+    const size_t sh = arg(8, 2), sw = arg(9, 1), ph = arg(10, 1), pw = arg(11, 1), dh = arg(12, 1), dw = arg(13, 1);
+    Fixture fx;
+    auto &cs = fx.cs;
+    Client client(cs, fx.sk);
+    Multiplier mul(client);
+    const auto &pk = client.network_public_key();
+    const size_t n = B * H * W * C;
+    auto val = [](size_t i) { return (float)((i * 5) % 15) - 7.0f; };          // within 4 bits, signed; x + x doubles it
+    auto v2 = [&](size_t i) { return 2.0f * val(i); };
+    auto at = [&](size_t b, size_t y, size_t x, size_t c) { return ((b * H + y) * W + x) * C + c; };
+    const float FILLV = 99.0f;
+    Owned<PT> px = plain_tensor(fx, {B, H, W, C}, val);
+    Owned<CT> cx = cs.encrypt_tensor(pk, px);
+    Owned<CT> r = cs.add_ciphertext_tensors(pk, cx, cx);
+    const CT fill = cs.encrypt(pk, cs.make_plaintext(FILLV));
+    const uint64_t downloads0 = cs.block_downloads();
+
+    struct Case {
+        std::string name;
+        Owned<CT> got;
+        std::vector<float> want;
+        std::vector<size_t> shape;
+    };
+    std::vector<Case> cases;
+    {   // permute by (3, 1, 0, 2): [C, H, B, W]
+        std::vector<float> w;
+        for (size_t c = 0; c < C; c++) for (size_t y = 0; y < H; y++) for (size_t b = 0; b < B; b++) for (size_t x = 0; x < W; x++) w.push_back(v2(at(b, y, x, c)));
+        cases.push_back({"permute", cs.permute_ciphertext_tensor(r, {3, 1, 0, 2}), w, {C, H, B, W}});
+    }
+    {   // rows H - 1, H - 3, ..: a negative step down to and including row 0
+        std::vector<float> w;
+        size_t rows = 0;
+        for (size_t b = 0; b < B; b++) {
+            rows = 0;
+            for (long y = (long)H - 1; y >= 0; y -= 2, rows++) for (size_t x = 0; x < W; x++) for (size_t c = 0; c < C; c++) w.push_back(v2(at(b, (size_t)y, x, c)));
+        }
+        cases.push_back({"slice", cs.slice_ciphertext_tensor(r, {0, (int64_t)H - 1, 0, 0}, {(int64_t)B, -1, (int64_t)W, (int64_t)C}, {1, -2, 1, 1}), w, {B, rows, W, C}});
+    }
+    {   // one row above, two columns left and one right
+        std::vector<float> w;
+        for (size_t b = 0; b < B; b++) for (size_t y = 0; y < H + 1; y++) for (size_t x = 0; x < W + 3; x++) for (size_t c = 0; c < C; c++)
+            w.push_back(y >= 1 && x >= 2 && x < W + 2 ? v2(at(b, y - 1, x - 2, c)) : FILLV);
+        cases.push_back({"pad", cs.pad_ciphertext_tensor(r, {0, 1, 2, 0}, {0, 0, 1, 0}, fill), w, {B, H + 1, W + 3, C}});
+    }
+    {   // three copies along a new leading axis
+        std::vector<float> w;
+        for (size_t rep = 0; rep < 3; rep++) for (size_t i = 0; i < n; i++) w.push_back(v2(i));
+        cases.push_back({"broadcast", cs.broadcast_ciphertext_tensor(r, {3, B, H, W, C}), w, {3, B, H, W, C}});
+    }
+    {   // the image and its mirror side by side along W
+        Owned<CT> mirror = cs.flip_ciphertext_tensor(r, 2);
+        std::vector<float> w;
+        for (size_t b = 0; b < B; b++) for (size_t y = 0; y < H; y++) for (size_t x = 0; x < 2 * W; x++) for (size_t c = 0; c < C; c++)
+            w.push_back(v2(at(b, y, x < W ? x : 2 * W - 1 - x, c)));
+        cases.push_back({"concat", cs.concat_ciphertext_tensors({r, mirror}, 2), w, {B, H, 2 * W, C}});
+    }
+    size_t Ho = 0, Wo = 0;
+    {
+        Owned<CT> taps = cs.window_taps_ciphertext_tensor(r, {kh, kw}, {sh, sw}, {ph, pw}, {dh, dw}, &fill);
+        if (taps->shape().size() != 6) throw std::runtime_error("window taps: not 6-D");
+        Ho = taps->shape()[3];
+        Wo = taps->shape()[4];
+        std::vector<float> w;
+        for (size_t dy = 0; dy < kh; dy++) for (size_t dx = 0; dx < kw; dx++) for (size_t b = 0; b < B; b++) for (size_t oy = 0; oy < Ho; oy++)
+            for (size_t ox = 0; ox < Wo; ox++) for (size_t c = 0; c < C; c++) {
+                const long y = (long)(oy * sh + dy * dh) - (long)ph, x = (long)(ox * sw + dx * dw) - (long)pw;
+                w.push_back(y >= 0 && y < (long)H && x >= 0 && x < (long)W ? v2(at(b, (size_t)y, (size_t)x, c)) : FILLV);
+            }
+        cases.push_back({"window_taps", std::move(taps), w, {kh, kw, B, Ho, Wo, C}});
+    }
+    {   // the elements backwards, every fifth one the fill
+        std::vector<uint32_t> idx(n);
+        std::vector<float> w(n);
+        for (size_t i = 0; i < n; i++) {
+            idx[i] = i % 5 == 4 ? COFHE_HIP_GATHER_FILL : (uint32_t)(n - 1 - i);
+            w[i] = i % 5 == 4 ? FILLV : v2(n - 1 - i);
+        }
+        cases.push_back({"gather", cs.gather_ciphertext_tensor(r, idx, &fill), w, {n}});
+    }
+    // the columns of an [n, 3] block, as the Beaver flows split a triplet block: pointers into one resident block, through upload
+    Owned<PT> p3 = plain_tensor(fx, {n, 3}, val);
+    Owned<CT> c3 = cs.encrypt_tensor(pk, p3);
+    Owned<CT> r3 = cs.add_ciphertext_tensors(pk, c3, c3);
+    auto column = [](const Tensor<CT *> &block, size_t rows, size_t j) {
+        Tensor<CT *> col(rows, nullptr);
+        for (size_t i = 0; i < rows; i++) col[i] = block[i * 3 + j];
+        return col;
+    };
+    for (size_t j = 0; j < 3; j++) {
+        std::vector<float> w;
+        for (size_t i = 0; i < n; i++) w.push_back(v2(i * 3 + j));
+        cases.push_back({"column_split_" + std::to_string(j), cs.download(cs.upload(column(r3, n, j))), w, {n}});
+    }
+    std::cout << "block_downloads=" << cs.block_downloads() - downloads0 << std::endl;
+
+    bool ok = true;
+    for (const Case &c : cases) {
+        const bool pass = c.got->shape() == c.shape && decrypts_to(fx, c.got, c.want);
+        std::cout << c.name << " " << (pass ? "ok" : "FAILED") << std::endl;
+        ok = ok && pass;
+    }
+    {   // max pooling with the geometry's padding on the 4-bit image itself; the least value stands in the padding
+        const uint32_t bits = 4;
+        Owned<CT> pooled = mul.max_pool2d_ciphertext_tensor(cx, {kh, kw}, {sh, sw}, bits, {ph, pw});
+        const size_t Hp = (H + 2 * ph - kh) / sh + 1, Wp = (W + 2 * pw - kw) / sw + 1;
+        std::vector<float> w;
+        for (size_t b = 0; b < B; b++) for (size_t oy = 0; oy < Hp; oy++) for (size_t ox = 0; ox < Wp; ox++) for (size_t c = 0; c < C; c++) {
+            float m = -8.0f;
+            for (size_t dy = 0; dy < kh; dy++) for (size_t dx = 0; dx < kw; dx++) {
+                const long y = (long)(oy * sh + dy) - (long)ph, x = (long)(ox * sw + dx) - (long)pw;
+                if (y >= 0 && y < (long)H && x >= 0 && x < (long)W) m = std::max(m, val(at(b, (size_t)y, (size_t)x, c)));
+            }
+            w.push_back(m);
+        }
+        const bool pass = pooled->shape() == std::vector<size_t>{B, Hp, Wp, C} && decrypts_to(fx, pooled, w);
+        std::cout << "max_pool2d_padded " << (pass ? "ok" : "FAILED") << std::endl;
+        ok = ok && pass;
+    }
+    {   // the device route against the host route: both give the same bytes
+        Tensor<CT *> col = column(r3, n, 1);
+        Owned<CT> dev = cs.download(cs.upload(col));
+        cs.set_resident_gather(false);
+        Owned<CT> host = cs.download(cs.upload(col));
+        cs.set_resident_gather(true);
+        const bool pass = cs.serialize_ciphertext_tensor(dev) == cs.serialize_ciphertext_tensor(host);
+        std::cout << "routes_agree " << (pass ? "ok" : "FAILED") << std::endl;
+        ok = ok && pass;
+    }
+    {   // the three columns of a 4096 x 3 block, a fresh block for every pass so that the host route pays its download each time
+        const size_t rows = 4096;
+        const int runs = 5;
+        Owned<PT> pbig = plain_tensor(fx, {rows, 3}, val);
+        Owned<CT> cbig = cs.encrypt_tensor(pk, pbig);
+        Owned<CT> block;
+        auto fresh_block = [&]() { block = cs.add_ciphertext_tensors(pk, cbig, cbig); };
+        auto split = [&]() -> Tensor<CT *> {
+            for (size_t j = 0; j < 2; j++) (void)cs.upload(column(block, rows, j));
+            return cs.download(cs.upload(column(block, rows, 2)));
+        };
+        const auto dev_ms = median_runs(cs, runs, split, fresh_block);
+        cs.set_resident_gather(false);
+        const auto host_ms = median_runs(cs, runs, split, fresh_block);
+        cs.set_resident_gather(true);
+        std::cout << "upload_ms device=" << median(dev_ms) << " host=" << median(host_ms) << " (4096 x 3 block, three columns, medians of " << runs
+                  << " runs; device [" << dev_ms.front() << ", " << dev_ms.back() << "] host [" << host_ms.front() << ", " << host_ms.back() << "])"
+                  << std::endl;
+    }
+    std::cout << "  agree: " << (ok ? "yes" : "NO") << std::endl;
+    if (!ok) throw std::runtime_error("rearrange mismatch");
+}
+
 // every mode: its name, its arguments with their defaults, its function
 static const struct Mode {
     const char *name, *synopsis;
@@ -1641,6 +1806,7 @@ static const struct Mode {
     {"divide", "[elements=64 [runs=0]]", bench_divide},
     {"lookup", "[elements=64 [runs=0]]", bench_lookup},
     {"spline", "[elements=256 [runs=0 [bits=5 [shift=11 [degree=2]]]]]", bench_spline},
+    {"rearrange", "[B=1 H=5 W=4 C=2 kh=3 kw=2 [sh=2 sw=1 ph=1 pw=1 dh=1 dw=1]]", bench_rearrange},
     {"formats", "", bench_formats},
     {"threads", "[rounds=4]", bench_threads},
     {"plaintexts", "<in> <out>", plaintexts_mode},

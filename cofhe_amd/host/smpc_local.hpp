@@ -455,23 +455,39 @@ class LocalCipherTextMultiplier {
         }
         return res;
     }
-    // max pooling of `bits`-bit signed values, channels last ([B, H, W, C] -> [B, Ho, Wo, C]), no padding: a pairwise tournament
+    // max pooling of `bits`-bit signed values, channels last ([B, H, W, C] -> [B, Ho, Wo, C]): a pairwise tournament
     // over the kernel[0] kernel[1] taps of a window, ceil(log2(taps)) rounds of ONE batched max_ciphertext_tensors call each (an
-    // odd tap passes through), taps - 1 lookups and opened values per output.  The taps are gathered by pointer arithmetic on
-    // the host tensor; nothing is copied.
+    // odd tap passes through), taps - 1 lookups and opened values per output.  Without padding the taps are gathered by pointer
+    // arithmetic on the host tensor and nothing is copied until the cryptosystem's upload gathers them on the device.  With
+    // pad != {0, 0} (each smaller than its kernel extent) the taps are window_taps_ciphertext_tensor of x with a fill of ONE fresh
+    // Enc(-2^(bits - 1)), the least `bits`-bit value: padding never wins, and a window wholly in the padding returns that value.
+    // The padding elements are copies of one ciphertext (they share its randomness); every output is the result of a lookup
+    // and carries randomness of its own.
     Tensor<CipherText *> max_pool2d_ciphertext_tensor(const Tensor<CipherText *> &x, const std::array<size_t, 2> &kernel,
-                                                      const std::array<size_t, 2> &stride, uint32_t bits) {
+                                                      const std::array<size_t, 2> &stride, uint32_t bits, const std::array<size_t, 2> &pad = {0, 0}) {
         if (x.is_zero_degree() || x.ndim() != 4) throw std::invalid_argument("max_pool2d_ciphertext_tensor: a [B, H, W, C] tensor");
         const size_t B = x.shape()[0], H = x.shape()[1], W = x.shape()[2], C = x.shape()[3], kh = kernel[0], kw = kernel[1];
-        if (kh == 0 || kw == 0 || stride[0] == 0 || stride[1] == 0 || kh > H || kw > W)
+        const bool padded = pad[0] != 0 || pad[1] != 0;
+        if (kh == 0 || kw == 0 || stride[0] == 0 || stride[1] == 0 || kh > H + 2 * pad[0] || kw > W + 2 * pad[1])
             throw std::invalid_argument("max_pool2d_ciphertext_tensor: the window lies inside the image, the strides are not 0");
-        const size_t Ho = (H - kh) / stride[0] + 1, Wo = (W - kw) / stride[1] + 1, n_out = B * Ho * Wo * C;
+        if (padded && (bits == 0 || bits + 1 > COFHE_HIP_LUT_MAX_BITS)) throw std::invalid_argument("max_ciphertext_tensors: 1 <= bits <= 11");
+        const size_t Ho = (H + 2 * pad[0] - kh) / stride[0] + 1, Wo = (W + 2 * pad[1] - kw) / stride[1] + 1, n_out = B * Ho * Wo * C;
         struct Tap {
             Tensor<CipherText *> t;
-            bool owned;                              // a result of an earlier round, not elements of x
+            bool owned;                              // a result of an earlier round or a copy, not elements of x
         };
         std::vector<Tap> taps;
-        for (size_t dy = 0; dy < kh; dy++)
+        if (padded) {
+            auto &cs = client_m.crypto_system();
+            const CipherText least = cs.encrypt(client_m.network_public_key(), cs.make_plaintext(-(float)((size_t)1 << (bits - 1))));
+            Tensor<CipherText *> all = cs.window_taps_ciphertext_tensor(x, kernel, stride, pad, {1, 1}, &least);      // [kh, kw, B, Ho, Wo, C]
+            for (size_t tap = 0; tap < kh * kw; tap++) {
+                Tensor<CipherText *> t(n_out, nullptr);
+                for (size_t i = 0; i < n_out; i++) t[i] = all[tap * n_out + i];
+                taps.push_back(Tap{t, true});
+            }
+        }
+        for (size_t dy = 0; dy < (padded ? 0 : kh); dy++)
             for (size_t dx = 0; dx < kw; dx++) {
                 Tensor<CipherText *> t(n_out, nullptr);
                 size_t o = 0;

@@ -113,6 +113,8 @@ int cofhe_hip_trim(cofhe_hip_ctx *ctx, size_t keep_bytes);
  *   "conv_chunk_rows"  >= 1: output positions per chunk of the convolution's direct route, taken as given (no rounding to a
  *                      multiple of 16, no decline for being small): how a test reaches several chunks and workgroups that
  *                      mix tree elements
+ *   "view_grid_blocks" >= 1: the grid of cofhe_hip_view_records and cofhe_hip_gather_records, taken as given: how a test reaches
+ *                      their grid-stride loops with a thousand records
  *   "profile_kernels"  != 0: cofhe_hip_scal_matmul_records brackets each of its kernels with HIP events on the launch
  *                      stream; cofhe_hip_profile_read(ctx, "k_tree_level" | "k_scal_matmul_wnaf" | "k_pow_table" | "k_wnaf_digits", ...)
  *                      waits for them and returns the summed duration and the launch count (clear != 0 drops all spans).
@@ -133,7 +135,8 @@ int cofhe_hip_stream_sync(cofhe_hip_ctx *ctx, void *stream);
 
 /* Device status word: every data-dependent loop of the kernels has a trip-count cap; a cap that is hit (possible only
  * for records that are not reduced forms of the context's discriminant) sets a bit instead of hanging or passing
- * silently: 1 = remainder sequence, 2 = reduction, 4 = division (by zero / no end).  clear != 0 resets it.
+ * silently: 1 = remainder sequence, 2 = reduction, 4 = division (by zero / no end).  32 = cofhe_hip_gather_records met
+ * an index beyond its source (nothing was read there).  clear != 0 resets it.
  * Synchronises `stream`. */
 int cofhe_hip_device_status(cofhe_hip_ctx *ctx, uint32_t *word, int clear, void *stream);
 /* *all_valid = 1 when every one of the n form records is a reduced, primitive form of the context's discriminant
@@ -400,6 +403,73 @@ int cofhe_hip_lut_select_records(cofhe_hip_ctx *ctx, const void *d_e, const void
 /* host only, no GPU: *bits of the tuples that go with opened values of shape shape_e[ndim_e], ndim_e <= 7.  COFHE_HIP_ESHAPE unless
  * shape_t is shape_e with one more, last dimension of 2^bits entries, 1 <= bits <= COFHE_HIP_LUT_MAX_BITS. */
 int cofhe_hip_lut_tuples_shape_bits(uint32_t ndim_e, const uint32_t *shape_e, uint32_t ndim_t, const uint32_t *shape_t, uint32_t *bits);
+/* ---- rearranging resident tensors: affine views and index gathers (cofhe_amd/csrc/view.hip, view.hpp) ----
+ * Pure data movement on records of `words` dwords each (336 a ciphertext, 168 a form or a partial decryption, 32 an exponent
+ * record): every record of the result is a byte-for-byte copy of a source record or of the fill record.  No composition runs and
+ * nothing is re-randomised: A COPY SHARES ITS RANDOMNESS WITH ITS SOURCE, so c2 o c2'^-1 of a copy and its original is the
+ * principal form; a caller that hands both to another party re-randomises one of them first (cofhe_hip_rerandomize_records).
+ *
+ * An AFFINE VIEW maps an output coordinate to a source coordinate.  It produces a box of out_extent elements (out_ndim axes; 0
+ * axes: one element) from a dense row-major source of src_extent (src_ndim axes): for the output coordinate o the source
+ * coordinate on source axis a is c_a = start[a] + sum_d map[a][d] o_d.  Where 0 <= c_a < src_extent[a] holds on every source axis,
+ * dst[rowmajor_dst(dst_start + o)] = src[rowmajor_src(c)]; otherwise that destination element receives the fill record.  The box
+ * lies at dst_start inside a dense row-major destination of dst_extent (out_ndim axes); destination elements outside the box are
+ * not written, which is how K calls concatenate K tensors into one.  One descriptor expresses a permutation of the axes (a
+ * permutation matrix), a slice with a step, a flip (-1), a broadcast (a zero column), padding (a negative start), a diagonal (a
+ * column with two ones) and sliding windows (two output axes mapped onto one source axis: y = oy sh + dy dh - ph). */
+#define COFHE_HIP_VIEW_MAX_DIMS 8
+typedef struct {
+    uint32_t out_ndim, src_ndim;                 /* 0..8; 0 = one element */
+    uint64_t out_extent[8], src_extent[8];       /* the box that is produced; the dense row-major source */
+    int64_t start[8];                            /* per SOURCE axis */
+    int32_t map[8][8];                           /* map[a][d]: source axis a advances by this per step of output axis d */
+    uint64_t dst_extent[8], dst_start[8];        /* the box lies at dst_start inside a dense row-major destination of dst_extent */
+} cofhe_hip_view;
+#define COFHE_HIP_GATHER_FILL 0xFFFFFFFFu        /* cofhe_hip_gather_records: this output receives the fill record */
+#define COFHE_HIP_GATHER_KEEP 0xFFFFFFFEu        /* ... this output is left as it is */
+/* host only, no GPU, no context: the element counts of the source, the box and the destination, and *needs_fill = 1 when some
+ * element of the box can read outside the source (exact: the range of every c_a over the box, by interval arithmetic in 128 bits).
+ * Any output pointer may be null.  COFHE_HIP_EINVAL: more than 8 axes; a box that does not lie inside dst_extent; a c_a that can
+ * leave the range of an int64; more than 2^48 elements in the source, the box or the destination.  A zero extent is legal and
+ * gives a count of 0. */
+int cofhe_hip_view_check(const cofhe_hip_view *view, uint64_t *n_src, uint64_t *n_box, uint64_t *n_dst, int *needs_fill);
+/* host only: the builders fill *view for a dense row-major source of shape[ndim], ndim <= 8, and set dst_extent = out_extent,
+ * dst_start = 0.  COFHE_HIP_EINVAL for a null pointer, more than 8 axes and what each names below.
+ * permute: output axis d is source axis perm[d] (numpy.transpose); perm must be a permutation of 0 .. ndim - 1.
+ * slice: out = src[start[0]:stop[0]:step[0], ...] with numpy's meaning for bounds given in range: step != 0; with step > 0,
+ *   0 <= start <= shape and 0 <= stop <= shape; with step < 0, -1 <= stop and start <= shape - 1, where a stop of -1 stands for
+ *   "down to and including element 0" (numpy's None).  An empty range gives an extent of 0.  |step| < 2^31.
+ * pad: out extent lo + shape + hi, the source at offset lo; the elements around it receive the fill record.
+ * broadcast: numpy's rule, right-aligned: every source extent equals the output extent it is aligned with, or is 1.
+ * window_taps: [B, H, W, C] -> [kh, kw, B, Ho, Wo, C], out[dy, dx, b, oy, ox, c] = src[b, oy sh + dy dh - ph, ox sw + dx dw - pw, c]
+ *   or the fill record in the padding, with the extents and the refusals of cofhe_hip_conv2d_geometry_out_shape; Co and groups
+ *   are ignored.
+ * into: places the box of an existing descriptor at dst_start inside a destination of dst_shape (out_ndim axes each). */
+int cofhe_hip_view_permute(const uint64_t *shape, uint32_t ndim, const uint32_t *perm, cofhe_hip_view *view);
+int cofhe_hip_view_slice(const uint64_t *shape, uint32_t ndim, const int64_t *start, const int64_t *stop, const int64_t *step,
+                         cofhe_hip_view *view);
+int cofhe_hip_view_pad(const uint64_t *shape, uint32_t ndim, const uint64_t *lo, const uint64_t *hi, cofhe_hip_view *view);
+int cofhe_hip_view_broadcast(const uint64_t *shape, uint32_t ndim, const uint64_t *out_shape, uint32_t out_ndim, cofhe_hip_view *view);
+int cofhe_hip_view_window_taps(const cofhe_hip_conv2d_geometry *geometry, cofhe_hip_view *view);
+int cofhe_hip_view_into(cofhe_hip_view *view, const uint64_t *dst_shape, const uint64_t *dst_start);
+/* The view on the device: purely stream-ordered, no read-back, no workspace, no lock; one launch ("k_view_records" under
+ * "profile_kernels"), none when the box is empty.  d_src: n_src records; d_fill: ONE record, may be null when the view needs no
+ * fill; d_dst: n_dst records, of which the n_box of the box are written.  16-byte accesses when the three pointers and the record
+ * size allow them, 4-byte ones otherwise.  Records of 64 pieces or more are moved by one wavefront each, shorter ones by eight lanes
+ * each; the grid strides beyond 64 workgroups per CU ("view_grid_blocks" pins the grid).  The status word is not touched.
+ * COFHE_HIP_EINVAL, nothing written: a descriptor that cofhe_hip_view_check refuses; a fill is needed and d_fill is null; words =
+ * 0; the destination overlaps the source or the fill. */
+int cofhe_hip_view_records(cofhe_hip_ctx *ctx, const cofhe_hip_view *view, const void *d_src, const void *d_fill, void *d_dst,
+                           uint32_t words, void *stream);
+/* dst[i] = src[index[i]], i < n_out: d_index holds n_out uint32_t on the device.  COFHE_HIP_GATHER_FILL writes the fill record,
+ * COFHE_HIP_GATHER_KEEP leaves dst[i] untouched (several source blocks are gathered into one destination by one call each, with
+ * KEEP at the other blocks' elements).  Any other index >= n_src writes the fill record -- or, with d_fill null, leaves dst[i]
+ * untouched -- and sets bit 32 of the device status word; nothing is ever read out of range.  d_fill may be null when no index is
+ * FILL (a FILL index is then treated like KEEP).  One launch ("k_gather_records"), none for n_out = 0; the lane mapping, the access
+ * width and "view_grid_blocks" as above.  COFHE_HIP_EINVAL, nothing written: words = 0; n_src > 0xFFFFFFFE; the destination
+ * overlaps the source, the indices or the fill. */
+int cofhe_hip_gather_records(cofhe_hip_ctx *ctx, const void *d_src, uint64_t n_src, const void *d_index, const void *d_fill, void *d_dst,
+                             uint64_t n_out, uint32_t words, void *stream);
 /* ---- piecewise-polynomial activations from one opened value (cofhe_amd/csrc/spline.hip) ----
  * A SPLINE TABLE over a window of W = shift + bits <= k bits is 2^bits pieces of d + 1 plaintext coefficients, 1 <= d <=
  * COFHE_HIP_POLY_MAX_DEGREE, 2^bits (d + 1) <= COFHE_HIP_SPLINE_MAX_TUPLE.  Piece p has the origin o(p) = sigma(p) 2^shift, sigma(p) the

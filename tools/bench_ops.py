@@ -11,7 +11,9 @@ the division by public divisors: k_plain_divfloor alone from its "profile_kernel
 and the protocol through local_bench with the kernel's share of it; written to profiles/r13_div/div_time.json, or to --out FILE.
 --lut-only: only the table lookups: k_lut_select next to a device-to-device copy of the same bytes, the parts of a ReLU over 256
 elements (tuple generation, decryption, selection), and the protocol through local_bench next to the degree-3 polynomial of the
-same run; written to profiles/r14_lut/lut_time.json, or to --out FILE."""
+same run; written to profiles/r14_lut/lut_time.json, or to --out FILE.  --view-only: only the rearrangements of resident tensors:
+k_view_records (identity, transpose, window taps) and k_gather_records next to k_lut_select and a device-to-device copy of the same
+bytes; written to --out FILE when given."""
 import json
 import os
 import sys
@@ -386,6 +388,93 @@ if "--lut-only" in sys.argv:
         json.dump(res, fh, indent=1)
     sys.exit(0 if all(r["device_status"] == 0 and r.get("exit_status", 0) == 0 and r.get("agree") is not False and r.get("same_records", True)
                       for r in res) else 1)
+
+# ---- rearranging resident tensors: k_view_records and k_gather_records next to k_lut_select and a copy --------------------------
+def view_ops(runs=5):
+    """"view_records" (an identity view, a 128 x 128 transpose and the 3 x 3 window taps with padding 1 of a 1 x 32 x 32 x 16 image)
+    and "gather_records" (a random permutation) on 16384 ciphertexts of arbitrary words, each next to cofhe_hip_lut_select_records
+    selecting the same number of ciphertexts (b = 1) and a contiguous device-to-device copy of the same output bytes, by device
+    events around 16 calls, alternating, `runs` windows each.  Every call of a window reads another of 16 source buffers (352 MB
+    in all, more than the Infinity Cache keeps)."""
+    from cofhe_amd import engine as E_
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    E, CTW, SETS = 16384, 336, 16
+    pool = torch.empty(SETS * 2 * E * CTW, dtype=torch.int32, device=dev).random_()        # also the b = 1 tuples of lut_select
+    srcs = [pool[j * 2 * E * CTW:(j * 2 + 1) * E * CTW] for j in range(SETS)]
+    fill = torch.empty(CTW, dtype=torch.int32, device=dev).random_()
+    perm = np.random.default_rng(1).permutation(E).astype(np.uint32)
+    dperm = dev_i32(perm)
+
+    def window(fn):
+        fn(0)
+        torch.cuda.synchronize()
+        a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for j in range(SETS):
+            fn(j)
+        z.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(z) / SETS
+
+    def exps(n, seed):
+        rec = np.zeros((n, 32), dtype=np.uint32)
+        rec[:, 0] = np.random.default_rng(seed).integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+        return dev_i32(rec.reshape(-1))
+
+    lines = []
+    views = [("identity", E_.view_permute([E], [0])), ("transpose_128x128", E_.view_permute([128, 128], [1, 0])),
+             ("window_taps_3x3_pad1_1x32x32x16", E_.view_window_taps((1, 32, 32, 16), (3, 3), (1, 1), (1, 1)))]
+    cases = [("view_records", name, v, E_.view_check(v)[1]) for name, v in views] + [("gather_records", "random_permutation", None, E)]
+    for op, name, v, n_out in cases:
+        out, dst = torch.zeros(n_out * CTW, dtype=torch.int32, device=dev), torch.zeros(n_out * CTW, dtype=torch.int32, device=dev)
+        reps = n_out // E                                    # the copy and the select move the same output bytes
+        tup = pool if reps == 1 else torch.empty(2 * n_out * CTW, dtype=torch.int32, device=dev).random_()
+        es = [exps(n_out, j) for j in range(4)]
+        big = None if reps == 1 else [tup[(j % 2) * n_out * CTW:((j % 2) + 1) * n_out * CTW] for j in range(SETS)]
+        if v is not None:
+            run = lambda j: eng.view_records(v, srcs[j].data_ptr(), fill.data_ptr(), out.data_ptr(), CTW)  # noqa: E731
+        else:
+            run = lambda j: eng.gather_records(srcs[j].data_ptr(), E, dperm.data_ptr(), 0, out.data_ptr(), E, CTW)  # noqa: E731
+        sel = lambda j: eng.lut_select_records(es[j % 4].data_ptr(), tup.data_ptr(), dst.data_ptr(), n_out, 1)  # noqa: E731
+        cpy = (lambda j: dst.copy_(srcs[j])) if reps == 1 else (lambda j: dst.copy_(big[j]))  # noqa: E731
+        run(3)
+        torch.cuda.synchronize()
+        if v is None:
+            same = bool(torch.equal(out.view(E, CTW), srcs[3].view(E, CTW)[torch.from_numpy(perm.astype(np.int64)).to(dev)]))
+        elif name == "identity":
+            same = bool(torch.equal(out, srcs[3]))
+        elif name.startswith("transpose"):
+            same = bool(torch.equal(out.view(128, 128, CTW), srcs[3].view(128, 128, CTW).transpose(0, 1)))
+        else:
+            img = torch.nn.functional.pad(srcs[3].view(32, 32, 16, CTW), (0, 0, 0, 0, 1, 1, 1, 1))
+            img[0, :], img[-1, :], img[:, 0], img[:, -1] = fill, fill, fill, fill
+            same = all(bool(torch.equal(out.view(3, 3, 32, 32, 16, CTW)[dy, dx], img[dy:dy + 32, dx:dx + 32])) for dy in range(3) for dx in range(3))
+        tv, ts, tc = [], [], []
+        for _ in range(runs):
+            tv.append(window(run))
+            ts.append(window(sel))
+            tc.append(window(cpy))
+        nbytes = n_out * CTW * 4
+        line = {"op": op, "case": name, "ciphertexts_out": n_out, "bytes_written": nbytes, "ms": round(med(tv), 4),
+                "ms_min_max": [round(min(tv), 4), round(max(tv), 4)], "lut_select_ms": round(med(ts), 4),
+                "lut_select_ms_min_max": [round(min(ts), 4), round(max(ts), 4)], "copy_ms": round(med(tc), 4),
+                "copy_ms_min_max": [round(min(tc), 4), round(max(tc), 4)], "over_lut_select": round(med(tv) / med(ts), 3),
+                "over_copy": round(med(tv) / med(tc), 3), "same_records": same, "runs": runs, "calls_per_window": SETS,
+                "device_status": eng.device_status()}
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+        del out, dst, tup, es, big
+    return lines
+
+
+if "--view-only" in sys.argv:
+    res = view_ops()
+    if "--out" in sys.argv:
+        path = sys.argv[sys.argv.index("--out") + 1]
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as fh:
+            json.dump(res, fh, indent=1)
+    sys.exit(0 if all(r["device_status"] == 0 and r["same_records"] for r in res) else 1)
 
 # ---- matadd C2 / C5 ---------------------------------------------------------------------------
 for side in ((128,) if (QUICK or "big" in SKIP) else (128, 1024)):
