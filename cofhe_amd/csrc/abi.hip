@@ -2,11 +2,11 @@
 // two-build launch, flag words, the table-cache lookup), the workspace plans, the launchers (one launch site per kernel and
 // route; product_tree is the pairwise tree of them all) and the host-side tensor formats.  The kernels are declared in
 // kernels.hpp and defined in cofhe_hip.hip, wide.hip, comb.hip, affine.hip, matmul_left.hip, conv.hip, conv_ct.hip, pow_dot.hip,
-// divide.hip, lut.hip, spline.hip and view.hip; this file holds no device code of its own.  conv.hip holds the three kernels of the
+// divide.hip, lut.hip, spline.hip, view.hip and compare.hip; this file holds no device code of its own.  conv.hip holds the three kernels of the
 // convolution, conv_ct.hip the two that ciphertext filters add, pow_dot.hip the two of
 // the polynomial evaluation, divide.hip the signed floor division of the division by public divisors, lut.hip the two copies of
 // the table lookups, spline.hip the three kernels of the piecewise-polynomial activations, view.hip the two that rearrange
-// resident tensors.
+// resident tensors, compare.hip the two of the digit comparisons.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -27,6 +27,7 @@
 #include "lut.hpp"
 #include "spline.hpp"
 #include "view.hpp"
+#include "compare.hpp"
 
 using namespace cofhe;
 using namespace cofhe_k;
@@ -2230,6 +2231,108 @@ int cofhe_hip_spline_tuples_shape(uint32_t ndim_e, const uint32_t *shape_e, uint
                                       "bits >= 1, 1 <= d <= 8, 2^bits (d + 1) <= 4096");
     *bits = b;
     *d = dd;
+    return COFHE_HIP_OK;
+}
+
+// ---- the sign on a window of up to 64 bits from digit comparisons (compare.hip) ---------------------------------------------
+static_assert(COFHE_HIP_CMP_MAX_BITS == CMP_MAX_BITS && COFHE_HIP_CMP_MAX_DIGIT_BITS == CMP_MAX_DIGIT_BITS, "the header's bounds are the kernels'");
+static_assert(CMP_MAX_DIGITS + 1 == LUT_MAX_BITS, "the lookup that closes a comparison has n + 1 bits");
+namespace {
+// what every comparison entry point refuses before it looks at a pointer: the window, the digit width and the digit count
+int cmp_check(uint32_t bits, uint32_t digit_bits, uint32_t kbits, uint64_t n) {
+    if (kbits == 0 || kbits > 32u * PMM_MAX_LIMBS - 1u) return fail(COFHE_HIP_EINVAL, "k out of range");
+    if (!cmp_shape_ok(bits, digit_bits, kbits, LUT_MAX_BITS))
+        return fail(COFHE_HIP_EINVAL, "cmp: a window of 2 <= bits <= min(k, 64) bits in n = ceil(bits / d) digits of 1 <= d <= 8 bits, "
+                                      "n + 1 <= min(12, k)");
+    if (n > (1ull << 36) / (CMP_MAX_DIGITS << CMP_MAX_DIGIT_BITS)) return fail(COFHE_HIP_EINVAL, "cmp: too many items");
+    return COFHE_HIP_OK;
+}
+}  // namespace
+// touches no shared state of the context: no lock.  16-byte pieces when the output allows them (a caller's pointer is only known
+// to be 4-byte aligned)
+int cofhe_hip_cmp_rows_records(cofhe_hip_ctx *ctx, const void *d_r, void *d_out, uint64_t n, uint32_t bits, uint32_t digit_bits, uint32_t kbits,
+                               void *stream) {
+    if (int rc = cmp_check(bits, digit_bits, kbits, n)) return rc;
+    if (n == 0) return COFHE_HIP_OK;
+    if (!d_r || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
+    const uint64_t recs = (n * cmp_digits(bits, digit_bits)) << digit_bits;
+    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4;
+    if (overlaps(d_out, recs * exp_bytes, d_r, n * exp_bytes)) return fail(COFHE_HIP_EINVAL, "cmp_rows: the output overlaps the input");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const bool vec16 = ((uintptr_t)d_out & 15) == 0;
+    const uint64_t total = recs * (vec16 ? EXP_REC_WORDS / 4 : EXP_REC_WORDS);
+    const unsigned blocks = (unsigned)std::min<uint64_t>((total + CMP_ROWS_THREADS - 1) / CMP_ROWS_THREADS, 64u * NUM_CUS);       // grid-stride beyond that
+    {
+        ProfScope ps(ctx, "k_cmp_rows", st);
+        hipLaunchKernelGGL(k_cmp_rows, dim3(blocks), dim3(CMP_ROWS_THREADS), 0, st, (const uint32_t *)d_r, (uint32_t *)d_out, n, bits, digit_bits,
+                           vec16 ? 1u : 0u);
+    }
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+
+// Needs no workspace plan of its own: the rows are one block of the block cache, and the fresh encryption that follows carves
+// the workspace by the plan "comb" (kind 1) over n nd 2^d plaintexts.
+int cofhe_hip_cmp_tuples_records(cofhe_hip_ctx *ctx, const void *d_r, const void *d_rho, const uint32_t *h_record, const uint32_t *pk_record,
+                                 const uint32_t *f_record, void *d_out, uint64_t n, uint32_t bits, uint32_t digit_bits, uint32_t kbits,
+                                 void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (int rc = cmp_check(bits, digit_bits, kbits, n)) return rc;
+    const uint64_t recs = (n * cmp_digits(bits, digit_bits)) << digit_bits;
+    if (int rc = comb_check(1, recs, 0, kbits, 0, 0)) return rc;
+    if (n == 0) return COFHE_HIP_OK;
+    if (!d_r || !d_rho || !h_record || !pk_record || !f_record || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
+    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4, rows_bytes = recs * exp_bytes, out_bytes = recs * 2 * REC_WORDS * 4;
+    if (overlaps(d_out, out_bytes, d_r, n * exp_bytes) || overlaps(d_out, out_bytes, d_rho, rows_bytes))
+        return fail(COFHE_HIP_EINVAL, "cmp_tuples: the output overlaps an input");
+    DevBuf rows;                                  // T[j][c] = 2^j sgn(r_j - c), the plaintexts of the tuples
+    rows.stream = stream;
+    if (int rc = rows.get(ctx, rows_bytes)) return rc;
+    if (int rc = cofhe_hip_cmp_rows_records(ctx, d_r, rows.p, n, bits, digit_bits, kbits, stream)) return rc;
+    return cofhe_hip_encrypt_fresh_records(ctx, rows.p, d_rho, h_record, pk_record, f_record, d_out, recs, kbits, stream);
+}
+
+// no workspace and no block; the lock is held because the kernel sets the context's status word through Ctx, as k_spline_close
+int cofhe_hip_cmp_close_records(cofhe_hip_ctx *ctx, const void *d_e, const void *d_tuples, void *d_out, void *d_wrap, uint64_t n, uint32_t bits,
+                                uint32_t digit_bits, uint32_t kbits, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (int rc = cmp_check(bits, digit_bits, kbits, n)) return rc;
+    if (n == 0) return COFHE_HIP_OK;
+    if (!d_e || !d_tuples || !d_out || !d_wrap) return fail(COFHE_HIP_EINVAL, "null argument");
+    const uint64_t recs = (n * cmp_digits(bits, digit_bits)) << digit_bits;
+    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4, ct_bytes = (size_t)2 * REC_WORDS * 4, out_bytes = 2 * n * ct_bytes;
+    if (overlaps(d_out, out_bytes, d_e, n * exp_bytes) || overlaps(d_out, out_bytes, d_tuples, recs * ct_bytes) ||
+        overlaps(d_wrap, n * exp_bytes, d_e, n * exp_bytes) || overlaps(d_wrap, n * exp_bytes, d_tuples, recs * ct_bytes) ||
+        overlaps(d_wrap, n * exp_bytes, d_out, out_bytes))
+        return fail(COFHE_HIP_EINVAL, "cmp_close: an output overlaps an input or the other output");
+    unsigned blocks;
+    if (int rc = compose_blocks(2 * n, &blocks)) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    {
+        ProfScope ps(ctx, "k_cmp_close", st);
+        hipLaunchKernelGGL(k_cmp_close, dim3(blocks), dim3(WG_BLOCK), 0, st, (const uint32_t *)d_e, (const uint32_t *)d_tuples, (uint32_t *)d_out,
+                           (uint32_t *)d_wrap, n, bits, digit_bits, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+    }
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+
+// host only: nd and nd 2^d, and the tuples of opened values of shape S as a tensor of shape S + [nd, 2^d]
+int cofhe_hip_cmp_shape(uint32_t bits, uint32_t digit_bits, uint32_t kbits, uint32_t ndim_e, const uint32_t *shape_e, uint32_t ndim_t,
+                        const uint32_t *shape_t, uint32_t *digits, uint32_t *entries) {
+    if (int rc = cmp_check(bits, digit_bits, kbits, 0)) return rc;
+    const uint32_t nd = cmp_digits(bits, digit_bits);
+    if (shape_t) {
+        if (ndim_e && !shape_e) return fail(COFHE_HIP_EINVAL, "null argument");
+        if (ndim_e > 6 || ndim_t != ndim_e + 2 || (ndim_e && memcmp(shape_t, shape_e, 4 * ndim_e) != 0) || shape_t[ndim_t - 2] != nd ||
+            shape_t[ndim_t - 1] != (1u << digit_bits))
+            return fail(COFHE_HIP_ESHAPE, "cmp_close: the tuples are a ciphertext tensor of e's shape and two last dimensions "
+                                          "[ceil(bits / d), 2^d]");
+    }
+    if (digits) *digits = nd;
+    if (entries) *entries = nd << digit_bits;
     return COFHE_HIP_OK;
 }
 

@@ -7,7 +7,8 @@
 // convolution and the patch gather of a plaintext image for ciphertext filters, pow_dot.hip the multi-exponentiation
 // and the Taylor shift of the polynomial evaluation, divide.hip the signed floor division on exponent records, lut.hip the row
 // rotation and the entry selection of the table lookups, spline.hip the rows, the powers and the closing walk of the
-// piecewise-polynomial activations, view.hip the affine view and the index gather that rearrange resident tensors.
+// piecewise-polynomial activations, view.hip the affine view and the index gather that rearrange resident tensors, compare.hip the
+// rows and the closing compositions of the digit comparisons.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -200,4 +201,15 @@ __global__ void k_view_records(cofhe_hip_view v, const uint32_t *__restrict__ sr
 __global__ void k_gather_records(const uint32_t *__restrict__ src, uint64_t n_src, const uint32_t *__restrict__ index,
                                  const uint32_t *__restrict__ fill, uint32_t *__restrict__ dst, uint64_t n_out, uint32_t words, uint32_t vec16,
                                  uint32_t *__restrict__ status);
+
+// the sign on a window of up to 64 bits from digit comparisons (compare.hip; compare.hpp): the plaintext rows out[(i n + j) 2^d + c]
+// = 2^j sgn(r_ij - c) on exponent records, r_ij digit j of r[i] mod 2^bits, n = ceil(bits / d) (pure stores, a grid-stride loop;
+// vec16: out is 16-byte aligned), and the closing compositions out[2 i + s] = prod_j tuples[(i n + j) 2^d + digit j of t_s] for
+// the two thresholds t_0 = A, t_1 = B of e[i] mod 2^bits, which share the n - 1 factors below the top digit, with wrap[i] = [A > B]
+// as an exponent record (one limb group per element and half, n compositions each)
+__global__ void k_cmp_rows(const uint32_t *__restrict__ r, uint32_t *__restrict__ out, uint64_t elements, uint32_t bits, uint32_t digit_bits,
+                           uint32_t vec16);
+__global__ void k_cmp_close(const uint32_t *__restrict__ e, const uint32_t *__restrict__ tuples, uint32_t *__restrict__ out,
+                            uint32_t *__restrict__ wrap, uint64_t elements, uint32_t bits, uint32_t digit_bits,
+                            const uint32_t *__restrict__ absdelta, int half_dbits, uint32_t *__restrict__ status);
 }  // namespace cofhe_k

@@ -211,6 +211,47 @@ class Engine:
             for p in held:
                 self.free(p)
 
+    def cmp_close_tensors_bytes(self, e: bytes, tuples: bytes, bits: int, digit_bits: int, kbits: int):
+        """e (plaintext tensor of the opened values x - r, shape S, at most 6 dimensions) and tuples (ciphertext tensor of the
+        comparison tuples' entries, shape S + [nd, 2^digit_bits], nd = ceil(bits / digit_bits)) -> (the ciphertext tensor of the
+        pairs [S_A], [S_B], shape S + [2], the plaintext tensor wrap of shape S).  Composed here from unpack_tensor_device (which
+        validates the incoming forms), cmp_shape (COFHE_HIP_ESHAPE when the tuples' shape is anything else), cmp_close_records
+        and pack_tensor_device, exactly as lut_select_tensors_bytes is: the library has no entry point of its own for it."""
+        held = []
+
+        def load(t, kind):
+            # every integer owns an 8-byte table entry: the record count is bounded by the length
+            cap = (len(t) // 8) // (3 if kind else 1) + 1
+            raw = self.malloc(len(t) + 4)
+            held.append(raw)
+            recs = self.malloc(cap * 4 * (REC_WORDS if kind else EXP_REC_WORDS))
+            held.append(recs)
+            self.upload(raw, t)
+            shape, n = self.unpack_tensor_device(raw, len(t), kind, recs, cap)
+            return recs, shape, n
+
+        def packed(recs, n_records, kind, shape):
+            cap = self.packed_size_bound(n_records, kind, len(shape))
+            buf = self.malloc(cap)
+            held.append(buf)
+            ln = self.pack_tensor_device(recs, n_records, kind, shape, buf, cap)
+            return self.download(buf, ln, dtype="uint8").tobytes()
+
+        try:
+            de, se, ne = load(e, 0)
+            dt, st, nt = load(tuples, 2)
+            _, entries = self.cmp_shape(bits, digit_bits, kbits, se, st)
+            assert nt == 2 * ne * entries                              # the counts are the shapes' products
+            dout = self.malloc(max(ne, 1) * 4 * REC_WORDS * 4)
+            held.append(dout)
+            dwrap = self.malloc(max(ne, 1) * EXP_REC_WORDS * 4)
+            held.append(dwrap)
+            self.cmp_close_records(de, dt, dout, dwrap, ne, bits, digit_bits, kbits)
+            return packed(dout, 4 * ne, 2, se + [2]), packed(dwrap, ne, 0, se)
+        finally:
+            for p in held:
+                self.free(p)
+
     def scal_ciphertext_tensors(self, s: bytes, cts: bytes, zero: bytes = None) -> bytes:
         out = C.POINTER(C.c_uint8)()
         n = C.c_size_t()
@@ -659,6 +700,40 @@ class Engine:
         ciphertexts; d_out must not overlap an input"""
         _chk(self.L.cofhe_hip_spline_close_records(self.ctx, C.c_void_p(d_e), C.c_void_p(d_tuples), C.c_void_p(d_out), C.c_uint64(n),
                                                    C.c_uint32(bits), C.c_uint32(shift), C.c_uint32(d), C.c_uint32(kbits), C.c_void_p(stream)))
+
+    def cmp_rows_records(self, d_r, d_out, n, bits, digit_bits, kbits, stream=0):
+        """the plaintext rows of n comparison tuples on exponent records: out[(i nd + j) 2^d + c] = 2^j sgn(r_ij - c), r_ij digit j
+        of r[i] mod 2^bits, nd = ceil(bits / d) (r: n, out: n nd 2^d); d_out must not overlap d_r"""
+        _chk(self.L.cofhe_hip_cmp_rows_records(self.ctx, C.c_void_p(d_r), C.c_void_p(d_out), C.c_uint64(n), C.c_uint32(bits),
+                                               C.c_uint32(digit_bits), C.c_uint32(kbits), C.c_void_p(stream)))
+
+    def cmp_tuples_records(self, d_r, d_rho, h_record, pk_record, f_record, d_out, n, bits, digit_bits, kbits, stream=0):
+        """the entries of n comparison tuples: cmp_rows_records, then encrypt_fresh_records over the n nd 2^d rows with the
+        randomness rho (as many exponent records, each used once); h_record, pk_record, f_record: host uint32[168]; d_out:
+        n nd 2^d ciphertexts"""
+        import numpy as np
+        recs = [np.ascontiguousarray(r, dtype=np.uint32) for r in (h_record, pk_record, f_record)]
+        assert all(r.size == 168 for r in recs)
+        _chk(self.L.cofhe_hip_cmp_tuples_records(self.ctx, C.c_void_p(d_r), C.c_void_p(d_rho), *[r.ctypes.data_as(C.POINTER(C.c_uint32)) for r in recs],
+                                                 C.c_void_p(d_out), C.c_uint64(n), C.c_uint32(bits), C.c_uint32(digit_bits), C.c_uint32(kbits),
+                                                 C.c_void_p(stream)))
+
+    def cmp_shape(self, bits, digit_bits, kbits, shape_e=None, shape_t=None):
+        """host only: (nd, nd 2^d) of a comparison on a window of `bits` bits in digits of digit_bits bits (COFHE_HIP_EINVAL for
+        the parameter bounds); with shape_t, also COFHE_HIP_ESHAPE unless shape_t = shape_e + [nd, 2^d]"""
+        nd, entries = C.c_uint32(), C.c_uint32()
+        se, st = list(shape_e or []), shape_t
+        _chk(self.L.cofhe_hip_cmp_shape(C.c_uint32(bits), C.c_uint32(digit_bits), C.c_uint32(kbits), C.c_uint32(len(se)),
+                                        (C.c_uint32 * max(len(se), 1))(*se), C.c_uint32(len(st) if st is not None else 0),
+                                        (C.c_uint32 * max(len(st), 1))(*st) if st is not None else None, C.byref(nd), C.byref(entries)))
+        return nd.value, entries.value
+
+    def cmp_close_records(self, d_e, d_tuples, d_out, d_wrap, n, bits, digit_bits, kbits, stream=0):
+        """the closing step of a comparison's first round: out[2 i + s] = the product of the nd entries of element i's tuple that
+        threshold s (A, then B) of e[i] mod 2^bits selects, wrap[i] = [A > B]; e: n exponent records of the opened values x - r,
+        tuples: n nd 2^d ciphertexts, out: 2 n ciphertexts, wrap: n exponent records; the outputs must not overlap an input"""
+        _chk(self.L.cofhe_hip_cmp_close_records(self.ctx, C.c_void_p(d_e), C.c_void_p(d_tuples), C.c_void_p(d_out), C.c_void_p(d_wrap),
+                                                C.c_uint64(n), C.c_uint32(bits), C.c_uint32(digit_bits), C.c_uint32(kbits), C.c_void_p(stream)))
 
     def decrypt_records(self, d_cts, d_sk, f_record, d_out, n_ciphertexts, kbits, stream=0):
         """f_record: host numpy uint32[168]; d_out: n * (ceil(k/32) + 1) words"""

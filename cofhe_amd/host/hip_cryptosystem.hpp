@@ -1087,6 +1087,76 @@ class HIPCryptoSystem {
         return out;
     }
 
+    // ---- the sign on a window of up to 64 bits from digit comparisons (cofhe_hip_cmp_*; include/cofhe_hip.h states the protocol) ----
+    // n = ceil(bits / digit_bits) digits and n 2^digit_bits entries per element; refuses what cofhe_hip_cmp_shape refuses
+    struct CmpShape {
+        uint32_t digits, entries;
+    };
+    CmpShape cmp_shape(uint32_t bits, uint32_t digit_bits) const {
+        CmpShape s{0, 0};
+        check(cofhe_hip_cmp_shape(bits, digit_bits, k_, 0, nullptr, 0, nullptr, &s.digits, &s.entries));
+        return s;
+    }
+    // the digit width for a window of `bits` bits that needs the fewest ciphertexts per element: n 2^d of the comparison tuple
+    // and 2 2^(n + 1) of the two lookups that close it; the smallest such d, 0 when the bounds allow none
+    uint32_t cmp_pick_digit_bits(uint32_t bits) const {
+        uint32_t best = 0;
+        uint64_t best_cost = 0;
+        for (uint32_t d = 1; d <= COFHE_HIP_CMP_MAX_DIGIT_BITS; d++) {
+            uint32_t n = 0;
+            if (cofhe_hip_cmp_shape(bits, d, k_, 0, nullptr, 0, nullptr, &n, nullptr) != COFHE_HIP_OK) continue;
+            const uint64_t cost = ((uint64_t)n << d) + ((uint64_t)1 << (n + 2));
+            if (best == 0 || cost < best_cost) {
+                best = d;
+                best_cost = cost;
+            }
+        }
+        return best;
+    }
+    // the plaintext rows of the comparison tuples: res[i, j, c] = 2^j sgn(r_ij - c), r_ij digit j of r[i] mod 2^bits, a tensor
+    // [n, digits, 2^digit_bits] for the n masks r (cofhe_hip_cmp_rows_records, k_cmp_rows)
+    Tensor<PlainText *> cmp_rows_plaintext_tensor(const Tensor<PlainText *> &r, uint32_t bits, uint32_t digit_bits) const {
+        const size_t n = r.num_elements();
+        const CmpShape s = cmp_shape(bits, digit_bits);
+        Staged dr = stage(pack_exponents(r)), drows = device_buffer(n * s.entries * EXPW * 4);
+        check(cofhe_hip_cmp_rows_records(ctx_, dr.ptr, drows.ptr, n, bits, digit_bits, k_, nullptr));
+        return read_plaintexts(drows.ptr, n * s.entries, EXPW, {n, (size_t)s.digits, (size_t)1 << digit_bits}, true);
+    }
+    // the entries of the comparison tuples: FRESH encryptions of those rows, a tensor [n, digits, 2^digit_bits]
+    // (cofhe_hip_cmp_tuples_records: the rows and the fresh-randomness comb, on the device from end to end).  Every entry has
+    // its own randomness WHATEVER the randomness mode: under a shared r the tuple would give the digits of the mask away.
+    Tensor<CipherText *> cmp_tuples_ciphertext_tensor(const PublicKey &pk, const Tensor<PlainText *> &r, uint32_t bits, uint32_t digit_bits) const {
+        const size_t n = r.num_elements();
+        const CmpShape s = cmp_shape(bits, digit_bits);
+        Staged dr = stage(pack_exponents(r)), drho = stage(draw_randomness(n * s.entries));
+        const std::array<uint32_t, REC> pkrec = record_of(pk);
+        DeviceTensor out = alloc(std::vector<size_t>{n, (size_t)s.digits, (size_t)1 << digit_bits}, n * s.entries);
+        check(cofhe_hip_cmp_tuples_records(ctx_, dr.ptr, drho.ptr, h_rec_.data(), pkrec.data(), f_rec_.data(), out.ptr_, n, bits, digit_bits, k_, nullptr));
+        return download(std::move(out));
+    }
+    // the closing step of a comparison's first round, for the opened values e = x - r and the tuple entries [n, digits,
+    // 2^digit_bits] of the masks r: pairs[i, 0] = [S_A], pairs[i, 1] = [S_B], the products of the entries that the two thresholds
+    // of e[i] mod 2^bits select, and wrap[i] = [A > B] (cofhe_hip_cmp_close_records).  The pairs carry the randomness of the
+    // entries they are products of, so they get no re-randomisation pass in any mode.
+    struct CmpClosed {
+        Tensor<CipherText *> pairs;          // [n, 2]
+        Tensor<PlainText *> wrap;            // [n]
+    };
+    CmpClosed cmp_close_ciphertext_tensor(const Tensor<PlainText *> &e, const Tensor<CipherText *> &tuples, uint32_t bits, uint32_t digit_bits) const {
+        return cmp_close_ciphertext_tensor(e, upload(tuples), bits, digit_bits);
+    }
+    // the same on resident tuples
+    CmpClosed cmp_close_ciphertext_tensor(const Tensor<PlainText *> &e, const DeviceTensor &tuples, uint32_t bits, uint32_t digit_bits) const {
+        const size_t E = e.num_elements();
+        const CmpShape s = cmp_shape(bits, digit_bits);
+        if (E == 0 || tuples.n_ != E * s.entries) throw std::invalid_argument("comparison tuples: ceil(bits / d) 2^d entries for every opened value");
+        Staged de = stage(pack_exponents(e)), dwrap = device_buffer(E * EXPW * 4);
+        DeviceTensor out = alloc(std::vector<size_t>{E, 2}, 2 * E);
+        check(cofhe_hip_cmp_close_records(ctx_, de.ptr, tuples.ptr_, out.ptr_, dwrap.ptr, E, bits, digit_bits, k_, nullptr));
+        Tensor<PlainText *> wrap = read_plaintexts(dwrap.ptr, E, EXPW, {E}, true);
+        return CmpClosed{download(std::move(out)), wrap};
+    }
+
     // ---- device-resident variants -------------------------------------------------------------
     // the block behind a tensor whose elements are, in order, ALL the elements of one device block (the result of
     // a previous operation handed back unchanged); nullptr otherwise

@@ -1034,6 +1034,148 @@ static void bench_lookup(const Args &arg) {
     if (!ok) throw std::runtime_error("lookup mismatch");
 }
 
+// the exact sign, ReLU and max of values on a window of `bits` bits from digit comparisons
+// (LocalCipherTextMultiplier::is_nonnegative_ciphertext_tensor, relu_wide_ciphertext_tensor, max_wide_ciphertext_tensors),
+// through the single-key and the 2-of-3 threshold client: the edges -2^(bits-1), -1, 0, 1, 2^(bits-1) - 1, then uniform values of
+// the window (the max runs on their halves, whose difference stays in it).  Every decrypted element must EQUAL the integer
+// computation; prints the opened values per element (3 for the sign, 5 for ReLU and max) and whether all c1 of one tuple tensor
+// are pairwise distinct in the default randomness mode.  runs > 0: medians of `runs` calls of the wide ReLU, of its tuple
+// generation, its opening and its closing step, and of the 8-bit lookup ReLU over the same element count, on one line
+static void bench_compare(const Args &arg) {
+    const size_t n = arg(2, 256);
+    const uint32_t bits = (uint32_t)arg(3, 32), digit_bits = (uint32_t)arg(4, 0);
+    const int runs = arg.integer(5, 0);
+    Fixture fx;
+    auto &cs = fx.cs;
+    const auto &sk = fx.sk;
+    const uint32_t k = cs.message_bits();
+    if (bits < 3 || bits > 64 || bits > k) throw std::invalid_argument("compare: a window of 3 to min(k, 64) bits");
+    const uint32_t d = digit_bits ? digit_bits : cs.cmp_pick_digit_bits(bits);
+    const auto shape = cs.cmp_shape(bits, d);
+    auto window = [&](uint64_t u) { return bits == 64 ? (int64_t)u : (int64_t)(u << (64 - bits)) >> (64 - bits); };      // sign-extended
+    const int64_t lo = window((uint64_t)1 << (bits - 1)), hi = (int64_t)(((uint64_t)1 << (bits - 1)) - 1);
+    std::vector<int64_t> xs(n), ys(n);
+    const int64_t fixed[5] = {lo, -1, 0, 1, hi};
+    for (size_t i = 0; i < n; i++) {
+        xs[i] = i < 5 ? fixed[i] : window(mpz_get_ui(cs.random_plaintext(bits).get()));
+        ys[i] = i < 5 ? fixed[4 - i] : window(mpz_get_ui(cs.random_plaintext(bits).get()));
+    }
+    auto residue = [&](int64_t v) {                                 // v mod 2^k
+        Mpz m;
+        mpz_set_si(m.get(), (long)v);
+        mpz_fdiv_r_2exp(m.get(), m.get(), k);
+        return m;
+    };
+    Owned<PT> px = plain_tensor(fx, {n}, [&](size_t i) { return residue(xs[i]); });
+    Owned<PT> pa = plain_tensor(fx, {n}, [&](size_t i) { return residue(xs[i] >> 1); });
+    Owned<PT> pb = plain_tensor(fx, {n}, [&](size_t i) { return residue(ys[i] >> 1); });
+    std::cout << "compare: " << n << " elements, window " << bits << " bits, " << shape.digits << " digits of " << d << " bits, " << shape.entries
+              << " + " << ((size_t)4 << shape.digits) << " ciphertexts of tuples per element" << std::endl;
+    bool ok = true;
+    for_both_clients(fx, [&](Client &client, Multiplier &mul, const std::string &who, bool threshold) {
+        const auto &pk = client.network_public_key();
+        Owned<CT> cx = cs.encrypt_tensor(pk, px), ca = cs.encrypt_tensor(pk, pa), cb = cs.encrypt_tensor(pk, pb);
+        const char *names[3] = {"sign", "relu", "max"};
+        const size_t per_element[3] = {3, 5, 5};
+        for (int what = 0; what < 3; what++) {
+            std::vector<Mpz> want(n);
+            for (size_t i = 0; i < n; i++)
+                want[i] = residue(what == 0 ? (xs[i] >= 0 ? 1 : 0) : what == 1 ? std::max<int64_t>(xs[i], 0) : std::max(xs[i] >> 1, ys[i] >> 1));
+            const size_t before = client.decrypted_elements();
+            cs.synchronize();
+            auto [ms, res] = timed(cs, [&]() -> Owned<CT> {
+                return what == 0 ? mul.is_nonnegative_ciphertext_tensor(cx, bits, digit_bits)
+                                 : what == 1 ? mul.relu_wide_ciphertext_tensor(cx, bits, digit_bits) : mul.max_wide_ciphertext_tensors(ca, cb, bits - 1, digit_bits);
+            });
+            const size_t opened = client.decrypted_elements() - before;
+            const bool pass = decrypts_to(fx, res, want) && opened == per_element[what] * n;
+            if (!threshold && what == 1) write_ciphertexts(fx, "local_bench_compare.bin", res);
+            std::cout << "  " << who << ": " << names[what] << " over " << n << " elements, opened_values_per_element " << (double)opened / (double)n << ", "
+                      << ms << " ms (host wall clock, tuple generation and the decryptions included): " << (pass ? "ok" : "FAILED") << std::endl;
+            ok = ok && pass;
+        }
+        if (threshold) return;
+        // the parts on their own: one 0-D element, the plaintext rows, the refusals, and the randomness of a tuple tensor
+        Owned<CT> y0 = mul.relu_wide_ciphertext_tensor(Tensor<CT *>(cx[4 % n]), bits, digit_bits);
+        bool parts = y0->is_zero_degree() && cs.decrypt(sk, *y0->get_value()) == residue(std::max<int64_t>(xs[4 % n], 0));
+        Mpz five(5ul);
+        Owned<PT> rows = cs.cmp_rows_plaintext_tensor(Tensor<PT *>(1, &five), bits, d);
+        for (uint32_t j = 0; j < shape.digits; j++)
+            for (uint32_t c = 0; c < (1u << d); c++) {
+                const int64_t rj = (int64_t)((5u >> (j * d < 32 ? j * d : 31)) & ((1u << d) - 1u)), s = rj > (int64_t)c ? 1 : rj < (int64_t)c ? -1 : 0;
+                parts = parts && mpz_cmp_si(rows[(j << d) + c]->get(), (long)(s * ((int64_t)1 << j))) == 0;
+            }
+        int refused = 0;
+        try {
+            (void)mul.is_nonnegative_ciphertext_tensor(cx, 65);
+        } catch (const std::invalid_argument &) {
+            refused++;
+        }
+        try {
+            (void)mul.is_nonnegative_ciphertext_tensor(cx, 64, 5);                  // 13 digits: the closing lookup would have 14 bits
+        } catch (const std::invalid_argument &) {
+            refused++;
+        }
+        try {
+            (void)mul.max_wide_ciphertext_tensors(ca, cb, 64);
+        } catch (const std::invalid_argument &) {
+            refused++;
+        }
+        parts = parts && refused == 3;
+        std::cout << "  0-D relu, cmp_rows_plaintext_tensor, the refusals of 65 bits, of 13 digits and of a max at 64 bits: " << (parts ? "ok" : "FAILED")
+                  << std::endl;
+        ok = ok && parts;
+        const bool default_mode = cs.tensor_randomness() == TensorRandomness::None;
+        auto tuples = client.get_comparison_tuples(4, bits, d);
+        size_t count = 0;
+        for (auto &t : tuples) count += t.num_elements();
+        const bool distinct = default_mode && count == 4 + 4 * (size_t)shape.entries && distinct_c1(tuples);
+        std::cout << "  " << count << " ciphertexts of the tuples of 4 elements, default randomness mode, distinct c1: " << (distinct ? "yes" : "NO")
+                  << std::endl;
+        ok = ok && distinct;
+        for (auto &t : tuples) free_all(t);
+    });
+    write_absdelta(fx);
+    if (runs > 0) {
+        Client client(cs, sk);
+        Multiplier mul(client);
+        const auto &pk = client.network_public_key();
+        Owned<CT> cx = cs.encrypt_tensor(pk, px);
+        Owned<PT> p8 = plain_tensor(fx, {n}, [&](size_t i) { return residue((int64_t)(int8_t)(xs[i] & 0xFF)); });
+        Owned<CT> c8 = cs.encrypt_tensor(pk, p8);
+        const auto relu_ms = median_runs(cs, runs, [&]() { return mul.relu_wide_ciphertext_tensor(cx, bits, digit_bits); });
+        const auto sign_ms = median_runs(cs, runs, [&]() { return mul.is_nonnegative_ciphertext_tensor(cx, bits, digit_bits); });
+        const auto relu8_ms = median_runs(cs, runs, [&]() { return mul.relu_ciphertext_tensor(c8, 8); });
+        // the three parts of round 1 on their own: the tuples, the opening of x - r, the closing compositions
+        std::vector<double> tuples_ms, open_ms, close_ms;
+        for (int pass = 0; pass <= runs; pass++) {
+            cs.synchronize();
+            auto a = timed(cs, [&]() { return client.get_comparison_tuples(n, bits, d); });
+            Owned<CT> diff = cs.sub_ciphertext_tensors(pk, cx, a.second[0]);
+            cs.synchronize();
+            auto b = timed(cs, [&]() -> Owned<PT> { return client.decrypt_tensor(diff); });
+            cs.synchronize();
+            auto c = timed(cs, [&]() { return cs.cmp_close_ciphertext_tensor(b.second, a.second[1], bits, d); });
+            free_all(c.second.pairs);
+            free_all(c.second.wrap);
+            for (auto &t : a.second) free_all(t);
+            if (pass) {
+                tuples_ms.push_back(a.first);
+                open_ms.push_back(b.first);
+                close_ms.push_back(c.first);
+            }
+        }
+        for (auto *v : {&tuples_ms, &open_ms, &close_ms}) std::sort(v->begin(), v->end());
+        std::cout << "compare_json: {\"E\": " << n << ", \"bits\": " << bits << ", \"digit_bits\": " << d << ", \"digits\": " << shape.digits
+                  << ", \"runs\": " << runs << ", " << MsJson{"relu_wide_ms", "relu_wide_ms_min_max", relu_ms} << ", "
+                  << MsJson{"sign_ms", "sign_ms_min_max", sign_ms} << ", " << MsJson{"tuples_ms", "tuples_ms_min_max", tuples_ms} << ", "
+                  << MsJson{"open_ms", "open_ms_min_max", open_ms} << ", " << MsJson{"close_ms", "close_ms_min_max", close_ms} << ", "
+                  << MsJson{"relu_lookup_8bit_ms", "relu_lookup_8bit_ms_min_max", relu8_ms} << "}" << std::endl;
+    }
+    std::cout << "  agree: " << (ok ? "yes" : "NO") << std::endl;
+    if (!ok) throw std::runtime_error("compare mismatch");
+}
+
 // a piecewise-polynomial activation on a ciphertext tensor from one opened value per element
 // (LocalCipherTextMultiplier::evaluate_spline_ciphertext_tensor), through the single-key and the 2-of-3 threshold client: the
 // logistic sigmoid on [-8, 8) as 2^bits pieces of degree d over a (shift + bits)-bit window, 40 fraction bits out
@@ -1805,6 +1947,7 @@ static const struct Mode {
     {"poly_activation", "[elements=64 [runs=0]]", bench_poly_activation},
     {"divide", "[elements=64 [runs=0]]", bench_divide},
     {"lookup", "[elements=64 [runs=0]]", bench_lookup},
+    {"compare", "[elements=256 [bits=32 [digit_bits=0 [runs=0]]]]", bench_compare},
     {"spline", "[elements=256 [runs=0 [bits=5 [shift=11 [degree=2]]]]]", bench_spline},
     {"rearrange", "[B=1 H=5 W=4 C=2 kh=3 kw=2 [sh=2 sw=1 ph=1 pw=1 dh=1 dw=1]]", bench_rearrange},
     {"formats", "", bench_formats},

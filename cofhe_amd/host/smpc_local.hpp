@@ -48,6 +48,12 @@
 // minus the piece's origin, per element:  e = Dec(x - r);  j = seg(e);  [y] = [q_{j,0}] o prod_{i=1..d} [q_{j,i}]^(e^i) -- one
 // opened value, one round, 2^b (d + 1) ciphertexts per element for a (t + b)-bit window; y is the value at x of the element's
 // own piece or of the piece below (the carry of the low t bits is lost), so a piece serves two segments.
+//
+// Sign, ReLU and max on windows of up to 64 bits (is_nonnegative_ciphertext_tensor, relu_wide_ciphertext_tensor,
+// max_wide_ciphertext_tensors; the reference has no comparison).  With a comparison tuple ([r], [T]), T[j][c] = 2^j sgn(r_j - c)
+// over the n = ceil(bits / d) digits of r mod 2^bits:  e = Dec(x - r) names two thresholds A, B with [x < 0] = [r >= A] - [r >= B]
+// + [A > B];  [S_t] = prod_j [T[j][t_j]] has the sign of r - t;  one lookup of n + 1 bits over [S_A], [S_B] closes it -- two
+// rounds, three opened values per element, n 2^d + 2^(n+2) ciphertexts per element where a lookup takes 2^bits; exact.
 #pragma once
 #include "hip_cryptosystem.hpp"
 
@@ -211,6 +217,22 @@ class LocalSMPCClient {
         Vector<Tensor<CipherText *>> t;
         t.push_back(cs_.encrypt_tensor_per_element(pk_, pr));
         t.push_back(cs_.spline_tuples_ciphertext_tensor(pk_, table, pr, bits, shift));
+        for (size_t i = 0; i < n; i++) delete pr[i];
+        return t;
+    }
+
+    // comparison tuples for n elements on a window of `bits` bits in digits of digit_bits bits: {[r] (n elements), [T] (n nd 2^d
+    // elements, [n, nd, 2^d], nd = ceil(bits / d))} with r uniform in Z/2^k per element and T[i, j, c] = 2^j sgn(r_ij - c), r_ij
+    // digit j of r_i mod 2^bits, used once; the caller owns the elements.  [r] and every [T] are encrypted with their OWN
+    // randomness whatever the randomness mode, for the reason given for the lookups.  Like the triplets, the tuples of the
+    // networked system would come from a protocol between the nodes.
+    Vector<Tensor<CipherText *>> get_comparison_tuples(size_t n, uint32_t bits, uint32_t digit_bits) {
+        (void)cs_.cmp_shape(bits, digit_bits);                   // refuse before anything is drawn
+        Tensor<PlainText *> pr(n, nullptr);
+        for (size_t i = 0; i < n; i++) pr[i] = new PlainText(cs_.random_plaintext(cs_.message_bits()));
+        Vector<Tensor<CipherText *>> t;
+        t.push_back(cs_.encrypt_tensor_per_element(pk_, pr));
+        t.push_back(cs_.cmp_tuples_ciphertext_tensor(pk_, pr, bits, digit_bits));
         for (size_t i = 0; i < n; i++) delete pr[i];
         return t;
     }
@@ -522,6 +544,90 @@ class LocalCipherTextMultiplier {
         if (!taps[0].owned)                          // a 1 x 1 window: the caller owns copies, as of every result tensor
             for (size_t i = 0; i < n_out; i++) res[i] = new CipherText(*res[i]);
         res.reshape({B, Ho, Wo, C});
+        return res;
+    }
+
+    // [x >= 0] element-wise (an encryption of 1 or 0) for x in the signed window of `bits` bits, 2 <= bits <= min(k, 64), exactly
+    // and with no failure probability: with a comparison tuple per element, round 1 opens e = Dec(x - r) and composes, for the two
+    // thresholds of e, the entries that their digits select; round 2 is ONE lookup of n + 1 bits over the 2 E products.  Three
+    // opened values per element, and n 2^d + 2^(n + 2) ciphertexts of tuples for n = ceil(bits / d) digits where a lookup takes
+    // 2^bits.  digit_bits = 0 picks the d that needs the fewest.  0-D and 1-D tensors; higher ranks are flattened and the result
+    // reshaped.
+    Tensor<CipherText *> is_nonnegative_ciphertext_tensor(const Tensor<CipherText *> &x, uint32_t bits, uint32_t digit_bits = 0) {
+        auto &cs = client_m.crypto_system();
+        const auto &pk = client_m.network_public_key();
+        const uint32_t d = digit_bits ? digit_bits : cs.cmp_pick_digit_bits(bits);
+        const uint32_t n = cs.cmp_shape(bits, d).digits;         // refuses d = 0 (no digit width fits) with everything else
+        return open_and_close(x, client_m.get_comparison_tuples(x.num_elements(), bits, d),
+                              [&](const Tensor<PlainText *> &e, const Vector<Tensor<CipherText *>> &tuples) {
+                                  const size_t E = e.num_elements();
+                                  auto closed = cs.cmp_close_ciphertext_tensor(e, tuples[1], bits, d);
+                                  // g[v] = 1 for v < 2^n, the non-negative half of the (n + 1)-bit two's-complement range
+                                  const size_t size = (size_t)2 << n;
+                                  std::vector<PlainText> vals(size);
+                                  Tensor<PlainText *> table(size, nullptr);
+                                  for (size_t v = 0; v < size; v++) {
+                                      if (v < size / 2) mpz_set_ui(vals[v].get(), 1ul);
+                                      table[v] = &vals[v];
+                                  }
+                                  Tensor<CipherText *> s = closed.pairs;
+                                  s.flatten();
+                                  auto g = lookup_ciphertext_tensor(table, s);
+                                  Tensor<CipherText *> ga(E, nullptr), gb(E, nullptr);
+                                  Tensor<PlainText *> c(E, nullptr);
+                                  for (size_t i = 0; i < E; i++) {
+                                      ga[i] = g[2 * i];
+                                      gb[i] = g[2 * i + 1];
+                                      c[i] = new PlainText(mpz_sgn(closed.wrap[i]->get()) != 0 ? 0ul : 1ul);
+                                  }
+                                  // [x >= 0] = (1 - wrap) - g(S_A) + g(S_B)
+                                  auto diff = cs.sub_ciphertext_tensors(pk, gb, ga);
+                                  auto res = cs.add_plaintext_tensor(pk, diff, c);
+                                  for (size_t i = 0; i < E; i++) {
+                                      delete s[2 * i];
+                                      delete s[2 * i + 1];
+                                      delete closed.wrap[i];
+                                      delete ga[i];
+                                      delete gb[i];
+                                      delete c[i];
+                                      delete diff[i];
+                                  }
+                                  return res;
+                              });
+    }
+    // max(x, 0) for x in the signed window of `bits` bits, 2 <= bits <= min(k, 64), exactly: x [x >= 0], the sign above and one
+    // Beaver product; five opened values per element.  Shapes as above.
+    Tensor<CipherText *> relu_wide_ciphertext_tensor(const Tensor<CipherText *> &x, uint32_t bits, uint32_t digit_bits = 0) {
+        Tensor<CipherText *> flat = x.is_zero_degree() ? Tensor<CipherText *>(1, x.get_value()) : x;
+        flat.flatten();
+        auto nonneg = is_nonnegative_ciphertext_tensor(flat, bits, digit_bits);
+        auto res = handle_vector_ciphertext_mul(flat, nonneg);
+        for (size_t i = 0; i < nonneg.num_elements(); i++) delete nonneg[i];
+        if (x.is_zero_degree()) return Tensor<CipherText *>(res.at(0));
+        res.reshape(x.shape());
+        return res;
+    }
+    // max(a, b) element-wise for values in the signed window of `bits` bits: b + relu(a - b), the difference a (bits + 1)-bit
+    // signed value, so 1 <= bits <= 63 and bits + 1 <= k
+    Tensor<CipherText *> max_wide_ciphertext_tensors(const Tensor<CipherText *> &a, const Tensor<CipherText *> &b, uint32_t bits, uint32_t digit_bits = 0) {
+        if (bits == 0 || bits > 63) throw std::invalid_argument("max_wide_ciphertext_tensors: 1 <= bits <= 63");
+        auto &cs = client_m.crypto_system();
+        const auto &pk = client_m.network_public_key();
+        auto diff = cs.sub_ciphertext_tensors(pk, a, b);
+        auto pos = relu_wide_ciphertext_tensor(diff, bits + 1, digit_bits);
+        auto res = cs.add_ciphertext_tensors(pk, b, pos);
+        if (diff.is_zero_degree()) {
+            delete diff.get_value();
+            delete pos.get_value();
+        } else {
+            Tensor<CipherText *> fd = diff, fp = pos;
+            fd.flatten();
+            fp.flatten();
+            for (size_t i = 0; i < fd.num_elements(); i++) {
+                delete fd[i];
+                delete fp[i];
+            }
+        }
         return res;
     }
 

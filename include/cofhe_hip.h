@@ -33,6 +33,9 @@
  *   cofhe_hip_spline_rows_...,       nothing: a piecewise polynomial (sigmoid, tanh, GELU, exp, 1/x as splines) over a (shift + bits)-bit
  *   cofhe_hip_spline_tuples_...,     window on a ciphertext tensor from ONE opened value per element (spline tuples of 2^bits (d + 1)
  *   cofhe_hip_spline_close_...       ciphertexts, not 2^(shift + bits)); the reference has no such operation
+ *   cofhe_hip_cmp_rows_...,          nothing: the exact sign (ReLU, max) of a value on a window of up to 64 bits, from digit
+ *   cofhe_hip_cmp_tuples_...,        comparisons against a masked opened value and one small lookup (comparison tuples of
+ *   cofhe_hip_cmp_close_...          ceil(bits / d) 2^d ciphertexts, not 2^bits); the reference has no comparison
  *   cofhe_hip_decrypt_records        decrypt_tensor's per-element work, cpu_cryptosystem_tensor_ops.inl:21-33
  *   cofhe_hip_part_decrypt_records,  part_decrypt_tensor / combine_part_decryption_results_tensor,
  *   cofhe_hip_combine_part_...       cpu_cryptosystem_tensor_ops.inl:35-73 (cpu_cryptosystem_distributed.inl:231-285)
@@ -403,6 +406,54 @@ int cofhe_hip_lut_select_records(cofhe_hip_ctx *ctx, const void *d_e, const void
 /* host only, no GPU: *bits of the tuples that go with opened values of shape shape_e[ndim_e], ndim_e <= 7.  COFHE_HIP_ESHAPE unless
  * shape_t is shape_e with one more, last dimension of 2^bits entries, 1 <= bits <= COFHE_HIP_LUT_MAX_BITS. */
 int cofhe_hip_lut_tuples_shape_bits(uint32_t ndim_e, const uint32_t *shape_e, uint32_t ndim_t, const uint32_t *shape_t, uint32_t *bits);
+/* ---- the sign on a window of up to 64 bits from digit comparisons (cofhe_amd/csrc/compare.hip, compare.hpp) ----
+ * For values known to lie in the signed window of l = bits bits, 2 <= l <= min(k, 64), the sign is computed exactly in two rounds
+ * with a tuple that grows with (l / d) 2^d, not 2^l.  r mod 2^l is read as n = ceil(l / d) digits r_j of d = digit_bits bits, 1 <=
+ * d <= COFHE_HIP_CMP_MAX_DIGIT_BITS, n + 1 <= min(COFHE_HIP_LUT_MAX_BITS, k).  A COMPARISON TUPLE of an element is ([r], [T]) with r
+ * uniform in Z/2^k and T[j][c] = 2^j sgn(r_j - c) mod 2^k, j < n, c < 2^d (every digit has 2^d entries, also the top one when d
+ * does not divide l), used once.  Round 1 opens e = Dec([x] - [r]); with u = e mod 2^l, x < 0 exactly when r mod 2^l lies in the
+ * cyclic interval [A, B), A = (2^(l-1) - u) mod 2^l, B = -u mod 2^l, so [x < 0] = [r >= A] - [r >= B] + wrap, wrap = [A > B] public.
+ * For a public threshold t, S_t = sum_j 2^j sgn(r_j - t_j) lies in (-2^n, 2^n) and [r >= t] = [S_t >= 0]; [S_t] = prod_j [T[j][t_j]].
+ * A and B differ in the top digit only.  Round 2 is one lookup (above) of n + 1 bits over the 2 E values [S_A], [S_B] with the
+ * table g[v] = 1 for v < 2^n, 0 otherwise: [x >= 0] = (1 - wrap) - g(S_A) + g(S_B).  EVERY T[j][c] MUST CARRY ITS OWN RANDOMNESS, for
+ * the reason given for the lookups.  A tuple is n 2^d * 1344 bytes per element.
+ * "u of a record" below: the low l bits of its value mod 2^k, read from words 0 and 1 and the sign word -- the 64-bit two's
+ * complement of the two words under a set sign word; -0 and magnitudes of 2^k and above follow the same rule.
+ * The records entry points: stream-ordered, no read-back of their own; 16-byte accesses where the pointers allow them, 4-byte ones
+ * otherwise.  COFHE_HIP_EINVAL, nothing written: bits < 2, bits > 64, bits > kbits; digit_bits = 0 or > 8; n + 1 >
+ * min(COFHE_HIP_LUT_MAX_BITS, kbits); kbits out of range; an output overlapping an input.  n = 0 does nothing. */
+#define COFHE_HIP_CMP_MAX_BITS 64
+#define COFHE_HIP_CMP_MAX_DIGIT_BITS 8
+/* the plaintext rows: out[(i nd + j) 2^d + c] = 2^j sgn(r_ij - c), i < n, j < nd = ceil(bits / d), c < 2^d, exponent records: the
+ * magnitude in word 0, a set sign word for a negative entry, an all-zero record for equality.  d_r: n records, of which u is
+ * used; d_out: n nd 2^d records.  One launch ("k_cmp_rows" under "profile_kernels"), no workspace, no lock. */
+int cofhe_hip_cmp_rows_records(cofhe_hip_ctx *ctx, const void *d_r, void *d_out, uint64_t n, uint32_t bits, uint32_t digit_bits,
+                               uint32_t kbits, void *stream);
+/* the tuples' entries: out[q] = (h^rho, pk^rho o f^(T_q mod 2^kbits)) with rho = rho[q], q < n nd 2^d, and T the rows of
+ * cofhe_hip_cmp_rows_records, which it runs into a block of the block cache; then cofhe_hip_encrypt_fresh_records over the
+ * n nd 2^d plaintexts, whose bytes these are (the plan "comb", kind 1, and its one read-back of the longest exponent).  d_rho:
+ * n nd 2^d exponent records of the caller's randomness, each used once; h_record, pk_record, f_record: HOST records.  Also
+ * COFHE_HIP_EINVAL: kbits out of the comb's range. */
+int cofhe_hip_cmp_tuples_records(cofhe_hip_ctx *ctx, const void *d_r, const void *d_rho, const uint32_t *h_record,
+                                 const uint32_t *pk_record, const uint32_t *f_record, void *d_out, uint64_t n, uint32_t bits,
+                                 uint32_t digit_bits, uint32_t kbits, void *stream);
+/* The closing step of round 1: out[2 i + s] = prod_{j < nd} tuples[(i nd + j) 2^d + digit j of t_s], t_0 = A and t_1 = B of
+ * u = u of e[i], i < n, ciphertexts; wrap[i] = [A > B] as an exponent record.  d_e: n exponent records of the opened values x - r;
+ * d_tuples: n nd 2^d ciphertexts, read in place; d_out: 2 n ciphertexts, [S_A] then [S_B] of each element; d_wrap: n exponent
+ * records.  One launch ("k_cmp_close" under "profile_kernels"): one limb group per element and half, the prefix below the top
+ * digit composed once, nd compositions each (nd = 1: two copies).  The results share their randomness with the entries they
+ * are products of, which are used once.  A composition that fails sets the device status word as everywhere.  No workspace.  It
+ * has NO serialised twin: tensors that arrive as bytes go through cofhe_hip_unpack_tensor_device (kind 0 for e of shape S, kind 2
+ * for the tuples of shape S + [nd, 2^d]; it validates the incoming forms), cofhe_hip_cmp_shape, this call and
+ * cofhe_hip_pack_tensor_device, as Engine.cmp_close_tensors_bytes does. */
+int cofhe_hip_cmp_close_records(cofhe_hip_ctx *ctx, const void *d_e, const void *d_tuples, void *d_out, void *d_wrap, uint64_t n,
+                                uint32_t bits, uint32_t digit_bits, uint32_t kbits, void *stream);
+/* host only, no GPU: *digits = nd = ceil(bits / digit_bits) and *entries = nd 2^digit_bits of one element's tuple (either may be
+ * null).  COFHE_HIP_EINVAL for the parameter bounds above.  With shape_t non-null it also validates the tuples that go with
+ * opened values of shape shape_e[ndim_e], ndim_e <= 6: COFHE_HIP_ESHAPE unless shape_t is shape_e with two more, last dimensions
+ * [nd, 2^digit_bits].  shape_t null (ndim_t ignored): the parameters only. */
+int cofhe_hip_cmp_shape(uint32_t bits, uint32_t digit_bits, uint32_t kbits, uint32_t ndim_e, const uint32_t *shape_e, uint32_t ndim_t,
+                        const uint32_t *shape_t, uint32_t *digits, uint32_t *entries);
 /* ---- rearranging resident tensors: affine views and index gathers (cofhe_amd/csrc/view.hip, view.hpp) ----
  * Pure data movement on records of `words` dwords each (336 a ciphertext, 168 a form or a partial decryption, 32 an exponent
  * record): every record of the result is a byte-for-byte copy of a source record or of the fill record.  No composition runs and
