@@ -8,6 +8,118 @@ _LIB = None
 REC_WORDS = 168
 EXP_REC_WORDS = 32
 
+COFHE_HIP_EINVAL, COFHE_HIP_ESHAPE, COFHE_HIP_ENDIM, COFHE_HIP_EHIP, COFHE_HIP_ENOMEM = -1, -2, -3, -4, -5
+
+# Every prototype of include/cofhe_hip.h as "return:parameters", one letter each (tests/test_engine_signatures_cpu.py compares the
+# table with the header).  Parameters: p pointer (anything with * or []), u uint32_t, q uint64_t, z size_t, i int, l int64_t.
+# Returns: i int, v void, z size_t, s const char *.
+_CTYPES = {"p": C.c_void_p, "u": C.c_uint32, "q": C.c_uint64, "z": C.c_size_t, "i": C.c_int, "l": C.c_int64, "v": None, "s": C.c_char_p}
+SIGNATURES = {
+    "cofhe_hip_last_error": "s:",
+    "cofhe_hip_record_words": "i:",
+    "cofhe_hip_exp_words": "i:",
+    "cofhe_hip_ctx_create": "i:ipzp",
+    "cofhe_hip_ctx_destroy": "v:p",
+    "cofhe_hip_malloc": "i:pzp",
+    "cofhe_hip_free": "i:pp",
+    "cofhe_hip_free_on_stream": "i:ppp",
+    "cofhe_hip_trim": "i:pz",
+    "cofhe_hip_ctx_set_option": "i:ppl",
+    "cofhe_hip_profile_read": "i:ppppi",
+    "cofhe_hip_upload": "i:pppzp",
+    "cofhe_hip_download": "i:pppzp",
+    "cofhe_hip_stream_sync": "i:pp",
+    "cofhe_hip_device_status": "i:ppip",
+    "cofhe_hip_validate_records": "i:ppqpp",
+    "cofhe_hip_compose_records": "i:ppppqp",
+    "cofhe_hip_compose_wide_records": "i:ppppqupp",
+    "cofhe_hip_add_ciphertext_records": "i:ppppqp",
+    "cofhe_hip_sub_ciphertext_records": "i:ppppqp",
+    "cofhe_hip_invert_records": "i:pppqp",
+    "cofhe_hip_pow_records": "i:ppppqp",
+    "cofhe_hip_scal_matmul_records": "i:pppppuuup",
+    "cofhe_hip_matmul_plain_ct_records": "i:pppppuuup",
+    "cofhe_hip_conv2d_out_shape": "i:ppp",
+    "cofhe_hip_conv2d_plain_ct_records": "i:ppppppp",
+    "cofhe_hip_conv2d_geometry_out_shape": "i:ppp",
+    "cofhe_hip_conv2d_grouped_plain_ct_records": "i:ppppppp",
+    "cofhe_hip_sum_pool2d_records": "i:pppppp",
+    "cofhe_hip_matmul_plain_plain_records": "i:ppppuuuup",
+    "cofhe_hip_conv2d_plain_plain_records": "i:pppppup",
+    "cofhe_hip_conv2d_ct_filters_records": "i:ppppppp",
+    "cofhe_hip_pow_dot_records": "i:ppppqup",
+    "cofhe_hip_poly_shift_records": "i:ppppquup",
+    "cofhe_hip_poly_close_records": "i:ppppppquup",
+    "cofhe_hip_divfloor_plain_records": "i:pppqpqup",
+    "cofhe_hip_div_close_records": "i:pppqpppqup",
+    "cofhe_hip_lut_rotate_records": "i:ppqppqup",
+    "cofhe_hip_lut_tuples_records": "i:ppqppppppquup",
+    "cofhe_hip_lut_select_records": "i:ppppqup",
+    "cofhe_hip_lut_tuples_shape_bits": "i:upupp",
+    "cofhe_hip_cmp_rows_records": "i:pppquuup",
+    "cofhe_hip_cmp_tuples_records": "i:pppppppquuup",
+    "cofhe_hip_cmp_close_records": "i:pppppquuup",
+    "cofhe_hip_cmp_shape": "i:uuuupuppp",
+    "cofhe_hip_view_check": "i:ppppp",
+    "cofhe_hip_view_permute": "i:pupp",
+    "cofhe_hip_view_slice": "i:pupppp",
+    "cofhe_hip_view_pad": "i:puppp",
+    "cofhe_hip_view_broadcast": "i:pupup",
+    "cofhe_hip_view_window_taps": "i:pp",
+    "cofhe_hip_view_into": "i:ppp",
+    "cofhe_hip_view_records": "i:pppppup",
+    "cofhe_hip_gather_records": "i:ppqpppqup",
+    "cofhe_hip_spline_rows_records": "i:ppqppquuuup",
+    "cofhe_hip_spline_tuples_records": "i:ppqppppppquuuup",
+    "cofhe_hip_spline_powers_records": "i:pppquup",
+    "cofhe_hip_spline_close_records": "i:ppppquuuup",
+    "cofhe_hip_spline_tuples_shape": "i:upuppp",
+    "cofhe_hip_decrypt_records": "i:pppppqup",
+    "cofhe_hip_accumulate_records": "i:ppppuuup",
+    "cofhe_hip_pow_form_records": "i:ppppqp",
+    "cofhe_hip_pow_fixed_base_record": "i:ppppp",
+    "cofhe_hip_pow_fixed_base_records": "i:pupppp",
+    "cofhe_hip_encrypt_records": "i:pppppqup",
+    "cofhe_hip_pow_fixed_base_many_records": "i:ppppqp",
+    "cofhe_hip_encrypt_fresh_records": "i:pppppppqup",
+    "cofhe_hip_rerandomize_records": "i:ppppppqp",
+    "cofhe_hip_add_plain_records": "i:ppppppppquip",
+    "cofhe_hip_comb_shape": "i:uquuuqppp",
+    "cofhe_hip_part_decrypt_records": "i:ppppqp",
+    "cofhe_hip_combine_part_decryptions_records": "i:pppupppqup",
+    "cofhe_hip_time_compose": "i:ppppqipp",
+    "cofhe_hip_workspace_plan": "i:ppupupp",
+    "cofhe_hip_timer_start": "i:ppp",
+    "cofhe_hip_timer_stop": "i:pppp",
+    "cofhe_hip_bytes_to_records": "i:pzpppp",
+    "cofhe_hip_records_to_bytes": "i:pquppp",
+    "cofhe_hip_pdr_bytes_to_records": "i:pzpppp",
+    "cofhe_hip_pdr_records_to_bytes": "i:pquppp",
+    "cofhe_hip_unpack_tensor_device": "i:ppzipqpppp",
+    "cofhe_hip_pack_tensor_device": "i:ppqiuppzpp",
+    "cofhe_hip_packed_size_bound": "z:qiu",
+    "cofhe_hip_bytes_to_exponents": "i:pzpppp",
+    "cofhe_hip_host_free": "v:p",
+    "cofhe_hip_add_ciphertext_tensors_bytes": "i:ppzpzpp",
+    "cofhe_hip_sub_ciphertext_tensors_bytes": "i:ppzpzpp",
+    "cofhe_hip_add_plaintext_tensor_bytes": "i:ppzpzpuipp",
+    "cofhe_hip_matmul_plain_ct_tensors_bytes": "i:ppzpzpzpp",
+    "cofhe_hip_conv2d_plain_ct_tensors_bytes": "i:ppzpzpzuuuupp",
+    "cofhe_hip_conv2d_grouped_plain_ct_tensors_bytes": "i:ppzpzpzuuuuuuupp",
+    "cofhe_hip_sum_pool2d_tensors_bytes": "i:ppzpzuuuuuupp",
+    "cofhe_hip_poly_close_tensors_bytes": "i:ppzpzpzpupp",
+    "cofhe_hip_div_close_tensors_bytes": "i:ppzpzpzpupp",
+    "cofhe_hip_scal_ciphertext_tensors_bytes": "i:ppzpzpzpp",
+    "cofhe_hip_shard_rows": "v:quupp",
+    "cofhe_hip_comm_unique_id": "i:p",
+    "cofhe_hip_comm_create": "i:ppuup",
+    "cofhe_hip_comm_destroy": "v:p",
+    "cofhe_hip_all_gather_rows": "i:pppqqpp",
+    "cofhe_hip_gather_plan": "i:qquppp",
+    "cofhe_hip_comm_info": "i:pppp",
+    "cofhe_hip_comm_set_option": "i:ppl",
+}
+
 
 class CofheHipError(RuntimeError):
     def __init__(self, code, msg):
@@ -40,7 +152,13 @@ def load_library(path=None):
             except Exception:       # a CPU-only torch build: nothing to order
                 pass
         L = C.CDLL(p)
-        L.cofhe_hip_last_error.restype = C.c_char_p
+        for name, sig in SIGNATURES.items():
+            fn = getattr(L, name, None)
+            if fn is None:
+                raise AttributeError("%s does not export %s: a build older than include/cofhe_hip.h" % (p, name))
+            ret, params = sig.split(":")
+            fn.restype = _CTYPES[ret]
+            fn.argtypes = [_CTYPES[c] for c in params]
         _LIB = L
     return _LIB
 
@@ -56,6 +174,59 @@ def _absdelta(delta):
     return m.to_bytes((m.bit_length() + 7) // 8, "little")
 
 
+def _host_record(x, words=REC_WORDS):
+    """a host record argument (f_record, h_record, pk_record, base_record; words=EXP_REC_WORDS: an exponent record) as a
+    contiguous uint32 array of exactly `words` words -- the library reads that many.  Pass its .ctypes.data and keep the array
+    in a local for the length of the call."""
+    import numpy as np
+    a = np.ascontiguousarray(x, dtype=np.uint32)
+    assert a.size == words
+    return a
+
+
+def _u32s(values):
+    """a uint32_t shape array argument (never of length 0: the count travels beside it)"""
+    return (C.c_uint32 * max(1, len(values)))(*values)
+
+
+class _DeviceScope:
+    """the device allocations of one Engine call on serialised tensors, freed on the way out (also by an exception): how the
+    entries that the library has no entry point for go from bytes to records, through a launcher and back to bytes"""
+
+    def __init__(self, eng):
+        self.eng = eng
+        self.held = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for p in self.held:
+            self.eng.free(p)
+
+    def alloc(self, nbytes):
+        p = self.eng.malloc(nbytes)
+        self.held.append(p)
+        return p
+
+    def load(self, t, kind):
+        """serialised tensor -> (d_records, shape, n_records); unpack_tensor_device validates the incoming forms"""
+        # every integer owns an 8-byte table entry: the record count is bounded by the length
+        cap = (len(t) // 8) // (3 if kind else 1) + 1
+        raw = self.alloc(len(t) + 4)
+        recs = self.alloc(cap * 4 * (REC_WORDS if kind else EXP_REC_WORDS))
+        self.eng.upload(raw, t)
+        shape, n = self.eng.unpack_tensor_device(raw, len(t), kind, recs, cap)
+        return recs, shape, n
+
+    def packed(self, d_records, n_records, kind, shape):
+        """records on the device -> the serialised tensor, as bytes"""
+        cap = self.eng.packed_size_bound(n_records, kind, len(shape))
+        buf = self.alloc(cap)
+        ln = self.eng.pack_tensor_device(d_records, n_records, kind, shape, buf, cap)
+        return self.eng.download(buf, ln, dtype="uint8").tobytes()
+
+
 class Engine:
     """One GPU + one discriminant.  All tensors cross as bytes in the reference's binary
     formats (or as device pointers to records for the resident-tensor entry points)."""
@@ -64,7 +235,7 @@ class Engine:
         self.L = load_library()
         self.ctx = C.c_void_p()
         d = _absdelta(delta)
-        _chk(self.L.cofhe_hip_ctx_create(C.c_int(device), C.c_char_p(d), C.c_size_t(len(d)), C.byref(self.ctx)))
+        _chk(self.L.cofhe_hip_ctx_create(device, d, len(d), C.byref(self.ctx)))
         self.delta = delta
         self.device = device
 
@@ -79,65 +250,48 @@ class Engine:
         except Exception:
             pass
 
+    def _call(self, fn, *args):
+        """fn(ctx, *args), then the error check: integers as integers and device pointers, bytes as host buffers"""
+        _chk(fn(self.ctx, *args))
+
     # ---- whole ops on host byte buffers -------------------------------------------------
     def _take(self, out, outlen):
         data = C.string_at(out, outlen.value)
         self.L.cofhe_hip_host_free(out)
         return data
 
-    def add_ciphertext_tensors(self, t1: bytes, t2: bytes) -> bytes:
-        out = C.POINTER(C.c_uint8)()
-        n = C.c_size_t()
-        _chk(self.L.cofhe_hip_add_ciphertext_tensors_bytes(self.ctx, C.c_char_p(t1), C.c_size_t(len(t1)),
-                                                           C.c_char_p(t2), C.c_size_t(len(t2)), C.byref(out), C.byref(n)))
+    def _bytes_out(self, fn, *args):
+        """fn(*args, uint8_t **out, size_t *outlen): the bytes the library allocated, which it gets back"""
+        out, n = C.c_void_p(), C.c_size_t()
+        _chk(fn(*args, C.byref(out), C.byref(n)))
         return self._take(out, n)
+
+    def add_ciphertext_tensors(self, t1: bytes, t2: bytes) -> bytes:
+        return self._bytes_out(self.L.cofhe_hip_add_ciphertext_tensors_bytes, self.ctx, t1, len(t1), t2, len(t2))
 
     def sub_ciphertext_tensors(self, t1: bytes, t2: bytes) -> bytes:
         """t1 - t2 element-wise (the compute node's SUBTRACT): one composition per record, with the inverse of t2's forms"""
-        out = C.POINTER(C.c_uint8)()
-        n = C.c_size_t()
-        _chk(self.L.cofhe_hip_sub_ciphertext_tensors_bytes(self.ctx, C.c_char_p(t1), C.c_size_t(len(t1)),
-                                                           C.c_char_p(t2), C.c_size_t(len(t2)), C.byref(out), C.byref(n)))
-        return self._take(out, n)
+        return self._bytes_out(self.L.cofhe_hip_sub_ciphertext_tensors_bytes, self.ctx, t1, len(t1), t2, len(t2))
 
     def add_plaintext_tensor(self, cts: bytes, pt: bytes, f_record, kbits: int, mode: int = 0) -> bytes:
         """mode 0: cts + pt, 1: cts - pt, 2: pt - cts, without an encryption: (c1, c2 o f^m); f_record: host uint32[168]"""
-        import numpy as np
-        f = np.ascontiguousarray(f_record, dtype=np.uint32)
-        assert f.size == 168
-        out = C.POINTER(C.c_uint8)()
-        n = C.c_size_t()
-        _chk(self.L.cofhe_hip_add_plaintext_tensor_bytes(self.ctx, C.c_char_p(cts), C.c_size_t(len(cts)), C.c_char_p(pt), C.c_size_t(len(pt)),
-                                                         f.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_uint32(kbits), C.c_int(mode),
-                                                         C.byref(out), C.byref(n)))
-        return self._take(out, n)
+        f = _host_record(f_record)
+        return self._bytes_out(self.L.cofhe_hip_add_plaintext_tensor_bytes, self.ctx, cts, len(cts), pt, len(pt), f.ctypes.data, kbits, mode)
 
     def poly_close_tensors(self, coef: bytes, e: bytes, powers: bytes, f_record, kbits: int) -> bytes:
         """coef (plaintext tensor [d + 1]), e (plaintext tensor of the opened values x - a) and powers (ciphertext tensor
         [d, shape of e] of the power tuples [a^i]) -> the ciphertext tensor of p(x), of e's shape; f_record: host uint32[168]"""
-        import numpy as np
-        f = np.ascontiguousarray(f_record, dtype=np.uint32)
-        assert f.size == 168
-        out = C.POINTER(C.c_uint8)()
-        n = C.c_size_t()
-        _chk(self.L.cofhe_hip_poly_close_tensors_bytes(self.ctx, C.c_char_p(coef), C.c_size_t(len(coef)), C.c_char_p(e), C.c_size_t(len(e)),
-                                                       C.c_char_p(powers), C.c_size_t(len(powers)), f.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                       C.c_uint32(kbits), C.byref(out), C.byref(n)))
-        return self._take(out, n)
+        f = _host_record(f_record)
+        return self._bytes_out(self.L.cofhe_hip_poly_close_tensors_bytes, self.ctx, coef, len(coef), e, len(e), powers, len(powers),
+                               f.ctypes.data, kbits)
 
     def div_close_tensors_bytes(self, e: bytes, div: bytes, rq: bytes, f_record, kbits: int) -> bytes:
         """e (plaintext tensor of the opened values x - r), div (plaintext tensor of one divisor, of e's last dimension or of e's
         shape) and rq (ciphertext tensor [r_q] of e's shape) -> the ciphertext tensor of floor(x / div) or one less, of e's
         shape; a divisor outside [1, 2^(kbits-1)) is refused; f_record: host uint32[168]"""
-        import numpy as np
-        f = np.ascontiguousarray(f_record, dtype=np.uint32)
-        assert f.size == 168
-        out = C.POINTER(C.c_uint8)()
-        n = C.c_size_t()
-        _chk(self.L.cofhe_hip_div_close_tensors_bytes(self.ctx, C.c_char_p(e), C.c_size_t(len(e)), C.c_char_p(div), C.c_size_t(len(div)),
-                                                      C.c_char_p(rq), C.c_size_t(len(rq)), f.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                      C.c_uint32(kbits), C.byref(out), C.byref(n)))
-        return self._take(out, n)
+        f = _host_record(f_record)
+        return self._bytes_out(self.L.cofhe_hip_div_close_tensors_bytes, self.ctx, e, len(e), div, len(div), rq, len(rq),
+                               f.ctypes.data, kbits)
 
     def lut_select_tensors_bytes(self, e: bytes, tuples: bytes) -> bytes:
         """e (plaintext tensor of the opened values x - r, shape S, at most 7 dimensions) and tuples (ciphertext tensor of the
@@ -145,35 +299,14 @@ class Engine:
         Composed here from unpack_tensor_device (which validates the incoming forms), lut_tuples_shape_bits (COFHE_HIP_ESHAPE when
         the tuples' shape is anything else), lut_select_records and pack_tensor_device: the library has no entry point of its own
         for it."""
-        held = []
-
-        def load(t, kind):
-            # every integer owns an 8-byte table entry: the record count is bounded by the length
-            cap = (len(t) // 8) // (3 if kind else 1) + 1
-            raw = self.malloc(len(t) + 4)
-            held.append(raw)
-            recs = self.malloc(cap * 4 * (REC_WORDS if kind else EXP_REC_WORDS))
-            held.append(recs)
-            self.upload(raw, t)
-            shape, n = self.unpack_tensor_device(raw, len(t), kind, recs, cap)
-            return recs, shape, n
-
-        try:
-            de, se, ne = load(e, 0)
-            dt, st, nt = load(tuples, 2)
+        with _DeviceScope(self) as dev:
+            de, se, ne = dev.load(e, 0)
+            dt, st, nt = dev.load(tuples, 2)
             bits = self.lut_tuples_shape_bits(se, st)
             assert nt == 2 * (ne << bits)                             # the counts are the shapes' products
-            dout = self.malloc(max(ne, 1) * 2 * REC_WORDS * 4)
-            held.append(dout)
+            dout = dev.alloc(max(ne, 1) * 2 * REC_WORDS * 4)
             self.lut_select_records(de, dt, dout, ne, bits)
-            cap = self.packed_size_bound(2 * ne, 2, len(se))
-            packed = self.malloc(cap)
-            held.append(packed)
-            ln = self.pack_tensor_device(dout, 2 * ne, 2, se, packed, cap)
-            return self.download(packed, ln, dtype="uint8").tobytes()
-        finally:
-            for p in held:
-                self.free(p)
+            return dev.packed(dout, 2 * ne, 2, se)
 
     def spline_close_tensors_bytes(self, e: bytes, tuples: bytes, shift: int, kbits: int) -> bytes:
         """e (plaintext tensor of the opened values x - r, shape S, at most 6 dimensions) and tuples (ciphertext tensor of the spline
@@ -181,35 +314,14 @@ class Engine:
         bits of the table.  Composed here from unpack_tensor_device (which validates the incoming forms), spline_tuples_shape
         (COFHE_HIP_ESHAPE when the tuples' shape is anything else), spline_close_records and pack_tensor_device, exactly as
         lut_select_tensors_bytes is: the library has no entry point of its own for it."""
-        held = []
-
-        def load(t, kind):
-            # every integer owns an 8-byte table entry: the record count is bounded by the length
-            cap = (len(t) // 8) // (3 if kind else 1) + 1
-            raw = self.malloc(len(t) + 4)
-            held.append(raw)
-            recs = self.malloc(cap * 4 * (REC_WORDS if kind else EXP_REC_WORDS))
-            held.append(recs)
-            self.upload(raw, t)
-            shape, n = self.unpack_tensor_device(raw, len(t), kind, recs, cap)
-            return recs, shape, n
-
-        try:
-            de, se, ne = load(e, 0)
-            dt, st, nt = load(tuples, 2)
+        with _DeviceScope(self) as dev:
+            de, se, ne = dev.load(e, 0)
+            dt, st, nt = dev.load(tuples, 2)
             bits, d = self.spline_tuples_shape(se, st)
             assert nt == 2 * (ne << bits) * (d + 1)                   # the counts are the shapes' products
-            dout = self.malloc(max(ne, 1) * 2 * REC_WORDS * 4)
-            held.append(dout)
+            dout = dev.alloc(max(ne, 1) * 2 * REC_WORDS * 4)
             self.spline_close_records(de, dt, dout, ne, bits, shift, d, kbits)
-            cap = self.packed_size_bound(2 * ne, 2, len(se))
-            packed = self.malloc(cap)
-            held.append(packed)
-            ln = self.pack_tensor_device(dout, 2 * ne, 2, se, packed, cap)
-            return self.download(packed, ln, dtype="uint8").tobytes()
-        finally:
-            for p in held:
-                self.free(p)
+            return dev.packed(dout, 2 * ne, 2, se)
 
     def cmp_close_tensors_bytes(self, e: bytes, tuples: bytes, bits: int, digit_bits: int, kbits: int):
         """e (plaintext tensor of the opened values x - r, shape S, at most 6 dimensions) and tuples (ciphertext tensor of the
@@ -217,74 +329,33 @@ class Engine:
         pairs [S_A], [S_B], shape S + [2], the plaintext tensor wrap of shape S).  Composed here from unpack_tensor_device (which
         validates the incoming forms), cmp_shape (COFHE_HIP_ESHAPE when the tuples' shape is anything else), cmp_close_records
         and pack_tensor_device, exactly as lut_select_tensors_bytes is: the library has no entry point of its own for it."""
-        held = []
-
-        def load(t, kind):
-            # every integer owns an 8-byte table entry: the record count is bounded by the length
-            cap = (len(t) // 8) // (3 if kind else 1) + 1
-            raw = self.malloc(len(t) + 4)
-            held.append(raw)
-            recs = self.malloc(cap * 4 * (REC_WORDS if kind else EXP_REC_WORDS))
-            held.append(recs)
-            self.upload(raw, t)
-            shape, n = self.unpack_tensor_device(raw, len(t), kind, recs, cap)
-            return recs, shape, n
-
-        def packed(recs, n_records, kind, shape):
-            cap = self.packed_size_bound(n_records, kind, len(shape))
-            buf = self.malloc(cap)
-            held.append(buf)
-            ln = self.pack_tensor_device(recs, n_records, kind, shape, buf, cap)
-            return self.download(buf, ln, dtype="uint8").tobytes()
-
-        try:
-            de, se, ne = load(e, 0)
-            dt, st, nt = load(tuples, 2)
+        with _DeviceScope(self) as dev:
+            de, se, ne = dev.load(e, 0)
+            dt, st, nt = dev.load(tuples, 2)
             _, entries = self.cmp_shape(bits, digit_bits, kbits, se, st)
             assert nt == 2 * ne * entries                              # the counts are the shapes' products
-            dout = self.malloc(max(ne, 1) * 4 * REC_WORDS * 4)
-            held.append(dout)
-            dwrap = self.malloc(max(ne, 1) * EXP_REC_WORDS * 4)
-            held.append(dwrap)
+            dout = dev.alloc(max(ne, 1) * 4 * REC_WORDS * 4)
+            dwrap = dev.alloc(max(ne, 1) * EXP_REC_WORDS * 4)
             self.cmp_close_records(de, dt, dout, dwrap, ne, bits, digit_bits, kbits)
-            return packed(dout, 4 * ne, 2, se + [2]), packed(dwrap, ne, 0, se)
-        finally:
-            for p in held:
-                self.free(p)
+            return dev.packed(dout, 4 * ne, 2, se + [2]), dev.packed(dwrap, ne, 0, se)
 
     def scal_ciphertext_tensors(self, s: bytes, cts: bytes, zero: bytes = None) -> bytes:
-        out = C.POINTER(C.c_uint8)()
-        n = C.c_size_t()
-        z = C.c_char_p(zero) if zero is not None else None
-        _chk(self.L.cofhe_hip_scal_ciphertext_tensors_bytes(self.ctx, C.c_char_p(s), C.c_size_t(len(s)), C.c_char_p(cts),
-                                                            C.c_size_t(len(cts)), z, C.c_size_t(len(zero) if zero else 0),
-                                                            C.byref(out), C.byref(n)))
-        return self._take(out, n)
+        return self._bytes_out(self.L.cofhe_hip_scal_ciphertext_tensors_bytes, self.ctx, s, len(s), cts, len(cts),
+                               zero, len(zero) if zero else 0)
 
     def matmul_plain_ct_tensors(self, s: bytes, cts: bytes, zero: bytes) -> bytes:
         """s (plaintext tensor, n x m) . cts (ciphertext tensor, m x p) from zero (1-element ciphertext tensor): the linear
         layer y = W x with plaintext weights, the mirror image of the 2-D scal_ciphertext_tensors"""
-        out = C.POINTER(C.c_uint8)()
-        n = C.c_size_t()
-        _chk(self.L.cofhe_hip_matmul_plain_ct_tensors_bytes(self.ctx, C.c_char_p(s), C.c_size_t(len(s)), C.c_char_p(cts),
-                                                            C.c_size_t(len(cts)), C.c_char_p(zero), C.c_size_t(len(zero)),
-                                                            C.byref(out), C.byref(n)))
-        return self._take(out, n)
+        return self._bytes_out(self.L.cofhe_hip_matmul_plain_ct_tensors_bytes, self.ctx, s, len(s), cts, len(cts), zero, len(zero))
 
     def conv2d_plain_ct_tensors(self, w: bytes, cts: bytes, zero: bytes, stride=(1, 1), pad=(0, 0), dilation=(1, 1), groups=1) -> bytes:
         """w (plaintext tensor [kh, kw, C / groups, Co]) over cts (ciphertext tensor [B, H, W, C]), channels last, from zero
         (1-element ciphertext tensor); stride, zero padding and dilation as (rows, columns).  Returns the ciphertext tensor
         [B, Ho, Wo, Co]"""
-        out = C.POINTER(C.c_uint8)()
-        n = C.c_size_t()
-        head = (self.ctx, C.c_char_p(w), C.c_size_t(len(w)), C.c_char_p(cts), C.c_size_t(len(cts)), C.c_char_p(zero), C.c_size_t(len(zero)),
-                C.c_uint32(stride[0]), C.c_uint32(stride[1]), C.c_uint32(pad[0]), C.c_uint32(pad[1]))
+        head = (self.ctx, w, len(w), cts, len(cts), zero, len(zero), stride[0], stride[1], pad[0], pad[1])
         if tuple(dilation) == (1, 1) and groups == 1:
-            _chk(self.L.cofhe_hip_conv2d_plain_ct_tensors_bytes(*head, C.byref(out), C.byref(n)))
-        else:
-            _chk(self.L.cofhe_hip_conv2d_grouped_plain_ct_tensors_bytes(*head, C.c_uint32(dilation[0]), C.c_uint32(dilation[1]), C.c_uint32(groups),
-                                                                        C.byref(out), C.byref(n)))
-        return self._take(out, n)
+            return self._bytes_out(self.L.cofhe_hip_conv2d_plain_ct_tensors_bytes, *head)
+        return self._bytes_out(self.L.cofhe_hip_conv2d_grouped_plain_ct_tensors_bytes, *head, dilation[0], dilation[1], groups)
 
     def conv2d_ct_filters_tensors(self, img: bytes, filters: bytes, zero: bytes, stride=(1, 1), pad=(0, 0), dilation=(1, 1)) -> bytes:
         """the plaintext tensor img [B, H, W, C] under the ciphertext tensor filters [kh, kw, C, Co], channels last, from zero
@@ -292,191 +363,121 @@ class Engine:
         [B, Ho, Wo, Co]: the E * [Bf] term of a convolution Beaver triplet.  Composed here from unpack_tensor_device (which
         validates the incoming forms), conv2d_ct_filters_records and pack_tensor_device, as lut_select_tensors_bytes is: the
         library has no entry point of its own for it.  COFHE_HIP_ESHAPE when an operand is not 4-D or the channels differ"""
-        held = []
-
-        def load(t, kind):
-            # every integer owns an 8-byte table entry: the record count is bounded by the length
-            cap = (len(t) // 8) // (3 if kind else 1) + 1
-            raw = self.malloc(len(t) + 4)
-            held.append(raw)
-            recs = self.malloc(cap * 4 * (REC_WORDS if kind else EXP_REC_WORDS))
-            held.append(recs)
-            self.upload(raw, t)
-            shape, n = self.unpack_tensor_device(raw, len(t), kind, recs, cap)
-            return recs, shape, n
-
-        try:
-            di, si, _ = load(img, 0)
-            df, sf, _ = load(filters, 2)
+        with _DeviceScope(self) as dev:
+            di, si, _ = dev.load(img, 0)
+            df, sf, _ = dev.load(filters, 2)
             if len(si) != 4 or len(sf) != 4:
-                raise CofheHipError(-2, "conv2d_ct_filters takes a 4-D image tensor [B, H, W, C] and a 4-D filter tensor [kh, kw, C, Co]")
+                raise CofheHipError(COFHE_HIP_ESHAPE, "conv2d_ct_filters takes a 4-D image tensor [B, H, W, C] and a 4-D filter tensor [kh, kw, C, Co]")
             ho, wo = conv2d_out_shape(si, sf, stride, pad, dilation, 1)          # ESHAPE when the channels differ
-            dz, _, nz = load(zero, 2)
+            dz, _, nz = dev.load(zero, 2)
             if nz != 2:
-                raise CofheHipError(-1, "zero must be a one-element ciphertext tensor")
+                raise CofheHipError(COFHE_HIP_EINVAL, "zero must be a one-element ciphertext tensor")
             so = [si[0], ho, wo, sf[3]]
             nout = 2 * so[0] * ho * wo * so[3]
-            dout = self.malloc(max(nout, 1) * REC_WORDS * 4)
-            held.append(dout)
+            dout = dev.alloc(max(nout, 1) * REC_WORDS * 4)
             self.conv2d_ct_filters_records(di, df, dz, dout, si, sf, stride, pad, dilation=dilation)
-            cap = self.packed_size_bound(nout, 2, 4)
-            packed = self.malloc(cap)
-            held.append(packed)
-            ln = self.pack_tensor_device(dout, nout, 2, so, packed, cap)
-            return self.download(packed, ln, dtype="uint8").tobytes()
-        finally:
-            for p in held:
-                self.free(p)
+            return dev.packed(dout, nout, 2, so)
 
     def sum_pool2d_tensors(self, cts: bytes, zero: bytes, kernel, stride=None, pad=(0, 0)) -> bytes:
         """the sums over kernel = (kh, kw) windows of the ciphertext tensor cts [B, H, W, C], channel by channel, from zero;
         stride defaults to the kernel.  Returns [B, Ho, Wo, C].  Average pooling: fold 1 / (kh kw) into the next layer's weights"""
         stride = kernel if stride is None else stride
-        out = C.POINTER(C.c_uint8)()
-        n = C.c_size_t()
-        _chk(self.L.cofhe_hip_sum_pool2d_tensors_bytes(self.ctx, C.c_char_p(cts), C.c_size_t(len(cts)), C.c_char_p(zero), C.c_size_t(len(zero)),
-                                                       C.c_uint32(kernel[0]), C.c_uint32(kernel[1]), C.c_uint32(stride[0]), C.c_uint32(stride[1]),
-                                                       C.c_uint32(pad[0]), C.c_uint32(pad[1]), C.byref(out), C.byref(n)))
-        return self._take(out, n)
+        return self._bytes_out(self.L.cofhe_hip_sum_pool2d_tensors_bytes, self.ctx, cts, len(cts), zero, len(zero),
+                               kernel[0], kernel[1], stride[0], stride[1], pad[0], pad[1])
 
     # ---- format conversion (host) ----------------------------------------------------------
-    def bytes_to_records(self, t: bytes):
+    def _to_records(self, fn, t, words):
+        """fn: a bytes -> (shape, records of `words` words) converter of the library, which gets its array back"""
         import numpy as np
-        ndim = C.c_uint32()
-        shape = (C.c_uint32 * 8)()
-        recs = C.POINTER(C.c_uint32)()
-        n = C.c_uint64()
-        _chk(self.L.cofhe_hip_bytes_to_records(C.c_char_p(t), C.c_size_t(len(t)), C.byref(ndim), shape, C.byref(recs), C.byref(n)))
-        arr = np.ctypeslib.as_array(recs, shape=(n.value * REC_WORDS,)).copy() if n.value else np.zeros(0, dtype=np.uint32)
+        ndim, shape, recs, n = C.c_uint32(), (C.c_uint32 * 8)(), C.POINTER(C.c_uint32)(), C.c_uint64()
+        _chk(fn(t, len(t), C.byref(ndim), shape, C.byref(recs), C.byref(n)))
+        arr = np.ctypeslib.as_array(recs, shape=(n.value * words,)).copy() if n.value else np.zeros(0, dtype=np.uint32)
         self.L.cofhe_hip_host_free(recs)
         return list(shape[:ndim.value]), arr
 
-    def records_to_bytes(self, recs, shape) -> bytes:
+    def _from_records(self, fn, recs, shape, words):
+        """fn: a (records of `words` words, shape) -> bytes converter of the library"""
         import numpy as np
         recs = np.ascontiguousarray(recs, dtype=np.uint32)
-        out = C.POINTER(C.c_uint8)()
-        n = C.c_size_t()
-        sh = (C.c_uint32 * len(shape))(*shape)
-        _chk(self.L.cofhe_hip_records_to_bytes(recs.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_uint64(recs.size // REC_WORDS),
-                                               C.c_uint32(len(shape)), sh, C.byref(out), C.byref(n)))
-        return self._take(out, n)
+        return self._bytes_out(fn, recs.ctypes.data, recs.size // words, len(shape), _u32s(shape))
+
+    def bytes_to_records(self, t: bytes):
+        return self._to_records(self.L.cofhe_hip_bytes_to_records, t, REC_WORDS)
+
+    def records_to_bytes(self, recs, shape) -> bytes:
+        return self._from_records(self.L.cofhe_hip_records_to_bytes, recs, shape, REC_WORDS)
 
     def pdr_bytes_to_records(self, t: bytes):
         """partial-decryption tensor (one form per element) -> records"""
-        import numpy as np
-        ndim = C.c_uint32()
-        shape = (C.c_uint32 * 8)()
-        recs = C.POINTER(C.c_uint32)()
-        n = C.c_uint64()
-        _chk(self.L.cofhe_hip_pdr_bytes_to_records(C.c_char_p(t), C.c_size_t(len(t)), C.byref(ndim), shape, C.byref(recs), C.byref(n)))
-        arr = np.ctypeslib.as_array(recs, shape=(n.value * REC_WORDS,)).copy() if n.value else np.zeros(0, dtype=np.uint32)
-        self.L.cofhe_hip_host_free(recs)
-        return list(shape[:ndim.value]), arr
+        return self._to_records(self.L.cofhe_hip_pdr_bytes_to_records, t, REC_WORDS)
 
     def pdr_records_to_bytes(self, recs, shape) -> bytes:
-        import numpy as np
-        recs = np.ascontiguousarray(recs, dtype=np.uint32)
-        out = C.POINTER(C.c_uint8)()
-        n = C.c_size_t()
-        sh = (C.c_uint32 * len(shape))(*shape)
-        _chk(self.L.cofhe_hip_pdr_records_to_bytes(recs.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_uint64(recs.size // REC_WORDS),
-                                                   C.c_uint32(len(shape)), sh, C.byref(out), C.byref(n)))
-        return self._take(out, n)
+        return self._from_records(self.L.cofhe_hip_pdr_records_to_bytes, recs, shape, REC_WORDS)
+
+    def bytes_to_exponents(self, t: bytes):
+        return self._to_records(self.L.cofhe_hip_bytes_to_exponents, t, EXP_REC_WORDS)
 
     # ---- format conversion on the GPU (device pointers) ------------------------------------
     def unpack_tensor_device(self, d_bytes, nbytes, kind, d_records, capacity_records, stream=0):
         """kind 2 ciphertexts / 1 partial decryptions / 0 plaintexts; returns (shape, n_records)"""
-        ndim = C.c_uint32()
-        shape = (C.c_uint32 * 8)()
-        n = C.c_uint64()
-        _chk(self.L.cofhe_hip_unpack_tensor_device(self.ctx, C.c_void_p(d_bytes), C.c_size_t(nbytes), C.c_int(kind),
-                                                   C.c_void_p(d_records), C.c_uint64(capacity_records), C.byref(ndim), shape,
-                                                   C.byref(n), C.c_void_p(stream)))
+        ndim, shape, n = C.c_uint32(), (C.c_uint32 * 8)(), C.c_uint64()
+        self._call(self.L.cofhe_hip_unpack_tensor_device, d_bytes, nbytes, kind, d_records, capacity_records, C.byref(ndim), shape,
+                   C.byref(n), stream)
         return list(shape[:ndim.value]), n.value
 
     def pack_tensor_device(self, d_records, n_records, kind, shape, d_bytes, capacity, stream=0) -> int:
         """returns the serialised length written to d_bytes"""
-        sh = (C.c_uint32 * max(len(shape), 1))(*shape)
         n = C.c_size_t()
-        _chk(self.L.cofhe_hip_pack_tensor_device(self.ctx, C.c_void_p(d_records), C.c_uint64(n_records), C.c_int(kind),
-                                                 C.c_uint32(len(shape)), sh, C.c_void_p(d_bytes), C.c_size_t(capacity),
-                                                 C.byref(n), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_pack_tensor_device, d_records, n_records, kind, len(shape), _u32s(shape), d_bytes, capacity,
+                   C.byref(n), stream)
         return n.value
 
     def packed_size_bound(self, n_records, kind, ndim) -> int:
-        self.L.cofhe_hip_packed_size_bound.restype = C.c_size_t
-        return self.L.cofhe_hip_packed_size_bound(C.c_uint64(n_records), C.c_int(kind), C.c_uint32(ndim))
-
-    def bytes_to_exponents(self, t: bytes):
-        import numpy as np
-        ndim = C.c_uint32()
-        shape = (C.c_uint32 * 8)()
-        ex = C.POINTER(C.c_uint32)()
-        n = C.c_uint64()
-        _chk(self.L.cofhe_hip_bytes_to_exponents(C.c_char_p(t), C.c_size_t(len(t)), C.byref(ndim), shape, C.byref(ex), C.byref(n)))
-        arr = np.ctypeslib.as_array(ex, shape=(n.value * EXP_REC_WORDS,)).copy() if n.value else np.zeros(0, dtype=np.uint32)
-        self.L.cofhe_hip_host_free(ex)
-        return list(shape[:ndim.value]), arr
+        return self.L.cofhe_hip_packed_size_bound(n_records, kind, ndim)
 
     # ---- kernels on device-resident records (pointers are ints, e.g. torch .data_ptr()) -----
     def compose_records(self, d_a, d_b, d_out, n_records, stream=0):
-        _chk(self.L.cofhe_hip_compose_records(self.ctx, C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_out),
-                                              C.c_uint64(n_records), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_compose_records, d_a, d_b, d_out, n_records, stream)
 
     def compose_wide_records(self, d_a, d_b, d_out, n_records, reps=1, count_fallbacks=False, stream=0):
         """one composition per wavefront in the wavefront-wide layout (the latency kernels' composition); returns the number
         of pairs that took the 8-lane fallback when count_fallbacks"""
         fb = C.c_uint32(0)
-        _chk(self.L.cofhe_hip_compose_wide_records(self.ctx, C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_out), C.c_uint64(n_records),
-                                                   C.c_uint32(reps), C.byref(fb) if count_fallbacks else None, C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_compose_wide_records, d_a, d_b, d_out, n_records, reps, C.byref(fb) if count_fallbacks else None, stream)
         return int(fb.value)
 
     def add_ciphertext_records(self, d_a, d_b, d_out, n_ciphertexts, stream=0):
         """ciphertext-level add: folds the shared c1 of encrypt_tensor-made operands (n + 1 compositions, not 2 n)"""
-        _chk(self.L.cofhe_hip_add_ciphertext_records(self.ctx, C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_out),
-                                                     C.c_uint64(n_ciphertexts), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_add_ciphertext_records, d_a, d_b, d_out, n_ciphertexts, stream)
 
     def sub_ciphertext_records(self, d_a, d_b, d_out, n_ciphertexts, stream=0):
         """out[i] = a[i] - b[i]: a o b^-1 per record, folding and launch routes as add_ciphertext_records; d_out may be d_a or d_b"""
-        _chk(self.L.cofhe_hip_sub_ciphertext_records(self.ctx, C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_out),
-                                                     C.c_uint64(n_ciphertexts), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_sub_ciphertext_records, d_a, d_b, d_out, n_ciphertexts, stream)
 
     def invert_records(self, d_in, d_out, n_records, stream=0):
         """out[i] = in[i]^-1 on form records (a ciphertext tensor: Enc(-m) at no composition); in place allowed"""
-        _chk(self.L.cofhe_hip_invert_records(self.ctx, C.c_void_p(d_in), C.c_void_p(d_out), C.c_uint64(n_records), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_invert_records, d_in, d_out, n_records, stream)
 
     def add_plain_records(self, d_cts, d_plain, f_record, d_out, n_ciphertexts, kbits, mode=0, d_r=None, h_record=None, pk_record=None,
                           stream=0):
         """mode 0: ct + m, 1: ct - m, 2: m - ct (d_plain: n exponent records).  Without d_r: (c1, c2 o f^m), deterministic and
         purely stream-ordered; with d_r (n exponent records) and the host records h, pk: fresh randomness in the same tree.
         d_out may be d_cts."""
-        import numpy as np
-        f = np.ascontiguousarray(f_record, dtype=np.uint32)
-        assert f.size == 168
-        hp = [None, None]
-        if d_r is not None:
-            hp = [np.ascontiguousarray(x, dtype=np.uint32) for x in (h_record, pk_record)]
-            assert all(x.size == 168 for x in hp)
-        _chk(self.L.cofhe_hip_add_plain_records(self.ctx, C.c_void_p(d_cts), C.c_void_p(d_plain), C.c_void_p(d_r),
-                                                *[x.ctypes.data_as(C.c_void_p) if x is not None else C.c_void_p() for x in hp],
-                                                f.ctypes.data_as(C.c_void_p), C.c_void_p(d_out), C.c_uint64(n_ciphertexts), C.c_uint32(kbits),
-                                                C.c_int(mode), C.c_void_p(stream)))
+        f = _host_record(f_record)
+        hp = [_host_record(h_record), _host_record(pk_record)] if d_r is not None else []
+        self._call(self.L.cofhe_hip_add_plain_records, d_cts, d_plain, d_r, *([x.ctypes.data for x in hp] or [None, None]),
+                   f.ctypes.data, d_out, n_ciphertexts, kbits, mode, stream)
 
     def pow_records(self, d_base, d_exp, d_out, n_ciphertexts, stream=0):
-        _chk(self.L.cofhe_hip_pow_records(self.ctx, C.c_void_p(d_base), C.c_void_p(d_exp), C.c_void_p(d_out),
-                                          C.c_uint64(n_ciphertexts), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_pow_records, d_base, d_exp, d_out, n_ciphertexts, stream)
 
     def scal_matmul_records(self, d_cts, d_exp, d_zero, d_out, n, m, p, stream=0):
-        _chk(self.L.cofhe_hip_scal_matmul_records(self.ctx, C.c_void_p(d_cts), C.c_void_p(d_exp), C.c_void_p(d_zero),
-                                                  C.c_void_p(d_out), C.c_uint32(n), C.c_uint32(m), C.c_uint32(p),
-                                                  C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_scal_matmul_records, d_cts, d_exp, d_zero, d_out, n, m, p, stream)
 
     def matmul_plain_ct_records(self, d_s, d_cts, d_zero, d_out, n, m, p, stream=0):
         """out[i,k] = zero o prod_j cts[j,k]^s[i,j]: s n x m exponent records, cts m x p, out n x p; scal_matmul_records on
         transposed views (temporaries from the block cache); d_out must not overlap an input"""
-        _chk(self.L.cofhe_hip_matmul_plain_ct_records(self.ctx, C.c_void_p(d_s), C.c_void_p(d_cts), C.c_void_p(d_zero),
-                                                      C.c_void_p(d_out), C.c_uint32(n), C.c_uint32(m), C.c_uint32(p),
-                                                      C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_matmul_plain_ct_records, d_s, d_cts, d_zero, d_out, n, m, p, stream)
 
     def conv2d_plain_ct_records(self, d_w, d_cts, d_zero, d_out, image, filters, stride=(1, 1), pad=(0, 0), stream=0, dilation=(1, 1), groups=1):
         """out [B, Ho, Wo, Co] = the convolution of the ciphertext image d_cts [B, H, W, C] = `image` with the plaintext filters
@@ -484,12 +485,10 @@ class Engine:
         overlap an input.  Returns (Ho, Wo)"""
         if tuple(dilation) == (1, 1) and groups == 1:
             shp = _conv_shape(image, filters, stride, pad)
-            _chk(self.L.cofhe_hip_conv2d_plain_ct_records(self.ctx, C.c_void_p(d_w), C.c_void_p(d_cts), C.c_void_p(d_zero), C.c_void_p(d_out),
-                                                          C.byref(shp), C.c_void_p(stream)))
+            self._call(self.L.cofhe_hip_conv2d_plain_ct_records, d_w, d_cts, d_zero, d_out, C.byref(shp), stream)
         else:
             geo = _conv_geometry(image, filters, stride, pad, dilation, groups)
-            _chk(self.L.cofhe_hip_conv2d_grouped_plain_ct_records(self.ctx, C.c_void_p(d_w), C.c_void_p(d_cts), C.c_void_p(d_zero),
-                                                                  C.c_void_p(d_out), C.byref(geo), C.c_void_p(stream)))
+            self._call(self.L.cofhe_hip_conv2d_grouped_plain_ct_records, d_w, d_cts, d_zero, d_out, C.byref(geo), stream)
         return conv2d_out_shape(image, filters, stride, pad, dilation, groups)
 
     def conv2d_out_shape(self, image, filters, stride=(1, 1), pad=(0, 0), dilation=(1, 1), groups=1):
@@ -502,8 +501,7 @@ class Engine:
         stride = kernel if stride is None else stride
         B, H, W, Cin = image
         geo = _ConvGeometry(B, H, W, Cin, kernel[0], kernel[1], Cin, stride[0], stride[1], pad[0], pad[1], 1, 1, max(Cin, 1))
-        _chk(self.L.cofhe_hip_sum_pool2d_records(self.ctx, C.c_void_p(d_cts), C.c_void_p(d_zero), C.c_void_p(d_out), C.byref(geo),
-                                                 C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_sum_pool2d_records, d_cts, d_zero, d_out, C.byref(geo), stream)
         ho, wo = C.c_uint32(), C.c_uint32()
         _chk(self.L.cofhe_hip_conv2d_geometry_out_shape(C.byref(geo), C.byref(ho), C.byref(wo)))
         return int(ho.value), int(wo.value)
@@ -511,17 +509,14 @@ class Engine:
     def matmul_plain_plain_records(self, d_a, d_b, d_out, n, m, p, kbits, stream=0):
         """out = a (n x m) . b (m x p) mod 2^kbits on exponent records, outputs in [0, 2^k) with sign word 0; one launch,
         purely stream-ordered"""
-        _chk(self.L.cofhe_hip_matmul_plain_plain_records(self.ctx, C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_out),
-                                                         C.c_uint32(n), C.c_uint32(m), C.c_uint32(p), C.c_uint32(kbits),
-                                                         C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_matmul_plain_plain_records, d_a, d_b, d_out, n, m, p, kbits, stream)
 
     def conv2d_plain_plain_records(self, d_img, d_w, d_out, image, filters, kbits, stride=(1, 1), pad=(0, 0), stream=0, dilation=(1, 1)):
         """out [B, Ho, Wo, Co] = the convolution mod 2^kbits of the plaintext image d_img [B, H, W, C] = `image` with the plaintext
         filters d_w [kh, kw, C, Co] = `filters`, all exponent records, channels last; outputs in [0, 2^k) with sign word 0; one
         launch, purely stream-ordered.  The E * D term of a convolution Beaver triplet.  Returns (Ho, Wo)"""
         geo = _conv_geometry(image, filters, stride, pad, dilation, 1)
-        _chk(self.L.cofhe_hip_conv2d_plain_plain_records(self.ctx, C.c_void_p(d_img), C.c_void_p(d_w), C.c_void_p(d_out), C.byref(geo),
-                                                         C.c_uint32(kbits), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_conv2d_plain_plain_records, d_img, d_w, d_out, C.byref(geo), kbits, stream)
         return conv2d_out_shape(image, filters, stride, pad, dilation, 1)
 
     def conv2d_ct_filters_records(self, d_img_exps, d_filters_cts, d_zero, d_out, image, filters, stride=(1, 1), pad=(0, 0), stream=0,
@@ -530,92 +525,72 @@ class Engine:
         CIPHERTEXT filters d_filters_cts [kh, kw, C, Co] = `filters`, channels last, from the ciphertext d_zero; d_out must not
         overlap an input.  The E * [Bf] term of a convolution Beaver triplet.  Returns (Ho, Wo)"""
         geo = _conv_geometry(image, filters, stride, pad, dilation, 1)
-        _chk(self.L.cofhe_hip_conv2d_ct_filters_records(self.ctx, C.c_void_p(d_img_exps), C.c_void_p(d_filters_cts), C.c_void_p(d_zero),
-                                                        C.c_void_p(d_out), C.byref(geo), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_conv2d_ct_filters_records, d_img_exps, d_filters_cts, d_zero, d_out, C.byref(geo), stream)
         return conv2d_out_shape(image, filters, stride, pad, dilation, 1)
 
     def pow_dot_records(self, d_bases, d_exps, d_out, n_ciphertexts, d, stream=0):
         """out[e] = prod_{i<d} bases[i][e]^exps[i][e]: d ciphertext tensors and d exponent tensors of n elements, power-major,
         one ladder per record with shared squarings (1 <= d <= 8); d_out must not overlap an input"""
-        _chk(self.L.cofhe_hip_pow_dot_records(self.ctx, C.c_void_p(d_bases), C.c_void_p(d_exps), C.c_void_p(d_out),
-                                              C.c_uint64(n_ciphertexts), C.c_uint32(d), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_pow_dot_records, d_bases, d_exps, d_out, n_ciphertexts, d, stream)
 
     def poly_shift_records(self, d_coef, d_x, d_q, n, d, kbits, stream=0):
         """q[i n + e] = sum_{j>=i} C(j,i) coef[j] x[e]^(j-i) mod 2^kbits, i <= d, on exponent records (coef: d + 1, x: n,
         q: (d + 1) n, power-major); outputs in [0, 2^k) with sign word 0"""
-        _chk(self.L.cofhe_hip_poly_shift_records(self.ctx, C.c_void_p(d_coef), C.c_void_p(d_x), C.c_void_p(d_q), C.c_uint64(n),
-                                                 C.c_uint32(d), C.c_uint32(kbits), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_poly_shift_records, d_coef, d_x, d_q, n, d, kbits, stream)
 
     def poly_close_records(self, d_coef, d_e, d_powers, f_record, d_out, n_ciphertexts, d, kbits, stream=0):
         """the closing step of a polynomial evaluation: out[e] = (prod_{i=1..d} powers[i-1][e]^q_i(e[e])) o f^q_0(e[e]) with q the
         Taylor shift of coef (d + 1 exponent records) at the opened values e (n exponent records); powers: d tensors [a^i],
         power-major; f_record: host uint32[168]; d_out must not overlap an input"""
-        import numpy as np
-        f = np.ascontiguousarray(f_record, dtype=np.uint32)
-        assert f.size == 168
-        _chk(self.L.cofhe_hip_poly_close_records(self.ctx, C.c_void_p(d_coef), C.c_void_p(d_e), C.c_void_p(d_powers),
-                                                 f.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(d_out), C.c_uint64(n_ciphertexts),
-                                                 C.c_uint32(d), C.c_uint32(kbits), C.c_void_p(stream)))
+        f = _host_record(f_record)
+        self._call(self.L.cofhe_hip_poly_close_records, d_coef, d_e, d_powers, f.ctypes.data, d_out, n_ciphertexts, d, kbits, stream)
 
     def divfloor_plain_records(self, d_v, d_div, n_div, d_q, n, kbits, stream=0):
         """q[e] = floor(s(v[e]) / div[e mod n_div]) mod 2^kbits on exponent records, s the centred residue (v: n, div: n_div,
         q: n); 1 <= div < 2^(kbits-1), else quotient 0 and bit 4 of device_status; outputs in [0, 2^k) with sign word 0"""
-        _chk(self.L.cofhe_hip_divfloor_plain_records(self.ctx, C.c_void_p(d_v), C.c_void_p(d_div), C.c_uint64(n_div), C.c_void_p(d_q),
-                                                     C.c_uint64(n), C.c_uint32(kbits), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_divfloor_plain_records, d_v, d_div, n_div, d_q, n, kbits, stream)
 
     def div_close_records(self, d_e, d_div, n_div, d_rq, f_record, d_out, n_ciphertexts, kbits, stream=0):
         """the closing step of a division by public divisors: out[e] = (c1, c2 o f^e_q) of rq[e] with e_q = floor(s(e[e]) /
         div[e mod n_div]) mod 2^kbits; e: n exponent records of the opened values x - r, rq: the [r_q] of the division pairs;
         f_record: host uint32[168]; d_out must not overlap an input"""
-        import numpy as np
-        f = np.ascontiguousarray(f_record, dtype=np.uint32)
-        assert f.size == 168
-        _chk(self.L.cofhe_hip_div_close_records(self.ctx, C.c_void_p(d_e), C.c_void_p(d_div), C.c_uint64(n_div), C.c_void_p(d_rq),
-                                                f.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(d_out), C.c_uint64(n_ciphertexts),
-                                                C.c_uint32(kbits), C.c_void_p(stream)))
+        f = _host_record(f_record)
+        self._call(self.L.cofhe_hip_div_close_records, d_e, d_div, n_div, d_rq, f.ctypes.data, d_out, n_ciphertexts, kbits, stream)
 
     def lut_rotate_records(self, d_table, n_tab, d_r, d_out, n, bits, stream=0):
         """out[i 2^bits + j] = table[(i mod n_tab) 2^bits + ((j + r[i]) mod 2^bits)] on exponent records (table: n_tab 2^bits, r: n,
         out: n 2^bits): the plaintext rows of the lookup tuples; 1 <= bits <= 12; d_out must not overlap an input"""
-        _chk(self.L.cofhe_hip_lut_rotate_records(self.ctx, C.c_void_p(d_table), C.c_uint64(n_tab), C.c_void_p(d_r), C.c_void_p(d_out),
-                                                 C.c_uint64(n), C.c_uint32(bits), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_lut_rotate_records, d_table, n_tab, d_r, d_out, n, bits, stream)
 
     def lut_tuples_records(self, d_table, n_tab, d_r, d_rho, h_record, pk_record, f_record, d_out, n, bits, kbits, stream=0):
         """the entries of n lookup tuples: lut_rotate_records, then encrypt_fresh_records over the n 2^bits rows with the randomness
         rho (n 2^bits exponent records, each used once); h_record, pk_record, f_record: host uint32[168]; d_out: n 2^bits
         ciphertexts"""
-        import numpy as np
-        recs = [np.ascontiguousarray(r, dtype=np.uint32) for r in (h_record, pk_record, f_record)]
-        assert all(r.size == 168 for r in recs)
-        _chk(self.L.cofhe_hip_lut_tuples_records(self.ctx, C.c_void_p(d_table), C.c_uint64(n_tab), C.c_void_p(d_r), C.c_void_p(d_rho),
-                                                 *[r.ctypes.data_as(C.POINTER(C.c_uint32)) for r in recs], C.c_void_p(d_out), C.c_uint64(n),
-                                                 C.c_uint32(bits), C.c_uint32(kbits), C.c_void_p(stream)))
+        h, pk, f = _host_record(h_record), _host_record(pk_record), _host_record(f_record)
+        self._call(self.L.cofhe_hip_lut_tuples_records, d_table, n_tab, d_r, d_rho, h.ctypes.data, pk.ctypes.data, f.ctypes.data, d_out, n,
+                   bits, kbits, stream)
 
     def lut_tuples_shape_bits(self, shape_e, shape_t) -> int:
         """host only: bits of the tuples (shape_t = shape_e + [2^bits]) that go with opened values of shape_e; COFHE_HIP_ESHAPE otherwise"""
         bits = C.c_uint32()
-        _chk(self.L.cofhe_hip_lut_tuples_shape_bits(C.c_uint32(len(shape_e)), (C.c_uint32 * max(len(shape_e), 1))(*shape_e), C.c_uint32(len(shape_t)),
-                                                    (C.c_uint32 * max(len(shape_t), 1))(*shape_t), C.byref(bits)))
+        _chk(self.L.cofhe_hip_lut_tuples_shape_bits(len(shape_e), _u32s(shape_e), len(shape_t), _u32s(shape_t), C.byref(bits)))
         return bits.value
 
     def lut_select_records(self, d_e, d_tuples, d_out, n, bits, stream=0):
         """the closing step of a lookup: out[i] = tuples[i 2^bits + (e[i] mod 2^bits)], ciphertexts copied byte for byte; e: n
         exponent records of the opened values x - r; d_out must not overlap an input"""
-        _chk(self.L.cofhe_hip_lut_select_records(self.ctx, C.c_void_p(d_e), C.c_void_p(d_tuples), C.c_void_p(d_out), C.c_uint64(n),
-                                                 C.c_uint32(bits), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_lut_select_records, d_e, d_tuples, d_out, n, bits, stream)
 
     def view_records(self, view, d_src, d_fill, d_dst, words, stream=0):
         """the box of an affine view (a View; module functions view_permute and kin build them) of records of `words` dwords:
         dst[view_dest(i)] = src[view_source(i)], or the one record at d_fill (0: none, for a view that needs no fill) where the view
         reads outside its source; the rest of the destination is not written.  A byte-for-byte copy: nothing is re-randomised."""
-        _chk(self.L.cofhe_hip_view_records(self.ctx, C.byref(view), C.c_void_p(d_src), C.c_void_p(d_fill), C.c_void_p(d_dst), C.c_uint32(words),
-                                           C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_view_records, C.byref(view), d_src, d_fill, d_dst, words, stream)
 
     def gather_records(self, d_src, n_src, d_index, d_fill, d_dst, n_out, words, stream=0):
         """dst[i] = src[index[i]] for the n_out uint32 at d_index: GATHER_FILL writes the record at d_fill, GATHER_KEEP leaves dst[i]
         alone, another index >= n_src writes the fill record (with d_fill 0: leaves dst[i] alone) and sets bit 32 of the status word"""
-        _chk(self.L.cofhe_hip_gather_records(self.ctx, C.c_void_p(d_src), C.c_uint64(n_src), C.c_void_p(d_index), C.c_void_p(d_fill),
-                                             C.c_void_p(d_dst), C.c_uint64(n_out), C.c_uint32(words), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_gather_records, d_src, n_src, d_index, d_fill, d_dst, n_out, words, stream)
 
     def view_tensor_bytes(self, data: bytes, view, fill: bytes = None, kind: int = 2) -> bytes:
         """a serialised tensor (kind 2 ciphertexts / 1 partial decryptions / 0 plaintexts) whose shape is the view's source ->
@@ -627,235 +602,176 @@ class Engine:
         rec_words = REC_WORDS if kind else EXP_REC_WORDS
         n_src, n_box, n_dst, needs_fill = view_check(view)
         if n_box != n_dst:
-            raise CofheHipError(-1, "view_tensor_bytes: the view's box is not its whole destination")
-        held = []
-
-        def load(t):
-            cap = (len(t) // 8) // (3 if kind else 1) + 1
-            raw = self.malloc(len(t) + 4)
-            held.append(raw)
-            recs = self.malloc(cap * 4 * rec_words)
-            held.append(recs)
-            self.upload(raw, t)
-            shape, n = self.unpack_tensor_device(raw, len(t), kind, recs, cap)
-            return recs, shape, n
-
-        try:
-            dsrc, shape, n = load(data)
+            raise CofheHipError(COFHE_HIP_EINVAL, "view_tensor_bytes: the view's box is not its whole destination")
+        with _DeviceScope(self) as dev:
+            dsrc, shape, n = dev.load(data, kind)
             if list(shape) != [int(view.src_extent[a]) for a in range(view.src_ndim)] or n != per * n_src:
-                raise CofheHipError(-2, "view_tensor_bytes: the tensor's shape is not the view's source")
+                raise CofheHipError(COFHE_HIP_ESHAPE, "view_tensor_bytes: the tensor's shape is not the view's source")
             dfill = 0
             if fill is not None:
-                dfill, _, nf = load(fill)
+                dfill, _, nf = dev.load(fill, kind)
                 if nf != per:
-                    raise CofheHipError(-2, "view_tensor_bytes: the fill is a tensor of one element")
+                    raise CofheHipError(COFHE_HIP_ESHAPE, "view_tensor_bytes: the fill is a tensor of one element")
             out_shape = [int(view.dst_extent[d]) for d in range(view.out_ndim)]
-            dout = self.malloc(max(n_dst, 1) * per * rec_words * 4)
-            held.append(dout)
+            dout = dev.alloc(max(n_dst, 1) * per * rec_words * 4)
             self.view_records(view, dsrc, dfill, dout, per * rec_words)
-            cap = self.packed_size_bound(per * n_dst, kind, len(out_shape))
-            packed = self.malloc(cap)
-            held.append(packed)
-            ln = self.pack_tensor_device(dout, per * n_dst, kind, out_shape, packed, cap)
-            return self.download(packed, ln, dtype="uint8").tobytes()
-        finally:
-            for p in held:
-                self.free(p)
+            return dev.packed(dout, per * n_dst, kind, out_shape)
 
     def spline_rows_records(self, d_pieces, n_tab, d_r, d_out, n, bits, shift, d, kbits, stream=0):
         """the plaintext rows of n spline tuples on exponent records: out[(i 2^bits + j) (d + 1) + c] = coefficient c of the Taylor
         shift of piece (j + rho_i) mod 2^bits of table i mod n_tab at r_i minus the piece's origin, rho_i = bits shift .. shift + bits
         - 1 of r_i mod 2^kbits (pieces: n_tab 2^bits (d + 1), r: n, out: n 2^bits (d + 1)); d_out must not overlap an input"""
-        _chk(self.L.cofhe_hip_spline_rows_records(self.ctx, C.c_void_p(d_pieces), C.c_uint64(n_tab), C.c_void_p(d_r), C.c_void_p(d_out),
-                                                  C.c_uint64(n), C.c_uint32(bits), C.c_uint32(shift), C.c_uint32(d), C.c_uint32(kbits),
-                                                  C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_spline_rows_records, d_pieces, n_tab, d_r, d_out, n, bits, shift, d, kbits, stream)
 
     def spline_tuples_records(self, d_pieces, n_tab, d_r, d_rho, h_record, pk_record, f_record, d_out, n, bits, shift, d, kbits, stream=0):
         """the entries of n spline tuples: spline_rows_records, then encrypt_fresh_records over the n 2^bits (d + 1) rows with the
         randomness rho (as many exponent records, each used once); h_record, pk_record, f_record: host uint32[168]; d_out:
         n 2^bits (d + 1) ciphertexts"""
-        import numpy as np
-        recs = [np.ascontiguousarray(r, dtype=np.uint32) for r in (h_record, pk_record, f_record)]
-        assert all(r.size == 168 for r in recs)
-        _chk(self.L.cofhe_hip_spline_tuples_records(self.ctx, C.c_void_p(d_pieces), C.c_uint64(n_tab), C.c_void_p(d_r), C.c_void_p(d_rho),
-                                                    *[r.ctypes.data_as(C.POINTER(C.c_uint32)) for r in recs], C.c_void_p(d_out), C.c_uint64(n),
-                                                    C.c_uint32(bits), C.c_uint32(shift), C.c_uint32(d), C.c_uint32(kbits), C.c_void_p(stream)))
+        h, pk, f = _host_record(h_record), _host_record(pk_record), _host_record(f_record)
+        self._call(self.L.cofhe_hip_spline_tuples_records, d_pieces, n_tab, d_r, d_rho, h.ctypes.data, pk.ctypes.data, f.ctypes.data, d_out,
+                   n, bits, shift, d, kbits, stream)
 
     def spline_tuples_shape(self, shape_e, shape_t):
         """host only: (bits, d) of the tuples (shape_t = shape_e + [2^bits, d + 1]) that go with opened values of shape_e;
         COFHE_HIP_ESHAPE otherwise"""
         bits, d = C.c_uint32(), C.c_uint32()
-        _chk(self.L.cofhe_hip_spline_tuples_shape(C.c_uint32(len(shape_e)), (C.c_uint32 * max(len(shape_e), 1))(*shape_e), C.c_uint32(len(shape_t)),
-                                                  (C.c_uint32 * max(len(shape_t), 1))(*shape_t), C.byref(bits), C.byref(d)))
+        _chk(self.L.cofhe_hip_spline_tuples_shape(len(shape_e), _u32s(shape_e), len(shape_t), _u32s(shape_t), C.byref(bits), C.byref(d)))
         return bits.value, d.value
 
     def spline_powers_records(self, d_e, d_out, n, d, kbits, stream=0):
         """out[(c - 1) n + i] = e[i]^c mod 2^kbits, c = 1 .. d, on exponent records (e: n, out: d n, power-major)"""
-        _chk(self.L.cofhe_hip_spline_powers_records(self.ctx, C.c_void_p(d_e), C.c_void_p(d_out), C.c_uint64(n), C.c_uint32(d),
-                                                    C.c_uint32(kbits), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_spline_powers_records, d_e, d_out, n, d, kbits, stream)
 
     def spline_close_records(self, d_e, d_tuples, d_out, n, bits, shift, d, kbits, stream=0):
         """the closing step of a spline: out[i] = [q_{j,0}] o prod_{c=1..d} [q_{j,c}]^(e[i]^c mod 2^kbits) over row j = bits shift ..
         shift + bits - 1 of e[i] of element i's tuple; e: n exponent records of the opened values x - r, tuples: n 2^bits (d + 1)
         ciphertexts; d_out must not overlap an input"""
-        _chk(self.L.cofhe_hip_spline_close_records(self.ctx, C.c_void_p(d_e), C.c_void_p(d_tuples), C.c_void_p(d_out), C.c_uint64(n),
-                                                   C.c_uint32(bits), C.c_uint32(shift), C.c_uint32(d), C.c_uint32(kbits), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_spline_close_records, d_e, d_tuples, d_out, n, bits, shift, d, kbits, stream)
 
     def cmp_rows_records(self, d_r, d_out, n, bits, digit_bits, kbits, stream=0):
         """the plaintext rows of n comparison tuples on exponent records: out[(i nd + j) 2^d + c] = 2^j sgn(r_ij - c), r_ij digit j
         of r[i] mod 2^bits, nd = ceil(bits / d) (r: n, out: n nd 2^d); d_out must not overlap d_r"""
-        _chk(self.L.cofhe_hip_cmp_rows_records(self.ctx, C.c_void_p(d_r), C.c_void_p(d_out), C.c_uint64(n), C.c_uint32(bits),
-                                               C.c_uint32(digit_bits), C.c_uint32(kbits), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_cmp_rows_records, d_r, d_out, n, bits, digit_bits, kbits, stream)
 
     def cmp_tuples_records(self, d_r, d_rho, h_record, pk_record, f_record, d_out, n, bits, digit_bits, kbits, stream=0):
         """the entries of n comparison tuples: cmp_rows_records, then encrypt_fresh_records over the n nd 2^d rows with the
         randomness rho (as many exponent records, each used once); h_record, pk_record, f_record: host uint32[168]; d_out:
         n nd 2^d ciphertexts"""
-        import numpy as np
-        recs = [np.ascontiguousarray(r, dtype=np.uint32) for r in (h_record, pk_record, f_record)]
-        assert all(r.size == 168 for r in recs)
-        _chk(self.L.cofhe_hip_cmp_tuples_records(self.ctx, C.c_void_p(d_r), C.c_void_p(d_rho), *[r.ctypes.data_as(C.POINTER(C.c_uint32)) for r in recs],
-                                                 C.c_void_p(d_out), C.c_uint64(n), C.c_uint32(bits), C.c_uint32(digit_bits), C.c_uint32(kbits),
-                                                 C.c_void_p(stream)))
+        h, pk, f = _host_record(h_record), _host_record(pk_record), _host_record(f_record)
+        self._call(self.L.cofhe_hip_cmp_tuples_records, d_r, d_rho, h.ctypes.data, pk.ctypes.data, f.ctypes.data, d_out, n, bits, digit_bits,
+                   kbits, stream)
 
     def cmp_shape(self, bits, digit_bits, kbits, shape_e=None, shape_t=None):
         """host only: (nd, nd 2^d) of a comparison on a window of `bits` bits in digits of digit_bits bits (COFHE_HIP_EINVAL for
         the parameter bounds); with shape_t, also COFHE_HIP_ESHAPE unless shape_t = shape_e + [nd, 2^d]"""
         nd, entries = C.c_uint32(), C.c_uint32()
         se, st = list(shape_e or []), shape_t
-        _chk(self.L.cofhe_hip_cmp_shape(C.c_uint32(bits), C.c_uint32(digit_bits), C.c_uint32(kbits), C.c_uint32(len(se)),
-                                        (C.c_uint32 * max(len(se), 1))(*se), C.c_uint32(len(st) if st is not None else 0),
-                                        (C.c_uint32 * max(len(st), 1))(*st) if st is not None else None, C.byref(nd), C.byref(entries)))
+        _chk(self.L.cofhe_hip_cmp_shape(bits, digit_bits, kbits, len(se), _u32s(se), len(st) if st is not None else 0,
+                                        _u32s(st) if st is not None else None, C.byref(nd), C.byref(entries)))
         return nd.value, entries.value
 
     def cmp_close_records(self, d_e, d_tuples, d_out, d_wrap, n, bits, digit_bits, kbits, stream=0):
         """the closing step of a comparison's first round: out[2 i + s] = the product of the nd entries of element i's tuple that
         threshold s (A, then B) of e[i] mod 2^bits selects, wrap[i] = [A > B]; e: n exponent records of the opened values x - r,
         tuples: n nd 2^d ciphertexts, out: 2 n ciphertexts, wrap: n exponent records; the outputs must not overlap an input"""
-        _chk(self.L.cofhe_hip_cmp_close_records(self.ctx, C.c_void_p(d_e), C.c_void_p(d_tuples), C.c_void_p(d_out), C.c_void_p(d_wrap),
-                                                C.c_uint64(n), C.c_uint32(bits), C.c_uint32(digit_bits), C.c_uint32(kbits), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_cmp_close_records, d_e, d_tuples, d_out, d_wrap, n, bits, digit_bits, kbits, stream)
 
     def decrypt_records(self, d_cts, d_sk, f_record, d_out, n_ciphertexts, kbits, stream=0):
         """f_record: host numpy uint32[168]; d_out: n * (ceil(k/32) + 1) words"""
-        import numpy as np
-        f = np.ascontiguousarray(f_record, dtype=np.uint32)
-        _chk(self.L.cofhe_hip_decrypt_records(self.ctx, C.c_void_p(d_cts), C.c_void_p(d_sk), f.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                              C.c_void_p(d_out), C.c_uint64(n_ciphertexts), C.c_uint32(kbits), C.c_void_p(stream)))
+        f = _host_record(f_record)
+        self._call(self.L.cofhe_hip_decrypt_records, d_cts, d_sk, f.ctypes.data, d_out, n_ciphertexts, kbits, stream)
 
     def accumulate_records(self, d_x, d_zero, d_out, n, m, p, stream=0):
         """out[i,k] = zero o prod_j x[i,j,k] (x: n*m*p ciphertexts, out: n*p)"""
-        _chk(self.L.cofhe_hip_accumulate_records(self.ctx, C.c_void_p(d_x), C.c_void_p(d_zero), C.c_void_p(d_out),
-                                                 C.c_uint32(n), C.c_uint32(m), C.c_uint32(p), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_accumulate_records, d_x, d_zero, d_out, n, m, p, stream)
 
     def pow_form_records(self, d_base, d_exp, d_out, n_forms, stream=0):
-        _chk(self.L.cofhe_hip_pow_form_records(self.ctx, C.c_void_p(d_base), C.c_void_p(d_exp), C.c_void_p(d_out),
-                                               C.c_uint64(n_forms), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_pow_form_records, d_base, d_exp, d_out, n_forms, stream)
 
     def pow_fixed_base_record(self, base_record, exp_record, d_out, stream=0):
         """base_record (168 u32) and exp_record (32 u32) are host numpy arrays; d_out one device record.  The
         context caches the table base^(2^j) of the last few bases."""
-        import numpy as np
-        b = np.ascontiguousarray(base_record, dtype=np.uint32)
-        e = np.ascontiguousarray(exp_record, dtype=np.uint32)
-        assert b.size == 168 and e.size == 32
-        _chk(self.L.cofhe_hip_pow_fixed_base_record(self.ctx, b.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p),
-                                                    C.c_void_p(d_out), C.c_void_p(stream)))
+        b, e = _host_record(base_record), _host_record(exp_record, EXP_REC_WORDS)
+        self._call(self.L.cofhe_hip_pow_fixed_base_record, b.ctypes.data, e.ctypes.data, d_out, stream)
 
     def pow_fixed_base_records(self, base_records, exp_records, d_out, stream=0):
         """n <= 4 fixed-base powers in one product tree; base_records n x 168 u32, exp_records n x 32 u32 (host)"""
         import numpy as np
         b = np.ascontiguousarray(base_records, dtype=np.uint32).reshape(-1)
         e = np.ascontiguousarray(exp_records, dtype=np.uint32).reshape(-1)
-        n = b.size // 168
-        assert b.size == n * 168 and e.size == n * 32
-        _chk(self.L.cofhe_hip_pow_fixed_base_records(self.ctx, C.c_uint32(n), b.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p),
-                                                     C.c_void_p(d_out), C.c_void_p(stream)))
+        n = b.size // REC_WORDS
+        assert b.size == n * REC_WORDS and e.size == n * EXP_REC_WORDS
+        self._call(self.L.cofhe_hip_pow_fixed_base_records, n, b.ctypes.data, e.ctypes.data, d_out, stream)
 
     def encrypt_records(self, d_plain, d_c1_pkr, f_record, d_out, n_ciphertexts, kbits, stream=0):
         """d_plain: n exponent records; d_c1_pkr: records of h^r and pk^r; d_out: 2n records"""
-        import numpy as np
-        f = np.ascontiguousarray(f_record, dtype=np.uint32)
-        _chk(self.L.cofhe_hip_encrypt_records(self.ctx, C.c_void_p(d_plain), C.c_void_p(d_c1_pkr),
-                                              f.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(d_out),
-                                              C.c_uint64(n_ciphertexts), C.c_uint32(kbits), C.c_void_p(stream)))
+        f = _host_record(f_record)
+        self._call(self.L.cofhe_hip_encrypt_records, d_plain, d_c1_pkr, f.ctypes.data, d_out, n_ciphertexts, kbits, stream)
 
     def pow_fixed_base_many_records(self, base_record, d_exps, d_out, n, stream=0):
         """out[i] = base^e[i] by the fixed-base comb: base_record a host uint32[168], d_exps n exponent records, d_out n records"""
-        import numpy as np
-        b = np.ascontiguousarray(base_record, dtype=np.uint32)
-        assert b.size == 168
-        _chk(self.L.cofhe_hip_pow_fixed_base_many_records(self.ctx, b.ctypes.data_as(C.c_void_p), C.c_void_p(d_exps), C.c_void_p(d_out),
-                                                          C.c_uint64(n), C.c_void_p(stream)))
+        b = _host_record(base_record)
+        self._call(self.L.cofhe_hip_pow_fixed_base_many_records, b.ctypes.data, d_exps, d_out, n, stream)
 
     def encrypt_fresh_records(self, d_plain, d_r, h_record, pk_record, f_record, d_out, n_ciphertexts, kbits, stream=0):
         """out[i] = (h^r_i, pk^r_i o f^(m_i mod 2^k)): one r per ciphertext (d_r: n exponent records); h, pk, f host records"""
-        import numpy as np
-        recs = [np.ascontiguousarray(x, dtype=np.uint32) for x in (h_record, pk_record, f_record)]
-        assert all(x.size == 168 for x in recs)
-        _chk(self.L.cofhe_hip_encrypt_fresh_records(self.ctx, C.c_void_p(d_plain), C.c_void_p(d_r), *[x.ctypes.data_as(C.c_void_p) for x in recs],
-                                                    C.c_void_p(d_out), C.c_uint64(n_ciphertexts), C.c_uint32(kbits), C.c_void_p(stream)))
+        h, pk, f = _host_record(h_record), _host_record(pk_record), _host_record(f_record)
+        self._call(self.L.cofhe_hip_encrypt_fresh_records, d_plain, d_r, h.ctypes.data, pk.ctypes.data, f.ctypes.data, d_out, n_ciphertexts,
+                   kbits, stream)
 
     def rerandomize_records(self, d_cts, d_r, h_record, pk_record, d_out, n_ciphertexts, stream=0):
         """out[i] = (c1_i o h^r_i, c2_i o pk^r_i); d_out may be d_cts"""
-        import numpy as np
-        recs = [np.ascontiguousarray(x, dtype=np.uint32) for x in (h_record, pk_record)]
-        assert all(x.size == 168 for x in recs)
-        _chk(self.L.cofhe_hip_rerandomize_records(self.ctx, C.c_void_p(d_cts), C.c_void_p(d_r), *[x.ctypes.data_as(C.c_void_p) for x in recs],
-                                                  C.c_void_p(d_out), C.c_uint64(n_ciphertexts), C.c_void_p(stream)))
+        h, pk = _host_record(h_record), _host_record(pk_record)
+        self._call(self.L.cofhe_hip_rerandomize_records, d_cts, d_r, h.ctypes.data, pk.ctypes.data, d_out, n_ciphertexts, stream)
 
     def part_decrypt_records(self, d_cts, d_share, d_out, n_ciphertexts, stream=0):
         """d_out: n form records = c1^share"""
-        _chk(self.L.cofhe_hip_part_decrypt_records(self.ctx, C.c_void_p(d_cts), C.c_void_p(d_share), C.c_void_p(d_out),
-                                                   C.c_uint64(n_ciphertexts), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_part_decrypt_records, d_cts, d_share, d_out, n_ciphertexts, stream)
 
     def combine_part_decryptions_records(self, d_cts, d_parts, lambdas, f_record, d_out, n_ciphertexts, kbits, stream=0):
         """d_parts: len(lambdas) x n form records (party-major); lambdas: +1 / -1 per party"""
-        import numpy as np
-        f = np.ascontiguousarray(f_record, dtype=np.uint32)
+        f = _host_record(f_record)
         lam = (C.c_int32 * len(lambdas))(*lambdas)
-        _chk(self.L.cofhe_hip_combine_part_decryptions_records(
-            self.ctx, C.c_void_p(d_cts), C.c_void_p(d_parts), C.c_uint32(len(lambdas)), lam,
-            f.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_void_p(d_out), C.c_uint64(n_ciphertexts), C.c_uint32(kbits),
-            C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_combine_part_decryptions_records, d_cts, d_parts, len(lambdas), lam, f.ctypes.data, d_out,
+                   n_ciphertexts, kbits, stream)
 
     # ---- device memory and fences of the library's own HIP runtime (bench.py uses no other) --------------------
     def malloc(self, nbytes: int) -> int:
         p = C.c_void_p()
-        _chk(self.L.cofhe_hip_malloc(self.ctx, C.c_size_t(nbytes), C.byref(p)))
+        self._call(self.L.cofhe_hip_malloc, nbytes, C.byref(p))
         return p.value
 
     def free(self, dptr: int, stream=0):
-        _chk(self.L.cofhe_hip_free_on_stream(self.ctx, C.c_void_p(dptr), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_free_on_stream, dptr, stream)
 
     def upload(self, dptr: int, host, stream=0):
         """host: a contiguous numpy array (or bytes); copies all of it to dptr"""
         import numpy as np
         a = np.frombuffer(host, dtype=np.uint8) if isinstance(host, (bytes, bytearray)) else np.ascontiguousarray(host)
-        _chk(self.L.cofhe_hip_upload(self.ctx, C.c_void_p(dptr), a.ctypes.data_as(C.c_void_p), C.c_size_t(a.nbytes), C.c_void_p(stream)))
-        _chk(self.L.cofhe_hip_stream_sync(self.ctx, C.c_void_p(stream)))       # the host array may go away after the call
+        self._call(self.L.cofhe_hip_upload, dptr, a.ctypes.data, a.nbytes, stream)
+        self._call(self.L.cofhe_hip_stream_sync, stream)       # the host array may go away after the call
 
     def download(self, dptr: int, nbytes: int, dtype="uint32", stream=0):
         """device -> a new numpy array of `dtype` (synchronises the stream)"""
         import numpy as np
         out = np.empty(nbytes // np.dtype(dtype).itemsize, dtype=dtype)
-        _chk(self.L.cofhe_hip_download(self.ctx, out.ctypes.data_as(C.c_void_p), C.c_void_p(dptr), C.c_size_t(out.nbytes), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_download, out.ctypes.data, dptr, out.nbytes, stream)
         return out
 
     def stream_sync(self, stream=0):
-        _chk(self.L.cofhe_hip_stream_sync(self.ctx, C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_stream_sync, stream)
 
     def profile_read(self, kernel: str, clear=False):
         """(summed ms, launches) of the spans the "profile_kernels" option recorded for `kernel`"""
         ms, n = C.c_float(), C.c_uint32()
-        _chk(self.L.cofhe_hip_profile_read(self.ctx, C.c_char_p(kernel.encode()), C.byref(ms), C.byref(n), C.c_int(1 if clear else 0)))
+        self._call(self.L.cofhe_hip_profile_read, kernel.encode(), C.byref(ms), C.byref(n), 1 if clear else 0)
         return float(ms.value), int(n.value)
 
     # ---- more than one GPU (cofhe_amd/csrc/shard.hip) -------------------------------------------------------
     def shard_rows(self, n_rows, world, rank):
         """(row0, n_local) of this rank's contiguous row block"""
         r0, nl = C.c_uint64(), C.c_uint64()
-        self.L.cofhe_hip_shard_rows.restype = None
-        self.L.cofhe_hip_shard_rows(C.c_uint64(n_rows), C.c_uint32(world), C.c_uint32(rank), C.byref(r0), C.byref(nl))
+        self.L.cofhe_hip_shard_rows(n_rows, world, rank, C.byref(r0), C.byref(nl))
         return r0.value, nl.value
 
     def comm_unique_id(self) -> bytes:
@@ -866,7 +782,7 @@ class Engine:
     def comm_create(self, unique_id: bytes, world: int, rank: int):
         comm = C.c_void_p()
         buf = (C.c_uint8 * 128).from_buffer_copy(unique_id)
-        _chk(self.L.cofhe_hip_comm_create(self.ctx, buf, C.c_uint32(world), C.c_uint32(rank), C.byref(comm)))
+        self._call(self.L.cofhe_hip_comm_create, buf, world, rank, C.byref(comm))
         return comm
 
     def comm_info(self, comm):
@@ -876,51 +792,47 @@ class Engine:
         return w.value, r.value, n.value
 
     def comm_set_option(self, comm, name: str, value: int):
-        _chk(self.L.cofhe_hip_comm_set_option(comm, C.c_char_p(name.encode()), C.c_int64(value)))
+        _chk(self.L.cofhe_hip_comm_set_option(comm, name.encode(), value))
 
     def comm_destroy(self, comm):
-        self.L.cofhe_hip_comm_destroy.restype = None
         self.L.cofhe_hip_comm_destroy(comm)
 
     def all_gather_rows(self, comm, d_local, n_rows, row_bytes, d_out, stream=0):
-        _chk(self.L.cofhe_hip_all_gather_rows(self.ctx, comm, C.c_void_p(d_local), C.c_uint64(n_rows), C.c_uint64(row_bytes),
-                                              C.c_void_p(d_out), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_all_gather_rows, comm, d_local, n_rows, row_bytes, d_out, stream)
 
     def set_option(self, name: str, value: int):
         """pins a launcher decision of the matrix product ("wnaf_width", "matmul_segments"; 0 = automatic)"""
-        _chk(self.L.cofhe_hip_ctx_set_option(self.ctx, C.c_char_p(name.encode()), C.c_int64(value)))
+        self._call(self.L.cofhe_hip_ctx_set_option, name.encode(), value)
 
     def device_status(self, clear=True, stream=0) -> int:
         """status word of the kernels (bit 1: Euclid cap, 2: reduction cap, 4: division; 32: gather_records met an index beyond
         its source and wrote the fill record): 0 unless a record was not a form or an index was bad"""
         w = C.c_uint32()
-        _chk(self.L.cofhe_hip_device_status(self.ctx, C.byref(w), C.c_int(1 if clear else 0), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_device_status, C.byref(w), 1 if clear else 0, stream)
         return w.value
 
     def validate_records(self, d_records, n_records, stream=0) -> bool:
         """True when every record is a reduced form of the context's discriminant"""
         ok = C.c_int()
-        _chk(self.L.cofhe_hip_validate_records(self.ctx, C.c_void_p(d_records), C.c_uint64(n_records), C.byref(ok), C.c_void_p(stream)))
+        self._call(self.L.cofhe_hip_validate_records, d_records, n_records, C.byref(ok), stream)
         return bool(ok.value)
 
     def time_compose(self, d_a, d_b, d_out, n_records, iters, stream=0) -> float:
         ms = C.c_float()
-        _chk(self.L.cofhe_hip_time_compose(self.ctx, C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_out),
-                                           C.c_uint64(n_records), C.c_int(iters), C.c_void_p(stream), C.byref(ms)))
+        self._call(self.L.cofhe_hip_time_compose, d_a, d_b, d_out, n_records, iters, stream, C.byref(ms))
         return float(ms.value)
-
 
     def time_stream(self, fn, iters=1, stream=0) -> float:
         """milliseconds per call of `iters` calls of fn() between two HIP events on `stream` (cofhe_hip_timer_*): the
         stream the library launches on"""
         h = C.c_void_p()
-        _chk(self.L.cofhe_hip_timer_start(self.ctx, C.c_void_p(stream), C.byref(h)))
+        self._call(self.L.cofhe_hip_timer_start, stream, C.byref(h))
         try:
             for _ in range(iters):
                 fn()
         finally:
             ms = C.c_float()
-            rc = self.L.cofhe_hip_timer_stop(self.ctx, h, C.c_void_p(stream), C.byref(ms))
+            rc = self.L.cofhe_hip_timer_stop(self.ctx, h, stream, C.byref(ms))
         _chk(rc)
         return float(ms.value) / iters
 
@@ -935,8 +847,7 @@ def workspace_plan(op: str, *args):
 
     regs = (Region * 8)()
     n, total = C.c_uint32(), C.c_uint64()
-    a = (C.c_uint64 * max(1, len(args)))(*[int(x) for x in args])
-    _chk(L.cofhe_hip_workspace_plan(op.encode(), a, C.c_uint32(len(args)), regs, C.c_uint32(8), C.byref(n), C.byref(total)))
+    _chk(L.cofhe_hip_workspace_plan(op.encode(), _u64s(args), len(args), regs, 8, C.byref(n), C.byref(total)))
     return [(regs[i].name.decode(), int(regs[i].offset), int(regs[i].bytes)) for i in range(n.value)], int(total.value)
 
 
@@ -948,7 +859,7 @@ def _conv_shape(image, filters, stride, pad):
     B, H, W, Cin = image
     kh, kw, Cf, Co = filters
     if Cf != Cin:
-        raise CofheHipError(-2, "conv2d: the channels of the filters and of the image differ")
+        raise CofheHipError(COFHE_HIP_ESHAPE, "conv2d: the channels of the filters and of the image differ")
     return _ConvShape(B, H, W, Cin, kh, kw, Co, stride[0], stride[1], pad[0], pad[1])
 
 
@@ -960,7 +871,7 @@ def _conv_geometry(image, filters, stride, pad, dilation, groups):
     B, H, W, Cin = image
     kh, kw, Cf, Co = filters
     if groups > 0 and Cf != Cin // groups:
-        raise CofheHipError(-2, "conv2d: the channels of the filters and of the image differ")
+        raise CofheHipError(COFHE_HIP_ESHAPE, "conv2d: the channels of the filters and of the image differ")
     return _ConvGeometry(B, H, W, Cin, kh, kw, Co, stride[0], stride[1], pad[0], pad[1], dilation[0], dilation[1], groups)
 
 
@@ -1016,27 +927,27 @@ def view_check(view):
 def view_permute(shape, perm):
     """output axis d is source axis perm[d] (numpy.transpose)"""
     v = View()
-    _chk(load_library().cofhe_hip_view_permute(_u64s(shape), C.c_uint32(len(shape)), (C.c_uint32 * max(1, len(perm)))(*perm), C.byref(v)))
+    _chk(load_library().cofhe_hip_view_permute(_u64s(shape), len(shape), _u32s(perm), C.byref(v)))
     return v
 
 
 def view_slice(shape, start, stop, step):
     """src[start:stop:step] per axis, bounds in range; with a negative step a stop of -1 means down to and including element 0"""
     v = View()
-    _chk(load_library().cofhe_hip_view_slice(_u64s(shape), C.c_uint32(len(shape)), _i64s(start), _i64s(stop), _i64s(step), C.byref(v)))
+    _chk(load_library().cofhe_hip_view_slice(_u64s(shape), len(shape), _i64s(start), _i64s(stop), _i64s(step), C.byref(v)))
     return v
 
 
 def view_pad(shape, lo, hi):
     v = View()
-    _chk(load_library().cofhe_hip_view_pad(_u64s(shape), C.c_uint32(len(shape)), _u64s(lo), _u64s(hi), C.byref(v)))
+    _chk(load_library().cofhe_hip_view_pad(_u64s(shape), len(shape), _u64s(lo), _u64s(hi), C.byref(v)))
     return v
 
 
 def view_broadcast(shape, out_shape):
     """numpy's rule, right-aligned"""
     v = View()
-    _chk(load_library().cofhe_hip_view_broadcast(_u64s(shape), C.c_uint32(len(shape)), _u64s(out_shape), C.c_uint32(len(out_shape)), C.byref(v)))
+    _chk(load_library().cofhe_hip_view_broadcast(_u64s(shape), len(shape), _u64s(out_shape), len(out_shape), C.byref(v)))
     return v
 
 
@@ -1062,19 +973,16 @@ COMB_POWERS, COMB_ENCRYPT, COMB_RERANDOMIZE = 0, 1, 2
 def comb_shape(kind: int, n: int, exp_bits: int, kbits: int = 0, w: int = 0, chunk: int = 0):
     """cofhe_hip_comb_shape (host only): (w, slots per output record, items per pass) the comb launcher takes for n items of
     `kind` whose longest exponent has exp_bits bits; w / chunk pin the "comb_width" / "comb_chunk" options (0: automatic)"""
-    L = load_library()
     ow, sl, ch = C.c_uint32(), C.c_uint32(), C.c_uint64()
-    _chk(L.cofhe_hip_comb_shape(C.c_uint32(kind), C.c_uint64(n), C.c_uint32(exp_bits), C.c_uint32(kbits), C.c_uint32(w), C.c_uint64(chunk),
-                                C.byref(ow), C.byref(sl), C.byref(ch)))
+    _chk(load_library().cofhe_hip_comb_shape(kind, n, exp_bits, kbits, w, chunk, C.byref(ow), C.byref(sl), C.byref(ch)))
     return int(ow.value), int(sl.value), int(ch.value)
 
 
 def gather_plan(n_rows: int, row_bytes: int, world: int):
     """cofhe_hip_gather_plan (host only): ([(byte offset, byte count)] per rank, uniform) -- the collective the
     library will run for a row-sharded tensor"""
-    L = load_library()
     offs = (C.c_uint64 * world)()
     cnts = (C.c_uint64 * world)()
     uni = C.c_int()
-    _chk(L.cofhe_hip_gather_plan(C.c_uint64(n_rows), C.c_uint64(row_bytes), C.c_uint32(world), offs, cnts, C.byref(uni)))
+    _chk(load_library().cofhe_hip_gather_plan(n_rows, row_bytes, world, offs, cnts, C.byref(uni)))
     return [(int(offs[r]), int(cnts[r])) for r in range(world)], bool(uni.value)
