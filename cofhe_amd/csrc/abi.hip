@@ -2,9 +2,10 @@
 // two-build launch, flag words, the table-cache lookup), the workspace plans, the launchers (one launch site per kernel and
 // route; product_tree is the pairwise tree of them all) and the host-side tensor formats.  The kernels are declared in
 // kernels.hpp and defined in cofhe_hip.hip, wide.hip, comb.hip, affine.hip, matmul_left.hip, conv.hip, conv_ct.hip, pow_dot.hip,
-// divide.hip, lut.hip, spline.hip, view.hip and compare.hip; this file holds no device code of its own.  conv.hip holds the three kernels of the
+// divide.hip, divide_exact.hip, lut.hip, spline.hip, view.hip and compare.hip; this file holds no device code of its own.  conv.hip holds the three kernels of the
 // convolution, conv_ct.hip the two that ciphertext filters add, pow_dot.hip the two of
-// the polynomial evaluation, divide.hip the signed floor division of the division by public divisors, lut.hip the two copies of
+// the polynomial evaluation, divide.hip the signed floor division of the division by public divisors, divide_exact.hip the four
+// kernels of the exact division by small divisors, lut.hip the two copies of
 // the table lookups, spline.hip the three kernels of the piecewise-polynomial activations, view.hip the two that rearrange
 // resident tensors, compare.hip the two of the digit comparisons.
 #include <hip/hip_runtime.h>
@@ -24,6 +25,7 @@
 #include "plain_mm.hpp"
 #include "poly_shift.hpp"
 #include "plain_div.hpp"
+#include "plain_divmod.hpp"
 #include "lut.hpp"
 #include "spline.hpp"
 #include "view.hpp"
@@ -1844,6 +1846,136 @@ int cofhe_hip_div_close_records(cofhe_hip_ctx *ctx, const void *d_e, const void 
     if (int rc = q.get(ctx, n_ct * exp_bytes)) return rc;
     if (int rc = cofhe_hip_divfloor_plain_records(ctx, d_e, d_div, n_div, q.p, n_ct, kbits, stream)) return rc;
     return cofhe_hip_add_plain_records(ctx, d_rq, q.p, nullptr, nullptr, nullptr, f_record, d_out, n_ct, kbits, 0, stream);
+}
+
+// ---- exact floor division by small public divisors from one opened value (divide_exact.hip) ---------------------------------
+static_assert(COFHE_HIP_DIVX_MAX_ROWS == DIVX_MAX_ROWS, "the header's bound is the kernels'");
+namespace {
+// what every exact-division entry point refuses before it looks at a pointer: k, the tuple length, and element i reading
+// divisor i mod n_div
+int divx_check(uint32_t kbits, uint32_t rows, uint64_t n_div, uint64_t n) {
+    if (kbits == 0 || kbits > PDV_MAX_KBITS) return fail(COFHE_HIP_EINVAL, "k out of range");
+    if (rows == 0 || rows > DIVX_MAX_ROWS) return fail(COFHE_HIP_EINVAL, "divx: a tuple has 1 <= rows <= 4096 entries");
+    if (n_div == 0 || n % n_div != 0) return fail(COFHE_HIP_EINVAL, "divx: the element count is a multiple of the divisor count, which is not 0");
+    if (n > (1ull << 36) / DIVX_MAX_ROWS) return fail(COFHE_HIP_EINVAL, "divx: too many items");
+    return COFHE_HIP_OK;
+}
+}  // namespace
+// touches no shared state of the context but the status word, which the kernel sets atomically: no lock
+int cofhe_hip_divmod_plain_records(cofhe_hip_ctx *ctx, const void *d_v, const void *d_div, uint64_t n_div, void *d_q, void *d_rem, uint64_t n,
+                                   uint32_t rows, uint32_t kbits, void *stream) {
+    if (int rc = divx_check(kbits, rows, n_div, n)) return rc;
+    if (n == 0) return COFHE_HIP_OK;
+    if (!d_v || !d_div || !d_q || !d_rem) return fail(COFHE_HIP_EINVAL, "null argument");
+    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4;
+    if (overlaps(d_q, n * exp_bytes, d_v, n * exp_bytes) || overlaps(d_q, n * exp_bytes, d_div, n_div * exp_bytes) ||
+        overlaps(d_rem, n * 4, d_v, n * exp_bytes) || overlaps(d_rem, n * 4, d_div, n_div * exp_bytes) || overlaps(d_rem, n * 4, d_q, n * exp_bytes))
+        return fail(COFHE_HIP_EINVAL, "divmod: an output overlaps an input or the other output");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned blocks = (unsigned)((n + PDV_GROUPS - 1) / PDV_GROUPS);       // n <= 2^24: divx_check
+    {
+        ProfScope ps(ctx, "k_plain_divmod", st);
+        hipLaunchKernelGGL(k_plain_divmod, dim3(blocks), dim3(PDV_THREADS), 0, st, (const uint32_t *)d_v, (const uint32_t *)d_div, n_div,
+                           (uint32_t *)d_q, (uint32_t *)d_rem, n, rows, kbits, ctx->d_status);
+    }
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+
+// the blocks of the divmod pass are one block of the block cache; the lock is held for it
+int cofhe_hip_divx_rows_records(cofhe_hip_ctx *ctx, const void *d_r, const void *d_div, uint64_t n_div, void *d_out, uint64_t n, uint32_t rows,
+                                uint32_t kbits, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (int rc = divx_check(kbits, rows, n_div, n)) return rc;
+    if (n == 0) return COFHE_HIP_OK;
+    if (!d_r || !d_div || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
+    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4, out_bytes = n * rows * exp_bytes;
+    if (overlaps(d_out, out_bytes, d_r, n * exp_bytes) || overlaps(d_out, out_bytes, d_div, n_div * exp_bytes))
+        return fail(COFHE_HIP_EINVAL, "divx_rows: the output overlaps an input");
+    DevBuf prep;                                  // q(r) | q(r) + 1 | (D - m(r), D) per element
+    prep.stream = stream;
+    if (int rc = prep.get(ctx, n * DIVX_PREP_WORDS * 4)) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    {
+        ProfScope ps(ctx, "k_divx_prep", st);
+        hipLaunchKernelGGL(k_divx_prep, dim3((unsigned)((n + PDV_GROUPS - 1) / PDV_GROUPS)), dim3(PDV_THREADS), 0, st, (const uint32_t *)d_r,
+                           (const uint32_t *)d_div, n_div, (uint32_t *)prep.p, n, rows, kbits, ctx->d_status);
+    }
+    HIPCHK(hipGetLastError());
+    const bool vec16 = (((uintptr_t)d_out | (uintptr_t)prep.p) & 15) == 0;
+    const uint64_t total = n * rows * (vec16 ? EXP_REC_WORDS / 4 : EXP_REC_WORDS);
+    const unsigned blocks = (unsigned)std::min<uint64_t>((total + DIVX_ROWS_THREADS - 1) / DIVX_ROWS_THREADS, 64u * NUM_CUS);       // grid-stride beyond that
+    {
+        ProfScope ps(ctx, "k_divx_rows", st);
+        hipLaunchKernelGGL(k_divx_rows, dim3(blocks), dim3(DIVX_ROWS_THREADS), 0, st, (const uint32_t *)prep.p, (uint32_t *)d_out, n, rows,
+                           vec16 ? 1u : 0u);
+    }
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+
+// Needs no workspace plan of its own: the rows are one block of the block cache, and the fresh encryption that follows carves
+// the workspace by the plan "comb" (kind 1) over n rows plaintexts.
+int cofhe_hip_divx_tuples_records(cofhe_hip_ctx *ctx, const void *d_r, const void *d_div, uint64_t n_div, const void *d_rho,
+                                  const uint32_t *h_record, const uint32_t *pk_record, const uint32_t *f_record, void *d_out, uint64_t n,
+                                  uint32_t rows, uint32_t kbits, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (int rc = divx_check(kbits, rows, n_div, n)) return rc;
+    if (int rc = comb_check(1, n * rows, 0, kbits, 0, 0)) return rc;
+    if (n == 0) return COFHE_HIP_OK;
+    if (!d_r || !d_div || !d_rho || !h_record || !pk_record || !f_record || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
+    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4, rows_bytes = n * rows * exp_bytes, out_bytes = n * rows * 2 * REC_WORDS * 4;
+    if (overlaps(d_out, out_bytes, d_r, n * exp_bytes) || overlaps(d_out, out_bytes, d_div, n_div * exp_bytes) ||
+        overlaps(d_out, out_bytes, d_rho, rows_bytes))
+        return fail(COFHE_HIP_EINVAL, "divx_tuples: the output overlaps an input");
+    DevBuf rws;                                   // T_j = q(r) + [m(r) + j >= D], the plaintexts of the tuples
+    rws.stream = stream;
+    if (int rc = rws.get(ctx, rows_bytes)) return rc;
+    if (int rc = cofhe_hip_divx_rows_records(ctx, d_r, d_div, n_div, rws.p, n, rows, kbits, stream)) return rc;
+    return cofhe_hip_encrypt_fresh_records(ctx, rws.p, d_rho, h_record, pk_record, f_record, d_out, n * rows, kbits, stream);
+}
+
+// Needs no workspace plan of its own: the quotients and the remainders of the opened values are one block of the block cache,
+// and the plaintext addend that closes the call carves the workspace by the plan "comb" (kind 3).
+int cofhe_hip_divx_close_records(cofhe_hip_ctx *ctx, const void *d_e, const void *d_div, uint64_t n_div, const void *d_tuples, uint32_t rows,
+                                 const uint32_t *f_record, void *d_out, uint64_t n, uint32_t kbits, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (int rc = divx_check(kbits, rows, n_div, n)) return rc;
+    if (int rc = comb_check(3, n, 0, kbits, 0, 0)) return rc;
+    if (n == 0) return COFHE_HIP_OK;
+    if (!d_e || !d_div || !d_tuples || !f_record || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
+    const size_t ct_bytes = (size_t)2 * REC_WORDS * 4, out_bytes = n * ct_bytes, exp_bytes = (size_t)EXP_REC_WORDS * 4;
+    if (overlaps(d_out, out_bytes, d_tuples, n * rows * ct_bytes) || overlaps(d_out, out_bytes, d_e, n * exp_bytes) ||
+        overlaps(d_out, out_bytes, d_div, n_div * exp_bytes))
+        return fail(COFHE_HIP_EINVAL, "divx_close: the output overlaps an input");
+    DevBuf qm;                                    // q(e): n exponent records, then m(e): n words
+    qm.stream = stream;
+    if (int rc = qm.get(ctx, n * exp_bytes + n * 4)) return rc;
+    uint32_t *d_rem = (uint32_t *)((uint8_t *)qm.p + n * exp_bytes);
+    if (int rc = cofhe_hip_divmod_plain_records(ctx, d_e, d_div, n_div, qm.p, d_rem, n, rows, kbits, stream)) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const bool vec16 = (((uintptr_t)d_tuples | (uintptr_t)d_out) & 15) == 0;
+    const unsigned blocks = (unsigned)((n + DIVX_SELECT_WAVES - 1) / DIVX_SELECT_WAVES);        // n <= 2^24: divx_check
+    {
+        ProfScope ps(ctx, "k_divx_select", st);
+        hipLaunchKernelGGL(k_divx_select, dim3(blocks), dim3(DIVX_SELECT_THREADS), 0, st, (const uint32_t *)d_rem, (const uint32_t *)d_tuples,
+                           (uint32_t *)d_out, n, rows, vec16 ? 1u : 0u, ctx->d_status);
+    }
+    HIPCHK(hipGetLastError());
+    return cofhe_hip_add_plain_records(ctx, d_out, qm.p, nullptr, nullptr, nullptr, f_record, d_out, n, kbits, 0, stream);
+}
+
+// host only: the tuples of opened values of shape S are a tensor of shape S + [rows]
+int cofhe_hip_divx_shape(uint32_t ndim_e, const uint32_t *shape_e, uint32_t ndim_t, const uint32_t *shape_t, uint32_t *rows) {
+    if (!rows || (ndim_e && !shape_e) || (ndim_t && !shape_t)) return fail(COFHE_HIP_EINVAL, "null argument");
+    if (ndim_e > 7 || ndim_t != ndim_e + 1 || (ndim_e && memcmp(shape_t, shape_e, 4 * ndim_e) != 0) || shape_t[ndim_t - 1] == 0 ||
+        shape_t[ndim_t - 1] > DIVX_MAX_ROWS)
+        return fail(COFHE_HIP_ESHAPE, "divx_close: the tuples are a ciphertext tensor of e's shape and a last dimension of 1 <= rows <= 4096");
+    *rows = shape_t[ndim_t - 1];
+    return COFHE_HIP_OK;
 }
 
 // ---- table lookups from one opened value (lut.hip) -------------------------------------------------------------------------

@@ -5,7 +5,8 @@
 // affine.hip the ciphertext difference and the record inverse, matmul_left.hip the record transpose and the plaintext
 // matrix product, conv.hip the convolution's level 0, its patch gather and its filter expansion, conv_ct.hip the plaintext
 // convolution and the patch gather of a plaintext image for ciphertext filters, pow_dot.hip the multi-exponentiation
-// and the Taylor shift of the polynomial evaluation, divide.hip the signed floor division on exponent records, lut.hip the row
+// and the Taylor shift of the polynomial evaluation, divide.hip the signed floor division on exponent records, divide_exact.hip
+// the quotient with its remainder, the rows and the entry selection of the exact division by small divisors, lut.hip the row
 // rotation and the entry selection of the table lookups, spline.hip the rows, the powers and the closing walk of the
 // piecewise-polynomial activations, view.hip the affine view and the index gather that rearrange resident tensors, compare.hip the
 // rows and the closing compositions of the digit comparisons.
@@ -171,6 +172,20 @@ __global__ void k_poly_shift(const uint32_t *__restrict__ coef, const uint32_t *
 // 2^kbits on exponent records, s the centred residue, one limb group per element
 __global__ void k_plain_divfloor(const uint32_t *__restrict__ v, const uint32_t *__restrict__ div, uint64_t n_div, uint32_t *__restrict__ q,
                                  uint64_t n, uint32_t kbits, uint32_t *__restrict__ status);
+
+// exact floor division by small public divisors from one opened value (divide_exact.hip; plain_divmod.hpp): the quotient q[e] and
+// the remainder rem[e] in [0, D) of s(v[e]) by D = div[e mod n_div] <= rows, one limb group per element; the blocks prep[e] = q(r[e])
+// | q(r[e]) + 1 | (D - m(r[e]), D) of the rows, launched the same way; the plaintext rows out[i rows + j] = q(r_i) + [m(r_i) + j >= D_i]
+// for j < D_i and zero records up to rows, stored from those blocks (a grid-stride loop over pieces; vec16: out is 16-byte
+// aligned); and the closing copy out[i] = tuples[i rows + index[i]] of ciphertexts (one wavefront per output ciphertext; an index
+// of rows or more reads entry 0 and sets CF_ST_DIV_CAP; vec16: tuples and out are 16-byte aligned)
+__global__ void k_plain_divmod(const uint32_t *__restrict__ v, const uint32_t *__restrict__ div, uint64_t n_div, uint32_t *__restrict__ q,
+                               uint32_t *__restrict__ rem, uint64_t n, uint32_t rows, uint32_t kbits, uint32_t *__restrict__ status);
+__global__ void k_divx_prep(const uint32_t *__restrict__ r, const uint32_t *__restrict__ div, uint64_t n_div, uint32_t *__restrict__ prep,
+                            uint64_t n, uint32_t rows, uint32_t kbits, uint32_t *__restrict__ status);
+__global__ void k_divx_rows(const uint32_t *__restrict__ prep, uint32_t *__restrict__ out, uint64_t n, uint32_t rows, uint32_t vec16);
+__global__ void k_divx_select(const uint32_t *__restrict__ index, const uint32_t *__restrict__ tuples, uint32_t *__restrict__ out, uint64_t n,
+                              uint32_t rows, uint32_t vec16, uint32_t *__restrict__ status);
 
 // table lookups from one opened value (lut.hip; lut.hpp): the plaintext rows out[i 2^bits + j] = table[(i mod n_tab) 2^bits +
 // ((j + r[i]) mod 2^bits)] on exponent records (a grid-stride loop over 16-byte pieces, 8 lanes per record), and the closing copy

@@ -52,6 +52,11 @@ SIGNATURES = {
     "cofhe_hip_poly_close_records": "i:ppppppquup",
     "cofhe_hip_divfloor_plain_records": "i:pppqpqup",
     "cofhe_hip_div_close_records": "i:pppqpppqup",
+    "cofhe_hip_divmod_plain_records": "i:pppqppquup",
+    "cofhe_hip_divx_rows_records": "i:pppqpquup",
+    "cofhe_hip_divx_tuples_records": "i:pppqpppppquup",
+    "cofhe_hip_divx_close_records": "i:pppqpuppqup",
+    "cofhe_hip_divx_shape": "i:upupp",
     "cofhe_hip_lut_rotate_records": "i:ppqppqup",
     "cofhe_hip_lut_tuples_records": "i:ppqppppppquup",
     "cofhe_hip_lut_select_records": "i:ppppqup",
@@ -292,6 +297,25 @@ class Engine:
         f = _host_record(f_record)
         return self._bytes_out(self.L.cofhe_hip_div_close_tensors_bytes, self.ctx, e, len(e), div, len(div), rq, len(rq),
                                f.ctypes.data, kbits)
+
+    def divx_close_tensors_bytes(self, e: bytes, div: bytes, tuples: bytes, f_record, kbits: int) -> bytes:
+        """e (plaintext tensor of the opened values x - r, shape S, at most 7 dimensions), div (plaintext tensor of one divisor, of
+        e's last dimension or of e's shape) and tuples (ciphertext tensor of the exact-division tuples' entries, shape S + [rows],
+        1 <= rows <= 4096) -> the ciphertext tensor of floor(x / div), shape S; f_record: host uint32[168].  Composed here from
+        unpack_tensor_device (which validates the incoming forms), divx_shape (COFHE_HIP_ESHAPE when the tuples' shape is anything
+        else, as for a divisor tensor of another shape), divx_close_records and pack_tensor_device, exactly as
+        lut_select_tensors_bytes is: the library has no entry point of its own for it."""
+        with _DeviceScope(self) as dev:
+            de, se, ne = dev.load(e, 0)
+            dd, sd, nd = dev.load(div, 0)
+            dt, st, nt = dev.load(tuples, 2)
+            rows = self.divx_shape(se, st)
+            if list(sd) not in ([1], list(se[-1:]), list(se)):
+                raise CofheHipError(-2, "divx_close: the divisors are one element, e's last dimension or e's shape")
+            assert nt == 2 * ne * rows                                # the counts are the shapes' products
+            dout = dev.alloc(max(ne, 1) * 2 * REC_WORDS * 4)
+            self.divx_close_records(de, dd, nd, dt, rows, f_record, dout, ne, kbits)
+            return dev.packed(dout, 2 * ne, 2, se)
 
     def lut_select_tensors_bytes(self, e: bytes, tuples: bytes) -> bytes:
         """e (plaintext tensor of the opened values x - r, shape S, at most 7 dimensions) and tuples (ciphertext tensor of the
@@ -556,6 +580,37 @@ class Engine:
         f_record: host uint32[168]; d_out must not overlap an input"""
         f = _host_record(f_record)
         self._call(self.L.cofhe_hip_div_close_records, d_e, d_div, n_div, d_rq, f.ctypes.data, d_out, n_ciphertexts, kbits, stream)
+
+    def divmod_plain_records(self, d_v, d_div, n_div, d_q, d_rem, n, rows, kbits, stream=0):
+        """q[e] = floor(s(v[e]) / D) mod 2^kbits on exponent records and rem[e] = s(v[e]) - D q(v[e]) in [0, D) as uint32, D =
+        div[e mod n_div]; 1 <= D <= rows <= 4096 and D < 2^(kbits-1), else quotient 0, remainder 0 and bit 4 of device_status"""
+        self._call(self.L.cofhe_hip_divmod_plain_records, d_v, d_div, n_div, d_q, d_rem, n, rows, kbits, stream)
+
+    def divx_rows_records(self, d_r, d_div, n_div, d_out, n, rows, kbits, stream=0):
+        """out[i rows + j] = (q(r[i]) + [m(r[i]) + j >= D]) mod 2^kbits for j < D = div[i mod n_div] and the zero record for D <= j <
+        rows, on exponent records (r: n, div: n_div, out: n rows): the plaintext rows of the exact-division tuples; d_out must not
+        overlap an input"""
+        self._call(self.L.cofhe_hip_divx_rows_records, d_r, d_div, n_div, d_out, n, rows, kbits, stream)
+
+    def divx_tuples_records(self, d_r, d_div, n_div, d_rho, h_record, pk_record, f_record, d_out, n, rows, kbits, stream=0):
+        """the entries of n exact-division tuples: divx_rows_records, then encrypt_fresh_records over the n rows plaintexts with the
+        randomness rho (n rows exponent records, each used once); h_record, pk_record, f_record: host uint32[168]; d_out: n rows
+        ciphertexts"""
+        h, pk, f = _host_record(h_record), _host_record(pk_record), _host_record(f_record)
+        self._call(self.L.cofhe_hip_divx_tuples_records, d_r, d_div, n_div, d_rho, h.ctypes.data, pk.ctypes.data, f.ctypes.data, d_out, n,
+                   rows, kbits, stream)
+
+    def divx_close_records(self, d_e, d_div, n_div, d_tuples, rows, f_record, d_out, n, kbits, stream=0):
+        """the closing step of an exact division: out[i] = (c1, c2 o f^q(e[i])) of tuples[i rows + m(e[i])]; e: n exponent records
+        of the opened values x - r, tuples: n rows ciphertexts; f_record: host uint32[168]; d_out must not overlap an input"""
+        f = _host_record(f_record)
+        self._call(self.L.cofhe_hip_divx_close_records, d_e, d_div, n_div, d_tuples, rows, f.ctypes.data, d_out, n, kbits, stream)
+
+    def divx_shape(self, shape_e, shape_t) -> int:
+        """host only: rows of the tuples (shape_t = shape_e + [rows]) that go with opened values of shape_e; COFHE_HIP_ESHAPE otherwise"""
+        rows = C.c_uint32()
+        _chk(self.L.cofhe_hip_divx_shape(len(shape_e), _u32s(shape_e), len(shape_t), _u32s(shape_t), C.byref(rows)))
+        return rows.value
 
     def lut_rotate_records(self, d_table, n_tab, d_r, d_out, n, bits, stream=0):
         """out[i 2^bits + j] = table[(i mod n_tab) 2^bits + ((j + r[i]) mod 2^bits)] on exponent records (table: n_tab 2^bits, r: n,

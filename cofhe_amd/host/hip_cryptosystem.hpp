@@ -975,6 +975,77 @@ class HIPCryptoSystem {
         check(cofhe_hip_div_close_records(ctx_, de.ptr, dd.ptr, nd, rq.ptr_, f_rec_.data(), out.ptr_, E, k_, nullptr));
         return out;
     }
+    // ---- exact floor division by small public divisors from one opened value (cofhe_hip_divx_*; include/cofhe_hip.h states the
+    // protocol and the caller's contract) ----
+    // check_divisors, and every divisor at most COFHE_HIP_DIVX_MAX_ROWS: one entry of the tuple per remainder.  Returns `rows`,
+    // the largest divisor, which is the length of every element's tuple.
+    uint32_t check_small_divisors(const Tensor<PlainText *> &div, size_t n) const {
+        check_divisors(div, n);
+        uint32_t rows = 1;
+        for (size_t i = 0; i < div.num_elements(); i++) {
+            if (div[i]->nbits() > 13 || mpz_get_ui(div[i]->get()) > COFHE_HIP_DIVX_MAX_ROWS)
+                throw std::invalid_argument("divisors of an exact division: 1 <= D <= 4096; chain factors for more");
+            rows = std::max<uint32_t>(rows, (uint32_t)mpz_get_ui(div[i]->get()));
+        }
+        return rows;
+    }
+    // {q, m}: q[e] = floor(s(v[e]) / D) mod 2^k and m[e] = s(v[e]) - D q(v[e]) in [0, D) for D = div[e mod count], both of v's
+    // shape (cofhe_hip_divmod_plain_records, k_plain_divmod)
+    Vector<Tensor<PlainText *>> divmod_plaintext_tensor(const Tensor<PlainText *> &v, const Tensor<PlainText *> &div) const {
+        const size_t E = v.num_elements(), nd = div.num_elements();
+        const uint32_t rows = check_small_divisors(div, E);
+        Staged dv = stage(pack_exponents(v)), dd = stage(pack_exponents(div)), dq = device_buffer(E * EXPW * 4), dm = device_buffer(E * 4);
+        check(cofhe_hip_divmod_plain_records(ctx_, dv.ptr, dd.ptr, nd, dq.ptr, dm.ptr, E, rows, k_, nullptr));
+        Vector<Tensor<PlainText *>> out;
+        out.push_back(read_plaintexts(dq.ptr, E, EXPW, shape_of(v), false));
+        std::vector<uint32_t> m(E);
+        check(cofhe_hip_download(ctx_, m.data(), dm.ptr, E * 4, nullptr));
+        Tensor<PlainText *> rem(shape_of(v), nullptr);
+        for (size_t i = 0; i < E; i++) rem[i] = new PlainText((unsigned long)m[i]);
+        out.push_back(rem);
+        return out;
+    }
+    // the plaintext rows of the exact-division tuples: res[i, j] = q(r[i]) + [m(r[i]) + j >= D_i] mod 2^k for j < D_i and 0 up to
+    // rows, a tensor [n, rows] for the n masks r (cofhe_hip_divx_rows_records: k_divx_prep, k_divx_rows)
+    Tensor<PlainText *> divx_rows_plaintext_tensor(const Tensor<PlainText *> &r, const Tensor<PlainText *> &div) const {
+        const size_t n = r.num_elements(), nd = div.num_elements();
+        const uint32_t rows = check_small_divisors(div, n);
+        Staged dr = stage(pack_exponents(r)), dd = stage(pack_exponents(div)), drows = device_buffer(n * rows * EXPW * 4);
+        check(cofhe_hip_divx_rows_records(ctx_, dr.ptr, dd.ptr, nd, drows.ptr, n, rows, k_, nullptr));
+        return read_plaintexts(drows.ptr, n * rows, EXPW, {n, (size_t)rows}, false);
+    }
+    // the entries of the exact-division tuples: res[i, j] = a FRESH encryption of row j of element i, a tensor [n, rows]
+    // (cofhe_hip_divx_tuples_records: the rows and the fresh-randomness comb, on the device from end to end).  Every entry has
+    // its own randomness WHATEVER the randomness mode: the rows differ by 0 or 1, so a shared r would give m(r) away.
+    Tensor<CipherText *> divx_tuples_ciphertext_tensor(const PublicKey &pk, const Tensor<PlainText *> &div, const Tensor<PlainText *> &r) const {
+        const size_t n = r.num_elements(), nd = div.num_elements();
+        const uint32_t rows = check_small_divisors(div, n);
+        Staged dr = stage(pack_exponents(r)), dd = stage(pack_exponents(div)), drho = stage(draw_randomness(n * rows));
+        const std::array<uint32_t, REC> pkrec = record_of(pk);
+        DeviceTensor out = alloc(std::vector<size_t>{n, (size_t)rows}, n * rows);
+        check(cofhe_hip_divx_tuples_records(ctx_, dr.ptr, dd.ptr, nd, drho.ptr, h_rec_.data(), pkrec.data(), f_rec_.data(), out.ptr_, n, rows, k_,
+                                            nullptr));
+        return download(std::move(out));
+    }
+    // the closing step of an exact division: res[i] = (c1, c2 o f^(q(e[i]))) of tuples[i, m(e[i])], of e's shape -- an encryption
+    // of floor(s(x[i]) / D) when the tuple is the element's and e[i] = x[i] - r without a wrap (cofhe_hip_divx_close_records: the
+    // division, the copy and the plaintext addend, on the device from end to end).  Re-randomised in PerElement mode.
+    Tensor<CipherText *> divx_close_ciphertext_tensor(const PublicKey &pk, const Tensor<PlainText *> &e, const Tensor<PlainText *> &div,
+                                                      const Tensor<CipherText *> &tuples) const {
+        DeviceTensor out = divx_close_ciphertext_tensor(e, div, upload(tuples));
+        rerandomize_result(pk, out);
+        return download(std::move(out));
+    }
+    // the same on resident tuples; deterministic
+    DeviceTensor divx_close_ciphertext_tensor(const Tensor<PlainText *> &e, const Tensor<PlainText *> &div, const DeviceTensor &tuples) const {
+        const size_t E = e.num_elements(), nd = div.num_elements();
+        const uint32_t rows = check_small_divisors(div, E);
+        if (E == 0 || tuples.n_ != E * rows) throw std::invalid_argument("exact-division tuples: one entry per remainder of the largest divisor");
+        Staged de = stage(pack_exponents(e)), dd = stage(pack_exponents(div));
+        DeviceTensor out = alloc(shape_of(e), E);
+        check(cofhe_hip_divx_close_records(ctx_, de.ptr, dd.ptr, nd, tuples.ptr_, rows, f_rec_.data(), out.ptr_, E, k_, nullptr));
+        return out;
+    }
     // ---- table lookups from one opened value (cofhe_hip_lut_*; include/cofhe_hip.h states the protocol) ----
     // the width b of a public lookup table for n elements: `table` is [2^b] (one table) or [n_tab, 2^b] (element i takes table
     // i mod n_tab, n a multiple of n_tab), 1 <= b <= COFHE_HIP_LUT_MAX_BITS, b <= k

@@ -917,6 +917,178 @@ static void bench_divide(const Args &arg) {
     if (!ok) throw std::runtime_error("division mismatch");
 }
 
+// exact division of a ciphertext tensor by small public divisors from one opened value per element and round
+// (LocalCipherTextMultiplier::divide_exact_ciphertext_tensor_by_plaintext and what is built on it), through the single-key and
+// the 2-of-3 threshold client: a scalar divisor, per-channel divisors (4 channels), Nearest rounding, truncate_exact by 2^8 (one
+// round) and by 2^16 (two rounds), the remainder, the decomposition of 20-bit values into 3 digits of 8 bits and the exact 2 x 2
+// average pool, over n elements with |x| < 2^40 of both signs (a wrap then has probability below 2^-80 per element and round at
+// k = 128); every decrypted element must EQUAL the plaintext integer from GMP on the host; prints client.decrypted_elements() per
+// call, which must equal the element count times the rounds.  runs > 0: the checks through the single-key client only, then the
+// median wall clock of `runs` scalar divisions on one line for tools/bench_ops.py
+static void bench_divide_exact(const Args &arg) {
+    const size_t n = arg(2, 64);
+    const int runs = arg.integer(3, 0);
+    Fixture fx;
+    auto &cs = fx.cs;
+    const auto &sk = fx.sk;
+    const uint32_t k = cs.message_bits();
+    const size_t C = n % 4 == 0 ? 4 : 1;
+    std::vector<Mpz> xs(n), smalls(n);                              // signed values: up to 40 bits, and up to 20 bits
+    auto residue = [&](const Mpz &x) {
+        Mpz m;
+        mpz_fdiv_r_2exp(m.get(), x.get(), k);
+        return m;
+    };
+    auto draw = [&](size_t i, uint32_t bits) {
+        // 0, 1, -1, the ends of the range, then uniform ones of both signs
+        Mpz x = i < 2 ? Mpz((unsigned long)i) : cs.random_plaintext(bits);
+        if (i == 3 || i == 4) {
+            mpz_set_ui(x.get(), 0);
+            mpz_setbit(x.get(), bits);
+            mpz_sub_ui(x.get(), x.get(), 1);
+        }
+        if (i == 2) mpz_set_ui(x.get(), 1);
+        if (i == 2 || i == 4 || (i > 4 && i % 2)) x.neg();
+        return x;
+    };
+    Owned<PT> px = plain_tensor(fx, {n}, [&](size_t i) { return residue(xs[i] = draw(i, 40)); });
+    Owned<PT> psmall = plain_tensor(fx, {n}, [&](size_t i) { return residue(smalls[i] = draw(i, 19)); });
+    Mpz seven(7ul), per_channel[4] = {Mpz(3ul), Mpz(100ul), Mpz(1ul), Mpz(8ul)}, two8(256ul), two16(65536ul);
+    Tensor<PT *> dscalar(1, &seven), dchan(C, nullptr);
+    for (size_t c = 0; c < C; c++) dchan[c] = &per_channel[c];
+    // floor(x / d), or the nearest integer with ties up, as a residue mod 2^k
+    auto quotient = [&](const Mpz &x, const Mpz &d, bool nearest) {
+        Mpz q, h;
+        mpz_fdiv_q_2exp(h.get(), d.get(), 1);
+        if (nearest) mpz_add(h.get(), h.get(), x.get());
+        mpz_fdiv_q(q.get(), nearest ? h.get() : x.get(), d.get());
+        return residue(q);
+    };
+    bool ok = true;
+    for_both_clients(fx, [&](Client &client, Multiplier &mul, const std::string &who, bool threshold) {
+        if (threshold && runs > 0) return;                          // the timed leg checks through the single-key client only
+        Owned<CT> cx = cs.encrypt_tensor(client.network_public_key(), px);
+        const char *names[6] = {"scalar divisor 7", "per-channel divisors", "nearest by 7", "truncate_exact by 2^8", "truncate_exact by 2^16",
+                                "remainder by 7"};
+        for (int what = 0; what < 6; what++) {
+            const Tensor<PT *> &div = what == 1 ? dchan : dscalar;
+            const size_t rounds = what == 4 ? 2 : 1, before = client.decrypted_elements();
+            cs.synchronize();
+            auto [ms, res] = timed(cs, [&]() -> Owned<CT> {
+                switch (what) {
+                case 2: return mul.divide_exact_ciphertext_tensor_by_plaintext(cx, div, Multiplier::Rounding::Nearest);
+                case 3: return mul.truncate_exact_ciphertext_tensor(cx, 8);
+                case 4: return mul.truncate_exact_ciphertext_tensor(cx, 16);
+                case 5: return mul.remainder_ciphertext_tensor(cx, div);
+                default: return mul.divide_exact_ciphertext_tensor_by_plaintext(cx, div);
+                }
+            });
+            const size_t opened = client.decrypted_elements() - before;
+            Owned<PT> dec = cs.decrypt_tensor(sk, res);
+            bool pass = opened == n * rounds;
+            for (size_t i = 0; i < n; i++) {
+                Mpz want;
+                if (what == 5)
+                    mpz_fdiv_r(want.get(), xs[i].get(), seven.get());
+                else
+                    want = quotient(xs[i], what == 3 ? two8 : what == 4 ? two16 : *div[i % div.num_elements()], what == 2);
+                if (!(*dec->at(i) == want)) pass = false;
+            }
+            if (!threshold && what == 0) write_ciphertexts(fx, "local_bench_divide_exact.bin", res);
+            std::cout << "  " << who << ": " << names[what] << " over " << n << " elements, opened_values " << opened << ", " << ms
+                      << " ms (host wall clock, tuple generation and the decryption included): " << (pass ? "ok" : "FAILED") << std::endl;
+            ok = ok && pass;
+        }
+        // 3 digits of 8 bits of 20-bit values: two digits in [0, 256) and the signed top part, recombined
+        {
+            Owned<CT> cs20 = cs.encrypt_tensor(client.network_public_key(), psmall);
+            const size_t before = client.decrypted_elements();
+            auto digits = mul.decompose_ciphertext_tensor(cs20, 8, 3);
+            const size_t opened = client.decrypted_elements() - before;
+            bool pass = opened == 2 * n && digits.size() == 3;
+            std::vector<Owned<PT>> dec;
+            for (auto &d : digits) {
+                Owned<CT> own(d);
+                dec.emplace_back(cs.decrypt_tensor(sk, own));
+            }
+            for (size_t i = 0; pass && i < n; i++) {
+                Mpz d0, d1, top, sum;
+                mpz_fdiv_r_2exp(d0.get(), smalls[i].get(), 8);
+                mpz_fdiv_q_2exp(top.get(), smalls[i].get(), 8);
+                mpz_fdiv_r_2exp(d1.get(), top.get(), 8);
+                mpz_fdiv_q_2exp(top.get(), top.get(), 8);
+                if (!(*dec[0]->at(i) == d0) || !(*dec[1]->at(i) == d1) || !(*dec[2]->at(i) == residue(top))) pass = false;
+                mpz_mul_2exp(sum.get(), top.get(), 8);
+                mpz_add(sum.get(), sum.get(), d1.get());
+                mpz_mul_2exp(sum.get(), sum.get(), 8);
+                mpz_add(sum.get(), sum.get(), d0.get());
+                if (!(sum == smalls[i])) pass = false;
+            }
+            std::cout << "  " << who << ": decompose into 3 digits of 8 bits over " << n << " elements, opened_values " << opened << ": "
+                      << (pass ? "ok" : "FAILED") << std::endl;
+            ok = ok && pass;
+        }
+        if (threshold) return;
+        // the parts on their own: one 0-D element, the plaintext quotients and remainders, the rows, the refusals of the divisors 0
+        // and 4097, and the exact mean of 2 x 2 windows
+        Owned<CT> q0 = mul.divide_exact_ciphertext_tensor_by_plaintext(Tensor<CT *>(cx[2 % n]), Tensor<PT *>(&seven));
+        auto dq0 = cs.decrypt(sk, *q0->get_value());
+        bool parts = q0->is_zero_degree() && dq0 == quotient(xs[2 % n], seven, false);
+        auto qm = cs.divmod_plaintext_tensor(px, dscalar);
+        Owned<PT> pq(qm[0]), pm(qm[1]);
+        Owned<PT> rows = cs.divx_rows_plaintext_tensor(px, dscalar);
+        for (size_t i = 0; i < n; i++) {
+            Mpz m;
+            mpz_fdiv_r(m.get(), xs[i].get(), seven.get());
+            if (!(*pq->at(i) == quotient(xs[i], seven, false)) || !(*pm->at(i) == m)) parts = false;
+            for (unsigned long j = 0; j < 7; j++) {
+                Mpz t = quotient(xs[i], seven, false);
+                if (mpz_get_ui(m.get()) + j >= 7) {
+                    mpz_add_ui(t.get(), t.get(), 1);
+                    t = residue(t);
+                }
+                if (!(*rows->at(i * 7 + j) == t)) parts = false;
+            }
+        }
+        Mpz zero(0ul), big(4097ul);
+        for (Mpz *bad : {&zero, &big}) {
+            bool refused = false;
+            try {
+                (void)mul.divide_exact_ciphertext_tensor_by_plaintext(cx, Tensor<PT *>(1, bad));
+            } catch (const std::invalid_argument &) {
+                refused = true;
+            }
+            parts = parts && refused;
+        }
+        if (n % 4 == 0) {
+            Tensor<CT *> img = cx;
+            img.reshape({1, 2, 2, n / 4});
+            Owned<CT> avg = mul.avg_pool2d_exact_ciphertext_tensor(img, {2, 2}, {2, 2});
+            Owned<PT> davg = cs.decrypt_tensor(sk, avg);
+            const Mpz four(4ul);
+            for (size_t c = 0; c < n / 4; c++) {
+                Mpz s;
+                for (size_t p = 0; p < 4; p++) mpz_add(s.get(), s.get(), xs[p * (n / 4) + c].get());
+                if (!(*davg[c] == quotient(s, four, false))) parts = false;
+            }
+        }
+        std::cout << "  0-D division, divmod_plaintext_tensor, divx_rows_plaintext_tensor, the refusals of the divisors 0 and 4097, avg_pool2d_exact: "
+                  << (parts ? "ok" : "FAILED") << std::endl;
+        ok = ok && parts;
+    });
+    write_absdelta(fx);
+    if (runs > 0) {
+        Client client(cs, sk);
+        Multiplier mul(client);
+        Owned<CT> cx = cs.encrypt_tensor(client.network_public_key(), px);
+        const auto ms = median_runs(cs, runs, [&]() { return mul.divide_exact_ciphertext_tensor_by_plaintext(cx, dscalar); });
+        std::cout << "divide_exact_json: {\"E\": " << n << ", \"runs\": " << runs << ", "
+                  << MsJson{"divide_exact_ms", "divide_exact_ms_min_max", ms} << "}" << std::endl;
+    }
+    std::cout << "  agree: " << (ok ? "yes" : "NO") << std::endl;
+    if (!ok) throw std::runtime_error("exact division mismatch");
+}
+
 // table lookups on a ciphertext tensor from one opened value per element (LocalCipherTextMultiplier::lookup_ciphertext_tensor),
 // through the single-key and the 2-of-3 threshold client: a random 8-bit table, relu and max at 8 bits over n elements of the
 // whole signed 8-bit range, and a 2 x 2 max pool of them (n a multiple of 4); every decrypted element must EQUAL the plaintext
@@ -1946,6 +2118,7 @@ static const struct Mode {
     {"conv2d_ciphertext", "[B=1 H=5 W=4 C=2 kh=3 kw=2 Co=2 [sh=1 sw=1 ph=0 pw=0 dh=1 dw=1 [t=0 parties=3 [runs=0]]]]", bench_conv2d_ciphertext},
     {"poly_activation", "[elements=64 [runs=0]]", bench_poly_activation},
     {"divide", "[elements=64 [runs=0]]", bench_divide},
+    {"divide_exact", "[elements=64 [runs=0]]", bench_divide_exact},
     {"lookup", "[elements=64 [runs=0]]", bench_lookup},
     {"compare", "[elements=256 [bits=32 [digit_bits=0 [runs=0]]]]", bench_compare},
     {"spline", "[elements=256 [runs=0 [bits=5 [shift=11 [degree=2]]]]]", bench_spline},

@@ -38,6 +38,12 @@
 // per element:  e = Dec(x - r);  [y] = [r_q] o f^(floor(s(e) / D)),  s the centred residue mod 2^k -- one opened value, no
 // encryption, no ladder; y is floor(x / D) or one less unless s(r) + s(e) wraps (probability |x| / 2^k per element).
 //
+// Exact division and remainders by small divisors (divide_exact_ciphertext_tensor_by_plaintext, truncate_exact_ciphertext_tensor,
+// remainder_ciphertext_tensor, decompose_ciphertext_tensor, avg_pool2d_exact_ciphertext_tensor).  With an exact-division tuple
+// ([r], [T_0], .., [T_{D-1}]), T_j = floor(s(r) / D) + [s(r) mod D + j >= D], per element:  e = Dec(x - r);  [y] = [T_{s(e) mod D}]
+// o f^(floor(s(e) / D)) -- one opened value, one round, y = floor(x / D) EXACTLY unless s(r) + s(e) wraps; D <= 4096 per round,
+// D fresh encryptions per element.  Every [T_j] carries its own randomness whatever the randomness mode.
+//
 // Table lookups (lookup_ciphertext_tensor, relu_ciphertext_tensor, max_ciphertext_tensors, max_pool2d_ciphertext_tensor; the
 // reference has no comparison).  With a lookup tuple ([r], [T_0], .., [T_{2^b - 1}]), T_j = g[(j + r) mod 2^b], per element:
 // e = Dec(x - r);  [y] = [T_{e mod 2^b}] -- one opened value, one round, y = g[x mod 2^b] exactly for ANY public table g of 2^b
@@ -185,6 +191,23 @@ class LocalSMPCClient {
             delete pr[i];
             delete prq[i];
         }
+        return t;
+    }
+
+    // exact-division tuples for n elements and the small public divisors div (element i takes divisor i mod count, every one at
+    // most 4096): {[r] (n elements), [T] (n rows elements, [n, rows], rows the largest divisor)} with r uniform in Z/2^k per
+    // element and T[i, j] = floor(s(r_i) / D_i) + [s(r_i) mod D_i + j >= D_i], used once; the caller owns the elements.  [r] and
+    // every [T_j] are encrypted with their OWN randomness whatever the randomness mode: the entries differ by 0 or 1, so entries
+    // that shared c1 would give s(r) mod D, and with the opened value x mod D, away.  Like the triplets, the tuples of the
+    // networked system would come from a protocol between the nodes.
+    Vector<Tensor<CipherText *>> get_exact_division_tuples(size_t n, const Tensor<PlainText *> &div) {
+        (void)cs_.check_small_divisors(div, n);                  // refuse before anything is drawn
+        Tensor<PlainText *> pr(n, nullptr);
+        for (size_t i = 0; i < n; i++) pr[i] = new PlainText(cs_.random_plaintext(cs_.message_bits()));
+        Vector<Tensor<CipherText *>> t;
+        t.push_back(cs_.encrypt_tensor_per_element(pk_, pr));
+        t.push_back(cs_.divx_tuples_ciphertext_tensor(pk_, div, pr));
+        for (size_t i = 0; i < n; i++) delete pr[i];
         return t;
     }
 
@@ -416,6 +439,120 @@ class LocalCipherTextMultiplier {
         Tensor<CipherText *> flat = sums;
         flat.flatten();
         for (size_t i = 0; i < flat.num_elements(); i++) delete flat[i];
+        return res;
+    }
+
+    // floor(x / D) EXACTLY, element-wise for small public divisors D, 1 <= D <= 4096 and D < 2^(k-1), x read as its centred
+    // residue: with an exact-division tuple per element, ONE opened value e = Dec(x - r) and one round; the closing step copies
+    // the entry s(e) mod D of the element's tuple and adds the plaintext floor(s(e) / D).  Wrong only where s(r) + s(e) wraps,
+    // which has probability |x| / 2^k per element (the caller keeps |x| <= 2^(k-1-sigma)), as for the inexact division.  Nearest
+    // adds the plaintext floor(D / 2) first: the nearest integer to x / D, ties up.  div holds one divisor, or one per channel
+    // of a channels-last tensor (its count divides x's), or one per element; a tuple is max(D) ciphertexts per element.  0-D
+    // and 1-D tensors; higher ranks are flattened and the result reshaped.
+    enum class Rounding { Floor, Nearest };
+    Tensor<CipherText *> divide_exact_ciphertext_tensor_by_plaintext(const Tensor<CipherText *> &x, const Tensor<PlainText *> &div,
+                                                                     Rounding rounding = Rounding::Floor) {
+        auto &cs = client_m.crypto_system();
+        const auto &pk = client_m.network_public_key();
+        Tensor<PlainText *> d = div.is_zero_degree() ? Tensor<PlainText *>(1, div.get_value()) : div;
+        d.flatten();
+        const size_t n = x.num_elements();
+        (void)cs.check_small_divisors(d, n);
+        auto close = [&](const Tensor<PlainText *> &e, const Vector<Tensor<CipherText *>> &tuples) {
+            return cs.divx_close_ciphertext_tensor(pk, e, d, tuples[1]);
+        };
+        if (rounding == Rounding::Floor) return open_and_close(x, client_m.get_exact_division_tuples(n, d), close);
+        // x + floor(D / 2) element-wise, then the floor
+        std::vector<PlainText> halves(d.num_elements());
+        for (size_t i = 0; i < d.num_elements(); i++) mpz_fdiv_q_2exp(halves[i].get(), d[i]->get(), 1);
+        Tensor<PlainText *> addend(n, nullptr);
+        for (size_t i = 0; i < n; i++) addend[i] = &halves[i % halves.size()];
+        Tensor<CipherText *> flat = x.is_zero_degree() ? Tensor<CipherText *>(1, x.get_value()) : x;
+        flat.flatten();
+        auto shifted = cs.add_plaintext_tensor(pk, flat, addend);
+        auto res = open_and_close(shifted, client_m.get_exact_division_tuples(n, d), close);
+        for (size_t i = 0; i < n; i++) delete shifted[i];
+        if (x.is_zero_degree()) return Tensor<CipherText *>(res.at(0));
+        res.reshape(x.shape());
+        return res;
+    }
+    // floor(x / 2^t) EXACTLY: the rescale after a product of two fixed-point values.  t <= 12 takes one round; a larger t takes
+    // ceil(t / 12) rounds of near-equal shifts (t = 16: 8 + 8, 512 tuple entries per element, not 12 + 4 with 4112), which is
+    // exact because nested floors by positive divisors compose: floor(floor(x / a) / b) = floor(x / (a b)).  1 <= t <= k - 2.
+    Tensor<CipherText *> truncate_exact_ciphertext_tensor(const Tensor<CipherText *> &x, uint32_t t) {
+        if (t == 0 || t + 2 > client_m.crypto_system().message_bits()) throw std::invalid_argument("truncate_exact_ciphertext_tensor: 1 <= t <= k - 2");
+        const uint32_t rounds = (t + 11) / 12;
+        Tensor<CipherText *> cur = x;
+        for (uint32_t i = 0; i < rounds; i++) {
+            const uint32_t shift = t / rounds + (i < t % rounds ? 1 : 0);
+            PlainText D;
+            mpz_setbit(D.get(), shift);
+            auto next = divide_exact_ciphertext_tensor_by_plaintext(cur, Tensor<PlainText *>(1, &D));
+            if (i > 0) free_elements(cur);
+            cur = next;
+        }
+        return cur;
+    }
+    // x - D floor(x / D) element-wise, in [0, D): one exact division, then a scaling by D and a difference
+    Tensor<CipherText *> remainder_ciphertext_tensor(const Tensor<CipherText *> &x, const Tensor<PlainText *> &div) {
+        auto &cs = client_m.crypto_system();
+        const auto &pk = client_m.network_public_key();
+        Tensor<PlainText *> d = div.is_zero_degree() ? Tensor<PlainText *>(1, div.get_value()) : div;
+        d.flatten();
+        const size_t n = x.num_elements();
+        auto y = divide_exact_ciphertext_tensor_by_plaintext(x, d);
+        Tensor<CipherText *> flat = x.is_zero_degree() ? Tensor<CipherText *>(1, x.get_value()) : x, yf = y.is_zero_degree() ? Tensor<CipherText *>(1, y.get_value()) : y;
+        flat.flatten();
+        yf.flatten();
+        Tensor<PlainText *> scale(n, nullptr);
+        for (size_t i = 0; i < n; i++) scale[i] = d[i % d.num_elements()];
+        auto dy = cs.scal_ciphertext_tensors(pk, scale, yf);
+        auto res = cs.sub_ciphertext_tensors(pk, flat, dy);
+        for (size_t i = 0; i < n; i++) {
+            delete yf[i];
+            delete dy[i];
+        }
+        if (x.is_zero_degree()) return Tensor<CipherText *>(res.at(0));
+        res.reshape(x.shape());
+        return res;
+    }
+    // x = sum_i digit_i 2^(digit_bits i): n_digits - 1 digits in [0, 2^digit_bits) and the signed top part, least significant
+    // first, each of x's shape; 1 <= digit_bits <= 12, n_digits >= 2.  One exact division by 2^digit_bits per digit below the
+    // top: the quotient is carried on and the digit is what the division leaves, cur - 2^digit_bits quotient.
+    Vector<Tensor<CipherText *>> decompose_ciphertext_tensor(const Tensor<CipherText *> &x, uint32_t digit_bits, uint32_t n_digits) {
+        if (digit_bits == 0 || digit_bits > 12 || n_digits < 2) throw std::invalid_argument("decompose_ciphertext_tensor: 1 <= digit_bits <= 12, n_digits >= 2");
+        auto &cs = client_m.crypto_system();
+        const auto &pk = client_m.network_public_key();
+        const size_t n = x.num_elements();
+        PlainText D;
+        mpz_setbit(D.get(), digit_bits);
+        Tensor<PlainText *> scale(n, &D);
+        Tensor<CipherText *> cur = x.is_zero_degree() ? Tensor<CipherText *>(1, x.get_value()) : x;
+        cur.flatten();
+        Vector<Tensor<CipherText *>> out;
+        for (uint32_t i = 0; i + 1 < n_digits; i++) {
+            auto q = divide_exact_ciphertext_tensor_by_plaintext(cur, Tensor<PlainText *>(1, &D));
+            auto dq = cs.scal_ciphertext_tensors(pk, scale, q);
+            auto digit = cs.sub_ciphertext_tensors(pk, cur, dq);
+            free_elements(dq);
+            if (i > 0) free_elements(cur);
+            if (!x.is_zero_degree()) digit.reshape(x.shape());
+            out.push_back(digit);
+            cur = q;
+        }
+        if (!x.is_zero_degree()) cur.reshape(x.shape());
+        out.push_back(cur);
+        return out;
+    }
+    // average pooling, channels last, EXACT: sum_pool2d_ciphertext_tensor over kernel[0] x kernel[1] windows, then the exact
+    // division by kernel[0] kernel[1] (at most 4096): the floor of the mean.  Padding counts as zeros in the mean.
+    Tensor<CipherText *> avg_pool2d_exact_ciphertext_tensor(const Tensor<CipherText *> &x, const std::array<size_t, 2> &kernel,
+                                                            const std::array<size_t, 2> &stride, const std::array<size_t, 2> &pad = {0, 0}) {
+        auto &cs = client_m.crypto_system();
+        auto sums = cs.sum_pool2d_ciphertext_tensor(client_m.network_public_key(), x, kernel, stride, pad);
+        PlainText D((unsigned long)(kernel[0] * kernel[1]));
+        auto res = divide_exact_ciphertext_tensor_by_plaintext(sums, Tensor<PlainText *>(1, &D));
+        free_elements(sums);
         return res;
     }
 
@@ -679,6 +816,12 @@ class LocalCipherTextMultiplier {
     }
 
   private:
+    // the elements of a tensor this class made, whatever its shape
+    static void free_elements(const Tensor<CipherText *> &t) {
+        Tensor<CipherText *> flat = t;
+        flat.flatten();
+        for (size_t i = 0; i < flat.num_elements(); i++) delete flat[i];
+    }
     // The protocol of one opened value, behind the polynomial, the division and the lookup: e = Dec(x - material[0]) element-wise,
     // then close(e, material) makes the result, which takes x's shape.  material is what the client handed out for x's elements,
     // the mask first; it is used once, so every element of it is freed here, with the difference and the opened values.  A 0-D x

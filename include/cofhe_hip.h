@@ -365,6 +365,58 @@ int cofhe_hip_divfloor_plain_records(cofhe_hip_ctx *ctx, const void *d_v, const 
  * (COFHE_HIP_EINVAL, as for the refusals above). */
 int cofhe_hip_div_close_records(cofhe_hip_ctx *ctx, const void *d_e, const void *d_div, uint64_t n_div, const void *d_rq,
                                 const uint32_t *f_record, void *d_out, uint64_t n_ct, uint32_t kbits, void *stream);
+/* ---- exact floor division and remainders by small public divisors from one opened value (cofhe_amd/csrc/divide_exact.hip) ----
+ * The division pair above loses the carry [r mod D + e mod D >= D] of the two remainders: about every second result is one less
+ * than the floor.  For a SMALL divisor, 1 <= D <= COFHE_HIP_DIVX_MAX_ROWS and D < 2^(k-1), the party that makes the tuple
+ * tabulates that carry over the D remainders the opened value can have.  With q(v) = floor(s(v) / D) and m(v) = s(v) - D q(v) in
+ * [0, D), an EXACT-DIVISION TUPLE of an element is ([r], [T_0], .., [T_{D-1}]) with r uniform in Z/2^k and
+ * T_j = (q(r) + [m(r) + j >= D]) mod 2^k, used once.  With the ONE opened value e = Dec([x] - [r]) -- uniform whatever x is --
+ *   [y] = [T_{m(e)}] o f^(q(e)) = (c1, c2 o f^(q(e))) of [T_{m(e)}]:
+ * a copy and a plaintext addend.  If s(x) = s(r) + s(e) over the integers, s(y) = floor(s(x) / D) EXACTLY and the remainder
+ * s(x) - D s(y) is (m(r) + m(e)) mod D.  Otherwise the sum wrapped, with the probability and under THE CALLER'S CONTRACT of the
+ * division pair: |x| <= 2^(k-1-sigma) for at most 2^(-sigma-1) per element.  EVERY [T_j] MUST CARRY ITS OWN RANDOMNESS, as the
+ * entries of a lookup tuple: the rows differ by 0 or 1, so under one shared randomness the quotients of the c2 reveal m(r) and,
+ * with e, x mod D; the tuples are made by the fresh-randomness comb (cofhe_hip_divx_tuples_records) and by nothing else.  A tuple
+ * of `rows` entries, rows the largest divisor of the call, is rows * 1344 bytes per element: D fresh encryptions against the 2
+ * of the inexact pair.  In all entry points element e reads divisor e mod n_div, and an INVALID divisor is one that
+ * cofhe_hip_divfloor_plain_records calls invalid or one above `rows`: it gives zero results and sets the division bit (4) of
+ * cofhe_hip_device_status.  COFHE_HIP_EINVAL, nothing written, checked before a pointer is looked at: kbits = 0 or kbits >
+ * COFHE_HIP_DIV_MAX_KBITS; rows = 0 or rows > COFHE_HIP_DIVX_MAX_ROWS; n_div = 0; n no multiple of n_div; then an output
+ * overlapping an input.  n = 0 does nothing. */
+#define COFHE_HIP_DIVX_MAX_ROWS 4096
+/* q[e] = floor(s(v[e]) / D) mod 2^kbits as an exponent record and rem[e] = s(v[e]) - D q(v[e]) in [0, D) as a uint32_t, D =
+ * div[e mod n_div], e < n: cofhe_hip_divfloor_plain_records that keeps the remainder, one 8-lane limb group per element.  An
+ * invalid divisor gives quotient 0 and remainder 0.  One launch ("k_plain_divmod" under "profile_kernels"), purely stream-ordered:
+ * no workspace, no read-back, no lock. */
+int cofhe_hip_divmod_plain_records(cofhe_hip_ctx *ctx, const void *d_v, const void *d_div, uint64_t n_div, void *d_q, void *d_rem, uint64_t n,
+                                   uint32_t rows, uint32_t kbits, void *stream);
+/* the plaintext rows: out[i rows + j] = T_j of element i for j < D_i = div[i mod n_div] and the zero record for D_i <= j < rows,
+ * i < n, exponent records in [0, 2^kbits) with sign word 0, every word written.  d_r: n records of the masks; d_out: n rows
+ * records.  Two launches: "k_divx_prep", one limb group per element, leaves q(r), q(r) + 1 and the threshold D - m(r) in a block of
+ * the block cache (it goes back behind the work queued on `stream`), and "k_divx_rows" stores the rows from it, 16-byte pieces
+ * when d_out allows them and 4-byte ones otherwise.  An invalid divisor gives `rows` zero records.  No read-back. */
+int cofhe_hip_divx_rows_records(cofhe_hip_ctx *ctx, const void *d_r, const void *d_div, uint64_t n_div, void *d_out, uint64_t n, uint32_t rows,
+                                uint32_t kbits, void *stream);
+/* the tuples' entries: out[i rows + j] = (h^rho, pk^rho o f^(T_j)) with rho = rho[i rows + j] and T the rows of
+ * cofhe_hip_divx_rows_records, which it runs into a block of the block cache; then cofhe_hip_encrypt_fresh_records over the n rows
+ * plaintexts, whose bytes these are (the plan "comb", kind 1, and its one read-back of the longest exponent).  d_rho: n rows
+ * exponent records of the caller's randomness, each used once; h_record, pk_record, f_record: HOST records.  Also
+ * COFHE_HIP_EINVAL: kbits out of the comb's range. */
+int cofhe_hip_divx_tuples_records(cofhe_hip_ctx *ctx, const void *d_r, const void *d_div, uint64_t n_div, const void *d_rho,
+                                  const uint32_t *h_record, const uint32_t *pk_record, const uint32_t *f_record, void *d_out, uint64_t n,
+                                  uint32_t rows, uint32_t kbits, void *stream);
+/* The closing step: out[i] = (c1, c2 o f^(q(e[i]))) of tuples[i rows + m(e[i])], i < n, an encryption of floor(s(x[i]) / D_i) when
+ * the tuple is the element's and e[i] = x[i] - r (see above).  d_e: n exponent records; d_div: n_div; d_tuples: n rows
+ * ciphertexts; f_record: HOST record of f.  Three steps on `stream`: cofhe_hip_divmod_plain_records into a block of the block
+ * cache, the copy of the named entries ("k_divx_select" under "profile_kernels": one wavefront per ciphertext, the entry index
+ * in 64 bits, never beyond the element's tuple), and the plaintext addend of cofhe_hip_add_plain_records (mode 0, no randomness)
+ * against the cached table of f.  Uses the block cache and, through the addend, the workspace plan "comb" (kind 3).  No
+ * read-back.  It has no serialised twin: Engine.divx_close_tensors_bytes composes one as Engine.lut_select_tensors_bytes does. */
+int cofhe_hip_divx_close_records(cofhe_hip_ctx *ctx, const void *d_e, const void *d_div, uint64_t n_div, const void *d_tuples, uint32_t rows,
+                                 const uint32_t *f_record, void *d_out, uint64_t n, uint32_t kbits, void *stream);
+/* host only, no GPU: *rows of the tuples that go with opened values of shape shape_e[ndim_e], ndim_e <= 7.  COFHE_HIP_ESHAPE unless
+ * shape_t is shape_e with one more, last dimension of `rows` entries, 1 <= rows <= COFHE_HIP_DIVX_MAX_ROWS. */
+int cofhe_hip_divx_shape(uint32_t ndim_e, const uint32_t *shape_e, uint32_t ndim_t, const uint32_t *shape_t, uint32_t *rows);
 /* ---- table lookups from one opened value (cofhe_amd/csrc/lut.hip) ----
  * For values known to lie in a b-bit range, 1 <= b <= COFHE_HIP_LUT_MAX_BITS, b <= k, ANY public function of them given as a table
  * g of 2^b plaintexts is evaluated exactly, in one round, with no failure probability.  A LOOKUP TUPLE of an element is
