@@ -1,5 +1,5 @@
-// abi.hip -- the C ABI of include/cofhe_hip.h, in this order: the context, the block cache, the launch helpers (spans, the
-// two-build launch, flag words, the table-cache lookup), the workspace plans, the launchers (one launch site per kernel and
+// abi.hip -- the C ABI of include/cofhe_hip.h, in this order: the context, the block cache, the entry helpers (the overlap
+// test, the piece grid, spans, the checked launch and its two-build form, flag words, the table-cache lookup), the workspace plans, the launchers (one launch site per kernel and
 // route; product_tree is the pairwise tree of them all) and the host-side tensor formats.  The kernels are declared in
 // kernels.hpp and defined in cofhe_hip.hip, wide.hip, comb.hip, affine.hip, matmul_left.hip, conv.hip, conv_ct.hip, pow_dot.hip,
 // divide.hip, divide_exact.hip, lut.hip, spline.hip, view.hip and compare.hip; this file holds no device code of its own.  conv.hip holds the three kernels of the
@@ -354,6 +354,11 @@ int cofhe_hip_device_status(cofhe_hip_ctx *ctx, uint32_t *word, int clear, void 
     return COFHE_HIP_OK;
 }
 
+namespace {
+// the checked launch of the launch helpers below, which this one entry precedes
+extern "C++" template <typename... P, typename... A>
+int launch(cofhe_hip_ctx *ctx, const char *span, void (*k)(P...), dim3 grid, dim3 block, hipStream_t st, A... args);
+}  // namespace
 int cofhe_hip_validate_records(cofhe_hip_ctx *ctx, const void *d_records, uint64_t n_records, int *all_valid, void *stream) {
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     if (!all_valid) return fail(COFHE_HIP_EINVAL, "null argument");
@@ -368,9 +373,9 @@ int cofhe_hip_validate_records(cofhe_hip_ctx *ctx, const void *d_records, uint64
     }
     uint32_t *d_err = ctx->d_status + 1;              // second word of the status area: validation verdict
     HIPCHK(hipMemsetAsync(d_err, 0, 4, (hipStream_t)stream));
-    hipLaunchKernelGGL(k_validate_forms, dim3(blocks), dim3(WG_BLOCK), 0, (hipStream_t)stream, (const uint32_t *)d_records, n_records,
-                       (const uint32_t *)ctx->d_absdelta, d_err);
-    HIPCHK(hipGetLastError());
+    if (int rc = launch(ctx, nullptr, k_validate_forms, blocks, WG_BLOCK, (hipStream_t)stream, (const uint32_t *)d_records, n_records,
+                        (const uint32_t *)ctx->d_absdelta, d_err))
+        return rc;
     uint32_t e = 0;
     HIPCHK(hipMemcpyAsync(&e, d_err, 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
@@ -379,10 +384,62 @@ int cofhe_hip_validate_records(cofhe_hip_ctx *ctx, const void *d_records, uint64
 }
 
 namespace {
+constexpr size_t EXP_BYTES = (size_t)EXP_REC_WORDS * 4;       // one exponent record
+constexpr size_t CT_BYTES = (size_t)2 * REC_WORDS * 4;        // one ciphertext: two form records
+// The one range of k, 1 <= k <= 639, whichever bound a kernel names: 2 k + 1 bits fit one 1280-bit plane, the limbs of the
+// plaintext kernels (PMM_MAX_LIMBS) and of the division (PDV_MAX_KBITS) hold k bits, and so does an exponent record
+static_assert(PDV_MAX_KBITS == 32u * PMM_MAX_LIMBS - 1u && 2 * PDV_MAX_KBITS + 1 <= (uint32_t)PLIMBS * 32 &&
+                  2 * (PDV_MAX_KBITS + 1) + 1 > (uint32_t)PLIMBS * 32 && PDV_MAX_KBITS <= EXP_MAG_WORDS * 32 - 1,
+              "the bounds of k coincide");
+constexpr bool k_in_range(uint64_t kbits) { return kbits >= 1 && kbits <= PDV_MAX_KBITS; }
+
+// what an entry does once it has checked its arguments: its device made current, its stream as HIP's type
+int on_device(cofhe_hip_ctx *ctx, void *stream, hipStream_t *st) {
+    HIPCHK(hipSetDevice(ctx->device));
+    *st = (hipStream_t)stream;
+    return COFHE_HIP_OK;
+}
+// The overlap test of the entries: whether the output `out` is clear of every span of `others`.  An empty span overlaps nothing.
+struct Span {
+    const void *p;
+    size_t bytes;
+};
+bool clear_of(Span out, std::initializer_list<Span> others) {
+    const uintptr_t x = (uintptr_t)out.p;
+    for (const Span &o : others) {
+        const uintptr_t y = (uintptr_t)o.p;
+        if (out.bytes && o.bytes && x < y + o.bytes && y < x + out.bytes) return false;
+    }
+    return true;
+}
+// whether every one of the pointers is 16-byte aligned (a caller's pointer is only known to be 4-byte aligned)
+bool aligned16(std::initializer_list<const void *> ptrs) {
+    uintptr_t all = 0;
+    for (const void *p : ptrs) all |= (uintptr_t)p;
+    return (all & 15) == 0;
+}
+// The grid of the kernels that move `records` records of `words` words in pieces: 16-byte pieces when the record length and
+// the pointers of `ptrs` allow them, words otherwise; one thread per piece in workgroups of `threads`, 64 workgroups per CU at
+// the most (the kernels stride beyond that)
+struct PieceGrid {
+    bool vec16;
+    uint64_t total;              // pieces
+    unsigned blocks;
+    uint32_t flag() const { return vec16 ? 1u : 0u; }
+};
+PieceGrid piece_grid(uint64_t records, uint32_t words, unsigned threads, std::initializer_list<const void *> ptrs) {
+    PieceGrid g;
+    g.vec16 = words % 4 == 0 && aligned16(ptrs);
+    g.total = records * (g.vec16 ? words / 4 : words);
+    g.blocks = (unsigned)std::min<uint64_t>((g.total + threads - 1) / threads, 64u * NUM_CUS);
+    return g;
+}
+
 struct DevBuf {                  // from the context's block cache
     cofhe_hip_ctx *ctx = nullptr;
     void *p = nullptr;
-    void *stream = nullptr;      // the block goes back behind the work queued on this stream (null: on any blocking stream)
+    void *stream;                // the block goes back behind the work queued on this stream (null: on any blocking stream)
+    explicit DevBuf(void *s = nullptr) : stream(s) {}
     int get(cofhe_hip_ctx *c, size_t bytes) {
         ctx = c;
         return cofhe_hip_malloc(c, bytes, &p);
@@ -418,13 +475,37 @@ struct ProfScope {
 // registers per lane, fewer spills) whenever the whole grid is resident at three workgroups per CU, the plain build, which
 // leaves room for four, otherwise
 bool fits_three_per_cu(unsigned blocks) { return blocks <= 3u * NUM_CUS; }
-// launches the build that fits a grid of `blocks` workgroups, in a "profile_kernels" span named span3 or span (null: none)
+// THE launch of a kernel with one build: in a "profile_kernels" span of the name `span` (null: none), and checked
 extern "C++" template <typename... P, typename... A>
-void launch_wg(cofhe_hip_ctx *ctx, void (*k3)(P...), void (*k)(P...), const char *span3, const char *span, unsigned blocks,
-               hipStream_t st, A... args) {
-    const bool three = fits_three_per_cu(blocks);
-    ProfScope ps(ctx, three ? span3 : span, st);
-    hipLaunchKernelGGL(three ? k3 : k, dim3(blocks), dim3(WG_BLOCK), 0, st, args...);
+int launch(cofhe_hip_ctx *ctx, const char *span, void (*k)(P...), dim3 grid, dim3 block, hipStream_t st, A... args) {
+    ProfScope ps(ctx, span, st);
+    hipLaunchKernelGGL(k, grid, block, 0, st, args...);
+    HIPCHK(hipGetLastError());
+    return COFHE_HIP_OK;
+}
+// and of one with two: the build that fits a grid of `blocks` workgroups, in a span named span3 or span (null: none)
+extern "C++" template <typename... P, typename... A>
+int launch_wg(cofhe_hip_ctx *ctx, void (*k3)(P...), void (*k)(P...), const char *span3, const char *span, unsigned blocks,
+              hipStream_t st, A... args) {
+    return launch(ctx, fits_three_per_cu(blocks) ? span3 : span, fits_three_per_cu(blocks) ? k3 : k, blocks, WG_BLOCK, st, args...);
+}
+// What the four *_tuples_records entries do once they have checked their arguments: a block of the block cache for the `recs`
+// plaintext rows, the rows by write_rows(block), and their fresh encryption into d_out, which carves the workspace by the plan
+// "comb" (kind 1) over `recs` plaintexts
+extern "C++" template <typename Rows>
+int encrypt_rows(cofhe_hip_ctx *ctx, uint64_t recs, uint32_t kbits, const void *d_rho, const uint32_t *h_record, const uint32_t *pk_record,
+                 const uint32_t *f_record, void *d_out, void *stream, Rows write_rows) {
+    DevBuf rows(stream);
+    if (int rc = rows.get(ctx, recs * EXP_BYTES)) return rc;
+    if (int rc = write_rows(rows.p)) return rc;
+    return cofhe_hip_encrypt_fresh_records(ctx, rows.p, d_rho, h_record, pk_record, f_record, d_out, recs, kbits, stream);
+}
+// The tail test of the four *_shape entries: whether shape_t is shape_e followed by `t` more dimensions, 8 at the most in all;
+// *tail: those dimensions
+bool tail_shape(uint32_t ndim_e, const uint32_t *shape_e, uint32_t ndim_t, const uint32_t *shape_t, uint32_t t, const uint32_t **tail) {
+    if (ndim_e > 8 - t || ndim_t != ndim_e + t || (ndim_e && memcmp(shape_t, shape_e, 4 * ndim_e) != 0)) return false;
+    *tail = shape_t + ndim_e;
+    return true;
 }
 int compose_blocks(uint64_t n, unsigned *blocks) {
     uint64_t b = (n + WG_GROUPS - 1) / WG_GROUPS;
@@ -444,7 +525,7 @@ unsigned scan_blocks(uint64_t n_ct) { return (unsigned)std::min<uint64_t>((n_ct 
 int max_exp_bits(cofhe_hip_ctx *ctx, const void *d_exps, uint64_t n_exps, hipStream_t st, uint32_t *bits) {
     uint32_t *d_bits = flag_word(ctx);
     HIPCHK(hipMemsetAsync(d_bits, 0, 4, st));
-    hipLaunchKernelGGL(k_exp_maxbits, dim3((unsigned)((n_exps + 255) / 256)), dim3(256), 0, st, (const uint32_t *)d_exps, n_exps, d_bits);
+    if (int rc = launch(ctx, nullptr, k_exp_maxbits, (unsigned)((n_exps + 255) / 256), 256, st, (const uint32_t *)d_exps, n_exps, d_bits)) return rc;
     HIPCHK(hipMemcpyAsync(bits, d_bits, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return COFHE_HIP_OK;
@@ -678,27 +759,26 @@ int cofhe_hip_compose_records(cofhe_hip_ctx *ctx, const void *d_a, const void *d
     if (n == 0) return COFHE_HIP_OK;
     unsigned blocks;
     if (int rc = compose_blocks(n, &blocks)) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    launch_wg(ctx, k_compose_wg3, k_compose_wg, "k_compose_wg3", "k_compose_wg", blocks, (hipStream_t)stream, (const uint32_t *)d_a,
-              (const uint32_t *)d_b, (uint32_t *)d_out, n, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
+    return launch_wg(ctx, k_compose_wg3, k_compose_wg, "k_compose_wg3", "k_compose_wg", blocks, st, (const uint32_t *)d_a,
+                     (const uint32_t *)d_b, (uint32_t *)d_out, n, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
 }
 
 int cofhe_hip_compose_wide_records(cofhe_hip_ctx *ctx, const void *d_a, const void *d_b, void *d_out, uint64_t n, uint32_t reps,
                                    uint32_t *fallbacks, void *stream) {
     if (n == 0) return COFHE_HIP_OK;
     if (n > 0x7FFFFFFFull) return fail(COFHE_HIP_EINVAL, "work size out of range");
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
     uint32_t *d_fb = nullptr;
     if (fallbacks) {
         d_fb = flag_word(ctx);
         HIPCHK(hipMemsetAsync(d_fb, 0, 4, st));
     }
-    hipLaunchKernelGGL(k_compose_wide, dim3((unsigned)n), dim3(64), 0, st, (const uint32_t *)d_a, (const uint32_t *)d_b, (uint32_t *)d_out, n,
-                       reps, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status, d_fb);
-    HIPCHK(hipGetLastError());
+    if (int rc = launch(ctx, nullptr, k_compose_wide, (unsigned)n, 64, st, (const uint32_t *)d_a, (const uint32_t *)d_b, (uint32_t *)d_out, n,
+                        reps, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status, d_fb))
+        return rc;
     if (fallbacks) {
         HIPCHK(hipMemcpyAsync(fallbacks, d_fb, 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
@@ -719,30 +799,30 @@ int ct_pair_launch(cofhe_hip_ctx *ctx, const CtPairBuilds &kb, const void *d_a, 
     if (n_ct > (1ull << 40)) return fail(COFHE_HIP_EINVAL, "tensor too large");
     unsigned blocks;
     if (int rc = compose_blocks(n_ct * 2, &blocks)) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
     uint32_t *flag = flag_word(ctx);
     HIPCHK(hipMemsetAsync(flag, 0, 4, st));
-    if (n_ct > 1)
-        hipLaunchKernelGGL(k_c1_distinct, dim3(scan_blocks(n_ct)), dim3(256), 0, st, (const uint32_t *)d_a, (const uint32_t *)d_b, n_ct, flag);
-    else
+    if (n_ct > 1) {
+        if (int rc = launch(ctx, nullptr, k_c1_distinct, scan_blocks(n_ct), 256, st, (const uint32_t *)d_a, (const uint32_t *)d_b, n_ct, flag)) return rc;
+    } else {
         HIPCHK(hipMemsetAsync(flag, 1, 1, st));                   // one ciphertext: nothing to fold
+    }
     unsigned blocks_shared;
     if (int rc = compose_blocks(n_ct + 1, &blocks_shared)) return rc;
     const auto add = [&](unsigned grid, uint32_t only) {
-        launch_wg(ctx, kb.k3, kb.k, kb.span3, kb.span, grid, st, (const uint32_t *)d_a, (const uint32_t *)d_b, (uint32_t *)d_out,
-                  n_ct, (const uint32_t *)flag, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status, only);
+        return launch_wg(ctx, kb.k3, kb.k, kb.span3, kb.span, grid, st, (const uint32_t *)d_a, (const uint32_t *)d_b, (uint32_t *)d_out,
+                         n_ct, (const uint32_t *)flag, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status, only);
     };
     if (!fits_three_per_cu(blocks) && fits_three_per_cu(blocks_shared)) {
         // only the folded case fits at three per CU, and the host does not know which case it is: a pair of launches, each
         // sized and built for its case; the one whose case it is not returns at once (128x128: 0.308 -> 0.29x ms folded)
-        add(blocks_shared, 1u);
-        add(blocks, 2u);
+        if (int rc = add(blocks_shared, 1u)) return rc;
+        if (int rc = add(blocks, 2u)) return rc;
     } else {
-        add(blocks, 0u);     // even with distinct c1, a grid that fits is resident at three workgroups per CU
+        if (int rc = add(blocks, 0u)) return rc;     // even with distinct c1, a grid that fits is resident at three workgroups per CU
     }
-    if (n_ct > 1) hipLaunchKernelGGL(k_c1_spread, dim3(scan_blocks(n_ct)), dim3(256), 0, st, (uint32_t *)d_out, n_ct, (const uint32_t *)flag);
-    HIPCHK(hipGetLastError());
+    if (n_ct > 1) return launch(ctx, nullptr, k_c1_spread, scan_blocks(n_ct), 256, st, (uint32_t *)d_out, n_ct, (const uint32_t *)flag);
     return COFHE_HIP_OK;
 }
 }  // namespace
@@ -759,18 +839,15 @@ namespace {
 int invert_launch(cofhe_hip_ctx *ctx, const void *d_in, void *d_out, uint64_t n, uint32_t stride, uint32_t offset, hipStream_t st) {
     unsigned blocks;
     if (int rc = compose_blocks(n, &blocks)) return rc;
-    ProfScope ps(ctx, "k_invert_records", st);
-    hipLaunchKernelGGL(k_invert_records, dim3(blocks), dim3(WG_BLOCK), 0, st, (const uint32_t *)d_in, (uint32_t *)d_out, n, stride, offset);
-    return COFHE_HIP_OK;
+    return launch(ctx, "k_invert_records", k_invert_records, blocks, WG_BLOCK, st, (const uint32_t *)d_in, (uint32_t *)d_out, n, stride, offset);
 }
 }  // namespace
 int cofhe_hip_invert_records(cofhe_hip_ctx *ctx, const void *d_in, void *d_out, uint64_t n_records, void *stream) {
     if (n_records == 0) return COFHE_HIP_OK;
     if (!d_in || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    if (int rc = invert_launch(ctx, d_in, d_out, n_records, 1u, 0u, (hipStream_t)stream)) return rc;
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
+    return invert_launch(ctx, d_in, d_out, n_records, 1u, 0u, st);
 }
 
 namespace {
@@ -779,24 +856,20 @@ namespace {
 int pow_launch(cofhe_hip_ctx *ctx, const void *d_base, const void *d_exp, void *d_out, uint64_t n_records, uint32_t exp_mode, void *stream) {
     unsigned blocks;
     if (int rc = compose_blocks(n_records, &blocks)) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
     const size_t bytes = (size_t)n_records * REC_WORDS * 4;
-    const uint8_t *b0 = (const uint8_t *)d_base, *o0 = (const uint8_t *)d_out;
     std::unique_lock<std::recursive_mutex> lk(ctx->mu, std::defer_lock);
     std::optional<WsUse> use;                                  // declared after the lock: released before it
-    if (b0 < o0 + bytes && o0 < b0 + bytes) {
+    if (!clear_of({d_out, bytes}, {{d_base, bytes}})) {
         lk.lock();                                             // the workspace belongs to one call at a time ...
         use.emplace(ctx, st);                                  // ... until its kernel has finished (k_pow reads the copy)
         if (int rc = ensure_workspace(ctx, bytes, st)) return rc;
         HIPCHK(hipMemcpyAsync(ctx->workspace, d_base, bytes, hipMemcpyDeviceToDevice, st));
         d_base = ctx->workspace;
     }
-    hipLaunchKernelGGL(k_pow, dim3(blocks), dim3(WG_BLOCK), 0, st, (const uint32_t *)d_base, (const uint32_t *)d_exp,
-                       (uint32_t *)d_out, n_records, 1u, exp_mode, (const uint32_t *)ctx->d_one,
-                       (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    return launch(ctx, nullptr, k_pow, blocks, WG_BLOCK, st, (const uint32_t *)d_base, (const uint32_t *)d_exp, (uint32_t *)d_out, n_records,
+                  1u, exp_mode, (const uint32_t *)ctx->d_one, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
 }
 // The pairwise product tree: folds src[n][mm][q] (mm slices of q records in each of n rows; a slice without a partner is
 // paired with the principal form) down to one slice per row, ceil(log2 mm) k_compose_pairs launches.  The levels go to
@@ -810,9 +883,9 @@ int product_tree(cofhe_hip_ctx *ctx, const uint32_t *src, uint32_t *next, uint32
         unsigned blocks;
         if (int rc = compose_blocks((uint64_t)n * mh * q, &blocks)) return rc;
         uint32_t *dst = mh == 1 && last ? last : next;
-        ProfScope ps(ctx, span, st);
-        hipLaunchKernelGGL(k_compose_pairs, dim3(blocks), dim3(WG_BLOCK), 0, st, src, (const uint32_t *)ctx->d_one, dst, n, mm, q, 0u,
-                           (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+        if (int rc = launch(ctx, span, k_compose_pairs, blocks, WG_BLOCK, st, src, (const uint32_t *)ctx->d_one, dst, n, mm, q, 0u,
+                            (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status))
+            return rc;
         src = dst;
         std::swap(next, other);
         mm = mh;
@@ -828,11 +901,11 @@ int accumulate_impl(cofhe_hip_ctx *ctx, const void *d_x, const void *d_zero, voi
     if (total == 0) return COFHE_HIP_OK;
     unsigned blocks;
     if (int rc = compose_blocks(total, &blocks)) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
     if (total < 16384 && m >= 4) {
         // too few outputs to fill 256 CUs with chains of m compositions: pairwise product tree, ceil(log2 m)
         // launches over [n][m'][2p] slices in two ping-pong buffers, then the composition with Enc(0)
-        hipStream_t st = (hipStream_t)stream;
         const uint32_t q = 2 * p;
         const WsPlan tp = plan_accumulate_tree(n, m, p);
         if (!tree_scratch) {
@@ -843,16 +916,11 @@ int accumulate_impl(cofhe_hip_ctx *ctx, const void *d_x, const void *d_zero, voi
         if (int rc = product_tree(ctx, (const uint32_t *)d_x, (uint32_t *)((uint8_t *)tree_scratch + tp.off("level_a")),
                                   (uint32_t *)((uint8_t *)tree_scratch + tp.off("level_b")), nullptr, n, m, q, nullptr, st, &src))
             return rc;
-        hipLaunchKernelGGL(k_compose_pairs, dim3(blocks), dim3(WG_BLOCK), 0, st, src, (const uint32_t *)d_zero, (uint32_t *)d_out, n,
-                           1u, q, 1u, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
-        HIPCHK(hipGetLastError());
-        return COFHE_HIP_OK;
+        return launch(ctx, nullptr, k_compose_pairs, blocks, WG_BLOCK, st, src, (const uint32_t *)d_zero, (uint32_t *)d_out, n, 1u, q, 1u,
+                      (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
     }
-    hipLaunchKernelGGL(k_accumulate, dim3(blocks), dim3(WG_BLOCK), 0, (hipStream_t)stream, (const uint32_t *)d_x,
-                       (const uint32_t *)d_zero, (uint32_t *)d_out, n, m, p, (const uint32_t *)ctx->d_absdelta,
-                       ctx->half_dbits, ctx->d_status);
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    return launch(ctx, nullptr, k_accumulate, blocks, WG_BLOCK, st, (const uint32_t *)d_x, (const uint32_t *)d_zero, (uint32_t *)d_out, n, m, p,
+                  (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
 }
 }  // namespace
 
@@ -887,10 +955,10 @@ int fixed_base_chain(cofhe_hip_ctx *ctx, const uint32_t *base_record, uint64_t c
         HIPCHK(hipMemcpyAsync(fb->d_table + (size_t)TABLE_LEN * REC_WORDS, base_record, REC_WORDS * 4, hipMemcpyHostToDevice, st));
         // one chain of ~1000 squarings: the latency kernel (one wavefront, wide layout); ladder_form 3 keeps the old one
         const bool old = ctx->opt_ladder_form == 3;
-        hipLaunchKernelGGL(old ? k_square_chain : k_square_chain_wide, dim3(1), dim3(old ? WG_BLOCK : 64), 0, st,
-                           (const uint32_t *)(fb->d_table + (size_t)TABLE_LEN * REC_WORDS), fb->d_table, TABLE_LEN,
-                           (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
-        HIPCHK(hipGetLastError());
+        if (int rc = launch(ctx, nullptr, old ? k_square_chain : k_square_chain_wide, 1, old ? WG_BLOCK : 64, st,
+                            (const uint32_t *)(fb->d_table + (size_t)TABLE_LEN * REC_WORDS), fb->d_table, TABLE_LEN,
+                            (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status))
+            return rc;
         memcpy(fb->base, base_record, REC_WORDS * 4);
         fb->len = TABLE_LEN;
     }
@@ -910,8 +978,8 @@ int cofhe_hip_pow_fixed_base_records(cofhe_hip_ctx *ctx, uint32_t n, const uint3
     if (!base_records || !exp_records || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
     if (n == 0) return COFHE_HIP_OK;
     if (n > 4) return fail(COFHE_HIP_EINVAL, "at most 4 fixed-base powers per call (the context keeps 4 tables)");
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
     WsUse use(ctx, st);
     const uint32_t TABLE_LEN = FIXED_BASE_CHAIN_LEN;
     // ---- tables of the bases (all n must be resident at once: the ones of this call are stamped first)
@@ -954,12 +1022,12 @@ int cofhe_hip_pow_fixed_base_records(cofhe_hip_ctx *ctx, uint32_t n, const uint3
     HIPCHK(hipStreamSynchronize(st));          // `host` is a local vector: the copy must have read it before it goes
     uint32_t *buf[2] = {(uint32_t *)(ws + fp.off("level_a")), (uint32_t *)(ws + fp.off("level_b"))};
     const uint32_t total = n * mmax;
-    hipLaunchKernelGGL(k_gather_signed, dim3((total + WG_GROUPS - 1) / WG_GROUPS), dim3(WG_BLOCK), 0, st, (const uint64_t *)d_tabs,
-                       (const uint32_t *)(d_tabs + n), (uint64_t)total, (const uint32_t *)ctx->d_one, buf[0]);
+    if (int rc = launch(ctx, nullptr, k_gather_signed, (total + WG_GROUPS - 1) / WG_GROUPS, WG_BLOCK, st, (const uint64_t *)d_tabs,
+                        (const uint32_t *)(d_tabs + n), (uint64_t)total, (const uint32_t *)ctx->d_one, buf[0]))
+        return rc;
     const uint32_t *res;
     if (int rc = product_tree(ctx, buf[0], buf[1], buf[0], (uint32_t *)d_out, n, mmax, 1u, nullptr, st, &res)) return rc;
     if (res != d_out) HIPCHK(hipMemcpyAsync(d_out, res, (size_t)n * REC_WORDS * 4, hipMemcpyDeviceToDevice, st));     // mmax == 1: nothing to fold
-    HIPCHK(hipGetLastError());
     return COFHE_HIP_OK;
 }
 int cofhe_hip_pow_fixed_base_record(cofhe_hip_ctx *ctx, const uint32_t *base_record, const uint32_t *exp_record, void *d_out, void *stream) {
@@ -982,8 +1050,7 @@ int comb_check(uint64_t kind, uint64_t n, uint64_t exp_bits, uint64_t kbits, uin
     if (n > (1ull << 36)) return fail(COFHE_HIP_EINVAL, "comb: too many items");
     if (exp_bits > COMB_EXP_BITS) return fail(COFHE_HIP_EINVAL, "comb: exponents have at most 992 bits");
     if (w != 0 && (w < (uint64_t)COMB_W_MIN || w > (uint64_t)COMB_W_MAX)) return fail(COFHE_HIP_EINVAL, "comb: w is 0 (automatic) or 2..10");
-    if ((kind == 1 || kind >= 3) && (kbits == 0 || 2 * kbits + 1 > (uint64_t)PLIMBS * 32 || kbits > EXP_MAG_WORDS * 32 - 1))
-        return fail(COFHE_HIP_EINVAL, "k out of range");
+    if ((kind == 1 || kind >= 3) && !k_in_range(kbits)) return fail(COFHE_HIP_EINVAL, "k out of range");
     if (chunk > (1ull << 32)) return fail(COFHE_HIP_EINVAL, "comb: chunk out of range");
     return COFHE_HIP_OK;
 }
@@ -1011,11 +1078,10 @@ int comb_table(cofhe_hip_ctx *ctx, const uint32_t *base_record, uint32_t w, uint
         for (uint32_t half = 1; half < D; half *= 2) {
             unsigned blocks;
             if (int rc = compose_blocks((uint64_t)npos * half, &blocks)) return rc;
-            ProfScope ps(ctx, "k_comb_table", st);
-            hipLaunchKernelGGL(k_comb_table, dim3(blocks), dim3(WG_BLOCK), 0, st, hit->d, npos, w, half, (const uint32_t *)ctx->d_absdelta,
-                               ctx->half_dbits, ctx->d_status);
+            if (int rc = launch(ctx, "k_comb_table", k_comb_table, blocks, WG_BLOCK, st, hit->d, npos, w, half, (const uint32_t *)ctx->d_absdelta,
+                                ctx->half_dbits, ctx->d_status))
+                return rc;
         }
-        HIPCHK(hipGetLastError());
         memcpy(hit->base, base_record, REC_WORDS * 4);
         hit->w = w;
     }
@@ -1040,8 +1106,8 @@ int comb_run(cofhe_hip_ctx *ctx, uint32_t kind, const uint32_t *const bases[3], 
     if (n == 0) return COFHE_HIP_OK;
     const bool has_r = kind != 3, has_m = kind == 1 || kind >= 3, has_leaf = kind >= 2;
     if (!d_out || (has_r && !d_r) || (has_m && !d_m) || (has_leaf && !d_leaf)) return fail(COFHE_HIP_EINVAL, "null argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
     WsUse use(ctx, st);
     const CombState &cs = comb_state(ctx);
     // the tree's shape follows the longest exponent: the one read-back of the call (kind 3: its shape follows from k alone)
@@ -1076,19 +1142,16 @@ int comb_run(cofhe_hip_ctx *ctx, uint32_t kind, const uint32_t *const bases[3], 
         uint32_t mm = cc.slots / 2;
         unsigned blocks;
         if (int rc = compose_blocks(ncols * mm, &blocks)) return rc;
-        {
-            ProfScope ps(ctx, "k_comb_first", st);
-            hipLaunchKernelGGL(k_comb_first, dim3(blocks), dim3(WG_BLOCK), 0, st, cc.s, tabs[0], tabs[1], tabs[2],
-                               d_r ? (const uint32_t *)d_r + e0 * EXP_REC_WORDS : nullptr, d_m ? (const uint32_t *)d_m + e0 * EXP_REC_WORDS : nullptr,
-                               d_leaf ? (const uint32_t *)d_leaf + e0 * R * REC_WORDS : nullptr, ncols, (const uint32_t *)ctx->d_one,
-                               mm == 1 && kind != 3 ? out : buf[0], (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
-        }
+        if (int rc = launch(ctx, "k_comb_first", k_comb_first, blocks, WG_BLOCK, st, cc.s, tabs[0], tabs[1], tabs[2],
+                            d_r ? (const uint32_t *)d_r + e0 * EXP_REC_WORDS : nullptr, d_m ? (const uint32_t *)d_m + e0 * EXP_REC_WORDS : nullptr,
+                            d_leaf ? (const uint32_t *)d_leaf + e0 * R * REC_WORDS : nullptr, ncols, (const uint32_t *)ctx->d_one,
+                            mm == 1 && kind != 3 ? out : buf[0], (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status))
+            return rc;
         // kind 3's columns are every second record of the output: its tree ends in the workspace and one strided copy places it
         const uint32_t *top = nullptr;
         if (int rc = product_tree(ctx, buf[0], buf[1], buf[0], kind == 3 ? nullptr : out, 1u, mm, (uint32_t)ncols, "k_compose_pairs", st, &top))
             return rc;
         if (kind == 3) HIPCHK(hipMemcpy2DAsync(out + REC_WORDS, 2 * rec_bytes, top, rec_bytes, rec_bytes, ne, hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipGetLastError());
     }
     return COFHE_HIP_OK;
 }
@@ -1151,7 +1214,7 @@ int pow_shared(cofhe_hip_ctx *ctx, const void *d_base, uint32_t stride, const vo
     // step, 3: the throughput kernel, 4: one wavefront per ladder, left to right with a table of odd powers)
     int form = ctx->opt_ladder_form ? ctx->opt_ladder_form : (n <= 256 ? 1 : 3);           // one ladder per CU at most: four per CU ran at half speed each
     if (form == 1 && n > POW_PAIR_MAX_LADDERS) form = 4;        // the pair's two workgroups must be resident together
-    hipLaunchKernelGGL(k_wnaf_digits, dim3(1), dim3(64), 0, st, (const uint32_t *)d_exp, (uint64_t)1, form == 1 ? 2u : w, digits, maxlen);
+    if (int rc = launch(ctx, nullptr, k_wnaf_digits, 1, 64, st, (const uint32_t *)d_exp, (uint64_t)1, form == 1 ? 2u : w, digits, maxlen)) return rc;
     // forms 4, 2 (while its ladders fit one wavefront) and 3 take the same arguments; the span is named after the kernel
     struct Ladder {
         decltype(&k_pow_shared) kernel;
@@ -1161,17 +1224,13 @@ int pow_shared(cofhe_hip_ctx *ctx, const void *d_base, uint32_t stride, const vo
     const Ladder l = form == 4                    ? Ladder{k_pow_shared_wide, (unsigned)n, 64, "k_pow_shared_wide"}
                      : (form == 2 && n <= 64 / G) ? Ladder{k_pow_shared_solo, 1, 64, "k_pow_shared_solo"}
                                                   : Ladder{k_pow_shared, blocks, WG_BLOCK, "k_pow_shared"};
-    ProfScope ps(ctx, form == 1 ? "k_pow_shared_pair" : l.span, st);
     if (form == 1)
-        hipLaunchKernelGGL(k_pow_shared_pair, dim3((unsigned)(2 * n)), dim3(64), 0, st, (const uint32_t *)d_base, (const int8_t *)digits,
-                           (const uint32_t *)maxlen, table, pairctl, (uint32_t *)d_out, n, stride, (const uint32_t *)ctx->d_one,
-                           (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);     // the table region serves as the rings
-    else
-        hipLaunchKernelGGL(l.kernel, dim3(l.grid), dim3(l.block), 0, st, (const uint32_t *)d_base, (const int8_t *)digits,
-                           (const uint32_t *)maxlen, table, (uint32_t *)d_out, n, stride, tw, (const uint32_t *)ctx->d_one,
-                           (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+        return launch(ctx, "k_pow_shared_pair", k_pow_shared_pair, (unsigned)(2 * n), 64, st, (const uint32_t *)d_base, (const int8_t *)digits,
+                      (const uint32_t *)maxlen, table, pairctl, (uint32_t *)d_out, n, stride, (const uint32_t *)ctx->d_one,
+                      (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);     // the table region serves as the rings
+    return launch(ctx, l.span, l.kernel, l.grid, l.block, st, (const uint32_t *)d_base, (const int8_t *)digits, (const uint32_t *)maxlen, table,
+                  (uint32_t *)d_out, n, stride, tw, (const uint32_t *)ctx->d_one, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits,
+                  ctx->d_status);
 }
 // out[i] = c1_i^e for the n_ct ciphertexts of a tensor (decryption, threshold decryption).  A tensor that encrypt_tensor
 // made -- or a sum of such tensors -- carries ONE c1 (cpu_cryptosystem_tensor_ops.inl:7-12): then one ladder runs and its
@@ -1184,7 +1243,7 @@ int pow_shared_c1(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_exp, void
     if (n_ct >= 64) {
         uint32_t *flag = flag_word(ctx);
         HIPCHK(hipMemsetAsync(flag, 0, 4, st));
-        hipLaunchKernelGGL(k_c1_distinct, dim3(scan_blocks(n_ct)), dim3(256), 0, st, (const uint32_t *)d_cts, (const uint32_t *)d_cts, n_ct, flag);
+        if (int rc = launch(ctx, nullptr, k_c1_distinct, scan_blocks(n_ct), 256, st, (const uint32_t *)d_cts, (const uint32_t *)d_cts, n_ct, flag)) return rc;
         uint32_t distinct = 1;
         HIPCHK(hipMemcpyAsync(&distinct, flag, 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
@@ -1196,10 +1255,7 @@ int pow_shared_c1(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_exp, void
     if (extra) *extra = ex;
     uint32_t *res = (uint32_t *)(d_out ? d_out : ex);
     const unsigned blocks = (unsigned)std::min<uint64_t>((n_ct * REC_WORDS + 255) / 256, 4096);
-    ProfScope ps(ctx, "k_spread_records", st);               // the witness of the shared route: one ladder, then this copy
-    hipLaunchKernelGGL(k_spread_records, dim3(blocks), dim3(256), 0, st, res, n_ct);
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    return launch(ctx, "k_spread_records", k_spread_records, blocks, 256, st, res, n_ct);     // the witness of the shared route: one ladder, then this copy
 }
 }  // namespace
 
@@ -1207,18 +1263,18 @@ int cofhe_hip_part_decrypt_records(cofhe_hip_ctx *ctx, const void *d_cts, const 
                                    uint64_t n_ct, void *stream) {
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     if (n_ct == 0) return COFHE_HIP_OK;
-    HIPCHK(hipSetDevice(ctx->device));
-    WsUse use(ctx, (hipStream_t)stream);
-    return pow_shared_c1(ctx, d_cts, d_share, d_out, n_ct, 0, nullptr, (hipStream_t)stream);
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
+    WsUse use(ctx, st);
+    return pow_shared_c1(ctx, d_cts, d_share, d_out, n_ct, 0, nullptr, st);
 }
 
 namespace {
 // ---- the matrix product: what its two routes share, the routes, then the entry point that chooses ------------------------
 // the width-w digits of n_exps exponents and the length of the longest, in a "k_wnaf_digits" span
-void wnaf_digits(cofhe_hip_ctx *ctx, const void *d_exp, uint64_t n_exps, uint32_t w, int8_t *digits, uint32_t *maxlen, hipStream_t st) {
-    if (n_exps == 0) return;
-    ProfScope ps(ctx, "k_wnaf_digits", st);
-    hipLaunchKernelGGL(k_wnaf_digits, dim3((unsigned)((n_exps + 255) / 256)), dim3(256), 0, st, (const uint32_t *)d_exp, n_exps, w, digits, maxlen);
+int wnaf_digits(cofhe_hip_ctx *ctx, const void *d_exp, uint64_t n_exps, uint32_t w, int8_t *digits, uint32_t *maxlen, hipStream_t st) {
+    if (n_exps == 0) return COFHE_HIP_OK;
+    return launch(ctx, "k_wnaf_digits", k_wnaf_digits, (unsigned)((n_exps + 255) / 256), 256, st, (const uint32_t *)d_exp, n_exps, w, digits, maxlen);
 }
 // the tw odd powers of each of the nbase records into `room`, in a "k_pow_table" span (around the "k_pow_table3" one of the
 // three-per-CU build); *table: where the route finds them
@@ -1228,8 +1284,9 @@ int pow_table(cofhe_hip_ctx *ctx, const void *d_cts, uint64_t nbase, uint32_t tw
     unsigned tblocks;
     if (int rc = compose_blocks(nbase, &tblocks)) return rc;
     ProfScope ps(ctx, "k_pow_table", st);
-    launch_wg(ctx, k_pow_table3, k_pow_table, "k_pow_table3", nullptr, tblocks, st, (const uint32_t *)d_cts, (uint32_t *)room, nbase, tw,
-              (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+    if (int rc = launch_wg(ctx, k_pow_table3, k_pow_table, "k_pow_table3", nullptr, tblocks, st, (const uint32_t *)d_cts, (uint32_t *)room, nbase, tw,
+                           (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status))
+        return rc;
     *table = (const uint32_t *)room;
     return COFHE_HIP_OK;
 }
@@ -1275,11 +1332,12 @@ int matmul_tree_route(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_exp, 
     uint32_t *d_info = (uint32_t *)(ws + tp.off("info"));
     const uint32_t S_cap = (exp_bits + 2) * p;
     HIPCHK(hipMemsetAsync(digits, 0, tp.off("maxlen") + 256 - tp.off("digits"), st));
-    wnaf_digits(ctx, d_exp, n_exps, w, digits, maxlen, st);
+    if (int rc = wnaf_digits(ctx, d_exp, n_exps, w, digits, maxlen, st)) return rc;
     HIPCHK(hipMemsetAsync(d_c, 0, (size_t)S_cap * 4, st));              // level 0 of segments beyond the longest exponent
-    hipLaunchKernelGGL(k_tree_count, dim3((unsigned)(((uint64_t)S_cap + 255) / 256)), dim3(256), 0, st, (const int8_t *)digits,
-                       (const uint32_t *)maxlen, m, p, d_c);
-    hipLaunchKernelGGL(k_tree_plan, dim3(1), dim3(1024), 0, st, (const uint32_t *)maxlen, p, S_cap, d_c, d_off, d_info);
+    if (int rc = launch(ctx, nullptr, k_tree_count, (unsigned)(((uint64_t)S_cap + 255) / 256), 256, st, (const int8_t *)digits,
+                        (const uint32_t *)maxlen, m, p, d_c))
+        return rc;
+    if (int rc = launch(ctx, nullptr, k_tree_plan, 1, 1024, st, (const uint32_t *)maxlen, p, S_cap, d_c, d_off, d_info)) return rc;
     uint32_t info[TREE_LEVELS + 3];
     HIPCHK(hipMemcpyAsync(info, d_info, sizeof(info), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));                           // `info` is on the host
@@ -1312,16 +1370,17 @@ int matmul_tree_route(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_exp, 
     for (uint32_t l = 1; l <= T; l++) map_words += info[l];
     const uint32_t len = p ? S / p : 0;                       // bit positions in use
     const uint32_t rcap_h = 2 * len + 2;
-    DevBuf b_ent, b_map, b_ops, b_cnt, b_lvl[2];
-    for (DevBuf *b : {&b_ent, &b_map, &b_ops, &b_cnt, &b_lvl[0], &b_lvl[1]}) b->stream = st;      // on every way out
+    DevBuf b_ent(st), b_map(st), b_ops(st), b_cnt(st), b_lvl[2] = {DevBuf(st), DevBuf(st)};      // back behind `st` on every way out
     if (int rc = b_ent.get(ctx, (size_t)info[0] * 4 + 4)) return rc;
     if (int rc = b_map.get(ctx, (size_t)map_words * 4 + 4)) return rc;
     if (int rc = b_ops.get(ctx, (size_t)p * rcap_h * 4)) return rc;
     if (int rc = b_cnt.get(ctx, (size_t)p * 4)) return rc;
-    hipLaunchKernelGGL(k_tree_fill, dim3(S ? S : 1), dim3(64), 0, st, (const int8_t *)digits, m, p, S_cap, (const uint32_t *)d_c,
-                       (const uint32_t *)d_off, (const uint32_t *)d_info, (uint32_t *)b_ent.p, (uint32_t *)b_map.p);
-    hipLaunchKernelGGL(k_tree_horner_schedule, dim3((p + 63) / 64), dim3(64), 0, st, (const uint32_t *)maxlen, p, S_cap, (const uint32_t *)d_c,
-                       (const uint32_t *)d_off, (const uint32_t *)d_info, rcap_h, (uint32_t *)b_ops.p, (uint32_t *)b_cnt.p, ctx->d_status);
+    if (int rc = launch(ctx, nullptr, k_tree_fill, S ? S : 1, 64, st, (const int8_t *)digits, m, p, S_cap, (const uint32_t *)d_c,
+                        (const uint32_t *)d_off, (const uint32_t *)d_info, (uint32_t *)b_ent.p, (uint32_t *)b_map.p))
+        return rc;
+    if (int rc = launch(ctx, nullptr, k_tree_horner_schedule, (p + 63) / 64, 64, st, (const uint32_t *)maxlen, p, S_cap, (const uint32_t *)d_c,
+                        (const uint32_t *)d_off, (const uint32_t *)d_info, rcap_h, (uint32_t *)b_ops.p, (uint32_t *)b_cnt.p, ctx->d_status))
+        return rc;
     const size_t lvl_bytes = (size_t)n1 * R * 2 * REC_WORDS * 4;
     if (int rc = b_lvl[0].get(ctx, lvl_bytes)) return rc;
     if (int rc = b_lvl[1].get(ctx, lvl_bytes)) return rc;
@@ -1335,30 +1394,30 @@ int matmul_tree_route(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_exp, 
             if (items == 0) break;
             if (int rc = compose_blocks(items, &lb)) return rc;
             if (cv && l == 0) {                                // the leaves of rows r0 .. r0 + rows - 1, from the image's table
-                ProfScope ps(ctx, "k_conv_level0", st);
-                hipLaunchKernelGGL(k_conv_level0, dim3(lb), dim3(WG_BLOCK), 0, st, *cv, table, (const uint32_t *)ctx->d_one, (const uint32_t *)b_ent.p,
-                                   (const uint32_t *)d_off, (const uint32_t *)(d_off + (S_cap + 1)), maps, info[1], r0, rows, tw,
-                                   (uint32_t *)b_lvl[0].p, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+                if (int rc = launch(ctx, "k_conv_level0", k_conv_level0, lb, WG_BLOCK, st, *cv, table, (const uint32_t *)ctx->d_one,
+                                    (const uint32_t *)b_ent.p, (const uint32_t *)d_off, (const uint32_t *)(d_off + (S_cap + 1)), maps, info[1], r0, rows,
+                                    tw, (uint32_t *)b_lvl[0].p, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status))
+                    return rc;
                 map_base += info[1];
                 continue;
             }
             const uint32_t *src = l == 0 ? table + (uint64_t)r0 * m * 2 * tw * REC_WORDS : (const uint32_t *)b_lvl[(l - 1) & 1].p;
-            ProfScope ps(ctx, "k_tree_level", st);
-            hipLaunchKernelGGL(k_tree_level, dim3(lb), dim3(WG_BLOCK), 0, st, src, l == 0 ? 1u : 0u, (const uint32_t *)b_ent.p,
-                               (const uint32_t *)(d_off + (uint64_t)l * (S_cap + 1)), (const uint32_t *)(d_off + (uint64_t)(l + 1) * (S_cap + 1)),
-                               maps + map_base, info[l], info[l + 1], rows, m, tw, (uint32_t *)b_lvl[l & 1].p,
-                               (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+            if (int rc = launch(ctx, "k_tree_level", k_tree_level, lb, WG_BLOCK, st, src, l == 0 ? 1u : 0u, (const uint32_t *)b_ent.p,
+                                (const uint32_t *)(d_off + (uint64_t)l * (S_cap + 1)), (const uint32_t *)(d_off + (uint64_t)(l + 1) * (S_cap + 1)),
+                                maps + map_base, info[l], info[l + 1], rows, m, tw, (uint32_t *)b_lvl[l & 1].p,
+                                (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status))
+                return rc;
             map_base += info[l + 1];
         }
         unsigned hb;
         if (int rc = compose_blocks((uint64_t)rows * p * 2, &hb)) return rc;
         ProfScope ps(ctx, "k_scal_matmul_wnaf", st);
-        launch_wg(ctx, k_scal_matmul_wnaf3, k_scal_matmul_wnaf, "k_scal_matmul_wnaf3", nullptr, hb, st, (const uint32_t *)b_lvl[(T - 1) & 1].p,
-                  (const uint32_t *)b_ops.p, (const uint32_t *)b_cnt.p, rcap_h, (const uint32_t *)d_zero,
-                  (uint32_t *)d_out + (uint64_t)r0 * p * 2 * REC_WORDS, rows, info[T] ? info[T] : 1u, p, 1u, 1u, (const uint32_t *)ctx->d_one,
-                  (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+        if (int rc = launch_wg(ctx, k_scal_matmul_wnaf3, k_scal_matmul_wnaf, "k_scal_matmul_wnaf3", nullptr, hb, st,
+                               (const uint32_t *)b_lvl[(T - 1) & 1].p, (const uint32_t *)b_ops.p, (const uint32_t *)b_cnt.p, rcap_h, (const uint32_t *)d_zero,
+                               (uint32_t *)d_out + (uint64_t)r0 * p * 2 * REC_WORDS, rows, info[T] ? info[T] : 1u, p, 1u, 1u,
+                               (const uint32_t *)ctx->d_one, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status))
+            return rc;
     }
-    HIPCHK(hipGetLastError());
     *taken = true;
     return COFHE_HIP_OK;
 }
@@ -1392,20 +1451,21 @@ int matmul_chains_route(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_exp
     uint32_t *counts = (uint32_t *)(ws + mp_.off("counts"));
     uint32_t *partial = (uint32_t *)(ws + mp_.off("partial"));
     HIPCHK(hipMemsetAsync(digits, 0, mp_.off("maxlen") + 256 - mp_.off("digits"), st));
-    wnaf_digits(ctx, d_exp, n_exps, w, digits, maxlen, st);
-    hipLaunchKernelGGL(k_matmul_schedule, dim3(ncols), dim3(64), 0, st, (const int8_t *)digits, (const uint32_t *)maxlen, m, p,
-                       segs, rcap, ops, counts, ctx->d_status);
+    if (int rc = wnaf_digits(ctx, d_exp, n_exps, w, digits, maxlen, st)) return rc;
+    if (int rc = launch(ctx, nullptr, k_matmul_schedule, ncols, 64, st, (const int8_t *)digits, (const uint32_t *)maxlen, m, p, segs, rcap, ops,
+                        counts, ctx->d_status))
+        return rc;
     const uint32_t *table;
     if (int rc = pow_table(ctx, d_cts, nbase, tw, ws + mp_.off("table"), st, &table)) return rc;
     unsigned mblocks;
     if (int rc = compose_blocks(out_forms * segs, &mblocks)) return rc;
     {
         ProfScope ps(ctx, "k_scal_matmul_wnaf", st);
-        launch_wg(ctx, k_scal_matmul_wnaf3, k_scal_matmul_wnaf, "k_scal_matmul_wnaf3", nullptr, mblocks, st, table, (const uint32_t *)ops,
-                  (const uint32_t *)counts, rcap, (const uint32_t *)d_zero, segs > 1 ? partial : (uint32_t *)d_out, n, m, p, tw, segs,
-                  (const uint32_t *)ctx->d_one, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+        if (int rc = launch_wg(ctx, k_scal_matmul_wnaf3, k_scal_matmul_wnaf, "k_scal_matmul_wnaf3", nullptr, mblocks, st, table, (const uint32_t *)ops,
+                               (const uint32_t *)counts, rcap, (const uint32_t *)d_zero, segs > 1 ? partial : (uint32_t *)d_out, n, m, p, tw, segs,
+                               (const uint32_t *)ctx->d_one, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status))
+            return rc;
     }
-    HIPCHK(hipGetLastError());
     if (segs > 1)
         return accumulate_impl(ctx, partial, d_zero, d_out, n, segs, p, ws + mp_.off("tree"), st);
     return COFHE_HIP_OK;
@@ -1418,8 +1478,8 @@ int cofhe_hip_scal_matmul_records(cofhe_hip_ctx *ctx, const void *d_cts, const v
     if ((uint64_t)n * p == 0) return COFHE_HIP_OK;
     unsigned blocks;
     if (int rc = compose_blocks((uint64_t)n * p * 2, &blocks)) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
     WsUse use(ctx, st);
     // window width (wnaf_auto_width): a base's table is used by the p columns of its row
     const uint64_t nbase = (uint64_t)n * m * 2;
@@ -1446,19 +1506,10 @@ int cofhe_hip_scal_matmul_records(cofhe_hip_ctx *ctx, const void *d_cts, const v
 namespace {
 // the one launch site of k_transpose_records: out (cols x rows) = in (rows x cols)^T, elements of `words` words; 16-byte pieces
 // when both pointers and the element size allow them (a caller's pointer is only known to be 4-byte aligned)
-int transpose_launch(const void *d_in, void *d_out, uint32_t rows, uint32_t cols, uint32_t words, hipStream_t st) {
-    const bool vec16 = words % 4 == 0 && (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0;
-    const uint64_t total = (uint64_t)rows * cols * (vec16 ? words / 4 : words);
-    if (total == 0) return COFHE_HIP_OK;
-    const unsigned blocks = (unsigned)std::min<uint64_t>((total + 255) / 256, 64u * NUM_CUS);       // grid-stride beyond that
-    hipLaunchKernelGGL(k_transpose_records, dim3(blocks), dim3(256), 0, st, (const uint32_t *)d_in, (uint32_t *)d_out, rows, cols, words,
-                       vec16 ? 1u : 0u);
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
-}
-bool overlaps(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
+int transpose_launch(cofhe_hip_ctx *ctx, const void *d_in, void *d_out, uint32_t rows, uint32_t cols, uint32_t words, hipStream_t st) {
+    const PieceGrid g = piece_grid((uint64_t)rows * cols, words, 256, {d_in, d_out});
+    if (g.total == 0) return COFHE_HIP_OK;
+    return launch(ctx, nullptr, k_transpose_records, g.blocks, 256, st, (const uint32_t *)d_in, (uint32_t *)d_out, rows, cols, words, g.flag());
 }
 // out (n x p) = zero o s (n x m) . cts (m x p) with s^T (m x n exponent records) as given -- by a transposition
 // (cofhe_hip_matmul_plain_ct_records) or written transposed in the first place (cofhe_hip_conv2d_ct_filters_records):
@@ -1468,14 +1519,13 @@ bool overlaps(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
 int plain_ct_transposed(cofhe_hip_ctx *ctx, const void *d_st, const void *d_cts, const void *d_zero, void *d_out, uint32_t n, uint32_t m, uint32_t p,
                         void *stream) {
     hipStream_t st = (hipStream_t)stream;
-    const size_t ct_bytes = (size_t)2 * REC_WORDS * 4, cts_bytes = (size_t)m * p * ct_bytes;
-    DevBuf cts_t, out_t;                         // cts^T (p x m), out^T (p x n)
-    cts_t.stream = out_t.stream = stream;
+    const size_t cts_bytes = (size_t)m * p * CT_BYTES;
+    DevBuf cts_t(stream), out_t(stream);         // cts^T (p x m), out^T (p x n)
     if (int rc = cts_t.get(ctx, cts_bytes ? cts_bytes : 4)) return rc;
-    if (int rc = out_t.get(ctx, (size_t)n * p * ct_bytes)) return rc;
-    if (int rc = transpose_launch(d_cts, cts_t.p, m, p, 2 * REC_WORDS, st)) return rc;
+    if (int rc = out_t.get(ctx, (size_t)n * p * CT_BYTES)) return rc;
+    if (int rc = transpose_launch(ctx, d_cts, cts_t.p, m, p, 2 * REC_WORDS, st)) return rc;
     if (int rc = cofhe_hip_scal_matmul_records(ctx, cts_t.p, d_st, d_zero, out_t.p, p, m, n, stream)) return rc;
-    return transpose_launch(out_t.p, d_out, p, n, 2 * REC_WORDS, st);
+    return transpose_launch(ctx, out_t.p, d_out, p, n, 2 * REC_WORDS, st);
 }
 }  // namespace
 
@@ -1485,18 +1535,17 @@ int cofhe_hip_matmul_plain_ct_records(cofhe_hip_ctx *ctx, const void *d_s, const
                                       uint32_t m, uint32_t p, void *stream) {
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     if ((uint64_t)n * p == 0) return COFHE_HIP_OK;
-    const size_t ct_bytes = (size_t)2 * REC_WORDS * 4, exp_bytes = (size_t)EXP_REC_WORDS * 4;
-    const size_t out_bytes = (size_t)n * p * ct_bytes, cts_bytes = (size_t)m * p * ct_bytes, s_bytes = (size_t)n * m * exp_bytes;
-    if (overlaps(d_out, out_bytes, d_cts, cts_bytes) || overlaps(d_out, out_bytes, d_s, s_bytes) || overlaps(d_out, out_bytes, d_zero, ct_bytes))
+    const size_t s_bytes = (size_t)n * m * EXP_BYTES;
+    if (!clear_of({d_out, (size_t)n * p * CT_BYTES}, {{d_cts, (size_t)m * p * CT_BYTES}, {d_s, s_bytes}, {d_zero, CT_BYTES}}))
         return fail(COFHE_HIP_EINVAL, "matmul_plain_ct: the output overlaps an input");
     if (m >= (1u << 21)) return fail(COFHE_HIP_EINVAL, "inner dimension beyond 2^21");
     unsigned blocks;
     if (int rc = compose_blocks((uint64_t)n * p * 2, &blocks)) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    DevBuf s_t;                                  // s^T (m x n)
-    s_t.stream = stream;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
+    DevBuf s_t(stream);                          // s^T (m x n)
     if (int rc = s_t.get(ctx, s_bytes ? s_bytes : 4)) return rc;
-    if (int rc = transpose_launch(d_s, s_t.p, n, m, EXP_REC_WORDS, (hipStream_t)stream)) return rc;
+    if (int rc = transpose_launch(ctx, d_s, s_t.p, n, m, EXP_REC_WORDS, st)) return rc;
     return plain_ct_transposed(ctx, s_t.p, d_cts, d_zero, d_out, n, m, p, stream);
 }
 
@@ -1512,28 +1561,18 @@ ConvShape conv_geometry_of(const cofhe_hip_conv2d_geometry &a) {      // (no ove
 // patch matrix is dense over C
 int gather_patches_launch(cofhe_hip_ctx *ctx, const ConvShape &s, const void *d_cts, void *d_patches, hipStream_t st) {
     const uint32_t n = conv_rows(s), m = conv_inner(s);
-    const bool vec16 = (((uintptr_t)d_cts | (uintptr_t)d_patches) & 15) == 0;
-    const uint64_t total = (uint64_t)n * m * 2 * (vec16 ? REC_WORDS / 4 : REC_WORDS);
-    if (total == 0) return COFHE_HIP_OK;
-    const unsigned blocks = (unsigned)std::min<uint64_t>((total + 255) / 256, 64u * NUM_CUS);       // grid-stride beyond that
-    ProfScope ps(ctx, "k_gather_patches", st);
-    hipLaunchKernelGGL(k_gather_patches, dim3(blocks), dim3(256), 0, st, s, (const uint32_t *)d_cts, (const uint32_t *)ctx->d_one,
-                       (uint32_t *)d_patches, n, m, vec16 ? 1u : 0u);
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    const PieceGrid g = piece_grid((uint64_t)n * m * 2, REC_WORDS, 256, {d_cts, d_patches});
+    if (g.total == 0) return COFHE_HIP_OK;
+    return launch(ctx, "k_gather_patches", k_gather_patches, g.blocks, 256, st, s, (const uint32_t *)d_cts, (const uint32_t *)ctx->d_one,
+                  (uint32_t *)d_patches, n, m, g.flag());
 }
 // the one launch site of k_expand_group_filters: the dense [kh, kw, C, Co] exponent tensor of the grouped filters d_w
 // [kh, kw, C / groups, Co] into d_dense (a block of the block cache), the zero exponent outside the blocks
 int expand_group_filters_launch(cofhe_hip_ctx *ctx, const ConvShape &s, const void *d_w, void *d_dense, hipStream_t st) {
-    const bool vec16 = ((uintptr_t)d_w & 15) == 0;
-    const uint64_t total = (uint64_t)s.kh * s.kw * s.C * s.Co * (vec16 ? EXP_REC_WORDS / 4 : EXP_REC_WORDS);
-    if (total == 0) return COFHE_HIP_OK;
-    const unsigned blocks = (unsigned)std::min<uint64_t>((total + 255) / 256, 64u * NUM_CUS);       // grid-stride beyond that
-    ProfScope ps(ctx, "k_expand_group_filters", st);
-    hipLaunchKernelGGL(k_expand_group_filters, dim3(blocks), dim3(256), 0, st, (const uint32_t *)d_w, (uint32_t *)d_dense, s.kh * s.kw, s.C, s.Co,
-                       s.groups, vec16 ? 1u : 0u);
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    const PieceGrid g = piece_grid((uint64_t)s.kh * s.kw * s.C * s.Co, EXP_REC_WORDS, 256, {d_w});
+    if (g.total == 0) return COFHE_HIP_OK;
+    return launch(ctx, "k_expand_group_filters", k_expand_group_filters, g.blocks, 256, st, (const uint32_t *)d_w, (uint32_t *)d_dense, s.kh * s.kw,
+                  s.C, s.Co, s.groups, g.flag());
 }
 
 // THE convolution, behind every entry point: the full geometry, validated here before the context or a pointer is looked at.
@@ -1547,13 +1586,12 @@ int conv2d_run(cofhe_hip_ctx *ctx, const void *d_w, const void *d_cts, const voi
     if (const char *why = conv_shape_check(s)) return fail(COFHE_HIP_EINVAL, why);
     const uint32_t n = conv_rows(s), m = conv_inner(s), p = s.Co;
     if ((uint64_t)n * p == 0) return COFHE_HIP_OK;
-    const size_t ct_bytes = (size_t)2 * REC_WORDS * 4;
-    const size_t out_bytes = (size_t)n * p * ct_bytes, cts_bytes = (size_t)s.B * s.H * s.W * s.C * ct_bytes, w_bytes = (size_t)m * p * EXP_REC_WORDS * 4;
-    if (overlaps(d_out, out_bytes, d_cts, cts_bytes) || overlaps(d_out, out_bytes, d_w, w_bytes) || overlaps(d_out, out_bytes, d_zero, ct_bytes))
+    if (!clear_of({d_out, (size_t)n * p * CT_BYTES},
+                  {{d_cts, (size_t)s.B * s.H * s.W * s.C * CT_BYTES}, {d_w, (size_t)m * p * EXP_BYTES}, {d_zero, CT_BYTES}}))
         return fail(COFHE_HIP_EINVAL, "conv2d: the output overlaps an input");
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
     const CombState &opt = comb_state(ctx);
     const bool grouped = s.groups > 1;
     // the gather route works on the dense inner dimension: kh kw C < 2^21 and the dense patch matrix within the formats' bound
@@ -1578,13 +1616,12 @@ int conv2d_run(cofhe_hip_ctx *ctx, const void *d_w, const void *d_cts, const voi
     if (!gather_fits)
         return fail(COFHE_HIP_EINVAL, "conv2d: the direct route declined and the dense patch matrix of the gather route does not fit");
     const ConvShape ds = conv_dense(s);
-    DevBuf patches, dense;
-    patches.stream = dense.stream = stream;
-    const size_t patch_bytes = (size_t)n * m_dense * ct_bytes;
+    DevBuf patches(stream), dense(stream);
+    const size_t patch_bytes = (size_t)n * m_dense * CT_BYTES;
     if (int rc = patches.get(ctx, patch_bytes ? patch_bytes : 4)) return rc;
     if (int rc = gather_patches_launch(ctx, ds, d_cts, patches.p, st)) return rc;
     if (grouped) {
-        const size_t dense_bytes = (size_t)m_dense * p * EXP_REC_WORDS * 4;
+        const size_t dense_bytes = (size_t)m_dense * p * EXP_BYTES;
         if (int rc = dense.get(ctx, dense_bytes ? dense_bytes : 4)) return rc;
         if (int rc = expand_group_filters_launch(ctx, s, d_w, dense.p, st)) return rc;
     }
@@ -1594,14 +1631,10 @@ int conv2d_run(cofhe_hip_ctx *ctx, const void *d_w, const void *d_cts, const voi
 // records), the zero exponent in the padding; 16-byte pieces when both pointers allow them.  s has no groups
 int gather_patch_exponents_launch(cofhe_hip_ctx *ctx, const ConvShape &s, const void *d_img, void *d_st, hipStream_t st) {
     const uint32_t n = conv_rows(s), m = conv_inner(s);
-    const bool vec16 = (((uintptr_t)d_img | (uintptr_t)d_st) & 15) == 0;
-    const uint64_t total = (uint64_t)n * m * (vec16 ? EXP_REC_WORDS / 4 : EXP_REC_WORDS);
-    if (total == 0) return COFHE_HIP_OK;
-    const unsigned blocks = (unsigned)std::min<uint64_t>((total + 255) / 256, 64u * NUM_CUS);       // grid-stride beyond that
-    ProfScope ps(ctx, "k_gather_patch_exponents", st);
-    hipLaunchKernelGGL(k_gather_patch_exponents, dim3(blocks), dim3(256), 0, st, s, (const uint32_t *)d_img, (uint32_t *)d_st, n, m, vec16 ? 1u : 0u);
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    const PieceGrid g = piece_grid((uint64_t)n * m, EXP_REC_WORDS, 256, {d_img, d_st});
+    if (g.total == 0) return COFHE_HIP_OK;
+    return launch(ctx, "k_gather_patch_exponents", k_gather_patch_exponents, g.blocks, 256, st, s, (const uint32_t *)d_img, (uint32_t *)d_st, n, m,
+                  g.flag());
 }
 // what the two entry points with a PLAINTEXT image check before the context or a pointer is looked at: the geometry, and that
 // it has no groups (with groups the patch matrix differs per column group); fills Ho, Wo
@@ -1616,23 +1649,22 @@ ConvShape pool_shape_of(const cofhe_hip_conv2d_geometry &a) {
     s.groups = s.C ? s.C : 1;
     return s;
 }
-}  // namespace
-
-int cofhe_hip_conv2d_out_shape(const cofhe_hip_conv2d_shape *shape, uint32_t *Ho, uint32_t *Wo) {
-    if (!shape || !Ho || !Wo) return fail(COFHE_HIP_EINVAL, "null argument");
-    ConvShape s = conv_shape_of(*shape);
+// the body of the two out_shape entries
+int conv_out_shape(ConvShape s, uint32_t *Ho, uint32_t *Wo) {
     if (const char *why = conv_shape_check(s)) return fail(COFHE_HIP_EINVAL, why);
     *Ho = s.Ho;
     *Wo = s.Wo;
     return COFHE_HIP_OK;
 }
+}  // namespace
+
+int cofhe_hip_conv2d_out_shape(const cofhe_hip_conv2d_shape *shape, uint32_t *Ho, uint32_t *Wo) {
+    if (!shape || !Ho || !Wo) return fail(COFHE_HIP_EINVAL, "null argument");
+    return conv_out_shape(conv_shape_of(*shape), Ho, Wo);
+}
 int cofhe_hip_conv2d_geometry_out_shape(const cofhe_hip_conv2d_geometry *geometry, uint32_t *Ho, uint32_t *Wo) {
     if (!geometry || !Ho || !Wo) return fail(COFHE_HIP_EINVAL, "null argument");
-    ConvShape s = conv_geometry_of(*geometry);
-    if (const char *why = conv_shape_check(s)) return fail(COFHE_HIP_EINVAL, why);
-    *Ho = s.Ho;
-    *Wo = s.Wo;
-    return COFHE_HIP_OK;
+    return conv_out_shape(conv_geometry_of(*geometry), Ho, Wo);
 }
 
 int cofhe_hip_conv2d_plain_ct_records(cofhe_hip_ctx *ctx, const void *d_w, const void *d_cts, const void *d_zero, void *d_out,
@@ -1656,36 +1688,31 @@ int cofhe_hip_sum_pool2d_records(cofhe_hip_ctx *ctx, const void *d_cts, const vo
     if (const char *why = conv_shape_check(s)) return fail(COFHE_HIP_EINVAL, why);
     const uint64_t nout = (uint64_t)conv_rows(s) * s.Co;
     if (nout == 0) return COFHE_HIP_OK;
-    const size_t ct_bytes = (size_t)2 * REC_WORDS * 4;
-    if (overlaps(d_out, nout * ct_bytes, d_cts, (size_t)s.B * s.H * s.W * s.C * ct_bytes) || overlaps(d_out, nout * ct_bytes, d_zero, ct_bytes))
+    if (!clear_of({d_out, nout * CT_BYTES}, {{d_cts, (size_t)s.B * s.H * s.W * s.C * CT_BYTES}, {d_zero, CT_BYTES}}))
         return fail(COFHE_HIP_EINVAL, "sum_pool2d: the output overlaps an input");
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    const size_t n_w = (size_t)conv_inner(s) * s.Co, rec_bytes = (size_t)EXP_REC_WORDS * 4;
-    DevBuf ones;
-    ones.stream = stream;
-    if (int rc = ones.get(ctx, n_w * rec_bytes)) return rc;
-    HIPCHK(hipMemsetAsync(ones.p, 0, n_w * rec_bytes, st));
-    HIPCHK(hipMemset2DAsync(ones.p, rec_bytes, 1, 1, n_w, st));         // one byte per record: magnitude 1, sign word 0
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
+    const size_t n_w = (size_t)conv_inner(s) * s.Co;
+    DevBuf ones(stream);
+    if (int rc = ones.get(ctx, n_w * EXP_BYTES)) return rc;
+    HIPCHK(hipMemsetAsync(ones.p, 0, n_w * EXP_BYTES, st));
+    HIPCHK(hipMemset2DAsync(ones.p, EXP_BYTES, 1, 1, n_w, st));         // one byte per record: magnitude 1, sign word 0
     return conv2d_run(ctx, ones.p, d_cts, d_zero, d_out, s, stream);
 }
 
 int cofhe_hip_matmul_plain_plain_records(cofhe_hip_ctx *ctx, const void *d_a, const void *d_b, void *d_out, uint32_t n, uint32_t m, uint32_t p,
                                          uint32_t kbits, void *stream) {
-    if (kbits == 0 || kbits > 32u * PMM_MAX_LIMBS || 2 * kbits + 1 > (uint32_t)PLIMBS * 32) return fail(COFHE_HIP_EINVAL, "k out of range");
+    if (!k_in_range(kbits)) return fail(COFHE_HIP_EINVAL, "k out of range");
     if ((uint64_t)n * p == 0) return COFHE_HIP_OK;
-    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4;
-    if (overlaps(d_out, (size_t)n * p * exp_bytes, d_a, (size_t)n * m * exp_bytes) ||
-        overlaps(d_out, (size_t)n * p * exp_bytes, d_b, (size_t)m * p * exp_bytes))
+    if (!clear_of({d_out, (size_t)n * p * EXP_BYTES}, {{d_a, (size_t)n * m * EXP_BYTES}, {d_b, (size_t)m * p * EXP_BYTES}}))
         return fail(COFHE_HIP_EINVAL, "matmul_plain_plain: the output overlaps an input");
     const uint32_t gx = (p + PMM_TILE - 1) / PMM_TILE, gy = (n + PMM_TILE - 1) / PMM_TILE;
     if (gy > 65535u) return fail(COFHE_HIP_EINVAL, "work size out of range");
-    HIPCHK(hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(k_plain_matmul, dim3(gx, gy), dim3(PMM_THREADS), 0, (hipStream_t)stream, (const uint32_t *)d_a, (const uint32_t *)d_b,
-                       (uint32_t *)d_out, n, m, p, kbits);
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
+    return launch(ctx, nullptr, k_plain_matmul, dim3(gx, gy), PMM_THREADS, st, (const uint32_t *)d_a, (const uint32_t *)d_b, (uint32_t *)d_out, n, m,
+                  p, kbits);
 }
 
 // the one launch site of k_plain_conv2d
@@ -1694,20 +1721,17 @@ int cofhe_hip_conv2d_plain_plain_records(cofhe_hip_ctx *ctx, const void *d_img, 
     if (!geometry) return fail(COFHE_HIP_EINVAL, "null argument");
     ConvShape s = conv_geometry_of(*geometry);
     if (const char *why = conv_plain_image_check(s)) return fail(COFHE_HIP_EINVAL, why);
-    if (kbits == 0 || kbits > 32u * PMM_MAX_LIMBS || 2 * kbits + 1 > (uint32_t)PLIMBS * 32) return fail(COFHE_HIP_EINVAL, "k out of range");
+    if (!k_in_range(kbits)) return fail(COFHE_HIP_EINVAL, "k out of range");
     const uint32_t n = conv_rows(s), m = conv_inner(s), p = s.Co;
     if ((uint64_t)n * p == 0) return COFHE_HIP_OK;
-    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4, out_bytes = (size_t)n * p * exp_bytes;
-    if (overlaps(d_out, out_bytes, d_img, (size_t)s.B * s.H * s.W * s.C * exp_bytes) || overlaps(d_out, out_bytes, d_w, (size_t)m * p * exp_bytes))
+    if (!clear_of({d_out, (size_t)n * p * EXP_BYTES}, {{d_img, (size_t)s.B * s.H * s.W * s.C * EXP_BYTES}, {d_w, (size_t)m * p * EXP_BYTES}}))
         return fail(COFHE_HIP_EINVAL, "conv2d_plain_plain: the output overlaps an input");
     const uint32_t gx = (n + PMM_TILE - 1) / PMM_TILE, gy = (p + PMM_TILE - 1) / PMM_TILE;
     if (gy > 65535u) return fail(COFHE_HIP_EINVAL, "work size out of range");
-    HIPCHK(hipSetDevice(ctx->device));
-    ProfScope ps(ctx, "k_plain_conv2d", (hipStream_t)stream);
-    hipLaunchKernelGGL(k_plain_conv2d, dim3(gx, gy), dim3(PMM_THREADS), 0, (hipStream_t)stream, s, (const uint32_t *)d_img, (const uint32_t *)d_w,
-                       (uint32_t *)d_out, kbits);
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
+    return launch(ctx, "k_plain_conv2d", k_plain_conv2d, dim3(gx, gy), PMM_THREADS, st, s, (const uint32_t *)d_img, (const uint32_t *)d_w,
+                  (uint32_t *)d_out, kbits);
 }
 
 // Needs no workspace plan of its own, like cofhe_hip_matmul_plain_ct_records: the transposed patch matrix of the image is
@@ -1719,17 +1743,16 @@ int cofhe_hip_conv2d_ct_filters_records(cofhe_hip_ctx *ctx, const void *d_img_ex
     if (const char *why = conv_plain_image_check(s)) return fail(COFHE_HIP_EINVAL, why);      // m < 2^21 and the launch limit among it
     const uint32_t n = conv_rows(s), m = conv_inner(s), p = s.Co;
     if ((uint64_t)n * p == 0) return COFHE_HIP_OK;
-    const size_t ct_bytes = (size_t)2 * REC_WORDS * 4, exp_bytes = (size_t)EXP_REC_WORDS * 4, out_bytes = (size_t)n * p * ct_bytes;
-    if (overlaps(d_out, out_bytes, d_img_exps, (size_t)s.B * s.H * s.W * s.C * exp_bytes) ||
-        overlaps(d_out, out_bytes, d_filters_cts, (size_t)m * p * ct_bytes) || overlaps(d_out, out_bytes, d_zero, ct_bytes))
+    if (!clear_of({d_out, (size_t)n * p * CT_BYTES},
+                  {{d_img_exps, (size_t)s.B * s.H * s.W * s.C * EXP_BYTES}, {d_filters_cts, (size_t)m * p * CT_BYTES}, {d_zero, CT_BYTES}}))
         return fail(COFHE_HIP_EINVAL, "conv2d_ct_filters: the output overlaps an input");
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t st_bytes = (size_t)n * m * exp_bytes;
-    DevBuf s_t;                                  // S^T (m x n): the patch matrix of the image, transposed
-    s_t.stream = stream;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
+    const size_t st_bytes = (size_t)n * m * EXP_BYTES;
+    DevBuf s_t(stream);                          // S^T (m x n): the patch matrix of the image, transposed
     if (int rc = s_t.get(ctx, st_bytes ? st_bytes : 4)) return rc;
-    if (int rc = gather_patch_exponents_launch(ctx, s, d_img_exps, s_t.p, (hipStream_t)stream)) return rc;
+    if (int rc = gather_patch_exponents_launch(ctx, s, d_img_exps, s_t.p, st)) return rc;
     return plain_ct_transposed(ctx, s_t.p, d_filters_cts, d_zero, d_out, n, m, p, stream);
 }
 
@@ -1741,43 +1764,31 @@ int cofhe_hip_pow_dot_records(cofhe_hip_ctx *ctx, const void *d_bases, const voi
     if (n_ct == 0) return COFHE_HIP_OK;
     if (!d_bases || !d_exps || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
     if (n_ct > (1ull << 36)) return fail(COFHE_HIP_EINVAL, "work size out of range");
-    const size_t out_bytes = (size_t)n_ct * 2 * REC_WORDS * 4, exp_bytes = (size_t)n_ct * EXP_REC_WORDS * 4;
     // k_pow_dot keeps the running product in the output record
-    if (overlaps(d_out, out_bytes, d_bases, d * out_bytes) || overlaps(d_out, out_bytes, d_exps, d * exp_bytes))
+    if (!clear_of({d_out, n_ct * CT_BYTES}, {{d_bases, d * n_ct * CT_BYTES}, {d_exps, d * n_ct * EXP_BYTES}}))
         return fail(COFHE_HIP_EINVAL, "pow_dot: the output overlaps an input");
     unsigned blocks;
     if (int rc = compose_blocks(2 * n_ct, &blocks)) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    {
-        ProfScope ps(ctx, "k_pow_dot", st);
-        hipLaunchKernelGGL(k_pow_dot, dim3(blocks), dim3(WG_BLOCK), 0, st, (const uint32_t *)d_bases, (const uint32_t *)d_exps, (uint32_t *)d_out,
-                           n_ct, d, (const uint32_t *)ctx->d_one, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
-    }
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
+    return launch(ctx, "k_pow_dot", k_pow_dot, blocks, WG_BLOCK, st, (const uint32_t *)d_bases, (const uint32_t *)d_exps, (uint32_t *)d_out, n_ct, d,
+                  (const uint32_t *)ctx->d_one, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
 }
 
 int cofhe_hip_poly_shift_records(cofhe_hip_ctx *ctx, const void *d_coef, const void *d_x, void *d_q, uint64_t n, uint32_t d, uint32_t kbits,
                                  void *stream) {
-    if (kbits == 0 || kbits > 32u * PMM_MAX_LIMBS || 2 * kbits + 1 > (uint32_t)PLIMBS * 32) return fail(COFHE_HIP_EINVAL, "k out of range");
+    if (!k_in_range(kbits)) return fail(COFHE_HIP_EINVAL, "k out of range");
     if (d > (uint32_t)POLY_MAX_DEGREE) return fail(COFHE_HIP_EINVAL, "poly_shift: degree beyond 8");
     if (n == 0) return COFHE_HIP_OK;
     if (!d_coef || !d_x || !d_q) return fail(COFHE_HIP_EINVAL, "null argument");
     const uint64_t blocks = (n + PSH_THREADS - 1) / PSH_THREADS;
     if (blocks > 0x7FFFFFFFull) return fail(COFHE_HIP_EINVAL, "work size out of range");
-    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4;
-    if (overlaps(d_q, (size_t)(d + 1) * n * exp_bytes, d_coef, (size_t)(d + 1) * exp_bytes) || overlaps(d_q, (size_t)(d + 1) * n * exp_bytes, d_x, n * exp_bytes))
+    if (!clear_of({d_q, (size_t)(d + 1) * n * EXP_BYTES}, {{d_coef, (size_t)(d + 1) * EXP_BYTES}, {d_x, n * EXP_BYTES}}))
         return fail(COFHE_HIP_EINVAL, "poly_shift: the output overlaps an input");
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    {
-        ProfScope ps(ctx, "k_poly_shift", st);
-        hipLaunchKernelGGL(k_poly_shift, dim3((unsigned)blocks), dim3(PSH_THREADS), 0, st, (const uint32_t *)d_coef, (const uint32_t *)d_x,
-                           (uint32_t *)d_q, n, d, kbits);
-    }
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
+    return launch(ctx, "k_poly_shift", k_poly_shift, (unsigned)blocks, PSH_THREADS, st, (const uint32_t *)d_coef, (const uint32_t *)d_x,
+                  (uint32_t *)d_q, n, d, kbits);
 }
 
 // Needs no workspace plan of its own: the d + 1 exponent tensors q_0 .. q_d are one block of the block cache, and the plaintext
@@ -1790,15 +1801,12 @@ int cofhe_hip_poly_close_records(cofhe_hip_ctx *ctx, const void *d_coef, const v
     if (int rc = comb_check(3, n_ct, 0, kbits, 0, 0)) return rc;
     if (n_ct == 0) return COFHE_HIP_OK;
     if (!d_coef || !d_e || !d_powers || !f_record || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
-    const size_t out_bytes = (size_t)n_ct * 2 * REC_WORDS * 4, exp_bytes = (size_t)EXP_REC_WORDS * 4;
-    if (overlaps(d_out, out_bytes, d_powers, d * out_bytes) || overlaps(d_out, out_bytes, d_coef, (d + 1) * exp_bytes) ||
-        overlaps(d_out, out_bytes, d_e, n_ct * exp_bytes))
+    if (!clear_of({d_out, n_ct * CT_BYTES}, {{d_powers, d * n_ct * CT_BYTES}, {d_coef, (d + 1) * EXP_BYTES}, {d_e, n_ct * EXP_BYTES}}))
         return fail(COFHE_HIP_EINVAL, "poly_close: the output overlaps an input");
-    DevBuf q;                                     // q_0 | q_1 .. q_d, power-major
-    q.stream = stream;
-    if (int rc = q.get(ctx, (size_t)(d + 1) * n_ct * exp_bytes)) return rc;
+    DevBuf q(stream);                             // q_0 | q_1 .. q_d, power-major
+    if (int rc = q.get(ctx, (size_t)(d + 1) * n_ct * EXP_BYTES)) return rc;
     if (int rc = cofhe_hip_poly_shift_records(ctx, d_coef, d_e, q.p, n_ct, d, kbits, stream)) return rc;
-    if (int rc = cofhe_hip_pow_dot_records(ctx, d_powers, (const uint8_t *)q.p + n_ct * exp_bytes, d_out, n_ct, d, stream)) return rc;
+    if (int rc = cofhe_hip_pow_dot_records(ctx, d_powers, (const uint8_t *)q.p + n_ct * EXP_BYTES, d_out, n_ct, d, stream)) return rc;
     return cofhe_hip_add_plain_records(ctx, d_out, q.p, nullptr, nullptr, nullptr, f_record, d_out, n_ct, kbits, 0, stream);
 }
 
@@ -1807,24 +1815,18 @@ static_assert(COFHE_HIP_DIV_MAX_KBITS == PDV_MAX_KBITS, "the header's bound is t
 // touches no shared state of the context but the status word, which the kernel sets atomically: no lock
 int cofhe_hip_divfloor_plain_records(cofhe_hip_ctx *ctx, const void *d_v, const void *d_div, uint64_t n_div, void *d_q, uint64_t n,
                                      uint32_t kbits, void *stream) {
-    if (kbits == 0 || kbits > PDV_MAX_KBITS) return fail(COFHE_HIP_EINVAL, "k out of range");
+    if (!k_in_range(kbits)) return fail(COFHE_HIP_EINVAL, "k out of range");
     if (n_div == 0 || n % n_div != 0) return fail(COFHE_HIP_EINVAL, "divfloor: the element count is a multiple of the divisor count, which is not 0");
     if (n == 0) return COFHE_HIP_OK;
     if (!d_v || !d_div || !d_q) return fail(COFHE_HIP_EINVAL, "null argument");
     const uint64_t blocks = (n + PDV_GROUPS - 1) / PDV_GROUPS;
     if (blocks > 0x7FFFFFFFull) return fail(COFHE_HIP_EINVAL, "work size out of range");
-    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4;
-    if (overlaps(d_q, n * exp_bytes, d_v, n * exp_bytes) || overlaps(d_q, n * exp_bytes, d_div, n_div * exp_bytes))
+    if (!clear_of({d_q, n * EXP_BYTES}, {{d_v, n * EXP_BYTES}, {d_div, n_div * EXP_BYTES}}))
         return fail(COFHE_HIP_EINVAL, "divfloor: the output overlaps an input");
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    {
-        ProfScope ps(ctx, "k_plain_divfloor", st);
-        hipLaunchKernelGGL(k_plain_divfloor, dim3((unsigned)blocks), dim3(PDV_THREADS), 0, st, (const uint32_t *)d_v, (const uint32_t *)d_div,
-                           n_div, (uint32_t *)d_q, n, kbits, ctx->d_status);
-    }
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
+    return launch(ctx, "k_plain_divfloor", k_plain_divfloor, (unsigned)blocks, PDV_THREADS, st, (const uint32_t *)d_v, (const uint32_t *)d_div, n_div,
+                  (uint32_t *)d_q, n, kbits, ctx->d_status);
 }
 
 // Needs no workspace plan of its own: the quotients of the opened values are one block of the block cache, and the plaintext
@@ -1832,18 +1834,15 @@ int cofhe_hip_divfloor_plain_records(cofhe_hip_ctx *ctx, const void *d_v, const 
 int cofhe_hip_div_close_records(cofhe_hip_ctx *ctx, const void *d_e, const void *d_div, uint64_t n_div, const void *d_rq, const uint32_t *f_record,
                                 void *d_out, uint64_t n_ct, uint32_t kbits, void *stream) {
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (kbits == 0 || kbits > PDV_MAX_KBITS) return fail(COFHE_HIP_EINVAL, "k out of range");
+    if (!k_in_range(kbits)) return fail(COFHE_HIP_EINVAL, "k out of range");
     if (n_div == 0 || n_ct % n_div != 0) return fail(COFHE_HIP_EINVAL, "div_close: the element count is a multiple of the divisor count, which is not 0");
     if (int rc = comb_check(3, n_ct, 0, kbits, 0, 0)) return rc;
     if (n_ct == 0) return COFHE_HIP_OK;
     if (!d_e || !d_div || !d_rq || !f_record || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
-    const size_t out_bytes = (size_t)n_ct * 2 * REC_WORDS * 4, exp_bytes = (size_t)EXP_REC_WORDS * 4;
-    if (overlaps(d_out, out_bytes, d_rq, out_bytes) || overlaps(d_out, out_bytes, d_e, n_ct * exp_bytes) ||
-        overlaps(d_out, out_bytes, d_div, n_div * exp_bytes))
+    if (!clear_of({d_out, n_ct * CT_BYTES}, {{d_rq, n_ct * CT_BYTES}, {d_e, n_ct * EXP_BYTES}, {d_div, n_div * EXP_BYTES}}))
         return fail(COFHE_HIP_EINVAL, "div_close: the output overlaps an input");
-    DevBuf q;                                     // e_q = floor(s(e) / D)
-    q.stream = stream;
-    if (int rc = q.get(ctx, n_ct * exp_bytes)) return rc;
+    DevBuf q(stream);                             // e_q = floor(s(e) / D)
+    if (int rc = q.get(ctx, n_ct * EXP_BYTES)) return rc;
     if (int rc = cofhe_hip_divfloor_plain_records(ctx, d_e, d_div, n_div, q.p, n_ct, kbits, stream)) return rc;
     return cofhe_hip_add_plain_records(ctx, d_rq, q.p, nullptr, nullptr, nullptr, f_record, d_out, n_ct, kbits, 0, stream);
 }
@@ -1854,7 +1853,7 @@ namespace {
 // what every exact-division entry point refuses before it looks at a pointer: k, the tuple length, and element i reading
 // divisor i mod n_div
 int divx_check(uint32_t kbits, uint32_t rows, uint64_t n_div, uint64_t n) {
-    if (kbits == 0 || kbits > PDV_MAX_KBITS) return fail(COFHE_HIP_EINVAL, "k out of range");
+    if (!k_in_range(kbits)) return fail(COFHE_HIP_EINVAL, "k out of range");
     if (rows == 0 || rows > DIVX_MAX_ROWS) return fail(COFHE_HIP_EINVAL, "divx: a tuple has 1 <= rows <= 4096 entries");
     if (n_div == 0 || n % n_div != 0) return fail(COFHE_HIP_EINVAL, "divx: the element count is a multiple of the divisor count, which is not 0");
     if (n > (1ull << 36) / DIVX_MAX_ROWS) return fail(COFHE_HIP_EINVAL, "divx: too many items");
@@ -1867,20 +1866,14 @@ int cofhe_hip_divmod_plain_records(cofhe_hip_ctx *ctx, const void *d_v, const vo
     if (int rc = divx_check(kbits, rows, n_div, n)) return rc;
     if (n == 0) return COFHE_HIP_OK;
     if (!d_v || !d_div || !d_q || !d_rem) return fail(COFHE_HIP_EINVAL, "null argument");
-    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4;
-    if (overlaps(d_q, n * exp_bytes, d_v, n * exp_bytes) || overlaps(d_q, n * exp_bytes, d_div, n_div * exp_bytes) ||
-        overlaps(d_rem, n * 4, d_v, n * exp_bytes) || overlaps(d_rem, n * 4, d_div, n_div * exp_bytes) || overlaps(d_rem, n * 4, d_q, n * exp_bytes))
+    const Span v{d_v, n * EXP_BYTES}, div{d_div, n_div * EXP_BYTES}, q{d_q, n * EXP_BYTES}, rem{d_rem, n * 4};
+    if (!clear_of(q, {v, div}) || !clear_of(rem, {v, div}) || !clear_of(rem, {q}))
         return fail(COFHE_HIP_EINVAL, "divmod: an output overlaps an input or the other output");
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
     const unsigned blocks = (unsigned)((n + PDV_GROUPS - 1) / PDV_GROUPS);       // n <= 2^24: divx_check
-    {
-        ProfScope ps(ctx, "k_plain_divmod", st);
-        hipLaunchKernelGGL(k_plain_divmod, dim3(blocks), dim3(PDV_THREADS), 0, st, (const uint32_t *)d_v, (const uint32_t *)d_div, n_div,
-                           (uint32_t *)d_q, (uint32_t *)d_rem, n, rows, kbits, ctx->d_status);
-    }
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    return launch(ctx, "k_plain_divmod", k_plain_divmod, blocks, PDV_THREADS, st, (const uint32_t *)d_v, (const uint32_t *)d_div, n_div,
+                  (uint32_t *)d_q, (uint32_t *)d_rem, n, rows, kbits, ctx->d_status);
 }
 
 // the blocks of the divmod pass are one block of the block cache; the lock is held for it
@@ -1890,30 +1883,17 @@ int cofhe_hip_divx_rows_records(cofhe_hip_ctx *ctx, const void *d_r, const void 
     if (int rc = divx_check(kbits, rows, n_div, n)) return rc;
     if (n == 0) return COFHE_HIP_OK;
     if (!d_r || !d_div || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
-    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4, out_bytes = n * rows * exp_bytes;
-    if (overlaps(d_out, out_bytes, d_r, n * exp_bytes) || overlaps(d_out, out_bytes, d_div, n_div * exp_bytes))
+    if (!clear_of({d_out, n * rows * EXP_BYTES}, {{d_r, n * EXP_BYTES}, {d_div, n_div * EXP_BYTES}}))
         return fail(COFHE_HIP_EINVAL, "divx_rows: the output overlaps an input");
-    DevBuf prep;                                  // q(r) | q(r) + 1 | (D - m(r), D) per element
-    prep.stream = stream;
+    DevBuf prep(stream);                          // q(r) | q(r) + 1 | (D - m(r), D) per element
     if (int rc = prep.get(ctx, n * DIVX_PREP_WORDS * 4)) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    {
-        ProfScope ps(ctx, "k_divx_prep", st);
-        hipLaunchKernelGGL(k_divx_prep, dim3((unsigned)((n + PDV_GROUPS - 1) / PDV_GROUPS)), dim3(PDV_THREADS), 0, st, (const uint32_t *)d_r,
-                           (const uint32_t *)d_div, n_div, (uint32_t *)prep.p, n, rows, kbits, ctx->d_status);
-    }
-    HIPCHK(hipGetLastError());
-    const bool vec16 = (((uintptr_t)d_out | (uintptr_t)prep.p) & 15) == 0;
-    const uint64_t total = n * rows * (vec16 ? EXP_REC_WORDS / 4 : EXP_REC_WORDS);
-    const unsigned blocks = (unsigned)std::min<uint64_t>((total + DIVX_ROWS_THREADS - 1) / DIVX_ROWS_THREADS, 64u * NUM_CUS);       // grid-stride beyond that
-    {
-        ProfScope ps(ctx, "k_divx_rows", st);
-        hipLaunchKernelGGL(k_divx_rows, dim3(blocks), dim3(DIVX_ROWS_THREADS), 0, st, (const uint32_t *)prep.p, (uint32_t *)d_out, n, rows,
-                           vec16 ? 1u : 0u);
-    }
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
+    if (int rc = launch(ctx, "k_divx_prep", k_divx_prep, (unsigned)((n + PDV_GROUPS - 1) / PDV_GROUPS), PDV_THREADS, st, (const uint32_t *)d_r,
+                        (const uint32_t *)d_div, n_div, (uint32_t *)prep.p, n, rows, kbits, ctx->d_status))
+        return rc;
+    const PieceGrid g = piece_grid(n * rows, EXP_REC_WORDS, DIVX_ROWS_THREADS, {d_out, prep.p});
+    return launch(ctx, "k_divx_rows", k_divx_rows, g.blocks, DIVX_ROWS_THREADS, st, (const uint32_t *)prep.p, (uint32_t *)d_out, n, rows, g.flag());
 }
 
 // Needs no workspace plan of its own: the rows are one block of the block cache, and the fresh encryption that follows carves
@@ -1926,15 +1906,11 @@ int cofhe_hip_divx_tuples_records(cofhe_hip_ctx *ctx, const void *d_r, const voi
     if (int rc = comb_check(1, n * rows, 0, kbits, 0, 0)) return rc;
     if (n == 0) return COFHE_HIP_OK;
     if (!d_r || !d_div || !d_rho || !h_record || !pk_record || !f_record || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
-    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4, rows_bytes = n * rows * exp_bytes, out_bytes = n * rows * 2 * REC_WORDS * 4;
-    if (overlaps(d_out, out_bytes, d_r, n * exp_bytes) || overlaps(d_out, out_bytes, d_div, n_div * exp_bytes) ||
-        overlaps(d_out, out_bytes, d_rho, rows_bytes))
+    if (!clear_of({d_out, n * rows * CT_BYTES}, {{d_r, n * EXP_BYTES}, {d_div, n_div * EXP_BYTES}, {d_rho, n * rows * EXP_BYTES}}))
         return fail(COFHE_HIP_EINVAL, "divx_tuples: the output overlaps an input");
-    DevBuf rws;                                   // T_j = q(r) + [m(r) + j >= D], the plaintexts of the tuples
-    rws.stream = stream;
-    if (int rc = rws.get(ctx, rows_bytes)) return rc;
-    if (int rc = cofhe_hip_divx_rows_records(ctx, d_r, d_div, n_div, rws.p, n, rows, kbits, stream)) return rc;
-    return cofhe_hip_encrypt_fresh_records(ctx, rws.p, d_rho, h_record, pk_record, f_record, d_out, n * rows, kbits, stream);
+    // T_j = q(r) + [m(r) + j >= D], the plaintexts of the tuples
+    return encrypt_rows(ctx, n * rows, kbits, d_rho, h_record, pk_record, f_record, d_out, stream,
+                        [&](void *d_rows) { return cofhe_hip_divx_rows_records(ctx, d_r, d_div, n_div, d_rows, n, rows, kbits, stream); });
 }
 
 // Needs no workspace plan of its own: the quotients and the remainders of the opened values are one block of the block cache,
@@ -1946,35 +1922,28 @@ int cofhe_hip_divx_close_records(cofhe_hip_ctx *ctx, const void *d_e, const void
     if (int rc = comb_check(3, n, 0, kbits, 0, 0)) return rc;
     if (n == 0) return COFHE_HIP_OK;
     if (!d_e || !d_div || !d_tuples || !f_record || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
-    const size_t ct_bytes = (size_t)2 * REC_WORDS * 4, out_bytes = n * ct_bytes, exp_bytes = (size_t)EXP_REC_WORDS * 4;
-    if (overlaps(d_out, out_bytes, d_tuples, n * rows * ct_bytes) || overlaps(d_out, out_bytes, d_e, n * exp_bytes) ||
-        overlaps(d_out, out_bytes, d_div, n_div * exp_bytes))
+    if (!clear_of({d_out, n * CT_BYTES}, {{d_tuples, n * rows * CT_BYTES}, {d_e, n * EXP_BYTES}, {d_div, n_div * EXP_BYTES}}))
         return fail(COFHE_HIP_EINVAL, "divx_close: the output overlaps an input");
-    DevBuf qm;                                    // q(e): n exponent records, then m(e): n words
-    qm.stream = stream;
-    if (int rc = qm.get(ctx, n * exp_bytes + n * 4)) return rc;
-    uint32_t *d_rem = (uint32_t *)((uint8_t *)qm.p + n * exp_bytes);
+    DevBuf qm(stream);                            // q(e): n exponent records, then m(e): n words
+    if (int rc = qm.get(ctx, n * EXP_BYTES + n * 4)) return rc;
+    uint32_t *d_rem = (uint32_t *)((uint8_t *)qm.p + n * EXP_BYTES);
     if (int rc = cofhe_hip_divmod_plain_records(ctx, d_e, d_div, n_div, qm.p, d_rem, n, rows, kbits, stream)) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    const bool vec16 = (((uintptr_t)d_tuples | (uintptr_t)d_out) & 15) == 0;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
     const unsigned blocks = (unsigned)((n + DIVX_SELECT_WAVES - 1) / DIVX_SELECT_WAVES);        // n <= 2^24: divx_check
-    {
-        ProfScope ps(ctx, "k_divx_select", st);
-        hipLaunchKernelGGL(k_divx_select, dim3(blocks), dim3(DIVX_SELECT_THREADS), 0, st, (const uint32_t *)d_rem, (const uint32_t *)d_tuples,
-                           (uint32_t *)d_out, n, rows, vec16 ? 1u : 0u, ctx->d_status);
-    }
-    HIPCHK(hipGetLastError());
+    if (int rc = launch(ctx, "k_divx_select", k_divx_select, blocks, DIVX_SELECT_THREADS, st, (const uint32_t *)d_rem, (const uint32_t *)d_tuples,
+                        (uint32_t *)d_out, n, rows, aligned16({d_tuples, d_out}) ? 1u : 0u, ctx->d_status))
+        return rc;
     return cofhe_hip_add_plain_records(ctx, d_out, qm.p, nullptr, nullptr, nullptr, f_record, d_out, n, kbits, 0, stream);
 }
 
 // host only: the tuples of opened values of shape S are a tensor of shape S + [rows]
 int cofhe_hip_divx_shape(uint32_t ndim_e, const uint32_t *shape_e, uint32_t ndim_t, const uint32_t *shape_t, uint32_t *rows) {
     if (!rows || (ndim_e && !shape_e) || (ndim_t && !shape_t)) return fail(COFHE_HIP_EINVAL, "null argument");
-    if (ndim_e > 7 || ndim_t != ndim_e + 1 || (ndim_e && memcmp(shape_t, shape_e, 4 * ndim_e) != 0) || shape_t[ndim_t - 1] == 0 ||
-        shape_t[ndim_t - 1] > DIVX_MAX_ROWS)
+    const uint32_t *tail;
+    if (!tail_shape(ndim_e, shape_e, ndim_t, shape_t, 1, &tail) || tail[0] == 0 || tail[0] > DIVX_MAX_ROWS)
         return fail(COFHE_HIP_ESHAPE, "divx_close: the tuples are a ciphertext tensor of e's shape and a last dimension of 1 <= rows <= 4096");
-    *rows = shape_t[ndim_t - 1];
+    *rows = tail[0];
     return COFHE_HIP_OK;
 }
 
@@ -1996,21 +1965,13 @@ int cofhe_hip_lut_rotate_records(cofhe_hip_ctx *ctx, const void *d_table, uint64
     if (int rc = lut_check(bits, n_tab, n)) return rc;
     if (n == 0) return COFHE_HIP_OK;
     if (!d_table || !d_r || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
-    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4, out_bytes = (n << bits) * exp_bytes;
-    if (overlaps(d_out, out_bytes, d_table, (n_tab << bits) * exp_bytes) || overlaps(d_out, out_bytes, d_r, n * exp_bytes))
+    if (!clear_of({d_out, (n << bits) * EXP_BYTES}, {{d_table, (n_tab << bits) * EXP_BYTES}, {d_r, n * EXP_BYTES}}))
         return fail(COFHE_HIP_EINVAL, "lut_rotate: the output overlaps an input");
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    const bool vec16 = (((uintptr_t)d_table | (uintptr_t)d_out) & 15) == 0;
-    const uint64_t total = (n << bits) * (vec16 ? EXP_REC_WORDS / 4 : EXP_REC_WORDS);
-    const unsigned blocks = (unsigned)std::min<uint64_t>((total + 255) / 256, 64u * NUM_CUS);       // grid-stride beyond that
-    {
-        ProfScope ps(ctx, "k_lut_rotate", st);
-        hipLaunchKernelGGL(k_lut_rotate, dim3(blocks), dim3(256), 0, st, (const uint32_t *)d_table, n_tab, (const uint32_t *)d_r, (uint32_t *)d_out, n,
-                           bits, vec16 ? 1u : 0u);
-    }
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
+    const PieceGrid g = piece_grid(n << bits, EXP_REC_WORDS, 256, {d_table, d_out});
+    return launch(ctx, "k_lut_rotate", k_lut_rotate, g.blocks, 256, st, (const uint32_t *)d_table, n_tab, (const uint32_t *)d_r, (uint32_t *)d_out, n,
+                  bits, g.flag());
 }
 
 // Needs no workspace plan of its own: the rotated rows are one block of the block cache, and the fresh encryption that follows
@@ -2024,15 +1985,11 @@ int cofhe_hip_lut_tuples_records(cofhe_hip_ctx *ctx, const void *d_table, uint64
     if (int rc = comb_check(1, n << bits, 0, kbits, 0, 0)) return rc;
     if (n == 0) return COFHE_HIP_OK;
     if (!d_table || !d_r || !d_rho || !h_record || !pk_record || !f_record || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
-    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4, rows_bytes = (n << bits) * exp_bytes, out_bytes = (n << bits) * 2 * REC_WORDS * 4;
-    if (overlaps(d_out, out_bytes, d_table, (n_tab << bits) * exp_bytes) || overlaps(d_out, out_bytes, d_r, n * exp_bytes) ||
-        overlaps(d_out, out_bytes, d_rho, rows_bytes))
+    if (!clear_of({d_out, (n << bits) * CT_BYTES}, {{d_table, (n_tab << bits) * EXP_BYTES}, {d_r, n * EXP_BYTES}, {d_rho, (n << bits) * EXP_BYTES}}))
         return fail(COFHE_HIP_EINVAL, "lut_tuples: the output overlaps an input");
-    DevBuf rows;                                  // T_j = g[(j + r) mod 2^bits], the plaintexts of the tuples
-    rows.stream = stream;
-    if (int rc = rows.get(ctx, rows_bytes)) return rc;
-    if (int rc = cofhe_hip_lut_rotate_records(ctx, d_table, n_tab, d_r, rows.p, n, bits, stream)) return rc;
-    return cofhe_hip_encrypt_fresh_records(ctx, rows.p, d_rho, h_record, pk_record, f_record, d_out, n << bits, kbits, stream);
+    // T_j = g[(j + r) mod 2^bits], the plaintexts of the tuples
+    return encrypt_rows(ctx, n << bits, kbits, d_rho, h_record, pk_record, f_record, d_out, stream,
+                        [&](void *d_rows) { return cofhe_hip_lut_rotate_records(ctx, d_table, n_tab, d_r, d_rows, n, bits, stream); });
 }
 
 // touches no shared state of the context: no lock.  One wavefront per output ciphertext, 16-byte pieces when the tuples and the
@@ -2041,29 +1998,23 @@ int cofhe_hip_lut_select_records(cofhe_hip_ctx *ctx, const void *d_e, const void
     if (int rc = lut_check(bits, 1, n)) return rc;
     if (n == 0) return COFHE_HIP_OK;
     if (!d_e || !d_tuples || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
-    const size_t ct_bytes = (size_t)2 * REC_WORDS * 4, out_bytes = n * ct_bytes;
-    if (overlaps(d_out, out_bytes, d_e, n * EXP_REC_WORDS * 4) || overlaps(d_out, out_bytes, d_tuples, (n << bits) * ct_bytes))
+    if (!clear_of({d_out, n * CT_BYTES}, {{d_e, n * EXP_BYTES}, {d_tuples, (n << bits) * CT_BYTES}}))
         return fail(COFHE_HIP_EINVAL, "lut_select: the output overlaps an input");
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    const bool vec16 = (((uintptr_t)d_tuples | (uintptr_t)d_out) & 15) == 0;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
     const unsigned blocks = (unsigned)std::min<uint64_t>((n + LUT_SELECT_WAVES - 1) / LUT_SELECT_WAVES, 0x7FFFFFFFull);      // grid-stride beyond that
-    {
-        ProfScope ps(ctx, "k_lut_select", st);
-        hipLaunchKernelGGL(k_lut_select, dim3(blocks), dim3(LUT_SELECT_THREADS), 0, st, (const uint32_t *)d_e, (const uint32_t *)d_tuples,
-                           (uint32_t *)d_out, n, bits, vec16 ? 1u : 0u);
-    }
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    return launch(ctx, "k_lut_select", k_lut_select, blocks, LUT_SELECT_THREADS, st, (const uint32_t *)d_e, (const uint32_t *)d_tuples,
+                  (uint32_t *)d_out, n, bits, aligned16({d_tuples, d_out}) ? 1u : 0u);
 }
 
 // host only: the tuples of opened values of shape S are a tensor of shape S + [2^bits]
 int cofhe_hip_lut_tuples_shape_bits(uint32_t ndim_e, const uint32_t *shape_e, uint32_t ndim_t, const uint32_t *shape_t, uint32_t *bits) {
     if (!bits || (ndim_e && !shape_e) || (ndim_t && !shape_t)) return fail(COFHE_HIP_EINVAL, "null argument");
+    const uint32_t *tail;
     uint32_t b = 0;
-    if (ndim_t >= 1)
-        while (b <= LUT_MAX_BITS && (1u << b) != shape_t[ndim_t - 1]) b++;
-    if (ndim_e > 7 || ndim_t != ndim_e + 1 || (ndim_e && memcmp(shape_t, shape_e, 4 * ndim_e) != 0) || b == 0 || b > LUT_MAX_BITS)
+    if (tail_shape(ndim_e, shape_e, ndim_t, shape_t, 1, &tail))
+        while (b <= LUT_MAX_BITS && (1u << b) != tail[0]) b++;
+    if (b == 0 || b > LUT_MAX_BITS)          // b stays 0 for a tensor of another shape
         return fail(COFHE_HIP_ESHAPE, "lut_select: the tuples are a ciphertext tensor of e's shape and a last dimension of 2^bits, 1 <= bits <= 12");
     *bits = b;
     return COFHE_HIP_OK;
@@ -2207,19 +2158,14 @@ int cofhe_hip_view_records(cofhe_hip_ctx *ctx, const cofhe_hip_view *view, const
     if (n_box == 0) return COFHE_HIP_OK;
     if (!d_dst || (n_src && !d_src)) return fail(COFHE_HIP_EINVAL, "null argument");
     const size_t rec_bytes = (size_t)words * 4;
-    if (overlaps(d_dst, n_dst * rec_bytes, d_src, n_src * rec_bytes) || (d_fill && overlaps(d_dst, n_dst * rec_bytes, d_fill, rec_bytes)))
+    if (!clear_of({d_dst, n_dst * rec_bytes}, {{d_src, n_src * rec_bytes}, {d_fill, d_fill ? rec_bytes : 0}}))
         return fail(COFHE_HIP_EINVAL, "view_records: the destination overlaps the source or the fill record");
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    const bool vec16 = words % 4 == 0 && (((uintptr_t)d_src | (uintptr_t)d_fill | (uintptr_t)d_dst) & 15) == 0;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
+    const bool vec16 = words % 4 == 0 && aligned16({d_src, d_fill, d_dst});
     const unsigned blocks = view_blocks(ctx, n_box, vec16 ? words / 4 : words);
-    {
-        ProfScope ps(ctx, "k_view_records", st);
-        hipLaunchKernelGGL(k_view_records, dim3(blocks), dim3(VIEW_THREADS), 0, st, *view, (const uint32_t *)d_src, (const uint32_t *)d_fill,
-                           (uint32_t *)d_dst, words, vec16 ? 1u : 0u);
-    }
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    return launch(ctx, "k_view_records", k_view_records, blocks, VIEW_THREADS, st, *view, (const uint32_t *)d_src, (const uint32_t *)d_fill,
+                  (uint32_t *)d_dst, words, vec16 ? 1u : 0u);
 }
 
 int cofhe_hip_gather_records(cofhe_hip_ctx *ctx, const void *d_src, uint64_t n_src, const void *d_index, const void *d_fill, void *d_dst,
@@ -2230,20 +2176,14 @@ int cofhe_hip_gather_records(cofhe_hip_ctx *ctx, const void *d_src, uint64_t n_s
     if (n_out == 0) return COFHE_HIP_OK;
     if (!d_dst || !d_index || (n_src && !d_src)) return fail(COFHE_HIP_EINVAL, "null argument");
     const size_t rec_bytes = (size_t)words * 4, out_bytes = n_out * rec_bytes;
-    if (overlaps(d_dst, out_bytes, d_src, n_src * rec_bytes) || overlaps(d_dst, out_bytes, d_index, n_out * 4) ||
-        (d_fill && overlaps(d_dst, out_bytes, d_fill, rec_bytes)))
+    if (!clear_of({d_dst, out_bytes}, {{d_src, n_src * rec_bytes}, {d_index, n_out * 4}, {d_fill, d_fill ? rec_bytes : 0}}))
         return fail(COFHE_HIP_EINVAL, "gather_records: the destination overlaps the source, the indices or the fill record");
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    const bool vec16 = words % 4 == 0 && (((uintptr_t)d_src | (uintptr_t)d_fill | (uintptr_t)d_dst) & 15) == 0;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
+    const bool vec16 = words % 4 == 0 && aligned16({d_src, d_fill, d_dst});
     const unsigned blocks = view_blocks(ctx, n_out, vec16 ? words / 4 : words);
-    {
-        ProfScope ps(ctx, "k_gather_records", st);
-        hipLaunchKernelGGL(k_gather_records, dim3(blocks), dim3(VIEW_THREADS), 0, st, (const uint32_t *)d_src, n_src, (const uint32_t *)d_index,
-                           (const uint32_t *)d_fill, (uint32_t *)d_dst, n_out, words, vec16 ? 1u : 0u, ctx->d_status);
-    }
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    return launch(ctx, "k_gather_records", k_gather_records, blocks, VIEW_THREADS, st, (const uint32_t *)d_src, n_src, (const uint32_t *)d_index,
+                  (const uint32_t *)d_fill, (uint32_t *)d_dst, n_out, words, vec16 ? 1u : 0u, ctx->d_status);
 }
 
 // ---- piecewise-polynomial activations from one opened value (spline.hip) ---------------------------------------------------
@@ -2252,7 +2192,7 @@ namespace {
 // what every spline entry point refuses before it looks at a pointer: the window, the degree, the tuple size, and element i
 // reading table i mod n_tab
 int spline_check(uint32_t bits, uint32_t shift, uint32_t d, uint32_t kbits, uint64_t n_tab, uint64_t n) {
-    if (kbits == 0 || kbits > 32u * PMM_MAX_LIMBS - 1u) return fail(COFHE_HIP_EINVAL, "k out of range");
+    if (!k_in_range(kbits)) return fail(COFHE_HIP_EINVAL, "k out of range");
     if (!spline_shape_ok(bits, shift, d, kbits))
         return fail(COFHE_HIP_EINVAL, "spline: 2^bits pieces of degree d, bits >= 1, 1 <= d <= 8, 2^bits (d + 1) <= 4096, shift + bits <= k");
     if (n_tab == 0 || n % n_tab != 0) return fail(COFHE_HIP_EINVAL, "spline: the element count is a multiple of the table count, which is not 0");
@@ -2266,20 +2206,15 @@ int cofhe_hip_spline_rows_records(cofhe_hip_ctx *ctx, const void *d_pieces, uint
     if (int rc = spline_check(bits, shift, d, kbits, n_tab, n)) return rc;
     if (n == 0) return COFHE_HIP_OK;
     if (!d_pieces || !d_r || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
-    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4, row_bytes = (size_t)(d + 1) * exp_bytes, out_bytes = (n << bits) * row_bytes;
-    if (overlaps(d_out, out_bytes, d_pieces, (n_tab << bits) * row_bytes) || overlaps(d_out, out_bytes, d_r, n * exp_bytes))
+    const size_t row_bytes = (size_t)(d + 1) * EXP_BYTES;
+    if (!clear_of({d_out, (n << bits) * row_bytes}, {{d_pieces, (n_tab << bits) * row_bytes}, {d_r, n * EXP_BYTES}}))
         return fail(COFHE_HIP_EINVAL, "spline_rows: the output overlaps an input");
     const uint64_t blocks = ((n << bits) + SPL_THREADS - 1) / SPL_THREADS;
     if (blocks > 0x7FFFFFFFull) return fail(COFHE_HIP_EINVAL, "work size out of range");
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    {
-        ProfScope ps(ctx, "k_spline_rows", st);
-        hipLaunchKernelGGL(k_spline_rows, dim3((unsigned)blocks), dim3(SPL_THREADS), 0, st, (const uint32_t *)d_pieces, n_tab, (const uint32_t *)d_r,
-                           (uint32_t *)d_out, n, bits, shift, d, kbits);
-    }
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
+    return launch(ctx, "k_spline_rows", k_spline_rows, (unsigned)blocks, SPL_THREADS, st, (const uint32_t *)d_pieces, n_tab, (const uint32_t *)d_r,
+                  (uint32_t *)d_out, n, bits, shift, d, kbits);
 }
 
 // Needs no workspace plan of its own: the rows are one block of the block cache, and the fresh encryption that follows carves
@@ -2293,15 +2228,12 @@ int cofhe_hip_spline_tuples_records(cofhe_hip_ctx *ctx, const void *d_pieces, ui
     if (int rc = comb_check(1, n * per, 0, kbits, 0, 0)) return rc;
     if (n == 0) return COFHE_HIP_OK;
     if (!d_pieces || !d_r || !d_rho || !h_record || !pk_record || !f_record || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
-    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4, rows_bytes = n * per * exp_bytes, out_bytes = n * per * 2 * REC_WORDS * 4;
-    if (overlaps(d_out, out_bytes, d_pieces, n_tab * per * exp_bytes) || overlaps(d_out, out_bytes, d_r, n * exp_bytes) ||
-        overlaps(d_out, out_bytes, d_rho, rows_bytes))
+    if (!clear_of({d_out, n * per * CT_BYTES}, {{d_pieces, n_tab * per * EXP_BYTES}, {d_r, n * EXP_BYTES}, {d_rho, n * per * EXP_BYTES}}))
         return fail(COFHE_HIP_EINVAL, "spline_tuples: the output overlaps an input");
-    DevBuf rows;                                  // q_{j,c}: the plaintexts of the tuples
-    rows.stream = stream;
-    if (int rc = rows.get(ctx, rows_bytes)) return rc;
-    if (int rc = cofhe_hip_spline_rows_records(ctx, d_pieces, n_tab, d_r, rows.p, n, bits, shift, d, kbits, stream)) return rc;
-    return cofhe_hip_encrypt_fresh_records(ctx, rows.p, d_rho, h_record, pk_record, f_record, d_out, n * per, kbits, stream);
+    // q_{j,c}: the plaintexts of the tuples
+    return encrypt_rows(ctx, n * per, kbits, d_rho, h_record, pk_record, f_record, d_out, stream, [&](void *d_rows) {
+        return cofhe_hip_spline_rows_records(ctx, d_pieces, n_tab, d_r, d_rows, n, bits, shift, d, kbits, stream);
+    });
 }
 
 // touches no shared state of the context: no lock
@@ -2309,17 +2241,11 @@ int cofhe_hip_spline_powers_records(cofhe_hip_ctx *ctx, const void *d_e, void *d
     if (int rc = spline_check(1, 0, d, kbits, 1, n)) return rc;
     if (n == 0) return COFHE_HIP_OK;
     if (!d_e || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
-    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4;
-    if (overlaps(d_out, (size_t)d * n * exp_bytes, d_e, n * exp_bytes)) return fail(COFHE_HIP_EINVAL, "spline_powers: the output overlaps the input");
+    if (!clear_of({d_out, (size_t)d * n * EXP_BYTES}, {{d_e, n * EXP_BYTES}})) return fail(COFHE_HIP_EINVAL, "spline_powers: the output overlaps the input");
     const uint64_t blocks = (n + SPL_THREADS - 1) / SPL_THREADS;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    {
-        ProfScope ps(ctx, "k_spline_powers", st);
-        hipLaunchKernelGGL(k_spline_powers, dim3((unsigned)blocks), dim3(SPL_THREADS), 0, st, (const uint32_t *)d_e, (uint32_t *)d_out, n, d, kbits);
-    }
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
+    return launch(ctx, "k_spline_powers", k_spline_powers, (unsigned)blocks, SPL_THREADS, st, (const uint32_t *)d_e, (uint32_t *)d_out, n, d, kbits);
 }
 
 // the powers of the opened values are one block of the block cache; the status word is set by the kernel through Ctx
@@ -2329,36 +2255,28 @@ int cofhe_hip_spline_close_records(cofhe_hip_ctx *ctx, const void *d_e, const vo
     if (int rc = spline_check(bits, shift, d, kbits, 1, n)) return rc;
     if (n == 0) return COFHE_HIP_OK;
     if (!d_e || !d_tuples || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
-    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4, ct_bytes = (size_t)2 * REC_WORDS * 4, out_bytes = n * ct_bytes;
-    if (overlaps(d_out, out_bytes, d_e, n * exp_bytes) || overlaps(d_out, out_bytes, d_tuples, (((uint64_t)(d + 1) * n) << bits) * ct_bytes))
+    if (!clear_of({d_out, n * CT_BYTES}, {{d_e, n * EXP_BYTES}, {d_tuples, (((uint64_t)(d + 1) * n) << bits) * CT_BYTES}}))
         return fail(COFHE_HIP_EINVAL, "spline_close: the output overlaps an input");
     unsigned blocks;
     if (int rc = compose_blocks(2 * n, &blocks)) return rc;
-    DevBuf powers;                                // e, e^2, .., e^d mod 2^k, power-major
-    powers.stream = stream;
-    if (int rc = powers.get(ctx, (size_t)d * n * exp_bytes)) return rc;
-    if (int rc = cofhe_hip_spline_powers_records(ctx, d_e, powers.p, n, d, kbits, stream)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    {
-        ProfScope ps(ctx, "k_spline_close", st);
-        hipLaunchKernelGGL(k_spline_close, dim3(blocks), dim3(WG_BLOCK), 0, st, (const uint32_t *)d_e, (const uint32_t *)powers.p,
-                           (const uint32_t *)d_tuples, (uint32_t *)d_out, n, bits, shift, d, kbits, (const uint32_t *)ctx->d_absdelta,
-                           ctx->half_dbits, ctx->d_status);
-    }
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    DevBuf powers(stream);                        // e, e^2, .., e^d mod 2^k, power-major
+    if (int rc = powers.get(ctx, (size_t)d * n * EXP_BYTES)) return rc;
+    if (int rc = cofhe_hip_spline_powers_records(ctx, d_e, powers.p, n, d, kbits, stream)) return rc;      // makes the device current
+    return launch(ctx, "k_spline_close", k_spline_close, blocks, WG_BLOCK, (hipStream_t)stream, (const uint32_t *)d_e, (const uint32_t *)powers.p,
+                  (const uint32_t *)d_tuples, (uint32_t *)d_out, n, bits, shift, d, kbits, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits,
+                  ctx->d_status);
 }
 
 // host only: the tuples of opened values of shape S are a tensor of shape S + [2^bits, d + 1]
 int cofhe_hip_spline_tuples_shape(uint32_t ndim_e, const uint32_t *shape_e, uint32_t ndim_t, const uint32_t *shape_t, uint32_t *bits, uint32_t *d) {
     if (!bits || !d || (ndim_e && !shape_e) || (ndim_t && !shape_t)) return fail(COFHE_HIP_EINVAL, "null argument");
+    const uint32_t *tail;
     uint32_t b = 0, dd = 0;
-    if (ndim_t >= 2) {
-        while (b <= 12u && (1u << b) != shape_t[ndim_t - 2]) b++;
-        dd = shape_t[ndim_t - 1] - 1u;                           // 0 entries: wraps to a degree that is refused
+    if (tail_shape(ndim_e, shape_e, ndim_t, shape_t, 2, &tail)) {      // b stays 0 for a tensor of another shape
+        while (b <= 12u && (1u << b) != tail[0]) b++;
+        dd = tail[1] - 1u;                                       // 0 entries: wraps to a degree that is refused
     }
-    if (ndim_e > 6 || ndim_t != ndim_e + 2 || (ndim_e && memcmp(shape_t, shape_e, 4 * ndim_e) != 0) || b == 0 || b > 12u || dd == 0 ||
-        dd > (uint32_t)POLY_MAX_DEGREE || ((uint64_t)(dd + 1) << b) > SPLINE_MAX_TUPLE)
+    if (b == 0 || b > 12u || dd == 0 || dd > (uint32_t)POLY_MAX_DEGREE || ((uint64_t)(dd + 1) << b) > SPLINE_MAX_TUPLE)
         return fail(COFHE_HIP_ESHAPE, "spline_close: the tuples are a ciphertext tensor of e's shape and two last dimensions [2^bits, d + 1], "
                                       "bits >= 1, 1 <= d <= 8, 2^bits (d + 1) <= 4096");
     *bits = b;
@@ -2372,7 +2290,7 @@ static_assert(CMP_MAX_DIGITS + 1 == LUT_MAX_BITS, "the lookup that closes a comp
 namespace {
 // what every comparison entry point refuses before it looks at a pointer: the window, the digit width and the digit count
 int cmp_check(uint32_t bits, uint32_t digit_bits, uint32_t kbits, uint64_t n) {
-    if (kbits == 0 || kbits > 32u * PMM_MAX_LIMBS - 1u) return fail(COFHE_HIP_EINVAL, "k out of range");
+    if (!k_in_range(kbits)) return fail(COFHE_HIP_EINVAL, "k out of range");
     if (!cmp_shape_ok(bits, digit_bits, kbits, LUT_MAX_BITS))
         return fail(COFHE_HIP_EINVAL, "cmp: a window of 2 <= bits <= min(k, 64) bits in n = ceil(bits / d) digits of 1 <= d <= 8 bits, "
                                       "n + 1 <= min(12, k)");
@@ -2388,20 +2306,11 @@ int cofhe_hip_cmp_rows_records(cofhe_hip_ctx *ctx, const void *d_r, void *d_out,
     if (n == 0) return COFHE_HIP_OK;
     if (!d_r || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
     const uint64_t recs = (n * cmp_digits(bits, digit_bits)) << digit_bits;
-    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4;
-    if (overlaps(d_out, recs * exp_bytes, d_r, n * exp_bytes)) return fail(COFHE_HIP_EINVAL, "cmp_rows: the output overlaps the input");
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    const bool vec16 = ((uintptr_t)d_out & 15) == 0;
-    const uint64_t total = recs * (vec16 ? EXP_REC_WORDS / 4 : EXP_REC_WORDS);
-    const unsigned blocks = (unsigned)std::min<uint64_t>((total + CMP_ROWS_THREADS - 1) / CMP_ROWS_THREADS, 64u * NUM_CUS);       // grid-stride beyond that
-    {
-        ProfScope ps(ctx, "k_cmp_rows", st);
-        hipLaunchKernelGGL(k_cmp_rows, dim3(blocks), dim3(CMP_ROWS_THREADS), 0, st, (const uint32_t *)d_r, (uint32_t *)d_out, n, bits, digit_bits,
-                           vec16 ? 1u : 0u);
-    }
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    if (!clear_of({d_out, recs * EXP_BYTES}, {{d_r, n * EXP_BYTES}})) return fail(COFHE_HIP_EINVAL, "cmp_rows: the output overlaps the input");
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
+    const PieceGrid g = piece_grid(recs, EXP_REC_WORDS, CMP_ROWS_THREADS, {d_out});
+    return launch(ctx, "k_cmp_rows", k_cmp_rows, g.blocks, CMP_ROWS_THREADS, st, (const uint32_t *)d_r, (uint32_t *)d_out, n, bits, digit_bits, g.flag());
 }
 
 // Needs no workspace plan of its own: the rows are one block of the block cache, and the fresh encryption that follows carves
@@ -2415,14 +2324,11 @@ int cofhe_hip_cmp_tuples_records(cofhe_hip_ctx *ctx, const void *d_r, const void
     if (int rc = comb_check(1, recs, 0, kbits, 0, 0)) return rc;
     if (n == 0) return COFHE_HIP_OK;
     if (!d_r || !d_rho || !h_record || !pk_record || !f_record || !d_out) return fail(COFHE_HIP_EINVAL, "null argument");
-    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4, rows_bytes = recs * exp_bytes, out_bytes = recs * 2 * REC_WORDS * 4;
-    if (overlaps(d_out, out_bytes, d_r, n * exp_bytes) || overlaps(d_out, out_bytes, d_rho, rows_bytes))
+    if (!clear_of({d_out, recs * CT_BYTES}, {{d_r, n * EXP_BYTES}, {d_rho, recs * EXP_BYTES}}))
         return fail(COFHE_HIP_EINVAL, "cmp_tuples: the output overlaps an input");
-    DevBuf rows;                                  // T[j][c] = 2^j sgn(r_j - c), the plaintexts of the tuples
-    rows.stream = stream;
-    if (int rc = rows.get(ctx, rows_bytes)) return rc;
-    if (int rc = cofhe_hip_cmp_rows_records(ctx, d_r, rows.p, n, bits, digit_bits, kbits, stream)) return rc;
-    return cofhe_hip_encrypt_fresh_records(ctx, rows.p, d_rho, h_record, pk_record, f_record, d_out, recs, kbits, stream);
+    // T[j][c] = 2^j sgn(r_j - c), the plaintexts of the tuples
+    return encrypt_rows(ctx, recs, kbits, d_rho, h_record, pk_record, f_record, d_out, stream,
+                        [&](void *d_rows) { return cofhe_hip_cmp_rows_records(ctx, d_r, d_rows, n, bits, digit_bits, kbits, stream); });
 }
 
 // no workspace and no block; the lock is held because the kernel sets the context's status word through Ctx, as k_spline_close
@@ -2433,22 +2339,15 @@ int cofhe_hip_cmp_close_records(cofhe_hip_ctx *ctx, const void *d_e, const void 
     if (n == 0) return COFHE_HIP_OK;
     if (!d_e || !d_tuples || !d_out || !d_wrap) return fail(COFHE_HIP_EINVAL, "null argument");
     const uint64_t recs = (n * cmp_digits(bits, digit_bits)) << digit_bits;
-    const size_t exp_bytes = (size_t)EXP_REC_WORDS * 4, ct_bytes = (size_t)2 * REC_WORDS * 4, out_bytes = 2 * n * ct_bytes;
-    if (overlaps(d_out, out_bytes, d_e, n * exp_bytes) || overlaps(d_out, out_bytes, d_tuples, recs * ct_bytes) ||
-        overlaps(d_wrap, n * exp_bytes, d_e, n * exp_bytes) || overlaps(d_wrap, n * exp_bytes, d_tuples, recs * ct_bytes) ||
-        overlaps(d_wrap, n * exp_bytes, d_out, out_bytes))
+    const Span e{d_e, n * EXP_BYTES}, tuples{d_tuples, recs * CT_BYTES}, out{d_out, 2 * n * CT_BYTES}, wrap{d_wrap, n * EXP_BYTES};
+    if (!clear_of(out, {e, tuples}) || !clear_of(wrap, {e, tuples}) || !clear_of(wrap, {out}))
         return fail(COFHE_HIP_EINVAL, "cmp_close: an output overlaps an input or the other output");
     unsigned blocks;
     if (int rc = compose_blocks(2 * n, &blocks)) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    {
-        ProfScope ps(ctx, "k_cmp_close", st);
-        hipLaunchKernelGGL(k_cmp_close, dim3(blocks), dim3(WG_BLOCK), 0, st, (const uint32_t *)d_e, (const uint32_t *)d_tuples, (uint32_t *)d_out,
-                           (uint32_t *)d_wrap, n, bits, digit_bits, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
-    }
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    hipStream_t st;
+    if (int rc = on_device(ctx, stream, &st)) return rc;
+    return launch(ctx, "k_cmp_close", k_cmp_close, blocks, WG_BLOCK, st, (const uint32_t *)d_e, (const uint32_t *)d_tuples, (uint32_t *)d_out,
+                  (uint32_t *)d_wrap, n, bits, digit_bits, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
 }
 
 // host only: nd and nd 2^d, and the tuples of opened values of shape S as a tensor of shape S + [nd, 2^d]
@@ -2458,8 +2357,8 @@ int cofhe_hip_cmp_shape(uint32_t bits, uint32_t digit_bits, uint32_t kbits, uint
     const uint32_t nd = cmp_digits(bits, digit_bits);
     if (shape_t) {
         if (ndim_e && !shape_e) return fail(COFHE_HIP_EINVAL, "null argument");
-        if (ndim_e > 6 || ndim_t != ndim_e + 2 || (ndim_e && memcmp(shape_t, shape_e, 4 * ndim_e) != 0) || shape_t[ndim_t - 2] != nd ||
-            shape_t[ndim_t - 1] != (1u << digit_bits))
+        const uint32_t *tail;
+        if (!tail_shape(ndim_e, shape_e, ndim_t, shape_t, 2, &tail) || tail[0] != nd || tail[1] != (1u << digit_bits))
             return fail(COFHE_HIP_ESHAPE, "cmp_close: the tuples are a ciphertext tensor of e's shape and two last dimensions "
                                           "[ceil(bits / d), 2^d]");
     }
@@ -2471,8 +2370,7 @@ int cofhe_hip_cmp_shape(uint32_t bits, uint32_t digit_bits, uint32_t kbits, uint
 namespace {
 // the table f^(-2^j), j < k, of the decryption kernels (built on first use, cached in the context)
 int ensure_ftab(cofhe_hip_ctx *ctx, const uint32_t *f_record, uint32_t kbits, void *stream) {
-    if (kbits == 0 || 2 * kbits + 1 > (uint32_t)PLIMBS * 32 || kbits > EXP_MAG_WORDS * 32 - 1)
-        return fail(COFHE_HIP_EINVAL, "k out of range");
+    if (!k_in_range(kbits)) return fail(COFHE_HIP_EINVAL, "k out of range");
     HIPCHK(hipSetDevice(ctx->device));
     if (ctx->ftab_k != kbits || memcmp(ctx->ftab_f, f_record, REC_WORDS * 4) != 0) {
         // ftab[2j], ftab[2j+1] = f^(-2^j): k "ciphertexts" (f, f) raised to -2^j by k_pow
@@ -2505,11 +2403,9 @@ int decrypt_launch(cofhe_hip_ctx *ctx, const void *d_cts, const void *d_parts, u
                    uint32_t kbits, void *stream) {
     unsigned blocks;
     if (int rc = compose_blocks(n_ct, &blocks)) return rc;
-    launch_wg(ctx, k_decrypt3, k_decrypt, "k_decrypt3", "k_decrypt", blocks, (hipStream_t)stream, (const uint32_t *)d_cts,
-              (const uint32_t *)d_parts, n_parts, negmask, (const uint32_t *)ctx->d_ftab, (uint32_t *)d_out, n_ct, (int)kbits,
-              (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
-    HIPCHK(hipGetLastError());
-    return COFHE_HIP_OK;
+    return launch_wg(ctx, k_decrypt3, k_decrypt, "k_decrypt3", "k_decrypt", blocks, (hipStream_t)stream, (const uint32_t *)d_cts,
+                     (const uint32_t *)d_parts, n_parts, negmask, (const uint32_t *)ctx->d_ftab, (uint32_t *)d_out, n_ct, (int)kbits,
+                     (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
 }
 }  // namespace
 
@@ -2551,8 +2447,9 @@ int cofhe_hip_encrypt_records(cofhe_hip_ctx *ctx, const void *d_plain, const voi
         uint32_t *buf[2] = {(uint32_t *)(ws + ep.off("level_a")), (uint32_t *)(ws + ep.off("level_b"))};
         const uint64_t tabs[3] = {(uint64_t)(uintptr_t)ctx->d_ftab, (uint64_t)(uintptr_t)d_c1_pkr, 0};
         HIPCHK(hipMemcpyAsync(d_tabs, tabs, sizeof(tabs), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_encrypt_select, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st,
-                           (const uint32_t *)d_plain + e0 * EXP_REC_WORDS, ne, (int)kbits, cap, d_idx, d_max);
+        if (int rc = launch(ctx, nullptr, k_encrypt_select, (unsigned)((ne + 255) / 256), 256, st, (const uint32_t *)d_plain + e0 * EXP_REC_WORDS, ne,
+                            (int)kbits, cap, d_idx, d_max))
+            return rc;
         uint32_t mmax = 0;
         HIPCHK(hipMemcpyAsync(&mmax, d_max, 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));                        // also: `tabs` has been read
@@ -2560,14 +2457,14 @@ int cofhe_hip_encrypt_records(cofhe_hip_ctx *ctx, const void *d_plain, const voi
         const uint64_t total = (uint64_t)mmax * ne;
         unsigned gblocks;
         if (int rc = compose_blocks(total, &gblocks)) return rc;
-        hipLaunchKernelGGL(k_gather_signed, dim3(gblocks), dim3(WG_BLOCK), 0, st, (const uint64_t *)d_tabs, (const uint32_t *)d_idx, total,
-                           (const uint32_t *)ctx->d_one, buf[0]);
+        if (int rc = launch(ctx, nullptr, k_gather_signed, gblocks, WG_BLOCK, st, (const uint64_t *)d_tabs, (const uint32_t *)d_idx, total,
+                            (const uint32_t *)ctx->d_one, buf[0]))
+            return rc;
         const uint32_t *c2;
         if (int rc = product_tree(ctx, buf[0], buf[1], buf[0], nullptr, 1u, mmax, (uint32_t)ne, nullptr, st, &c2)) return rc;
         const unsigned zblocks = (unsigned)std::min<uint64_t>((ne * 2 * REC_WORDS + 255) / 256, 4096);
-        hipLaunchKernelGGL(k_zip_ciphertexts, dim3(zblocks), dim3(256), 0, st, (const uint32_t *)d_c1_pkr, c2, ne,
-                           (uint32_t *)d_out + e0 * 2 * REC_WORDS);
-        HIPCHK(hipGetLastError());
+        if (int rc = launch(ctx, nullptr, k_zip_ciphertexts, zblocks, 256, st, (const uint32_t *)d_c1_pkr, c2, ne, (uint32_t *)d_out + e0 * 2 * REC_WORDS))
+            return rc;
     }
     return COFHE_HIP_OK;
 }
@@ -2598,15 +2495,15 @@ int cofhe_hip_time_compose(cofhe_hip_ctx *ctx, const void *d_a, const void *d_b,
     HIPCHK(hipEventCreate(&e1));
     HIPCHK(hipEventRecord(e0, (hipStream_t)stream));
     for (int i = 0; i < iters; i++)      // what cofhe_hip_compose_records launches, without its span
-        launch_wg(ctx, k_compose_wg3, k_compose_wg, nullptr, nullptr, blocks, (hipStream_t)stream, (const uint32_t *)d_a,
-                  (const uint32_t *)d_b, (uint32_t *)d_out, n, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status);
+        if (int rc = launch_wg(ctx, k_compose_wg3, k_compose_wg, nullptr, nullptr, blocks, (hipStream_t)stream, (const uint32_t *)d_a,
+                               (const uint32_t *)d_b, (uint32_t *)d_out, n, (const uint32_t *)ctx->d_absdelta, ctx->half_dbits, ctx->d_status))
+            return rc;
     HIPCHK(hipEventRecord(e1, (hipStream_t)stream));
     HIPCHK(hipEventSynchronize(e1));
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, e0, e1));
     hipEventDestroy(e0);
     hipEventDestroy(e1);
-    HIPCHK(hipGetLastError());
     *ms_per_launch = ms / iters;
     return COFHE_HIP_OK;
 }
@@ -3088,7 +2985,7 @@ int cofhe_hip_poly_close_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *coef, 
 int cofhe_hip_div_close_tensors_bytes(cofhe_hip_ctx *ctx, const uint8_t *e, size_t le, const uint8_t *div, size_t ldiv, const uint8_t *rq,
                                       size_t lrq, const uint32_t *f_record, uint32_t kbits, uint8_t **out, size_t *outlen) {
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (kbits == 0 || kbits > PDV_MAX_KBITS) return fail(COFHE_HIP_EINVAL, "k out of range");
+    if (!k_in_range(kbits)) return fail(COFHE_HIP_EINVAL, "k out of range");
     // the divisors are public host values: read and judged here, as the kernel judges them
     uint32_t ndd, sd[8], *hdiv = nullptr;
     uint64_t nd;
