@@ -342,7 +342,58 @@ int cofhe_hip_stream_sync(cofhe_hip_ctx *ctx, void *stream) {
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     return COFHE_HIP_OK;
 }
-
+// A stream of the library's own HIP runtime on the context's device: what a client that shares one context among worker
+// threads gives each of them (a handle of another runtime in the process, PyTorch's for one, means nothing here).
+int cofhe_hip_stream_create(cofhe_hip_ctx *ctx, int nonblocking, void **stream) {
+    if (!ctx || !stream) return fail(COFHE_HIP_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = nullptr;
+    HIPCHK(hipStreamCreateWithFlags(&s, nonblocking ? hipStreamNonBlocking : hipStreamDefault));
+    *stream = (void *)s;
+    return COFHE_HIP_OK;
+}
+int cofhe_hip_stream_destroy(cofhe_hip_ctx *ctx, void *stream) {
+    if (!ctx) return fail(COFHE_HIP_EINVAL, "null argument");
+    if (!stream) return COFHE_HIP_OK;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    // An event keeps a pointer to the stream it was last recorded on, and the runtime looks at that stream (is it being
+    // captured?) before it waits for the event: after hipStreamDestroy that is a read of freed memory, which came back as
+    // hipErrorCapturedEvent / hipErrorStreamCaptureUnsupported from the hipEventSynchronize of cofhe_hip_malloc.  So nothing the
+    // context keeps may still name this stream.  Its work has finished, so every event recorded on it has completed:
+    // the workspace's last user, if it was this stream, leaves nothing to wait for (and a later stream that gets the same
+    // handle value is not taken for it) ...
+    if (ctx->ws_stream == (hipStream_t)stream) {
+        ctx->ws_stream = nullptr;
+        ctx->ws_event_set = false;
+    }
+    // ... and a cached block whose event has completed gets a fresh, unrecorded event, which any wait passes at once.  (An
+    // event that has not completed was recorded on another stream, which is alive, and stays.)
+    for (auto &kv : ctx->pool) {
+        const hipError_t q = hipEventQuery(kv.second.ev);
+        if (q == hipErrorNotReady) {
+            (void)hipGetLastError();
+            continue;
+        }
+        HIPCHK(q);
+        hipEvent_t fresh = nullptr;
+        HIPCHK(hipEventCreateWithFlags(&fresh, hipEventDisableTiming));
+        (void)hipEventDestroy(kv.second.ev);
+        kv.second.ev = fresh;
+    }
+    HIPCHK(hipStreamDestroy((hipStream_t)stream));
+    return COFHE_HIP_OK;
+}
+int cofhe_hip_stream_query(cofhe_hip_ctx *ctx, void *stream, int *busy) {
+    if (!ctx || !busy) return fail(COFHE_HIP_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    const hipError_t e = hipStreamQuery((hipStream_t)stream);
+    if (e != hipSuccess && e != hipErrorNotReady) return fail(COFHE_HIP_EHIP, std::string("hipStreamQuery: ") + hipGetErrorString(e));
+    if (e == hipErrorNotReady) (void)hipGetLastError();        // "not ready" is an answer: the thread's next checked launch must not see it
+    *busy = e == hipErrorNotReady;
+    return COFHE_HIP_OK;
+}
 
 int cofhe_hip_device_status(cofhe_hip_ctx *ctx, uint32_t *word, int clear, void *stream) {
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);

@@ -29,6 +29,9 @@ SIGNATURES = {
     "cofhe_hip_upload": "i:pppzp",
     "cofhe_hip_download": "i:pppzp",
     "cofhe_hip_stream_sync": "i:pp",
+    "cofhe_hip_stream_create": "i:pip",
+    "cofhe_hip_stream_destroy": "i:pp",
+    "cofhe_hip_stream_query": "i:ppp",
     "cofhe_hip_device_status": "i:ppip",
     "cofhe_hip_validate_records": "i:ppqpp",
     "cofhe_hip_compose_records": "i:ppppqp",
@@ -815,6 +818,23 @@ class Engine:
 
     def stream_sync(self, stream=0):
         self._call(self.L.cofhe_hip_stream_sync, stream)
+
+    def stream_create(self, nonblocking=1) -> int:
+        """a stream of the library's own HIP runtime on the context's device (a torch.cuda.Stream handle belongs to torch's
+        runtime and means nothing to the library); nonblocking: the null stream does not order it"""
+        s = C.c_void_p()
+        self._call(self.L.cofhe_hip_stream_create, 1 if nonblocking else 0, C.byref(s))
+        return s.value
+
+    def stream_destroy(self, stream):
+        """waits for the work queued on the stream, then releases it; 0 / None is a no-op"""
+        self._call(self.L.cofhe_hip_stream_destroy, stream)
+
+    def stream_query(self, stream=0) -> int:
+        """1 while work queued on the stream is pending, 0 when it is idle; does not wait"""
+        busy = C.c_int()
+        self._call(self.L.cofhe_hip_stream_query, stream, C.byref(busy))
+        return int(busy.value)
 
     def profile_read(self, kernel: str, clear=False):
         """(summed ms, launches) of the spans the "profile_kernels" option recorded for `kernel`"""

@@ -54,8 +54,11 @@
  * Concurrency: a context may be shared by host threads: the entry points that use its grow-only workspace, its
  * cached tables or its status area (matrix product, encrypt, decrypt, part_decrypt, combine, accumulate, validate,
  * device_status, the *_bytes operations) take the context's lock for the duration of the call; their kernels run
- * in stream order, so callers that pass DIFFERENT streams for those operations must order them themselves (the
- * NULL stream, which HIPCryptoSystem uses, needs nothing).  compose / pow / the converters are stateless.
+ * in stream order.  Calls on DIFFERENT streams of one context (cofhe_hip_stream_create) are safe, not concurrent: the last
+ * user of the workspace records an event and the next one's stream waits for it, tables are built before their readers
+ * run, and a block of the block cache is handed out again only after the work queued behind its free.  What a caller
+ * orders itself is its own data: a buffer written on one stream and read on another.  compose / pow / the converters are
+ * stateless.
  *
  * All functions return 0 on success, a negative COFHE_HIP_E* code otherwise;
  * cofhe_hip_last_error() gives the message for the calling thread.  The library never falls
@@ -135,6 +138,19 @@ int cofhe_hip_profile_read(cofhe_hip_ctx *ctx, const char *kernel, float *total_
 int cofhe_hip_upload(cofhe_hip_ctx *ctx, void *dst_dev, const void *src_host, size_t bytes, void *stream);
 int cofhe_hip_download(cofhe_hip_ctx *ctx, void *dst_host, const void *src_dev, size_t bytes, void *stream);
 int cofhe_hip_stream_sync(cofhe_hip_ctx *ctx, void *stream);
+/* Streams of the library's own HIP runtime, on the context's device: what a client that serves several worker threads from one
+ * context gives each of them.  (A process that also holds PyTorch holds two HIP runtimes; a torch.cuda.Stream handle belongs to
+ * the other one and means nothing here.)  nonblocking != 0: hipStreamNonBlocking -- the null stream neither waits for such a
+ * stream nor is waited for by it; 0: a blocking stream.  cofhe_hip_stream_destroy waits for the work queued on the stream, then
+ * releases it; the context forgets it as the last user of its workspace, so that a later stream with the same handle value
+ * is not taken for it, and lets go of every event it recorded on it (the blocks of the block cache that were freed behind
+ * it: a HIP event names the stream it was last recorded on, and waiting for one whose stream is gone fails).  So a stream that
+ * was handed to this library is ended HERE, not with hipStreamDestroy, and "profile_kernels" spans recorded on it are read
+ * (cofhe_hip_profile_read) before it goes.  A null stream is a no-op.  cofhe_hip_stream_query: *busy = 1 while work queued on
+ * the stream is pending (hipStreamQuery), 0 when it is idle; it does not wait.  COFHE_HIP_EINVAL for a null ctx or out-pointer. */
+int cofhe_hip_stream_create(cofhe_hip_ctx *ctx, int nonblocking, void **stream);
+int cofhe_hip_stream_destroy(cofhe_hip_ctx *ctx, void *stream);
+int cofhe_hip_stream_query(cofhe_hip_ctx *ctx, void *stream, int *busy);
 
 /* Device status word: every data-dependent loop of the kernels has a trip-count cap; a cap that is hit (possible only
  * for records that are not reduced forms of the context's discriminant) sets a bit instead of hanging or passing
@@ -164,7 +180,10 @@ int cofhe_hip_compose_wide_records(cofhe_hip_ctx *ctx, const void *d_a, const vo
  * 2 n_ct records).  When every ciphertext of a shares one c1 and every ciphertext of b shares one c1 -- tensors that
  * encrypt_tensor made with its one r per tensor (cpu_cryptosystem_tensor_ops.inl:7-12), and sums of such tensors --
  * the composition c1 o c1' is computed once and copied: n_ct + 1 compositions instead of 2 n_ct.  Detected on the
- * device per call (one pass over the c1 records); tensors with differing c1 take the plain path.  d_out may be d_a. */
+ * device per call (one pass over the c1 records); tensors with differing c1 take the plain path.  d_out may be d_a.
+ * The verdict of that pass lives in one of the context's 256 flag words, handed out round robin: purely stream-ordered, no
+ * read-back, and safe on any number of streams as long as at most 256 flag-using calls of one context are in flight (queued
+ * and not yet run) at a time; the 257th would reuse the word of the first. */
 int cofhe_hip_add_ciphertext_records(cofhe_hip_ctx *ctx, const void *d_a, const void *d_b, void *d_out, uint64_t n_ct, void *stream);
 /* out[i] = a[i] - b[i]: (a.c1 o b.c1^-1, a.c2 o b.c2^-1), one composition per record -- the inverse of a reduced form is a
  * sign flip -- where negate (b^(2^k - 1), k squarings and a product per record) followed by an addition spends k + 2.  Folding
